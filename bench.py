@@ -2,7 +2,7 @@
 """bench.py -- throughput of the x266 DCT32 / SATD hot path on MI355X.
 
 Contract (one JSON line on stdout from rank 0):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   (plain `python bench.py --gpus N` without WORLD_SIZE in the environment spawns exactly that itself)
@@ -10,9 +10,18 @@ Contract (one JSON line on stdout from rank 0):
 Workload = BASELINE.json configs[1]: 1,048,576 synthetic 9-bit residual blocks of 32x32 int16 per GPU, resident in HBM
 before the timed region (values a-b, a,b uniform bytes -- the reference's stimulus distribution, src_tb/dct32.c:191-193 --
 from SplitMix64 seed 0x266).  A "step" is one forward 2-D DCT32 pass over the batch (xDct32FwdBatchDev through the C ABI).
-`value` is whole-job forward blocks/s over all ranks; every other leg (inverse, fused forward+inverse, the 8x8 SATD residual
-batch of 2^24 blocks, motion search, the transform set, the 8K frame stream of configs[4], ...) is one function below,
-measured the same way, and lands under "also".
+`value` is whole-job forward blocks/s over all ranks.
+
+A plain run does only what that figure needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.
+Everything else is behind --full: the same-box memory streams, the live counter passes behind roofline.traffic, the output
+checksum over ranks, the CPU baseline, and every other leg (inverse, fused forward+inverse, the 8x8 SATD residual batch of
+2^24 blocks, motion search, the transform set, the 8K frame stream of configs[4], ...), each one function below, measured
+the same way, under "also".
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed as DIR/dct32_fwd_coefficients.npy,
+float32 [S, 1024] -- the coefficients of S = min(8192, blocks per GPU) blocks of its shard, chosen by a fixed seed and kept in
+block order (32 MiB at most).  The inputs come from a fixed seed too, so two builds run with the same arguments can be
+compared output for output.
 
 The process runs on the runtime the library ships on: device memory, streams and events come from the C ABI (xHipMalloc,
 xHipMemcpy*, xHipEvent*) and, for the two raw link copies of the host-API leg, from the HIP runtime libx266hip.so itself
@@ -79,6 +88,11 @@ def parse_args():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic (replay profiles/traffic.json instead)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)   # the profiled child of the live traffic passes
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (same-box streams, live traffic passes, checksum, CPU baseline, 'also'); "
+                         "the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a fixed, seeded sample of the last timed step's output to DIR/dct32_fwd_coefficients.npy (float32)")
     return ap.parse_args()
 
 
@@ -360,8 +374,8 @@ class Bench:
         return self.world * units_per_step * leg["steps"] / leg["wall_s"]
 
     def of_box(self, achieved_bytes_per_s, kind):
-        """fraction of this box's own stream of that kind"""
-        return achieved_bytes_per_s / self.ceil[kind]
+        """fraction of this box's own stream of that kind (None in a plain run: the same-box streams are measured under --full)"""
+        return achieved_bytes_per_s / self.ceil[kind] if kind in self.ceil else None
 
     def hbm(self, leg, bytes_per_step, box_kind="copy"):
         """{hbm_frac, frac_of_same_box_<kind>} of a leg, from the trimmed mean of its launches"""
@@ -562,16 +576,33 @@ def spawn_ranks(args):
     raise SystemExit(subprocess.call(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1")))
 
 
+DUMP_BLOCKS, DUMP_SEED = 8192, 0x266D
+
+
+def dump_outputs(b, z, out_dir):
+    """the headline's output of its last step, as a caller would receive it (int16 coefficients, here as float32): a fixed, seeded
+    sample of blocks in block order, copied block by block from the device (the whole batch is 2 GiB)"""
+    n = min(DUMP_BLOCKS, b.n_dct)
+    blocks = np.sort(np.random.default_rng(DUMP_SEED).choice(b.n_dct, n, replace=False))
+    out = np.empty((n, 1024), np.int16)
+    for i, blk in enumerate(blocks):
+        b.codec._check(b.codec.L.xHipMemcpyD2H(b.codec.ctx, out[i].ctypes.data, z.ptr + int(blk) * 2048, 2048), "xHipMemcpyD2H")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "dct32_fwd_coefficients.npy"), out.astype(np.float32))
+
+
 def headline(b, x, z, same_box):
     head = b.timed_leg(lambda: b.codec.dct32_fwd_dev(x.ptr, z.ptr, b.n_dct, b.stream))
-    pmc, pmc_src = traffic_of_headline(b)
+    if b.args.dump_outputs and b.rank == 0:
+        dump_outputs(b, z, b.args.dump_outputs)
+    pmc, pmc_src = traffic_of_headline(b) if b.args.full else ({}, None)
     result = {
         "metric": "dct32_fwd_blocks_per_s", "value": b.rate(head, b.n_dct), "unit": "blocks/s", "n_gpus": b.world,
         "steps": b.K, "warmup": b.W, "ms_per_step": head["ms_per_step"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "i32", "data": "synthetic",
         "config": {"workload": "BASELINE configs[1]: batched 32x32 forward DCT, %d random 9-bit residual blocks per GPU "
-                               "resident in HBM (inverse, fused fwd+inv, 8x8 SATD and the other configs under 'also')" % b.n_dct,
+                               "resident in HBM (with --full: inverse, fused fwd+inv, 8x8 SATD and the other configs under 'also')" % b.n_dct,
                    "blocks_per_gpu": b.n_dct, "block_bytes_in_plus_out": DCT_BYTES_PER_BLOCK,
                    "arithmetic": "int16 data as two int8 planes x int8 coefficients on v_mfma_i32_32x32x32_i8, int32 accumulate",
                    "sharding": "contiguous shard per rank, no data-path collective",
@@ -606,13 +637,15 @@ def main():
     x, z = b.dev(b.n_dct * 2048), b.dev(b.n_dct * 2048)
     codec.fill_residual_dev(x.ptr, b.n_dct * 1024, DCT_SEED, rank * b.n_dct * 1024, b.stream)
     b.hip.device_sync()
-    same_box = leg_same_box(b, x, z)
+    same_box = leg_same_box(b, x, z) if args.full else None
     result, pmc, pmc_src = headline(b, x, z, same_box)
-    # ---- checksum of the forward output across ranks (validates the sharded run) ----------------
-    z_host = z.download(np.int16, b.n_dct * 1024)
-    result["output_checksum_sum_i16"] = b.sum_over_ranks_i64(int(z_host.astype(np.int64).sum()))
+    result["output_checksum_sum_i16"] = None
+    if args.full:
+        # ---- checksum of the forward output across ranks (validates the sharded run) ----------------
+        z_host = z.download(np.int16, b.n_dct * 1024)
+        result["output_checksum_sum_i16"] = b.sum_over_ranks_i64(int(z_host.astype(np.int64).sum()))
 
-    if not args.no_also:
+    if args.full and not args.no_also:
         also, me = {}, {}
 
         def leg(name, fn, merge=False):
@@ -652,7 +685,7 @@ def main():
         also["rccl_libraries_in_process"] = loaded_libraries("librccl")
 
     # ---- CPU baseline for the headline leg (rank 0, N = 1 only) ------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             x_host = x.download(np.int16, b.n_dct * 1024).reshape(b.n_dct, 1024)
             base, exact = cpu_baseline_dct(x_host, z_host.reshape(b.n_dct, 1024))

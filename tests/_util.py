@@ -5,6 +5,8 @@ Only tests/, bench.py's cpu_baseline leg and __graft_entry__.smoke() may touch
 anything under oracle/ -- it is the checker, never the product.
 """
 import ctypes
+import hashlib
+import json
 import os
 import subprocess
 
@@ -199,6 +201,18 @@ class Oracle:
 
 def ref_path():
     return os.path.join(ORACLE_DIR, "_ref", "libx266ref.so")
+
+
+def digest(a):
+    """what tests/golden/ref_digests.json records of an output array: SHA-256 of its bytes (C order), shape, dtype"""
+    a = np.ascontiguousarray(a)
+    return {"sha256": hashlib.sha256(a.tobytes()).hexdigest(), "shape": list(a.shape), "dtype": a.dtype.str}
+
+
+def ref_digest(name):
+    """the real reference's answer recorded by tests/golden/gen_ref_digests.py (inputs: the seeded ones of the test that asks)"""
+    with open(os.path.join(GOLDEN_DIR, "ref_digests.json")) as f:
+        return json.load(f)[name]
 
 
 class Reference:

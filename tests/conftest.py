@@ -35,16 +35,6 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def reference():
-    """The real reference golden models (oracle/_ref); absent outside the build
-    container unless the prebuilt .so travelled with the snapshot."""
-    from _util import Reference, ref_path
-    if not os.path.exists(ref_path()):
-        pytest.skip("oracle/_ref/libx266ref.so not built (needs /root/reference)")
-    return Reference()
-
-
-@pytest.fixture(scope="session")
 def codec():
     """GPU context through the C ABI.  No fallback: a missing library or device
     is a hard failure for -m gpu tests."""

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from _util import ROOT
@@ -36,7 +37,7 @@ def _run(args, tmp):
 
 
 def test_bench_small_run_has_every_leg_and_field(tmp_path):
-    line, d = _run(["--steps", "3", "--warmup", "1", "--dct-blocks", "8192", "--satd-blocks", "131072"], str(tmp_path))
+    line, d = _run(["--full", "--steps", "3", "--warmup", "1", "--dct-blocks", "8192", "--satd-blocks", "131072"], str(tmp_path))
     for k in CONTRACT:
         assert k in d, k
     # the driver's line: numbers only, every leg as one scalar, every boolean check of the run green, the chip named
@@ -80,13 +81,32 @@ def test_bench_small_run_has_every_leg_and_field(tmp_path):
     assert "error" not in d
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """without --full: the headline's K timed steps and nothing else; --dump-outputs writes the seeded sample of the last step's
+    coefficients, which are the oracle's transform of the same seeded inputs"""
+    import bench
+    from _util import Oracle, residual_np
+    n, tmp = 20000, str(tmp_path)
+    line, d = _run(["--steps", "7", "--warmup", "2", "--dct-blocks", str(n), "--dump-outputs", os.path.join(tmp, "out")], tmp)
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "blocks/s"
+    assert d["metric"] == "dct32_fwd_blocks_per_s" and d["higher_is_better"] is True and d["dtype"] == "i32"
+    assert "also" not in d and d["cpu_baseline"] is None and d["roofline"]["same_box"] is None and d["roofline"]["traffic"] is None
+    assert line["roofline"]["kernel_ms_per_launch"] <= line["ms_per_step"] * 1.0001
+    assert os.listdir(os.path.join(tmp, "out")) == ["dct32_fwd_coefficients.npy"]
+    got = np.load(os.path.join(tmp, "out", "dct32_fwd_coefficients.npy"))
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_BLOCKS, 1024)
+    blocks = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, bench.DUMP_BLOCKS, replace=False))
+    x = residual_np(n * 1024, bench.DCT_SEED).reshape(n, 1024)[blocks]
+    assert np.array_equal(got, Oracle().dct32_fwd(x).astype(np.float32))
+
+
 def test_bench_two_ranks_share_the_gpu_and_agree_with_one_rank(tmp_path):
     """The N > 1 path of bench.py on a one-GPU box (X266_BENCH_SHARE_GPU: ranks share the device, control plane on gloo):
     every rank transforms its own slice of the one seeded stream, so two ranks x n blocks must give the output checksum
     of one rank x 2n blocks; the JSON reports n_gpus = 2 and the whole-job rate."""
     n = 16384
     tmp = str(tmp_path)
-    _, one = _run(["--steps", "3", "--warmup", "1", "--dct-blocks", str(2 * n), "--no-also", "--no-cpu-baseline", "--no-live-traffic"], tmp)
+    _, one = _run(["--full", "--steps", "3", "--warmup", "1", "--dct-blocks", str(2 * n), "--no-also", "--no-cpu-baseline", "--no-live-traffic"], tmp)
     import socket
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -94,7 +114,7 @@ def test_bench_two_ranks_share_the_gpu_and_agree_with_one_rank(tmp_path):
     s.close()
     env = dict(os.environ, X266_BENCH_SHARE_GPU="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1",
                           "--dct-blocks", str(n), "--no-also", "--no-cpu-baseline"], cwd=tmp, env=env, capture_output=True, text=True, timeout=900)
     line2, two = _line_and_full(out, tmp)                           # rank 0 only
     assert len(line2["roofline"]["frac_by_rank"]) == 2 and line2["cpu_baseline"] is None
@@ -105,7 +125,7 @@ def test_bench_two_ranks_share_the_gpu_and_agree_with_one_rank(tmp_path):
     # the same job WITHOUT torchrun on the command line: plain `python bench.py --gpus 2` spawns its own ranks (how a scaling harness
     # that re-uses the single-GPU command shape would call it)
     env2 = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1",
                           "--dct-blocks", str(n), "--no-also", "--no-cpu-baseline"], cwd=tmp, env=env2, capture_output=True, text=True, timeout=900)
     _, self_spawned = _line_and_full(out, tmp)
     assert self_spawned["n_gpus"] == 2 and self_spawned["output_checksum_sum_i16"] == one["output_checksum_sum_i16"]
@@ -123,7 +143,7 @@ def test_bench_node_legs_with_one_process_per_rank_under_the_rccl_model(ranks, t
     env = dict(os.environ, X266_BENCH_SHARE_GPU="1", X266HIP_RCCL_LIB=model, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     # no torchrun on the command line: bench.py --gpus N spawns its own ranks
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--full", "--steps", "3", "--warmup", "1",
                           "--dct-blocks", "16384", "--satd-blocks", "65536", "--stream8k", "6", "--no-transform-set", "--no-cpu-baseline"],
                          cwd=tmp, env=env, capture_output=True, text=True, timeout=1500)
     line, d = _line_and_full(out, tmp)
@@ -150,7 +170,7 @@ def test_bench_prints_its_line_when_a_peer_never_joins(tmp_path):
     env = dict(os.environ, X266_BENCH_SHARE_GPU="1", X266HIP_RCCL_LIB=model, HSA_ENABLE_IPC_MODE_LEGACY="0", X266_BENCH_TEST_STALL_RANK="1")
     env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dct-blocks", "16384",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--dct-blocks", "16384",
                           "--satd-blocks", "65536", "--stream8k", "6", "--no-transform-set", "--no-me", "--no-cpu-baseline", "--node-timeout", "10"],
                          cwd=tmp, env=env, capture_output=True, text=True, timeout=300)
     took = time.time() - t0

@@ -1,15 +1,14 @@
 """GPU: the HIP path against the REAL reference, directly and in volume (missing #3).
 
-oracle/_ref/libx266ref.so is src_tb/dct32.c + satd.c compiled where they lie (oracle/Makefile); it travels to the GPU box with the
-snapshot.  Every other -m gpu test compares with the oracle (this repo's restatement, itself pinned to the reference in the build
-container): valid, but one hop longer than needed.  Here the batch kernels' outputs are compared with the reference's own
-partialButterfly32 x 2 (src_tb/dct32.c:197-198) on 1.2e5 mixed blocks, with its satd8x8 (src_tb/satd.c:31-118) on 1.3e6 blocks, and
-the 1-D pass with partialButterfly32 itself at the two shifts dct32_genNew uses (src_tb/dct32.c:180-181).  Skipped (with the reason)
-where the prebuilt reference is absent."""
+Every other -m gpu test compares with the oracle (this repo's restatement, itself pinned to the reference): valid, but one hop
+longer than needed.  Here the batch kernels' outputs are compared with the answers of the reference's own partialButterfly32 x 2
+(src_tb/dct32.c:197-198) on 1.2e5 mixed blocks, of its satd8x8 (src_tb/satd.c:31-118) on 1.3e6 blocks, and of partialButterfly32
+itself for the 1-D pass at the two shifts dct32_genNew uses (src_tb/dct32.c:180-181).  Those answers were recorded where the
+reference lies (tests/golden/gen_ref_digests.py): tests/golden/ref_digests.json holds the SHA-256 of each output array."""
 import numpy as np
 import pytest
 
-from _util import dct_edge_blocks, extremes_np, fullrange_np, residual_np, satd_edge_blocks
+from _util import dct_edge_blocks, digest, extremes_np, fullrange_np, ref_digest, residual_np, satd_edge_blocks
 
 pytestmark = pytest.mark.gpu
 
@@ -21,35 +20,39 @@ def _mixed(n_tri, n_full, n_ext, unit, seed, edge):
     return x[np.random.RandomState(seed).permutation(x.shape[0])]          # the kinds interleaved, not in runs
 
 
-def test_dct32_forward_batch_equals_the_reference_on_120k_mixed_blocks(codec, reference):
+def _where(got, want):
+    """the message of a digest mismatch: which blocks leave the oracle (pinned to the same digests by tests/test_oracle_vs_ref.py)"""
+    bad = np.flatnonzero((got.reshape(got.shape[0], -1) != want.reshape(want.shape[0], -1)).any(axis=1))
+    return "differs from the reference's digest; %d block(s) differ from the oracle, the first: %s" % (bad.size, bad[:1].tolist())
+
+
+def test_dct32_forward_batch_equals_the_reference_on_120k_mixed_blocks(codec, oracle):
     x = _mixed(80000, 30000, 10000, 1024, 0x51, dct_edge_blocks()[0])
     assert x.shape[0] >= 100000
     got = codec.dct32_fwd(x)                                              # host-pointer call: staging pipeline + the batch kernel
-    want = reference.dct32_fwd(x)
-    assert np.array_equal(got, want), "first differing block %d" % int(np.argmax((got != want).any(axis=1)))
+    assert digest(got) == ref_digest("gpu_vs_reference.dct32_fwd"), _where(got, oracle.dct32_fwd(x, threads=8))
 
 
-def test_satd8x8_batch_equals_the_reference_on_1m3_mixed_blocks(codec, reference):
+def test_satd8x8_batch_equals_the_reference_on_1m3_mixed_blocks(codec, oracle):
     x = _mixed(900000, 300000, 100000, 64, 0x52, satd_edge_blocks()[0])
     assert x.shape[0] >= 1000000
-    want = reference.satd8x8(x)
+    want = ref_digest("gpu_vs_reference.satd8x8")
     for variant in (0, 1, 3):                                             # by batch size / staged kernel / LDS-DMA kernel
         codec.set_option("satd_variant", variant)
         got = codec.satd8x8(x)
-        assert np.array_equal(got, want), (variant, int(np.argmax(got != want)))
+        assert digest(got) == want, (variant, _where(got, oracle.satd8x8(x, threads=8)))
     codec.set_option("satd_variant", 0)
 
 
 @pytest.mark.parametrize("shift", [4, 11])
-def test_one_dimensional_pass_equals_partialButterfly32(codec, reference, shift):
+def test_one_dimensional_pass_equals_partialButterfly32(codec, oracle, shift):
     """xDct32PassDev = partialButterfly32(src, dst, shift, 32) with its transposed store, 1000 mixed blocks per shift"""
     x = _mixed(600, 300, 84, 1024, 0x53 + shift, dct_edge_blocks()[0])[:1000]
     got = codec.dct32_pass(x, shift)
-    for b in range(x.shape[0]):
-        assert np.array_equal(got[b], reference.dct32_pass(x[b], shift)), (shift, b)
+    assert digest(got) == ref_digest("gpu_vs_reference.dct32_pass_%d" % shift), _where(got, np.stack([oracle.dct32_pass(b, shift) for b in x]))
 
 
-def test_fused_forward_half_equals_the_reference(codec, reference):
+def test_fused_forward_half_equals_the_reference(codec, oracle):
     """the coefficients xDct32FwdInvBatchDev writes are the reference's (its inverse half has no upstream counterpart)"""
     x = _mixed(6000, 1500, 500, 1024, 0x54, dct_edge_blocks()[0])
     n = x.shape[0]
@@ -57,4 +60,5 @@ def test_fused_forward_half_equals_the_reference(codec, reference):
     d_in.upload(x)
     codec.dct32_fwd_inv_dev(d_in.ptr, d_coef.ptr, d_rec.ptr, n)
     codec.stream_sync()
-    assert np.array_equal(d_coef.download(np.int16, n * 1024).reshape(n, 1024), reference.dct32_fwd(x))
+    got = d_coef.download(np.int16, n * 1024).reshape(n, 1024)
+    assert digest(got) == ref_digest("gpu_vs_reference.fused_forward"), _where(got, oracle.dct32_fwd(x, threads=8))

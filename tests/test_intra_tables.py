@@ -1,17 +1,12 @@
 """CPU: the 32x32 intra predictor's oracle (oracle/intra_oracle.c, PARITY UNPINNED).
-(a) its closed forms against the tables of the reference's WIP RTL sketch, read from
-    /root/reference/src/mkIntra32-wip.bsv where that file is present (this container only);
+(a) its angle and inverse-angle tables;
 (b) against an independent numpy statement of H.265 8.4.4.2.4-6;
 (c) structural properties of the modes."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from _util import intra_refs_np
 
-BSV = "/root/reference/src/mkIntra32-wip.bsv"
 ANGLES = [32, 26, 21, 17, 13, 9, 5, 2, 0, -2, -5, -9, -13, -17, -21, -26, -32, -26, -21, -17, -13, -9, -5, -2, 0, 2, 5, 9, 13, 17, 21, 26, 32]
 INV = {11: -4096, 12: -1638, 13: -910, 14: -630, 15: -482, 16: -390, 17: -315, 18: -256, 19: -315, 20: -390, 21: -482,
        22: -630, 23: -910, 24: -1638, 25: -4096}
@@ -23,36 +18,6 @@ def test_angle_tables(oracle):
     assert {m: L.orc_intra_inv_angle(m) for m in range(11, 26)} == INV
     for m, a in zip(range(11, 26), ANGLES[9:24]):            # invAngle = round(8192 / angle)
         assert abs(INV[m] - round(8192 / a)) <= 1
-
-
-def _rows(text, name):
-    body = text[text.index(name):]
-    body = body[body.index("{") + 1:body.index("};")]
-    return [[int(v) for v in re.findall(r"-?\d+", row)] for row in re.findall(r"\{([^{}]*)\}", body)]
-
-
-@pytest.mark.skipif(not os.path.exists(BSV), reason="reference not present (GPU box)")
-def test_closed_forms_match_the_reference_tables():
-    text = open(BSV).read()
-    map_tbl, fac_tbl = _rows(text, "Integer mapTbl"), _rows(text, "Integer facTbl")
-    assert len(map_tbl) == 17 and len(fac_tbl) == 16 and all(len(r) == 32 for r in map_tbl + fac_tbl)
-    k = np.arange(32) + 1
-    typos = 0
-    for row, mode in enumerate(range(2, 18)):                # rows 0..15 <-> HEVC modes 2..17 (the file's own comments)
-        a = ANGLES[mode - 2]
-        idx, fact = (k * a) >> 5, (k * a) & 31
-        assert fac_tbl[row] == fact.tolist(), mode           # iFact, exactly
-        want = (idx if a >= 0 else idx - idx.min()).tolist()  # iIdx; negative angles re-based to the smallest shift
-        if map_tbl[row] != want:                             # the WIP file's "Mode 16" row has transposed entries
-            assert mode == 16 and sorted(map_tbl[row]) == sorted(want)
-            typos += int(np.sum(np.array(map_tbl[row]) != np.array(want)))
-    assert typos == 2                                        # entries 22 and 23 of that row are swapped (4, 5 for 5, 4)
-    assert map_tbl[16] == list(range(32, 0, -1))             # modes 18-25 row: pure diagonal walk
-    # projected side references of getRefPixels (e.g. case 17 = HEVC mode 19): ((x*invAngle + 128) >> 8)
-    case17 = text[text.index("        17: begin"):text.index("        18: begin")]
-    listed = [int(v) for v in re.findall(r"xL\[\s*(\d+)\]", case17)]
-    proj = [((x * INV[19] + 128) >> 8) for x in range(-1, ((32 * ANGLES[17]) >> 5) - 1, -1)]
-    assert sorted(listed) == sorted(proj)[:-1]               # same projection; the file lists 25 of the 26 samples (stops at xL[31])
 
 
 def _numpy_predict(left, top, mode):

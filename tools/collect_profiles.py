@@ -38,7 +38,7 @@ def sq_summary(tag, sq_dir, lds_dir):
     """SQ / LDS counters -> profiles/<tag>_pmc_sq_counters.csv plus derived per-SIMD utilisations."""
     out = ["# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_I8 SQ_INSTS_VALU SQ_WAVE_CYCLES "
            "SQ_ACTIVE_INST_VALU SQ_WAVES GRBM_GUI_ACTIVE   and a second pass   --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS "
-           "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY   -- python bench.py --no-cpu-baseline --steps 5 --warmup 2",
+           "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY   -- python bench.py --full --no-cpu-baseline --steps 5 --warmup 2",
            "# mean per dispatch, summed over the chip as rocprofv3 reports it", "kernel,counter,dispatches,mean"]
     tab = collections.defaultdict(dict)
     for d in (sq_dir, lds_dir):
@@ -73,7 +73,7 @@ def main():
         for r in rows:
             w.writerow([r["Name"][:160], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"], r["StdDev"]])
     out = {}
-    lines = ["# rocprofv3 --kernel-trace --pmc <counter> -- python bench.py --no-cpu-baseline --steps 5 --warmup 2",
+    lines = ["# rocprofv3 --kernel-trace --pmc <counter> -- python bench.py --full --no-cpu-baseline --steps 5 --warmup 2",
              "# one counter per pass (FETCH_SIZE and WRITE_SIZE do not fit one pass); units: KB per dispatch",
              "kernel,counter,dispatches,mean_KB,min_KB,max_KB"]
     for ctr, d in (("FETCH_SIZE", fdir), ("WRITE_SIZE", wdir)):

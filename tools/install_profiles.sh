@@ -1,17 +1,19 @@
 #!/bin/bash
-# After tools/run_profiles.sh <round> <suffix> has come back through gpurun: copy its outputs into profiles/ and regenerate profiles/MEASURED.md and DESIGN.md section 0.
-#   tools/install_profiles.sh <round-tag, e.g. r04> <suffix>
+# After tools/run_profiles.sh <round> <suffix> [<out-dir>] has run on the GPU box and its <out-dir> is back here: copy its outputs into
+# profiles/ and regenerate profiles/MEASURED.md and DESIGN.md section 0.
+#   tools/install_profiles.sh <round-tag, e.g. r04> <suffix> [<out-dir>, default profile_out]
 set -e
 T=${1:?round tag}; S=${2:?suffix}
 R=$(cd "$(dirname "$0")/.." && pwd)
 cd "$R"
-python tools/collect_profiles.py $T gpurun_out/prof_$S gpurun_out/pmc_fetch_$S gpurun_out/pmc_write_$S gpurun_out/bench_${T}_$S.json gpurun_out/pytest_gpu.log gpurun_out/pmc_sq_$S gpurun_out/pmc_lds_$S | tail -1
-cp gpurun_out/bench_${T}_$S.json profiles/${T}_bench.json
-cp gpurun_out/bench_${T}_${S}_driver_args.json profiles/${T}_bench_driver_args.json
-cp gpurun_out/stream8k_${T}_$S.json profiles/${T}_stream8k.json
-cp gpurun_out/bench_${T}_${S}_line.json profiles/${T}_bench_line.json                      # the compact line, as the driver sees it
-cp gpurun_out/bench_${T}_${S}_driver_args_line.json profiles/${T}_bench_driver_args_line.json
-cp gpurun_out/bench_${T}_${S}_profiled_run.json profiles/${T}_bench_profiled_run.json
+O=${3:-profile_out}
+python tools/collect_profiles.py $T $O/prof_$S $O/pmc_fetch_$S $O/pmc_write_$S $O/bench_${T}_$S.json $O/pytest_gpu.log $O/pmc_sq_$S $O/pmc_lds_$S | tail -1
+cp $O/bench_${T}_$S.json profiles/${T}_bench.json
+cp $O/bench_${T}_${S}_driver_args.json profiles/${T}_bench_driver_args.json
+cp $O/stream8k_${T}_$S.json profiles/${T}_stream8k.json
+cp $O/bench_${T}_${S}_line.json profiles/${T}_bench_line.json                      # the compact line, as the driver sees it
+cp $O/bench_${T}_${S}_driver_args_line.json profiles/${T}_bench_driver_args_line.json
+cp $O/bench_${T}_${S}_profiled_run.json profiles/${T}_bench_profiled_run.json
 python tools/design_table.py profiles/${T}_bench.json --write
 python - "$T" <<'PY'
 import csv, json, re, sys
