@@ -284,6 +284,35 @@ int xDct32FwdCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, co
  * d_out_v = d_out_u + 1 interleaves the two costs.  width, height multiples of 16. */
 int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                                int width, int height, uint32_t *d_out_u, uint32_t *d_out_v, size_t pitch, void *stream);
+/* Reconstruction into tiles, the way back from the stage above (no upstream counterpart, as for residual formation):
+ * recon = clamp(pred + residual, 0, 255) per sample, computed exactly for every int16 residual (pred 100 + 32767 gives 255),
+ * written into the tiled frame d_recon.  Luma calls write only m_Y and chroma calls only m_C of d_recon, so a luma call and
+ * a chroma call compose into one frame; no call writes m_I (as xConvInputFmtDev).  d_recon == d_pred is allowed (an encoder
+ * reconstructs over its prediction); any other overlap of d_recon with an input returns X266HIP_EINVAL.  Buffers 16-byte
+ * aligned.
+ * Luma: the mirror of xResidualLumaDev -- d_residual holds int16 row-major blocks in raster order of blocks, exactly the
+ * layout xResidualLumaDev emits; block_edge 32 (width, height multiples of 32) or 8 (multiples of 16).
+ * xResidualLumaDev(cur, pred) followed by xReconLumaDev(pred, ..) gives back cur's m_Y. */
+int xReconLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_residual, int width, int height,
+                  int block_edge, x266_ref_block_t *d_recon, void *stream);
+/* Chroma: the mirror of xResidualChromaDev -- the same U / V block streams, block_edge and block_pitch conventions (block b
+ * of U at d_res_u + b * block_pitch * edge^2; block_pitch 2 with d_res_v = d_res_u + edge^2 is the CTU-interleaved stream);
+ * writes the interleaved (U, V) pairs of m_C (src/x266.cpp:441-449, as xConvInputFmtDev packs them).  block_edge 8: width,
+ * height multiples of 16; 32: multiples of 64.  A block_pitch of 0, or one whose stream would not fit in the address space,
+ * returns X266HIP_EINVAL. */
+int xReconChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_res_u, const int16_t *d_res_v,
+                    size_t block_pitch, int width, int height, int block_edge, x266_ref_block_t *d_recon, void *stream);
+/* Fused inverse DCT32 + reconstruction: m_Y of d_recon = clamp(pred + IDCT32(coef), 0, 255) for every 32x32 luma block,
+ * coefficients in frame raster order of blocks (the order xDct32FwdFromTilesDev emits) -- bit-identical to
+ * xDct32InvBatchDev followed by xReconLumaDev(.., 32, ..), without the residual touching HBM (4 KiB moved per block
+ * instead of 8).  width, height multiples of 32. */
+int xDct32InvToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
+                        x266_ref_block_t *d_recon, void *stream);
+/* The inverse of xDct32FwdCtuFromTilesDev: input 12 KiB per 64x64 CTU (Y0 Y1 Y2 Y3 U V, CTUs in raster order); one launch
+ * writes m_Y and m_C of every CTU's 16 tiles -- bit-identical to xDct32InvBatchDev of the six blocks followed by
+ * xReconLumaDev(.., 32, ..) and xReconChromaDev(.., 32, ..).  width, height multiples of 64. */
+int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
+                           x266_ref_block_t *d_recon, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; buffers 16-byte
  * aligned): d_out[b] = sum |a - b|, exactly sad() of

@@ -82,6 +82,10 @@ def load_library(path=None):
     L.xDct32FwdChromaFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]
     L.xDct32FwdCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xSatd8x8ChromaFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]
+    L.xReconLumaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xReconChromaDev.argtypes = [_P, _P, _P, _P, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xDct32InvToTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xDct32InvCtuToTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xSadBatchDev.argtypes = [_P, ctypes.c_int, _P, _P, _P, _SZ, _P]
     L.xTransformInvBatchDev.argtypes = [_P, ctypes.c_int, ctypes.c_int, _P, _P, _SZ, _P, _P]
     L.xTransformTilesDev.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P, _P, _P]
@@ -412,6 +416,18 @@ class Codec:
     def satd8x8_chroma_from_tiles_dev(self, d_cur, d_pred, w, h, d_out_u, d_out_v, pitch=1, stream=0):
         self._check(self.L.xSatd8x8ChromaFromTilesDev(self.ctx, d_cur, d_pred, w, h, d_out_u, d_out_v, pitch, stream),
                     "xSatd8x8ChromaFromTilesDev")
+
+    def recon_luma_dev(self, d_pred, d_res, w, h, edge, d_recon, stream=0):
+        self._check(self.L.xReconLumaDev(self.ctx, d_pred, d_res, w, h, edge, d_recon, stream), "xReconLumaDev")
+
+    def recon_chroma_dev(self, d_pred, d_res_u, d_res_v, w, h, edge, d_recon, block_pitch=1, stream=0):
+        self._check(self.L.xReconChromaDev(self.ctx, d_pred, d_res_u, d_res_v, block_pitch, w, h, edge, d_recon, stream), "xReconChromaDev")
+
+    def dct32_inv_to_tiles_dev(self, d_coef, d_pred, w, h, d_recon, stream=0):
+        self._check(self.L.xDct32InvToTilesDev(self.ctx, d_coef, d_pred, w, h, d_recon, stream), "xDct32InvToTilesDev")
+
+    def dct32_inv_ctu_to_tiles_dev(self, d_coef, d_pred, w, h, d_recon, stream=0):
+        self._check(self.L.xDct32InvCtuToTilesDev(self.ctx, d_coef, d_pred, w, h, d_recon, stream), "xDct32InvCtuToTilesDev")
 
     def sad_dev(self, edge, d_a, d_b, d_out, n_blocks, stream=0):
         self._check(self.L.xSadBatchDev(self.ctx, edge, d_a, d_b, d_out, n_blocks, stream), "xSadBatchDev")

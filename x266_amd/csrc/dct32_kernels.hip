@@ -33,7 +33,8 @@
 //
 // Kernels in this file: dct32_lds_kernel (LDS-staged line-dense traffic, forward / inverse),
 // dct32_fwdinv_kernel (coefficients + reconstruction in one pass, LDS-DMA fed), dct32_from_tiles_kernel
-// (residual formation fused in), dct32_pass_kernel (the 1-D pass by itself, for checking).  The direct
+// (residual formation fused in), dct32_inv_to_tiles_kernel / dct32_inv_ctu_to_tiles_kernel (the inverse with the
+// reconstruction into tiles fused in), dct32_pass_kernel (the 1-D pass by itself, for checking).  The direct
 // fragment-load forms and the variants without cache-policy hints of rounds 1-3 are gone: every A/B they
 // served is frozen in profiles/r01_*.txt (line-dense traffic +9 %, "nt" loads / "sc1 nt" stores +3-5 %).
 #include <hip/hip_runtime.h>
@@ -483,6 +484,149 @@ __global__ __launch_bounds__(256) void dct32_ctu_from_tiles_kernel(const x266_re
     }
 }
 
+// ---- fused inverse transform + reconstruction into tiles -----------------------------------------------------------------
+// recon.m_Y = clip8(pred.m_Y + IDCT32(coef)) for every 32x32 luma block, coefficients in frame raster order of blocks (the
+// order dct32_from_tiles_kernel emits): 2 KiB of coefficients + 1 KiB of pred in, 1 KiB out per block instead of the 2 + 2 KiB
+// in and out of the inverse batch followed by 2 + 1 KiB in, 1 KiB out of the residual-to-tile pass.  The input side is
+// dct32_lds_kernel<true> (1 KiB-linear loads staged through the wave's 2 KiB slot, column reads, the next block's loads under
+// this block's arithmetic).  After inv_passes lane (c, h) holds output row c, columns 16h .. 16h+15 -- one 16-byte luma row
+// (c & 15) of tile (2 by + (c >> 4), 2 bx + h), the fragment dct32_from_tiles_kernel loads: one pred load, the saturating
+// add, one store per lane, no LDS on the way out.  pred and recon are not __restrict__ (recon == pred is allowed); each lane
+// reads exactly the pred bytes it writes.
+__global__ __launch_bounds__(256) void dct32_inv_to_tiles_kernel(const int16_t *__restrict__ coef, const x266_ref_block_t *pred,
+                                                                 x266_ref_block_t *recon, int blocks_x, int tiles_x, size_t n_blocks,
+                                                                 const DctOps *__restrict__ ops, unsigned blocks_per_wave)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    const int lane = threadIdx.x & 63;
+    unsigned char *slot = stage + (threadIdx.x >> 6) * 2048;
+    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    size_t b = wave * blocks_per_wave;
+    const size_t end = b + blocks_per_wave < n_blocks ? b + blocks_per_wave : n_blocks;
+    if (b >= end) return;
+
+    const unsigned c = lane & 31, h = lane >> 5;
+    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
+    unsigned col_base[4];
+    {
+        const unsigned u = (unsigned)kappa((int)c);
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) col_base[j] = 16u * h * 64u + ((((u >> 3) ^ j) & 3u) << 4) + (u & 7u) * 2u;
+    }
+    const char *src = reinterpret_cast<const char *>(coef) + lane * 16;
+    v4i g0 = load16<true>(src + b * 2048), g1 = load16<true>(src + b * 2048 + 1024);
+    const LaneConsts k = load_consts(ops, lane);
+    v16i c2r;
+    {
+        const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
+    }
+    while (true) {
+        const size_t nb = b + 1;
+        *reinterpret_cast<v4i *>(slot + lin0) = g0;
+        *reinterpret_cast<v4i *>(slot + lin1) = g1;
+        const size_t by = b / (size_t)blocks_x, bx = b - by * (size_t)blocks_x;
+        const size_t off = ((by * 2 + (c >> 4)) * (size_t)tiles_x + bx * 2 + h) * sizeof(x266_ref_block_t) + (c & 15) * 16;
+        const v4i p = load16<true>(reinterpret_cast<const unsigned char *>(pred) + off);   // four tiles' luma per instruction
+        if (nb < end) {
+            g0 = load16<true>(src + nb * 2048);
+            g1 = load16<true>(src + nb * 2048 + 1024);
+        }
+        __builtin_amdgcn_wave_barrier();
+        uint32_t w[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const uint32_t e0 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m) >> 2) & 3] + (2 * m) * 64);
+            const uint32_t e1 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m + 1) >> 2) & 3] + (2 * m + 1) * 64);
+            w[m] = e0 | (e1 << 16);
+        }
+        v4i lo, hi, o0, o1;
+        split_planes(v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]}, lo, hi);
+        inv_passes(lo, hi, k, c2r, o0, o1);
+        __builtin_amdgcn_wave_barrier();                                   // the slot is rewritten by the next block
+        store16_sc1nt(reinterpret_cast<unsigned char *>(recon) + off, recon_luma16(p, o0, o1));
+        if (nb >= end) break;
+        b = nb;
+    }
+}
+
+// ---- the whole-CTU inverse: 12 KiB of coefficients per CTU back into its 16 tiles ----------------------------------------------
+// Input = what dct32_ctu_from_tiles_kernel emits (Y0 Y1 Y2 Y3 U V per 64x64 CTU, CTUs in raster order).  Five waves per CTU:
+// four take one luma quadrant each (dct32_inv_to_tiles_kernel's body), the fifth inverts U and V through the same slot and
+// re-interleaves them into m_C -- lane (c, h) then holds row c, columns 16h .. 16h+15 of both planes = chroma row (c & 7) of
+// tiles 2h and 2h+1 of tile row (c >> 3): the two 16-byte m_C rows dct32_chroma_from_tiles_kernel loads, here one pred load
+// and one store each.  m_I is not touched; recon == pred is allowed, as above.
+__global__ __launch_bounds__(256) void dct32_inv_ctu_to_tiles_kernel(const int16_t *__restrict__ coef, const x266_ref_block_t *pred,
+                                                                     x266_ref_block_t *recon, int ctus_x, int tiles_x, size_t n_ctus,
+                                                                     const DctOps *__restrict__ ops, unsigned lds_per_wave)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    const int lane = threadIdx.x & 63;
+    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    unsigned char *slot = stage + wave_in_wg * lds_per_wave;
+    const size_t unit = (size_t)blockIdx.x * (blockDim.x >> 6) + wave_in_wg;
+    const size_t ctu = unit / 5;
+    const unsigned part = (unsigned)(unit - ctu * 5);
+    if (ctu >= n_ctus) return;
+    const unsigned c = lane & 31, h = lane >> 5;
+    const size_t cy = ctu / ctus_x, cx = ctu - cy * ctus_x;
+    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
+    unsigned col_base[4];
+    {
+        const unsigned u = (unsigned)kappa((int)c);
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) col_base[j] = 16u * h * 64u + ((((u >> 3) ^ j) & 3u) << 4) + (u & 7u) * 2u;
+    }
+    const char *src = reinterpret_cast<const char *>(coef + ctu * 6144) + lane * 16;
+    const LaneConsts k = load_consts(ops, lane);
+    v16i c2r;
+    {
+        const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
+    }
+    // one 32x32 block, given as the lane's two linear 16-byte pieces -> row c, columns 16h .. 16h+15 of the inverse
+    auto inverse = [&](const v4i &g0, const v4i &g1, v4i &o0, v4i &o1) {
+        __builtin_amdgcn_wave_barrier();                                   // a previous block's column reads are done with the slot
+        *reinterpret_cast<v4i *>(slot + lin0) = g0;
+        *reinterpret_cast<v4i *>(slot + lin1) = g1;
+        __builtin_amdgcn_wave_barrier();
+        uint32_t w[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const uint32_t e0 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m) >> 2) & 3] + (2 * m) * 64);
+            const uint32_t e1 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m + 1) >> 2) & 3] + (2 * m + 1) * 64);
+            w[m] = e0 | (e1 << 16);
+        }
+        v4i lo, hi;
+        split_planes(v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]}, lo, hi);
+        inv_passes(lo, hi, k, c2r, o0, o1);
+    };
+    if (part < 4) {
+        const v4i g0 = load16<true>(src + part * 2048), g1 = load16<true>(src + part * 2048 + 1024);
+        const size_t tile = (cy * 4 + (part >> 1) * 2 + (c >> 4)) * (size_t)tiles_x + cx * 4 + (part & 1) * 2 + h;
+        const size_t off = tile * sizeof(x266_ref_block_t) + (c & 15) * 16;
+        const v4i p = load16<true>(reinterpret_cast<const unsigned char *>(pred) + off);
+        v4i o0, o1;
+        inverse(g0, g1, o0, o1);
+        store16_sc1nt(reinterpret_cast<unsigned char *>(recon) + off, recon_luma16(p, o0, o1));
+        return;
+    }
+    const v4i u0 = load16<true>(src + 4 * 2048), u1 = load16<true>(src + 4 * 2048 + 1024);
+    const v4i v0 = load16<true>(src + 5 * 2048), v1 = load16<true>(src + 5 * 2048 + 1024);
+    const size_t tile = (cy * 4 + (c >> 3)) * (size_t)tiles_x + cx * 4 + 2 * h;
+    const size_t off = tile * sizeof(x266_ref_block_t) + 256 + (c & 7) * 16;
+    const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred) + off;
+    const v4i p0 = load16<true>(pp), p1 = load16<true>(pp + 512);          // tiles 2h and 2h + 1 of the CTU's tile row
+    v4i ou0, ou1, ov0, ov1;
+    inverse(u0, u1, ou0, ou1);
+    inverse(v0, v1, ov0, ov1);
+    unsigned char *pr = reinterpret_cast<unsigned char *>(recon) + off;
+    store16_sc1nt(pr, recon_chroma16(p0, ou0, ov0));
+    store16_sc1nt(pr + 512, recon_chroma16(p1, ou1, ov1));
+}
+
 // ---- the 1-D pass on its own (partialButterfly32, src_tb/dct32.c:66-170; RTL stage src/mkDct32.bsv:213-284) --------
 // dst[k*32 + j] = (int16)((sum_n g[k][n] * src[j*32 + n] + (1 << (shift-1))) >> shift): one MFMA pass of the forward
 // kernel with the accumulators stored TRANSPOSED, as the reference does.  Lane (c, h) holds frequency kappa(c) for the 16
@@ -613,6 +757,38 @@ hipError_t launch_dct32_ctu_from_tiles(const x266_ref_block_t *d_cur, const x266
     const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave;
     hipLaunchKernelGGL(dct32_ctu_from_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_cur, d_pred, d_out,
                        ctus_x, width / 16, n_ctus, d_fwd_ops, per_wave);
+    return hipGetLastError();
+}
+
+// the inverse batch's launch shape (cfg_for(ctx, 1), its LDS charge): same input side, same arithmetic
+hipError_t launch_dct32_inv_to_tiles(const int16_t *d_coef, const x266_ref_block_t *d_pred, x266_ref_block_t *d_recon, int width, int height,
+                                     const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream)
+{
+    const int blocks_x = width / 32;
+    const size_t n_blocks = (size_t)blocks_x * (size_t)(height / 32);
+    if (n_blocks == 0) return hipSuccess;
+    const unsigned tpb = (unsigned)cfg.wg_threads;
+    const size_t wpw = tpb / 64;
+    const unsigned bpw = units_per_wave_for(cfg, n_blocks);
+    const size_t waves = (n_blocks + bpw - 1) / bpw, wgs = (waves + wpw - 1) / wpw;
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t lds = wpw * (size_t)cfg.lds_bytes_per_wave;
+    hipLaunchKernelGGL(dct32_inv_to_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_coef, d_pred, d_recon, blocks_x, width / 16, n_blocks, d_inv_ops, bpw);
+    return hipGetLastError();
+}
+
+hipError_t launch_dct32_inv_ctu_to_tiles(const int16_t *d_coef, const x266_ref_block_t *d_pred, x266_ref_block_t *d_recon, int width, int height,
+                                         const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream)
+{
+    const int ctus_x = width / 64;
+    const size_t n_ctus = (size_t)ctus_x * (size_t)(height / 64);
+    if (n_ctus == 0) return hipSuccess;
+    const unsigned tpb = (unsigned)cfg.wg_threads;
+    const size_t wpw = tpb / 64, units = n_ctus * 5, wgs = (units + wpw - 1) / wpw;
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave;
+    hipLaunchKernelGGL(dct32_inv_ctu_to_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_coef, d_pred, d_recon,
+                       ctus_x, width / 16, n_ctus, d_inv_ops, per_wave);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 // tiled frames, emitted as the row-major int16 blocks the DCT32 / SATD kernels consume) has no
 // upstream counterpart -- upstream stops before the residual stage (xEncodeFrame,
 // src/x266.cpp:526-555) -- and is defined in include/x266hip.h.
+// Reconstruction (recon = clip8(pred + residual) back into m_Y / m_C) is its mirror image, likewise defined there.
 //
 // Pure data movement, HBM-bound.  One thread per 16-byte luma row of a tile; the first 8 rows of
 // a tile also carry its chroma row (8 U + 8 V bytes <-> 16 interleaved bytes).  A wave takes eight
@@ -248,6 +249,100 @@ __global__ __launch_bounds__(256) void residual_chroma_kernel(const x266_ref_blo
     store16_sc1nt(res_v + off, dv);
 }
 
+
+// ---- reconstruction: recon = clip8(pred + residual) into tiles --------------------------------------------------------
+// The mirror of the two residual kernels: the same units and lane mappings with loads and stores swapped, so that every
+// instruction still covers whole 128-byte lines on both sides.  Only m_Y (luma) or m_C (chroma) of the output tiles is
+// written.  pred and recon are NOT __restrict__: recon == pred is allowed (an encoder reconstructs over its prediction),
+// and every pred byte is read by the lane that later writes it.
+template <int LOGB>
+__global__ __launch_bounds__(256) void recon_luma_kernel(const x266_ref_block_t *pred, const int16_t *__restrict__ res,
+                                                         x266_ref_block_t *recon, int tiles_x, int groups_x, size_t n_units)
+{
+    constexpr int B = 1 << LOGB;
+    __shared__ __attribute__((aligned(16))) unsigned char stage[B == 32 ? 4 * 2048 : 16];
+    const size_t unit = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    const TileRow r = tile_row_of_unit(unit, lane, tiles_x, groups_x, n_units);
+    if (!r.unit_live) return;                                               // wave-uniform
+    const size_t width = (size_t)tiles_x * 16;
+    const size_t py = r.ty * 16 + r.i, px = r.tx * 16;                      // pixel coordinates of this lane's segment
+    // pred first, so that it is in flight with the residual (lanes past the frame edge read the clamped last tile: valid,
+    // read in the same instruction as its own lane's read, and they store nothing)
+    const v4i p = load16<true>(reinterpret_cast<const uint8_t *>(pred + r.tile) + r.i * 16);
+    v4i d0, d1;                                                             // its 16 residuals
+    if (B == 32) {
+        // the unit's 2 KiB of residual (four 512-byte runs of 8 rows x 64 bytes) arrive with two 1 KiB-linear loads and are
+        // re-ordered through the wave's LDS slot into the lanes' 32-byte row segments (residual_luma_kernel backwards)
+        unsigned char *slot = stage + (threadIdx.x >> 6) * 2048;
+        const size_t tx0 = (unit >> 1) % (size_t)groups_x * 8;
+        v4i g[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {                                       // both loads in flight before the first wait
+            const int c = lane + 64 * j, run = c >> 5;
+            size_t bx = (tx0 >> 1) + run;
+            if (bx * 2 >= (size_t)tiles_x) bx = tx0 >> 1;                   // a run beyond the frame edge re-reads the group's first: no lane uses it
+            const size_t blk = (py >> 5) * (width >> 5) + bx;
+            g[j] = load16<true>(reinterpret_cast<const char *>(res + blk * 1024 + ((py & 31) & ~7) * 32) + (c & 31) * 16);
+        }
+        *reinterpret_cast<v4i *>(slot + lane * 16) = g[0];
+        *reinterpret_cast<v4i *>(slot + 1024 + lane * 16) = g[1];
+        __builtin_amdgcn_wave_barrier();
+        const int t = lane & 7, rr = lane >> 3;
+        const unsigned char *mine = slot + (t >> 1) * 512 + rr * 64 + (t & 1) * 32;
+        d0 = *reinterpret_cast<const v4i *>(mine);
+        d1 = *reinterpret_cast<const v4i *>(mine + 16);
+        if (!r.live) return;
+    } else {                                                                // two 8x8 blocks side by side
+        if (!r.live) return;
+        const size_t blk = (py >> 3) * (width >> 3) + (px >> 3);
+        const int16_t *src = res + blk * 64 + (py & 7) * 8;
+        d0 = load16<true>(src);
+        d1 = load16<true>(src + 64);
+    }
+    store16_sc1nt(reinterpret_cast<uint8_t *>(recon + r.tile) + r.i * 16, recon_luma16(p, d0, d1));
+}
+
+// chroma: residual_chroma_kernel backwards.  LOGB = 3: a tile's 8x8 U and V rows straight from the block streams;
+// LOGB = 5: the unit's quarter-height slab of one 32x32 block arrives as ONE 1 KiB-linear load per plane and changes hands
+// through the wave's LDS slot (the same swizzled positions as the residual kernel, read and written the other way round).
+template <int LOGB>
+__global__ __launch_bounds__(256) void recon_chroma_kernel(const x266_ref_block_t *pred, const int16_t *__restrict__ res_u,
+                                                           const int16_t *__restrict__ res_v, size_t block_pitch,
+                                                           x266_ref_block_t *recon, int tiles_x, int groups_x, size_t n_units)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    const size_t unit = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (unit >= n_units) return;
+    const int lane = threadIdx.x & 63;
+    const size_t uy = unit / (size_t)groups_x, g = unit - uy * (size_t)groups_x;
+    const int t = lane >> 3, row = lane & 7;
+    const size_t ty = LOGB == 3 ? uy : uy * 2 + (size_t)(t >> 2);
+    const size_t tx = LOGB == 3 ? g * 8 + (size_t)t : g * 4 + (size_t)(t & 3);
+    if (LOGB == 3 && tx >= (size_t)tiles_x) return;                         // LOGB = 5 has no ragged units
+    const size_t tile = ty * (size_t)tiles_x + tx;
+    const v4i p = load16<true>(reinterpret_cast<const uint8_t *>(pred + tile) + 256 + row * 16);   // in flight with the residual
+    v4i du, dv;
+    if (LOGB == 5) {
+        unsigned char *slot = stage + (threadIdx.x >> 6) * 2048;
+        const size_t blk = (uy >> 1) * (size_t)(tiles_x >> 2) + g;
+        const size_t off = blk * block_pitch * 1024 + (uy & 1) * 512 + (size_t)lane * 8;
+        const v4i su = load16<true>(res_u + off), sv = load16<true>(res_v + off);
+        const unsigned rd = (unsigned)((lane & ~3) + ((lane & 3) ^ ((lane >> 3) & 3)));
+        *reinterpret_cast<v4i *>(slot + rd * 16) = su;
+        *reinterpret_cast<v4i *>(slot + 1024 + rd * 16) = sv;
+        __builtin_amdgcn_wave_barrier();
+        const unsigned wr = (unsigned)((t >> 2) * 32 + row * 4 + ((t & 3) ^ ((row >> 1) & 3)));
+        du = *reinterpret_cast<const v4i *>(slot + wr * 16);
+        dv = *reinterpret_cast<const v4i *>(slot + 1024 + wr * 16);
+    } else {
+        const size_t off = tile * block_pitch * 64 + (size_t)row * 8;       // tiles and 8x8 chroma blocks share their raster
+        du = load16<true>(res_u + off);
+        dv = load16<true>(res_v + off);
+    }
+    store16_sc1nt(reinterpret_cast<uint8_t *>(recon + tile) + 256 + row * 16, recon_chroma16(p, du, dv));
+}
+
 }  // namespace
 
 // Units per wave, measured (tools/probes/gpu_tilefmt_probe.py, 32768^2 frame): unpacking gains 13 % from two units per wave (its planar
@@ -302,6 +397,37 @@ hipError_t launch_residual_chroma(int block_edge, const x266_ref_block_t *d_cur,
     dim3 grid((unsigned)n_units), block(kThreads);
     if (block_edge == 32) hipLaunchKernelGGL(residual_chroma_kernel<5>, grid, block, kLdsPerWorkgroup, stream, d_cur, d_pred, d_res_u, d_res_v, block_pitch, tiles_x, groups_x, n_units);
     else                  hipLaunchKernelGGL(residual_chroma_kernel<3>, grid, block, kLdsPerWorkgroup, stream, d_cur, d_pred, d_res_u, d_res_v, block_pitch, tiles_x, groups_x, n_units);
+    return hipGetLastError();
+}
+
+// the launch shapes of the residual kernels they mirror
+hipError_t launch_recon_luma(int block_edge, const x266_ref_block_t *d_pred, const int16_t *d_res, x266_ref_block_t *d_recon,
+                             int width, int height, hipStream_t stream)
+{
+    const int tiles_x = width / 16, groups_x = (tiles_x + 7) / 8;
+    const size_t n_units = (size_t)groups_x * (height / 16) * 2;
+    if (n_units == 0) return hipSuccess;
+    constexpr unsigned kThreads = 128, kLdsPerWorkgroup = 20480;
+    const size_t wgs = (n_units + 1) / 2;
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    dim3 grid((unsigned)wgs), block(kThreads);
+    if (block_edge == 32) hipLaunchKernelGGL(recon_luma_kernel<5>, grid, block, kLdsPerWorkgroup - 4 * 2048, stream, d_pred, d_res, d_recon, tiles_x, groups_x, n_units);
+    else                  hipLaunchKernelGGL(recon_luma_kernel<3>, grid, block, kLdsPerWorkgroup, stream, d_pred, d_res, d_recon, tiles_x, groups_x, n_units);
+    return hipGetLastError();
+}
+
+hipError_t launch_recon_chroma(int block_edge, const x266_ref_block_t *d_pred, const int16_t *d_res_u, const int16_t *d_res_v, size_t block_pitch,
+                               x266_ref_block_t *d_recon, int width, int height, hipStream_t stream)
+{
+    const int tiles_x = width / 16, tiles_y = height / 16;
+    const int groups_x = block_edge == 32 ? tiles_x / 4 : (tiles_x + 7) / 8;
+    const size_t n_units = (size_t)groups_x * (size_t)(block_edge == 32 ? tiles_y / 2 : tiles_y);
+    if (n_units == 0) return hipSuccess;
+    constexpr unsigned kThreads = 64, kLdsPerWorkgroup = 12288;
+    if (n_units > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    dim3 grid((unsigned)n_units), block(kThreads);
+    if (block_edge == 32) hipLaunchKernelGGL(recon_chroma_kernel<5>, grid, block, kLdsPerWorkgroup, stream, d_pred, d_res_u, d_res_v, block_pitch, d_recon, tiles_x, groups_x, n_units);
+    else                  hipLaunchKernelGGL(recon_chroma_kernel<3>, grid, block, kLdsPerWorkgroup, stream, d_pred, d_res_u, d_res_v, block_pitch, d_recon, tiles_x, groups_x, n_units);
     return hipGetLastError();
 }
 

@@ -210,4 +210,46 @@ __device__ __forceinline__ void inv_passes(const v4i &zlo, const v4i &zhi, const
     inv_passes_with(zlo, zhi, k, [&](int g) { return v4i{c2r[4 * g], c2r[4 * g + 1], c2r[4 * g + 2], c2r[4 * g + 3]}; }, o0, o1);
 }
 
+// ---- reconstruction: clip8(pred + residual), exact for every int16 residual --------------------------------------------------
+// Two pixels per 16-bit lane pair: v_pk_add_i16 with clamp saturates pred (0..255) + residual to int16, which never moves the
+// result across the 0 / 255 bounds, then v_pk_max_i16 / v_pk_min_i16 clip it to 0..255 (a wrapping add would turn 100 + 32767
+// into a negative number).  `p` holds the two pred bytes zero-extended to 16 bits, `r` the two int16 residuals.
+__device__ __forceinline__ uint32_t add_clip8x2(uint32_t p, uint32_t r)
+{
+    typedef short v2i16 __attribute__((ext_vector_type(2)));
+    const v2i16 lo = {0, 0}, hi = {255, 255};
+    const v2i16 s = __builtin_elementwise_add_sat(__builtin_bit_cast(v2i16, p), __builtin_bit_cast(v2i16, r));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(s, lo), hi));
+}
+
+// 16 luma pixels: p = 16 pred bytes, r0 / r1 = residuals 0..7 / 8..15 as int16 pairs in column order
+__device__ __forceinline__ v4i recon_luma16(const v4i &p, const v4i &r0, const v4i &r1)
+{
+    const uint32_t r[8] = {(uint32_t)r0[0], (uint32_t)r0[1], (uint32_t)r0[2], (uint32_t)r0[3],
+                           (uint32_t)r1[0], (uint32_t)r1[1], (uint32_t)r1[2], (uint32_t)r1[3]};
+    v4i o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t x = (uint32_t)p[q];
+        const uint32_t s01 = add_clip8x2(bperm(0u, x, 0x0c010c00u), r[2 * q]);      // pixels 4q, 4q+1 (sel 0x0c = zero byte)
+        const uint32_t s23 = add_clip8x2(bperm(0u, x, 0x0c030c02u), r[2 * q + 1]);  // pixels 4q+2, 4q+3
+        o[q] = (int)bperm(s23, s01, 0x06040200u);
+    }
+    return o;
+}
+
+// 8 interleaved (U, V) chroma pairs of m_C: p = 16 pred bytes u0 v0 u1 v1 ..., ru / rv = the 8 U / 8 V residuals as int16 pairs
+__device__ __forceinline__ v4i recon_chroma16(const v4i &p, const v4i &ru, const v4i &rv)
+{
+    v4i o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t x = (uint32_t)p[q];                                                  // u(2q) v(2q) u(2q+1) v(2q+1)
+        const uint32_t su = add_clip8x2(bperm(0u, x, 0x0c020c00u), (uint32_t)ru[q]);
+        const uint32_t sv = add_clip8x2(bperm(0u, x, 0x0c030c01u), (uint32_t)rv[q]);
+        o[q] = (int)bperm(sv, su, 0x06020400u);                                            // re-interleave
+    }
+    return o;
+}
+
 }  // namespace x266

@@ -964,6 +964,104 @@ int xDct32FwdCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, co
     return X266HIP_OK;
 }
 
+// ---- reconstruction into tiles: the way back from residuals / coefficients to a frame --------------------------------------
+// The output tile array may BE the pred array (an encoder reconstructs over its prediction) but must not otherwise overlap
+// it, nor any other input.
+static bool recon_in_place_or_disjoint(const void *recon, const void *pred, size_t tile_bytes)
+{
+    return recon == pred || !ranges_overlap(recon, tile_bytes, pred, tile_bytes);
+}
+
+// bytes from the first byte of block 0 to the last byte of block n - 1 of a stream with a pitch of `pitch` blocks, and the
+// stream must not run past the end of the address space: false where either does not fit (no wrap-around)
+static bool block_stream_span(const void *p, size_t n_blocks, size_t pitch, size_t block_bytes, size_t *span)
+{
+    size_t t = 0;
+    uintptr_t end = 0;
+    if (n_blocks == 0) { *span = 0; return true; }
+    return !__builtin_mul_overflow(n_blocks - 1, pitch, &t) && !__builtin_add_overflow(t, (size_t)1, &t) &&
+           !__builtin_mul_overflow(t, block_bytes, span) && !__builtin_add_overflow((uintptr_t)p, *span, &end);
+}
+
+int xReconLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_residual, int width, int height,
+                  int block_edge, x266_ref_block_t *d_recon, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (block_edge != 8 && block_edge != 32) return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: block_edge must be 8 or 32");
+    const int mask = block_edge == 32 ? 31 : 15;
+    if (width <= 0 || height <= 0 || (width & mask) || (height & mask)) return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: frame size");
+    if (!d_pred || !d_residual || !d_recon || ((((uintptr_t)d_pred | (uintptr_t)d_residual | (uintptr_t)d_recon)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: NULL or unaligned buffer");
+    const size_t pixels = (size_t)width * (size_t)height, tile_bytes = pixels * 2;       // 512 bytes per 256 pixels
+    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_residual, pixels * 2))
+        return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    X_DEV(ctx);
+    hipError_t e = launch_recon_luma(block_edge, d_pred, d_residual, d_recon, width, height, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "recon launch", e);
+    return X266HIP_OK;
+}
+
+int xReconChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_res_u, const int16_t *d_res_v, size_t block_pitch,
+                    int width, int height, int block_edge, x266_ref_block_t *d_recon, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (block_edge != 8 && block_edge != 32) return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: block_edge must be 8 or 32");
+    const int mask = block_edge == 32 ? 63 : 15;
+    if (width <= 0 || height <= 0 || (width & mask) || (height & mask)) return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: frame size");
+    if (!d_pred || !d_res_u || !d_res_v || !d_recon ||
+        ((((uintptr_t)d_pred | (uintptr_t)d_res_u | (uintptr_t)d_res_v | (uintptr_t)d_recon)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: NULL or unaligned buffer");
+    const size_t n_blocks = (size_t)(width / 2 / block_edge) * (size_t)(height / 2 / block_edge), block_bytes = (size_t)block_edge * block_edge * 2;
+    size_t span_u = 0, span_v = 0;
+    if (block_pitch < 1 || !block_stream_span(d_res_u, n_blocks, block_pitch, block_bytes, &span_u) ||
+        !block_stream_span(d_res_v, n_blocks, block_pitch, block_bytes, &span_v))
+        return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: block_pitch < 1, or the residual streams do not fit in the address space");
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2;
+    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_res_u, span_u) ||
+        ranges_overlap(d_recon, tile_bytes, d_res_v, span_v))
+        return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    X_DEV(ctx);
+    hipError_t e = launch_recon_chroma(block_edge, d_pred, d_res_u, d_res_v, block_pitch, d_recon, width, height, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "chroma recon launch", e);
+    return X266HIP_OK;
+}
+
+int xDct32InvToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
+                        x266_ref_block_t *d_recon, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 31) || (height & 31)) return fail(ctx, X266HIP_EINVAL, "xDct32InvToTilesDev: width/height must be multiples of 32");
+    if (!d_coef || !d_pred || !d_recon || ((((uintptr_t)d_coef | (uintptr_t)d_pred | (uintptr_t)d_recon)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, "xDct32InvToTilesDev: NULL or unaligned buffer");
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2;                      // and as many bytes of coefficients
+    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_coef, tile_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xDct32InvToTilesDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    X_DEV(ctx);
+    LaunchCfg cfg = cfg_for(ctx, 1);
+    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
+    hipError_t e = launch_dct32_inv_to_tiles(d_coef, d_pred, d_recon, width, height, ctx->d_inv_lds, cfg, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused inverse transform launch", e);
+    return X266HIP_OK;
+}
+
+int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
+                           x266_ref_block_t *d_recon, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 63) || (height & 63)) return fail(ctx, X266HIP_EINVAL, "xDct32InvCtuToTilesDev: width/height must be multiples of 64");
+    if (!d_coef || !d_pred || !d_recon || ((((uintptr_t)d_coef | (uintptr_t)d_pred | (uintptr_t)d_recon)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, "xDct32InvCtuToTilesDev: NULL or unaligned buffer");
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, coef_bytes = (size_t)(width / 64) * (size_t)(height / 64) * 12288;
+    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_coef, coef_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xDct32InvCtuToTilesDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    X_DEV(ctx);
+    LaunchCfg cfg = cfg_for(ctx, 1);
+    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
+    hipError_t e = launch_dct32_inv_ctu_to_tiles(d_coef, d_pred, d_recon, width, height, ctx->d_inv_lds, cfg, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused CTU inverse launch", e);
+    return X266HIP_OK;
+}
+
 int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                                uint32_t *d_out_u, uint32_t *d_out_v, size_t pitch, void *stream)
 {
