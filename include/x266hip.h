@@ -86,7 +86,8 @@ int  xHipDeviceInfo(const x266hip_ctx *ctx, char *name, size_t name_cap,
  *                            the largest workgroup = the 64 KiB a launch may ask for; values below the kernel's own need are raised to it)
  *   "tile_tiles_per_wave"    xTransformTilesDev: consecutive tiles per wave (0 = 2)
  *   "adaptive_per_wave"      shrink the per-wave run on small batches (default 1)
- *   "me_tile_rows"           motion-search tile height in block rows (0, the default: chosen from the frame size and the CU count)
+ *   "me_tile_rows"           motion-search tile height in block rows (0, the default: chosen from the frame size and the CU count);
+ *                            applies to xSatd8x8SearchDev / xSad8x8SearchDev and their tiled forms ...SearchFromTilesDev alike
  *   "autotune"               0 (default) / 1: boxes differ in which launch shape a few kernels run fastest in (by up to 5 %).  With 1, the FIRST
  *                            large call of a family -- xDct32FwdInvBatchDev with and without d_coef (>= 2^18 blocks), xSatd8x8BatchDev
  *                            (>= 2^23 blocks), xSadBatchDev edge >= 8 (>= 128 MiB per input) -- times the family's candidate shapes on the
@@ -313,6 +314,30 @@ int xDct32InvToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_
  * xReconLumaDev(.., 32, ..) and xReconChromaDev(.., 32, ..).  width, height multiples of 64. */
 int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
                            x266_ref_block_t *d_recon, void *stream);
+/* Inter prediction on tiled frames (no upstream counterpart: upstream keeps its references as tiled frames, codec_t.m_frames[],
+ * src/x266.cpp:96-102, but has no search or compensation for them).  Edge convention of every call below: a reference sample
+ * outside the frame takes the nearest in-frame sample, ref[clamp(y, 0, H-1)][clamp(x, 0, W-1)] -- edge replication on all four
+ * sides, defined for any displacement, a range larger than the frame included.  width, height multiples of 16; tile buffers
+ * 16-byte aligned; records 8-byte aligned, cost maps 4-byte aligned.
+ * The searches: xSatd8x8SearchDev / xSad8x8SearchDev (same cost per candidate, candidate order, tie-break, d_best and d_costs
+ * layouts, 1 <= range <= 64) with cur and ref the m_Y planes of two tiled frames -- bit-identical to the planar calls on
+ * np.pad(ref_plane, range, mode="edge").  d_cur == d_ref is allowed (both are read-only); d_best or d_costs overlapping either
+ * frame, or a cost map whose size does not fit in the address space, returns X266HIP_EINVAL.  The SATD form uses the same
+ * per-stream scratch as xSatd8x8SearchDev: under a stream capture call xHipMeScratchReserve first (or run one search on that
+ * stream beforehand). */
+int xSatd8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
+                               int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
+                               void *stream);
+int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
+                              int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
+                              void *stream);
+/* Integer-pel luma motion compensation: one x266_me_result_t per 8x8 block in raster order of blocks (exactly the searches'
+ * d_best; cost is ignored), pred[8by+y][8bx+x] = ref[clamp(8by+y+mvy, 0, H-1)][clamp(8bx+x+mvx, 0, W-1)] for any int16 vector.
+ * Writes only m_Y of d_pred; m_C and m_I are left untouched, as xReconLumaDev leaves them.  Blocks read what other blocks
+ * would overwrite, so d_pred overlapping d_ref or d_mv returns X266HIP_EINVAL.  Chroma is not compensated: with integer luma
+ * vectors 4:2:0 chroma needs fractional-sample interpolation, for which no convention exists here yet. */
+int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                       int width, int height, x266_ref_block_t *d_pred, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; buffers 16-byte
  * aligned): d_out[b] = sum |a - b|, exactly sad() of
@@ -383,8 +408,8 @@ int xHipStreamDestroy(x266hip_ctx *ctx, void *stream);
  * xHipGraphBegin and xHipGraphEnd -- any of the ...Dev calls above, in any number -- is recorded
  * instead of run, and xHipGraphLaunch replays the whole sequence with one submission.  The recorded
  * calls keep their pointer and size arguments, so a graph is replayed over the same buffers with new
- * contents.  xSatd8x8SearchDev sizes an internal scratch buffer per (stream, frame size) on first use, which is
- * illegal inside a capture: call xHipMeScratchReserve (below) or run one search on that stream beforehand. */
+ * contents.  xSatd8x8SearchDev and xSatd8x8SearchFromTilesDev size an internal scratch buffer per (stream, frame size) on first
+ * use, which is illegal inside a capture: call xHipMeScratchReserve (below) or run one search on that stream beforehand. */
 typedef struct x266hip_graph x266hip_graph;
 int xHipGraphBegin(x266hip_ctx *ctx, void *stream);
 int xHipGraphEnd(x266hip_ctx *ctx, void *stream, x266hip_graph **graph);

@@ -100,6 +100,9 @@ def load_library(path=None):
                                     ctypes.c_int, _P, _P, _P]
     L.xSad8x8SearchDev.argtypes = [_P, _P, ctypes.c_ssize_t, _P, ctypes.c_ssize_t, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, _P, _P, _P]
+    for name in ("xSatd8x8SearchFromTilesDev", "xSad8x8SearchFromTilesDev"):
+        getattr(L, name).argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]
+    L.xMotionCompLumaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     for name in ("xDct32FwdBatch", "xDct32InvBatch", "xSatd8x8Batch"):
         getattr(L, name).argtypes = [_P, _P, _P, _SZ]
     L.xHipMalloc.argtypes = [_P, ctypes.POINTER(_P), _SZ]
@@ -522,6 +525,55 @@ class Codec:
         cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
         costs = dcost.download(np.uint32, nb * ncand).reshape(nb, ncand) if want_costs else None
         return mv, cost, costs
+
+    def satd_search_from_tiles_dev(self, d_cur, d_ref, width, height, rng, d_best, d_costs=0, stream=0):
+        self._check(self.L.xSatd8x8SearchFromTilesDev(self.ctx, d_cur, d_ref, width, height, rng, d_best, d_costs or None, stream),
+                    "xSatd8x8SearchFromTilesDev")
+
+    def sad_search_from_tiles_dev(self, d_cur, d_ref, width, height, rng, d_best, d_costs=0, stream=0):
+        self._check(self.L.xSad8x8SearchFromTilesDev(self.ctx, d_cur, d_ref, width, height, rng, d_best, d_costs or None, stream),
+                    "xSad8x8SearchFromTilesDev")
+
+    def motion_comp_luma_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
+        self._check(self.L.xMotionCompLumaDev(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompLumaDev")
+
+    def search_tiles(self, cur_tiles, ref_tiles, w, h, rng, want_costs=False, metric="satd"):
+        """numpy convenience around xSatd8x8SearchFromTilesDev / xSad8x8SearchFromTilesDev: two tile arrays of a w x h frame
+        (uint8, 512 bytes per tile) -> (mv [nb, 2] int16, cost [nb] uint32, costs [nb, (2R+1)^2] or None), as satd_search."""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
+        assert cur.size == w * h * 2 and ref.size == w * h * 2
+        nb = (h // 8) * (w // 8)
+        ncand = (2 * rng + 1) ** 2
+        dc, dr, db = self.alloc(cur.nbytes), self.alloc(ref.nbytes), self.alloc(nb * 8)
+        dcost = self.alloc(nb * ncand * 4) if want_costs else None
+        dc.upload(cur)
+        dr.upload(ref)
+        fn = self.satd_search_from_tiles_dev if metric == "satd" else self.sad_search_from_tiles_dev
+        fn(dc.ptr, dr.ptr, w, h, rng, db.ptr, dcost.ptr if want_costs else 0)
+        self.stream_sync()
+        raw = db.download(np.uint8, nb * 8)
+        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
+        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
+        costs = dcost.download(np.uint32, nb * ncand).reshape(nb, ncand) if want_costs else None
+        return mv, cost, costs
+
+    def motion_comp_luma(self, ref_tiles, mv, w, h, base=None):
+        """numpy convenience around xMotionCompLumaDev: ref tile array, mv [nb, 2] int16 (mvx, mvy per 8x8 block, raster order)
+        -> the predicted tile array; m_C / m_I come from `base` (a tile array; None: zeros), as the call leaves them."""
+        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
+        assert ref.size == w * h * 2
+        nb = (h // 8) * (w // 8)
+        rec = np.zeros((nb, 4), np.int16)
+        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
+        pred = np.zeros(ref.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
+        dr, dm, dp = self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(pred.nbytes)
+        dr.upload(ref)
+        dm.upload(rec)
+        dp.upload(pred)
+        self.motion_comp_luma_dev(dr.ptr, dm.ptr, w, h, dp.ptr)
+        self.stream_sync()
+        return dp.download(np.uint8, pred.size)
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

@@ -125,9 +125,47 @@ __device__ __forceinline__ void load_window8(const unsigned char *lds0, int win_
     }
 }
 
+// Pixel source of the searches (template parameter TILED): a planar luma plane (cur / ref point at pixel (0,0), rows
+// cur_stride / ref_stride bytes apart, ref padded by `range`), or the m_Y planes of two ref_block_t tile arrays (cur / ref
+// point at tile 0; sample (y, x) at byte ((y >> 4) * (width >> 4) + (x >> 4)) * 512 + (y & 15) * 16 + (x & 15)).  Only the
+// current-block loads and the reference-window fill differ; a tiled reference sample outside the frame takes the nearest
+// in-frame one (edge replication on all four sides), which is what the padded planar search reads after np.pad(.., "edge").
+__device__ __forceinline__ const uint8_t *tile_block_row(const uint8_t *tiles, int tiles_x, int bx, int by)
+{   // row 0 of 8x8 block (bx, by) of a tiled frame: an aligned quadrant of tile (by >> 1, bx >> 1), rows 16 bytes apart
+    return tiles + ((size_t)(by >> 1) * (size_t)tiles_x + (size_t)(bx >> 1)) * 512 + (by & 1) * 128 + (bx & 1) * 8;
+}
+
+// Reference samples (gy, gx0 .. gx0 + 3) of a tiled frame as one dword, gy inside the frame, every x clamped to [0, width - 1].
+// `row` = tile (gy >> 4, 0) + (gy & 15) * 16.  Inside the frame: two aligned dwords (each within one 16-byte tile row; the
+// second one is clamped into the frame where the shift makes it unused) and a funnel shift; at the left / right edge: bytes.
+__device__ __forceinline__ uint32_t tiled_ref_dword(const uint8_t *row, int width, int gx0)
+{
+    if (gx0 >= 0 && gx0 + 3 <= width - 1) {
+        const int xa = gx0 & ~3, xb = xa + 4 < width ? xa + 4 : xa;
+        const uint32_t d0 = *reinterpret_cast<const uint32_t *>(row + (size_t)(xa >> 4) * 512 + (xa & 15));
+        const uint32_t d1 = *reinterpret_cast<const uint32_t *>(row + (size_t)(xb >> 4) * 512 + (xb & 15));
+        return __builtin_amdgcn_alignbit(d1, d0, (gx0 & 3) * 8);
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        int gx = gx0 + b;
+        gx = gx < 0 ? 0 : (gx > width - 1 ? width - 1 : gx);
+        v |= (uint32_t)row[(size_t)(gx >> 4) * 512 + (gx & 15)] << (8 * b);
+    }
+    return v;
+}
+
+__device__ __forceinline__ const uint8_t *tiled_ref_row(const MeParams &P, int gy)
+{
+    gy = gy < 0 ? 0 : (gy > P.height - 1 ? P.height - 1 : gy);
+    return P.ref + (size_t)(gy >> 4) * (size_t)(P.width >> 4) * 512 + (gy & 15) * 16;
+}
+
 // Pre-pass: Hc of every 8x8 block of the current frame, 32 dwords per block in hadamard_lane's order.
 // Blocks are stored TILE-MAJOR (search tile, then block row, then block column inside the tile): the
 // search kernel addresses all blocks of its tile from one scalar base.
+template <bool TILED>
 __global__ __launch_bounds__(256) void me_coef_kernel(const uint8_t *__restrict__ cur, long long cur_stride,
                                                       int blocks_x, int n_blocks, int tiles_x, int tby,
                                                       uint32_t *__restrict__ coef)
@@ -139,16 +177,26 @@ __global__ __launch_bounds__(256) void me_coef_kernel(const uint8_t *__restrict_
     const bool live = blk < n_blocks;
     if (!live) blk = n_blocks - 1;
     const int bx = blk % blocks_x, by = blk / blocks_x;
-    const uint8_t *src = cur + (long long)(by * 8) * cur_stride + bx * 8;
     v4i px[4];
+    if constexpr (TILED) {
+        const uint8_t *src = tile_block_row(cur, blocks_x >> 1, bx, by);
 #pragma unroll
-    for (int y = 0; y < 8; ++y) {
-        const uint8_t *q = src + (long long)y * cur_stride;
-        uint32_t lo = 0, hi = 0;
+        for (int y = 0; y < 8; ++y) {
+            const uint2 q = *reinterpret_cast<const uint2 *>(src + y * 16);
+            px[y >> 1][2 * (y & 1)]     = (int)(q.x ^ 0x80808080u);
+            px[y >> 1][2 * (y & 1) + 1] = (int)(q.y ^ 0x80808080u);
+        }
+    } else {
+        const uint8_t *src = cur + (long long)(by * 8) * cur_stride + bx * 8;
 #pragma unroll
-        for (int b = 0; b < 4; ++b) { lo |= (uint32_t)q[b] << (8 * b); hi |= (uint32_t)q[4 + b] << (8 * b); }
-        px[y >> 1][2 * (y & 1)]     = (int)(lo ^ 0x80808080u);
-        px[y >> 1][2 * (y & 1) + 1] = (int)(hi ^ 0x80808080u);
+        for (int y = 0; y < 8; ++y) {
+            const uint8_t *q = src + (long long)y * cur_stride;
+            uint32_t lo = 0, hi = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { lo |= (uint32_t)q[b] << (8 * b); hi |= (uint32_t)q[4 + b] << (8 * b); }
+            px[y >> 1][2 * (y & 1)]     = (int)(lo ^ 0x80808080u);
+            px[y >> 1][2 * (y & 1) + 1] = (int)(hi ^ 0x80808080u);
+        }
     }
     const LaneOps O = make_lane_ops(lane);
     uint32_t p[32];
@@ -246,7 +294,7 @@ __device__ __forceinline__ void score_blocks(const uint32_t (&pa)[32], const uin
 // VALU stream): no registers, so the block loop is a real loop.
 // The remaining rem columns and rem rows of every window ("+1" at R = 64: 257 of 16641 candidates) are
 // scored by narrow units -- 64 positions down one column, or along one row -- with per-lane validity.
-template <int TBY, bool COSTS, int WG, int WPS>
+template <int TBY, bool COSTS, int WG, int WPS, bool TILED>
 __global__ __launch_bounds__(WG, WPS) void satd_search_kernel(const MeParams P, const uint32_t *__restrict__ coef)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -273,7 +321,7 @@ __global__ __launch_bounds__(WG, WPS) void satd_search_kernel(const MeParams P, 
     {   // reference window, signed pixels: a wave takes whole rows (one dword per lane), eight rows in flight
         typedef uint32_t u32_any_align __attribute__((aligned(1)));
         const int dwords_per_row = (8 * n_ucols + 20) >> 2;                // what this range reads of a row (51 at R = 64)
-        const int gx0 = x0 - R + 4 * lane;                               // >= -R: only the right and bottom edges clamp
+        const int gx0 = x0 - R + 4 * lane;                               // >= -R: only the right and bottom edges clamp (planar)
         const bool inside = gx0 + 3 <= P.width + R - 1;
         const int last_x = P.width + R - 1, last_y = P.height + R - 1;
         for (int ry0 = wave; ry0 < win_rows; ry0 += 8 * n_waves) {
@@ -282,13 +330,17 @@ __global__ __launch_bounds__(WG, WPS) void satd_search_kernel(const MeParams P, 
             for (int u = 0; u < 8; ++u) {
                 const int ry = ry0 + u * n_waves;
                 int gy = y0 - R + (ry < win_rows ? ry : win_rows - 1);
-                gy = gy > last_y ? last_y : gy;
-                const uint8_t *row = P.ref + (long long)gy * P.ref_stride;
-                if (inside) v[u] = *reinterpret_cast<const u32_any_align *>(row + gx0);
-                else {
-                    v[u] = 0;
+                if constexpr (TILED) {
+                    v[u] = tiled_ref_dword(tiled_ref_row(P, gy), P.width, gx0);
+                } else {
+                    gy = gy > last_y ? last_y : gy;
+                    const uint8_t *row = P.ref + (long long)gy * P.ref_stride;
+                    if (inside) v[u] = *reinterpret_cast<const u32_any_align *>(row + gx0);
+                    else {
+                        v[u] = 0;
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) { const int gx = gx0 + b > last_x ? last_x : gx0 + b; v[u] |= (uint32_t)row[gx] << (8 * b); }
+                        for (int b = 0; b < 4; ++b) { const int gx = gx0 + b > last_x ? last_x : gx0 + b; v[u] |= (uint32_t)row[gx] << (8 * b); }
+                    }
                 }
             }
 #pragma unroll
@@ -454,7 +506,7 @@ __global__ __launch_bounds__(WG, WPS) void satd_search_kernel(const MeParams P, 
 // ============================================================================
 __device__ __forceinline__ uint32_t sadhi8(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_sad_hi_u8(a, b, c); }
 
-template <int TBY, bool COSTS>
+template <int TBY, bool COSTS, bool TILED>
 __global__ __launch_bounds__(256) void sad_search_kernel(const MeParams P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -484,13 +536,17 @@ __global__ __launch_bounds__(256) void sad_search_kernel(const MeParams P)
             for (int u = 0; u < 8; ++u) {
                 const int ry = ry0 + u * n_waves;
                 int gy = y0 - R + (ry < win_rows ? ry : win_rows - 1);
-                gy = gy > last_y ? last_y : gy;
-                const uint8_t *row = P.ref + (long long)gy * P.ref_stride;
-                if (inside) v[u] = *reinterpret_cast<const u32_any_align *>(row + gx0);
-                else {
-                    v[u] = 0;
+                if constexpr (TILED) {
+                    v[u] = tiled_ref_dword(tiled_ref_row(P, gy), P.width, gx0);
+                } else {
+                    gy = gy > last_y ? last_y : gy;
+                    const uint8_t *row = P.ref + (long long)gy * P.ref_stride;
+                    if (inside) v[u] = *reinterpret_cast<const u32_any_align *>(row + gx0);
+                    else {
+                        v[u] = 0;
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) { const int gx = gx0 + b > last_x ? last_x : gx0 + b; v[u] |= (uint32_t)row[gx] << (8 * b); }
+                        for (int b = 0; b < 4; ++b) { const int gx = gx0 + b > last_x ? last_x : gx0 + b; v[u] |= (uint32_t)row[gx] << (8 * b); }
+                    }
                 }
             }
 #pragma unroll
@@ -533,7 +589,9 @@ __global__ __launch_bounds__(256) void sad_search_kernel(const MeParams P)
             const int by = ty * TBY + (j < blocks_left_y ? j : blocks_left_y - 1);
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
-                const uint32_t *q = reinterpret_cast<const uint32_t *>(P.cur + (long long)(by * 8 + p) * P.cur_stride + (tx * kTileBlocksX + i) * 8) + lane0;
+                const uint32_t *q;
+                if constexpr (TILED) q = reinterpret_cast<const uint32_t *>(tile_block_row(P.cur, P.width >> 4, tx * kTileBlocksX + i, by) + p * 16) + lane0;
+                else q = reinterpret_cast<const uint32_t *>(P.cur + (long long)(by * 8 + p) * P.cur_stride + (tx * kTileBlocksX + i) * 8) + lane0;
                 c[j][p][0] = q[0];
                 c[j][p][1] = q[1];
             }
@@ -654,7 +712,7 @@ __global__ __launch_bounds__(256) void sad_search_kernel(const MeParams P)
 
 hipError_t launch_satd_search(const uint8_t *d_cur, long long cur_stride, const uint8_t *d_ref, long long ref_stride,
                                int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
-                               int tile_rows, uint32_t *d_coef_scratch, int cu_count, hipStream_t stream)
+                               int tile_rows, uint32_t *d_coef_scratch, int cu_count, bool tiled, hipStream_t stream)
 {
     MeParams P;
     P.cur = d_cur; P.ref = d_ref; P.cur_stride = cur_stride; P.ref_stride = ref_stride;
@@ -690,8 +748,10 @@ hipError_t launch_satd_search(const uint8_t *d_cur, long long cur_stride, const 
     const int n_rows = 8 * (tby - 1) + span;
     P.best = d_best; P.costs = d_costs;
     const int n_blocks = P.blocks_x * P.blocks_y;
-    hipLaunchKernelGGL(me_coef_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, stream, d_cur, cur_stride,
-                       P.blocks_x, n_blocks, P.tiles_x, tby, d_coef_scratch);
+    if (tiled) hipLaunchKernelGGL(me_coef_kernel<true>, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, stream, d_cur, cur_stride,
+                                  P.blocks_x, n_blocks, P.tiles_x, tby, d_coef_scratch);
+    else       hipLaunchKernelGGL(me_coef_kernel<false>, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, stream, d_cur, cur_stride,
+                                  P.blocks_x, n_blocks, P.tiles_x, tby, d_coef_scratch);
     {
         const hipError_t e0 = hipGetLastError();
         if (e0 != hipSuccess) return e0;
@@ -703,10 +763,13 @@ hipError_t launch_satd_search(const uint8_t *d_cur, long long cur_stride, const 
     const dim3 grid((unsigned)(P.tiles_x * tiles_y)), block(512);        // 8-wave workgroups, two per CU: 4 waves per SIMD
     const uint32_t *cf = d_coef_scratch;
 #ifdef X266_ME_TIMING
-#define X266_ME5(T) hipLaunchKernelGGL((satd_search_kernel<T, false, 512, 4>), grid, block, lds, stream, P, cf)
+#define X266_ME5(T) do { if (tiled) hipLaunchKernelGGL((satd_search_kernel<T, false, 512, 4, true>), grid, block, lds, stream, P, cf); \
+                         else       hipLaunchKernelGGL((satd_search_kernel<T, false, 512, 4, false>), grid, block, lds, stream, P, cf); } while (0)
 #else
-#define X266_ME5(T) do { if (d_costs) hipLaunchKernelGGL((satd_search_kernel<T, true, 512, 4>), grid, block, lds, stream, P, cf); \
-                         else         hipLaunchKernelGGL((satd_search_kernel<T, false, 512, 4>), grid, block, lds, stream, P, cf); } while (0)
+#define X266_ME5(T) do { if (tiled && d_costs) hipLaunchKernelGGL((satd_search_kernel<T, true, 512, 4, true>), grid, block, lds, stream, P, cf); \
+                         else if (tiled)       hipLaunchKernelGGL((satd_search_kernel<T, false, 512, 4, true>), grid, block, lds, stream, P, cf); \
+                         else if (d_costs)     hipLaunchKernelGGL((satd_search_kernel<T, true, 512, 4, false>), grid, block, lds, stream, P, cf); \
+                         else                  hipLaunchKernelGGL((satd_search_kernel<T, false, 512, 4, false>), grid, block, lds, stream, P, cf); } while (0)
 #endif
     if (tby == 8) X266_ME5(8); else if (tby == 4) X266_ME5(4); else X266_ME5(2);
 #undef X266_ME5
@@ -715,7 +778,7 @@ hipError_t launch_satd_search(const uint8_t *d_cur, long long cur_stride, const 
 
 hipError_t launch_sad_search(const uint8_t *d_cur, long long cur_stride, const uint8_t *d_ref, long long ref_stride,
                               int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
-                              int tile_rows, hipStream_t stream)
+                              int tile_rows, bool tiled, hipStream_t stream)
 {
     MeParams P;
     P.cur = d_cur; P.ref = d_ref; P.cur_stride = cur_stride; P.ref_stride = ref_stride;
@@ -730,8 +793,10 @@ hipError_t launch_sad_search(const uint8_t *d_cur, long long cur_stride, const u
     P.best = d_best; P.costs = d_costs;
     dim3 grid((unsigned)(P.tiles_x * tiles_y)), block(256);
     const size_t lds = 256 + (size_t)(n_rows + 7) * kPitch;
-#define X266_SADS(T) do { if (d_costs) hipLaunchKernelGGL((sad_search_kernel<T, true>), grid, block, lds, stream, P); \
-                          else         hipLaunchKernelGGL((sad_search_kernel<T, false>), grid, block, lds, stream, P); } while (0)
+#define X266_SADS(T) do { if (tiled && d_costs) hipLaunchKernelGGL((sad_search_kernel<T, true, true>), grid, block, lds, stream, P); \
+                          else if (tiled)       hipLaunchKernelGGL((sad_search_kernel<T, false, true>), grid, block, lds, stream, P); \
+                          else if (d_costs)     hipLaunchKernelGGL((sad_search_kernel<T, true, false>), grid, block, lds, stream, P); \
+                          else                  hipLaunchKernelGGL((sad_search_kernel<T, false, false>), grid, block, lds, stream, P); } while (0)
     X266_SADS(2);
 #undef X266_SADS
     return hipGetLastError();

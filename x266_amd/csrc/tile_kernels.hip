@@ -343,6 +343,51 @@ __global__ __launch_bounds__(256) void recon_chroma_kernel(const x266_ref_block_
     store16_sc1nt(reinterpret_cast<uint8_t *>(recon + tile) + 256 + row * 16, recon_chroma16(p, du, dv));
 }
 
+// Integer-pel luma motion compensation: pred[8by + y][8bx + x] = ref[clamp(8by + y + mvy, 0, H - 1)][clamp(8bx + x + mvx, 0, W - 1)]
+// with (mvx, mvy) the x266_me_result_t record of 8x8 block (bx, by) (raster order of blocks, the searches' d_best layout).
+// One lane per 16-byte row of an output tile -- the rows of the tile's left and right 8x8 blocks -- so sixteen lanes write a
+// tile's m_Y and a wave four whole tiles (1 KiB of full lines).  The reads are a gather: a source row of 8 samples inside the
+// frame is three aligned dwords (each within one 16-byte tile row, possibly of two tiles) and two funnel shifts; rows that
+// reach past the left or right edge are read sample by sample.
+__global__ __launch_bounds__(256) void motion_comp_luma_kernel(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
+                                                               x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x,
+                                                               size_t n_rows)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_rows) return;
+    const size_t tile = g >> 4, ty = tile / (size_t)tiles_x, tx = tile - ty * (size_t)tiles_x;
+    const int i = (int)(g & 15);
+    const x266_me_result_t *m = mv + (ty * 2 + (size_t)(i >> 3)) * (size_t)(2 * tiles_x) + tx * 2;
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(ref);
+    uint32_t out[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const x266_me_result_t r = m[h];
+        int sy = (int)(ty * 16) + i + r.mvy;
+        sy = sy < 0 ? 0 : (sy > height - 1 ? height - 1 : sy);
+        const uint8_t *row = src + (size_t)(sy >> 4) * (size_t)tiles_x * 512 + (sy & 15) * 16;
+        const int sx = (int)(tx * 16) + 8 * h + r.mvx;
+        if (sx >= 0 && sx + 7 <= width - 1) {
+            const int xa = sx & ~3, xc = xa + 8 < width ? xa + 8 : xa + 4;     // the third dword is unused when sx is aligned
+            const uint32_t d0 = *reinterpret_cast<const uint32_t *>(row + (size_t)(xa >> 4) * 512 + (xa & 15));
+            const uint32_t d1 = *reinterpret_cast<const uint32_t *>(row + (size_t)((xa + 4) >> 4) * 512 + ((xa + 4) & 15));
+            const uint32_t d2 = *reinterpret_cast<const uint32_t *>(row + (size_t)(xc >> 4) * 512 + (xc & 15));
+            const int sh = (sx & 3) * 8;
+            out[2 * h] = __builtin_amdgcn_alignbit(d1, d0, sh);
+            out[2 * h + 1] = __builtin_amdgcn_alignbit(d2, d1, sh);
+        } else {
+            out[2 * h] = out[2 * h + 1] = 0;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                int x = sx + b;
+                x = x < 0 ? 0 : (x > width - 1 ? width - 1 : x);
+                out[2 * h + (b >> 2)] |= (uint32_t)row[(size_t)(x >> 4) * 512 + (x & 15)] << (8 * (b & 3));
+            }
+        }
+    }
+    store16_sc1nt(reinterpret_cast<uint8_t *>(pred + tile) + i * 16, v4i{(int)out[0], (int)out[1], (int)out[2], (int)out[3]});
+}
+
 }  // namespace
 
 // Units per wave, measured (tools/probes/gpu_tilefmt_probe.py, 32768^2 frame): unpacking gains 13 % from two units per wave (its planar
@@ -428,6 +473,18 @@ hipError_t launch_recon_chroma(int block_edge, const x266_ref_block_t *d_pred, c
     dim3 grid((unsigned)n_units), block(kThreads);
     if (block_edge == 32) hipLaunchKernelGGL(recon_chroma_kernel<5>, grid, block, kLdsPerWorkgroup, stream, d_pred, d_res_u, d_res_v, block_pitch, d_recon, tiles_x, groups_x, n_units);
     else                  hipLaunchKernelGGL(recon_chroma_kernel<3>, grid, block, kLdsPerWorkgroup, stream, d_pred, d_res_u, d_res_v, block_pitch, d_recon, tiles_x, groups_x, n_units);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_comp_luma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
+                                   int width, int height, hipStream_t stream)
+{
+    const int tiles_x = width / 16;
+    const size_t n_rows = (size_t)tiles_x * (size_t)(height / 16) * 16;     // one lane per 16-byte output row
+    if (n_rows == 0) return hipSuccess;
+    const size_t wgs = (n_rows + 255) / 256;
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(motion_comp_luma_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_ref, d_mv, d_pred, width, height, tiles_x, n_rows);
     return hipGetLastError();
 }
 

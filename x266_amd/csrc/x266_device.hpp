@@ -170,10 +170,10 @@ hipError_t launch_satd8x8(const int16_t *d_diff, uint32_t *d_out, size_t n_block
                           const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_satd_search(const uint8_t *d_cur, long long cur_stride, const uint8_t *d_ref, long long ref_stride,
                                int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
-                               int tile_rows, uint32_t *d_coef_scratch, int cu_count, hipStream_t stream);
+                               int tile_rows, uint32_t *d_coef_scratch, int cu_count, bool tiled, hipStream_t stream);
 hipError_t launch_sad_search(const uint8_t *d_cur, long long cur_stride, const uint8_t *d_ref, long long ref_stride,
                               int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
-                              int tile_rows, hipStream_t stream);
+                              int tile_rows, bool tiled, hipStream_t stream);
 hipError_t launch_sad(int edge, const uint8_t *d_a, const uint8_t *d_b, uint32_t *d_out, size_t n_blocks, int waves_per_wg, int lds_per_wg, hipStream_t stream);
 hipError_t launch_tile_convert(bool pack, x266_ref_block_t *d_tiles, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v,
                                long long strd_y, long long strd_c, int width, int height, hipStream_t stream);
@@ -195,6 +195,8 @@ hipError_t launch_dct32_inv_to_tiles(const int16_t *d_coef, const x266_ref_block
                                      const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_dct32_inv_ctu_to_tiles(const int16_t *d_coef, const x266_ref_block_t *d_pred, x266_ref_block_t *d_recon, int width, int height,
                                          const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream);
+hipError_t launch_motion_comp_luma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
+                                   int width, int height, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

@@ -1143,7 +1143,7 @@ int xSatd8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_strid
     d_me_coef = slot->p;
     (void)hipGetLastError();
     hipError_t e = launch_satd_search(d_cur, (long long)cur_stride, d_ref, (long long)ref_stride, width, height, range,
-                                      d_best, d_costs, ctx->me_tile_rows, d_me_coef, ctx->prop.multiProcessorCount, (hipStream_t)stream);
+                                      d_best, d_costs, ctx->me_tile_rows, d_me_coef, ctx->prop.multiProcessorCount, false, (hipStream_t)stream);
     if (e == hipSuccess && slot->last_use && !slot->capturing_now) (void)hipEventRecord(slot->last_use, (hipStream_t)stream);   // what an eviction waits for
     if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "search launch", e);
     return X266HIP_OK;
@@ -1162,8 +1162,76 @@ int xSad8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_stride
     if (((uintptr_t)d_best & 7u) || ((uintptr_t)d_costs & 3u)) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: unaligned output");
     X_DEV(ctx);
     hipError_t e = launch_sad_search(d_cur, (long long)cur_stride, d_ref, (long long)ref_stride, width, height, range,
-                                     d_best, d_costs, ctx->me_tile_rows, (hipStream_t)stream);
+                                     d_best, d_costs, ctx->me_tile_rows, false, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAD search launch", e);
+    return X266HIP_OK;
+}
+
+// ---- motion search and compensation on tiled frames ---------------------------------------------------------------------------
+// The searches' arguments: "" when they are valid, else what is wrong.  The inputs are read-only, so d_cur == d_ref is fine; the
+// outputs must not overlap either input frame, and the cost map's size must neither wrap size_t nor run past the address space.
+static const char *search_tiles_args(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height, int range,
+                                     const x266_me_result_t *d_best, const uint32_t *d_costs)
+{
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return "width/height must be multiples of 16";
+    if (range < 1 || range > 64) return "range must be 1..64";
+    if (!d_cur || !d_ref || !d_best) return "NULL buffer";
+    if ((((uintptr_t)d_cur | (uintptr_t)d_ref) & 15u) || ((uintptr_t)d_best & 7u) || ((uintptr_t)d_costs & 3u)) return "unaligned buffer";
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_blocks = (size_t)(width / 8) * (size_t)(height / 8);
+    const size_t span = (size_t)(2 * range + 1);
+    size_t cost_bytes = 0;
+    uintptr_t end = 0;
+    if (d_costs && (__builtin_mul_overflow(n_blocks, span * span * 4, &cost_bytes) || __builtin_add_overflow((uintptr_t)d_costs, cost_bytes, &end)))
+        return "the cost map does not fit in the address space";
+    if (ranges_overlap(d_best, n_blocks * 8, d_cur, tile_bytes) || ranges_overlap(d_best, n_blocks * 8, d_ref, tile_bytes) ||
+        ranges_overlap(d_costs, cost_bytes, d_cur, tile_bytes) || ranges_overlap(d_costs, cost_bytes, d_ref, tile_bytes))
+        return "d_best / d_costs overlaps an input frame";
+    return "";
+}
+
+int xSatd8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
+                               int range, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = search_tiles_args(d_cur, d_ref, width, height, range, d_best, d_costs); *why)
+        return fail(ctx, X266HIP_EINVAL, (std::string("xSatd8x8SearchFromTilesDev: ") + why).c_str());
+    X_DEV(ctx);
+    x266hip_ctx::MeScratch *slot = nullptr;
+    if (const int rc = me_scratch_for(ctx, (hipStream_t)stream, width, height, &slot)) return rc;
+    (void)hipGetLastError();
+    hipError_t e = launch_satd_search(reinterpret_cast<const uint8_t *>(d_cur), 0, reinterpret_cast<const uint8_t *>(d_ref), 0, width, height,
+                                      range, d_best, d_costs, ctx->me_tile_rows, slot->p, ctx->prop.multiProcessorCount, true, (hipStream_t)stream);
+    if (e == hipSuccess && slot->last_use && !slot->capturing_now) (void)hipEventRecord(slot->last_use, (hipStream_t)stream);   // what an eviction waits for
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "search launch", e);
+    return X266HIP_OK;
+}
+
+int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
+                              int range, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = search_tiles_args(d_cur, d_ref, width, height, range, d_best, d_costs); *why)
+        return fail(ctx, X266HIP_EINVAL, (std::string("xSad8x8SearchFromTilesDev: ") + why).c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_sad_search(reinterpret_cast<const uint8_t *>(d_cur), 0, reinterpret_cast<const uint8_t *>(d_ref), 0, width, height,
+                                     range, d_best, d_costs, ctx->me_tile_rows, true, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAD search launch", e);
+    return X266HIP_OK;
+}
+
+int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
+                       x266_ref_block_t *d_pred, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return fail(ctx, X266HIP_EINVAL, "xMotionCompLumaDev: width/height must be multiples of 16");
+    if (!d_ref || !d_mv || !d_pred || ((((uintptr_t)d_ref | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_mv & 7u))
+        return fail(ctx, X266HIP_EINVAL, "xMotionCompLumaDev: NULL or unaligned buffer");
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
+    if (ranges_overlap(d_pred, tile_bytes, d_ref, tile_bytes) || ranges_overlap(d_pred, tile_bytes, d_mv, mv_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xMotionCompLumaDev: d_pred overlaps d_ref or d_mv");
+    X_DEV(ctx);
+    hipError_t e = launch_motion_comp_luma(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "motion compensation launch", e);
     return X266HIP_OK;
 }
 
