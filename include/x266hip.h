@@ -163,8 +163,8 @@ int xTransformFwdBatchDev(x266hip_ctx *ctx, int type, int size, const int16_t *d
  * src/mkDct32.bsv:132-141, 385-387).  slot 0 / 1 = the "DCT-II" / "DST-VII" slot of the type codes above,
  * size in {4, 8, 16}; m[k*size + n], row k = basis function, int8 (any values: the kernels only need the int8
  * operand images rebuilt); m == NULL restores the built-in matrix.  Affects every entry point of the set --
- * forward, inverse (which applies the transposes, columns first), the per-class and the one-launch calls --
- * of THIS context from the next call on.  Synchronises the device (launches in flight read the old tables);
+ * forward, inverse (which applies the transposes, columns first), the per-class and the one-launch calls, and the CTU calls on
+ * tiled frames xTransformCtuFromTilesDev / xTransformCtuToTilesDev -- of THIS context from the next call on.  Synchronises the device (launches in flight read the old tables);
  * not to be called concurrently with other calls on the context.  The 32-point DCT-II cannot be replaced. */
 int xTransformSetMatrix(x266hip_ctx *ctx, int slot, int size, const int8_t *m);
 int xTransformGetMatrix(const x266hip_ctx *ctx, int slot, int size, int8_t *m);
@@ -314,6 +314,34 @@ int xDct32InvToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_
  * xReconLumaDev(.., 32, ..) and xReconChromaDev(.., 32, ..).  width, height multiples of 64. */
 int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
                            x266_ref_block_t *d_recon, void *stream);
+/* The mixed transform set (xTransformTilesDev) per CTU, straight from and into tiled frames of any size.
+ * Frame: width, height positive multiples of 16; ceil(width / 64) x ceil(height / 64) CTUs of 64x64 in raster order, the right
+ * and bottom ones possibly cut by the frame edge.  Each CTU has six 32x32 regions q = 0..5: q = 0..3 its luma quadrants
+ * (top-left, top-right, bottom-left, bottom-right), q = 4 its 32x32 U and q = 5 its 32x32 V samples (m_C of its 4x4 tiles) --
+ * the order and the 12 KiB-per-CTU layout of xDct32FwdCtuFromTilesDev.  Region q of CTU b has the class d_class[6b + q],
+ * read as xTransformTilesDev reads its class bytes (X266_TILE_CLASS(type, size), low four bits; size 32 is always the 32-point
+ * DCT-II) and cut into (32/N)^2 blocks of N x N, block-major, blocks in raster order inside the region: xTransformTilesDev's
+ * tile layout, so the forward call's d_coef is the input of xTransformTilesDev(1, .., d_class) or of xTransformCtuToTilesDev.
+ * Frame edge: samples outside the frame count as residual 0 forward, their inverse outputs are discarded.  A region wholly
+ * outside the frame (Y2 / Y3 of the last CTU row at 4320p) gets all-zero coefficients; its slot is still written.  A class
+ * whose N divides the region's in-frame extent keeps every block wholly inside or wholly outside the frame -- luma N <= 16 on
+ * the 16-row / 16-column strips, chroma N <= 16 on 16-row and N <= 8 on 8- and 24-row strips, the classes an encoder uses
+ * there; larger classes give defined output too, and no class byte is checked.
+ * Forward: d_coef[b * 6144 + q * 1024 ..] for every region of every CTU (12 KiB per CTU), bit-identical to forming the
+ * CTU-ordered residual cur - pred (int16, zero outside the frame, block-major per region class) and running
+ * xTransformTilesDev(0, .., d_class) on it.  Inverse: m_Y and m_C of d_recon = clamp(pred + inverse_class(coef), 0, 255) at
+ * every in-frame sample, exact for every int16 coefficient (the set's int16 clipping after each pass); m_I is never written.
+ * With every class (DCT-II, 32) on a frame whose sides are multiples of 64 the two calls are bit-identical to
+ * xDct32FwdCtuFromTilesDev and xDct32InvCtuToTilesDev.
+ * Tile and coefficient buffers 16-byte aligned, d_class any alignment.  X266HIP_EINVAL for a bad size, a NULL or unaligned buffer,
+ * a buffer whose span does not fit in the address space, or an output overlapping an input -- d_recon == d_pred is allowed, as
+ * in the recon calls, and so is d_cur == d_pred (both read-only); X266HIP_EDEVICE when the context's transform tables are
+ * invalid.  Neither call allocates: both can be captured into a graph. */
+int xTransformCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
+                              int width, int height, const uint8_t *d_class, int16_t *d_coef, void *stream);
+int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8_t *d_class,
+                            const x266_ref_block_t *d_pred, int width, int height,
+                            x266_ref_block_t *d_recon, void *stream);
 /* Inter prediction on tiled frames (no upstream counterpart: upstream keeps its references as tiled frames, codec_t.m_frames[],
  * src/x266.cpp:96-102, but has no search or compensation for them).  Edge convention of every call below: a reference sample
  * outside the frame takes the nearest in-frame sample, ref[clamp(y, 0, H-1)][clamp(x, 0, W-1)] -- edge replication on all four

@@ -103,6 +103,8 @@ def load_library(path=None):
     for name in ("xSatd8x8SearchFromTilesDev", "xSad8x8SearchFromTilesDev"):
         getattr(L, name).argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xMotionCompLumaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
+    L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     for name in ("xDct32FwdBatch", "xDct32InvBatch", "xSatd8x8Batch"):
         getattr(L, name).argtypes = [_P, _P, _P, _SZ]
     L.xHipMalloc.argtypes = [_P, ctypes.POINTER(_P), _SZ]
@@ -574,6 +576,51 @@ class Codec:
         self.motion_comp_luma_dev(dr.ptr, dm.ptr, w, h, dp.ptr)
         self.stream_sync()
         return dp.download(np.uint8, pred.size)
+
+    def transform_ctu_from_tiles_dev(self, d_cur, d_pred, w, h, d_class, d_coef, stream=0):
+        self._check(self.L.xTransformCtuFromTilesDev(self.ctx, d_cur, d_pred, w, h, d_class, d_coef, stream), "xTransformCtuFromTilesDev")
+
+    def transform_ctu_to_tiles_dev(self, d_coef, d_class, d_pred, w, h, d_recon, stream=0):
+        self._check(self.L.xTransformCtuToTilesDev(self.ctx, d_coef, d_class, d_pred, w, h, d_recon, stream), "xTransformCtuToTilesDev")
+
+    @staticmethod
+    def ctu_count(w, h):
+        """CTUs of 64x64 that cover a w x h frame (the right and bottom ones possibly cut)"""
+        return ((w + 63) // 64) * ((h + 63) // 64)
+
+    def transform_ctu_from_tiles(self, cur_tiles, pred_tiles, w, h, classes):
+        """numpy convenience around xTransformCtuFromTilesDev: two tile arrays of a w x h frame (uint8, 512 bytes per tile) and
+        6 class bytes per CTU -> coefficients [n_ctus, 6, 1024] int16 (Y0 Y1 Y2 Y3 U V, each block-major for its class)."""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
+        cls = np.ascontiguousarray(classes, np.uint8).ravel()
+        n = self.ctu_count(w, h)
+        assert cur.size == w * h * 2 and pred.size == w * h * 2 and cls.size == 6 * n
+        dc, dp, dk, dz = self.alloc(cur.nbytes), self.alloc(pred.nbytes), self.alloc(max(cls.nbytes, 16)), self.alloc(n * 12288)
+        dc.upload(cur)
+        dp.upload(pred)
+        dk.upload(cls)
+        self.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr, dz.ptr)
+        self.stream_sync()
+        return dz.download(np.int16, n * 6144).reshape(n, 6, 1024)
+
+    def transform_ctu_to_tiles(self, coef, classes, pred_tiles, w, h, base=None):
+        """numpy convenience around xTransformCtuToTilesDev: coefficients [n_ctus, 6, 1024] int16, their class bytes and the pred
+        tile array -> the reconstructed tile array; m_I (never written) comes from `base` (a tile array; None: pred's)."""
+        n = self.ctu_count(w, h)
+        z = np.ascontiguousarray(coef, np.int16).ravel()
+        cls = np.ascontiguousarray(classes, np.uint8).ravel()
+        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
+        assert z.size == n * 6144 and cls.size == 6 * n and pred.size == w * h * 2
+        out = pred if base is None else np.ascontiguousarray(base, np.uint8).ravel()
+        dz, dk, dp, dr = self.alloc(z.nbytes), self.alloc(max(cls.nbytes, 16)), self.alloc(pred.nbytes), self.alloc(out.nbytes)
+        dz.upload(z)
+        dk.upload(cls)
+        dp.upload(pred)
+        dr.upload(out)
+        self.transform_ctu_to_tiles_dev(dz.ptr, dk.ptr, dp.ptr, w, h, dr.ptr)
+        self.stream_sync()
+        return dr.download(np.uint8, out.size)
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

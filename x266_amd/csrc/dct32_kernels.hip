@@ -41,6 +41,7 @@
 
 #include <cstdint>
 
+#include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 #include "x266_mfma_blocks.hpp"
 #include "x266_tables.hpp"
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(256) void dct32_chroma_from_tiles_kernel(const x266
     if (ctu >= n_ctus) return;
     const unsigned c = lane & 31, h = lane >> 5;
     const size_t cy = ctu / ctus_x, cx = ctu - cy * ctus_x;
-    const size_t tile = (cy * 4 + (c >> 3)) * (size_t)tiles_x + cx * 4 + 2 * h;
+    const size_t tile = ctu_chroma_tile(cy, cx, c, h, tiles_x);
     const unsigned char *pc = reinterpret_cast<const unsigned char *>(cur + tile) + 256 + (c & 7) * 16;
     const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred + tile) + 256 + (c & 7) * 16;
     const v4i a0 = load16<true>(pc), a1 = load16<true>(pc + 512), b0 = load16<true>(pp), b1 = load16<true>(pp + 512);
@@ -441,9 +442,9 @@ __global__ __launch_bounds__(256) void dct32_ctu_from_tiles_kernel(const x266_re
     char *dst = reinterpret_cast<char *>(out + ctu * 6144) + lane * 16;
     if (part < 4) {
         // luma quadrant (part >> 1, part & 1): row c of the quadrant, columns 16h .. 16h+15 = one 16-byte luma row of one tile
-        const size_t tile = (cy * 4 + (part >> 1) * 2 + (c >> 4)) * (size_t)tiles_x + cx * 4 + (part & 1) * 2 + h;
-        const v4i a = load16<true>(reinterpret_cast<const unsigned char *>(cur + tile) + (c & 15) * 16);
-        const v4i b = load16<true>(reinterpret_cast<const unsigned char *>(pred + tile) + (c & 15) * 16);
+        const size_t tile = ctu_luma_tile(cy, cx, part, c, h, tiles_x);
+        const v4i a = load16<true>(reinterpret_cast<const unsigned char *>(cur + tile) + ctu_luma_row_offset(c));
+        const v4i b = load16<true>(reinterpret_cast<const unsigned char *>(pred + tile) + ctu_luma_row_offset(c));
         const v4i bias = {(int)S, (int)S, (int)S, (int)S};
         v16i acc = mfma(a ^ bias, k.p1, round1);
         acc = mfma(b ^ bias, k.tr, acc);
@@ -458,7 +459,7 @@ __global__ __launch_bounds__(256) void dct32_ctu_from_tiles_kernel(const x266_re
         store16_sc1nt(dst + part * 2048 + 1024, s1);
         return;
     }
-    const size_t tile = (cy * 4 + (c >> 3)) * (size_t)tiles_x + cx * 4 + 2 * h;
+    const size_t tile = ctu_chroma_tile(cy, cx, c, h, tiles_x);
     const unsigned char *pc = reinterpret_cast<const unsigned char *>(cur + tile) + 256 + (c & 7) * 16;
     const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred + tile) + 256 + (c & 7) * 16;
     const v4i a0 = load16<true>(pc), a1 = load16<true>(pc + 512), b0 = load16<true>(pp), b1 = load16<true>(pp + 512);
@@ -605,7 +606,7 @@ __global__ __launch_bounds__(256) void dct32_inv_ctu_to_tiles_kernel(const int16
     };
     if (part < 4) {
         const v4i g0 = load16<true>(src + part * 2048), g1 = load16<true>(src + part * 2048 + 1024);
-        const size_t tile = (cy * 4 + (part >> 1) * 2 + (c >> 4)) * (size_t)tiles_x + cx * 4 + (part & 1) * 2 + h;
+        const size_t tile = ctu_luma_tile(cy, cx, part, c, h, tiles_x);
         const size_t off = tile * sizeof(x266_ref_block_t) + (c & 15) * 16;
         const v4i p = load16<true>(reinterpret_cast<const unsigned char *>(pred) + off);
         v4i o0, o1;
@@ -615,7 +616,7 @@ __global__ __launch_bounds__(256) void dct32_inv_ctu_to_tiles_kernel(const int16
     }
     const v4i u0 = load16<true>(src + 4 * 2048), u1 = load16<true>(src + 4 * 2048 + 1024);
     const v4i v0 = load16<true>(src + 5 * 2048), v1 = load16<true>(src + 5 * 2048 + 1024);
-    const size_t tile = (cy * 4 + (c >> 3)) * (size_t)tiles_x + cx * 4 + 2 * h;
+    const size_t tile = ctu_chroma_tile(cy, cx, c, h, tiles_x);
     const size_t off = tile * sizeof(x266_ref_block_t) + 256 + (c & 7) * 16;
     const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred) + off;
     const v4i p0 = load16<true>(pp), p1 = load16<true>(pp + 512);          // tiles 2h and 2h + 1 of the CTU's tile row

@@ -19,6 +19,7 @@
 
 #include <cstdint>
 
+#include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 #include "x266_mfma_blocks.hpp"
 #include "x266_tables.hpp"
@@ -492,6 +493,304 @@ __global__ __launch_bounds__(256) void tr_tiles_kernel(const int16_t *__restrict
     tr_tiles_body<INVERSE>(stage, wave, in, out, n_tiles, tile_offsets, tile_class, T, tiles_per_wave, lds_per_wave);
 }
 
+// ---- the mixed set straight from and into tiled frames, one CTU per wave ----------------------------------------------------
+// A 64x64 CTU is six 32x32 regions (Y0 Y1 Y2 Y3 U V, x266_ctu_tiles.hpp), each of the class its byte names; the coefficient stream
+// is 12 KiB per CTU in the tile layout of tr_tiles_kernel, so the same tile_of_class runs on the same slot contents.  Lane (c, h)
+// holds row c, columns 16h .. 16h+15 of a region, and in the block-major layout of every class those 16 samples are whole
+// runs: one 32-byte run (N = 32, 16), two of 16 bytes (N = 8) or four of 8 bytes (N = 4) -- exactly the fragment pieces
+// fwd_tile_in_slot reads.  One wave per CTU: the 2 KiB table copy serves six regions instead of tr_tiles_kernel's two.
+// Frames of any size that is a multiple of 16: lanes whose tile lies outside the frame load nothing and stand for residual 0
+// (forward) or store nothing (inverse); a region wholly outside gets zero coefficients without a transform.
+
+// byte offset in a region's block-major layout of run p of lane (c, h)'s row segment (N = 1 << LOGN, 16 / N runs for N < 16)
+template <int LOGN>
+__device__ __forceinline__ unsigned segment_run(unsigned c, unsigned h, unsigned p)
+{
+    constexpr unsigned N = 1u << LOGN;
+    const unsigned sb = (c >> LOGN) * (32u >> LOGN) + ((16u * h + p * N) >> LOGN);
+    return (sb * N * N + (c & (N - 1)) * N + (LOGN == 5 ? 16u * h : 0u)) * 2u;
+}
+
+// d = 16 int16 samples of the row segment as pairs, in column order
+template <int LOGN>
+__device__ __forceinline__ void put_segment_of(unsigned char *slot, unsigned c, unsigned h, const uint32_t (&d)[8])
+{
+    if constexpr (LOGN >= 4) {
+        unsigned char *p = slot + segment_run<LOGN>(c, h, 0);
+        *reinterpret_cast<v4i *>(p) = v4i{(int)d[0], (int)d[1], (int)d[2], (int)d[3]};
+        *reinterpret_cast<v4i *>(p + 16) = v4i{(int)d[4], (int)d[5], (int)d[6], (int)d[7]};
+    } else if constexpr (LOGN == 3) {
+#pragma unroll
+        for (unsigned p = 0; p < 2; ++p)
+            *reinterpret_cast<v4i *>(slot + segment_run<3>(c, h, p)) = v4i{(int)d[4 * p], (int)d[4 * p + 1], (int)d[4 * p + 2], (int)d[4 * p + 3]};
+    } else {
+#pragma unroll
+        for (unsigned p = 0; p < 4; ++p) *reinterpret_cast<uint2 *>(slot + segment_run<2>(c, h, p)) = make_uint2(d[2 * p], d[2 * p + 1]);
+    }
+}
+
+template <int LOGN>
+__device__ __forceinline__ void get_segment_of(const unsigned char *slot, unsigned c, unsigned h, uint32_t (&d)[8])
+{
+    if constexpr (LOGN >= 4) {
+        const unsigned char *p = slot + segment_run<LOGN>(c, h, 0);
+        const v4i a = *reinterpret_cast<const v4i *>(p), b = *reinterpret_cast<const v4i *>(p + 16);
+        d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; d[3] = a[3]; d[4] = b[0]; d[5] = b[1]; d[6] = b[2]; d[7] = b[3];
+    } else if constexpr (LOGN == 3) {
+#pragma unroll
+        for (unsigned p = 0; p < 2; ++p) {
+            const v4i a = *reinterpret_cast<const v4i *>(slot + segment_run<3>(c, h, p));
+            d[4 * p] = a[0]; d[4 * p + 1] = a[1]; d[4 * p + 2] = a[2]; d[4 * p + 3] = a[3];
+        }
+    } else {
+#pragma unroll
+        for (unsigned p = 0; p < 4; ++p) {
+            const uint2 a = *reinterpret_cast<const uint2 *>(slot + segment_run<2>(c, h, p));
+            d[2 * p] = a.x; d[2 * p + 1] = a.y;
+        }
+    }
+}
+
+// the class is wave-uniform: one branch per region
+__device__ __forceinline__ void put_segment(unsigned char *slot, int cls, unsigned c, unsigned h, const uint32_t (&d)[8])
+{
+    switch (cls & 3) {
+    case 0: put_segment_of<2>(slot, c, h, d); break;
+    case 1: put_segment_of<3>(slot, c, h, d); break;
+    case 2: put_segment_of<4>(slot, c, h, d); break;
+    default: put_segment_of<5>(slot, c, h, d); break;
+    }
+}
+
+__device__ __forceinline__ void get_segment(const unsigned char *slot, int cls, unsigned c, unsigned h, uint32_t (&d)[8])
+{
+    switch (cls & 3) {
+    case 0: get_segment_of<2>(slot, c, h, d); break;
+    case 1: get_segment_of<3>(slot, c, h, d); break;
+    case 2: get_segment_of<4>(slot, c, h, d); break;
+    default: get_segment_of<5>(slot, c, h, d); break;
+    }
+}
+
+typedef short v2s __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t sub_pairs(uint32_t x, uint32_t z)    // two 9-bit residuals, v_pk_sub_i16
+{
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2s, x) - __builtin_bit_cast(v2s, z));
+}
+
+// 16 luma residuals of one tile row: cur - pred, pixel order
+__device__ __forceinline__ void luma_residual16(const v4i &a, const v4i &b, uint32_t (&d)[8])
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t x = (uint32_t)a[q], z = (uint32_t)b[q];
+        d[2 * q] = sub_pairs(bperm(0u, x, 0x0c010c00u), bperm(0u, z, 0x0c010c00u));
+        d[2 * q + 1] = sub_pairs(bperm(0u, x, 0x0c030c02u), bperm(0u, z, 0x0c030c02u));
+    }
+}
+
+// 8 U and 8 V residuals of one m_C row (u v u v ...): even bytes U, odd bytes V
+__device__ __forceinline__ void chroma_residual8(const v4i &a, const v4i &b, uint32_t *du, uint32_t *dv)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t x = (uint32_t)a[q], z = (uint32_t)b[q];
+        du[q] = sub_pairs(x & 0x00FF00FFu, z & 0x00FF00FFu);
+        dv[q] = sub_pairs((x >> 8) & 0x00FF00FFu, (z >> 8) & 0x00FF00FFu);
+    }
+}
+
+struct CtuPlace {
+    size_t cy, cx;
+    int tiles_x, tiles_y;
+    __device__ bool luma_in(unsigned part) const { return ctu_luma_tile_col(cx, part, 0) < (size_t)tiles_x && ctu_luma_tile_row(cy, part, 0) < (size_t)tiles_y; }
+};
+
+// the wave's LDS copy of the TileTab (2 KiB): two 16-byte loads per lane
+__device__ __forceinline__ void copy_table(unsigned char *tab, const TileTab *__restrict__ T, int lane)
+{
+    const char *src = reinterpret_cast<const char *>(T->b) + lane * 16;
+    const v4i q0 = *reinterpret_cast<const v4i *>(src), q1 = *reinterpret_cast<const v4i *>(src + 1024);
+    *reinterpret_cast<v4i *>(tab + lane * 16) = q0;
+    *reinterpret_cast<v4i *>(tab + 1024 + lane * 16) = q1;
+}
+
+// forward: slot holds region q's residual (block-major for its class) -> its 2 KiB of coefficients at dst, 1 KiB-linear
+__device__ __forceinline__ void fwd_region_out(unsigned char *slot, const unsigned char *tab, int lane, int cls, char *dst)
+{
+    tile_of_class<false>(slot, tab, lane, cls);
+    __builtin_amdgcn_wave_barrier();
+    const v4i s0 = *reinterpret_cast<const v4i *>(slot + lane * 16);
+    const v4i s1 = *reinterpret_cast<const v4i *>(slot + 1024 + lane * 16);
+    store16_sc1nt(dst, s0);
+    store16_sc1nt(dst + 1024, s1);
+}
+
+__device__ __forceinline__ void zero_region_out(char *dst)
+{
+    const v4i z = {0, 0, 0, 0};
+    store16_sc1nt(dst, z);
+    store16_sc1nt(dst + 1024, z);
+}
+
+// LDS per wave: table 2 KiB + two region slots of 2 KiB; the six regions go through the slots in pairs (Y0 Y1, Y2 Y3, U V).
+__global__ __launch_bounds__(256) void tr_ctu_from_tiles_kernel(const x266_ref_block_t *__restrict__ cur, const x266_ref_block_t *__restrict__ pred,
+                                                                const uint8_t *__restrict__ ctu_class, int16_t *__restrict__ out,
+                                                                const TileTab *__restrict__ T, int ctus_x, int tiles_x, int tiles_y,
+                                                                size_t n_ctus, unsigned lds_per_wave)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    const int lane = threadIdx.x & 63;
+    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    unsigned char *tab = stage + wave_in_wg * lds_per_wave;
+    unsigned char *slot[2] = {tab + 2048, tab + 4096};
+    const size_t ctu = (size_t)blockIdx.x * (blockDim.x >> 6) + wave_in_wg;
+    if (ctu >= n_ctus) return;
+    const unsigned c = lane & 31, h = lane >> 5;
+    const CtuPlace at = {ctu / (size_t)ctus_x, ctu % (size_t)ctus_x, tiles_x, tiles_y};
+    copy_table(tab, T, lane);
+    // every load of the CTU up front: four luma rows and two m_C rows per frame and lane, none outside the frame
+    v4i a[4], b[4];
+#pragma unroll
+    for (unsigned q = 0; q < 4; ++q) {
+        a[q] = b[q] = v4i{0, 0, 0, 0};
+        if (ctu_luma_tile_row(at.cy, q, c) < (size_t)tiles_y && ctu_luma_tile_col(at.cx, q, h) < (size_t)tiles_x) {
+            const size_t off = ctu_luma_tile(at.cy, at.cx, q, c, h, tiles_x) * sizeof(x266_ref_block_t) + ctu_luma_row_offset(c);
+            a[q] = load16<true>(reinterpret_cast<const unsigned char *>(cur) + off);
+            b[q] = load16<true>(reinterpret_cast<const unsigned char *>(pred) + off);
+        }
+    }
+    v4i ca[2], cb[2];
+    const bool crow = ctu_chroma_tile_row(at.cy, c) < (size_t)tiles_y;
+    const size_t coff = ctu_chroma_tile(at.cy, at.cx, c, h, tiles_x) * sizeof(x266_ref_block_t) + ctu_chroma_row_offset(c);
+#pragma unroll
+    for (unsigned j = 0; j < 2; ++j) {
+        ca[j] = cb[j] = v4i{0, 0, 0, 0};
+        if (crow && ctu_chroma_tile_col(at.cx, h) + j < (size_t)tiles_x) {
+            ca[j] = load16<true>(reinterpret_cast<const unsigned char *>(cur) + coff + j * sizeof(x266_ref_block_t));
+            cb[j] = load16<true>(reinterpret_cast<const unsigned char *>(pred) + coff + j * sizeof(x266_ref_block_t));
+        }
+    }
+    char *dst = reinterpret_cast<char *>(out + ctu * 6144) + lane * 16;
+#pragma unroll
+    for (unsigned pair = 0; pair < 3; ++pair) {
+        const unsigned q0 = 2 * pair, q1 = 2 * pair + 1;
+        const int cls0 = tile_class_of(ctu_class, ctu * 6 + q0), cls1 = tile_class_of(ctu_class, ctu * 6 + q1);
+        const bool in0 = pair == 2 || at.luma_in(q0), in1 = pair == 2 || at.luma_in(q1);   // wave-uniform; chroma is never wholly outside
+        __builtin_amdgcn_wave_barrier();                                   // the previous pair has left the slots
+        uint32_t d0[8], d1[8];
+        if (pair < 2) {
+            luma_residual16(a[q0], b[q0], d0);
+            luma_residual16(a[q1], b[q1], d1);
+        } else {
+            chroma_residual8(ca[0], cb[0], d0, d1);
+            chroma_residual8(ca[1], cb[1], d0 + 4, d1 + 4);
+        }
+        if (in0) put_segment(slot[0], cls0, c, h, d0);
+        if (in1) put_segment(slot[1], cls1, c, h, d1);
+        __builtin_amdgcn_wave_barrier();
+        if (in0) fwd_region_out(slot[0], tab, lane, cls0, dst + q0 * 2048);
+        else     zero_region_out(dst + q0 * 2048);
+        if (in1) fwd_region_out(slot[1], tab, lane, cls1, dst + q1 * 2048);
+        else     zero_region_out(dst + q1 * 2048);
+    }
+}
+
+// inverse: region q's 2 KiB of coefficients (the lane's two 1 KiB-linear pieces) -> row segment d of the residual
+__device__ __forceinline__ void inv_region_segment(unsigned char *slot, const unsigned char *tab, int lane, int cls, const v4i &g0, const v4i &g1,
+                                                   uint32_t (&d)[8])
+{
+    *reinterpret_cast<v4i *>(slot + lane * 16) = g0;
+    *reinterpret_cast<v4i *>(slot + 1024 + lane * 16) = g1;
+    __builtin_amdgcn_wave_barrier();
+    tile_of_class<true>(slot, tab, lane, cls);
+    __builtin_amdgcn_wave_barrier();
+    get_segment(slot, cls, (unsigned)lane & 31u, (unsigned)lane >> 5, d);
+}
+
+// Loads: the coefficients of in-frame regions (1 KiB-linear), the pred rows of in-frame lanes; stores: m_Y / m_C rows of in-frame
+// lanes only.  pred and recon are not __restrict__ (recon == pred is allowed): every lane reads exactly the pred bytes it writes.
+__global__ __launch_bounds__(256) void tr_ctu_to_tiles_kernel(const int16_t *__restrict__ coef, const uint8_t *__restrict__ ctu_class,
+                                                              const x266_ref_block_t *pred, x266_ref_block_t *recon,
+                                                              const TileTab *__restrict__ T, int ctus_x, int tiles_x, int tiles_y,
+                                                              size_t n_ctus, unsigned lds_per_wave)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    const int lane = threadIdx.x & 63;
+    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    unsigned char *tab = stage + wave_in_wg * lds_per_wave;
+    unsigned char *slot[2] = {tab + 2048, tab + 4096};
+    const size_t ctu = (size_t)blockIdx.x * (blockDim.x >> 6) + wave_in_wg;
+    if (ctu >= n_ctus) return;
+    const unsigned c = lane & 31, h = lane >> 5;
+    const CtuPlace at = {ctu / (size_t)ctus_x, ctu % (size_t)ctus_x, tiles_x, tiles_y};
+    copy_table(tab, T, lane);
+    const char *src = reinterpret_cast<const char *>(coef + ctu * 6144) + lane * 16;
+    const unsigned char *pin = reinterpret_cast<const unsigned char *>(pred);
+    unsigned char *pout = reinterpret_cast<unsigned char *>(recon);
+    // every region's coefficients up front (wave-uniform: none for a region wholly outside the frame)
+    v4i g[6][2];
+#pragma unroll
+    for (unsigned q = 0; q < 6; ++q) {
+        g[q][0] = g[q][1] = v4i{0, 0, 0, 0};
+        if (q >= 4 || at.luma_in(q)) {
+            g[q][0] = load16<true>(src + q * 2048);
+            g[q][1] = load16<true>(src + q * 2048 + 1024);
+        }
+    }
+#pragma unroll
+    for (unsigned pair = 0; pair < 3; ++pair) {
+        const unsigned q0 = 2 * pair, q1 = 2 * pair + 1;
+        const int cls0 = tile_class_of(ctu_class, ctu * 6 + q0), cls1 = tile_class_of(ctu_class, ctu * 6 + q1);
+        const bool in0 = pair == 2 || at.luma_in(q0), in1 = pair == 2 || at.luma_in(q1);   // wave-uniform
+        const v4i g0 = g[q0][0], g1 = g[q0][1], g2 = g[q1][0], g3 = g[q1][1];
+        __builtin_amdgcn_wave_barrier();                                   // the previous pair has left the slots
+        if (pair < 2) {
+            size_t off[2];
+            bool live[2];
+            v4i p[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+            for (unsigned j = 0; j < 2; ++j) {
+                const unsigned q = q0 + j;
+                live[j] = ctu_luma_tile_row(at.cy, q, c) < (size_t)tiles_y && ctu_luma_tile_col(at.cx, q, h) < (size_t)tiles_x;
+                off[j] = ctu_luma_tile(at.cy, at.cx, q, c, h, tiles_x) * sizeof(x266_ref_block_t) + ctu_luma_row_offset(c);
+                if (live[j]) p[j] = load16<true>(pin + off[j]);
+            }
+            uint32_t d[8];
+            if (in0) {
+                inv_region_segment(slot[0], tab, lane, cls0, g0, g1, d);
+                if (live[0])
+                    store16_sc1nt(pout + off[0], recon_luma16(p[0], v4i{(int)d[0], (int)d[1], (int)d[2], (int)d[3]}, v4i{(int)d[4], (int)d[5], (int)d[6], (int)d[7]}));
+            }
+            if (in1) {
+                inv_region_segment(slot[1], tab, lane, cls1, g2, g3, d);
+                if (live[1])
+                    store16_sc1nt(pout + off[1], recon_luma16(p[1], v4i{(int)d[0], (int)d[1], (int)d[2], (int)d[3]}, v4i{(int)d[4], (int)d[5], (int)d[6], (int)d[7]}));
+            }
+        } else {
+            const bool crow = ctu_chroma_tile_row(at.cy, c) < (size_t)tiles_y;
+            const size_t coff = ctu_chroma_tile(at.cy, at.cx, c, h, tiles_x) * sizeof(x266_ref_block_t) + ctu_chroma_row_offset(c);
+            bool live[2];
+            v4i p[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+            for (unsigned j = 0; j < 2; ++j) {
+                live[j] = crow && ctu_chroma_tile_col(at.cx, h) + j < (size_t)tiles_x;
+                if (live[j]) p[j] = load16<true>(pin + coff + j * sizeof(x266_ref_block_t));
+            }
+            uint32_t du[8], dv[8];
+            inv_region_segment(slot[0], tab, lane, cls0, g0, g1, du);
+            inv_region_segment(slot[1], tab, lane, cls1, g2, g3, dv);
+#pragma unroll
+            for (unsigned j = 0; j < 2; ++j)
+                if (live[j])
+                    store16_sc1nt(pout + coff + j * sizeof(x266_ref_block_t),
+                                  recon_chroma16(p[j], v4i{(int)du[4 * j], (int)du[4 * j + 1], (int)du[4 * j + 2], (int)du[4 * j + 3]},
+                                                 v4i{(int)dv[4 * j], (int)dv[4 * j + 1], (int)dv[4 * j + 2], (int)dv[4 * j + 3]}));
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_transform_small(int log2n, const int16_t *d_in, int16_t *d_out, size_t n_blocks, const DctOps *d_ops,
@@ -551,6 +850,28 @@ hipError_t launch_transform_tiles(bool inverse, const int16_t *d_in, int16_t *d_
 #define X266_TT(INV) hipLaunchKernelGGL((tr_tiles_kernel<INV>), grid, block, lds, stream, d_in, d_out, n_tiles, d_tile_offsets, d_tile_class, d_tab, tpw, per_wave)
     if (inverse) X266_TT(true); else X266_TT(false);
 #undef X266_TT
+    return hipGetLastError();
+}
+
+// one wave per CTU of ceil(width / 64) x ceil(height / 64); width, height multiples of 16
+hipError_t launch_transform_ctu_tiles(bool inverse, const x266_ref_block_t *d_cur, const int16_t *d_coef_in, const x266_ref_block_t *d_pred,
+                                      const uint8_t *d_class, int16_t *d_coef_out, x266_ref_block_t *d_recon, int width, int height,
+                                      const TileTab *d_tab, const LaunchCfg &cfg, hipStream_t stream)
+{
+    const int ctus_x = (width + 63) / 64;
+    const size_t n_ctus = (size_t)ctus_x * (size_t)((height + 63) / 64);
+    if (n_ctus == 0) return hipSuccess;
+    const unsigned tpb = (unsigned)cfg.wg_threads;
+    const size_t wpw = tpb / 64, wgs = (n_ctus + wpw - 1) / wpw;
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const unsigned per_wave = (unsigned)(cfg.lds_bytes_per_wave < 6144 ? 6144 : (cfg.lds_bytes_per_wave + 15) & ~15);   // table + two region slots, then padding
+    const size_t lds = wpw * (size_t)per_wave;
+    if (inverse)
+        hipLaunchKernelGGL(tr_ctu_to_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_coef_in, d_class, d_pred, d_recon, d_tab,
+                           ctus_x, width / 16, height / 16, n_ctus, per_wave);
+    else
+        hipLaunchKernelGGL(tr_ctu_from_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_cur, d_pred, d_class, d_coef_out, d_tab,
+                           ctus_x, width / 16, height / 16, n_ctus, per_wave);
     return hipGetLastError();
 }
 

@@ -150,6 +150,9 @@ hipError_t launch_intra32_costs(const x266_intra_ref_t *d_refs, const uint8_t *d
 hipError_t launch_satd8x8_butterfly(const int16_t *d_diff, uint32_t *d_out, size_t n_blocks, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_transform_tiles(bool inverse, const int16_t *d_in, int16_t *d_out, size_t n_tiles, const uint32_t *d_tile_offsets,
                                   const uint8_t *d_tile_class, const TileTab *d_tab, const LaunchCfg &cfg, hipStream_t stream);
+hipError_t launch_transform_ctu_tiles(bool inverse, const x266_ref_block_t *d_cur, const int16_t *d_coef_in, const x266_ref_block_t *d_pred,
+                                      const uint8_t *d_class, int16_t *d_coef_out, x266_ref_block_t *d_recon, int width, int height,
+                                      const TileTab *d_tab, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_dct32_butterfly(const int16_t *d_in, int16_t *d_out, size_t n_blocks, hipStream_t stream);
 hipError_t launch_dct32_pass(const int16_t *d_in, int16_t *d_out, size_t n_blocks, int shift, const DctOps *d_fwd_ops, hipStream_t stream);
 hipError_t launch_dct32_fwdinv(const int16_t *d_in, int16_t *d_coef, int16_t *d_recon, size_t n_blocks,

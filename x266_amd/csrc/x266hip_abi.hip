@@ -1062,6 +1062,74 @@ int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_r
     return X266HIP_OK;
 }
 
+// ---- the mixed transform set from and into tiles, per CTU ----------------------------------------------------------------------
+// Byte spans of the CTU calls' buffers for a frame of width x height (multiples of 16, positive): the tile arrays, the coefficient
+// stream (12 KiB per CTU) and the class bytes (6 per CTU).  Every product is checked before it is formed, and so is every buffer's
+// end against the address space; false where anything would not fit.
+static bool ctu_spans(int width, int height, const void *tiles_a, const void *tiles_b, const void *coef, const void *cls,
+                      size_t *tile_bytes, size_t *coef_bytes, size_t *class_bytes)
+{
+    const size_t ctus_x = ((size_t)width + 63) / 64, ctus_y = ((size_t)height + 63) / 64;
+    size_t n = 0;
+    uintptr_t end = 0;
+    return !__builtin_mul_overflow((size_t)width, (size_t)height, tile_bytes) && !__builtin_mul_overflow(*tile_bytes, (size_t)2, tile_bytes) &&
+           !__builtin_mul_overflow(ctus_x, ctus_y, &n) && !__builtin_mul_overflow(n, (size_t)12288, coef_bytes) &&
+           !__builtin_mul_overflow(n, (size_t)6, class_bytes) &&
+           !__builtin_add_overflow((uintptr_t)tiles_a, *tile_bytes, &end) && !__builtin_add_overflow((uintptr_t)tiles_b, *tile_bytes, &end) &&
+           !__builtin_add_overflow((uintptr_t)coef, *coef_bytes, &end) && !__builtin_add_overflow((uintptr_t)cls, *class_bytes, &end);
+}
+
+static LaunchCfg ctu_tiles_cfg(const x266hip_ctx *ctx, int inverse)
+{
+    LaunchCfg cfg = cfg_for(ctx, inverse);
+    cfg.lds_bytes_per_wave = x266hip_ctx::kTileLdsPerWave;
+    return cfg;
+}
+
+int xTransformCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
+                              const uint8_t *d_class, int16_t *d_coef, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: width/height must be positive multiples of 16");
+    if (!d_cur || !d_pred || !d_class || !d_coef || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_coef)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: NULL or unaligned buffer");
+    size_t tile_bytes = 0, coef_bytes = 0, class_bytes = 0;
+    if (!ctu_spans(width, height, d_cur, d_pred, d_coef, d_class, &tile_bytes, &coef_bytes, &class_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: a buffer does not fit in the address space");
+    if (ranges_overlap(d_coef, coef_bytes, d_cur, tile_bytes) || ranges_overlap(d_coef, coef_bytes, d_pred, tile_bytes) ||
+        ranges_overlap(d_coef, coef_bytes, d_class, class_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: d_coef overlaps an input");
+    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformCtuFromTilesDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    X_DEV(ctx);
+    hipError_t e = launch_transform_ctu_tiles(false, d_cur, nullptr, d_pred, d_class, d_coef, nullptr, width, height, ctx->d_tile_fwd,
+                                              ctu_tiles_cfg(ctx, 0), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "CTU transform from tiles launch", e);
+    return X266HIP_OK;
+}
+
+int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8_t *d_class, const x266_ref_block_t *d_pred, int width,
+                            int height, x266_ref_block_t *d_recon, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: width/height must be positive multiples of 16");
+    if (!d_coef || !d_class || !d_pred || !d_recon || ((((uintptr_t)d_coef | (uintptr_t)d_pred | (uintptr_t)d_recon)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: NULL or unaligned buffer");
+    size_t tile_bytes = 0, coef_bytes = 0, class_bytes = 0;
+    if (!ctu_spans(width, height, d_pred, d_recon, d_coef, d_class, &tile_bytes, &coef_bytes, &class_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: a buffer does not fit in the address space");
+    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_coef, coef_bytes) ||
+        ranges_overlap(d_recon, tile_bytes, d_class, class_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformCtuToTilesDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    X_DEV(ctx);
+    hipError_t e = launch_transform_ctu_tiles(true, nullptr, d_coef, d_pred, d_class, nullptr, d_recon, width, height, ctx->d_tile_inv,
+                                              ctu_tiles_cfg(ctx, 1), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "CTU transform into tiles launch", e);
+    return X266HIP_OK;
+}
+
 int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                                uint32_t *d_out_u, uint32_t *d_out_v, size_t pitch, void *stream)
 {
