@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer probe: same-box, same-process A/B of the inverse-transform family between tools/_ab/libx266hip_ref.so
 (tools/ab_build.sh <git-ref>) and the working tree's library: DCT32 inverse, fused forward+inverse, the small-N inverses,
-the one-launch tile inverse.  HIP events per launch (xHipEvent*), best of alternating rounds."""
+the one-launch tile inverse, the DCT32 inverses into tiles (frame raster and whole-CTU order).  HIP events per launch
+(xHipEvent*), best of alternating rounds."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ctypes.c_void_p
@@ -20,6 +21,7 @@ def load(path):
     L.xDct32FwdInvBatchDev.argtypes = [P, P, P, P, SZ, P]
     L.xTransformInvBatchDev.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, SZ, P, P]
     L.xTransformTilesDev.argtypes = [P, ctypes.c_int, P, P, SZ, P, P, P]
+    L.xDct32InvToTilesDev.argtypes = L.xDct32InvCtuToTilesDev.argtypes = [P, P, P, ctypes.c_int, ctypes.c_int, P, P]
     ev = [P() for _ in range(2)]
     for e in ev: assert L.xHipEventCreate(ctx, ctypes.byref(e)) == 0
     return L, ctx, ev
@@ -51,6 +53,16 @@ for n in (4, 8, 16):
     legs.append(("dct2 inverse %dx%d" % (n, n), 4096, (lambda n, per: lambda L, c: L.xTransformInvBatchDev(c, 0, n, din, dout, N * per, None, None))(n, per)))
 legs.append(("tiles one launch fwd", 4096, lambda L, c: L.xTransformTilesDev(c, 0, din, dout, N, None, dcls, None)))
 legs.append(("tiles one launch inv", 4096, lambda L, c: L.xTransformTilesDev(c, 1, din, dout, N, None, dcls, None)))
+# a 32768^2 frame: din's 2^20 luma blocks onto the luma of its 2^22 tiles, and its 2^18 CTUs of 12 KiB; recon in place (recon == pred)
+W = 32768
+dtile, dctu = P(), P()
+for b, n in ((dtile, (W // 16) ** 2 * 512), (dctu, (W // 64) ** 2 * 12288)): assert L0.xHipMalloc(c0, ctypes.byref(b), n) == 0
+L0.xFillResidualDev(c0, dtile, (W // 16) ** 2 * 256, 0x267, 0, None); L0.xFillResidualDev(c0, dctu, (W // 64) ** 2 * 6144, 0x268, 0, None)
+L0.xHipStreamSync(c0, None)
+legs.append(("dct32 inv to tiles", 4096, lambda L, c: L.xDct32InvToTilesDev(c, din, dtile, W, W, dtile, None)))
+legs.append(("dct32 inv ctu to tiles", 4608, lambda L, c: L.xDct32InvCtuToTilesDev(c, dctu, dtile, W, W, dtile, None)))   # N * 4608 = 12 KiB in + 3 KiB of pred + 3 KiB out per CTU
+for name, unit, fn in legs:                                       # every call must succeed in both libraries before it is timed
+    for tag, (L, c, ev) in libs: assert fn(L, c) == 0, (name, tag)
 for tag, (L, c, ev) in libs: timed(L, c, ev, legs[0][2], 100)     # clocks
 for name, unit, fn in legs:
     best = {"ref": 1e9, "new": 1e9}

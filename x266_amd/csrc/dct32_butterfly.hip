@@ -108,9 +108,9 @@ __global__ __launch_bounds__(256) void dct32_butterfly_kernel(const int16_t *__r
 hipError_t launch_dct32_butterfly(const int16_t *d_in, int16_t *d_out, size_t n_blocks, hipStream_t stream)
 {
     if (n_blocks == 0) return hipSuccess;
-    const size_t wgs = (n_blocks + 7) / 8;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dct32_butterfly_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_in, d_out, n_blocks);
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_blocks, 8, &wgs)) return e;
+    hipLaunchKernelGGL(dct32_butterfly_kernel, dim3(wgs), dim3(256), 0, stream, d_in, d_out, n_blocks);
     return hipGetLastError();
 }
 

@@ -34,9 +34,12 @@
 // Kernels in this file: dct32_lds_kernel (LDS-staged line-dense traffic, forward / inverse),
 // dct32_fwdinv_kernel (coefficients + reconstruction in one pass, LDS-DMA fed), dct32_from_tiles_kernel
 // (residual formation fused in), dct32_inv_to_tiles_kernel / dct32_inv_ctu_to_tiles_kernel (the inverse with the
-// reconstruction into tiles fused in), dct32_pass_kernel (the 1-D pass by itself, for checking).  The direct
-// fragment-load forms and the variants without cache-policy hints of rounds 1-3 are gone: every A/B they
-// served is frozen in profiles/r01_*.txt (line-dense traffic +9 %, "nt" loads / "sc1 nt" stores +3-5 %).
+// reconstruction into tiles fused in), dct32_pass_kernel (the 1-D pass by itself, for checking).  They share their per-wave
+// steps: the blocks of x266_mfma_blocks.hpp (tile_lanes, frag_to_linear, column_base / read_column_planes, load_c2r,
+// fwd_from_pixels, chroma_plane) and, here, inv_from_slot, luma_from_tiles and chroma_from_tiles -- the bodies that the
+// standalone from-tiles kernels and the whole-CTU kernels are both built on.  The direct fragment-load forms and the variants
+// without cache-policy hints of rounds 1-3 are gone: every A/B they served is frozen in profiles/r01_*.txt (line-dense
+// traffic +9 %, "nt" loads / "sc1 nt" stores +3-5 %).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -54,6 +57,15 @@ namespace {
 // R[y][x] = clip16((sum_u g[u][x] T[u][y] + 2048) >> 12)
 // The first contraction runs over the ROW index of the loaded block, which a row-per-lane fragment cannot
 // feed: with the tile staged in LDS each lane reads its COLUMN instead (see dct32_lds_kernel).
+
+// one block staged in `slot` -> row c, columns 16h .. 16h+15 of its inverse in lane (c, h)
+__device__ __forceinline__ void inv_from_slot(const unsigned char *slot, const unsigned (&col_base)[4], const LaneConsts &k, const v16i &c2r,
+                                              v4i &o0, v4i &o1)
+{
+    v4i lo, hi;
+    read_column_planes(slot, col_base, lo, hi);
+    inv_passes(lo, hi, k, c2r, o0, o1);
+}
 
 // ---- kernels ---------------------------------------------------------------
 // Each wave transforms blocks_per_wave consecutive blocks, one wave per chunk, a grid as large as
@@ -74,6 +86,7 @@ namespace {
 // the four DS accesses is bank-conflict-free.  Waves never share a slot, so there is
 // no barrier, only the in-order LDS queue of the wave itself.
 // (lds_slot itself lives in x266_mfma_blocks.hpp: the fused frame kernel of satd_kernels.hip stages DCT32 tiles the same way)
+// (tile_lanes and frag_to_linear, the lane's offsets into a slot and the slot as converter on the way out, live there too)
 
 template <bool INVERSE>
 __global__ __launch_bounds__(256) void dct32_lds_kernel(const int16_t *__restrict__ in,
@@ -92,63 +105,35 @@ __global__ __launch_bounds__(256) void dct32_lds_kernel(const int16_t *__restric
     if (b >= end) return;
 
     const unsigned c = lane & 31, h = lane >> 5;
-    // this lane's two linear chunks (16 B each) and its two fragment chunks
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
-    const unsigned frag0 = lds_slot(c, 2 * h), frag1 = lds_slot(c, 2 * h + 1);
-    // inverse: byte offset of element (row 16h + t, column u) is col_base[(t >> 2) & 3] + 64 t, u = kappa(c)
-    unsigned col_base[4];
-    {
-        const unsigned u = (unsigned)kappa((int)c);
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) col_base[j] = 16u * h * 64u + ((((u >> 3) ^ j) & 3u) << 4) + (u & 7u) * 2u;
-    }
+    const TileLanes t = tile_lanes(lane);                      // this lane's two linear chunks (16 B each) and its two fragment chunks
+    unsigned col_base[4];                                      // inverse: where the lane's column starts
+    column_base(c, h, col_base);
     const char *src = reinterpret_cast<const char *>(in) + lane * 16;
     char *dst = reinterpret_cast<char *>(out) + lane * 16;
 
     v4i g0 = load16<true>(src + b * 2048), g1 = load16<true>(src + b * 2048 + 1024);
     const LaneConsts k = load_consts(ops, lane);
     v16i c2r;
-    if (INVERSE) {
-        // the pass-B constants depend on (half, register) only: two scalar loads (wave-uniform
-        // addresses) and a per-lane select instead of 64 bytes of vector loads per lane and wave
-        const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
-    }
+    if (INVERSE) c2r = load_c2r(ops, h);
     while (true) {
         const size_t nb = b + 1;
-        *reinterpret_cast<v4i *>(slot + lin0) = g0;
-        *reinterpret_cast<v4i *>(slot + lin1) = g1;
+        *reinterpret_cast<v4i *>(slot + t.lin0) = g0;
+        *reinterpret_cast<v4i *>(slot + t.lin1) = g1;
         if (nb < end) {                                        // next tile's loads fly under this tile's arithmetic
             g0 = load16<true>(src + nb * 2048);
             g1 = load16<true>(src + nb * 2048 + 1024);
         }
         __builtin_amdgcn_wave_barrier();
-        v4i o0, o1;
+        v4i o0, o1, s0, s1;
         if (INVERSE) {
-            // The inverse contracts over the block's ROW index first: with the tile in LDS the lane
-            // simply reads its COLUMN (16 x ds_read_u16).  Lane (c, h): column kappa(c), rows 16h..16h+15.
-            uint32_t w[8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const uint32_t e0 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m) >> 2) & 3] + (2 * m) * 64);
-                const uint32_t e1 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m + 1) >> 2) & 3] + (2 * m + 1) * 64);
-                w[m] = e0 | (e1 << 16);
-            }
-            v4i lo, hi;
-            split_planes(v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]}, lo, hi);
-            inv_passes(lo, hi, k, c2r, o0, o1);
+            inv_from_slot(slot, col_base, k, c2r, o0, o1);
         } else {
-            const v4i a0 = *reinterpret_cast<const v4i *>(slot + frag0);
-            const v4i a1 = *reinterpret_cast<const v4i *>(slot + frag1);
+            const v4i a0 = *reinterpret_cast<const v4i *>(slot + t.frag0);
+            const v4i a1 = *reinterpret_cast<const v4i *>(slot + t.frag1);
             fwd_block<4, 11>(a0, a1, k, o0, o1);
         }
         __builtin_amdgcn_wave_barrier();
-        *reinterpret_cast<v4i *>(slot + frag0) = o0;
-        *reinterpret_cast<v4i *>(slot + frag1) = o1;
-        __builtin_amdgcn_wave_barrier();
-        const v4i s0 = *reinterpret_cast<const v4i *>(slot + lin0);
-        const v4i s1 = *reinterpret_cast<const v4i *>(slot + lin1);
+        frag_to_linear(slot, t, o0, o1, s0, s1);
         __builtin_amdgcn_wave_barrier();
         store16_sc1nt(dst + b * 2048, s0);
         store16_sc1nt(dst + b * 2048 + 1024, s1);
@@ -207,9 +192,8 @@ __global__ __launch_bounds__(256) void dct32_fwdinv_kernel(const int16_t *__rest
     unsigned char *conv = slots + DEPTH * 2048;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)slots;
 
-    const unsigned c = lane & 31, h = lane >> 5;
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
-    const unsigned frag0 = lds_slot(c, 2 * h), frag1 = lds_slot(c, 2 * h + 1);
+    const unsigned h = lane >> 5;
+    const TileLanes t = tile_lanes(lane);
     // the lane's LDS position 16 * lane (+ 1024) holds chunk (row, (lane & 3) ^ swizzle(row)) of the block
     const unsigned goff0 = (unsigned)(lane >> 2) * 64u + ((((unsigned)lane & 3u) ^ (((unsigned)lane >> 4) & 3u)) << 4), goff1 = goff0 + 1024u;
     const unsigned lane_off = (unsigned)lane * 16u;
@@ -217,12 +201,7 @@ __global__ __launch_bounds__(256) void dct32_fwdinv_kernel(const int16_t *__rest
 
     LaneConsts kf = load_consts(fwd_ops, lane);
     LaneConsts ki = load_consts(inv_ops, lane);
-    v16i c2r;
-    {
-        const int *__restrict__ s0 = inv_ops->c2r[0], *__restrict__ s1 = inv_ops->c2r[32];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
-    }
+    v16i c2r = load_c2r(inv_ops, h);
     auto fetch = [&](unsigned j, unsigned s) {                    // block j of this wave's run into input slot s
         const char *blk = src + (size_t)j * 2048;
         const unsigned lds = lds0 + s * 2048u;
@@ -256,8 +235,8 @@ __global__ __launch_bounds__(256) void dct32_fwdinv_kernel(const int16_t *__rest
         unsigned char *slot = slots + si * 2048u;
         v4i ylo, yhi;
         {
-            const v4i a0 = *reinterpret_cast<const v4i *>(slot + frag0);
-            const v4i a1 = *reinterpret_cast<const v4i *>(slot + frag1);
+            const v4i a0 = *reinterpret_cast<const v4i *>(slot + t.frag0);
+            const v4i a1 = *reinterpret_cast<const v4i *>(slot + t.frag1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // the fragments are in registers: the slot may be refilled
             if (i + DEPTH < cnt) fetch(i + DEPTH, si);
             v4i lo, hi;
@@ -293,25 +272,16 @@ __global__ __launch_bounds__(256) void dct32_fwdinv_kernel(const int16_t *__rest
             for (int m = 0; m < 8; ++m)
                 z[m] = bperm((uint32_t)(acc[2 * m + 1] >> 11), (uint32_t)(acc[2 * m] >> 11), 0x05040100u);
             __builtin_amdgcn_wave_barrier();
-            *reinterpret_cast<v4i *>(conv + frag0) = v4i{(int)z[0], (int)z[1], (int)z[2], (int)z[3]};
-            *reinterpret_cast<v4i *>(conv + frag1) = v4i{(int)z[4], (int)z[5], (int)z[6], (int)z[7]};
-            __builtin_amdgcn_wave_barrier();
-            const v4i s0 = *reinterpret_cast<const v4i *>(conv + lin0);
-            const v4i s1 = *reinterpret_cast<const v4i *>(conv + lin1);
+            v4i s0, s1;
+            frag_to_linear(conv, t, v4i{(int)z[0], (int)z[1], (int)z[2], (int)z[3]}, v4i{(int)z[4], (int)z[5], (int)z[6], (int)z[7]}, s0, s1);
             store_tile_sc1nt(reinterpret_cast<char *>(coef_out) + (first + i) * 2048, lane_off, s0, s1);
         }
-        v4i o0, o1;
+        v4i o0, o1, s0, s1;
         inv_passes(zlo, zhi, ki, c2r, o0, o1);
         __builtin_amdgcn_wave_barrier();
-        *reinterpret_cast<v4i *>(conv + frag0) = o0;
-        *reinterpret_cast<v4i *>(conv + frag1) = o1;
+        frag_to_linear(conv, t, o0, o1, s0, s1);
         __builtin_amdgcn_wave_barrier();
-        {
-            const v4i s0 = *reinterpret_cast<const v4i *>(conv + lin0);
-            const v4i s1 = *reinterpret_cast<const v4i *>(conv + lin1);
-            __builtin_amdgcn_wave_barrier();
-            store_tile_sc1nt(reinterpret_cast<char *>(recon_out) + (first + i) * 2048, lane_off, s0, s1);
-        }
+        store_tile_sc1nt(reinterpret_cast<char *>(recon_out) + (first + i) * 2048, lane_off, s0, s1);
         si = si + 1 == (unsigned)DEPTH ? 0u : si + 1;
     }
 }
@@ -326,6 +296,21 @@ __global__ __launch_bounds__(256) void dct32_fwdinv_kernel(const int16_t *__rest
 // inline C operand.  A lane's fragment (row c, columns 16h..16h+15 of the 32x32 block) is exactly
 // one 16-byte luma row of one tile, so fragment loads are line-dense as they are; only the stores
 // go through the LDS slot (section "LDS-staged variant").
+// The body: lane (c, h)'s row of the block is luma row (c & 15) of tile `tile`; dst = the lane's first piece (+ lane * 16) of the
+// block's 2 KiB of coefficients.
+__device__ __forceinline__ void luma_from_tiles(const x266_ref_block_t *__restrict__ cur, const x266_ref_block_t *__restrict__ pred, size_t tile,
+                                                char *dst, unsigned char *slot, int lane, const TileLanes &t, const LaneConsts &k)
+{
+    // each instruction reads the whole 256-byte luma part of four tiles: line-dense, so streaming hints pay
+    const v4i a = load16<true>(reinterpret_cast<const unsigned char *>(cur + tile) + ctu_luma_row_offset(lane & 31));
+    const v4i b = load16<true>(reinterpret_cast<const unsigned char *>(pred + tile) + ctu_luma_row_offset(lane & 31));
+    v4i o0, o1, s0, s1;
+    fwd_from_pixels(a, b, k, o0, o1);
+    frag_to_linear(slot, t, o0, o1, s0, s1);
+    store16_sc1nt(dst, s0);
+    store16_sc1nt(dst + 1024, s1);
+}
+
 __global__ __launch_bounds__(256) void dct32_from_tiles_kernel(const x266_ref_block_t *__restrict__ cur,
                                                                const x266_ref_block_t *__restrict__ pred,
                                                                int16_t *__restrict__ out, int blocks_x, int tiles_x,
@@ -339,26 +324,8 @@ __global__ __launch_bounds__(256) void dct32_from_tiles_kernel(const x266_ref_bl
     const unsigned c = lane & 31, h = lane >> 5;
     const size_t by = blk / blocks_x, bx = blk - by * blocks_x;
     const size_t tile = (by * 2 + (c >> 4)) * (size_t)tiles_x + bx * 2 + h;
-    // each instruction reads the whole 256-byte luma part of four tiles: line-dense, so streaming hints pay
-    const v4i a = load16<true>(reinterpret_cast<const unsigned char *>(cur + tile) + (c & 15) * 16);
-    const v4i b = load16<true>(reinterpret_cast<const unsigned char *>(pred + tile) + (c & 15) * 16);
-    const LaneConsts k = load_consts(ops, lane);
-    const v4i bias = {(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u};
-    const v16i round1 = {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8};
-    v16i acc = mfma(a ^ bias, k.p1, round1);
-    acc = mfma(b ^ bias, k.tr, acc);                          // k.tr = -p1 in the forward tables
-    v4i o0, o1;
-    fwd_finish<4, 11>(acc, k, o0, o1);
-    *reinterpret_cast<v4i *>(slot + lds_slot(c, 2 * h)) = o0;
-    *reinterpret_cast<v4i *>(slot + lds_slot(c, 2 * h + 1)) = o1;
-    __builtin_amdgcn_wave_barrier();
-    const v4i s0 = *reinterpret_cast<const v4i *>(slot + lds_slot(lane >> 2, lane & 3));
-    const v4i s1 = *reinterpret_cast<const v4i *>(slot + lds_slot(16 + (lane >> 2), lane & 3));
-    char *dst = reinterpret_cast<char *>(out) + blk * 2048 + lane * 16;
-    store16_sc1nt(dst, s0);
-    store16_sc1nt(dst + 1024, s1);
+    luma_from_tiles(cur, pred, tile, reinterpret_cast<char *>(out) + blk * 2048 + lane * 16, slot, lane, tile_lanes(lane), load_consts(ops, lane));
 }
-
 
 // ---- fused chroma residual + forward transform -------------------------------------------------
 // A 64x64 CTU in 4:2:0 carries one 32x32 U and one 32x32 V block -- the headline transform size -- spread over the m_C lines
@@ -367,6 +334,27 @@ __global__ __launch_bounds__(256) void dct32_from_tiles_kernel(const x266_ref_bl
 // (c >> 3), tiles 2h and 2h+1 -- two 16-byte loads per frame, whose even bytes are the U fragment and odd bytes the V
 // fragment.  Eight lanes share a tile's line, so every load instruction consumes whole lines.  Arithmetic as for luma
 // (dct32_from_tiles_kernel): one byte plane per frame, G*cur + (-G)*pred, the +128 of the offset trick cancels.
+// The body: `tile` = ctu_chroma_tile of lane (c, h); dst_u / dst_v = the lane's first piece (+ lane * 16) of each plane's 2 KiB of coefficients.
+__device__ __forceinline__ void chroma_from_tiles(const x266_ref_block_t *__restrict__ cur, const x266_ref_block_t *__restrict__ pred, size_t tile,
+                                                  char *dst_u, char *dst_v, unsigned char *slot, int lane, const TileLanes &t, const LaneConsts &k)
+{
+    const unsigned char *pc = reinterpret_cast<const unsigned char *>(cur + tile) + ctu_chroma_row_offset(lane & 31);
+    const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred + tile) + ctu_chroma_row_offset(lane & 31);
+    const v4i a0 = load16<true>(pc), a1 = load16<true>(pc + 512), b0 = load16<true>(pp), b1 = load16<true>(pp + 512);
+    // U, then V through the same slot (both planes computed first and converted through two slots: 1-2 % slower, profiles/r06_chroma_shapes.txt)
+#pragma unroll
+    for (int plane = 0; plane < 2; ++plane) {
+        const uint32_t sel = plane ? kSelV : kSelU;
+        v4i o0, o1, s0, s1;
+        fwd_from_pixels(chroma_plane(a0, a1, sel), chroma_plane(b0, b1, sel), k, o0, o1);
+        if (plane) __builtin_amdgcn_wave_barrier();                       // the U tile has left the slot
+        frag_to_linear(slot, t, o0, o1, s0, s1);
+        char *dst = plane ? dst_v : dst_u;
+        store16_sc1nt(dst, s0);
+        store16_sc1nt(dst + 1024, s1);
+    }
+}
+
 __global__ __launch_bounds__(256) void dct32_chroma_from_tiles_kernel(const x266_ref_block_t *__restrict__ cur,
                                                                       const x266_ref_block_t *__restrict__ pred,
                                                                       int16_t *__restrict__ out_u, int16_t *__restrict__ out_v,
@@ -381,44 +369,16 @@ __global__ __launch_bounds__(256) void dct32_chroma_from_tiles_kernel(const x266
     const unsigned c = lane & 31, h = lane >> 5;
     const size_t cy = ctu / ctus_x, cx = ctu - cy * ctus_x;
     const size_t tile = ctu_chroma_tile(cy, cx, c, h, tiles_x);
-    const unsigned char *pc = reinterpret_cast<const unsigned char *>(cur + tile) + 256 + (c & 7) * 16;
-    const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred + tile) + 256 + (c & 7) * 16;
-    const v4i a0 = load16<true>(pc), a1 = load16<true>(pc + 512), b0 = load16<true>(pp), b1 = load16<true>(pp + 512);
-    const LaneConsts k = load_consts(ops, lane);
-    const uint32_t S = 0x80808080u;
-    const v16i round1 = {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8};
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
-    const unsigned frag0 = lds_slot(c, 2 * h), frag1 = lds_slot(c, 2 * h + 1);
-    // U, then V through the same slot (both planes computed first and converted through two slots: 1-2 % slower, profiles/r06_chroma_shapes.txt)
-#pragma unroll
-    for (int plane = 0; plane < 2; ++plane) {
-        const uint32_t sel = plane ? 0x07050301u : 0x06040200u;           // odd bytes = V, even bytes = U
-        const v4i a = {(int)(bperm((uint32_t)a0[1], (uint32_t)a0[0], sel) ^ S), (int)(bperm((uint32_t)a0[3], (uint32_t)a0[2], sel) ^ S),
-                       (int)(bperm((uint32_t)a1[1], (uint32_t)a1[0], sel) ^ S), (int)(bperm((uint32_t)a1[3], (uint32_t)a1[2], sel) ^ S)};
-        const v4i b = {(int)(bperm((uint32_t)b0[1], (uint32_t)b0[0], sel) ^ S), (int)(bperm((uint32_t)b0[3], (uint32_t)b0[2], sel) ^ S),
-                       (int)(bperm((uint32_t)b1[1], (uint32_t)b1[0], sel) ^ S), (int)(bperm((uint32_t)b1[3], (uint32_t)b1[2], sel) ^ S)};
-        v16i acc = mfma(a, k.p1, round1);
-        acc = mfma(b, k.tr, acc);                                         // k.tr = -p1 in the forward tables
-        v4i o0, o1;
-        fwd_finish<4, 11>(acc, k, o0, o1);
-        if (plane) __builtin_amdgcn_wave_barrier();                       // the U tile has left the slot
-        *reinterpret_cast<v4i *>(slot + frag0) = o0;
-        *reinterpret_cast<v4i *>(slot + frag1) = o1;
-        __builtin_amdgcn_wave_barrier();
-        const v4i s0 = *reinterpret_cast<const v4i *>(slot + lin0);
-        const v4i s1 = *reinterpret_cast<const v4i *>(slot + lin1);
-        char *dst = reinterpret_cast<char *>((plane ? out_v : out_u) + ctu * block_pitch * 1024) + lane * 16;
-        store16_sc1nt(dst, s0);
-        store16_sc1nt(dst + 1024, s1);
-    }
+    char *dst_u = reinterpret_cast<char *>(out_u + ctu * block_pitch * 1024) + lane * 16, *dst_v = reinterpret_cast<char *>(out_v + ctu * block_pitch * 1024) + lane * 16;
+    chroma_from_tiles(cur, pred, tile, dst_u, dst_v, slot, lane, tile_lanes(lane), load_consts(ops, lane));
 }
 
 // ---- a whole 4:2:0 CTU in one launch ----------------------------------------------------------------------------------------
 // coef[ctu][0..3] = DCT32 of the CTU's four 32x32 luma residual quadrants (raster order inside the CTU), coef[ctu][4] = U,
 // coef[ctu][5] = V: 12 KiB per 64x64 CTU, CTUs in raster order -- the order a per-CTU encoder loop consumes, from ONE grid
 // instead of xDct32FwdFromTilesDev + xDct32FwdChromaFromTilesDev (frame-raster luma, separate chroma streams).  Five waves per
-// CTU: four take one luma quadrant each (dct32_from_tiles_kernel's body), the fifth both chroma planes
-// (dct32_chroma_from_tiles_kernel's body: their fragments come from the same loads).  The part index is wave-uniform.
+// CTU: four take one luma quadrant each (dct32_from_tiles_kernel's body, luma_from_tiles), the fifth both chroma planes
+// (dct32_chroma_from_tiles_kernel's body, chroma_from_tiles: their fragments come from the same loads).  The part index is wave-uniform.
 __global__ __launch_bounds__(256) void dct32_ctu_from_tiles_kernel(const x266_ref_block_t *__restrict__ cur,
                                                                    const x266_ref_block_t *__restrict__ pred,
                                                                    int16_t *__restrict__ out, int ctus_x, int tiles_x, size_t n_ctus,
@@ -435,54 +395,11 @@ __global__ __launch_bounds__(256) void dct32_ctu_from_tiles_kernel(const x266_re
     const unsigned c = lane & 31, h = lane >> 5;
     const size_t cy = ctu / ctus_x, cx = ctu - cy * ctus_x;
     const LaneConsts k = load_consts(ops, lane);
-    const uint32_t S = 0x80808080u;
-    const v16i round1 = {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8};
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
-    const unsigned frag0 = lds_slot(c, 2 * h), frag1 = lds_slot(c, 2 * h + 1);
+    const TileLanes t = tile_lanes(lane);
     char *dst = reinterpret_cast<char *>(out + ctu * 6144) + lane * 16;
-    if (part < 4) {
-        // luma quadrant (part >> 1, part & 1): row c of the quadrant, columns 16h .. 16h+15 = one 16-byte luma row of one tile
-        const size_t tile = ctu_luma_tile(cy, cx, part, c, h, tiles_x);
-        const v4i a = load16<true>(reinterpret_cast<const unsigned char *>(cur + tile) + ctu_luma_row_offset(c));
-        const v4i b = load16<true>(reinterpret_cast<const unsigned char *>(pred + tile) + ctu_luma_row_offset(c));
-        const v4i bias = {(int)S, (int)S, (int)S, (int)S};
-        v16i acc = mfma(a ^ bias, k.p1, round1);
-        acc = mfma(b ^ bias, k.tr, acc);
-        v4i o0, o1;
-        fwd_finish<4, 11>(acc, k, o0, o1);
-        *reinterpret_cast<v4i *>(slot + frag0) = o0;
-        *reinterpret_cast<v4i *>(slot + frag1) = o1;
-        __builtin_amdgcn_wave_barrier();
-        const v4i s0 = *reinterpret_cast<const v4i *>(slot + lin0);
-        const v4i s1 = *reinterpret_cast<const v4i *>(slot + lin1);
-        store16_sc1nt(dst + part * 2048, s0);
-        store16_sc1nt(dst + part * 2048 + 1024, s1);
-        return;
-    }
-    const size_t tile = ctu_chroma_tile(cy, cx, c, h, tiles_x);
-    const unsigned char *pc = reinterpret_cast<const unsigned char *>(cur + tile) + 256 + (c & 7) * 16;
-    const unsigned char *pp = reinterpret_cast<const unsigned char *>(pred + tile) + 256 + (c & 7) * 16;
-    const v4i a0 = load16<true>(pc), a1 = load16<true>(pc + 512), b0 = load16<true>(pp), b1 = load16<true>(pp + 512);
-#pragma unroll
-    for (int plane = 0; plane < 2; ++plane) {
-        const uint32_t sel = plane ? 0x07050301u : 0x06040200u;
-        const v4i a = {(int)(bperm((uint32_t)a0[1], (uint32_t)a0[0], sel) ^ S), (int)(bperm((uint32_t)a0[3], (uint32_t)a0[2], sel) ^ S),
-                       (int)(bperm((uint32_t)a1[1], (uint32_t)a1[0], sel) ^ S), (int)(bperm((uint32_t)a1[3], (uint32_t)a1[2], sel) ^ S)};
-        const v4i b = {(int)(bperm((uint32_t)b0[1], (uint32_t)b0[0], sel) ^ S), (int)(bperm((uint32_t)b0[3], (uint32_t)b0[2], sel) ^ S),
-                       (int)(bperm((uint32_t)b1[1], (uint32_t)b1[0], sel) ^ S), (int)(bperm((uint32_t)b1[3], (uint32_t)b1[2], sel) ^ S)};
-        v16i acc = mfma(a, k.p1, round1);
-        acc = mfma(b, k.tr, acc);
-        v4i o0, o1;
-        fwd_finish<4, 11>(acc, k, o0, o1);
-        if (plane) __builtin_amdgcn_wave_barrier();
-        *reinterpret_cast<v4i *>(slot + frag0) = o0;
-        *reinterpret_cast<v4i *>(slot + frag1) = o1;
-        __builtin_amdgcn_wave_barrier();
-        const v4i s0 = *reinterpret_cast<const v4i *>(slot + lin0);
-        const v4i s1 = *reinterpret_cast<const v4i *>(slot + lin1);
-        store16_sc1nt(dst + (4 + plane) * 2048, s0);
-        store16_sc1nt(dst + (4 + plane) * 2048 + 1024, s1);
-    }
+    // luma quadrant (part >> 1, part & 1): row c of the quadrant, columns 16h .. 16h+15 = one 16-byte luma row of one tile
+    if (part < 4) luma_from_tiles(cur, pred, ctu_luma_tile(cy, cx, part, c, h, tiles_x), dst + part * 2048, slot, lane, t, k);
+    else          chroma_from_tiles(cur, pred, ctu_chroma_tile(cy, cx, c, h, tiles_x), dst + 4 * 2048, dst + 5 * 2048, slot, lane, t, k);
 }
 
 // ---- fused inverse transform + reconstruction into tiles -----------------------------------------------------------------
@@ -507,26 +424,17 @@ __global__ __launch_bounds__(256) void dct32_inv_to_tiles_kernel(const int16_t *
     if (b >= end) return;
 
     const unsigned c = lane & 31, h = lane >> 5;
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
+    const TileLanes t = tile_lanes(lane);
     unsigned col_base[4];
-    {
-        const unsigned u = (unsigned)kappa((int)c);
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) col_base[j] = 16u * h * 64u + ((((u >> 3) ^ j) & 3u) << 4) + (u & 7u) * 2u;
-    }
+    column_base(c, h, col_base);
     const char *src = reinterpret_cast<const char *>(coef) + lane * 16;
     v4i g0 = load16<true>(src + b * 2048), g1 = load16<true>(src + b * 2048 + 1024);
     const LaneConsts k = load_consts(ops, lane);
-    v16i c2r;
-    {
-        const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
-    }
+    const v16i c2r = load_c2r(ops, h);
     while (true) {
         const size_t nb = b + 1;
-        *reinterpret_cast<v4i *>(slot + lin0) = g0;
-        *reinterpret_cast<v4i *>(slot + lin1) = g1;
+        *reinterpret_cast<v4i *>(slot + t.lin0) = g0;
+        *reinterpret_cast<v4i *>(slot + t.lin1) = g1;
         const size_t by = b / (size_t)blocks_x, bx = b - by * (size_t)blocks_x;
         const size_t off = ((by * 2 + (c >> 4)) * (size_t)tiles_x + bx * 2 + h) * sizeof(x266_ref_block_t) + (c & 15) * 16;
         const v4i p = load16<true>(reinterpret_cast<const unsigned char *>(pred) + off);   // four tiles' luma per instruction
@@ -535,16 +443,8 @@ __global__ __launch_bounds__(256) void dct32_inv_to_tiles_kernel(const int16_t *
             g1 = load16<true>(src + nb * 2048 + 1024);
         }
         __builtin_amdgcn_wave_barrier();
-        uint32_t w[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const uint32_t e0 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m) >> 2) & 3] + (2 * m) * 64);
-            const uint32_t e1 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m + 1) >> 2) & 3] + (2 * m + 1) * 64);
-            w[m] = e0 | (e1 << 16);
-        }
-        v4i lo, hi, o0, o1;
-        split_planes(v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]}, lo, hi);
-        inv_passes(lo, hi, k, c2r, o0, o1);
+        v4i o0, o1;
+        inv_from_slot(slot, col_base, k, c2r, o0, o1);
         __builtin_amdgcn_wave_barrier();                                   // the slot is rewritten by the next block
         store16_sc1nt(reinterpret_cast<unsigned char *>(recon) + off, recon_luma16(p, o0, o1));
         if (nb >= end) break;
@@ -554,7 +454,8 @@ __global__ __launch_bounds__(256) void dct32_inv_to_tiles_kernel(const int16_t *
 
 // ---- the whole-CTU inverse: 12 KiB of coefficients per CTU back into its 16 tiles ----------------------------------------------
 // Input = what dct32_ctu_from_tiles_kernel emits (Y0 Y1 Y2 Y3 U V per 64x64 CTU, CTUs in raster order).  Five waves per CTU:
-// four take one luma quadrant each (dct32_inv_to_tiles_kernel's body), the fifth inverts U and V through the same slot and
+// four take one luma quadrant each (dct32_inv_to_tiles_kernel's steps without its pipelining across blocks: stage the block,
+// inv_from_slot, recon_luma16 onto one pred load), the fifth inverts U and V through the same slot and
 // re-interleaves them into m_C -- lane (c, h) then holds row c, columns 16h .. 16h+15 of both planes = chroma row (c & 7) of
 // tiles 2h and 2h+1 of tile row (c >> 3): the two 16-byte m_C rows dct32_chroma_from_tiles_kernel loads, here one pred load
 // and one store each.  m_I is not touched; recon == pred is allowed, as above.
@@ -572,37 +473,19 @@ __global__ __launch_bounds__(256) void dct32_inv_ctu_to_tiles_kernel(const int16
     if (ctu >= n_ctus) return;
     const unsigned c = lane & 31, h = lane >> 5;
     const size_t cy = ctu / ctus_x, cx = ctu - cy * ctus_x;
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
+    const TileLanes t = tile_lanes(lane);
     unsigned col_base[4];
-    {
-        const unsigned u = (unsigned)kappa((int)c);
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) col_base[j] = 16u * h * 64u + ((((u >> 3) ^ j) & 3u) << 4) + (u & 7u) * 2u;
-    }
+    column_base(c, h, col_base);
     const char *src = reinterpret_cast<const char *>(coef + ctu * 6144) + lane * 16;
     const LaneConsts k = load_consts(ops, lane);
-    v16i c2r;
-    {
-        const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
-    }
+    const v16i c2r = load_c2r(ops, h);
     // one 32x32 block, given as the lane's two linear 16-byte pieces -> row c, columns 16h .. 16h+15 of the inverse
     auto inverse = [&](const v4i &g0, const v4i &g1, v4i &o0, v4i &o1) {
         __builtin_amdgcn_wave_barrier();                                   // a previous block's column reads are done with the slot
-        *reinterpret_cast<v4i *>(slot + lin0) = g0;
-        *reinterpret_cast<v4i *>(slot + lin1) = g1;
+        *reinterpret_cast<v4i *>(slot + t.lin0) = g0;
+        *reinterpret_cast<v4i *>(slot + t.lin1) = g1;
         __builtin_amdgcn_wave_barrier();
-        uint32_t w[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const uint32_t e0 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m) >> 2) & 3] + (2 * m) * 64);
-            const uint32_t e1 = *reinterpret_cast<const uint16_t *>(slot + col_base[((2 * m + 1) >> 2) & 3] + (2 * m + 1) * 64);
-            w[m] = e0 | (e1 << 16);
-        }
-        v4i lo, hi;
-        split_planes(v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]}, lo, hi);
-        inv_passes(lo, hi, k, c2r, o0, o1);
+        inv_from_slot(slot, col_base, k, c2r, o0, o1);
     };
     if (part < 4) {
         const v4i g0 = load16<true>(src + part * 2048), g1 = load16<true>(src + part * 2048 + 1024);
@@ -670,21 +553,20 @@ hipError_t launch_dct32(bool inverse, const int16_t *d_in, int16_t *d_out, size_
     const unsigned tpb = cfg.wg_threads;                       // 64 .. 256, multiple of 64
     const size_t waves_per_wg = tpb / 64;
     const unsigned bpw = units_per_wave_for(cfg, n_blocks);
-    const size_t waves = (n_blocks + bpw - 1) / bpw;
-    const size_t wgs = (waves + waves_per_wg - 1) / waves_per_wg;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    unsigned wgs;
+    if (hipError_t e = wave_grid((n_blocks + bpw - 1) / bpw, waves_per_wg, &wgs)) return e;
     const size_t lds = waves_per_wg * (size_t)cfg.lds_bytes_per_wave;   // 2 KiB used per wave; the rest caps the resident waves per CU
-    if (inverse) hipLaunchKernelGGL(dct32_lds_kernel<true>, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_in, d_out, n_blocks, d_ops, bpw);
-    else         hipLaunchKernelGGL(dct32_lds_kernel<false>, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_in, d_out, n_blocks, d_ops, bpw);
+    if (inverse) hipLaunchKernelGGL(dct32_lds_kernel<true>, dim3(wgs), dim3(tpb), lds, stream, d_in, d_out, n_blocks, d_ops, bpw);
+    else         hipLaunchKernelGGL(dct32_lds_kernel<false>, dim3(wgs), dim3(tpb), lds, stream, d_in, d_out, n_blocks, d_ops, bpw);
     return hipGetLastError();
 }
 
 hipError_t launch_dct32_pass(const int16_t *d_in, int16_t *d_out, size_t n_blocks, int shift, const DctOps *d_fwd_ops, hipStream_t stream)
 {
     if (n_blocks == 0) return hipSuccess;
-    const size_t wgs = (n_blocks + 3) / 4;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dct32_pass_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_in, d_out, n_blocks, d_fwd_ops, shift);
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_blocks, 4, &wgs)) return e;
+    hipLaunchKernelGGL(dct32_pass_kernel, dim3(wgs), dim3(256), 0, stream, d_in, d_out, n_blocks, d_fwd_ops, shift);
     return hipGetLastError();
 }
 
@@ -694,14 +576,15 @@ static hipError_t launch_dct32_fwdinv_depth(const int16_t *d_in, int16_t *d_coef
 {
     const unsigned tpb = (unsigned)cfg.wg_threads;
     const unsigned bpw = units_per_wave_for(cfg, n_blocks);
-    const size_t wpw = tpb / 64, waves = (n_blocks + bpw - 1) / bpw, wgs = (waves + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid((n_blocks + bpw - 1) / bpw, wpw, &wgs)) return e;
     const unsigned need = (DEPTH + 1) * 2048u;                                 // input slots + the converter
     const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave < need ? need : (unsigned)cfg.lds_bytes_per_wave;
     const size_t lds = wpw * (size_t)per_wave;
     if (lds > 65536) return hipErrorInvalidValue;
-    if (d_coef) hipLaunchKernelGGL((dct32_fwdinv_kernel<DEPTH, true>), dim3((unsigned)wgs), dim3(tpb), lds, stream, d_in, d_coef, d_recon, n_blocks, d_fwd_ops, d_inv_acc_ops, bpw, per_wave);
-    else        hipLaunchKernelGGL((dct32_fwdinv_kernel<DEPTH, false>), dim3((unsigned)wgs), dim3(tpb), lds, stream, d_in, d_coef, d_recon, n_blocks, d_fwd_ops, d_inv_acc_ops, bpw, per_wave);
+    if (d_coef) hipLaunchKernelGGL((dct32_fwdinv_kernel<DEPTH, true>), dim3(wgs), dim3(tpb), lds, stream, d_in, d_coef, d_recon, n_blocks, d_fwd_ops, d_inv_acc_ops, bpw, per_wave);
+    else        hipLaunchKernelGGL((dct32_fwdinv_kernel<DEPTH, false>), dim3(wgs), dim3(tpb), lds, stream, d_in, d_coef, d_recon, n_blocks, d_fwd_ops, d_inv_acc_ops, bpw, per_wave);
     return hipGetLastError();
 }
 
@@ -722,10 +605,11 @@ hipError_t launch_dct32_from_tiles(const x266_ref_block_t *d_cur, const x266_ref
     const size_t n_blocks = (size_t)blocks_x * (size_t)(height / 32);
     if (n_blocks == 0) return hipSuccess;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, wgs = (n_blocks + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_blocks, wpw, &wgs)) return e;
     const size_t lds = wpw * (size_t)cfg.lds_bytes_per_wave;
-    hipLaunchKernelGGL(dct32_from_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_cur, d_pred, d_out, blocks_x, width / 16, n_blocks, d_fwd_ops);
+    hipLaunchKernelGGL(dct32_from_tiles_kernel, dim3(wgs), dim3(tpb), lds, stream, d_cur, d_pred, d_out, blocks_x, width / 16, n_blocks, d_fwd_ops);
     return hipGetLastError();
 }
 
@@ -736,12 +620,13 @@ hipError_t launch_dct32_chroma_from_tiles(const x266_ref_block_t *d_cur, const x
     const size_t n_ctus = (size_t)ctus_x * (size_t)(height / 64);
     if (n_ctus == 0) return hipSuccess;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, wgs = (n_ctus + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_ctus, wpw, &wgs)) return e;
     // a wave lives for two blocks here: 12 KiB charged per wave (13 resident per CU) instead of the forward kernel's 8 -- paired on a 32768^2 frame
     // 0.332 against 0.340 ms, 0.97 of the box's copy of the same bytes (tools/probes/gpu_chroma_shapes.py, profiles/r06_chroma_shapes.txt)
     const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave < 12288u ? 12288u : (unsigned)cfg.lds_bytes_per_wave;
-    hipLaunchKernelGGL(dct32_chroma_from_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_cur, d_pred, d_out_u, d_out_v, block_pitch,
+    hipLaunchKernelGGL(dct32_chroma_from_tiles_kernel, dim3(wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_cur, d_pred, d_out_u, d_out_v, block_pitch,
                        ctus_x, width / 16, n_ctus, d_fwd_ops, per_wave);
     return hipGetLastError();
 }
@@ -753,10 +638,11 @@ hipError_t launch_dct32_ctu_from_tiles(const x266_ref_block_t *d_cur, const x266
     const size_t n_ctus = (size_t)ctus_x * (size_t)(height / 64);
     if (n_ctus == 0) return hipSuccess;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, units = n_ctus * 5, wgs = (units + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_ctus * 5, wpw, &wgs)) return e;
     const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave;
-    hipLaunchKernelGGL(dct32_ctu_from_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_cur, d_pred, d_out,
+    hipLaunchKernelGGL(dct32_ctu_from_tiles_kernel, dim3(wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_cur, d_pred, d_out,
                        ctus_x, width / 16, n_ctus, d_fwd_ops, per_wave);
     return hipGetLastError();
 }
@@ -771,10 +657,10 @@ hipError_t launch_dct32_inv_to_tiles(const int16_t *d_coef, const x266_ref_block
     const unsigned tpb = (unsigned)cfg.wg_threads;
     const size_t wpw = tpb / 64;
     const unsigned bpw = units_per_wave_for(cfg, n_blocks);
-    const size_t waves = (n_blocks + bpw - 1) / bpw, wgs = (waves + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    unsigned wgs;
+    if (hipError_t e = wave_grid((n_blocks + bpw - 1) / bpw, wpw, &wgs)) return e;
     const size_t lds = wpw * (size_t)cfg.lds_bytes_per_wave;
-    hipLaunchKernelGGL(dct32_inv_to_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_coef, d_pred, d_recon, blocks_x, width / 16, n_blocks, d_inv_ops, bpw);
+    hipLaunchKernelGGL(dct32_inv_to_tiles_kernel, dim3(wgs), dim3(tpb), lds, stream, d_coef, d_pred, d_recon, blocks_x, width / 16, n_blocks, d_inv_ops, bpw);
     return hipGetLastError();
 }
 
@@ -785,10 +671,11 @@ hipError_t launch_dct32_inv_ctu_to_tiles(const int16_t *d_coef, const x266_ref_b
     const size_t n_ctus = (size_t)ctus_x * (size_t)(height / 64);
     if (n_ctus == 0) return hipSuccess;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, units = n_ctus * 5, wgs = (units + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_ctus * 5, wpw, &wgs)) return e;
     const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave;
-    hipLaunchKernelGGL(dct32_inv_ctu_to_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_coef, d_pred, d_recon,
+    hipLaunchKernelGGL(dct32_inv_ctu_to_tiles_kernel, dim3(wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_coef, d_pred, d_recon,
                        ctus_x, width / 16, n_ctus, d_inv_ops, per_wave);
     return hipGetLastError();
 }

@@ -321,9 +321,7 @@ __global__ __launch_bounds__(256) void intra32_residual_dct32_kernel(const x266_
     }
     const LaneConsts k = load_consts(ops, lane);
     __builtin_amdgcn_wave_barrier();
-    const v4i bias = {(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u};
-    const v16i round1 = {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8};
-    const unsigned c = lane & 31, h = lane >> 5;
+    const TileLanes t = tile_lanes(lane);
 #pragma unroll
     for (int j = 0; j < kFusedUnits; ++j) {
         if (j >= count) break;
@@ -332,16 +330,10 @@ __global__ __launch_bounds__(256) void intra32_residual_dct32_kernel(const x266_
         uint32_t px[4];
         if (predict_line16<true>(mode, left, top, ext, lane, px)) turn_columns_to_fragment(tile, lane, px);
         const v4i pv = {(int)px[0], (int)px[1], (int)px[2], (int)px[3]};
-        v16i acc = mfma(sv[j] ^ bias, k.p1, round1);
-        acc = mfma(pv ^ bias, k.tr, acc);                         // k.tr = -p1 in the forward tables
-        v4i o0, o1;
-        fwd_finish<4, 11>(acc, k, o0, o1);
+        v4i o0, o1, s0, s1;
+        fwd_from_pixels(sv[j], pv, k, o0, o1);
         __builtin_amdgcn_wave_barrier();
-        *reinterpret_cast<v4i *>(conv + lds_slot(c, 2 * h)) = o0;
-        *reinterpret_cast<v4i *>(conv + lds_slot(c, 2 * h + 1)) = o1;
-        __builtin_amdgcn_wave_barrier();
-        const v4i s0 = *reinterpret_cast<const v4i *>(conv + lds_slot(lane >> 2, lane & 3));
-        const v4i s1 = *reinterpret_cast<const v4i *>(conv + lds_slot(16 + (lane >> 2), lane & 3));
+        frag_to_linear(conv, t, o0, o1, s0, s1);
         char *dst = reinterpret_cast<char *>(coef) + (unit0 + j) * 2048 + lane * 16;
         store16_sc1nt(dst, s0);
         store16_sc1nt(dst + 1024, s1);
@@ -453,11 +445,11 @@ hipError_t launch_intra32_predict(const x266_intra_ref_t *d_refs, const uint8_t 
     if (rounds < 1) rounds = 1;
     while (rounds > 1 && n / (size_t)(kUnits * rounds) < 8192) --rounds;      // small batches: keep the grid large enough to fill the chip
     const size_t per_wave = (size_t)kUnits * rounds;
-    const size_t waves = (n + per_wave - 1) / per_wave, wgs = (waves + 3) / 4;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    unsigned wgs;
+    if (hipError_t e = wave_grid((n + per_wave - 1) / per_wave, 4, &wgs)) return e;
     // (not write-bound: capping the resident waves the way the write-only stream likes it -- 10 per CU, 7.4 TB/s -- slows this
     //  kernel from 5.4 to 3.2-5.1 TB/s written; it is paced by its own VALU + LDS work, profiles/r04_intra_occupancy.txt)
-    hipLaunchKernelGGL(intra32_predict_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_refs, d_modes, d_ref_index, d_pred, n, rounds);
+    hipLaunchKernelGGL(intra32_predict_kernel, dim3(wgs), dim3(256), 0, stream, d_refs, d_modes, d_ref_index, d_pred, n, rounds);
     return hipGetLastError();
 }
 
@@ -468,10 +460,10 @@ hipError_t launch_intra32_residual_dct32(const x266_intra_ref_t *d_refs, const u
     // launch shape (tools/probes/gpu_intra_fused.py over units 1 / 2 / 4 / 7 x workgroup 64 / 128 / 256 x LDS charge, profiles/r05_intra_fused.txt): everything
     // from 2 units per wave up lies within 3 %, occupancy caps only cost -- the kernel runs at what its 1 : 2 read : write mix allows
     constexpr int kUnitsPerWave = 4;
-    const size_t waves = (n + kUnitsPerWave - 1) / kUnitsPerWave, wgs = (waves + 3) / 4;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    unsigned wgs;
+    if (hipError_t e = wave_grid((n + kUnitsPerWave - 1) / kUnitsPerWave, 4, &wgs)) return e;
     constexpr unsigned per_wave = (unsigned)((fused_slot_bytes(kUnitsPerWave) + 15) & ~15);
-    hipLaunchKernelGGL(intra32_residual_dct32_kernel<kUnitsPerWave>, dim3((unsigned)wgs), dim3(256), 4 * per_wave, stream, d_refs, d_modes, d_ref_index, d_src, d_coef, n, d_fwd_ops, per_wave);
+    hipLaunchKernelGGL(intra32_residual_dct32_kernel<kUnitsPerWave>, dim3(wgs), dim3(256), 4 * per_wave, stream, d_refs, d_modes, d_ref_index, d_src, d_coef, n, d_fwd_ops, per_wave);
     return hipGetLastError();
 }
 
@@ -483,9 +475,9 @@ hipError_t launch_intra32_costs(const x266_intra_ref_t *d_refs, const uint8_t *d
                                 size_t n, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    const size_t wgs = (n + 3) / 4;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(intra32_costs_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_refs, d_src, d_costs, d_best_mode, n);
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n, 4, &wgs)) return e;
+    hipLaunchKernelGGL(intra32_costs_kernel, dim3(wgs), dim3(256), 0, stream, d_refs, d_src, d_costs, d_best_mode, n);
     return hipGetLastError();
 }
 

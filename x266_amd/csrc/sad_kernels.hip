@@ -110,9 +110,9 @@ hipError_t launch_sad(int edge, const uint8_t *d_a, const uint8_t *d_b, uint32_t
     const size_t lds = edge == 4 ? 8192 : (lds_per_wg > 0 ? (size_t)lds_per_wg : 32768);
     if (wpw > 4 || lds > 65536) return hipErrorInvalidValue;
     const size_t waves = (chunks + 64 * steps - 1) / (64 * steps);
-    const size_t wgs = (waves + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    dim3 grid((unsigned)wgs), block(64 * wpw);
+    unsigned wgs;
+    if (hipError_t e = wave_grid(waves, wpw, &wgs)) return e;
+    dim3 grid(wgs), block(64 * wpw);
     switch (edge) {
     case 4:  hipLaunchKernelGGL((sad_kernel<0, 1>), grid, block, lds, stream, d_a, d_b, d_out, n_blocks); break;
     case 8:  hipLaunchKernelGGL((sad_kernel<2, 4>), grid, block, lds, stream, d_a, d_b, d_out, n_blocks); break;

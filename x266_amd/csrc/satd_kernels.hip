@@ -619,13 +619,12 @@ hipError_t launch_satd8x8(const int16_t *d_diff, uint32_t *d_out, size_t n_block
     if (per_wave < min_lds) per_wave = min_lds;
     const size_t waves_per_wg = tpb / 64;
     const unsigned gpw = units_per_wave_for(c, groups);
-    const size_t waves = (groups + gpw - 1) / gpw;
-    const size_t wgs = (waves + waves_per_wg - 1) / waves_per_wg;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    unsigned wgs;
+    if (hipError_t e = wave_grid((groups + gpw - 1) / gpw, waves_per_wg, &wgs)) return e;
     const size_t lds = waves_per_wg * (size_t)per_wave;
     if (lds > 65536) return hipErrorInvalidValue;
-    if (dma) hipLaunchKernelGGL(satd8x8_dma_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_diff, d_out, n_blocks, gpw, per_wave);
-    else     hipLaunchKernelGGL(satd8x8_lds_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_diff, d_out, n_blocks, gpw, per_wave);
+    if (dma) hipLaunchKernelGGL(satd8x8_dma_kernel, dim3(wgs), dim3(tpb), lds, stream, d_diff, d_out, n_blocks, gpw, per_wave);
+    else     hipLaunchKernelGGL(satd8x8_lds_kernel, dim3(wgs), dim3(tpb), lds, stream, d_diff, d_out, n_blocks, gpw, per_wave);
     return hipGetLastError();
 }
 

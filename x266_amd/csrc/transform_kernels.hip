@@ -209,15 +209,6 @@ __device__ __forceinline__ void inv_tile_in_slot(unsigned char *slot, int lane, 
     inv_tile_in_slot_with<LOGN, decltype(group), true>(slot, lane, k, group);
 }
 
-__device__ __forceinline__ v16i load_c2r(const DctOps *__restrict__ ops, int h)
-{
-    const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
-    v16i c2r;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
-    return c2r;
-}
-
 // Inverse transforms of the set (UNPINNED upstream; columns first, shifts 7 and 12, int16 clipping
 // after each pass -- DESIGN.md section 10), contiguous batches, same block-diagonal tile idea.  The
 // first contraction runs over the tile's ROW index, so each lane reads its COLUMN out of the staged
@@ -802,10 +793,11 @@ hipError_t launch_transform_small(int log2n, const int16_t *d_in, int16_t *d_out
     const unsigned tpw = units_per_wave_for(cfg, tiles);
     const size_t waves = (tiles + tpw - 1) / tpw;
     const unsigned tpb = (unsigned)cfg.wg_threads;                // same launch shape as the staged DCT32 kernel
-    const size_t wpw = tpb / 64, wgs = (waves + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(waves, wpw, &wgs)) return e;
     const size_t lds = wpw * (size_t)cfg.lds_bytes_per_wave;
-    dim3 grid((unsigned)wgs), block(tpb);
+    dim3 grid(wgs), block(tpb);
 #define X266_TRL(L) hipLaunchKernelGGL((tr_fwd_small_lds_kernel<L>), grid, block, lds, stream, d_in, d_out, n_blocks, d_ops, d_offsets, tpw)
     if (log2n == 2) X266_TRL(2); else if (log2n == 3) X266_TRL(3); else if (log2n == 4) X266_TRL(4);
     else if (log2n == 5 && d_offsets) X266_TRL(5);                     // contiguous 32x32 batches are the DCT32 kernel's
@@ -823,10 +815,11 @@ hipError_t launch_transform_small_inv(int log2n, const int16_t *d_in, int16_t *d
     const unsigned tpw = units_per_wave_for(cfg, tiles);
     const size_t waves = (tiles + tpw - 1) / tpw;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, wgs = (waves + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(waves, wpw, &wgs)) return e;
     const size_t lds = wpw * (size_t)cfg.lds_bytes_per_wave;
-    dim3 grid((unsigned)wgs), block(tpb);
+    dim3 grid(wgs), block(tpb);
 #define X266_TRI(L) hipLaunchKernelGGL((tr_inv_small_lds_kernel<L>), grid, block, lds, stream, d_in, d_out, n_blocks, d_ops, d_offsets, tpw)
     if (log2n == 2) X266_TRI(2); else if (log2n == 3) X266_TRI(3); else if (log2n == 4) X266_TRI(4);
     else if (log2n == 5 && d_offsets) X266_TRI(5);
@@ -842,11 +835,12 @@ hipError_t launch_transform_tiles(bool inverse, const int16_t *d_in, int16_t *d_
     const unsigned tpw = units_per_wave_for(cfg, n_tiles);
     const size_t waves = (n_tiles + tpw - 1) / tpw;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, wgs = (waves + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(waves, wpw, &wgs)) return e;
     const unsigned per_wave = (unsigned)(cfg.lds_bytes_per_wave < 6144 ? 6144 : (cfg.lds_bytes_per_wave + 15) & ~15);   // table + two tiles, then padding
     const size_t lds = wpw * (size_t)per_wave;
-    dim3 grid((unsigned)wgs), block(tpb);
+    dim3 grid(wgs), block(tpb);
 #define X266_TT(INV) hipLaunchKernelGGL((tr_tiles_kernel<INV>), grid, block, lds, stream, d_in, d_out, n_tiles, d_tile_offsets, d_tile_class, d_tab, tpw, per_wave)
     if (inverse) X266_TT(true); else X266_TT(false);
 #undef X266_TT
@@ -862,15 +856,16 @@ hipError_t launch_transform_ctu_tiles(bool inverse, const x266_ref_block_t *d_cu
     const size_t n_ctus = (size_t)ctus_x * (size_t)((height + 63) / 64);
     if (n_ctus == 0) return hipSuccess;
     const unsigned tpb = (unsigned)cfg.wg_threads;
-    const size_t wpw = tpb / 64, wgs = (n_ctus + wpw - 1) / wpw;
-    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_ctus, wpw, &wgs)) return e;
     const unsigned per_wave = (unsigned)(cfg.lds_bytes_per_wave < 6144 ? 6144 : (cfg.lds_bytes_per_wave + 15) & ~15);   // table + two region slots, then padding
     const size_t lds = wpw * (size_t)per_wave;
     if (inverse)
-        hipLaunchKernelGGL(tr_ctu_to_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_coef_in, d_class, d_pred, d_recon, d_tab,
+        hipLaunchKernelGGL(tr_ctu_to_tiles_kernel, dim3(wgs), dim3(tpb), lds, stream, d_coef_in, d_class, d_pred, d_recon, d_tab,
                            ctus_x, width / 16, height / 16, n_ctus, per_wave);
     else
-        hipLaunchKernelGGL(tr_ctu_from_tiles_kernel, dim3((unsigned)wgs), dim3(tpb), lds, stream, d_cur, d_pred, d_class, d_coef_out, d_tab,
+        hipLaunchKernelGGL(tr_ctu_from_tiles_kernel, dim3(wgs), dim3(tpb), lds, stream, d_cur, d_pred, d_class, d_coef_out, d_tab,
                            ctus_x, width / 16, height / 16, n_ctus, per_wave);
     return hipGetLastError();
 }

@@ -141,6 +141,15 @@ inline unsigned units_per_wave_for(const LaunchCfg &cfg, size_t n_units)
     return u;
 }
 
+// Workgroups of a one-dimensional grid of n_waves waves, waves_per_wg to a workgroup; a grid dimension holds 2^31 - 1 at most
+inline hipError_t wave_grid(size_t n_waves, size_t waves_per_wg, unsigned *wgs)
+{
+    const size_t n = (n_waves + waves_per_wg - 1) / waves_per_wg;
+    if (n > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    *wgs = (unsigned)n;
+    return hipSuccess;
+}
+
 hipError_t launch_intra32_predict(const x266_intra_ref_t *d_refs, const uint8_t *d_modes, const uint32_t *d_ref_index,
                                   uint8_t *d_pred, size_t n, int rounds, hipStream_t stream);
 hipError_t launch_intra32_residual_dct32(const x266_intra_ref_t *d_refs, const uint8_t *d_modes, const uint32_t *d_ref_index, const uint8_t *d_src,

@@ -1,6 +1,10 @@
 // x266_mfma_blocks.hpp -- device-side building blocks shared by the transform kernels:
-// byte-plane split / re-pack around v_mfma_i32_32x32x32_i8 and the two-pass forward
-// transform of one 32x32 tile held in registers (see dct32_kernels.hip for the derivation).
+// byte-plane split / re-pack around v_mfma_i32_32x32x32_i8, the two-pass forward transform of one
+// 32x32 tile held in registers (fwd_block; fwd_from_pixels for 8-bit cur / pred rows, chroma_plane
+// for their U,V de-interleave), the inverse's passes with their constants and column gather
+// (inv_passes, load_c2r, column_base / read_column_planes), the wave-private LDS slot as layout
+// converter (lds_slot, TileLanes, frag_to_linear, fwd_tile_staged) and the reconstruction into pixels
+// (recon_luma16 / recon_chroma16).  See dct32_kernels.hip for the derivation.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -122,6 +126,26 @@ __device__ __forceinline__ void fwd_block(const v4i &w0, const v4i &w1, const La
     fwd_finish<S1, S2>(acc, k, o0, o1);
 }
 
+// The forward transform of cur - pred on 8-bit pixels as they are (dct32_kernels.hip, "fused residual + forward transform"):
+// pass 1 is G*cur + (-G)*pred, ONE byte plane per frame, the +128 of the (x ^ 0x80) signed-offset trick cancels and the
+// rounding constant is the MFMA's inline C operand.  a / b: the lane's 16 cur / pred pixels (row c, columns 16h .. 16h+15).
+__device__ __forceinline__ void fwd_from_pixels(const v4i &a, const v4i &b, const LaneConsts &k, v4i &o0, v4i &o1)
+{
+    const v4i bias = {(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u};
+    const v16i round1 = {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8};
+    v16i acc = mfma(a ^ bias, k.p1, round1);
+    acc = mfma(b ^ bias, k.tr, acc);                          // k.tr = -p1 in the forward tables
+    fwd_finish<4, 11>(acc, k, o0, o1);
+}
+
+// One chroma plane's 16 pixels out of two m_C lines (8 interleaved U,V pairs each): sel = kSelU / kSelV
+constexpr uint32_t kSelU = 0x06040200u, kSelV = 0x07050301u;       // even bytes = U, odd bytes = V
+__device__ __forceinline__ v4i chroma_plane(const v4i &a0, const v4i &a1, uint32_t sel)
+{
+    return v4i{(int)bperm((uint32_t)a0[1], (uint32_t)a0[0], sel), (int)bperm((uint32_t)a0[3], (uint32_t)a0[2], sel),
+               (int)bperm((uint32_t)a1[1], (uint32_t)a1[0], sel), (int)bperm((uint32_t)a1[3], (uint32_t)a1[2], sel)};
+}
+
 // ---- one 32x32 tile through a wave-private 2 KiB LDS slot (dct32_kernels.hip, "LDS-staged variant") ----------
 // Chunk (row r, quarter q) lives at r*64 + ((q ^ ((r >> 2) & 3)) << 4): linear writes, row-per-lane fragment reads and
 // the way back are all bank-conflict-free.
@@ -130,27 +154,42 @@ __device__ __forceinline__ unsigned lds_slot(unsigned row, unsigned quarter)
     return row * 64u + ((quarter ^ ((row >> 2) & 3u)) << 4);
 }
 
-// g0 / g1: the lane's two 16-byte pieces of the tile in LINEAR order (bytes lane*16 and 1024 + lane*16);
-// returns the transformed tile's pieces in the same linear order.
+// A lane's four 16-byte chunks of a slot: lin0 / lin1 = its pieces of the tile in LINEAR order (bytes lane*16 and 1024 + lane*16, what a
+// 1 KiB-linear global instruction moves), frag0 / frag1 = its fragment, row (lane & 31), columns 16 (lane >> 5) .. +15.
+struct TileLanes {
+    unsigned lin0, lin1, frag0, frag1;
+};
+__device__ __forceinline__ TileLanes tile_lanes(int lane)
+{
+    const unsigned c = lane & 31, h = lane >> 5;
+    return {lds_slot(lane >> 2, lane & 3), lds_slot(16 + (lane >> 2), lane & 3), lds_slot(c, 2 * h), lds_slot(c, 2 * h + 1)};
+}
+
+// the slot as layout converter on the way out: fragments (o0, o1) in, the same tile's linear pieces (s0, s1) out.  The barriers that
+// order this against the slot's previous and next use are the caller's.
+__device__ __forceinline__ void frag_to_linear(unsigned char *slot, const TileLanes &t, const v4i &o0, const v4i &o1, v4i &s0, v4i &s1)
+{
+    *reinterpret_cast<v4i *>(slot + t.frag0) = o0;
+    *reinterpret_cast<v4i *>(slot + t.frag1) = o1;
+    __builtin_amdgcn_wave_barrier();
+    s0 = *reinterpret_cast<const v4i *>(slot + t.lin0);
+    s1 = *reinterpret_cast<const v4i *>(slot + t.lin1);
+}
+
+// g0 / g1: the lane's two linear pieces of the tile; returns the transformed tile's pieces in the same linear order.
 template <int S1, int S2>
 __device__ __forceinline__ void fwd_tile_staged(unsigned char *slot, int lane, const LaneConsts &k, const v4i &g0, const v4i &g1, v4i &s0, v4i &s1)
 {
-    const unsigned c = lane & 31, h = lane >> 5;
-    const unsigned lin0 = lds_slot(lane >> 2, lane & 3), lin1 = lds_slot(16 + (lane >> 2), lane & 3);
-    const unsigned frag0 = lds_slot(c, 2 * h), frag1 = lds_slot(c, 2 * h + 1);
-    *reinterpret_cast<v4i *>(slot + lin0) = g0;
-    *reinterpret_cast<v4i *>(slot + lin1) = g1;
+    const TileLanes t = tile_lanes(lane);
+    *reinterpret_cast<v4i *>(slot + t.lin0) = g0;
+    *reinterpret_cast<v4i *>(slot + t.lin1) = g1;
     __builtin_amdgcn_wave_barrier();
-    const v4i a0 = *reinterpret_cast<const v4i *>(slot + frag0);
-    const v4i a1 = *reinterpret_cast<const v4i *>(slot + frag1);
+    const v4i a0 = *reinterpret_cast<const v4i *>(slot + t.frag0);
+    const v4i a1 = *reinterpret_cast<const v4i *>(slot + t.frag1);
     v4i o0, o1;
     fwd_block<S1, S2>(a0, a1, k, o0, o1);
     __builtin_amdgcn_wave_barrier();
-    *reinterpret_cast<v4i *>(slot + frag0) = o0;
-    *reinterpret_cast<v4i *>(slot + frag1) = o1;
-    __builtin_amdgcn_wave_barrier();
-    s0 = *reinterpret_cast<const v4i *>(slot + lin0);
-    s1 = *reinterpret_cast<const v4i *>(slot + lin1);
+    frag_to_linear(slot, t, o0, o1, s0, s1);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -208,6 +247,39 @@ __device__ __forceinline__ void inv_passes(const v4i &zlo, const v4i &zhi, const
                                            const v16i &c2r, v4i &o0, v4i &o1)
 {
     inv_passes_with(zlo, zhi, k, [&](int g) { return v4i{c2r[4 * g], c2r[4 * g + 1], c2r[4 * g + 2], c2r[4 * g + 3]}; }, o0, o1);
+}
+
+// the pass-B constants depend on (half, register) only: two scalar loads (wave-uniform addresses) and a per-lane select
+// instead of 64 bytes of vector loads per lane and wave
+__device__ __forceinline__ v16i load_c2r(const DctOps *__restrict__ ops, int h)
+{
+    const int *__restrict__ s0 = ops->c2r[0], *__restrict__ s1 = ops->c2r[32];
+    v16i c2r;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) c2r[r] = h ? s1[r] : s0[r];
+    return c2r;
+}
+
+// The inverse contracts over the block's ROW index first: with the tile staged in a slot (lds_slot layout) lane (c, h) simply reads
+// its COLUMN u = kappa(c), rows 16h .. 16h+15.  Byte offset of element (row 16h + t, column u): base[(t >> 2) & 3] + 64 t.
+__device__ __forceinline__ void column_base(unsigned c, unsigned h, unsigned (&base)[4])
+{
+    const unsigned u = (unsigned)kappa((int)c);
+#pragma unroll
+    for (unsigned j = 0; j < 4; ++j) base[j] = 16u * h * 64u + ((((u >> 3) ^ j) & 3u) << 4) + (u & 7u) * 2u;
+}
+
+// 16 x ds_read_u16 down the lane's column, then the byte planes inv_passes takes
+__device__ __forceinline__ void read_column_planes(const unsigned char *slot, const unsigned (&base)[4], v4i &lo, v4i &hi)
+{
+    uint32_t w[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const uint32_t e0 = *reinterpret_cast<const uint16_t *>(slot + base[((2 * m) >> 2) & 3] + (2 * m) * 64);
+        const uint32_t e1 = *reinterpret_cast<const uint16_t *>(slot + base[((2 * m + 1) >> 2) & 3] + (2 * m + 1) * 64);
+        w[m] = e0 | (e1 << 16);
+    }
+    split_planes(v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]}, v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]}, lo, hi);
 }
 
 // ---- reconstruction: clip8(pred + residual), exact for every int16 residual --------------------------------------------------
