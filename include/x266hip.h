@@ -362,10 +362,31 @@ int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, c
 /* Integer-pel luma motion compensation: one x266_me_result_t per 8x8 block in raster order of blocks (exactly the searches'
  * d_best; cost is ignored), pred[8by+y][8bx+x] = ref[clamp(8by+y+mvy, 0, H-1)][clamp(8bx+x+mvx, 0, W-1)] for any int16 vector.
  * Writes only m_Y of d_pred; m_C and m_I are left untouched, as xReconLumaDev leaves them.  Blocks read what other blocks
- * would overwrite, so d_pred overlapping d_ref or d_mv returns X266HIP_EINVAL.  Chroma is not compensated: with integer luma
- * vectors 4:2:0 chroma needs fractional-sample interpolation, for which no convention exists here yet. */
+ * would overwrite, so d_pred overlapping d_ref or d_mv returns X266HIP_EINVAL. */
 int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                        int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* 4:2:0 chroma motion compensation with the same records: the vector of 8x8 luma block (bx, by) moves the 4x4 block (bx, by) of
+ * U and of V (chroma samples 4bx..4bx+3, 4by..4by+3 of the CW x CH = W/2 x H/2 planes) by half of it.  The filter is the
+ * half-sample chroma filter of HEVC / VVC, T = (-4, 36, 36, -4), at 8-bit depth -- as recalled, unverified offline (like the
+ * DST-VII presets); the arithmetic here is the contract, not a standard text.  For any int16 vector
+ *   ix = mvx >> 1, fx = mvx & 1, iy = mvy >> 1, fy = mvy & 1    (arithmetic shift: -1 -> ix = -1, fx = 1),
+ *   S(y, x) = plane[clamp(y, 0, CH-1)][clamp(x, 0, CW-1)]       (the inter stage's edge rule, on the chroma plane),
+ * and for chroma sample (x, y) of either plane, with clip8 the clamp to 0..255:
+ *   fx = 0, fy = 0:  out = S(y+iy, x+ix)                                                   (a pure gather)
+ *   fx = 1, fy = 0:  out = clip8((sum_k T[k] * S(y+iy, x+ix+k-1) + 32) >> 6),  k = 0..3
+ *   fx = 0, fy = 1:  out = clip8((sum_k T[k] * S(y+iy+k-1, x+ix) + 32) >> 6)
+ *   fx = 1, fy = 1:  h(r) = sum_k T[k] * S(r, x+ix+k-1)          (no shift; -2040..18360)
+ *                    v = (sum_k T[k] * h(y+iy+k-1)) >> 6         (arithmetic: floors a negative sum)
+ *                    out = clip8((v + 32) >> 6)
+ * So a zero vector copies m_C, even vectors move bytes unchanged, and a constant plane stays constant for every vector.
+ * xMotionCompChromaDev writes only m_C of d_pred (both planes) and leaves m_Y and m_I untouched: after it and
+ * xMotionCompLumaDev d_pred is a whole 4:2:0 prediction.  xMotionCompDev writes m_Y and m_C in one launch, bit-identical to the
+ * luma call followed by the chroma call; m_I is never written.  Arguments as for xMotionCompLumaDev; neither call allocates,
+ * both can be captured into a graph. */
+int xMotionCompChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                         int width, int height, x266_ref_block_t *d_pred, void *stream);
+int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                   int width, int height, x266_ref_block_t *d_pred, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; buffers 16-byte
  * aligned): d_out[b] = sum |a - b|, exactly sad() of

@@ -103,6 +103,8 @@ def load_library(path=None):
     for name in ("xSatd8x8SearchFromTilesDev", "xSad8x8SearchFromTilesDev"):
         getattr(L, name).argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xMotionCompLumaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xMotionCompChromaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xMotionCompDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     for name in ("xDct32FwdBatch", "xDct32InvBatch", "xSatd8x8Batch"):
@@ -539,6 +541,12 @@ class Codec:
     def motion_comp_luma_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
         self._check(self.L.xMotionCompLumaDev(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompLumaDev")
 
+    def motion_comp_chroma_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
+        self._check(self.L.xMotionCompChromaDev(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompChromaDev")
+
+    def motion_comp_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
+        self._check(self.L.xMotionCompDev(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompDev")
+
     def search_tiles(self, cur_tiles, ref_tiles, w, h, rng, want_costs=False, metric="satd"):
         """numpy convenience around xSatd8x8SearchFromTilesDev / xSad8x8SearchFromTilesDev: two tile arrays of a w x h frame
         (uint8, 512 bytes per tile) -> (mv [nb, 2] int16, cost [nb] uint32, costs [nb, (2R+1)^2] or None), as satd_search."""
@@ -574,6 +582,24 @@ class Codec:
         dm.upload(rec)
         dp.upload(pred)
         self.motion_comp_luma_dev(dr.ptr, dm.ptr, w, h, dp.ptr)
+        self.stream_sync()
+        return dp.download(np.uint8, pred.size)
+
+    def motion_comp(self, ref_tiles, mv, w, h, base=None, planes="both"):
+        """numpy convenience around xMotionCompDev (planes="both") / xMotionCompChromaDev (planes="chroma"): as motion_comp_luma;
+        what the call does not write (m_I, and m_Y for "chroma") comes from `base`."""
+        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
+        assert ref.size == w * h * 2
+        fn = {"both": self.motion_comp_dev, "chroma": self.motion_comp_chroma_dev}[planes]
+        nb = (h // 8) * (w // 8)
+        rec = np.zeros((nb, 4), np.int16)
+        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
+        pred = np.zeros(ref.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
+        dr, dm, dp = self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(pred.nbytes)
+        dr.upload(ref)
+        dm.upload(rec)
+        dp.upload(pred)
+        fn(dr.ptr, dm.ptr, w, h, dp.ptr)
         self.stream_sync()
         return dp.download(np.uint8, pred.size)
 

@@ -349,14 +349,11 @@ __global__ __launch_bounds__(256) void recon_chroma_kernel(const x266_ref_block_
 // tile's m_Y and a wave four whole tiles (1 KiB of full lines).  The reads are a gather: a source row of 8 samples inside the
 // frame is three aligned dwords (each within one 16-byte tile row, possibly of two tiles) and two funnel shifts; rows that
 // reach past the left or right edge are read sample by sample.
-__global__ __launch_bounds__(256) void motion_comp_luma_kernel(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
-                                                               x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x,
-                                                               size_t n_rows)
+// Row i (0..15) of m_Y of tile (tx, ty): shared by the luma kernel and the fused one.
+__device__ __forceinline__ void mc_luma_row(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
+                                            x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x, size_t tile, int i)
 {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_rows) return;
-    const size_t tile = g >> 4, ty = tile / (size_t)tiles_x, tx = tile - ty * (size_t)tiles_x;
-    const int i = (int)(g & 15);
+    const size_t ty = tile / (size_t)tiles_x, tx = tile - ty * (size_t)tiles_x;
     const x266_me_result_t *m = mv + (ty * 2 + (size_t)(i >> 3)) * (size_t)(2 * tiles_x) + tx * 2;
     const uint8_t *src = reinterpret_cast<const uint8_t *>(ref);
     uint32_t out[4];
@@ -386,6 +383,146 @@ __global__ __launch_bounds__(256) void motion_comp_luma_kernel(const x266_ref_bl
         }
     }
     store16_sc1nt(reinterpret_cast<uint8_t *>(pred + tile) + i * 16, v4i{(int)out[0], (int)out[1], (int)out[2], (int)out[3]});
+}
+
+__global__ __launch_bounds__(256) void motion_comp_luma_kernel(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
+                                                               x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x,
+                                                               size_t n_rows)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_rows) return;
+    mc_luma_row(ref, mv, pred, width, height, tiles_x, g >> 4, (int)(g & 15));
+}
+
+// 4:2:0 chroma motion compensation (the convention of include/x266hip.h): the luma vector of 8x8 block (bx, by) moves the 4x4
+// block (bx, by) of U and of V by (mv >> 1) whole samples, and an odd component adds the half-sample filter (-4, 36, 36, -4)
+// along that axis.  U and V of a pair share position and taps, so a pair is filtered as one packed 2 x int16 value: the
+// horizontal stage (-2040..18360) and the 1-D results fit int16, only the vertical stage of the 2-D case is widened to 32 bits.
+typedef short v2s __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ v2s mc_half_taps(v2s a, v2s b, v2s c, v2s d)     // -4 a + 36 b + 36 c - 4 d
+{
+    return (b + c) * (short)36 - (a + d) * (short)4;
+}
+
+__device__ __forceinline__ v2s mc_round_clip8(v2s s)                         // clip8((s + 32) >> 6) on both halves
+{
+    const v2s lo = {0, 0}, hi = {255, 255};
+    return __builtin_elementwise_min(__builtin_elementwise_max((s + (short)32) >> (short)6, lo), hi);
+}
+
+// The four (U, V) pairs from chroma x = cx of one clamped chroma row (`row` points at the row's bytes in tile column 0), each
+// as a packed int16 pair: the samples themselves (fx = 0) or the unshifted horizontal filter sums (fx = 1, pairs cx - 1 .. cx + 5
+// are read).  In-frame spans are aligned dwords (two pairs each, within one 16-byte m_C row) and funnel shifts; spans that cross
+// the left or right edge are read pair by pair with clamped x.
+__device__ __forceinline__ void mc_chroma_row4(const uint8_t *row, int cx, int fx, int cw, v2s out[4])
+{
+    const int xs = cx - fx, n = 4 + 3 * fx;
+    uint32_t w[4];
+    if (xs >= 0 && xs + n - 1 <= cw - 1) {
+        const int xa = xs & ~1;
+        uint32_t d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = xa + 2 * k < cw - 2 ? xa + 2 * k : cw - 2;        // a clamped dword holds no pair that is used
+            d[k] = (k < 3 || fx) ? *reinterpret_cast<const uint32_t *>(row + (size_t)(x >> 3) * 512 + (x & 7) * 2) : 0u;
+        }
+        const int sh = (xs & 1) * 16;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
+        w[3] = d[3] >> sh;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = 0;
+#pragma unroll
+        for (int b = 0; b < 7; ++b) {
+            int x = xs + b;
+            x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
+            if (b < 4 || fx) w[b >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t *>(row + (size_t)(x >> 3) * 512 + (x & 7) * 2) << (16 * (b & 1));
+        }
+    }
+    v2s q[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        q[2 * k] = __builtin_bit_cast(v2s, bperm(0u, w[k], 0x0c010c00u));      // u | v << 16 (sel 0x0c = zero byte)
+        q[2 * k + 1] = __builtin_bit_cast(v2s, bperm(0u, w[k], 0x0c030c02u));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = fx ? mc_half_taps(q[k], q[k + 1], q[k + 2], q[k + 3]) : q[k];
+}
+
+// Half h (0 left, 1 right) of row j (0..7) of m_C of tile (tx, ty): row j & 3 of the 4x4 (U, V) blocks of one 8x8 luma block,
+// 8 bytes.  One lane per half, not per 16-byte row: a lane of the 2-D class gathers four source rows, and at the size of a
+// frame the call is bound by that chain of loads, not by bytes -- twice the lanes with half the chain each.
+__device__ __forceinline__ void mc_chroma_half(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
+                                               x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x, size_t tile, int j, int h)
+{
+    const size_t ty = tile / (size_t)tiles_x, tx = tile - ty * (size_t)tiles_x;
+    const x266_me_result_t r = mv[(ty * 2 + (size_t)(j >> 2)) * (size_t)(2 * tiles_x) + tx * 2 + (size_t)h];
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(ref) + 256;
+    const int cw = width >> 1, ch = height >> 1;
+    const int fx = r.mvx & 1, fy = r.mvy & 1;
+    const int cx = (int)(tx * 8) + 4 * h + (r.mvx >> 1), cy = (int)(ty * 8) + j + (r.mvy >> 1);
+    v2s o[4];
+    if (!fy) {
+        const int sy = cy < 0 ? 0 : (cy > ch - 1 ? ch - 1 : cy);
+        mc_chroma_row4(src + (size_t)(sy >> 3) * (size_t)tiles_x * 512 + (sy & 7) * 16, cx, fx, cw, o);
+        if (fx) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = mc_round_clip8(o[k]);
+        }
+    } else {
+        v2s t[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            int sy = cy + a - 1;
+            sy = sy < 0 ? 0 : (sy > ch - 1 ? ch - 1 : sy);
+            mc_chroma_row4(src + (size_t)(sy >> 3) * (size_t)tiles_x * 512 + (sy & 7) * 16, cx, fx, cw, t[a]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!fx) {
+                o[k] = mc_round_clip8(mc_half_taps(t[0][k], t[1][k], t[2][k], t[3][k]));
+            } else {                                                        // the sum of sums needs 32 bits; >> floors
+                int c[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int v = (36 * ((int)t[1][k][e] + (int)t[2][k][e]) - 4 * ((int)t[0][k][e] + (int)t[3][k][e])) >> 6;
+                    const int s = (v + 32) >> 6;
+                    c[e] = s < 0 ? 0 : (s > 255 ? 255 : s);
+                }
+                o[k] = v2s{(short)c[0], (short)c[1]};
+            }
+        }
+    }
+    const uint2 out = make_uint2(bperm(__builtin_bit_cast(uint32_t, o[1]), __builtin_bit_cast(uint32_t, o[0]), 0x06040200u),      // u0 v0 u1 v1
+                                 bperm(__builtin_bit_cast(uint32_t, o[3]), __builtin_bit_cast(uint32_t, o[2]), 0x06040200u));
+    __builtin_nontemporal_store(out.x | ((unsigned long long)out.y << 32),
+                                reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(pred + tile) + 256 + j * 16 + h * 8));
+}
+
+// one lane per 8-byte half of an m_C row: sixteen lanes write a tile's 128 chroma bytes, a wave the whole lines of four tiles
+__global__ __launch_bounds__(256) void motion_comp_chroma_kernel(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
+                                                                 x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x,
+                                                                 size_t n_halves)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_halves) return;
+    mc_chroma_half(ref, mv, pred, width, height, tiles_x, g >> 4, (int)(g >> 1) & 7, (int)(g & 1));
+}
+
+// m_Y and m_C in one launch, the role fixed per WAVE: a workgroup of four waves takes eight tiles, waves 0 and 1 their 128 luma
+// rows, waves 2 and 3 their 128 chroma halves -- no wave runs both code paths, every store instruction still covers whole
+// lines, and the chroma waves' longer gather overlaps the luma waves' (profiles/r10_mc_chroma.txt: under the two calls back to back).
+__global__ __launch_bounds__(256) void motion_comp_kernel(const x266_ref_block_t *__restrict__ ref, const x266_me_result_t *__restrict__ mv,
+                                                          x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x,
+                                                          size_t n_tiles)
+{
+    const int t = threadIdx.x & 127;
+    const size_t tile = (size_t)blockIdx.x * 8 + (size_t)(t >> 4);
+    if (tile >= n_tiles) return;
+    if (threadIdx.x < 128) mc_luma_row(ref, mv, pred, width, height, tiles_x, tile, t & 15);
+    else                   mc_chroma_half(ref, mv, pred, width, height, tiles_x, tile, (t >> 1) & 7, t & 1);
 }
 
 }  // namespace
@@ -485,6 +622,30 @@ hipError_t launch_motion_comp_luma(const x266_ref_block_t *d_ref, const x266_me_
     const size_t wgs = (n_rows + 255) / 256;
     if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(motion_comp_luma_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_ref, d_mv, d_pred, width, height, tiles_x, n_rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_comp_chroma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
+                                     int width, int height, hipStream_t stream)
+{
+    const int tiles_x = width / 16;
+    const size_t n_halves = (size_t)tiles_x * (size_t)(height / 16) * 16;   // one lane per 8-byte half of an m_C row
+    if (n_halves == 0) return hipSuccess;
+    const size_t wgs = (n_halves + 255) / 256;
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(motion_comp_chroma_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_ref, d_mv, d_pred, width, height, tiles_x, n_halves);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_comp(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
+                              int width, int height, hipStream_t stream)
+{
+    const int tiles_x = width / 16;
+    const size_t n_tiles = (size_t)tiles_x * (size_t)(height / 16);
+    if (n_tiles == 0) return hipSuccess;
+    const size_t wgs = (n_tiles + 7) / 8;                                    // eight tiles per four-wave workgroup
+    if (wgs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(motion_comp_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, d_ref, d_mv, d_pred, width, height, tiles_x, n_tiles);
     return hipGetLastError();
 }
 

@@ -209,6 +209,10 @@ hipError_t launch_dct32_inv_ctu_to_tiles(const int16_t *d_coef, const x266_ref_b
                                          const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_motion_comp_luma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
                                    int width, int height, hipStream_t stream);
+hipError_t launch_motion_comp_chroma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
+                                     int width, int height, hipStream_t stream);
+hipError_t launch_motion_comp(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
+                              int width, int height, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

@@ -1287,20 +1287,42 @@ int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, c
     return X266HIP_OK;
 }
 
+// The three motion compensation calls share their argument rules and differ in the planes they write.
+typedef hipError_t (*mc_launch_fn)(const x266_ref_block_t *, const x266_me_result_t *, x266_ref_block_t *, int, int, hipStream_t);
+
+static int motion_comp_call(x266hip_ctx *ctx, const char *name, mc_launch_fn launch, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                            int width, int height, x266_ref_block_t *d_pred, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
+    if (!d_ref || !d_mv || !d_pred || ((((uintptr_t)d_ref | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_mv & 7u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
+    if (ranges_overlap(d_pred, tile_bytes, d_ref, tile_bytes) || ranges_overlap(d_pred, tile_bytes, d_mv, mv_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": d_pred overlaps d_ref or d_mv").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "motion compensation launch", e);
+    return X266HIP_OK;
+}
+
 int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                        x266_ref_block_t *d_pred, void *stream)
 {
-    if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return fail(ctx, X266HIP_EINVAL, "xMotionCompLumaDev: width/height must be multiples of 16");
-    if (!d_ref || !d_mv || !d_pred || ((((uintptr_t)d_ref | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_mv & 7u))
-        return fail(ctx, X266HIP_EINVAL, "xMotionCompLumaDev: NULL or unaligned buffer");
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
-    if (ranges_overlap(d_pred, tile_bytes, d_ref, tile_bytes) || ranges_overlap(d_pred, tile_bytes, d_mv, mv_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xMotionCompLumaDev: d_pred overlaps d_ref or d_mv");
-    X_DEV(ctx);
-    hipError_t e = launch_motion_comp_luma(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "motion compensation launch", e);
-    return X266HIP_OK;
+    return motion_comp_call(ctx, "xMotionCompLumaDev", launch_motion_comp_luma, d_ref, d_mv, width, height, d_pred, stream);
+}
+
+int xMotionCompChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
+                         x266_ref_block_t *d_pred, void *stream)
+{
+    return motion_comp_call(ctx, "xMotionCompChromaDev", launch_motion_comp_chroma, d_ref, d_mv, width, height, d_pred, stream);
+}
+
+int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
+                   x266_ref_block_t *d_pred, void *stream)
+{
+    return motion_comp_call(ctx, "xMotionCompDev", launch_motion_comp, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 // ---- host-pointer batch API --------------------------------------------------
