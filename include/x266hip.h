@@ -106,20 +106,33 @@ int  xHipAutotuneReport(const x266hip_ctx *ctx, char *buf, size_t cap);
 /* batch API, device pointers (inputs already resident in HBM)               */
 /* `stream` holds a hipStream_t (NULL = the default stream).  Asynchronous:  */
 /* returns after enqueueing; use xHipStreamSync or the caller's own stream   */
-/* API to wait.  d_in / d_out must be 16-byte aligned and must not overlap.   */
+/* API to wait.  Inputs and outputs must not overlap unless a call says so.   */
 /* ------------------------------------------------------------------------ */
+/* Alignment: every ...Dev declaration below is preceded by an "Alignment in bytes" line that names each of its pointer
+ * arguments with the alignment the call's argument check enforces (1 = none); a pointer aligned to less returns
+ * X266HIP_EINVAL and launches nothing, and nothing MORE than that alignment is needed -- sample, coefficient and tile buffers
+ * 16, x266_me_result_t records and the chroma planes of the two conversion calls 8, uint32_t outputs and index / offset
+ * tables 4 (the SATD output of xDct32SatdFrameDev: 16), mode and class bytes and the pixel planes of the planar searches none
+ * (the current plane of xSad8x8SearchDev: 4).
+ * tests/test_gpu_placement.py runs every call at exactly these alignments and checks these lines against its table.
+ * A call reads nothing whose value can reach its result outside the documented extent of its inputs, and writes nothing
+ * outside the documented extent of its outputs. */
 /* 2-D forward 32x32 DCT-II, shifts 4 then 11, truncating int16 stores:
  * bit-exact with partialButterfly32 x2 as called by dct32_genNew
  * (src_tb/dct32.c:66-170,180-198).  out[v*32+u], v = vertical frequency. */
+/* Alignment in bytes: d_in 16, d_out 16. */
 int xDct32FwdBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out,
                       size_t n_blocks, void *stream);
 /* 2-D inverse (no upstream counterpart; HEVC/VVC inverse for 8-bit video:
  * column pass shift 7, row pass shift 12, int16 clipping after each pass). */
+/* Alignment in bytes: d_in 16, d_out 16. */
 int xDct32InvBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out,
                       size_t n_blocks, void *stream);
 /* The two lanes of a frame in ONE launch: xDct32FwdBatchDev of one batch and xSatd8x8BatchDev of another, bit-identical
  * to the two calls (BASELINE configs[4]: a 7680x4320 frame is 32 400 DCT32 blocks + 518 400 SATD blocks, ~15 us of kernel
- * each -- submissions, not arithmetic, pace a frame stream on one GPU).  Either count may be 0. */
+ * each -- submissions, not arithmetic, pace a frame stream on one GPU).  Either count may be 0.  All four buffers are checked
+ * for 16 bytes here, d_satd_out included (xSatd8x8BatchDev alone takes it at 4). */
+/* Alignment in bytes: d_dct_in 16, d_dct_out 16, d_diff 16, d_satd_out 16. */
 int xDct32SatdFrameDev(x266hip_ctx *ctx, const int16_t *d_dct_in, int16_t *d_dct_out, size_t n_dct_blocks,
                        const int16_t *d_diff, uint32_t *d_satd_out, size_t n_satd_blocks, void *stream);
 /* The 1-D pass by itself: partialButterfly32(src, dst, shift, line = 32) (src_tb/dct32.c:66-170; the RTL's first stage,
@@ -127,15 +140,18 @@ int xDct32SatdFrameDev(x266hip_ctx *ctx, const int16_t *d_dct_in, int16_t *d_dct
  * src[j*32 + n] + (1 << (shift-1))) >> shift) -- note the TRANSPOSED store.  xDct32PassDev(shift 4) followed by
  * xDct32PassDev(shift 11) is xDct32FwdBatchDev; on its own it lets a testbench compare the intermediate of a DUT.
  * Exact for every int16 input at shifts 1..15.  (A checking entry point: one block per wave, not a tuned kernel.) */
+/* Alignment in bytes: d_in 16, d_out 16. */
 int xDct32PassDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out, size_t n_blocks, int shift, void *stream);
 /* Forward and inverse in one pass over the batch: d_coef = forward(d_in) (may be NULL when only
  * the reconstruction is wanted), d_recon = inverse(forward(d_in)) -- the transform half of an
  * encoder's reconstruction loop; SURVEY 8(d) "fused fwd+inv", 6144 bytes per block instead of
  * 8192.  Bit-identical to xDct32FwdBatchDev followed by xDct32InvBatchDev. */
+/* Alignment in bytes: d_in 16, d_coef 16, d_recon 16. */
 int xDct32FwdInvBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_coef, int16_t *d_recon,
                          size_t n_blocks, void *stream);
 /* 8x8 Hadamard SATD of n residual blocks: bit-exact with satd8x8
- * (src_tb/satd.c:31-118), including its int16 wraparound.  d_out[n] uint32. */
+ * (src_tb/satd.c:31-118), including its int16 wraparound.  d_out[n] uint32, 4-byte aligned (d_diff 16). */
+/* Alignment in bytes: d_diff 16, d_out 4. */
 int xSatd8x8BatchDev(x266hip_ctx *ctx, const int16_t *d_diff, uint32_t *d_out,
                      size_t n_blocks, void *stream);
 /* The mixed transform set of BASELINE configs[3]: forward 2-D transforms of square N x N
@@ -157,6 +173,7 @@ int xSatd8x8BatchDev(x266hip_ctx *ctx, const int16_t *d_diff, uint32_t *d_out,
 #define X266_TR_DST7 1            /* slot 1 (DST-VII) horizontally and vertically */
 #define X266_TR_DST7_DCT2 2       /* slot 1 horizontally (along rows), slot 0 vertically: N = 4, 8, 16 */
 #define X266_TR_DCT2_DST7 3       /* slot 0 horizontally, slot 1 vertically */
+/* Alignment in bytes: d_in 16, d_out 16, d_offsets 4. */
 int xTransformFwdBatchDev(x266hip_ctx *ctx, int type, int size, const int16_t *d_in, int16_t *d_out,
                           size_t n_blocks, const uint32_t *d_offsets, void *stream);
 /* Caller-supplied 1-D transform matrices (the RTL re-uses one datapath for any tap set the same way,
@@ -185,6 +202,7 @@ int xTransformPreset(const x266hip_ctx *ctx);
 /* Inverse transforms of the same set (no upstream counterpart): columns first, shifts 7 and 12
  * (8-bit video), int16 clipping after each pass; (DCT-II, 32) contiguous is xDct32InvBatchDev.
  * d_offsets as in the forward call. */
+/* Alignment in bytes: d_in 16, d_out 16, d_offsets 4. */
 int xTransformInvBatchDev(x266hip_ctx *ctx, int type, int size, const int16_t *d_in, int16_t *d_out,
                           size_t n_blocks, const uint32_t *d_offsets, void *stream);
 /* The whole mixed set in ONE launch (BASELINE configs[3], "batched per CTU").  The buffers are sequences of
@@ -194,6 +212,7 @@ int xTransformInvBatchDev(x266hip_ctx *ctx, int type, int size, const int16_t *d
  * in order -- a CTU-ordered residual buffer whose 64x64 CTUs are four such tiles).  inverse = 0 forward,
  * 1 inverse; results identical to the per-class calls above. */
 #define X266_TILE_CLASS(type, size) ((uint8_t)((type) * 4 + ((size) == 4 ? 0 : (size) == 8 ? 1 : (size) == 16 ? 2 : 3)))
+/* Alignment in bytes: d_in 16, d_out 16, d_tile_offsets 4, d_tile_class 1. */
 int xTransformTilesDev(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16_t *d_out, size_t n_tiles,
                        const uint32_t *d_tile_offsets, const uint8_t *d_tile_class, void *stream);
 /* Full-search motion estimation with the 8x8 SATD cost (BASELINE configs[2]).
@@ -206,22 +225,25 @@ int xTransformTilesDev(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16
  * every side (rows are ref_stride bytes apart; negative offsets are read).
  * 1 <= range <= 64.  d_costs may be NULL; otherwise it receives every cost,
  * d_costs[block * (2*range+1)^2 + (dy+range)*(2*range+1) + (dx+range)].
- * Strides follow src/x266.cpp:419 (intptr_t, in bytes). */
+ * Strides follow src/x266.cpp:419 (intptr_t, in bytes).  d_cur and d_ref need no alignment and the strides no multiple;
+ * d_best is 8-byte and d_costs 4-byte aligned. */
 typedef struct x266_me_result_t {
     int16_t  mvx, mvy;      /* best displacement */
     uint32_t cost;          /* its SATD          */
 } x266_me_result_t;
+/* Alignment in bytes: d_cur 1, d_ref 1, d_best 8, d_costs 4. */
 int xSatd8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_stride,
                       const uint8_t *d_ref, intptr_t ref_stride, int width, int height,
                       int range, x266_me_result_t *d_best, uint32_t *d_costs, void *stream);
 /* The same search with the cheaper metric: cost = sum |cur - ref| over the 8x8 block,
  * i.e. sad() of riscv/programs/benchmarks/sad/sad.c:28-39 at n = 8; same candidate order and
- * tie-break.  d_cur must be 4-byte aligned with cur_stride a multiple of 4. */
+ * tie-break.  d_cur must be 4-byte aligned with cur_stride a multiple of 4; d_ref, d_best and d_costs as above. */
 /* Allocates xSatd8x8SearchDev's scratch (128 bytes per 8x8 block of the frame) for searches of frames up to
  * width x height enqueued on `stream`, so that no launch path allocates: for stream captures and real-time loops.
  * The library keeps one buffer per stream, for at most 8 streams (the least recently used one is released after
  * its last search has finished); buffers handed out under a capture live as long as the context. */
 int xHipMeScratchReserve(x266hip_ctx *ctx, void *stream, int width, int height);
+/* Alignment in bytes: d_cur 4, d_ref 1, d_best 8, d_costs 4. */
 int xSad8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_stride, const uint8_t *d_ref,
                      intptr_t ref_stride, int width, int height, int range, x266_me_result_t *d_best,
                      uint32_t *d_costs, void *stream);
@@ -235,25 +257,30 @@ typedef struct x266_ref_block_t {
 /* xConvInputFmt (src/x266.cpp:415-453) on the device: planar YUV 4:2:0 -> tiles.  width and
  * height multiples of 16; chroma stride = strdY / 2 as upstream; rows 16-byte (luma) and
  * 8-byte (chroma) aligned.  m_I is left untouched, as upstream leaves it. */
+/* Alignment in bytes: d_tiles 16, d_y 16, d_u 8, d_v 8. */
 int xConvInputFmtDev(x266hip_ctx *ctx, x266_ref_block_t *d_tiles, const uint8_t *d_y, const uint8_t *d_u,
                      const uint8_t *d_v, intptr_t strdY, int width, int height, void *stream);
 /* xConvOutput420 (src/x266.cpp:455-492) on the device: tiles -> planar YUV 4:2:0. */
+/* Alignment in bytes: d_tiles 16, d_y 16, d_u 8, d_v 8. */
 int xConvOutput420Dev(x266hip_ctx *ctx, const x266_ref_block_t *d_tiles, uint8_t *d_y, intptr_t strdY,
                       uint8_t *d_u, uint8_t *d_v, intptr_t strdC, int width, int height, void *stream);
 /* Residual formation (no upstream counterpart: upstream stops before the residual stage):
  * luma of two tiled frames, residual = cur - pred as int16, emitted as row-major blocks in
  * raster order of blocks -- block_edge 32 feeds xDct32FwdBatchDev (width, height multiples
  * of 32), block_edge 8 feeds xSatd8x8BatchDev (multiples of 16). */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_residual 16. */
 int xResidualLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                      int width, int height, int block_edge, int16_t *d_residual, void *stream);
 /* Fused residual formation + forward DCT32: d_coef[block] = DCT32(cur - pred) for every 32x32 luma
  * block of two tiled frames, blocks in raster order -- bit-identical to xResidualLumaDev(.., 32, ..)
  * followed by xDct32FwdBatchDev, without the residual ever touching HBM (half the traffic). */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_coef 16. */
 int xDct32FwdFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                           int width, int height, int16_t *d_coef, void *stream);
 /* Fused residual formation + SATD: d_out[block] = satd8x8(cur - pred) for every 8x8 luma block of
  * two tiled frames (raster order of blocks) -- bit-identical to xResidualLumaDev(.., 8, ..) followed
  * by xSatd8x8BatchDev.  width, height multiples of 16. */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_out 4. */
 int xSatd8x8FromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                          int width, int height, uint32_t *d_out, void *stream);
 /* The chroma half of the same stage.  A tile's chroma is m_C (src/x266.cpp:60): 8 rows of 8 interleaved (U, V) pairs, as
@@ -264,12 +291,14 @@ int xSatd8x8FromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const 
  * U goes to d_res_u + b * block_pitch * edge^2, of V to d_res_v + b * block_pitch * edge^2 (block_pitch >= 1, in blocks):
  * block_pitch 1 with two buffers gives two planar block streams, block_pitch 2 with d_res_v = d_res_u + edge^2 gives
  * the CTU-ordered stream U0 V0 U1 V1 ...  (No upstream counterpart, as for luma.) */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_res_u 16, d_res_v 16. */
 int xResidualChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                        int width, int height, int block_edge, int16_t *d_res_u, int16_t *d_res_v,
                        size_t block_pitch, void *stream);
 /* Fused chroma residual + forward DCT32: both 32x32 chroma blocks of every 64x64 CTU, one wave per CTU -- bit-identical to
  * xResidualChromaDev(.., 32, ..) followed by xDct32FwdBatchDev; coefficients of CTU b's U block at
  * d_coef_u + b * block_pitch * 1024, V likewise.  width, height multiples of 64. */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_coef_u 16, d_coef_v 16. */
 int xDct32FwdChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                                 int width, int height, int16_t *d_coef_u, int16_t *d_coef_v, size_t block_pitch,
                                 void *stream);
@@ -278,11 +307,13 @@ int xDct32FwdChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur,
  * bottom-left, bottom-right), q = 4 of its 32x32 U residual, q = 5 of V -- bit-identical to xDct32FwdFromTilesDev and
  * xDct32FwdChromaFromTilesDev, whose frame-raster luma and separate chroma streams it re-orders into the order a per-CTU
  * encoder loop consumes (BASELINE configs[3]: "batched per-CTU").  width, height multiples of 64. */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_coef 16. */
 int xDct32FwdCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                              int width, int height, int16_t *d_coef, void *stream);
 /* Fused chroma residual + SATD: d_out_u[t * pitch] = satd8x8 of tile t's U residual, d_out_v[t * pitch] of its V residual
  * (tiles in raster order) -- bit-identical to xResidualChromaDev(.., 8, ..) followed by xSatd8x8BatchDev.  pitch 2 with
  * d_out_v = d_out_u + 1 interleaves the two costs.  width, height multiples of 16. */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_out_u 4, d_out_v 4. */
 int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                                int width, int height, uint32_t *d_out_u, uint32_t *d_out_v, size_t pitch, void *stream);
 /* Reconstruction into tiles, the way back from the stage above (no upstream counterpart, as for residual formation):
@@ -294,6 +325,7 @@ int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, 
  * Luma: the mirror of xResidualLumaDev -- d_residual holds int16 row-major blocks in raster order of blocks, exactly the
  * layout xResidualLumaDev emits; block_edge 32 (width, height multiples of 32) or 8 (multiples of 16).
  * xResidualLumaDev(cur, pred) followed by xReconLumaDev(pred, ..) gives back cur's m_Y. */
+/* Alignment in bytes: d_pred 16, d_residual 16, d_recon 16. */
 int xReconLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_residual, int width, int height,
                   int block_edge, x266_ref_block_t *d_recon, void *stream);
 /* Chroma: the mirror of xResidualChromaDev -- the same U / V block streams, block_edge and block_pitch conventions (block b
@@ -301,17 +333,20 @@ int xReconLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_
  * writes the interleaved (U, V) pairs of m_C (src/x266.cpp:441-449, as xConvInputFmtDev packs them).  block_edge 8: width,
  * height multiples of 16; 32: multiples of 64.  A block_pitch of 0, or one whose stream would not fit in the address space,
  * returns X266HIP_EINVAL. */
+/* Alignment in bytes: d_pred 16, d_res_u 16, d_res_v 16, d_recon 16. */
 int xReconChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_res_u, const int16_t *d_res_v,
                     size_t block_pitch, int width, int height, int block_edge, x266_ref_block_t *d_recon, void *stream);
 /* Fused inverse DCT32 + reconstruction: m_Y of d_recon = clamp(pred + IDCT32(coef), 0, 255) for every 32x32 luma block,
  * coefficients in frame raster order of blocks (the order xDct32FwdFromTilesDev emits) -- bit-identical to
  * xDct32InvBatchDev followed by xReconLumaDev(.., 32, ..), without the residual touching HBM (4 KiB moved per block
  * instead of 8).  width, height multiples of 32. */
+/* Alignment in bytes: d_coef 16, d_pred 16, d_recon 16. */
 int xDct32InvToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
                         x266_ref_block_t *d_recon, void *stream);
 /* The inverse of xDct32FwdCtuFromTilesDev: input 12 KiB per 64x64 CTU (Y0 Y1 Y2 Y3 U V, CTUs in raster order); one launch
  * writes m_Y and m_C of every CTU's 16 tiles -- bit-identical to xDct32InvBatchDev of the six blocks followed by
  * xReconLumaDev(.., 32, ..) and xReconChromaDev(.., 32, ..).  width, height multiples of 64. */
+/* Alignment in bytes: d_coef 16, d_pred 16, d_recon 16. */
 int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
                            x266_ref_block_t *d_recon, void *stream);
 /* The mixed transform set (xTransformTilesDev) per CTU, straight from and into tiled frames of any size.
@@ -337,8 +372,10 @@ int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_r
  * a buffer whose span does not fit in the address space, or an output overlapping an input -- d_recon == d_pred is allowed, as
  * in the recon calls, and so is d_cur == d_pred (both read-only); X266HIP_EDEVICE when the context's transform tables are
  * invalid.  Neither call allocates: both can be captured into a graph. */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_class 1, d_coef 16. */
 int xTransformCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred,
                               int width, int height, const uint8_t *d_class, int16_t *d_coef, void *stream);
+/* Alignment in bytes: d_coef 16, d_class 1, d_pred 16, d_recon 16. */
 int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8_t *d_class,
                             const x266_ref_block_t *d_pred, int width, int height,
                             x266_ref_block_t *d_recon, void *stream);
@@ -353,9 +390,11 @@ int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8
  * frame, or a cost map whose size does not fit in the address space, returns X266HIP_EINVAL.  The SATD form uses the same
  * per-stream scratch as xSatd8x8SearchDev: under a stream capture call xHipMeScratchReserve first (or run one search on that
  * stream beforehand). */
+/* Alignment in bytes: d_cur 16, d_ref 16, d_best 8, d_costs 4. */
 int xSatd8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
                                int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
                                void *stream);
+/* Alignment in bytes: d_cur 16, d_ref 16, d_best 8, d_costs 4. */
 int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
                               int width, int height, int range, x266_me_result_t *d_best, uint32_t *d_costs,
                               void *stream);
@@ -363,6 +402,7 @@ int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, c
  * d_best; cost is ignored), pred[8by+y][8bx+x] = ref[clamp(8by+y+mvy, 0, H-1)][clamp(8bx+x+mvx, 0, W-1)] for any int16 vector.
  * Writes only m_Y of d_pred; m_C and m_I are left untouched, as xReconLumaDev leaves them.  Blocks read what other blocks
  * would overwrite, so d_pred overlapping d_ref or d_mv returns X266HIP_EINVAL. */
+/* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                        int width, int height, x266_ref_block_t *d_pred, void *stream);
 /* 4:2:0 chroma motion compensation with the same records: the vector of 8x8 luma block (bx, by) moves the 4x4 block (bx, by) of
@@ -383,14 +423,17 @@ int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x2
  * xMotionCompLumaDev d_pred is a whole 4:2:0 prediction.  xMotionCompDev writes m_Y and m_C in one launch, bit-identical to the
  * luma call followed by the chroma call; m_I is never written.  Arguments as for xMotionCompLumaDev; neither call allocates,
  * both can be captured into a graph. */
+/* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                          int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                    int width, int height, x266_ref_block_t *d_pred, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
- * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; buffers 16-byte
- * aligned): d_out[b] = sum |a - b|, exactly sad() of
+ * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; d_a and d_b 16-byte,
+ * d_out 4-byte aligned): d_out[b] = sum |a - b|, exactly sad() of
  * riscv/programs/benchmarks/sad/sad.c:28-39 (whose 64 x 64 known answer 344807 the tests replay). */
+/* Alignment in bytes: d_a 16, d_b 16, d_out 4. */
 int xSadBatchDev(x266hip_ctx *ctx, int edge, const uint8_t *d_a, const uint8_t *d_b, uint32_t *d_out,
                  size_t n_blocks, void *stream);
 /* 32x32 intra prediction.  Upstream has only a work-in-progress RTL sketch of this
@@ -398,12 +441,14 @@ int xSadBatchDev(x266hip_ctx *ctx, int edge, const uint8_t *d_a, const uint8_t *
  * (H.265 8.4.4.2.4-6, nTbS = 32) -- mode 0 planar, 1 DC, 2..34 angular -- on references used as
  * given.  x266_intra_ref_t mirrors IntraRef_t (:36-39): left[y] = p[-1][y], top[0] = the corner
  * sample, top[1+x] = p[x][-1]; padded to 144 bytes so that sets are 16-byte aligned.
- * Output block i (1024 bytes, row-major) = mode d_modes[i] on set d_ref_index[i] (NULL: set i). */
+ * Output block i (1024 bytes, row-major) = mode d_modes[i] on set d_ref_index[i] (NULL: set i).
+ * d_refs and d_pred 16-byte, d_ref_index 4-byte aligned; d_modes is bytes at any address. */
 typedef struct x266_intra_ref_t {
     uint8_t left[64];
     uint8_t top[65];
     uint8_t reserved[15];
 } x266_intra_ref_t;
+/* Alignment in bytes: d_refs 16, d_modes 1, d_ref_index 4, d_pred 16. */
 int xIntra32PredictDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_modes,
                        const uint32_t *d_ref_index, uint8_t *d_pred, size_t n, void *stream);
 /* The encoder loop's form of intra coding, in ONE kernel: d_coef[i] = forward DCT32 (xDct32FwdBatchDev's transform,
@@ -411,18 +456,22 @@ int xIntra32PredictDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const u
  * The prediction never reaches memory: 1 KiB of source samples (row-major 32x32 uint8) + 144 bytes of references in, 2 KiB of
  * coefficients out per block.  Bit-identical to xIntra32PredictDev -> residual -> xDct32FwdBatchDev.  Modes above 34 are
  * undefined input, as for xIntra32PredictDev. */
+/* Alignment in bytes: d_refs 16, d_modes 1, d_ref_index 4, d_src 16, d_coef 16. */
 int xIntra32ResidualDct32Dev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_modes, const uint32_t *d_ref_index,
                              const uint8_t *d_src, int16_t *d_coef, size_t n, void *stream);
 /* Intra mode decision (the sketch's "Decide" channel, IntraChannel_t :41-44): for block b with reference
  * set d_refs[b] and source samples d_src[b*1024 ..] (row-major 32x32, 16-byte aligned),
  * d_costs[b*35 + m] = sum over the sixteen 8x8 sub-blocks of satd8x8(src - prediction m)
  * (satd8x8 = src_tb/satd.c:31-118), m = 0..34; d_best_mode[b] (may be NULL) = the cheapest mode,
- * lowest index on ties.  The predictions are never written to memory. */
+ * lowest index on ties.  The predictions are never written to memory.  d_costs 4-byte aligned, d_best_mode
+ * bytes at any address. */
+/* Alignment in bytes: d_refs 16, d_src 16, d_costs 4, d_best_mode 1. */
 int xIntra32CostsDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_src,
                      uint32_t *d_costs, uint8_t *d_best_mode, size_t n_blocks, void *stream);
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */
+/* Alignment in bytes: d_dst 16. */
 int xFillResidualDev(x266hip_ctx *ctx, int16_t *d_dst, size_t n_samples,
                      uint64_t seed, uint64_t first_index, void *stream);
 
@@ -486,6 +535,7 @@ int xHipTimeKernel(x266hip_ctx *ctx, int op, const void *d_in, void *d_out,
 #define X266_MEM_WRITE 2
 #define X266_MEM_READ_PROBE 3
 #define X266_MEM_PROBE_MAGIC 0x12345678u
+/* Alignment in bytes: d_src 16, d_dst 16. */
 int xHipMemCeilingDev(x266hip_ctx *ctx, int kind, const void *d_src, void *d_dst, size_t bytes, void *stream);
 /* HIP events for hosts without HIP headers, so that ANY sequence of the ...Dev calls can be timed on the
  * stream it is launched on (record an event before every launch and one after the last: consecutive

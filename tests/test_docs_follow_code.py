@@ -101,3 +101,20 @@ def test_design_states_the_kernel_count_of_the_built_library():
     s = open(os.path.join(ROOT, "DESIGN.md")).read()
     stated = [int(x) for x in re.findall(r"(\d+)\*{0,2} kernels\b", s)]
     assert len(names) in stated, "DESIGN.md states %s kernels, the build has %d" % (stated, len(names))
+
+
+def test_header_states_the_alignments_the_placement_table_tests():
+    """every ...Dev declaration of the header carries an "Alignment in bytes" line, and it names the declaration's pointer arguments
+    with the alignments of the table of tests/test_gpu_placement.py -- which the GPU tests hold against the library's argument
+    checks from both sides (accepted at exactly that alignment, refused at half of it)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_placement import ROWS, header_alignments
+    hdr = open(os.path.join(ROOT, "include", "x266hip.h")).read()
+    stated = header_alignments()
+    assert set(stated) == set(ROWS), sorted(set(stated) ^ set(ROWS))
+    for name, r in ROWS.items():
+        assert stated[name] == dict(r.ptrs), (name, stated[name], dict(r.ptrs))
+        decl = re.search(r"int %s\(([^;]*)\);" % name, hdr).group(1)
+        for ptr in r.ptrs:
+            assert re.search(r"\*\s*%s\b" % ptr, decl), (name, ptr)          # the names are the declaration's pointer arguments
+        assert decl.count("*") == len(r.ptrs) + 2, (name, decl)              # ... all of them (besides ctx and stream)
