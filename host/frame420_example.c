@@ -6,9 +6,11 @@
  *     -> xConvInputFmtDev                    (xConvInputFmt, src/x266.cpp:415-453: 512-byte ref_block_t tiles)
  *     -> xDct32FwdCtuFromTilesDev            one launch: per 64x64 CTU the coefficients of Y0 Y1 Y2 Y3 U V (12 KiB)
  *     -> xSatd8x8FromTilesDev / xSatd8x8ChromaFromTilesDev   the 8x8 costs of the same residual, luma and chroma
+ *     -> xDct32CodeCtuTilesGpu               one launch: the levels and non-zero counts of every CTU at a qp, and the reconstruction
  *
  * and checks every output against the two-step calls it fuses (residual formed in HBM by xResidualLumaDev / xResidualChromaDev,
- * then the pinned batch kernels) -- on the host, block by block.
+ * then the pinned batch kernels; for the coding call xDct32FwdCtuFromTilesDev -> xQuantRegionsGpu(0) -> xQuantRegionsGpu(1) ->
+ * xDct32InvCtuToTilesDev) -- on the host, block by block.
  *
  *   usage: frame420_example [width height]      (multiples of 64; default 1920 1088)      exit code 0 on success
  */
@@ -68,6 +70,34 @@ int main(int argc, char **argv)
     CHECK(xSatd8x8FromTilesDev(hip, cur, pred, w, h, (uint32_t *)d_cost_y, NULL));
     CHECK(xSatd8x8ChromaFromTilesDev(hip, cur, pred, w, h, (uint32_t *)d_cost_c, (uint32_t *)d_cost_c + 1, 2, NULL));   /* (U, V) pairs per tile */
 
+    /* the coding loop in one launch (luma qp 27, chroma qp 30 through the per-region bytes; rounding a third), and the four calls it fuses */
+    const int rounding = 171;
+    uint8_t *qp = malloc(n_ctu * 6);
+    for (size_t i = 0; i < n_ctu * 6; i++) qp[i] = i % 6 < 4 ? 27 : 30;
+    void *d_qp, *d_level, *d_nnz, *d_recon, *d_level2, *d_nnz2, *d_recon2;
+    CHECK(xHipMalloc(hip, &d_qp, n_ctu * 6)); CHECK(xHipMemcpyH2D(hip, d_qp, qp, n_ctu * 6));
+    CHECK(xHipMalloc(hip, &d_level, n_ctu * 6 * 2048)); CHECK(xHipMalloc(hip, &d_level2, n_ctu * 6 * 2048));
+    CHECK(xHipMalloc(hip, &d_nnz, n_ctu * 6 * 4)); CHECK(xHipMalloc(hip, &d_nnz2, n_ctu * 6 * 4));
+    CHECK(xHipMalloc(hip, &d_recon, n_tiles * sizeof(x266_ref_block_t))); CHECK(xHipMalloc(hip, &d_recon2, n_tiles * sizeof(x266_ref_block_t)));
+    CHECK(xDct32CodeCtuTilesGpu(hip, cur, pred, w, h, d_qp, 0, rounding, (int16_t *)d_level, (uint32_t *)d_nnz, (x266_ref_block_t *)d_recon, NULL));
+    CHECK(xQuantRegionsGpu(hip, 0, (const int16_t *)d_ctu, (int16_t *)d_level2, n_ctu * 6, NULL, d_qp, 0, rounding, (uint32_t *)d_nnz2, NULL));
+    CHECK(xHipStreamSync(hip, NULL));
+    int16_t *level = malloc(n_ctu * 6 * 2048), *level2 = malloc(n_ctu * 6 * 2048);
+    uint32_t *nnz = malloc(n_ctu * 6 * 4), *nnz2 = malloc(n_ctu * 6 * 4);
+    uint8_t *recon = malloc(n_tiles * sizeof(x266_ref_block_t)), *recon2 = malloc(n_tiles * sizeof(x266_ref_block_t));
+    CHECK(xHipMemcpyD2H(hip, level, d_level, n_ctu * 6 * 2048)); CHECK(xHipMemcpyD2H(hip, level2, d_level2, n_ctu * 6 * 2048));
+    CHECK(xHipMemcpyD2H(hip, nnz, d_nnz, n_ctu * 6 * 4)); CHECK(xHipMemcpyD2H(hip, nnz2, d_nnz2, n_ctu * 6 * 4));
+    CHECK(xQuantRegionsGpu(hip, 1, (const int16_t *)d_level2, (int16_t *)d_level2, n_ctu * 6, NULL, d_qp, 0, 0, NULL, NULL));   /* in place */
+    CHECK(xDct32InvCtuToTilesDev(hip, (const int16_t *)d_level2, pred, w, h, (x266_ref_block_t *)d_recon2, NULL));
+    CHECK(xHipStreamSync(hip, NULL));
+    CHECK(xHipMemcpyD2H(hip, recon, d_recon, n_tiles * sizeof(x266_ref_block_t))); CHECK(xHipMemcpyD2H(hip, recon2, d_recon2, n_tiles * sizeof(x266_ref_block_t)));
+    size_t coded_bad = 0;
+    unsigned long long nonzero = 0;
+    if (memcmp(level, level2, n_ctu * 6 * 2048) || memcmp(nnz, nnz2, n_ctu * 6 * 4)) coded_bad++;
+    for (size_t t = 0; t < n_tiles; t++)                                   /* m_Y and m_C; neither call writes m_I */
+        if (memcmp(recon + t * sizeof(x266_ref_block_t), recon2 + t * sizeof(x266_ref_block_t), 384)) coded_bad++;
+    for (size_t i = 0; i < n_ctu * 6; i++) nonzero += nnz[i];
+
     /* the two-step calls: residual in HBM, then the pinned batch kernels */
     void *d_res_y, *d_res_c, *d_coef_y, *d_coef_c, *d_res8_y, *d_res8_c, *d_cost2_y, *d_cost2_c;
     CHECK(xHipMalloc(hip, &d_res_y, npx * 2)); CHECK(xHipMalloc(hip, &d_coef_y, npx * 2));
@@ -119,7 +149,8 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < npx / 64; i++) sum_y += cost_y[i];
     for (size_t i = 0; i < n_tiles * 2; i++) sum_c += cost_c[i];
     printf("{\"frame\": \"%dx%d 4:2:0\", \"ctus\": %zu, \"coefficient_bytes\": %zu, \"luma_satd_sum\": %llu, \"chroma_satd_sum\": %llu, "
-           "\"fused_equals_two_step\": %s}\n", w, h, n_ctu, n_ctu * 6 * 2048, sum_y, sum_c, bad ? "false" : "true");
+           "\"fused_equals_two_step\": %s, \"nonzero_levels\": %llu, \"coded_equals_chain\": %s}\n", w, h, n_ctu, n_ctu * 6 * 2048, sum_y, sum_c,
+           bad ? "false" : "true", nonzero, coded_bad ? "false" : "true");
     xHipCodecFree(hip);
-    return bad ? 1 : 0;
+    return bad || coded_bad ? 1 : 0;
 }

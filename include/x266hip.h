@@ -379,6 +379,46 @@ int xTransformCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, c
 int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8_t *d_class,
                             const x266_ref_block_t *d_pred, int width, int height,
                             x266_ref_block_t *d_recon, void *stream);
+/* Quantisation (no upstream counterpart: SURVEY, "No residual, transform, quant, or entropy stage exists").  The flat scalar
+ * quantiser of HEVC / VVC at 8-bit depth, without scaling lists or dependent quantisation, matched to the transforms of this
+ * library (forward shifts log2N - 1 and log2N + 6, inverse shifts 7 and 12) -- the constants as recalled, unverified offline
+ * (like the DST-VII presets and the chroma filter); the arithmetic here is the contract, not a standard text.  For an N x N
+ * block with n = log2 N in 2..5, qp in 0..51 and rounding in 0..511 (units of 1/512; 171 is a third, 256 a half):
+ *   f[6] = {26214, 23302, 20560, 18396, 16384, 14564}      g[6] = {40, 45, 51, 57, 64, 72}
+ *   qbits = 14 + qp/6 + (7 - n)
+ *   level = sign(c) * ((|c| * f[qp%6] + (rounding << (qbits - 9))) >> qbits)
+ *   coef' = clip_int16((level * (g[qp%6] << (qp/6)) + (1 << (n - 2))) >> (n - 1))       (arithmetic shift)
+ * What follows: qbits >= 16, so qbits - 9 >= 7; |c| <= 32768 gives |level| <= 13108, so the forward direction needs no clip;
+ * |c| * f + offset < 2^30 and |level| * (g << qp/6) < 2^30 for every int16 level, so 32-bit arithmetic is exact (and both
+ * products fit the 24-bit multiply-add); the dequantiser does need its clip: level 13107 at qp 0, n = 5 rounds to 32768.
+ * Example: c = 1000, n = 5, qp = 22, rounding = 171 gives level 31 and coef' 992; c = -1000 gives -31 and -992.
+ *
+ * xQuantRegionsGpu: d_in and d_out are sequences of n_regions regions of 1024 samples (the unit of xTransformTilesDev and of the
+ * 12 KiB-per-CTU layouts, six regions per CTU).  Region r has the block size N of its class byte d_class[r], read as
+ * xTransformTilesDev reads its class bytes (low bits: n = 2 + (class & 3)); d_class == NULL means every region is 32x32, which
+ * also covers a plain DCT32 batch with n_regions = n_blocks.  N is uniform per region, so the block-major layout inside a region
+ * does not matter: the operation is element-wise.  Region r uses min(d_qp[r], 51) when d_qp != NULL (a caller's own chroma qp
+ * mapping goes into the bytes of regions 4 and 5 of a CTU), otherwise the scalar qp.  inverse = 0: coefficients -> levels, and
+ * d_nnz[r], if d_nnz != NULL, receives the number of non-zero levels of region r (the coded-block flag).  inverse = 1: levels
+ * -> coefficients; d_nnz must be NULL.  d_out == d_in (in place) is allowed; any other overlap returns X266HIP_EINVAL.
+ * The sample buffers d_in and d_out are 16-byte aligned, d_nnz is 4-byte aligned, d_class and d_qp need no alignment.
+ * X266HIP_EINVAL for a NULL or misaligned buffer, a scalar qp outside 0..51 when d_qp == NULL, rounding outside 0..511, or a
+ * span that does not fit in the address space.  n_regions == 0 returns 0 and launches nothing.  The call allocates nothing and
+ * can be captured into a graph. */
+int xQuantRegionsGpu(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16_t *d_out, size_t n_regions,
+                     const uint8_t *d_class, const uint8_t *d_qp, int qp, int rounding, uint32_t *d_nnz, void *stream);
+/* The coding loop of a frame in one launch.  width, height multiples of 64.  For every 64x64 CTU in raster order and its six
+ * 32x32 regions q = 0..5 (Y0 Y1 Y2 Y3 U V, as xDct32FwdCtuFromTilesDev): d_level[ctu * 6144 + q * 1024 ..] = Q(DCT32(cur - pred)),
+ * d_nnz[6 ctu + q] = its number of non-zero levels (d_nnz may be NULL), and m_Y and m_C of d_recon =
+ * clamp(pred + IDCT32(Q^-1(level)), 0, 255); m_I is never written.  Bit-identical to xDct32FwdCtuFromTilesDev ->
+ * xQuantRegionsGpu(0) -> xQuantRegionsGpu(1) -> xDct32InvCtuToTilesDev with the same qp arguments (d_qp indexed 6 ctu + q,
+ * clamped to 51; NULL: the scalar qp), moving 30 KiB per CTU instead of 96.  d_recon == d_pred and d_cur == d_pred are
+ * allowed, as in the calls it fuses; d_level and d_nnz must overlap nothing.
+ * The tile buffers d_cur, d_pred, d_recon and the level buffer d_level are 16-byte aligned, d_nnz is 4-byte aligned, d_qp needs
+ * no alignment.  X266HIP_EINVAL as for the calls above.  The call allocates nothing and can be captured into a graph. */
+int xDct32CodeCtuTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width,
+                          int height, const uint8_t *d_qp, int qp, int rounding, int16_t *d_level, uint32_t *d_nnz,
+                          x266_ref_block_t *d_recon, void *stream);
 /* Inter prediction on tiled frames (no upstream counterpart: upstream keeps its references as tiled frames, codec_t.m_frames[],
  * src/x266.cpp:96-102, but has no search or compensation for them).  Edge convention of every call below: a reference sample
  * outside the frame takes the nearest in-frame sample, ref[clamp(y, 0, H-1)][clamp(x, 0, W-1)] -- edge replication on all four

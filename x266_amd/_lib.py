@@ -107,6 +107,8 @@ def load_library(path=None):
     L.xMotionCompDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xQuantRegionsGpu.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xDct32CodeCtuTilesGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]
     for name in ("xDct32FwdBatch", "xDct32InvBatch", "xSatd8x8Batch"):
         getattr(L, name).argtypes = [_P, _P, _P, _SZ]
     L.xHipMalloc.argtypes = [_P, ctypes.POINTER(_P), _SZ]
@@ -647,6 +649,61 @@ class Codec:
         self.transform_ctu_to_tiles_dev(dz.ptr, dk.ptr, dp.ptr, w, h, dr.ptr)
         self.stream_sync()
         return dr.download(np.uint8, out.size)
+
+    def quant_regions_dev(self, inverse, d_in, d_out, n_regions, d_class=0, d_qp=0, qp=0, rounding=0, d_nnz=0, stream=0):
+        self._check(self.L.xQuantRegionsGpu(self.ctx, int(inverse), d_in, d_out, n_regions, d_class or None, d_qp or None, int(qp), int(rounding),
+                                            d_nnz or None, stream), "xQuantRegionsGpu")
+
+    def dct32_code_ctu_tiles_dev(self, d_cur, d_pred, w, h, d_qp, qp, rounding, d_level, d_nnz, d_recon, stream=0):
+        self._check(self.L.xDct32CodeCtuTilesGpu(self.ctx, d_cur, d_pred, w, h, d_qp or None, int(qp), int(rounding), d_level, d_nnz or None, d_recon,
+                                                 stream), "xDct32CodeCtuTilesGpu")
+
+    def quant_regions(self, x, inverse=False, classes=None, qps=None, qp=0, rounding=0):
+        """numpy convenience around xQuantRegionsGpu: [n_regions, 1024] int16, optional class and qp bytes per region -> the levels
+        and their non-zero counts per region (inverse=False), or the coefficients (inverse=True)."""
+        x = np.ascontiguousarray(x, np.int16).reshape(-1, 1024)
+        n = x.shape[0]
+        din, dout = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16))
+        din.upload(x)
+        tabs = []
+        for t in (classes, qps):
+            if t is None:
+                tabs.append(None)
+                continue
+            t = np.ascontiguousarray(t, np.uint8).ravel()
+            assert t.size == n
+            tabs.append(self.alloc(max(n, 16)))
+            tabs[-1].upload(t)
+        dn = None if inverse else self.alloc(max(4 * n, 16))
+        self.quant_regions_dev(inverse, din.ptr, dout.ptr, n, tabs[0].ptr if tabs[0] else 0, tabs[1].ptr if tabs[1] else 0, qp, rounding,
+                               dn.ptr if dn else 0)
+        self.stream_sync()
+        out = dout.download(np.int16, n * 1024).reshape(n, 1024)
+        return out if inverse else (out, dn.download(np.uint32, n))
+
+    def code_ctu_tiles(self, cur_tiles, pred_tiles, w, h, qps=None, qp=0, rounding=0, base=None):
+        """numpy convenience around xDct32CodeCtuTilesGpu: two tile arrays of a w x h frame (multiples of 64) and optionally 6 qp bytes per
+        CTU -> (levels [n_ctus, 6, 1024] int16, non-zero counts [n_ctus, 6] uint32, the reconstructed tile array); m_I (never
+        written) comes from `base` (a tile array; None: pred's)."""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
+        n = self.ctu_count(w, h)
+        assert cur.size == w * h * 2 and pred.size == w * h * 2
+        out = pred if base is None else np.ascontiguousarray(base, np.uint8).ravel()
+        dc, dp, dr = self.alloc(cur.nbytes), self.alloc(pred.nbytes), self.alloc(out.nbytes)
+        dl, dn = self.alloc(n * 12288), self.alloc(max(n * 24, 16))
+        dc.upload(cur)
+        dp.upload(pred)
+        dr.upload(out)
+        dq = None
+        if qps is not None:
+            q = np.ascontiguousarray(qps, np.uint8).ravel()
+            assert q.size == 6 * n
+            dq = self.alloc(max(q.nbytes, 16))
+            dq.upload(q)
+        self.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, dq.ptr if dq else 0, qp, rounding, dl.ptr, dn.ptr, dr.ptr)
+        self.stream_sync()
+        return dl.download(np.int16, n * 6144).reshape(n, 6, 1024), dn.download(np.uint32, n * 6).reshape(n, 6), dr.download(np.uint8, out.size)
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

@@ -34,7 +34,8 @@
 // Kernels in this file: dct32_lds_kernel (LDS-staged line-dense traffic, forward / inverse),
 // dct32_fwdinv_kernel (coefficients + reconstruction in one pass, LDS-DMA fed), dct32_from_tiles_kernel
 // (residual formation fused in), dct32_inv_to_tiles_kernel / dct32_inv_ctu_to_tiles_kernel (the inverse with the
-// reconstruction into tiles fused in), dct32_pass_kernel (the 1-D pass by itself, for checking).  They share their per-wave
+// reconstruction into tiles fused in), dct32_code_ctu_tiles_kernel (a CTU's forward, quantise, dequantise, inverse and reconstruction in
+// one pass), dct32_pass_kernel (the 1-D pass by itself, for checking).  They share their per-wave
 // steps: the blocks of x266_mfma_blocks.hpp (tile_lanes, frag_to_linear, column_base / read_column_planes, load_c2r,
 // fwd_from_pixels, chroma_plane) and, here, inv_from_slot, luma_from_tiles and chroma_from_tiles -- the bodies that the
 // standalone from-tiles kernels and the whole-CTU kernels are both built on.  The direct fragment-load forms and the variants
@@ -47,6 +48,7 @@
 #include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 #include "x266_mfma_blocks.hpp"
+#include "x266_quant.hpp"
 #include "x266_tables.hpp"
 
 namespace x266 {
@@ -511,6 +513,102 @@ __global__ __launch_bounds__(256) void dct32_inv_ctu_to_tiles_kernel(const int16
     store16_sc1nt(pr + 512, recon_chroma16(p1, ou1, ov1));
 }
 
+// ---- the coding loop of a whole CTU in one launch: forward, quantise, dequantise, inverse, reconstruct ------------------------------
+// level = Q(DCT32(cur - pred)) for the six 32x32 regions of every 64x64 CTU (the 12 KiB-per-CTU layout of dct32_ctu_from_tiles_kernel)
+// with the count of non-zero levels per region, and recon = clip8(pred + IDCT32(Q^-1(level))) into the CTU's tiles: what
+// dct32_ctu_from_tiles_kernel -> quant_regions_kernel<false> -> quant_regions_kernel<true> -> dct32_inv_ctu_to_tiles_kernel do in four
+// launches over 96 KiB per CTU, here over 30 KiB (6 + 6 KiB of pixels in, 12 KiB of levels and 6 KiB of pixels out).  Five waves per
+// CTU as in those kernels.  One region (code_region): pass 1 from the pixels (pixels_pass1), then pass 2 in BOTH operand orientations
+// as dct32_fwdinv_kernel does -- the natural one is quantised into the level tile, the swapped one is quantised and dequantised in
+// registers and is the inverse's input fragment (inv_passes with the accumulator-order tables).  Quantisation is element-wise
+// (x266_quant.hpp, the functions quant_regions_kernel runs), so the two orientations hold the same levels.  The pred fragment the
+// forward pass loaded is the one the reconstruction adds to: a lane reads exactly the pred bytes it writes, so recon == pred is safe.
+__device__ __forceinline__ void code_region(const v4i &a, const v4i &b, const LaneConsts &kf, const LaneConsts &ki, const v16i &c2r,
+                                            const QuantParams &q, unsigned lane, unsigned char *slot, const TileLanes &t, char *dst_level,
+                                            uint32_t *nnz, v4i &o0, v4i &o1)
+{
+    v4i ylo, yhi;
+    pass1_planes<4>(pixels_pass1(a, b, kf), ylo, yhi);
+    {
+        const v16i acc = fwd_pass2(ylo, yhi, kf);
+        uint32_t z[8];
+        unsigned nonzero = 0;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int lo = quantise((int)(int16_t)(acc[2 * m] >> 11), q), hi = quantise((int)(int16_t)(acc[2 * m + 1] >> 11), q);
+            nonzero += (lo != 0) + (hi != 0);
+            z[m] = ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16);
+        }
+        v4i s0, s1;
+        frag_to_linear(slot, t, v4i{(int)z[0], (int)z[1], (int)z[2], (int)z[3]}, v4i{(int)z[4], (int)z[5], (int)z[6], (int)z[7]}, s0, s1);
+        store16_sc1nt(dst_level, s0);
+        store16_sc1nt(dst_level + 1024, s1);
+        if (nnz) {
+            const uint32_t total = wave_sum(nonzero);
+            if (lane == 0) *nnz = total;
+        }
+    }
+    v16i acc = fwd_pass2_swapped(ylo, yhi, kf, lane >> 5);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = dequantise(quantise((int)(int16_t)(acc[r] >> 11), q), q);   // bytes 0 / 1 = the int16 coefficient
+    v4i zlo, zhi;
+    pack_planes(acc, zlo, zhi);
+    inv_passes(zlo, zhi, ki, c2r, o0, o1);
+}
+
+// region `region` of the frame (6 per CTU): its qp byte clamped to 51, or the scalar qp
+__device__ __forceinline__ QuantParams region_quant(const uint8_t *__restrict__ qps, size_t region, unsigned qp, unsigned rounding)
+{
+    if (qps) {
+        qp = uniform_byte(qps, region);
+        qp = qp < 51u ? qp : 51u;
+    }
+    return quant_params(5u, qp, rounding);
+}
+
+__global__ __launch_bounds__(256) void dct32_code_ctu_tiles_kernel(const x266_ref_block_t *cur, const x266_ref_block_t *pred, x266_ref_block_t *recon,
+                                                                   int16_t *__restrict__ level, uint32_t *__restrict__ nnz,
+                                                                   const uint8_t *__restrict__ qps, unsigned qp, unsigned rounding, int ctus_x,
+                                                                   int tiles_x, size_t n_ctus, const DctOps *__restrict__ fwd_ops,
+                                                                   const DctOps *__restrict__ inv_ops, unsigned lds_per_wave)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    unsigned char *slot = stage + wave_in_wg * lds_per_wave;
+    const size_t unit = (size_t)blockIdx.x * (blockDim.x >> 6) + wave_in_wg;
+    const size_t ctu = unit / 5;
+    const unsigned part = (unsigned)(unit - ctu * 5);
+    if (ctu >= n_ctus) return;
+    const unsigned c = lane & 31, h = lane >> 5;
+    const size_t cy = ctu / ctus_x, cx = ctu - cy * ctus_x;
+    const LaneConsts kf = load_consts(fwd_ops, (int)lane), ki = load_consts(inv_ops, (int)lane);
+    const v16i c2r = load_c2r(inv_ops, (int)h);
+    const TileLanes t = tile_lanes((int)lane);
+    char *dst = reinterpret_cast<char *>(level + ctu * 6144) + lane * 16;
+    uint32_t *cnt = nnz ? nnz + ctu * 6 : nullptr;
+    if (part < 4) {
+        const size_t off = ctu_luma_tile(cy, cx, part, c, h, tiles_x) * sizeof(x266_ref_block_t) + ctu_luma_row_offset(c);
+        const v4i a = load16<true>(reinterpret_cast<const unsigned char *>(cur) + off);
+        const v4i b = load16<true>(reinterpret_cast<const unsigned char *>(pred) + off);
+        v4i o0, o1;
+        code_region(a, b, kf, ki, c2r, region_quant(qps, ctu * 6 + part, qp, rounding), lane, slot, t, dst + part * 2048, cnt ? cnt + part : nullptr, o0, o1);
+        store16_sc1nt(reinterpret_cast<unsigned char *>(recon) + off, recon_luma16(b, o0, o1));
+        return;
+    }
+    const size_t off = ctu_chroma_tile(cy, cx, c, h, tiles_x) * sizeof(x266_ref_block_t) + ctu_chroma_row_offset(c);
+    const unsigned char *pc = reinterpret_cast<const unsigned char *>(cur) + off, *pp = reinterpret_cast<const unsigned char *>(pred) + off;
+    const v4i a0 = load16<true>(pc), a1 = load16<true>(pc + 512), b0 = load16<true>(pp), b1 = load16<true>(pp + 512);   // tiles 2h and 2h + 1
+    const QuantParams qu = region_quant(qps, ctu * 6 + 4, qp, rounding), qv = region_quant(qps, ctu * 6 + 5, qp, rounding);   // both before U's stores: no wait behind them
+    v4i ou0, ou1, ov0, ov1;
+    code_region(chroma_plane(a0, a1, kSelU), chroma_plane(b0, b1, kSelU), kf, ki, c2r, qu, lane, slot, t, dst + 4 * 2048, cnt ? cnt + 4 : nullptr, ou0, ou1);
+    __builtin_amdgcn_wave_barrier();                                       // the U levels have left the slot
+    code_region(chroma_plane(a0, a1, kSelV), chroma_plane(b0, b1, kSelV), kf, ki, c2r, qv, lane, slot, t, dst + 5 * 2048, cnt ? cnt + 5 : nullptr, ov0, ov1);
+    unsigned char *pr = reinterpret_cast<unsigned char *>(recon) + off;
+    store16_sc1nt(pr, recon_chroma16(b0, ou0, ov0));
+    store16_sc1nt(pr + 512, recon_chroma16(b1, ou1, ov1));
+}
+
 // ---- the 1-D pass on its own (partialButterfly32, src_tb/dct32.c:66-170; RTL stage src/mkDct32.bsv:213-284) --------
 // dst[k*32 + j] = (int16)((sum_n g[k][n] * src[j*32 + n] + (1 << (shift-1))) >> shift): one MFMA pass of the forward
 // kernel with the accumulators stored TRANSPOSED, as the reference does.  Lane (c, h) holds frequency kappa(c) for the 16
@@ -677,6 +775,24 @@ hipError_t launch_dct32_inv_ctu_to_tiles(const int16_t *d_coef, const x266_ref_b
     const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave;
     hipLaunchKernelGGL(dct32_inv_ctu_to_tiles_kernel, dim3(wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_coef, d_pred, d_recon,
                        ctus_x, width / 16, n_ctus, d_inv_ops, per_wave);
+    return hipGetLastError();
+}
+
+// the fused inverse's launch shape (cfg_for(ctx, 1), its LDS charge): the wave's chain is the forward's plus the inverse's
+hipError_t launch_dct32_code_ctu_tiles(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, x266_ref_block_t *d_recon, int16_t *d_level,
+                                       uint32_t *d_nnz, const uint8_t *d_qp, int qp, int rounding, int width, int height, const DctOps *d_fwd_ops,
+                                       const DctOps *d_inv_acc_ops, const LaunchCfg &cfg, hipStream_t stream)
+{
+    const int ctus_x = width / 64;
+    const size_t n_ctus = (size_t)ctus_x * (size_t)(height / 64);
+    if (n_ctus == 0) return hipSuccess;
+    const unsigned tpb = (unsigned)cfg.wg_threads;
+    const size_t wpw = tpb / 64;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_ctus * 5, wpw, &wgs)) return e;
+    const unsigned per_wave = (unsigned)cfg.lds_bytes_per_wave < 2048u ? 2048u : (unsigned)cfg.lds_bytes_per_wave;
+    hipLaunchKernelGGL(dct32_code_ctu_tiles_kernel, dim3(wgs), dim3(tpb), wpw * (size_t)per_wave, stream, d_cur, d_pred, d_recon, d_level, d_nnz, d_qp,
+                       (unsigned)qp, (unsigned)rounding, ctus_x, width / 16, n_ctus, d_fwd_ops, d_inv_acc_ops, per_wave);
     return hipGetLastError();
 }
 

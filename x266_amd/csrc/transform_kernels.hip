@@ -290,13 +290,10 @@ __global__ __launch_bounds__(256) void tr_inv_small_lds_kernel(const int16_t *__
 // there once the class byte has arrived: the block-diagonal 32x32 operand of an N-point transform is the N x N matrix
 // repeated along the diagonal, so a lane's 16 operand bytes are at most 16 bytes of ONE matrix row, masked to the
 // K-slots that fall into the lane's diagonal block.
-// class byte of tile t through the scalar cache: the aligned dword that holds it (t is wave-uniform, so this is an
-// s_load_dword and the class lands in an SGPR without a vector-memory round trip), for any alignment of the table
+// class byte of tile t through the scalar cache (uniform_byte, x266_device.hpp: t is wave-uniform), for any alignment of the table
 __device__ __forceinline__ int tile_class_of(const uint8_t *__restrict__ tile_class, size_t t)
 {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(tile_class) + t;
-    const uint32_t w = *reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-    return (int)((w >> (8 * (unsigned)(a & 3))) & 15u);
+    return (int)(uniform_byte(tile_class, t) & 15u);
 }
 
 // Operand bytes B[16h + t][idx], t = 0..15, of blockdiag(M) given as rows: M[idx % N][(16h + t) % N] where the K-slot

@@ -93,6 +93,18 @@ __device__ __forceinline__ uint32_t sum_over_row16(uint32_t x)
     return x;
 }
 
+// Byte i of a read-only table of any alignment, for a wave-uniform i, as a wave-uniform value: the aligned dword that holds it is
+// read through a constant-address-space pointer, which the compiler turns into s_load_dword (a pointer made from an integer is
+// otherwise a generic one and costs a flat_load and a vector-memory round trip), and readfirstlane pins the result to an SGPR so
+// that whatever is derived from it runs on the scalar ALU.  Class and qp bytes are read this way.
+__device__ __forceinline__ unsigned uniform_byte(const uint8_t *table, size_t i)
+{
+    typedef const __attribute__((address_space(4))) uint32_t *const_dword_ptr;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(table) + i;
+    const uint32_t w = *(const_dword_ptr)(a & ~(uintptr_t)3);
+    return ((uint32_t)__builtin_amdgcn_readfirstlane((int)w) >> (8 * (unsigned)(a & 3))) & 255u;
+}
+
 // Result streams -- a few bytes written per hundred read (SATD / SAD costs): agent-scope "sc1" stores without the streaming hint.  Measured on
 // the SATD batch, paired over eight allocation sets (profiles/r05_result_stores.txt): plain or sc0 0.360 ms, nt 0.334-0.360, sc1 nt 0.329-0.339,
 // sc1 or sc0 sc1 0.325-0.330 -- and the kernel no longer follows where its small output buffer landed.
@@ -207,6 +219,11 @@ hipError_t launch_dct32_inv_to_tiles(const int16_t *d_coef, const x266_ref_block
                                      const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_dct32_inv_ctu_to_tiles(const int16_t *d_coef, const x266_ref_block_t *d_pred, x266_ref_block_t *d_recon, int width, int height,
                                          const DctOps *d_inv_ops, const LaunchCfg &cfg, hipStream_t stream);
+hipError_t launch_dct32_code_ctu_tiles(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, x266_ref_block_t *d_recon, int16_t *d_level,
+                                       uint32_t *d_nnz, const uint8_t *d_qp, int qp, int rounding, int width, int height, const DctOps *d_fwd_ops,
+                                       const DctOps *d_inv_acc_ops, const LaunchCfg &cfg, hipStream_t stream);
+hipError_t launch_quant_regions(bool inverse, const int16_t *d_in, int16_t *d_out, size_t n_regions, const uint8_t *d_class,
+                                const uint8_t *d_qp, int qp, int rounding, uint32_t *d_nnz, hipStream_t stream);
 hipError_t launch_motion_comp_luma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,
                                    int width, int height, hipStream_t stream);
 hipError_t launch_motion_comp_chroma(const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, x266_ref_block_t *d_pred,

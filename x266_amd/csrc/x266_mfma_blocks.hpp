@@ -1,7 +1,9 @@
 // x266_mfma_blocks.hpp -- device-side building blocks shared by the transform kernels:
 // byte-plane split / re-pack around v_mfma_i32_32x32x32_i8, the two-pass forward transform of one
 // 32x32 tile held in registers (fwd_block; fwd_from_pixels for 8-bit cur / pred rows, chroma_plane
-// for their U,V de-interleave), the inverse's passes with their constants and column gather
+// for their U,V de-interleave; their steps pixels_pass1, pass1_planes, fwd_pass2, and the other operand
+// orientation fwd_pass2_swapped of the CTU coding kernel, which feeds an inverse from registers), the inverse's passes
+// with their constants and column gather
 // (inv_passes, load_c2r, column_base / read_column_planes), the wave-private LDS slot as layout
 // converter (lds_slot, TileLanes, frag_to_linear, fwd_tile_staged) and the reconstruction into pixels
 // (recon_luma16 / recon_chroma16).  See dct32_kernels.hip for the derivation.
@@ -84,22 +86,49 @@ __device__ __forceinline__ LaneConsts load_consts(const DctOps *ops, int lane)
 }
 
 // ---- forward: one block held as (w0, w1) -> (o0, o1) ------------------------
+// the pass-1 sums (rounding term included) shifted and re-packed to the byte planes pass 2 takes
+template <int S1>
+__device__ __forceinline__ void pass1_planes(v16i acc, v4i &ylo, v4i &yhi)
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = acc[r] >> S1;        // bytes 0/1 = int16 result
+    pack_planes(acc, ylo, yhi);
+}
+
+// pass 2 (columns), natural orientation: data = A (pass-1 accumulators re-packed), coefficients = B.  The sums before the final
+// shift: 16 consecutive coefficients of one output row per lane.
+__device__ __forceinline__ v16i fwd_pass2(const v4i &ylo, const v4i &yhi, const LaneConsts &k)
+{
+    const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    v16i acc = mfma(yhi, k.p2, zero);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = (int)(((uint32_t)acc[r] << 8) + (uint32_t)k.c2);
+    return mfma(ylo, k.p2, acc);
+}
+
+// pass 2 in the OTHER operand orientation (coefficients = A, data = B; dct32_kernels.hip, "fused forward + inverse"): lane (i, h)
+// gets the sums Z[acc_row(r, h)][kappa(i)] of the 32-point DCT-II with final shift 11 -- sixteen rows of one column, the A
+// fragment of the inverse's first contraction in accumulator-row order.  The byte-plane offset fix belongs to output row 0 =
+// accumulator register 0 of the lower half-wave.  dct32_fwdinv_kernel keeps its own inline form of this pass: its loop is scheduled
+// around hand-counted waits and hoists the offset constant, and it is left exactly as measured.
+__device__ __forceinline__ v16i fwd_pass2_swapped(const v4i &ylo, const v4i &yhi, const LaneConsts &k, unsigned h)
+{
+    const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    v16i acc = mfma(k.p2, yhi, zero);
+    acc[0] = (int)(((uint32_t)acc[0] << 8) + (uint32_t)((1 << 10) + (h ? 0 : 128 * 2048)));
+#pragma unroll
+    for (int r = 1; r < 16; ++r) acc[r] = (int)(((uint32_t)acc[r] << 8) + (1u << 10));
+    return mfma(k.p2, ylo, acc);
+}
+
 // Second half of the forward transform: `acc` holds the pass-1 sums INCLUDING the rounding term;
 // shift, re-pack to byte planes, pass 2, final shift and int16 packing.
 template <int S1, int S2>
 __device__ __forceinline__ void fwd_finish(v16i acc, const LaneConsts &k, v4i &o0, v4i &o1)
 {
-    const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = acc[r] >> S1;        // bytes 0/1 = int16 result
     v4i ylo, yhi;
-    pack_planes(acc, ylo, yhi);
-
-    // pass 2 (columns): data = A (pass-1 accumulators re-packed), coefficients = B
-    acc = mfma(yhi, k.p2, zero);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = (int)(((uint32_t)acc[r] << 8) + (uint32_t)k.c2);
-    acc = mfma(ylo, k.p2, acc);
+    pass1_planes<S1>(acc, ylo, yhi);
+    acc = fwd_pass2(ylo, yhi, k);
 
     // (acc >> S2) truncated to int16, pairs packed into dwords
     uint32_t z[8];
@@ -129,13 +158,17 @@ __device__ __forceinline__ void fwd_block(const v4i &w0, const v4i &w1, const La
 // The forward transform of cur - pred on 8-bit pixels as they are (dct32_kernels.hip, "fused residual + forward transform"):
 // pass 1 is G*cur + (-G)*pred, ONE byte plane per frame, the +128 of the (x ^ 0x80) signed-offset trick cancels and the
 // rounding constant is the MFMA's inline C operand.  a / b: the lane's 16 cur / pred pixels (row c, columns 16h .. 16h+15).
-__device__ __forceinline__ void fwd_from_pixels(const v4i &a, const v4i &b, const LaneConsts &k, v4i &o0, v4i &o1)
+__device__ __forceinline__ v16i pixels_pass1(const v4i &a, const v4i &b, const LaneConsts &k)
 {
     const v4i bias = {(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u};
     const v16i round1 = {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8};
-    v16i acc = mfma(a ^ bias, k.p1, round1);
-    acc = mfma(b ^ bias, k.tr, acc);                          // k.tr = -p1 in the forward tables
-    fwd_finish<4, 11>(acc, k, o0, o1);
+    const v16i acc = mfma(a ^ bias, k.p1, round1);
+    return mfma(b ^ bias, k.tr, acc);                         // k.tr = -p1 in the forward tables
+}
+
+__device__ __forceinline__ void fwd_from_pixels(const v4i &a, const v4i &b, const LaneConsts &k, v4i &o0, v4i &o1)
+{
+    fwd_finish<4, 11>(pixels_pass1(a, b, k), k, o0, o1);
 }
 
 // One chroma plane's 16 pixels out of two m_C lines (8 interleaved U,V pairs each): sel = kSelU / kSelV

@@ -1130,6 +1130,76 @@ int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8
     return X266HIP_OK;
 }
 
+// ---- the quantiser (x266_quant.hpp) -----------------------------------------------------------------------------------------------
+// n * unit bytes from p on, where both the product and the buffer's end fit in the address space
+static bool span_fits(const void *p, size_t n, size_t unit, size_t *bytes)
+{
+    uintptr_t end = 0;
+    return !__builtin_mul_overflow(n, unit, bytes) && !__builtin_add_overflow((uintptr_t)p, *bytes, &end);
+}
+
+static bool quant_scalars_ok(const uint8_t *d_qp, int qp, int rounding)
+{
+    return (d_qp || (qp >= 0 && qp <= 51)) && rounding >= 0 && rounding <= 511;
+}
+
+int xQuantRegionsGpu(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16_t *d_out, size_t n_regions, const uint8_t *d_class,
+                     const uint8_t *d_qp, int qp, int rounding, uint32_t *d_nnz, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (!quant_scalars_ok(d_qp, qp, rounding)) return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: qp must be 0..51 (without d_qp) and rounding 0..511");
+    if (inverse && d_nnz) return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: d_nnz must be NULL with inverse = 1");
+    if (n_regions == 0) return X266HIP_OK;
+    if (bad_ptrs(d_in, d_out, n_regions) || ((uintptr_t)d_nnz & 3u)) return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: NULL or unaligned buffer");
+    size_t bytes = 0, nnz_bytes = 0, tab_bytes = 0;
+    if (!span_fits(d_in, n_regions, 2048, &bytes) || !span_fits(d_out, n_regions, 2048, &bytes) || !span_fits(d_nnz, n_regions, 4, &nnz_bytes) ||
+        !span_fits(d_class, n_regions, 1, &tab_bytes) || !span_fits(d_qp, n_regions, 1, &tab_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: a buffer does not fit in the address space");
+    if ((d_out != d_in && ranges_overlap(d_out, bytes, d_in, bytes)) || ranges_overlap(d_out, bytes, d_class, tab_bytes) ||
+        ranges_overlap(d_out, bytes, d_qp, tab_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: d_out overlaps an input (only d_out == d_in is allowed)");
+    if (ranges_overlap(d_nnz, nnz_bytes, d_in, bytes) || ranges_overlap(d_nnz, nnz_bytes, d_out, bytes) ||
+        ranges_overlap(d_nnz, nnz_bytes, d_class, tab_bytes) || ranges_overlap(d_nnz, nnz_bytes, d_qp, tab_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: d_nnz overlaps another buffer");
+    X_DEV(ctx);
+    hipError_t e = launch_quant_regions(inverse != 0, d_in, d_out, n_regions, d_class, d_qp, qp, rounding, d_nnz, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "quantiser launch", e);
+    return X266HIP_OK;
+}
+
+int xDct32CodeCtuTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
+                          const uint8_t *d_qp, int qp, int rounding, int16_t *d_level, uint32_t *d_nnz, x266_ref_block_t *d_recon, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 63) || (height & 63)) return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: width/height must be multiples of 64");
+    if (!quant_scalars_ok(d_qp, qp, rounding)) return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: qp must be 0..51 (without d_qp) and rounding 0..511");
+    if (!d_cur || !d_pred || !d_level || !d_recon || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_level | (uintptr_t)d_recon)) & 15u) ||
+        ((uintptr_t)d_nnz & 3u))
+        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: NULL or unaligned buffer");
+    const size_t n_ctus = (size_t)(width / 64) * (size_t)(height / 64);
+    size_t tile_bytes = 0, level_bytes = 0, nnz_bytes = 0, qp_bytes = 0;
+    if (!span_fits(d_cur, (size_t)width * 2, (size_t)height, &tile_bytes) || !span_fits(d_pred, (size_t)width * 2, (size_t)height, &tile_bytes) ||
+        !span_fits(d_recon, (size_t)width * 2, (size_t)height, &tile_bytes) || !span_fits(d_level, n_ctus, 12288, &level_bytes) ||
+        !span_fits(d_nnz, n_ctus, 24, &nnz_bytes) || !span_fits(d_qp, n_ctus, 6, &qp_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: a buffer does not fit in the address space");
+    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || (d_cur != d_pred && ranges_overlap(d_recon, tile_bytes, d_cur, tile_bytes)) ||
+        ranges_overlap(d_recon, tile_bytes, d_qp, qp_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    if (ranges_overlap(d_level, level_bytes, d_cur, tile_bytes) || ranges_overlap(d_level, level_bytes, d_pred, tile_bytes) ||
+        ranges_overlap(d_level, level_bytes, d_recon, tile_bytes) || ranges_overlap(d_level, level_bytes, d_qp, qp_bytes) ||
+        ranges_overlap(d_nnz, nnz_bytes, d_cur, tile_bytes) || ranges_overlap(d_nnz, nnz_bytes, d_pred, tile_bytes) ||
+        ranges_overlap(d_nnz, nnz_bytes, d_recon, tile_bytes) || ranges_overlap(d_nnz, nnz_bytes, d_qp, qp_bytes) ||
+        ranges_overlap(d_nnz, nnz_bytes, d_level, level_bytes))
+        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: d_level or d_nnz overlaps another buffer");
+    X_DEV(ctx);
+    LaunchCfg cfg = cfg_for(ctx, 1);
+    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
+    hipError_t e = launch_dct32_code_ctu_tiles(d_cur, d_pred, d_recon, d_level, d_nnz, d_qp, qp, rounding, width, height, ctx->d_fwd, ctx->d_inv_acc, cfg,
+                                               (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused CTU coding launch", e);
+    return X266HIP_OK;
+}
+
 int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                                uint32_t *d_out_u, uint32_t *d_out_v, size_t pitch, void *stream)
 {
