@@ -7,6 +7,9 @@
  *     -> xDct32FwdCtuFromTilesDev            one launch: per 64x64 CTU the coefficients of Y0 Y1 Y2 Y3 U V (12 KiB)
  *     -> xSatd8x8FromTilesDev / xSatd8x8ChromaFromTilesDev   the 8x8 costs of the same residual, luma and chroma
  *     -> xDct32CodeCtuTilesGpu               one launch: the levels and non-zero counts of every CTU at a qp, and the reconstruction
+ *     -> xSatd8x8SearchFromTilesDev -> xSatd8x8RefineQpelFromTilesGpu -> xMotionCompQpelGpu -> xDct32CodeCtuTilesGpu
+ *                                            the inter loop with the second frame as the reference: integer search, quarter-sample
+ *                                            refinement in place, a whole 4:2:0 prediction, and the coding call over it
  *
  * and checks every output against the two-step calls it fuses (residual formed in HBM by xResidualLumaDev / xResidualChromaDev,
  * then the pinned batch kernels; for the coding call xDct32FwdCtuFromTilesDev -> xQuantRegionsGpu(0) -> xQuantRegionsGpu(1) ->
@@ -145,12 +148,42 @@ int main(int argc, char **argv)
     }
     if (memcmp(cost_y, cost2_y, npx / 64 * 4)) bad++;
     if (memcmp(cost_c, cost2_c, n_tiles * 8)) bad++;
+    /* the inter loop: the second frame as the reference.  The refined record's cost is the SATD of the prediction it yields, and no
+     * block costs more than at its integer vector (the centre candidate of the refinement) */
+    const size_t n_blk = npx / 64;
+    void *d_mv, *d_mvq, *d_inter, *d_cost_q;
+    CHECK(xHipMalloc(hip, &d_mv, n_blk * sizeof(x266_me_result_t))); CHECK(xHipMalloc(hip, &d_mvq, n_blk * sizeof(x266_me_result_t)));
+    CHECK(xHipMalloc(hip, &d_inter, n_tiles * sizeof(x266_ref_block_t))); CHECK(xHipMalloc(hip, &d_cost_q, n_blk * 4));
+    CHECK(xSatd8x8SearchFromTilesDev(hip, cur, pred, w, h, 4, (x266_me_result_t *)d_mv, NULL, NULL));
+    CHECK(xSatd8x8RefineQpelFromTilesGpu(hip, cur, pred, w, h, (const x266_me_result_t *)d_mv, (x266_me_result_t *)d_mvq, NULL, NULL));
+    CHECK(xMotionCompQpelGpu(hip, pred, (const x266_me_result_t *)d_mvq, w, h, (x266_ref_block_t *)d_inter, NULL));
+    CHECK(xSatd8x8FromTilesDev(hip, cur, (const x266_ref_block_t *)d_inter, w, h, (uint32_t *)d_cost_q, NULL));
+    CHECK(xDct32CodeCtuTilesGpu(hip, cur, (const x266_ref_block_t *)d_inter, w, h, d_qp, 0, rounding, (int16_t *)d_level, (uint32_t *)d_nnz,
+                                (x266_ref_block_t *)d_inter, NULL));       /* reconstructs over the prediction: the next reference */
+    CHECK(xHipStreamSync(hip, NULL));
+    x266_me_result_t *mv_i = malloc(n_blk * sizeof(x266_me_result_t)), *mv_q = malloc(n_blk * sizeof(x266_me_result_t));
+    uint32_t *cost_q = malloc(n_blk * 4);
+    CHECK(xHipMemcpyD2H(hip, mv_i, d_mv, n_blk * sizeof(x266_me_result_t))); CHECK(xHipMemcpyD2H(hip, mv_q, d_mvq, n_blk * sizeof(x266_me_result_t)));
+    CHECK(xHipMemcpyD2H(hip, cost_q, d_cost_q, n_blk * 4)); CHECK(xHipMemcpyD2H(hip, nnz, d_nnz, n_ctu * 6 * 4));
+    size_t inter_bad = 0, fractional = 0;
+    unsigned long long sum_int = 0, sum_q = 0, inter_nonzero = 0;
+    for (size_t b = 0; b < n_blk; b++) {
+        if (mv_q[b].cost > mv_i[b].cost || mv_q[b].cost != cost_q[b]) inter_bad++;
+        if (mv_q[b].mvx - 4 * mv_i[b].mvx < -3 || mv_q[b].mvx - 4 * mv_i[b].mvx > 3 || mv_q[b].mvy - 4 * mv_i[b].mvy < -3 || mv_q[b].mvy - 4 * mv_i[b].mvy > 3) inter_bad++;
+        fractional += ((mv_q[b].mvx | mv_q[b].mvy) & 3) != 0;
+        sum_int += mv_i[b].cost;
+        sum_q += mv_q[b].cost;
+    }
+    for (size_t i = 0; i < n_ctu * 6; i++) inter_nonzero += nnz[i];
+    bad += inter_bad;
     unsigned long long sum_y = 0, sum_c = 0;
     for (size_t i = 0; i < npx / 64; i++) sum_y += cost_y[i];
     for (size_t i = 0; i < n_tiles * 2; i++) sum_c += cost_c[i];
     printf("{\"frame\": \"%dx%d 4:2:0\", \"ctus\": %zu, \"coefficient_bytes\": %zu, \"luma_satd_sum\": %llu, \"chroma_satd_sum\": %llu, "
-           "\"fused_equals_two_step\": %s, \"nonzero_levels\": %llu, \"coded_equals_chain\": %s}\n", w, h, n_ctu, n_ctu * 6 * 2048, sum_y, sum_c,
-           bad ? "false" : "true", nonzero, coded_bad ? "false" : "true");
+           "\"fused_equals_two_step\": %s, \"nonzero_levels\": %llu, \"coded_equals_chain\": %s, \"inter_satd_sum_integer\": %llu, "
+           "\"inter_satd_sum_quarter\": %llu, \"inter_fractional_blocks\": %zu, \"inter_nonzero_levels\": %llu, \"inter_consistent\": %s}\n",
+           w, h, n_ctu, n_ctu * 6 * 2048, sum_y, sum_c, bad ? "false" : "true", nonzero, coded_bad ? "false" : "true", sum_int, sum_q, fractional,
+           inter_nonzero, inter_bad ? "false" : "true");
     xHipCodecFree(hip);
     return bad || coded_bad ? 1 : 0;
 }

@@ -469,6 +469,51 @@ int xMotionCompChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const 
 /* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                    int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* Quarter-sample inter prediction: the calls above stop at whole luma samples, the four below predict at the quarter-sample luma
+ * (eighth-sample 4:2:0 chroma) precision of HEVC / VVC.  The filter constants are HEVC's as recalled, unverified offline (like
+ * the half-sample chroma filter above); the arithmetic here is the contract, not a standard text.  The same tap row serves both axes.
+ *   luma, 8 taps, tap k at offset k - 3:    TL[0] = { 0, 0,   0, 64,  0,   0, 0,  0}    TL[1] = {-1, 4, -10, 58, 17,  -5, 1,  0}
+ *                                           TL[2] = {-1, 4, -11, 40, 40, -11, 4, -1}    TL[3] = { 0, 1,  -5, 17, 58, -10, 4, -1}
+ *   chroma, 4 taps, tap k at offset k - 1:  TC[0] = { 0, 64,  0,  0}  TC[1] = {-2, 58, 10, -2}  TC[2] = {-4, 54, 16, -2}
+ *       TC[3] = {-6, 46, 28, -4}  TC[4] = {-4, 36, 36, -4}  TC[5] = {-4, 28, 46, -6}  TC[6] = {-2, 16, 54, -4}  TC[7] = {-2, 10, 58, -2}
+ * The records are x266_me_result_t in QUARTER luma samples, one per 8x8 luma block in raster order of blocks; the vector of luma
+ * block (bx, by) also moves the 4x4 U and V blocks (bx, by), as in xMotionCompChromaDev.  Luma uses T = TL, lg = 2, o = 3 on the luma
+ * plane, chroma T = TC, lg = 3, o = 1 on each chroma plane; S(y, x) = plane[clamp(y, 0, H-1)][clamp(x, 0, W-1)] is the inter stage's
+ * edge rule on that plane.  For any int16 vector (arithmetic shifts: -1 has integer part -1 and fraction 2^lg - 1)
+ *   ix = mvx >> lg, fx = mvx & (2^lg - 1), iy = mvy >> lg, fy = mvy & (2^lg - 1)
+ *   fx = 0, fy = 0:  out = S(y+iy, x+ix)
+ *   fy = 0:          out = clip8((sum_k T[fx][k] * S(y+iy, x+ix+k-o) + 32) >> 6)
+ *   fx = 0:          out = clip8((sum_k T[fy][k] * S(y+iy+k-o, x+ix) + 32) >> 6)
+ *   otherwise:       h(r) = sum_k T[fx][k] * S(r, x+ix+k-o)         (no shift; luma -6120..22440, fits int16)
+ *                    v = (sum_k T[fy][k] * h(y+iy+k-o)) >> 6        (32-bit sum; arithmetic: floors a negative sum)
+ *                    out = clip8((v + 32) >> 6)
+ * The horizontal stage is unshifted, so v comes from the exact double sum and the order of the two passes does not matter.
+ * What follows: a vector 4m reproduces xMotionCompLumaDev and xMotionCompChromaDev with vector m bit for bit, for |m| <= 8191
+ * (chroma phase 4 is the (-4, 36, 36, -4) of that call); a constant plane stays constant for every vector.
+ * xMotionCompQpelLumaGpu writes only m_Y of d_pred, xMotionCompQpelChromaGpu only m_C, xMotionCompQpelGpu both in one launch,
+ * bit-identical to the pair; m_I is never read or written.  Arguments as for the three integer calls: width, height multiples of 16,
+ * d_ref and d_pred 16-byte aligned, d_mv 8-byte aligned; X266HIP_EINVAL for a NULL or misaligned pointer, a bad size, a buffer whose
+ * span does not fit in the address space, or d_pred overlapping d_ref or d_mv.  Nothing is allocated; the calls can be captured
+ * into a graph.  Tile offsets are size_t as in the integer calls, but frames beyond 2^32 bytes are untested for these four calls. */
+int xMotionCompQpelLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                           int width, int height, x266_ref_block_t *d_pred, void *stream);
+int xMotionCompQpelChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                             int width, int height, x266_ref_block_t *d_pred, void *stream);
+int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+                       int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* Quarter-sample refinement of integer vectors.  d_int holds one integer record per 8x8 luma block (the searches' d_best; its cost
+ * is ignored).  For block b, m = clamp(mv_int, -8191, 8191) per component, so that every candidate fits int16; the 49 candidates
+ * are q = 4m + (dx, dy), dx, dy in -3..3, and cost(q) = satd8x8(cur_block - P_q) with P_q the block's 8x8 luma prediction of
+ * xMotionCompQpelLumaGpu under q and satd8x8 the metric of the searches (src_tb/satd.c:31-118).  d_best[b] = the candidate of least
+ * cost, in quarter samples, with its cost; among equal costs (0, 0) wins, after it the first in raster order (dy ascending, then dx
+ * ascending).  d_costs may be NULL; otherwise d_costs[49 b + 7 (dy + 3) + (dx + 3)] receives every cost, so its centre entry is the
+ * integer search's cost of m.  d_best == d_int (in place) and d_cur == d_ref are allowed; any other overlap of d_best or d_costs
+ * with anything returns X266HIP_EINVAL.  d_cur and d_ref are 16-byte aligned, d_int and d_best 8-byte, d_costs 4-byte; other
+ * arguments and errors as above.  No per-stream scratch is used (unlike the SATD search): the call allocates nothing, needs no
+ * xHipMeScratchReserve and can be captured into a graph. */
+int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
+                                   int width, int height, const x266_me_result_t *d_int, x266_me_result_t *d_best,
+                                   uint32_t *d_costs, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; d_a and d_b 16-byte,
  * d_out 4-byte aligned): d_out[b] = sum |a - b|, exactly sad() of

@@ -105,6 +105,9 @@ def load_library(path=None):
     L.xMotionCompLumaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xMotionCompChromaDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xMotionCompDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    for name in ("xMotionCompQpelLumaGpu", "xMotionCompQpelChromaGpu", "xMotionCompQpelGpu"):
+        getattr(L, name).argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xSatd8x8RefineQpelFromTilesGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xQuantRegionsGpu.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -604,6 +607,60 @@ class Codec:
         fn(dr.ptr, dm.ptr, w, h, dp.ptr)
         self.stream_sync()
         return dp.download(np.uint8, pred.size)
+
+    def motion_comp_qpel_luma_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
+        self._check(self.L.xMotionCompQpelLumaGpu(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompQpelLumaGpu")
+
+    def motion_comp_qpel_chroma_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
+        self._check(self.L.xMotionCompQpelChromaGpu(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompQpelChromaGpu")
+
+    def motion_comp_qpel_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
+        self._check(self.L.xMotionCompQpelGpu(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompQpelGpu")
+
+    def satd_refine_qpel_from_tiles_dev(self, d_cur, d_ref, width, height, d_int, d_best, d_costs=0, stream=0):
+        self._check(self.L.xSatd8x8RefineQpelFromTilesGpu(self.ctx, d_cur, d_ref, width, height, d_int, d_best, d_costs or None, stream),
+                    "xSatd8x8RefineQpelFromTilesGpu")
+
+    def motion_comp_qpel(self, ref_tiles, mv, w, h, base=None, planes="both"):
+        """numpy convenience around xMotionCompQpelGpu (planes="both") / ...LumaGpu ("luma") / ...ChromaGpu ("chroma"): ref tile
+        array, mv [nb, 2] int16 in quarter luma samples per 8x8 block -> the predicted tile array; what the call does not write
+        comes from `base` (a tile array; None: zeros)."""
+        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
+        assert ref.size == w * h * 2
+        fn = {"both": self.motion_comp_qpel_dev, "luma": self.motion_comp_qpel_luma_dev, "chroma": self.motion_comp_qpel_chroma_dev}[planes]
+        nb = (h // 8) * (w // 8)
+        rec = np.zeros((nb, 4), np.int16)
+        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
+        pred = np.zeros(ref.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
+        dr, dm, dp = self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(pred.nbytes)
+        dr.upload(ref)
+        dm.upload(rec)
+        dp.upload(pred)
+        fn(dr.ptr, dm.ptr, w, h, dp.ptr)
+        self.stream_sync()
+        return dp.download(np.uint8, pred.size)
+
+    def refine_qpel_tiles(self, cur_tiles, ref_tiles, w, h, mv_int, want_costs=False):
+        """numpy convenience around xSatd8x8RefineQpelFromTilesGpu: two tile arrays and integer vectors [nb, 2] int16 ->
+        (mv [nb, 2] int16 in quarter samples, cost [nb] uint32, costs [nb, 49] or None)."""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
+        assert cur.size == w * h * 2 and ref.size == w * h * 2
+        nb = (h // 8) * (w // 8)
+        rec = np.zeros((nb, 4), np.int16)
+        rec[:, :2] = np.asarray(mv_int, np.int16).reshape(nb, 2)
+        dc, dr, di, db = self.alloc(cur.nbytes), self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(nb * 8)
+        dcost = self.alloc(nb * 49 * 4) if want_costs else None
+        dc.upload(cur)
+        dr.upload(ref)
+        di.upload(rec)
+        self.satd_refine_qpel_from_tiles_dev(dc.ptr, dr.ptr, w, h, di.ptr, db.ptr, dcost.ptr if want_costs else 0)
+        self.stream_sync()
+        raw = db.download(np.uint8, nb * 8)
+        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
+        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
+        costs = dcost.download(np.uint32, nb * 49).reshape(nb, 49) if want_costs else None
+        return mv, cost, costs
 
     def transform_ctu_from_tiles_dev(self, d_cur, d_pred, w, h, d_class, d_coef, stream=0):
         self._check(self.L.xTransformCtuFromTilesDev(self.ctx, d_cur, d_pred, w, h, d_class, d_coef, stream), "xTransformCtuFromTilesDev")

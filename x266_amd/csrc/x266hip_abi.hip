@@ -1395,6 +1395,77 @@ int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_m
     return motion_comp_call(ctx, "xMotionCompDev", launch_motion_comp, d_ref, d_mv, width, height, d_pred, stream);
 }
 
+// ---- quarter-sample prediction on tiled frames ---------------------------------------------------------------------------------------
+static bool span_fits(const void *p, size_t bytes)
+{
+    uintptr_t end;
+    return !__builtin_add_overflow((uintptr_t)p, bytes, &end);
+}
+
+// The argument rules of the integer calls, plus: a frame or record span must not run past the end of the address space.
+static int motion_comp_qpel_call(x266hip_ctx *ctx, const char *name, mc_launch_fn launch, const x266_ref_block_t *d_ref,
+                                 const x266_me_result_t *d_mv, int width, int height, x266_ref_block_t *d_pred, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
+    if (!d_ref || !d_mv || !d_pred || ((((uintptr_t)d_ref | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_mv & 7u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
+    if (!span_fits(d_ref, tile_bytes) || !span_fits(d_pred, tile_bytes) || !span_fits(d_mv, mv_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": a buffer does not fit in the address space").c_str());
+    if (ranges_overlap(d_pred, tile_bytes, d_ref, tile_bytes) || ranges_overlap(d_pred, tile_bytes, d_mv, mv_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": d_pred overlaps d_ref or d_mv").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "quarter-sample motion compensation launch", e);
+    return X266HIP_OK;
+}
+
+int xMotionCompQpelLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
+                           x266_ref_block_t *d_pred, void *stream)
+{
+    return motion_comp_qpel_call(ctx, "xMotionCompQpelLumaGpu", launch_mc_qpel_luma, d_ref, d_mv, width, height, d_pred, stream);
+}
+
+int xMotionCompQpelChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
+                             x266_ref_block_t *d_pred, void *stream)
+{
+    return motion_comp_qpel_call(ctx, "xMotionCompQpelChromaGpu", launch_mc_qpel_chroma, d_ref, d_mv, width, height, d_pred, stream);
+}
+
+int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
+                       x266_ref_block_t *d_pred, void *stream)
+{
+    return motion_comp_qpel_call(ctx, "xMotionCompQpelGpu", launch_mc_qpel, d_ref, d_mv, width, height, d_pred, stream);
+}
+
+int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
+                                   const x266_me_result_t *d_int, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
+{
+    const char *name = "xSatd8x8RefineQpelFromTilesGpu: ";
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be multiples of 16").c_str());
+    if (!d_cur || !d_ref || !d_int || !d_best) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL buffer").c_str());
+    if ((((uintptr_t)d_cur | (uintptr_t)d_ref) & 15u) || (((uintptr_t)d_int | (uintptr_t)d_best) & 7u) || ((uintptr_t)d_costs & 3u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "unaligned buffer").c_str());
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_blocks = (size_t)(width / 8) * (size_t)(height / 8);
+    const size_t rec_bytes = n_blocks * 8, cost_bytes = d_costs ? n_blocks * 49 * 4 : 0;      // n_blocks < 2^56: no product wraps
+    if (!span_fits(d_cur, tile_bytes) || !span_fits(d_ref, tile_bytes) || !span_fits(d_int, rec_bytes) || !span_fits(d_best, rec_bytes) ||
+        !span_fits(d_costs, cost_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
+    if (ranges_overlap(d_best, rec_bytes, d_cur, tile_bytes) || ranges_overlap(d_best, rec_bytes, d_ref, tile_bytes) ||
+        (d_best != d_int && ranges_overlap(d_best, rec_bytes, d_int, rec_bytes)) ||
+        ranges_overlap(d_costs, cost_bytes, d_cur, tile_bytes) || ranges_overlap(d_costs, cost_bytes, d_ref, tile_bytes) ||
+        ranges_overlap(d_costs, cost_bytes, d_int, rec_bytes) || ranges_overlap(d_costs, cost_bytes, d_best, rec_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "an output overlaps another buffer (only d_best == d_int is allowed)").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_satd_refine_qpel(d_cur, d_ref, width, height, d_int, d_best, d_costs, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "quarter-sample refinement launch", e);
+    return X266HIP_OK;
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).
