@@ -514,6 +514,68 @@ int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x2
 int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
                                    int width, int height, const x266_me_result_t *d_int, x266_me_result_t *d_best,
                                    uint32_t *d_costs, void *stream);
+/* In-loop deblocking of a tiled reconstructed frame (no upstream counterpart, as for the quantiser): HEVC's deblocking filter at
+ * 8-bit depth, as recalled, unverified offline; the arithmetic here is the contract, not a standard text.  clip8 = clamp to 0..255,
+ * clamp(v, lo, hi) as usual, shifts arithmetic.
+ *   BETA[52]: 0 for index < 16, 6..18 in steps of 1 for 16..28, 20..64 in steps of 2 for 29..51
+ *   TC[54]:   18 x 0, 9 x 1, 4 x 2, 4 x 3, 3 x 4, 2 x 5, 2 x 6, then 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 22, 24
+ * Frame: width, height positive multiples of 16; ceil(width / 64) x ceil(height / 64) CTUs, cut CTUs and the region index 6 ctu + q
+ * (q = 0..3 the luma quadrants, 4 = U, 5 = V) exactly as in xTransformCtuFromTilesDev; entries of regions wholly outside the frame
+ * are never read.  Per region: N = 4 << (class & 3) its block size (d_class NULL: 32), qp = min(d_qp byte, 51) (d_qp NULL: the scalar
+ * qp), coded = d_nnz entry != 0 (d_nnz NULL: coded), and for luma quadrants intra = d_intra byte != 0 (d_intra NULL: not intra).
+ * Luma.  Edges lie on the 8-sample grid, x = 8k and y = 8m strictly inside the frame (the frame border is never filtered); an edge
+ * separates two adjacent 8x8 blocks P (left / above) and Q.  It is a transform edge if P and Q lie in different luma regions or its
+ * coordinate inside their common 32x32 region is a multiple of N (for N <= 8: every grid edge).  Boundary strength, first match:
+ *   Bs = 2  transform edge and (intra(P) or intra(Q))
+ *   Bs = 1  transform edge and (coded(P) or coded(Q))
+ *   Bs = 1  neither intra, d_mv != NULL and (|mvxP - mvxQ| >= 4 or |mvyP - mvyQ| >= 4)   (d_mv: quarter luma samples, one record
+ *           per 8x8 block in raster order, cost ignored; differences taken in 32 bits)
+ *   Bs = 0  otherwise: the edge is left alone.
+ *   qP = (qp(P) + qp(Q) + 1) >> 1,  beta = BETA[clamp(qP + 2 beta_offset_div2, 0, 51)],
+ *   tc = TC[clamp(qP + 2 (Bs - 1) + 2 tc_offset_div2, 0, 53)]
+ * An 8-sample edge is two segments of 4 lines; the samples across the edge on line i are p3 p2 p1 p0 | q0 q1 q2 q3.  Per segment,
+ * with i in {0, 3}: dp_i = |p2 - 2 p1 + p0|, dq_i = |q2 - 2 q1 + q0|, d = dp_0 + dq_0 + dp_3 + dq_3; d >= beta: the segment is
+ * left alone.  It is strong if for both i: 2 (dp_i + dq_i) < (beta >> 2) and |p3 - p0| + |q0 - q3| < (beta >> 3) and
+ * |p0 - q0| < ((5 tc + 1) >> 1).  dEp = (dp_0 + dp_3) < ((beta + (beta >> 1)) >> 3), dEq likewise from dq.
+ *   strong, per line, each result clamped to +-2 tc around its input:
+ *     p0' = (p2 + 2 p1 + 2 p0 + 2 q0 + q1 + 4) >> 3, p1' = (p2 + p1 + p0 + q0 + 2) >> 2, p2' = (2 p3 + 3 p2 + p1 + p0 + q0 + 4) >> 3,
+ *     q0', q1', q2' mirrored
+ *   normal, per line: D = (9 (q0 - p0) - 3 (q1 - p1) + 8) >> 4; |D| >= 10 tc: the line is left alone; otherwise D = clamp(D, -tc, tc),
+ *     p0' = clip8(p0 + D), q0' = clip8(q0 - D),
+ *     if dEp: p1' = clip8(p1 + clamp((((p2 + p0 + 1) >> 1) - p1 + D) >> 1, -(tc >> 1), tc >> 1))
+ *     if dEq: q1' = clip8(q1 + clamp((((q2 + q0 + 1) >> 1) - q1 - D) >> 1, -(tc >> 1), tc >> 1))
+ * Chroma.  U and V are handled each on its own; edges lie on the 8-chroma-sample grid, i.e. exactly on the tile boundaries, and
+ * separate the 8x8 chroma blocks of two adjacent tiles P and Q.  An edge is filtered iff it is a transform edge of that plane (P and Q
+ * in different CTUs, or its coordinate in the CTU's 32x32 chroma region is a multiple of the N of region 4 for U, 5 for V) and the luma
+ * quadrant containing P's tile or Q's tile is intra.  tc = TC[clamp(((qpC(P) + qpC(Q) + 1) >> 1) + 2 + 2 tc_offset_div2, 0, 53)] with
+ * qpC the qp of region 4 (U) or 5 (V) of the tile's CTU: the caller's chroma mapping lives in those bytes, as for the quantiser.
+ *   per line: D = clamp((((q0 - p0) << 2) + p1 - q1 + 4) >> 3, -tc, tc), p0' = clip8(p0 + D), q0' = clip8(q0 - D)
+ * Order, per plane: all vertical edges of the frame, then all horizontal edges on the result of the first pass.
+ * What follows: an edge reads 4 samples (chroma 2) and changes at most 3 (chroma 1) on each side, and decisions use only lines of their
+ * own segment; so the 8x8 areas centred on the grid crossings, [8k-4, 8k+4) x [8m-4, 8m+4) clipped at the frame, partition the plane and
+ * the whole two-pass result inside such an area depends only on that area's own input samples.  The kernels rely on it: a workgroup
+ * reads only what it alone writes, which makes d_out == d_in (in place, the case an encoder uses) legal and the stage one read and one
+ * write of the plane.
+ * xDeblockLumaGpu writes only m_Y of d_out -- every in-frame sample, filtered or copied --, xDeblockChromaGpu only m_C, xDeblockGpu both
+ * in one launch, bit-identical to the pair; m_I is never read or written.  x266_deblock_t is a host struct read during the call; the
+ * pointers in it are device pointers.  d_in and d_out are 16-byte aligned, d_mv 8, d_nnz 4, the byte arrays 1.  X266HIP_EINVAL for a NULL
+ * p, a NULL or misaligned frame, a misaligned side array, a bad size, qp outside 0..51 when d_qp == NULL, an offset outside -6..6, a span
+ * that does not fit in the address space, or d_out overlapping d_in (other than d_out == d_in) or a side array.  The calls allocate
+ * nothing and can be captured into a graph. */
+typedef struct x266_deblock_t {
+    const uint8_t  *d_class;             /* [6 n_ctu] as xTransformCtuFromTilesDev reads it; NULL: every region is (DCT-II, 32) */
+    const uint8_t  *d_intra;             /* [6 n_ctu], entries q = 0..3 (luma quadrants) read, non-zero = intra; NULL: none    */
+    const uint32_t *d_nnz;               /* [6 n_ctu] as xDct32CodeCtuTilesGpu writes it; NULL: every region counts as coded  */
+    const uint8_t  *d_qp;                /* [6 n_ctu], min(.., 51) as xQuantRegionsGpu; NULL: the scalar qp (0..51)            */
+    const x266_me_result_t *d_mv;        /* quarter luma samples, one per 8x8 block, raster order; NULL: the motion term never fires */
+    int qp, beta_offset_div2, tc_offset_div2;   /* offsets -6..6 */
+} x266_deblock_t;
+int xDeblockLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
+                    x266_ref_block_t *d_out, void *stream);
+int xDeblockChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
+                      x266_ref_block_t *d_out, void *stream);
+int xDeblockGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
+                x266_ref_block_t *d_out, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; d_a and d_b 16-byte,
  * d_out 4-byte aligned): d_out[b] = sum |a - b|, exactly sad() of

@@ -14,6 +14,12 @@ OP_DCT32_FWD, OP_DCT32_INV, OP_SATD8X8 = 0, 1, 2
 PRESET_CLOSED_FORM, PRESET_VTM_DST7, PRESET_VTM_DCT8 = 0, 1, 2
 
 
+class DeblockParams(ctypes.Structure):
+    """x266_deblock_t of include/x266hip.h"""
+    _fields_ = [("d_class", _P), ("d_intra", _P), ("d_nnz", _P), ("d_qp", _P), ("d_mv", _P),
+                ("qp", ctypes.c_int), ("beta_offset_div2", ctypes.c_int), ("tc_offset_div2", ctypes.c_int)]
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -108,6 +114,8 @@ def load_library(path=None):
     for name in ("xMotionCompQpelLumaGpu", "xMotionCompQpelChromaGpu", "xMotionCompQpelGpu"):
         getattr(L, name).argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xSatd8x8RefineQpelFromTilesGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]
+    for name in ("xDeblockLumaGpu", "xDeblockChromaGpu", "xDeblockGpu"):
+        getattr(L, name).argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeblockParams), _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xQuantRegionsGpu.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -661,6 +669,55 @@ class Codec:
         cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
         costs = dcost.download(np.uint32, nb * 49).reshape(nb, 49) if want_costs else None
         return mv, cost, costs
+
+    @staticmethod
+    def deblock_params(d_class=0, d_intra=0, d_nnz=0, d_qp=0, d_mv=0, qp=0, beta_offset_div2=0, tc_offset_div2=0):
+        """an x266_deblock_t from device addresses (0: NULL, the documented default of that array)"""
+        return DeblockParams(d_class or None, d_intra or None, d_nnz or None, d_qp or None, d_mv or None, qp, beta_offset_div2, tc_offset_div2)
+
+    def deblock_luma_dev(self, d_in, width, height, params, d_out, stream=0):
+        self._check(self.L.xDeblockLumaGpu(self.ctx, d_in, width, height, ctypes.byref(params), d_out, stream), "xDeblockLumaGpu")
+
+    def deblock_chroma_dev(self, d_in, width, height, params, d_out, stream=0):
+        self._check(self.L.xDeblockChromaGpu(self.ctx, d_in, width, height, ctypes.byref(params), d_out, stream), "xDeblockChromaGpu")
+
+    def deblock_dev(self, d_in, width, height, params, d_out, stream=0):
+        self._check(self.L.xDeblockGpu(self.ctx, d_in, width, height, ctypes.byref(params), d_out, stream), "xDeblockGpu")
+
+    def deblock(self, tiles, w, h, planes="both", in_place=False, base=None, cls=None, intra=None, nnz=None, qps=None, mv=None,
+                qp=0, beta_offset_div2=0, tc_offset_div2=0):
+        """numpy convenience around xDeblockGpu (planes="both") / xDeblockLumaGpu ("luma") / xDeblockChromaGpu ("chroma"): a tile
+        array and the side arrays of x266_deblock_t (cls, intra, qps: uint8 [6 n_ctu]; nnz: uint32 [6 n_ctu]; mv: int16 [nb, 2] in
+        quarter samples; None: NULL) -> the deblocked tile array.  in_place: d_out == d_in; otherwise what the call does not write
+        comes from `base` (a tile array; None: zeros)."""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        assert src.size == w * h * 2
+        fn = {"both": self.deblock_dev, "luma": self.deblock_luma_dev, "chroma": self.deblock_chroma_dev}[planes]
+        keep = []
+
+        def up(a, dtype):
+            if a is None:
+                return 0
+            a = np.ascontiguousarray(a, dtype)
+            keep.append(self.alloc(max(a.nbytes, 16)))
+            keep[-1].upload(a)
+            return keep[-1].ptr
+
+        rec = None
+        if mv is not None:
+            rec = np.zeros(((h // 8) * (w // 8), 4), np.int16)
+            rec[:, :2] = np.asarray(mv, np.int16).reshape(-1, 2)
+        params = self.deblock_params(up(cls, np.uint8), up(intra, np.uint8), up(nnz, np.uint32), up(qps, np.uint8), up(rec, np.int16),
+                                     qp, beta_offset_div2, tc_offset_div2)
+        d_in = self.alloc(src.nbytes)
+        d_in.upload(src)
+        d_out = d_in
+        if not in_place:
+            d_out = self.alloc(src.nbytes)
+            d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        fn(d_in.ptr, w, h, params, d_out.ptr)
+        self.stream_sync()
+        return d_out.download(np.uint8, src.size)
 
     def transform_ctu_from_tiles_dev(self, d_cur, d_pred, w, h, d_class, d_coef, stream=0):
         self._check(self.L.xTransformCtuFromTilesDev(self.ctx, d_cur, d_pred, w, h, d_class, d_coef, stream), "xTransformCtuFromTilesDev")

@@ -238,6 +238,9 @@ hipError_t launch_mc_qpel(const x266_ref_block_t *d_ref, const x266_me_result_t 
                           hipStream_t stream);
 hipError_t launch_satd_refine_qpel(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
                                    const x266_me_result_t *d_int, x266_me_result_t *d_best, uint32_t *d_costs, hipStream_t stream);
+// planes: 1 = m_Y, 2 = m_C, 3 = both in one launch
+hipError_t launch_deblock(int planes, const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const x266_deblock_t &p,
+                          hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

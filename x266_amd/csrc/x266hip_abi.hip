@@ -1466,6 +1466,52 @@ int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_c
     return X266HIP_OK;
 }
 
+// ---- in-loop deblocking of tiled frames (x266_deblock.hpp) ---------------------------------------------------------------------------
+// The three calls share their argument rules and differ in the planes they write (1 = m_Y, 2 = m_C, 3 = both).
+static int deblock_call(x266hip_ctx *ctx, const char *name, int planes, const x266_ref_block_t *d_in, int width, int height,
+                        const x266_deblock_t *p, x266_ref_block_t *d_out, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (!p) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL parameter struct").c_str());
+    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
+    if ((!p->d_qp && (p->qp < 0 || p->qp > 51)) || p->beta_offset_div2 < -6 || p->beta_offset_div2 > 6 || p->tc_offset_div2 < -6 || p->tc_offset_div2 > 6)
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": qp must be 0..51 (without d_qp) and the offsets -6..6").c_str());
+    if (!d_in || !d_out || ((((uintptr_t)d_in | (uintptr_t)d_out)) & 15u) || ((uintptr_t)p->d_mv & 7u) || ((uintptr_t)p->d_nnz & 3u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
+    const size_t n_ctus = (size_t)((width + 63) / 64) * (size_t)((height + 63) / 64), tab_bytes = n_ctus * 6, nnz_bytes = n_ctus * 24;
+    if (!span_fits(d_in, tile_bytes) || !span_fits(d_out, tile_bytes) || !span_fits(p->d_mv, mv_bytes) || !span_fits(p->d_nnz, nnz_bytes) ||
+        !span_fits(p->d_class, tab_bytes) || !span_fits(p->d_intra, tab_bytes) || !span_fits(p->d_qp, tab_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": a buffer does not fit in the address space").c_str());
+    if ((d_out != d_in && ranges_overlap(d_out, tile_bytes, d_in, tile_bytes)) || ranges_overlap(d_out, tile_bytes, p->d_mv, mv_bytes) ||
+        ranges_overlap(d_out, tile_bytes, p->d_nnz, nnz_bytes) || ranges_overlap(d_out, tile_bytes, p->d_class, tab_bytes) ||
+        ranges_overlap(d_out, tile_bytes, p->d_intra, tab_bytes) || ranges_overlap(d_out, tile_bytes, p->d_qp, tab_bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": d_out overlaps an input (only d_out == d_in is allowed)").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_deblock(planes, d_in, d_out, width, height, *p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "deblocking launch", e);
+    return X266HIP_OK;
+}
+
+int xDeblockLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p, x266_ref_block_t *d_out,
+                    void *stream)
+{
+    return deblock_call(ctx, "xDeblockLumaGpu", 1, d_in, width, height, p, d_out, stream);
+}
+
+int xDeblockChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p, x266_ref_block_t *d_out,
+                      void *stream)
+{
+    return deblock_call(ctx, "xDeblockChromaGpu", 2, d_in, width, height, p, d_out, stream);
+}
+
+int xDeblockGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p, x266_ref_block_t *d_out,
+                void *stream)
+{
+    return deblock_call(ctx, "xDeblockGpu", 3, d_in, width, height, p, d_out, stream);
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).
