@@ -576,6 +576,60 @@ int xDeblockChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width,
                       x266_ref_block_t *d_out, void *stream);
 int xDeblockGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
                 x266_ref_block_t *d_out, void *stream);
+/* Sample adaptive offset (SAO) of a tiled frame, the second in-loop filter (no upstream counterpart, as for the quantiser and the
+ * deblocking filter): HEVC's SAO at 8-bit depth, encoder statistics and decision included.  The categories, ranges and rate model
+ * are HEVC's as recalled, unverified offline; the arithmetic here is the contract, not a standard text.  clip8 = clamp to 0..255.
+ * Frame: width, height positive multiples of 16; ceil(width / 64) x ceil(height / 64) CTUs in raster order, the right and bottom
+ * ones cut by the frame exactly as in xTransformCtuFromTilesDev.  Component 0 of CTU t is Y (m_Y, up to 64 x 64 samples), 1 and 2
+ * are U and V (the even and odd bytes of m_C, up to 32 x 32 samples each); only in-frame samples exist; m_I is never read or written.
+ * Categories.  `dec` is the frame being filtered, `org` the source.  For sample c = dec[y][x] of a PW x PH plane, edge-offset (EO)
+ * class k has the neighbours a, b:  k = 0: (x-1, y), (x+1, y);  1: (x, y-1), (x, y+1);  2: (x-1, y-1), (x+1, y+1);
+ * 3: (x+1, y-1), (x-1, y+1).  A neighbour outside the plane: category 0 for that class.  A neighbour in another CTU is an ordinary
+ * sample of the input frame.  Otherwise s = sign(c - a) + sign(c - b) gives the category: -2 -> 1, -1 -> 2, 0 -> 0, +1 -> 3,
+ * +2 -> 4.  The band of a sample is c >> 3 (0..31).
+ * Statistics.  d_stats holds per CTU t and component m 48 pairs (count uint32, sum int32), pair e at
+ * d_stats[((3 t + m) 48 + e) 2 + {0, 1}] (384 bytes per record): e = 4 k + (cat - 1) for EO class k and category 1..4, e = 16 + band
+ * for the bands; count = the CTU's in-frame samples of that component in the bin, sum = the sum of (org - dec) over them.  Every
+ * record of every CTU is written (zeros where nothing falls).  |sum| <= 4096 * 255: int32 is exact.
+ * Decision.  lambda_q4 in 0..65535 is the Lagrange multiplier in 1/16 of a squared-error unit per bin; all arithmetic is integer.
+ *   Offset of a bin (N, E) in [lo, hi]: h0 = clamp(sign(E) ((2 |E| + N) / (2 N)), lo, hi), h0 = 0 if N = 0; the candidates are h0,
+ *   each step of 1 towards 0, and 0; J(h) = 16 (N h^2 - 2 h E) + lambda_q4 R(h), R(h) = min(|h| + 1, 7), plus 1 for a band with
+ *   h != 0 (its sign); least J wins, among equal costs the smaller |h|.
+ *   EO class k: categories 1, 2 use [0, 7], 3, 4 use [-7, 0]; J_EO(k) = the sum of the four least J.
+ *   Band offset (BO): every band uses [-7, 7]; position p in 0..28 minimises J_BO(p) = sum_{i<4} J(band p + i), the smallest p first.
+ *   Luma, candidates in this order: off, J = lambda_q4;  EO k = 0..3, J = 4 lambda_q4 + J_EO(k);  BO, J = 7 lambda_q4 + J_BO(p).
+ *   Chroma: U and V share the type and, for EO, the class (HEVC's syntax); offsets and the band position are per plane.  off,
+ *   J = lambda_q4;  EO k, J = 4 lambda_q4 + J_EO^U(k) + J_EO^V(k);  BO, J = 12 lambda_q4 + J_BO^U(p_U) + J_BO^V(p_V).
+ *   The candidate of least J wins, among equal costs the first in the order.
+ *   32 bits suffice: a CTU component has at most 4096 samples, so over the bins of one class (or over all bands) sum N <= 4096 and
+ *   sum |E| <= 4096 * 255; with |h| <= 7, |16 sum (N h^2 - 2 h E)| <= 16 (4096 * 49 + 14 * 4096 * 255) < 2.4e8, the rate terms of
+ *   a candidate are at most 65535 * (12 + 8 * 8) < 5.1e6, and a chroma candidate adds two such sums: below 2^31.
+ *   Output: one x266_sao_t per CTU and component at d_param[3 t + m]: type 0 off, 1 BO, 2 EO; arg = the EO class or the band
+ *   position; off = the offsets of categories 1..4 (EO) or of bands p..p+3 (BO); an off record is all zero; zero[] is written as 0.
+ * Apply.  Each sample uses the record of its own CTU and component.  type == 2: out = clip8(c + off[cat - 1]) for category 1..4 of
+ * class arg & 3, category 0 copies.  type == 1: j = ((c >> 3) - arg) & 31; j < 4: out = clip8(c + off[j]), otherwise a copy (the
+ * position wraps as in the standard, although the decision emits none above 28).  Any other type copies.  Offsets are taken as any
+ * int8; no device byte is validated.  Every in-frame sample of m_Y and m_C of d_out is written, filtered or copied.
+ * xSaoSearchGpu is xSaoStatsGpu and xSaoDecideGpu in one launch, bit-identical to the pair (the form an encoder uses: the bins need
+ * not reach memory); a non-NULL d_stats also receives the statistics.
+ * Frames are 16-byte aligned, d_stats 4, d_param 8.  d_org == d_dec is allowed (both are read-only).  Apply reads neighbours that
+ * other workgroups write: d_out overlapping d_in in any way, d_out == d_in included, returns X266HIP_EINVAL, as does any output
+ * overlapping any other buffer of its call, a NULL or misaligned pointer (only xSaoSearchGpu's d_stats may be NULL), a bad size,
+ * lambda_q4 outside 0..65535, n_ctu >= 2^31 or a span that does not fit in the address space.  n_ctu == 0 returns 0 and launches
+ * nothing.  Nothing is allocated; every call can be captured into a graph; a refused call launches nothing and names itself in
+ * xHipLastError. */
+typedef struct x266_sao_t {
+    uint8_t type, arg;
+    int8_t  off[4];
+    uint8_t zero[2];
+} x266_sao_t;                            /* 8 bytes */
+int xSaoStatsGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height,
+                 int32_t *d_stats, void *stream);
+int xSaoDecideGpu(x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, int lambda_q4, x266_sao_t *d_param, void *stream);
+int xSaoSearchGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height,
+                  int lambda_q4, x266_sao_t *d_param, int32_t *d_stats, void *stream);
+int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_sao_t *d_param,
+                 x266_ref_block_t *d_out, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; d_a and d_b 16-byte,
  * d_out 4-byte aligned): d_out[b] = sum |a - b|, exactly sad() of

@@ -116,6 +116,10 @@ def load_library(path=None):
     L.xSatd8x8RefineQpelFromTilesGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]
     for name in ("xDeblockLumaGpu", "xDeblockChromaGpu", "xDeblockGpu"):
         getattr(L, name).argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeblockParams), _P, _P]
+    L.xSaoStatsGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xSaoDecideGpu.argtypes = [_P, _P, _SZ, ctypes.c_int, _P, _P]
+    L.xSaoSearchGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]
+    L.xSaoApplyGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xQuantRegionsGpu.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -716,6 +720,71 @@ class Codec:
             d_out = self.alloc(src.nbytes)
             d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
         fn(d_in.ptr, w, h, params, d_out.ptr)
+        self.stream_sync()
+        return d_out.download(np.uint8, src.size)
+
+    def sao_stats_dev(self, d_org, d_dec, width, height, d_stats, stream=0):
+        self._check(self.L.xSaoStatsGpu(self.ctx, d_org, d_dec, width, height, d_stats, stream), "xSaoStatsGpu")
+
+    def sao_decide_dev(self, d_stats, n_ctu, lambda_q4, d_param, stream=0):
+        self._check(self.L.xSaoDecideGpu(self.ctx, d_stats, n_ctu, int(lambda_q4), d_param, stream), "xSaoDecideGpu")
+
+    def sao_search_dev(self, d_org, d_dec, width, height, lambda_q4, d_param, d_stats=0, stream=0):
+        self._check(self.L.xSaoSearchGpu(self.ctx, d_org, d_dec, width, height, int(lambda_q4), d_param, d_stats or None, stream), "xSaoSearchGpu")
+
+    def sao_apply_dev(self, d_in, width, height, d_param, d_out, stream=0):
+        self._check(self.L.xSaoApplyGpu(self.ctx, d_in, width, height, d_param, d_out, stream), "xSaoApplyGpu")
+
+    def _sao_frames(self, org_tiles, dec_tiles, w, h):
+        org = np.ascontiguousarray(org_tiles, np.uint8).ravel()
+        dec = np.ascontiguousarray(dec_tiles, np.uint8).ravel()
+        assert org.size == w * h * 2 and dec.size == w * h * 2
+        d_org, d_dec = self.alloc(org.nbytes), self.alloc(dec.nbytes)
+        d_org.upload(org)
+        d_dec.upload(dec)
+        return d_org, d_dec
+
+    def sao_stats(self, org_tiles, dec_tiles, w, h):
+        """numpy convenience around xSaoStatsGpu: the source and the decoded tile array -> int32 [n_ctu, 3, 48, 2] (count, sum)"""
+        n = self.ctu_count(w, h)
+        d_org, d_dec = self._sao_frames(org_tiles, dec_tiles, w, h)
+        d_stats = self.alloc(n * 1152)
+        self.sao_stats_dev(d_org.ptr, d_dec.ptr, w, h, d_stats.ptr)
+        self.stream_sync()
+        return d_stats.download(np.int32, n * 288).reshape(n, 3, 48, 2)
+
+    def sao_decide(self, stats, lambda_q4):
+        """numpy convenience around xSaoDecideGpu: int32 [n_ctu, 3, 48, 2] -> the x266_sao_t records as uint8 [n_ctu, 3, 8]"""
+        st = np.ascontiguousarray(stats, np.int32).reshape(-1, 3, 48, 2)
+        n = st.shape[0]
+        d_stats, d_param = self.alloc(max(st.nbytes, 16)), self.alloc(max(n * 24, 16))
+        d_stats.upload(st)
+        self.sao_decide_dev(d_stats.ptr, n, lambda_q4, d_param.ptr)
+        self.stream_sync()
+        return d_param.download(np.uint8, n * 24).reshape(n, 3, 8)
+
+    def sao_search(self, org_tiles, dec_tiles, w, h, lambda_q4, want_stats=False):
+        """numpy convenience around xSaoSearchGpu: two tile arrays -> (records uint8 [n_ctu, 3, 8], statistics or None)"""
+        n = self.ctu_count(w, h)
+        d_org, d_dec = self._sao_frames(org_tiles, dec_tiles, w, h)
+        d_param = self.alloc(n * 24)
+        d_stats = self.alloc(n * 1152) if want_stats else None
+        self.sao_search_dev(d_org.ptr, d_dec.ptr, w, h, lambda_q4, d_param.ptr, d_stats.ptr if want_stats else 0)
+        self.stream_sync()
+        return (d_param.download(np.uint8, n * 24).reshape(n, 3, 8),
+                d_stats.download(np.int32, n * 288).reshape(n, 3, 48, 2) if want_stats else None)
+
+    def sao_apply(self, tiles, w, h, params, base=None):
+        """numpy convenience around xSaoApplyGpu: a tile array and the records (uint8 [n_ctu, 3, 8]) -> the filtered tile array; m_I,
+        which the call does not write, comes from `base` (a tile array; None: zeros)"""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        rec = np.ascontiguousarray(params, np.uint8).ravel()
+        assert src.size == w * h * 2 and rec.size == self.ctu_count(w, h) * 24
+        d_in, d_par, d_out = self.alloc(src.nbytes), self.alloc(rec.nbytes), self.alloc(src.nbytes)
+        d_in.upload(src)
+        d_par.upload(rec)
+        d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        self.sao_apply_dev(d_in.ptr, w, h, d_par.ptr, d_out.ptr)
         self.stream_sync()
         return d_out.download(np.uint8, src.size)
 

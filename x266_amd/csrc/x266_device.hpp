@@ -241,6 +241,11 @@ hipError_t launch_satd_refine_qpel(const x266_ref_block_t *d_cur, const x266_ref
 // planes: 1 = m_Y, 2 = m_C, 3 = both in one launch
 hipError_t launch_deblock(int planes, const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const x266_deblock_t &p,
                           hipStream_t stream);
+// d_param NULL: statistics only; otherwise statistics and decision in one launch, and d_stats may be NULL
+hipError_t launch_sao_stats(const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, int lambda_q4, int32_t *d_stats,
+                            x266_sao_t *d_param, hipStream_t stream);
+hipError_t launch_sao_decide(const int32_t *d_stats, size_t n_ctu, int lambda_q4, x266_sao_t *d_param, hipStream_t stream);
+hipError_t launch_sao_apply(const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const x266_sao_t *d_param, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

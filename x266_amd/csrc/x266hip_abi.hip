@@ -1512,6 +1512,93 @@ int xDeblockGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int h
     return deblock_call(ctx, "xDeblockGpu", 3, d_in, width, height, p, d_out, stream);
 }
 
+// ---- sample adaptive offset on tiled frames (x266_sao.hpp) -----------------------------------------------------------------------------
+struct SaoSpan {
+    const void *p;
+    size_t bytes;
+};
+
+static bool sao_frame_ok(int width, int height) { return width > 0 && height > 0 && !(width & 15) && !(height & 15); }
+
+// every output against every other buffer of the call; `n_out` leading entries of `spans` are the outputs (a NULL one has 0 bytes)
+static bool sao_outputs_overlap(const SaoSpan *spans, int n, int n_out)
+{
+    for (int o = 0; o < n_out; ++o)
+        for (int i = 0; i < n; ++i)
+            if (i != o && ranges_overlap(spans[o].p, spans[o].bytes, spans[i].p, spans[i].bytes)) return true;
+    return false;
+}
+
+static int sao_stats_call(x266hip_ctx *ctx, const char *name, bool decide, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width,
+                          int height, int lambda_q4, x266_sao_t *d_param, int32_t *d_stats, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (!sao_frame_ok(width, height)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
+    if (lambda_q4 < 0 || lambda_q4 > 65535) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": lambda_q4 must be 0..65535").c_str());
+    if (!d_org || !d_dec || (decide ? !d_param : !d_stats) || ((((uintptr_t)d_org | (uintptr_t)d_dec)) & 15u) || ((uintptr_t)d_param & 7u) ||
+        ((uintptr_t)d_stats & 3u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_ctus = (size_t)((width + 63) / 64) * (size_t)((height + 63) / 64);
+    const SaoSpan spans[4] = {{d_param, d_param ? n_ctus * 24 : 0}, {d_stats, d_stats ? n_ctus * 1152 : 0}, {d_org, tile_bytes}, {d_dec, tile_bytes}};
+    for (const SaoSpan &s : spans)
+        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": a buffer does not fit in the address space").c_str());
+    if (sao_outputs_overlap(spans, 4, 2)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": an output overlaps another buffer").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_sao_stats(d_org, d_dec, width, height, lambda_q4, d_stats, d_param, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAO statistics launch", e);
+    return X266HIP_OK;
+}
+
+int xSaoStatsGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, int32_t *d_stats, void *stream)
+{
+    return sao_stats_call(ctx, "xSaoStatsGpu", false, d_org, d_dec, width, height, 0, nullptr, d_stats, stream);
+}
+
+int xSaoSearchGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, int lambda_q4,
+                  x266_sao_t *d_param, int32_t *d_stats, void *stream)
+{
+    return sao_stats_call(ctx, "xSaoSearchGpu", true, d_org, d_dec, width, height, lambda_q4, d_param, d_stats, stream);
+}
+
+int xSaoDecideGpu(x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, int lambda_q4, x266_sao_t *d_param, void *stream)
+{
+    const char *name = "xSaoDecideGpu: ";
+    if (!ctx) return X266HIP_EINVAL;
+    if (lambda_q4 < 0 || lambda_q4 > 65535) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "lambda_q4 must be 0..65535").c_str());
+    if (!d_stats || !d_param || ((uintptr_t)d_stats & 3u) || ((uintptr_t)d_param & 7u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
+    if (n_ctu > 0x7FFFFFFFull) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "n_ctu must be below 2^31").c_str());
+    const SaoSpan spans[2] = {{d_param, n_ctu * 24}, {d_stats, n_ctu * 1152}};
+    if (!span_fits(spans[0].p, spans[0].bytes) || !span_fits(spans[1].p, spans[1].bytes))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
+    if (sao_outputs_overlap(spans, 2, 1)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "d_param overlaps d_stats").c_str());
+    if (n_ctu == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    hipError_t e = launch_sao_decide(d_stats, n_ctu, lambda_q4, d_param, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAO decision launch", e);
+    return X266HIP_OK;
+}
+
+int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_sao_t *d_param, x266_ref_block_t *d_out,
+                 void *stream)
+{
+    const char *name = "xSaoApplyGpu: ";
+    if (!ctx) return X266HIP_EINVAL;
+    if (!sao_frame_ok(width, height)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be multiples of 16").c_str());
+    if (!d_in || !d_out || !d_param || ((((uintptr_t)d_in | (uintptr_t)d_out)) & 15u) || ((uintptr_t)d_param & 7u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
+    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_ctus = (size_t)((width + 63) / 64) * (size_t)((height + 63) / 64);
+    const SaoSpan spans[3] = {{d_out, tile_bytes}, {d_in, tile_bytes}, {d_param, n_ctus * 24}};
+    for (const SaoSpan &s : spans)
+        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
+    if (sao_outputs_overlap(spans, 3, 1))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "d_out overlaps d_in or d_param (in place is not possible)").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_sao_apply(d_in, d_out, width, height, d_param, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAO apply launch", e);
+    return X266HIP_OK;
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).
