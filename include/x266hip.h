@@ -669,6 +669,62 @@ int xIntra32ResidualDct32Dev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, c
 /* Alignment in bytes: d_refs 16, d_src 16, d_costs 4, d_best_mode 1. */
 int xIntra32CostsDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_src,
                      uint32_t *d_costs, uint8_t *d_best_mode, size_t n_blocks, void *stream);
+/* Intra coding of tiled frames.  HEVC's 32x32 intra scheme at 8 bits as recalled, unverified offline; the arithmetic written here is the
+ * contract.  width, height positive multiples of 64 (the caller pads); CTUs of 64x64 in raster order, n_ctu of them.
+ *
+ * The reference set of a 32x32 block is an x266_intra_ref_t: left[y] = p[-1][y], y = 0..63; top[0] = the corner sample;
+ * top[1+x] = p[x][-1], x = 0..63; the 15 reserved bytes are written as 0.  It has five segments: BL = left[32..63], L = left[0..31],
+ * C = top[0], T = top[1..32], TR = top[33..64].  A segment is available iff the 32x32 block that holds it lies inside the frame and
+ * precedes the current block in coding order: CTUs in raster order, inside a CTU the luma quadrants q = 0, 1, 2, 3 (top-left,
+ * top-right, bottom-left, bottom-right).  For luma block (bx, by) on the 32-sample grid, q = 2 (by & 1) + (bx & 1):
+ *     L  = block (bx-1, by)    in the frame            T  = block (bx, by-1)    in the frame
+ *     C  = block (bx-1, by-1)  in the frame            TR = block (bx+1, by-1)  in the frame and q != 3
+ *     BL = block (bx-1, by+1)  in the frame and q == 0
+ * For the 32x32 U or V block of CTU (cx, cy), on its own plane, in a frame ctus_x CTUs wide:
+ *     L: cx > 0     T: cy > 0     C: cx > 0 and cy > 0     TR: cy > 0 and cx + 1 < ctus_x     BL: never
+ * Substitution (H.265 8.4.4.2.2): order the 129 samples left[63], ..., left[0], top[0], top[1], ..., top[64].  If none is available,
+ * every sample is 128.  Otherwise every sample in front of the first available one takes that one's value, and every later
+ * unavailable sample takes the value of its predecessor in this order.  No reference smoothing filter and no DC / horizontal /
+ * vertical edge filter is applied (xIntra32PredictDev has none, and HEVC has no edge filter at 32).
+ *
+ * xIntra32RefsFromTilesGpu -- the open-loop gather: the sets of a frame's OWN samples under exactly this rule.  component 0 (luma,
+ * m_Y): 4 n_ctu sets, d_refs[4 ctu + q]; component 1 (U) or 2 (V) (the even / odd bytes of m_C): n_ctu sets, d_refs[ctu].  It
+ * connects xIntra32CostsDev / PredictDev / ResidualDct32Dev to tiled frames; on the source frame it gives the open-loop mode
+ * decision of a whole frame in one launch.  m_I is never read.  d_frame and d_refs are 16-byte aligned.  X266HIP_EINVAL for a NULL
+ * or misaligned pointer, a bad size, a component outside 0..2, a span that does not fit in the address space, or d_refs
+ * overlapping d_frame.
+ *
+ * xIntra32CodeFrameGpu -- the closed loop, in which a block's references are the reconstructed samples of its neighbours.  Regions
+ * are 6 ctu + q as for xDct32CodeCtuTilesGpu: Y0 Y1 Y2 Y3 U V.  For every CTU in coding order and every luma quadrant q:
+ *   1. the set is gathered from m_Y of d_recon by the rule above;
+ *   2. the mode: d_mode_in == NULL: the mode of least xIntra32CostsDev cost -- the sum over the sixteen 8x8 sub-blocks of
+ *      satd8x8(cur - prediction m), m = 0..34, the lowest index on ties; otherwise d_mode_in[6 ctu + q] (modes above 34 are
+ *      undefined input, as for xIntra32PredictDev);
+ *   3. pred = the xIntra32PredictDev prediction of that mode on that set;
+ *   4. level = Q(DCT32(cur - pred)) with n = 5, the region's qp = min(d_qp[6 ctu + q], 51), or the scalar qp when d_qp == NULL,
+ *      and `rounding`, exactly as xQuantRegionsGpu;
+ *   5. recon = clip8(pred + IDCT32(Q^-1(level))) into m_Y of d_recon.
+ * Then U and V of the CTU: one set per plane from m_C of d_recon; both planes share ONE mode out of the candidate list
+ * (0, 26, 10, 1, the mode chosen for quadrant 0), in that order: cost(m) = cost_U(m) + cost_V(m), each the same 16-sub-block SATD
+ * sum on its plane; least cost wins, the first in the list on ties (a duplicate candidate is harmless).  With d_mode_in,
+ * d_mode_in[6 ctu + 4] serves both planes and entry 5 is ignored.  U is coded with the qp of region 4 and V with that of region 5,
+ * steps 3 to 5 as for luma, into m_C of d_recon.
+ * Outputs: d_level[ctu * 6144 + q * 1024 ..] and d_nnz[6 ctu + q] (d_nnz may be NULL), laid out as xDct32CodeCtuTilesGpu writes
+ * them; d_mode[6 ctu + q] = the mode used, entries 4 and 5 both the chroma mode; m_Y and m_C of d_recon.  m_I of d_recon is never
+ * read or written and m_I of d_cur is never read.  d_mode == d_mode_in is allowed; any other overlap of an output with any buffer
+ * of the call returns X266HIP_EINVAL, d_recon == d_cur included.
+ * Schedule: the dependence is serial by nature, so the call is a sequence of launches on the caller's stream, one per step, and
+ * stream order is its only synchronisation (no workgroup waits for another): region (cx, cy, q) runs at step 4 cx + 6 cy + q and a
+ * CTU's chroma at its q = 3 step, 4 ctus_x + 6 ctus_y - 6 steps in all; the result does not depend on the schedule.
+ * d_cur, d_recon and d_level are 16-byte aligned, d_nnz 4-byte; d_qp, d_mode_in and d_mode are bytes at any address.
+ * X266HIP_EINVAL for a NULL (d_cur, d_level, d_mode, d_recon) or misaligned pointer, a bad size, a scalar qp outside 0..51 when
+ * d_qp == NULL, rounding outside 0..511, or a span that does not fit in the address space.
+ * Both calls allocate nothing and can be captured into a graph; a refused call launches nothing and names itself in xHipLastError. */
+int xIntra32RefsFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_frame, int width, int height, int component,
+                             x266_intra_ref_t *d_refs, void *stream);
+int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int width, int height, const uint8_t *d_qp, int qp,
+                         int rounding, const uint8_t *d_mode_in, int16_t *d_level, uint32_t *d_nnz, uint8_t *d_mode,
+                         x266_ref_block_t *d_recon, void *stream);
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */

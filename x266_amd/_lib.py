@@ -120,6 +120,8 @@ def load_library(path=None):
     L.xSaoDecideGpu.argtypes = [_P, _P, _SZ, ctypes.c_int, _P, _P]
     L.xSaoSearchGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xSaoApplyGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
+    L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xIntra32CodeFrameGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xTransformCtuToTilesDev.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xQuantRegionsGpu.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -380,6 +382,52 @@ class Codec:
         self.intra32_costs_dev(d_r.ptr, d_s.ptr, d_c.ptr, d_b.ptr, n)
         self.stream_sync()
         return d_c.download(np.uint32, n * 35).reshape(n, 35), d_b.download(np.uint8, n)
+
+    def intra32_refs_from_tiles_dev(self, d_frame, w, h, component, d_refs, stream=0):
+        self._check(self.L.xIntra32RefsFromTilesGpu(self.ctx, d_frame, w, h, int(component), d_refs, stream), "xIntra32RefsFromTilesGpu")
+
+    def intra32_refs_from_tiles(self, tiles, w, h, component, base=None):
+        """numpy convenience around xIntra32RefsFromTilesGpu: a tile array of a w x h frame (multiples of 64) -> the reference sets of
+        its own samples as uint8 [n_sets, 144] (left[64] | top[65] | 15 reserved bytes): 4 per CTU for component 0, 1 for U (1) / V (2).
+        `base` pre-fills the output (None: zeros)"""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        n = self.ctu_count(w, h) * (4 if component == 0 else 1)
+        assert src.size == w * h * 2
+        d_in, d_out = self.alloc(src.nbytes), self.alloc(n * 144)
+        d_in.upload(src)
+        d_out.upload(np.zeros(n * 144, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        self.intra32_refs_from_tiles_dev(d_in.ptr, w, h, component, d_out.ptr)
+        self.stream_sync()
+        return d_out.download(np.uint8, n * 144).reshape(n, 144)
+
+    def intra32_code_frame_dev(self, d_cur, w, h, d_qp, qp, rounding, d_mode_in, d_level, d_nnz, d_mode, d_recon, stream=0):
+        self._check(self.L.xIntra32CodeFrameGpu(self.ctx, d_cur, w, h, d_qp or None, int(qp), int(rounding), d_mode_in or None, d_level, d_nnz or None,
+                                                d_mode, d_recon, stream), "xIntra32CodeFrameGpu")
+
+    def intra32_code_frame(self, cur_tiles, w, h, qps=None, qp=0, rounding=0, modes_in=None, base=None):
+        """numpy convenience around xIntra32CodeFrameGpu: the tile array of a w x h frame (multiples of 64), optionally 6 qp bytes and 6
+        mode bytes per CTU -> (levels [n_ctus, 6, 1024] int16, non-zero counts [n_ctus, 6] uint32, modes [n_ctus, 6] uint8, the
+        reconstructed tile array); m_I (never written) comes from `base` (a tile array; None: zeros)"""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        n = self.ctu_count(w, h)
+        assert cur.size == w * h * 2
+        dc, dr = self.alloc(cur.nbytes), self.alloc(cur.nbytes)
+        dl, dn, dm = self.alloc(n * 12288), self.alloc(max(n * 24, 16)), self.alloc(max(n * 6, 16))
+        dc.upload(cur)
+        dr.upload(np.zeros(cur.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        tabs = []
+        for t in (qps, modes_in):
+            if t is None:
+                tabs.append(None)
+                continue
+            t = np.ascontiguousarray(t, np.uint8).ravel()
+            assert t.size == 6 * n
+            tabs.append(self.alloc(max(t.nbytes, 16)))
+            tabs[-1].upload(t)
+        self.intra32_code_frame_dev(dc.ptr, w, h, tabs[0].ptr if tabs[0] else 0, qp, rounding, tabs[1].ptr if tabs[1] else 0, dl.ptr, dn.ptr, dm.ptr, dr.ptr)
+        self.stream_sync()
+        return (dl.download(np.int16, n * 6144).reshape(n, 6, 1024), dn.download(np.uint32, n * 6).reshape(n, 6),
+                dm.download(np.uint8, n * 6).reshape(n, 6), dr.download(np.uint8, cur.size))
 
     def mem_ceiling_dev(self, kind, d_src, d_dst, nbytes, stream=0):
         """kind 0 = streaming copy, 1 = read-only stream (one uint32 XOR per 2 KiB into d_dst): this box's memory ceilings"""

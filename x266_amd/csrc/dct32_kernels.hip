@@ -45,6 +45,7 @@
 
 #include <cstdint>
 
+#include "x266_code_region.hpp"
 #include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 #include "x266_mfma_blocks.hpp"
@@ -523,48 +524,7 @@ __global__ __launch_bounds__(256) void dct32_inv_ctu_to_tiles_kernel(const int16
 // registers and is the inverse's input fragment (inv_passes with the accumulator-order tables).  Quantisation is element-wise
 // (x266_quant.hpp, the functions quant_regions_kernel runs), so the two orientations hold the same levels.  The pred fragment the
 // forward pass loaded is the one the reconstruction adds to: a lane reads exactly the pred bytes it writes, so recon == pred is safe.
-__device__ __forceinline__ void code_region(const v4i &a, const v4i &b, const LaneConsts &kf, const LaneConsts &ki, const v16i &c2r,
-                                            const QuantParams &q, unsigned lane, unsigned char *slot, const TileLanes &t, char *dst_level,
-                                            uint32_t *nnz, v4i &o0, v4i &o1)
-{
-    v4i ylo, yhi;
-    pass1_planes<4>(pixels_pass1(a, b, kf), ylo, yhi);
-    {
-        const v16i acc = fwd_pass2(ylo, yhi, kf);
-        uint32_t z[8];
-        unsigned nonzero = 0;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int lo = quantise((int)(int16_t)(acc[2 * m] >> 11), q), hi = quantise((int)(int16_t)(acc[2 * m + 1] >> 11), q);
-            nonzero += (lo != 0) + (hi != 0);
-            z[m] = ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16);
-        }
-        v4i s0, s1;
-        frag_to_linear(slot, t, v4i{(int)z[0], (int)z[1], (int)z[2], (int)z[3]}, v4i{(int)z[4], (int)z[5], (int)z[6], (int)z[7]}, s0, s1);
-        store16_sc1nt(dst_level, s0);
-        store16_sc1nt(dst_level + 1024, s1);
-        if (nnz) {
-            const uint32_t total = wave_sum(nonzero);
-            if (lane == 0) *nnz = total;
-        }
-    }
-    v16i acc = fwd_pass2_swapped(ylo, yhi, kf, lane >> 5);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = dequantise(quantise((int)(int16_t)(acc[r] >> 11), q), q);   // bytes 0 / 1 = the int16 coefficient
-    v4i zlo, zhi;
-    pack_planes(acc, zlo, zhi);
-    inv_passes(zlo, zhi, ki, c2r, o0, o1);
-}
-
-// region `region` of the frame (6 per CTU): its qp byte clamped to 51, or the scalar qp
-__device__ __forceinline__ QuantParams region_quant(const uint8_t *__restrict__ qps, size_t region, unsigned qp, unsigned rounding)
-{
-    if (qps) {
-        qp = uniform_byte(qps, region);
-        qp = qp < 51u ? qp : 51u;
-    }
-    return quant_params(5u, qp, rounding);
-}
+// (code_region and region_quant live in x266_code_region.hpp: the intra frame kernels code their regions with the same functions)
 
 __global__ __launch_bounds__(256) void dct32_code_ctu_tiles_kernel(const x266_ref_block_t *cur, const x266_ref_block_t *pred, x266_ref_block_t *recon,
                                                                    int16_t *__restrict__ level, uint32_t *__restrict__ nnz,

@@ -168,6 +168,13 @@ hipError_t launch_intra32_residual_dct32(const x266_intra_ref_t *d_refs, const u
                                          int16_t *d_coef, size_t n, const DctOps *d_fwd_ops, hipStream_t stream);
 hipError_t launch_intra32_costs(const x266_intra_ref_t *d_refs, const uint8_t *d_src, uint32_t *d_costs, uint8_t *d_best_mode,
                                 size_t n, hipStream_t stream);
+// the sets of a tiled frame's own samples (component 0: four per CTU; 1 / 2: one), and the closed-loop intra coding of a frame: one launch per step
+hipError_t launch_intra32_refs_from_tiles(const x266_ref_block_t *d_frame, int width, int height, int component, x266_intra_ref_t *d_refs,
+                                          hipStream_t stream);
+int intra32_frame_steps(int width, int height);
+hipError_t launch_intra32_code_frame(const x266_ref_block_t *d_cur, x266_ref_block_t *d_recon, int16_t *d_level, uint32_t *d_nnz, const uint8_t *d_qp,
+                                     int qp, int rounding, const uint8_t *d_mode_in, uint8_t *d_mode, int width, int height,
+                                     const DctOps *d_fwd_ops, const DctOps *d_inv_acc_ops, hipStream_t stream);
 hipError_t launch_satd8x8_butterfly(const int16_t *d_diff, uint32_t *d_out, size_t n_blocks, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_transform_tiles(bool inverse, const int16_t *d_in, int16_t *d_out, size_t n_tiles, const uint32_t *d_tile_offsets,
                                   const uint8_t *d_tile_class, const TileTab *d_tab, const LaunchCfg &cfg, hipStream_t stream);

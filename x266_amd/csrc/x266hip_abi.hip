@@ -1599,6 +1599,54 @@ int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int 
     return X266HIP_OK;
 }
 
+// ---- intra coding of tiled frames (intra_frame_kernels.hip) ------------------------------------------------------------------------------
+int xIntra32RefsFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_frame, int width, int height, int component, x266_intra_ref_t *d_refs,
+                             void *stream)
+{
+    const char *name = "xIntra32RefsFromTilesGpu: ";
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 63) || (height & 63))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be positive multiples of 64").c_str());
+    if (component < 0 || component > 2) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "component must be 0, 1 or 2").c_str());
+    if (!d_frame || !d_refs || ((((uintptr_t)d_frame | (uintptr_t)d_refs)) & 15u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
+    const size_t n_sets = (size_t)(width / 64) * (size_t)(height / 64) * (component == 0 ? 4u : 1u);
+    const SaoSpan spans[2] = {{d_refs, n_sets * sizeof(x266_intra_ref_t)}, {d_frame, (size_t)width * (size_t)height * 2}};
+    for (const SaoSpan &s : spans)
+        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
+    if (sao_outputs_overlap(spans, 2, 1)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "d_refs overlaps d_frame").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_intra32_refs_from_tiles(d_frame, width, height, component, d_refs, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra reference gather launch", e);
+    return X266HIP_OK;
+}
+
+int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int width, int height, const uint8_t *d_qp, int qp, int rounding,
+                         const uint8_t *d_mode_in, int16_t *d_level, uint32_t *d_nnz, uint8_t *d_mode, x266_ref_block_t *d_recon, void *stream)
+{
+    const char *name = "xIntra32CodeFrameGpu: ";
+    if (!ctx) return X266HIP_EINVAL;
+    if (width <= 0 || height <= 0 || (width & 63) || (height & 63))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be positive multiples of 64").c_str());
+    if (!quant_scalars_ok(d_qp, qp, rounding)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "qp must be 0..51 (without d_qp) and rounding 0..511").c_str());
+    if (!d_cur || !d_level || !d_mode || !d_recon || ((((uintptr_t)d_cur | (uintptr_t)d_level | (uintptr_t)d_recon)) & 15u) || ((uintptr_t)d_nnz & 3u))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
+    const size_t n_ctus = (size_t)(width / 64) * (size_t)(height / 64), tile_bytes = (size_t)width * (size_t)height * 2;
+    // the four outputs first; d_mode_in may be d_mode itself (then it is not a buffer of its own) and d_nnz, d_qp, d_mode_in may be NULL
+    const bool in_place = d_mode_in == d_mode;
+    const SaoSpan spans[7] = {{d_recon, tile_bytes}, {d_level, n_ctus * 12288}, {d_mode, n_ctus * 6}, {d_nnz, d_nnz ? n_ctus * 24 : 0},
+                              {d_cur, tile_bytes}, {d_qp, d_qp ? n_ctus * 6 : 0}, {d_mode_in, d_mode_in && !in_place ? n_ctus * 6 : 0}};
+    for (const SaoSpan &s : spans)
+        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
+    if (sao_outputs_overlap(spans, 7, 4))
+        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "an output overlaps another buffer (only d_mode == d_mode_in is allowed)").c_str());
+    X_DEV(ctx);
+    hipError_t e = launch_intra32_code_frame(d_cur, d_recon, d_level, d_nnz, d_qp, qp, rounding, d_mode_in, d_mode, width, height, ctx->d_fwd, ctx->d_inv_acc,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra frame coding launch", e);
+    return X266HIP_OK;
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).
