@@ -91,15 +91,23 @@ int  xHipDeviceInfo(const x266hip_ctx *ctx, char *name, size_t name_cap,
  *   "autotune"               0 (default) / 1: boxes differ in which launch shape a few kernels run fastest in (by up to 5 %).  With 1, the FIRST
  *                            large call of a family -- xDct32FwdInvBatchDev with and without d_coef (>= 2^18 blocks), xSatd8x8BatchDev
  *                            (>= 2^23 blocks), xSadBatchDev edge >= 8 (>= 128 MiB per input) -- times the family's candidate shapes on the
- *                            caller's own buffers and stream (that one call is synchronous and launches the kernel ~20 times; every
- *                            launch writes the same bytes) and the context keeps the fastest (the default unless beaten by > 2 %); xHipAutotuneReport shows what was
- *                            measured.  Skipped under stream capture, for overlapping buffers and when the family's own knobs are set.
+ *                            caller's own buffers and stream (that one call is synchronous: 4 launches per candidate shape plus the final
+ *                            one, 33 for the 8 shapes of the first family; every launch writes the same bytes) and the context keeps the
+ *                            fastest (the default unless beaten by > 2 %); xHipAutotuneReport shows what was measured.  Skipped under
+ *                            stream capture, for overlapping buffers and when the family's own knobs are set ("satd_variant" included).
+ *                            2 + k (k = 0 .. 8) is a test hook: every call of these families, at any batch size > 0, launches candidate
+ *                            k of its table -- no timing, so also under capture; the same calls as above keep the default shape -- and
+ *                            a family with k or fewer candidates (8 / 5 / 6 / 5) returns X266HIP_EINVAL and launches nothing.
+ *                            Setting the option to any value forgets what the context has tuned or counted so far.
  * Rounds 1-3 had sixteen more (cache-policy bits, LDS staging on / off, padding, per-kernel LDS charges, ...): the forms they
  * selected lost their A/Bs (profiles/r01_*.txt) and are gone. */
 int  xHipSetOption(x266hip_ctx *ctx, const char *key, int value);
 int  xHipGetOption(const x266hip_ctx *ctx, const char *key, int *value);
 /* "autotune": one text line per tuned family -- "<family> choice <index> ms <per-candidate milliseconds, -1 = not launchable>" --
- * candidate 0 being the default shape (x266_amd/csrc/x266hip_abi.hip, k*Cands). */
+ * candidate 0 being the default shape (x266_amd/csrc/x266hip_abi.hip, k*Cands); under "autotune" = 2 + k one line per family
+ * that has launched since the option was set -- "<family> forced <k> launches <number of launches that took candidate k>".
+ * Families: dct32_fwd_inv, dct32_recon_only, satd8x8, sad8, sad16, sad32, sad64.  A `cap` that does not hold the whole text and
+ * its terminator returns X266HIP_EINVAL (buf[0] = 0): never a cut line. */
 int  xHipAutotuneReport(const x266hip_ctx *ctx, char *buf, size_t cap);
 
 /* ------------------------------------------------------------------------ */

@@ -1,6 +1,8 @@
 """GPU (-m gpu): the opt-in "autotune" option (include/x266hip.h).  Results never depend on it: every family is run with the option
 off and on, on the same inputs, and must write the same bytes -- whatever candidate shape the box made it keep; small batches, knobs set
 by the caller and overlapping buffers leave it untuned."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -45,15 +47,32 @@ def test_fused_forward_inverse_same_bytes_with_any_chosen_shape(tuned_codec, ora
     assert _same(codec, z0, z1, n * 2048) and _same(codec, r0, r1, n * 2048)
     head = z1.download(np.int16, 64 * 1024).reshape(64, 1024)
     assert np.array_equal(head, oracle.dct32_fwd(oracle.fill_residual(64 * 1024, 0x51)))
-    # every candidate, forced in turn through a fresh tuned state, writes the same bytes (the shapes differ in pipeline depth and run length)
+    # the tuning call launched all eight candidates over z1 / r1, but its last launch -- the kept shape -- overwrote what the others wrote: the
+    # comparison above holds that one shape.  Each candidate by itself is forced and held against the oracle in tests/test_gpu_launch_shapes.py
     codec.dct32_fwd_inv_dev(x.ptr, 0, r1.ptr, n)                         # reconstruction only: its own family
     codec.stream_sync()
     assert "dct32_recon_only" in codec.autotune_report() and _same(codec, r0, r1, n * 2048)
+    # the report: a buffer that cannot hold the whole text and its terminator is refused, never handed a cut line; the full text parses
+    full = ctypes.create_string_buffer(4096)
+    assert codec.L.xHipAutotuneReport(codec.ctx, full, len(full)) == 0
+    text = full.value
+    assert text.count(b"\n") == 2 and text.endswith(b"\n")
+    for cap in (1, 16, len(text)):
+        small = ctypes.create_string_buffer(b"?" * cap, cap)
+        assert codec.L.xHipAutotuneReport(codec.ctx, small, cap) == -1 and small.raw[:1] == b"\0", cap
+    exact = ctypes.create_string_buffer(len(text) + 1)
+    assert codec.L.xHipAutotuneReport(codec.ctx, exact, len(exact)) == 0 and exact.value == text
+    rep = codec.autotune_report()
+    assert sorted(rep) == ["dct32_fwd_inv", "dct32_recon_only"] and len(rep["dct32_fwd_inv"]["ms"]) == 8 and len(rep["dct32_recon_only"]["ms"]) == 5
+    assert all(0 <= v["choice"] < len(v["ms"]) and "forced" not in v for v in rep.values())
     # the caller's own knob wins over the tuner; overlapping buffers are never tuned on
     codec.set_option("dct32_fwdinv_blocks_per_wave", 3)
     codec.dct32_fwd_inv_dev(x.ptr, z1.ptr, r1.ptr, n)
     codec.stream_sync()
     assert _same(codec, z0, z1, n * 2048) and _same(codec, r0, r1, n * 2048)
+    assert sorted(codec.autotune_report()) == ["dct32_fwd_inv", "dct32_recon_only"]
+    codec.set_option("autotune", 1)                                      # setting the option, even to the value it has, forgets what was tuned
+    assert codec.autotune_report() == {}
 
 
 def test_satd_and_sad_batches_same_bytes(tuned_codec):

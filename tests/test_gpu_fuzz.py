@@ -72,6 +72,33 @@ def test_dct_and_satd_random_sizes_and_options(codec, oracle, n, kind, seed, opt
 
 
 @fuzz(25)
+@given(n=st.integers(1, 3000), cand=st.integers(0, 12), kind=st.integers(0, 2), seed=st.integers(1, 1 << 30), adaptive=st.integers(0, 1))
+def test_fused_forced_launch_shapes_random(codec, oracle, n, cand, kind, seed, adaptive):
+    """the fused forward + inverse call under every launch shape of the autotuner's two tables ("autotune" = 2 + k: cand 0..7 with the coefficient
+    output, 8..12 without), random sizes and data mixes, the per-wave run as the table has it or shrunk -- coefficients and reconstruction equal
+    the oracle, and the library reports that the forced candidate was the one launched"""
+    with_coef, k = cand < 8, cand % 8
+    family = "dct32_fwd_inv" if with_coef else "dct32_recon_only"
+    saved = codec.get_option("adaptive_per_wave")
+    try:
+        codec.set_option("adaptive_per_wave", adaptive)
+        codec.set_option("autotune", 2 + k)
+        x = _data(kind, n, 1024, seed)
+        z = oracle.dct32_fwd(x, threads=8)
+        din, dco, dre = codec.alloc(n * 2048), codec.alloc(n * 2048), codec.alloc(n * 2048)
+        din.upload(x)
+        codec.dct32_fwd_inv_dev(din.ptr, dco.ptr if with_coef else 0, dre.ptr, n)
+        codec.stream_sync()
+        assert codec.autotune_report() == {family: {"forced": k, "launches": 1}}
+        if with_coef:
+            assert np.array_equal(dco.download(np.int16, n * 1024).reshape(n, 1024), z), (k, n)
+        assert np.array_equal(dre.download(np.int16, n * 1024).reshape(n, 1024), oracle.dct32_inv(z, threads=8)), (family, k, n)
+    finally:
+        codec.set_option("autotune", 0)
+        codec.set_option("adaptive_per_wave", saved)
+
+
+@fuzz(25)
 @given(ttype=st.integers(0, 1), size=st.sampled_from([4, 8, 16]), n=st.integers(1, 3000), kind=st.integers(0, 1), seed=st.integers(1, 1 << 30),
        tpb=st.sampled_from([64, 128, 192, 256]), per_wave=st.integers(1, 4))
 def test_transform_set_random(codec, oracle, ttype, size, n, kind, seed, tpb, per_wave):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from _util import ROOT
+from test_gpu_launch_shapes import FUSED, FUSED_PARAMS, _fused_sizes
 
 pytestmark = pytest.mark.gpu
 W0 = os.path.join(ROOT, "x266_amd", "libx266hip_waits0.so")
@@ -51,8 +52,8 @@ def test_fused_forward_inverse(codec, waits0, n, with_coef, bpw):
 
 
 def test_fused_depth_three_shapes_of_the_autotuner(waits0):
-    """the DEPTH = 3 instantiation only runs when "autotune" picks it: force every candidate by timing on a box-sized batch and compare
-    tuned output (whatever was kept) against the all-waiting library's default"""
+    """a tuning call on a box-sized batch launches all eight candidates over the outputs; what is left, and compared with the all-waiting library's
+    default, is the output of the shape that was kept (each candidate by itself: test_fused_candidates_forced_in_both_builds below)"""
     import x266_amd
     n = (1 << 18) + 3
     tuned = x266_amd.Codec(0)
@@ -64,6 +65,30 @@ def test_fused_depth_three_shapes_of_the_autotuner(waits0):
         tuned.close()
     b = _fused(waits0, n, True, 0x71, {})
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("family,k", FUSED_PARAMS)
+def test_fused_candidates_forced_in_both_builds(codec, waits0, family, k):
+    """every entry of the autotuner's two fused tables -- the DEPTH = 3 and 4 pipelines among them -- forced ("autotune" = 2 + k) in the product and
+    in the all-waiting build alike, at the ragged sizes of tests/test_gpu_launch_shapes.py (the last wave's run at every value where the counted
+    waits change case, and a large ragged batch): the same bytes.  A count that is too high usually still passes -- the late DMA lands in time --
+    so this extends the check above to the deep shapes without proving their counts; the oracle comparison of test_gpu_launch_shapes.py is the
+    deterministic one."""
+    with_coef = family == "dct32_fwd_inv"
+    _, ragged = _fused_sizes(FUSED[family][k])
+    try:
+        for cd in (codec, waits0):
+            cd.set_option("autotune", 2 + k)
+        for n in ragged:
+            a, b = (_fused(cd, n, with_coef, 0x75 + n, {"adaptive_per_wave": 0}) for cd in (codec, waits0))
+            assert np.array_equal(a[1], b[1]), (family, k, n)
+            if with_coef:
+                assert np.array_equal(a[0], b[0]), (family, k, n)
+        for cd in (codec, waits0):                                       # both really ran candidate k, every time
+            assert cd.autotune_report()[family] == {"forced": k, "launches": len(ragged)}
+    finally:
+        for cd in (codec, waits0):
+            cd.set_option("autotune", 0); cd.set_option("adaptive_per_wave", 1)
 
 
 @pytest.mark.parametrize("n", [1, 31, 32, 33, 1000, (1 << 17) + 7])

@@ -283,13 +283,17 @@ class Codec:
         return v.value
 
     def autotune_report(self):
-        """{family: {"choice": index, "ms": [per-candidate ms]}} of the families the "autotune" option has tuned so far"""
+        """{family: {"choice": index, "ms": [per-candidate ms]}} of the families the "autotune" option has tuned so far; under "autotune" = 2 + k
+        {family: {"forced": k, "launches": count}} of the families that have launched candidate k since the option was set"""
         buf = ctypes.create_string_buffer(4096)
         self._check(self.L.xHipAutotuneReport(self.ctx, buf, len(buf)), "xHipAutotuneReport")
         out = {}
         for line in buf.value.decode().splitlines():
             w = line.split()
-            out[w[0]] = {"choice": int(w[2]), "ms": [float(x) for x in w[4:]]}
+            if w[1] == "forced":
+                out.setdefault(w[0], {}).update({"forced": int(w[2]), "launches": int(w[4])})
+            else:
+                out.setdefault(w[0], {}).update({"choice": int(w[2]), "ms": [float(x) for x in w[4:]]})
         return out
 
     # -- host-pointer batch API (numpy in, numpy out) -------------------------

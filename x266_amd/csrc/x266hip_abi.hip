@@ -48,7 +48,7 @@ struct x266hip_ctx {
     int adaptive_per_wave = 1;                      // shrink the per-wave run on small batches
     int dct_wg_threads = 0;                         // workgroup size of the DCT32 / transform-set kernels; 0 = the measured best: one-wave workgroups (profiles/r01_wg_occupancy.txt), four-wave ones for the fused forward + inverse kernel (profiles/r05_fused_variants.txt)
     int tile_tiles_per_wave = 0;                    // mixed-class tile kernel: consecutive tiles per wave (0 = 2: the wave's table copy serves two tiles)
-    int autotune = 0;                               // 1: the first large batch of a kernel family times its box-dependent launch shapes on the caller's buffers and keeps the fastest (tune_family below)
+    int autotune = 0;                               // 1: the first large batch of a kernel family times its box-dependent launch shapes on the caller's buffers and keeps the fastest (tune_family below); 2 + k: every family launches candidate k, untimed (the tests' hook)
     int me_tile_rows = 0;                           // block rows per ME tile: 0 = by frame size (SATD search: 8, 4 or 2; SAD search: 2), else 2, 4, 8 (8: SATD search only; 1 is served by 2)
     // fixed launch shapes (options in rounds 1-3; their sweeps are frozen in profiles/r01_*.txt, r03_tiles_one_launch.txt)
     static constexpr int kDctLdsPerWave = 8192;     // 2 KiB used: at most 20 resident waves per CU
@@ -74,6 +74,9 @@ struct x266hip_ctx {
     static constexpr int kTuneMaxCands = 8;
     struct Tuned { int choice = -1; int n = 0; float ms[kTuneMaxCands] = {}; };
     Tuned tuned[kTuneFamilies];
+    // "autotune" = 2 + k: per family the candidate its forced launches took (-1 = none yet) and how many there were (xHipAutotuneReport)
+    struct Forced { int cand = -1; unsigned long long launches = 0; };
+    Forced forced[kTuneFamilies];
     hipEvent_t tune_ev[2] = {};
     static constexpr size_t kMeScratchMax = 8;
     static constexpr int kScratchKinds = 1;
@@ -188,8 +191,11 @@ int launch_op(x266hip_ctx *ctx, int op, const void *d_in, void *d_out, size_t n,
 // family whose batch is large enough to time (the caller says so by `big`) runs every candidate on the caller's own buffers and
 // stream -- one warm-up and three timed launches each, HIP events on that stream, so this one call is synchronous -- and the
 // context keeps the fastest; the default shape (candidate 0) stays unless another one beats it by more than 2 %.  Every candidate
-// writes the same bytes (tests/test_gpu_autotune.py compares option off / on per family; tests/test_gpu_waits.py every fused candidate against the
-// wait-for-everything build), so the extra launches only rewrite the outputs.
+// writes the same bytes, so the extra launches only rewrite the outputs.  The tuning call's last launch overwrites what the others wrote, so
+// comparing its outputs checks the kept shape alone (tests/test_gpu_autotune.py: option off / on per family); each candidate by itself is
+// checked through "autotune" = 2 + k, which launches candidate k of every family at any batch size, untimed: tests/test_gpu_launch_shapes.py
+// holds every entry of the four tables against the CPU oracle at the run lengths where the pipelines switch cases, inside guard bands, and
+// tests/test_gpu_waits.py every fused entry against the wait-for-everything build.
 // Not while the stream is being captured, and not for calls whose buffers overlap (the caller checks): those use the default.
 template <class Launch>
 int tune_family(x266hip_ctx *ctx, int family, int n_cands, bool big, hipStream_t stream, Launch &&launch)
@@ -233,6 +239,14 @@ const ShapeCand kReconCands[] = {{8, 256, 12288, 2}, {4, 256, 12288, 2}, {16, 25
 const ShapeCand kSatdCands[] = {{4, 256, 16384, 3}, {2, 256, 16384, 3}, {8, 256, 16384, 3}, {4, 128, 12288, 3}, {6, 256, 12288, 3}, {3, 256, 12288, 3}};
 // SAD batch: (-, waves per workgroup x 64, LDS per WORKGROUP)
 const ShapeCand kSadCands[] = {{0, 256, 32768, 0}, {0, 128, 16384, 0}, {0, 64, 8192, 0}, {0, 256, 24576, 0}, {0, 256, 40960, 0}};
+
+// "autotune" = 2 + k (the tests' hook): the candidate every family is to launch, -1 when the option does not force one
+int forced_cand(const x266hip_ctx *ctx) { return ctx->autotune >= 2 ? ctx->autotune - 2 : -1; }
+void count_forced(x266hip_ctx *ctx, int family, int cand)
+{
+    ctx->forced[family].cand = cand;
+    ++ctx->forced[family].launches;
+}
 
 static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
@@ -527,7 +541,7 @@ static const OptionDesc kOptions[] = {
     {"satd_lds_bytes_per_wave", &x266hip_ctx::satd_lds_per_wave, 0, 16384, 16},      // whole 16-byte rows; 16 KiB x the four waves of the largest workgroup = the 64 KiB a launch may ask for
     {"tile_tiles_per_wave", &x266hip_ctx::tile_tiles_per_wave, 0, 64, 1},
     {"me_tile_rows", &x266hip_ctx::me_tile_rows, 0, 8, 1},
-    {"autotune", &x266hip_ctx::autotune, 0, 1, 1},
+    {"autotune", &x266hip_ctx::autotune, 0, 2 + x266hip_ctx::kTuneMaxCands, 1},           // 2 + k forces candidate k; a k past a family's table (k = 8: past every table) is refused by that family's calls
 };
 
 static const OptionDesc *find_option(const char *key)
@@ -545,6 +559,8 @@ int xHipSetOption(x266hip_ctx *ctx, const char *key, int value)
     if (!o) return fail(ctx, X266HIP_EINVAL, "unknown option");
     if (value < o->lo || value > o->hi || value % o->multiple_of) return fail(ctx, X266HIP_EINVAL, "option value out of range");
     ctx->*(o->member) = value;
+    if (o->member == &x266hip_ctx::autotune)                                   // any value: what was tuned or forced so far is forgotten
+        for (int f = 0; f < x266hip_ctx::kTuneFamilies; ++f) { ctx->tuned[f] = x266hip_ctx::Tuned(); ctx->forced[f] = x266hip_ctx::Forced(); }
     return X266HIP_OK;
 }
 
@@ -564,13 +580,18 @@ int xHipAutotuneReport(const x266hip_ctx *ctx, char *buf, size_t cap)
     char line[160];
     for (int f = 0; f < x266hip_ctx::kTuneFamilies; ++f) {
         const x266hip_ctx::Tuned &t = ctx->tuned[f];
+        if (ctx->forced[f].cand >= 0) {
+            std::snprintf(line, sizeof line, "%s forced %d launches %llu\n", names[f], ctx->forced[f].cand, ctx->forced[f].launches);
+            out += line;
+        }
         if (t.choice < 0) continue;
         std::snprintf(line, sizeof line, "%s choice %d ms", names[f], t.choice);
         out += line;
         for (int c = 0; c < t.n; ++c) { std::snprintf(line, sizeof line, " %.4f", t.ms[c]); out += line; }
         out += "\n";
     }
-    std::snprintf(buf, cap, "%s", out.c_str());
+    if (out.size() >= cap) { buf[0] = '\0'; return X266HIP_EINVAL; }           // never a cut line
+    std::memcpy(buf, out.c_str(), out.size() + 1);
     return X266HIP_OK;
 }
 
@@ -630,15 +651,19 @@ int xDct32FwdInvBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_coef,
     hipError_t e;
     const bool knobs_untouched = !ctx->dct_fwdinv_blocks_per_wave && !ctx->dct_wg_threads;
     const bool disjoint = !ranges_overlap(d_in, n * 2048, d_recon, n * 2048) && !ranges_overlap(d_in, n * 2048, d_coef, n * 2048);
-    if (ctx->autotune && knobs_untouched && disjoint) {
+    const int forced = forced_cand(ctx);
+    if (ctx->autotune && n && knobs_untouched && disjoint) {
         const ShapeCand *cands = d_coef ? kFwdInvCands : kReconCands;
         const int n_cands = d_coef ? (int)(sizeof kFwdInvCands / sizeof kFwdInvCands[0]) : (int)(sizeof kReconCands / sizeof kReconCands[0]);
+        const int family = d_coef ? x266hip_ctx::kTuneFwdInv : x266hip_ctx::kTuneRecon;
+        if (forced >= n_cands) return fail(ctx, X266HIP_EINVAL, "xDct32FwdInvBatchDev: option \"autotune\" forces a launch shape this family does not have");
         auto run = [&](int c) {
             LaunchCfg k = cfg;
             k.units_per_wave = cands[c].units_per_wave; k.wg_threads = cands[c].wg_threads; k.lds_bytes_per_wave = cands[c].lds_bytes_per_wave; k.shape = cands[c].shape;
             return launch_dct32_fwdinv(d_in, d_coef, d_recon, n, ctx->d_fwd, ctx->d_inv_acc, k, (hipStream_t)stream);
         };
-        e = run(tune_family(ctx, d_coef ? x266hip_ctx::kTuneFwdInv : x266hip_ctx::kTuneRecon, n_cands, n >= ((size_t)1 << 18), (hipStream_t)stream, run));
+        e = run(forced >= 0 ? forced : tune_family(ctx, family, n_cands, n >= ((size_t)1 << 18), (hipStream_t)stream, run));
+        if (forced >= 0 && e == hipSuccess) count_forced(ctx, family, forced);
     } else {
         e = launch_dct32_fwdinv(d_in, d_coef, d_recon, n, ctx->d_fwd, ctx->d_inv_acc, cfg, (hipStream_t)stream);
     }
@@ -653,14 +678,18 @@ int xSatd8x8BatchDev(x266hip_ctx *ctx, const int16_t *d_diff, uint32_t *d_out, s
         return fail(ctx, X266HIP_EINVAL, "xSatd8x8BatchDev: NULL or unaligned buffer");
     X_DEV(ctx);
     const bool knobs_untouched = !ctx->satd_variant && !ctx->satd_groups_per_wave && !ctx->satd_wg_threads && !ctx->satd_lds_per_wave;
-    if (ctx->autotune && knobs_untouched && n >= kSatdDmaMinBlocks && !ranges_overlap(d_diff, n * 128, d_out, n * 4)) {
+    const int forced = forced_cand(ctx);                                      // forcing: at any size (the LDS-DMA kernel runs from one block on, as under "satd_variant" 3)
+    if (ctx->autotune && knobs_untouched && (forced >= 0 ? n > 0 : n >= kSatdDmaMinBlocks) && !ranges_overlap(d_diff, n * 128, d_out, n * 4)) {
+        const int n_cands = (int)(sizeof kSatdCands / sizeof kSatdCands[0]);
+        if (forced >= n_cands) return fail(ctx, X266HIP_EINVAL, "xSatd8x8BatchDev: option \"autotune\" forces a launch shape this family does not have");
         auto run = [&](int c) {
             LaunchCfg k = cfg_for(ctx, 2);
             k.units_per_wave = kSatdCands[c].units_per_wave; k.wg_threads = kSatdCands[c].wg_threads; k.lds_bytes_per_wave = kSatdCands[c].lds_bytes_per_wave; k.shape = kSatdCands[c].shape;
             return launch_satd8x8(d_diff, d_out, n, k, (hipStream_t)stream);
         };
-        const hipError_t e = run(tune_family(ctx, x266hip_ctx::kTuneSatd, (int)(sizeof kSatdCands / sizeof kSatdCands[0]), n >= ((size_t)1 << 23), (hipStream_t)stream, run));
+        const hipError_t e = run(forced >= 0 ? forced : tune_family(ctx, x266hip_ctx::kTuneSatd, n_cands, n >= ((size_t)1 << 23), (hipStream_t)stream, run));
         if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "kernel launch", e);
+        if (forced >= 0) count_forced(ctx, x266hip_ctx::kTuneSatd, forced);
         return X266HIP_OK;
     }
     return launch_op(ctx, 2, d_diff, d_out, n, (hipStream_t)stream);
@@ -1224,10 +1253,14 @@ int xSadBatchDev(x266hip_ctx *ctx, int edge, const uint8_t *d_a, const uint8_t *
     X_DEV(ctx);
     hipError_t e;
     const size_t in_bytes = n * (size_t)(edge * edge);
-    if (ctx->autotune && edge >= 8 && !ranges_overlap(d_a, in_bytes, d_out, n * 4) && !ranges_overlap(d_b, in_bytes, d_out, n * 4)) {
+    const int forced = forced_cand(ctx);
+    if (ctx->autotune && n && edge >= 8 && !ranges_overlap(d_a, in_bytes, d_out, n * 4) && !ranges_overlap(d_b, in_bytes, d_out, n * 4)) {
+        const int n_cands = (int)(sizeof kSadCands / sizeof kSadCands[0]);
+        if (forced >= n_cands) return fail(ctx, X266HIP_EINVAL, "xSadBatchDev: option \"autotune\" forces a launch shape this family does not have");
         auto run = [&](int c) { return launch_sad(edge, d_a, d_b, d_out, n, kSadCands[c].wg_threads / 64, kSadCands[c].lds_bytes_per_wave, (hipStream_t)stream); };
         const int family = edge == 8 ? x266hip_ctx::kTuneSad8 : edge == 16 ? x266hip_ctx::kTuneSad16 : edge == 32 ? x266hip_ctx::kTuneSad32 : x266hip_ctx::kTuneSad64;
-        e = run(tune_family(ctx, family, (int)(sizeof kSadCands / sizeof kSadCands[0]), in_bytes >= ((size_t)128 << 20), (hipStream_t)stream, run));
+        e = run(forced >= 0 ? forced : tune_family(ctx, family, n_cands, in_bytes >= ((size_t)128 << 20), (hipStream_t)stream, run));
+        if (forced >= 0 && e == hipSuccess) count_forced(ctx, family, forced);
     } else {
         e = launch_sad(edge, d_a, d_b, d_out, n, 0, 0, (hipStream_t)stream);
     }
