@@ -48,6 +48,8 @@ extern "C" {
 /* return codes (x266.cpp style: 0 ok, negative failure)                     */
 /* ------------------------------------------------------------------------ */
 #define X266HIP_OK        0
+/* X266HIP_EINVAL from a device call: nothing was launched, and xHipLastError says "<entry point>: <the rule broken>"; the rules
+ * of every device call (NULL, alignment, spans, overlap, sizes, scalar ranges) are those of x266_amd/csrc/x266_args.hpp. */
 #define X266HIP_EINVAL   (-1)   /* bad argument (NULL pointer with n > 0, ...)  */
 #define X266HIP_EDEVICE  (-2)   /* no gfx950 device / HIP runtime error         */
 #define X266HIP_ENOMEM   (-3)   /* device or host allocation failed             */

@@ -9,7 +9,7 @@ gaps, m_I, the plane a call does not write) must still hold the fill, and each c
 The same case at natural alignment (displacement 0) makes a failure attributable to placement.  The rejection table displaces
 one argument at a time by half its alignment: X266HIP_EINVAL, an error text, not one byte written.
 
-ROWS is the table: per entry point the pointer arguments with the alignment x266hip_abi.hip enforces (1 = none), the variants
+ROWS is the table: per entry point the pointer arguments with the alignment x266_amd/csrc/x266_args.hpp enforces (1 = none), the variants
 (shapes at which a tail or a per-wave run can go wrong, launch forms forced through the options), and how to build inputs,
 output extents and the reference.  Two tests here need no GPU: the table covers the header's `...Dev` declarations exactly, and
 every variant builds; tests/test_docs_follow_code.py checks that the header states the table's alignments."""

@@ -1,0 +1,376 @@
+// x266_args.hpp -- the argument rules of the device entry points of include/x266hip.h, host-only: plain C++17, no HIP, no context.
+//
+// Every `...Dev` / `...Gpu` call has one rule function here (calls with the same rules share one).  It takes the call's arguments
+// and returns the reason the call is refused, or nullptr when it is accepted; it reads nothing through the pointers and touches
+// no state, so tests/cpp/arg_rules_check.cpp holds the rules without a device.  x266hip_abi.hip turns a reason into
+// X266HIP_EINVAL and the text "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here.
+//
+// A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
+// space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
+// older calls check NULL and alignment only.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/x266hip.h"
+
+namespace x266 {
+namespace args {
+
+constexpr const char *kNull = "a required pointer is NULL";
+constexpr const char *kMisaligned = "a pointer is misaligned";
+constexpr const char *kNoFit = "a buffer does not fit in the address space";
+constexpr const char *kOverlap = "an output overlaps another buffer";
+constexpr const char *kQuantScalars = "qp must be 0..51 (without d_qp) and rounding 0..511";
+constexpr const char *kChroma = "pitch < 1 or overlapping U / V outputs";
+
+struct Buf {
+    const char *name;
+    const void *p;
+    unsigned align;
+    size_t bytes;                   // 0: no extent in this call's rules
+    bool output, optional, fitted;  // fitted: the span's end is checked against the address space
+    const char *same_as;            // an output may BE this input (the very same address), and must not overlap it otherwise
+};
+constexpr Buf in(const char *name, const void *p, unsigned align, size_t bytes = 0) { return {name, p, align, bytes, false, false, true, nullptr}; }
+constexpr Buf out(const char *name, const void *p, unsigned align, size_t bytes = 0, const char *same_as = nullptr) { return {name, p, align, bytes, true, false, true, same_as}; }
+constexpr Buf opt(Buf b) { b.optional = true; return b; }
+constexpr Buf unfitted(Buf b) { b.fitted = false; return b; }    // overlap is tested, the span's end is not: the calls from before the quantiser
+
+inline const char *check(const Buf *b, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (!b[i].p && !b[i].optional) return kNull;
+    for (size_t i = 0; i < n; ++i)
+        if ((uintptr_t)b[i].p & (b[i].align - 1u)) return kMisaligned;
+    for (size_t i = 0; i < n; ++i) {
+        uintptr_t end = 0;
+        if (b[i].p && b[i].fitted && __builtin_add_overflow((uintptr_t)b[i].p, b[i].bytes, &end)) return kNoFit;
+    }
+    for (size_t o = 0; o < n; ++o) {
+        if (!b[o].output || !b[o].p || !b[o].bytes) continue;
+        for (size_t i = 0; i < n; ++i) {
+            if (i == o || !b[i].p || !b[i].bytes) continue;
+            if (b[o].p == b[i].p && b[o].same_as && !std::strcmp(b[o].same_as, b[i].name)) continue;
+            const uintptr_t x = (uintptr_t)b[o].p, y = (uintptr_t)b[i].p;
+            if (x < y + b[i].bytes && y < x + b[o].bytes) return kOverlap;
+        }
+    }
+    return nullptr;
+}
+template <size_t N> const char *check(const Buf (&b)[N]) { return check(b, N); }
+
+// ---- extents: the checked arithmetic.  A product that wraps size_t saturates, and a saturated span fits behind no pointer.
+inline size_t mul(size_t a, size_t b)
+{
+    size_t r = 0;
+    return __builtin_mul_overflow(a, b, &r) ? SIZE_MAX : r;
+}
+// first byte of block 0 to the last byte of block n - 1 of a stream with a pitch of `pitch` blocks
+inline size_t stream_bytes(size_t n_blocks, size_t pitch, size_t block_bytes)
+{
+    if (n_blocks == 0) return 0;
+    const size_t t = mul(n_blocks - 1, pitch);
+    return mul(t == SIZE_MAX ? t : t + 1, block_bytes);
+}
+inline size_t tile_bytes(int w, int h) { return (size_t)w * (size_t)h * 2; }                  // 512 bytes per 256 pixels
+inline size_t blocks8(int w, int h) { return (size_t)(w / 8) * (size_t)(h / 8); }
+inline size_t ctus(int w, int h) { return (((size_t)w + 63) / 64) * (((size_t)h + 63) / 64); }
+
+// ---- frame sizes and scalar ranges
+inline const char *frame(int w, int h, int granule)
+{
+    if (w > 0 && h > 0 && w % granule == 0 && h % granule == 0) return nullptr;
+    return granule == 8 ? "width/height must be positive multiples of 8" : granule == 16 ? "width/height must be positive multiples of 16"
+         : granule == 32 ? "width/height must be positive multiples of 32" : "width/height must be positive multiples of 64";
+}
+inline bool qp_ok(const void *d_qp, int qp) { return d_qp || (qp >= 0 && qp <= 51); }
+inline bool rounding_ok(int rounding) { return rounding >= 0 && rounding <= 511; }
+inline bool range_ok(int range) { return range >= 1 && range <= 64; }
+inline bool offset_ok(int offset_div2) { return offset_div2 >= -6 && offset_div2 <= 6; }
+inline bool lambda_ok(int lambda_q4) { return lambda_q4 >= 0 && lambda_q4 <= 65535; }
+inline bool edge_8_or_32(int block_edge) { return block_edge == 8 || block_edge == 32; }
+
+// the two output streams of a chroma call must not overlap: plane V starts at or after U's first block ends (interleaved
+// form) or anywhere else outside [U, U + span)
+inline bool chroma_outputs_ok(const void *u, const void *v, size_t block_bytes, size_t n_blocks, size_t pitch)
+{
+    if (!u || !v || pitch < 1 || n_blocks == 0) return u && v && pitch >= 1;
+    const uintptr_t a = (uintptr_t)u, b = (uintptr_t)v;
+    const uintptr_t lo = a < b ? a : b, hi = a < b ? b : a;
+    const size_t gap = (size_t)(hi - lo);
+    if (gap >= ((n_blocks - 1) * pitch + 1) * block_bytes) return true;     // disjoint spans
+    // interleaved: the other plane's blocks sit in the holes of this one's pitch
+    return pitch >= 2 && gap % block_bytes == 0 && gap / block_bytes >= 1 && gap / block_bytes <= pitch - 1;
+}
+
+// ---- the batch calls: NULL and alignment only, and n == 0 is accepted whatever the pointers are ------------------------------------
+// xDct32FwdBatchDev, xDct32InvBatchDev, either half of xDct32SatdFrameDev, xSatd8x8BatchDev (out_align 4)
+inline const char *batch(const void *d_in, const void *d_out, unsigned out_align, size_t n)
+{
+    const Buf b[] = {in("d_in", d_in, 16), out("d_out", d_out, out_align)};
+    return n ? check(b) : nullptr;
+}
+inline const char *dct32_satd_frame(const void *d_dct_in, const void *d_dct_out, size_t n_dct, const void *d_diff, const void *d_satd_out, size_t n_satd)
+{
+    const char *why = batch(d_dct_in, d_dct_out, 16, n_dct);
+    return why ? why : batch(d_diff, d_satd_out, 16, n_satd);
+}
+inline const char *dct32_pass(const void *d_in, const void *d_out, size_t n, int shift)
+{
+    return shift < 1 || shift > 15 ? "shift must be 1..15" : batch(d_in, d_out, 16, n);
+}
+inline const char *dct32_fwd_inv_batch(const void *d_in, const void *d_coef, const void *d_recon, size_t n)
+{
+    const Buf b[] = {in("d_in", d_in, 16), opt(out("d_coef", d_coef, 16)), out("d_recon", d_recon, 16)};
+    return n ? check(b) : nullptr;
+}
+inline const char *mem_ceiling(int kind, const void *d_src, const void *d_dst, size_t bytes)
+{
+    if (kind < X266_MEM_COPY || kind > X266_MEM_READ_PROBE) return "kind must be X266_MEM_COPY, _READ, _WRITE or _READ_PROBE";
+    if (bytes & 15u) return "bytes must be a multiple of 16";
+    const Buf b[] = {out("d_dst", d_dst, 16), in("d_src", d_src, 16)};       // X266_MEM_WRITE reads nothing: d_src is not looked at
+    return bytes ? check(b, kind == X266_MEM_WRITE ? 1 : 2) : nullptr;
+}
+inline const char *intra32_predict(const void *d_refs, const void *d_modes, const void *d_ref_index, const void *d_pred, size_t n)
+{
+    const Buf b[] = {in("d_refs", d_refs, 16), in("d_modes", d_modes, 1), opt(in("d_ref_index", d_ref_index, 4)), out("d_pred", d_pred, 16)};
+    return n ? check(b) : nullptr;
+}
+inline const char *intra32_residual_dct32(const void *d_refs, const void *d_modes, const void *d_ref_index, const void *d_src, const void *d_coef, size_t n)
+{
+    const Buf b[] = {in("d_refs", d_refs, 16), in("d_modes", d_modes, 1), opt(in("d_ref_index", d_ref_index, 4)), in("d_src", d_src, 16), out("d_coef", d_coef, 16)};
+    return n ? check(b) : nullptr;
+}
+inline const char *intra32_costs(const void *d_refs, const void *d_src, const void *d_costs, const void *d_best_mode, size_t n)
+{
+    const Buf b[] = {in("d_refs", d_refs, 16), in("d_src", d_src, 16), out("d_costs", d_costs, 4), opt(out("d_best_mode", d_best_mode, 1))};
+    return n ? check(b) : nullptr;
+}
+inline const char *fill_residual(const void *d_dst, size_t n_samples)
+{
+    const Buf b[] = {out("d_dst", d_dst, 16)};
+    return n_samples ? check(b) : nullptr;
+}
+constexpr int kTransformTypes = 4;                  // DCT-II, DST-VII, and the two mixed horizontal / vertical pairs
+// xTransformFwdBatchDev, xTransformInvBatchDev
+inline const char *transform_batch(int type, int size, const void *d_in, const void *d_out, size_t n, const void *d_offsets)
+{
+    if (type < 0 || type >= kTransformTypes) return "unknown transform type";
+    if (size != 4 && size != 8 && size != 16 && !(size == 32 && type == X266_TR_DCT2)) return "size must be 4, 8, 16 (or 32 for DCT-II)";
+    const Buf b[] = {in("d_in", d_in, 16), out("d_out", d_out, 16), opt(in("d_offsets", d_offsets, 4))};
+    return n ? check(b) : nullptr;
+}
+inline const char *transform_tiles(const void *d_in, const void *d_out, size_t n_tiles, const void *d_tile_offsets, const void *d_tile_class)
+{
+    const Buf b[] = {in("d_in", d_in, 16), out("d_out", d_out, 16), opt(in("d_tile_offsets", d_tile_offsets, 4)), in("d_tile_class", d_tile_class, 1)};
+    return n_tiles ? check(b) : nullptr;
+}
+inline const char *sad_batch(int edge, const void *d_a, const void *d_b, const void *d_out, size_t n)
+{
+    if (edge != 4 && edge != 8 && edge != 16 && edge != 32 && edge != 64) return "edge must be 4, 8, 16, 32 or 64";
+    const Buf b[] = {in("d_a", d_a, 16), in("d_b", d_b, 16), out("d_out", d_out, 4)};
+    return n ? check(b) : nullptr;
+}
+
+// ---- planar frames <-> tiles, and the calls from tiles: NULL and alignment only ----------------------------------------------------
+// xConvInputFmtDev (to_tiles: the planes are the inputs, strdC is not an argument) and xConvOutput420Dev
+inline const char *tile_convert(bool to_tiles, const void *d_tiles, const void *d_y, const void *d_u, const void *d_v, intptr_t strdY, intptr_t strdC, int w, int h)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (strdY < w || (strdY & 15) || (!to_tiles && (strdC < w / 2 || (strdC & 7)))) return "a stride is too small or misaligned";
+    Buf b[] = {in("d_tiles", d_tiles, 16), in("d_y", d_y, 16), in("d_u", d_u, 8), in("d_v", d_v, 8)};
+    for (Buf &x : b) x.output = to_tiles == (&x == b);
+    return check(b);
+}
+inline const char *residual_luma(const void *d_cur, const void *d_pred, int w, int h, int block_edge, const void *d_residual)
+{
+    if (!edge_8_or_32(block_edge)) return "block_edge must be 8 or 32";
+    if (const char *why = frame(w, h, block_edge == 32 ? 32 : 16)) return why;
+    const Buf b[] = {in("d_cur", d_cur, 16), in("d_pred", d_pred, 16), out("d_residual", d_residual, 16)};
+    return check(b);
+}
+// xDct32FwdFromTilesDev (granule 32), xSatd8x8FromTilesDev (16, out_align 4), xDct32FwdCtuFromTilesDev (64)
+inline const char *from_tiles(const void *d_cur, const void *d_pred, int w, int h, int granule, const void *d_out, unsigned out_align)
+{
+    if (const char *why = frame(w, h, granule)) return why;
+    const Buf b[] = {in("d_cur", d_cur, 16), in("d_pred", d_pred, 16), out("d_out", d_out, out_align)};
+    return check(b);
+}
+// xResidualChromaDev (block_edge 8 or 32), xDct32FwdChromaFromTilesDev (32, 16-byte outputs), xSatd8x8ChromaFromTilesDev (block_edge 8: one
+// 4-byte sum per 8x8 chroma block); the luma frame of a 32x32 chroma block is a 64x64 CTU's
+inline const char *chroma_from_tiles(const void *d_cur, const void *d_pred, int w, int h, int block_edge, const void *d_u, const void *d_v, unsigned out_align,
+                                     size_t block_bytes, size_t pitch)
+{
+    if (!edge_8_or_32(block_edge)) return "block_edge must be 8 or 32";
+    if (const char *why = frame(w, h, block_edge == 32 ? 64 : 16)) return why;
+    const Buf b[] = {in("d_cur", d_cur, 16), in("d_pred", d_pred, 16), out("d_u", d_u, out_align), out("d_v", d_v, out_align)};
+    if (const char *why = check(b)) return why;
+    return chroma_outputs_ok(d_u, d_v, block_bytes, (size_t)(w / 2 / block_edge) * (size_t)(h / 2 / block_edge), pitch) ? nullptr : kChroma;
+}
+
+// ---- reconstruction into tiles: the output may BE the prediction, and must not overlap an input otherwise --------------------------
+inline const char *recon_luma(const void *d_pred, const void *d_residual, int w, int h, int block_edge, const void *d_recon)
+{
+    if (!edge_8_or_32(block_edge)) return "block_edge must be 8 or 32";
+    if (const char *why = frame(w, h, block_edge == 32 ? 32 : 16)) return why;
+    const Buf b[] = {unfitted(in("d_pred", d_pred, 16, tile_bytes(w, h))), unfitted(in("d_residual", d_residual, 16, tile_bytes(w, h))),
+                     unfitted(out("d_recon", d_recon, 16, tile_bytes(w, h), "d_pred"))};
+    return check(b);
+}
+inline const char *recon_chroma(const void *d_pred, const void *d_res_u, const void *d_res_v, size_t pitch, int w, int h, int block_edge, const void *d_recon)
+{
+    if (!edge_8_or_32(block_edge)) return "block_edge must be 8 or 32";
+    if (const char *why = frame(w, h, block_edge == 32 ? 64 : 16)) return why;
+    if (pitch < 1) return "block_pitch < 1";
+    const size_t span = stream_bytes((size_t)(w / 2 / block_edge) * (size_t)(h / 2 / block_edge), pitch, (size_t)block_edge * block_edge * 2);
+    const Buf b[] = {unfitted(in("d_pred", d_pred, 16, tile_bytes(w, h))), in("d_res_u", d_res_u, 16, span), in("d_res_v", d_res_v, 16, span),
+                     unfitted(out("d_recon", d_recon, 16, tile_bytes(w, h), "d_pred"))};
+    return check(b);
+}
+// xDct32InvToTilesDev (granule 32: as many bytes of coefficients as of tiles), xDct32InvCtuToTilesDev (64: 12 KiB per CTU)
+inline const char *inv_to_tiles(const void *d_coef, const void *d_pred, int w, int h, int granule, const void *d_recon)
+{
+    if (const char *why = frame(w, h, granule)) return why;
+    const Buf b[] = {unfitted(in("d_coef", d_coef, 16, granule == 64 ? ctus(w, h) * 12288 : tile_bytes(w, h))), unfitted(in("d_pred", d_pred, 16, tile_bytes(w, h))),
+                     unfitted(out("d_recon", d_recon, 16, tile_bytes(w, h), "d_pred"))};
+    return check(b);
+}
+
+// ---- the mixed transform set per CTU, the quantiser, the fused CTU coding call -----------------------------------------------------
+inline const char *transform_ctu_from_tiles(const void *d_cur, const void *d_pred, int w, int h, const void *d_class, const void *d_coef)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    const Buf b[] = {in("d_cur", d_cur, 16, tile_bytes(w, h)), in("d_pred", d_pred, 16, tile_bytes(w, h)), in("d_class", d_class, 1, ctus(w, h) * 6),
+                     out("d_coef", d_coef, 16, ctus(w, h) * 12288)};
+    return check(b);
+}
+inline const char *transform_ctu_to_tiles(const void *d_coef, const void *d_class, const void *d_pred, int w, int h, const void *d_recon)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    const Buf b[] = {in("d_coef", d_coef, 16, ctus(w, h) * 12288), in("d_class", d_class, 1, ctus(w, h) * 6), in("d_pred", d_pred, 16, tile_bytes(w, h)),
+                     out("d_recon", d_recon, 16, tile_bytes(w, h), "d_pred")};
+    return check(b);
+}
+// scalar errors first; the entry point then accepts n_regions == 0 whatever the pointers are
+inline const char *quant_regions(int inverse, const void *d_in, const void *d_out, size_t n_regions, const void *d_class, const void *d_qp, int qp, int rounding,
+                                 const void *d_nnz)
+{
+    if (!qp_ok(d_qp, qp) || !rounding_ok(rounding)) return kQuantScalars;
+    if (inverse && d_nnz) return "d_nnz must be NULL with inverse = 1";
+    const Buf b[] = {in("d_in", d_in, 16, mul(n_regions, 2048)), out("d_out", d_out, 16, mul(n_regions, 2048), "d_in"), opt(in("d_class", d_class, 1, n_regions)),
+                     opt(in("d_qp", d_qp, 1, n_regions)), opt(out("d_nnz", d_nnz, 4, mul(n_regions, 4)))};
+    return n_regions ? check(b) : nullptr;
+}
+inline const char *dct32_code_ctu_tiles(const void *d_cur, const void *d_pred, int w, int h, const void *d_qp, int qp, int rounding, const void *d_level,
+                                        const void *d_nnz, const void *d_recon)
+{
+    if (const char *why = frame(w, h, 64)) return why;
+    if (!qp_ok(d_qp, qp) || !rounding_ok(rounding)) return kQuantScalars;
+    const Buf b[] = {in("d_pred", d_pred, 16, tile_bytes(w, h)), opt(in("d_qp", d_qp, 1, ctus(w, h) * 6)), out("d_level", d_level, 16, ctus(w, h) * 12288),
+                     opt(out("d_nnz", d_nnz, 4, ctus(w, h) * 24)), out("d_recon", d_recon, 16, tile_bytes(w, h), "d_pred"), in("d_cur", d_cur, 16, tile_bytes(w, h))};
+    return check(b, d_cur == d_pred ? 5 : 6);                              // one frame given as both inputs is one buffer
+}
+
+// ---- motion search and compensation ------------------------------------------------------------------------------------------------
+// xSatd8x8SearchDev and xSad8x8SearchDev (sad: the current frame is read four bytes at a time) on planar frames: NULL and alignment only
+inline const char *plane_search(bool sad, const void *d_cur, intptr_t cur_stride, const void *d_ref, intptr_t ref_stride, int w, int h, int range,
+                                const void *d_best, const void *d_costs)
+{
+    if (const char *why = frame(w, h, 8)) return why;
+    if (!range_ok(range)) return "range must be 1..64";
+    if (cur_stride < w || ref_stride < (intptr_t)w + 2 * range) return "stride too small";
+    if (sad && (cur_stride & 3)) return "the current frame's stride must be a multiple of 4";
+    const Buf b[] = {in("d_cur", d_cur, sad ? 4 : 1), in("d_ref", d_ref, 1), out("d_best", d_best, 8), opt(out("d_costs", d_costs, 4))};
+    return check(b);
+}
+// xSatd8x8SearchFromTilesDev, xSad8x8SearchFromTilesDev.  The inputs are read-only, so d_cur == d_ref is fine.  Each output is held against
+// the two frames, not against the other output, and only the cost map's end against the address space: two lists.
+inline const char *tile_search(const void *d_cur, const void *d_ref, int w, int h, int range, const void *d_best, const void *d_costs)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (!range_ok(range)) return "range must be 1..64";
+    const size_t span = (size_t)(2 * range + 1);
+    const Buf best[] = {unfitted(in("d_cur", d_cur, 16, tile_bytes(w, h))), unfitted(in("d_ref", d_ref, 16, tile_bytes(w, h))),
+                        unfitted(out("d_best", d_best, 8, blocks8(w, h) * 8))};
+    const Buf costs[] = {best[0], best[1], opt(out("d_costs", d_costs, 4, mul(blocks8(w, h), span * span * 4)))};
+    const char *why = check(best);
+    return why ? why : check(costs);
+}
+// xMotionComp{,Luma,Chroma}Dev, and xMotionCompQpel{,Luma,Chroma}Gpu (fitted: a span must not run past the end of the address space)
+inline const char *motion_comp(bool fitted, const void *d_ref, const void *d_mv, int w, int h, const void *d_pred)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    Buf b[] = {in("d_ref", d_ref, 16, tile_bytes(w, h)), in("d_mv", d_mv, 8, blocks8(w, h) * 8), out("d_pred", d_pred, 16, tile_bytes(w, h))};
+    for (Buf &x : b) x.fitted = fitted;
+    return check(b);
+}
+inline const char *refine_qpel(const void *d_cur, const void *d_ref, int w, int h, const void *d_int, const void *d_best, const void *d_costs)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    const Buf b[] = {in("d_cur", d_cur, 16, tile_bytes(w, h)), in("d_ref", d_ref, 16, tile_bytes(w, h)), in("d_int", d_int, 8, blocks8(w, h) * 8),
+                     out("d_best", d_best, 8, blocks8(w, h) * 8, "d_int"), opt(out("d_costs", d_costs, 4, blocks8(w, h) * 49 * 4))};   // n_blocks < 2^56: no product wraps
+    return check(b);
+}
+
+// ---- the in-loop filters -----------------------------------------------------------------------------------------------------------
+// xDeblockLumaGpu, xDeblockChromaGpu, xDeblockGpu
+inline const char *deblock(const void *d_in, int w, int h, const x266_deblock_t *p, const void *d_out)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(w, h, 16)) return why;
+    if (!qp_ok(p->d_qp, p->qp) || !offset_ok(p->beta_offset_div2) || !offset_ok(p->tc_offset_div2)) return "qp must be 0..51 (without d_qp) and the offsets -6..6";
+    const size_t tab = ctus(w, h) * 6;
+    const Buf b[] = {in("d_in", d_in, 16, tile_bytes(w, h)), out("d_out", d_out, 16, tile_bytes(w, h), "d_in"), opt(in("d_mv", p->d_mv, 8, blocks8(w, h) * 8)),
+                     opt(in("d_nnz", p->d_nnz, 4, ctus(w, h) * 24)), opt(in("d_class", p->d_class, 1, tab)), opt(in("d_intra", p->d_intra, 1, tab)),
+                     opt(in("d_qp", p->d_qp, 1, tab))};
+    return check(b);
+}
+// xSaoStatsGpu (d_param NULL, lambda_q4 0) and xSaoSearchGpu (decide: d_param is the required output, d_stats the optional one)
+inline const char *sao_stats(bool decide, const void *d_org, const void *d_dec, int w, int h, int lambda_q4, const void *d_param, const void *d_stats)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (!lambda_ok(lambda_q4)) return "lambda_q4 must be 0..65535";
+    Buf b[] = {out("d_param", d_param, 8, ctus(w, h) * 24), out("d_stats", d_stats, 4, ctus(w, h) * 1152), in("d_org", d_org, 16, tile_bytes(w, h)),
+               in("d_dec", d_dec, 16, tile_bytes(w, h))};
+    b[decide ? 1 : 0].optional = true;
+    return check(b);
+}
+// the entry point then accepts n_ctu == 0 without a launch
+inline const char *sao_decide(const void *d_stats, size_t n_ctu, int lambda_q4, const void *d_param)
+{
+    if (!lambda_ok(lambda_q4)) return "lambda_q4 must be 0..65535";
+    if (n_ctu > 0x7FFFFFFFull) return "n_ctu must be below 2^31";
+    const Buf b[] = {out("d_param", d_param, 8, n_ctu * 24), in("d_stats", d_stats, 4, n_ctu * 1152)};
+    return check(b);
+}
+inline const char *sao_apply(const void *d_in, int w, int h, const void *d_param, const void *d_out)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    const Buf b[] = {out("d_out", d_out, 16, tile_bytes(w, h)), in("d_in", d_in, 16, tile_bytes(w, h)), in("d_param", d_param, 8, ctus(w, h) * 24)};
+    return check(b);                                                        // in place is not possible
+}
+
+// ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------
+inline const char *intra32_refs_from_tiles(const void *d_frame, int w, int h, int component, const void *d_refs)
+{
+    if (const char *why = frame(w, h, 64)) return why;
+    if (component < 0 || component > 2) return "component must be 0, 1 or 2";
+    const Buf b[] = {out("d_refs", d_refs, 16, ctus(w, h) * (component == 0 ? 4u : 1u) * sizeof(x266_intra_ref_t)), in("d_frame", d_frame, 16, tile_bytes(w, h))};
+    return check(b);
+}
+inline const char *intra32_code_frame(const void *d_cur, int w, int h, const void *d_qp, int qp, int rounding, const void *d_mode_in, const void *d_level,
+                                      const void *d_nnz, const void *d_mode, const void *d_recon)
+{
+    if (const char *why = frame(w, h, 64)) return why;
+    if (!qp_ok(d_qp, qp) || !rounding_ok(rounding)) return kQuantScalars;
+    const Buf b[] = {out("d_recon", d_recon, 16, tile_bytes(w, h)), out("d_level", d_level, 16, ctus(w, h) * 12288), out("d_mode", d_mode, 1, ctus(w, h) * 6, "d_mode_in"),
+                     opt(out("d_nnz", d_nnz, 4, ctus(w, h) * 24)), in("d_cur", d_cur, 16, tile_bytes(w, h)), opt(in("d_qp", d_qp, 1, ctus(w, h) * 6)),
+                     opt(in("d_mode_in", d_mode_in, 1, ctus(w, h) * 6))};
+    return check(b);
+}
+
+}  // namespace args
+}  // namespace x266

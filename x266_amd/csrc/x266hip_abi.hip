@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/x266hip.h"
+#include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_tables.hpp"
 
@@ -112,6 +113,23 @@ int fail(x266hip_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess
         }
     }
     return code;
+}
+
+// a refused call: X266HIP_EINVAL and the text "<entry point>: <reason>" (the reasons: x266_args.hpp); nothing is launched
+int refuse(x266hip_ctx *ctx, const char *entry, const char *why)
+{
+    ctx->err = entry;
+    ctx->err += ": ";
+    ctx->err += why;
+    return X266HIP_EINVAL;
+}
+
+// the tail of every entry point: the launch's status as the return code
+int launched(x266hip_ctx *ctx, const char *what, hipError_t e) { return e == hipSuccess ? X266HIP_OK : fail(ctx, X266HIP_EDEVICE, what, e); }
+
+int tables_invalid(x266hip_ctx *ctx, const char *entry)
+{
+    return fail(ctx, X266HIP_EDEVICE, (std::string(entry) + ": the transform tables of this context are invalid (a failed xTransformSetMatrix)").c_str());
 }
 
 #define X_HIP(ctx, call)                                                     \
@@ -230,7 +248,10 @@ int tune_family(x266hip_ctx *ctx, int family, int n_cands, bool big, hipStream_t
     return best;
 }
 
-struct ShapeCand { int units_per_wave, wg_threads, lds_bytes_per_wave, shape; };
+struct ShapeCand {
+    int units_per_wave, wg_threads, lds_bytes_per_wave, shape;
+    LaunchCfg over(LaunchCfg c) const { c.units_per_wave = units_per_wave; c.wg_threads = wg_threads; c.lds_bytes_per_wave = lds_bytes_per_wave; c.shape = shape; return c; }
+};
 // fused forward + inverse with both outputs: the default first, then the deep long-lived shapes of profiles/r05_fused_variants.txt
 const ShapeCand kFwdInvCands[] = {{2, 256, 12288, 2}, {16, 256, 16384, 3}, {24, 256, 16384, 3}, {16, 128, 20480, 3}, {12, 256, 16384, 3}, {4, 128, 12288, 2},
                                   {16, 256, 16384, 4}, {4, 64, 16384, 3}};
@@ -248,17 +269,22 @@ void count_forced(x266hip_ctx *ctx, int family, int cand)
     ++ctx->forced[family].launches;
 }
 
+// One launch of a family under "autotune": the forced candidate (refused when it is past the family's table), else the tuned one.
+template <class Launch>
+int run_family(x266hip_ctx *ctx, const char *entry, int family, int n_cands, bool big, hipStream_t stream, Launch &&run, hipError_t *e)
+{
+    const int forced = forced_cand(ctx);
+    if (forced >= n_cands) return refuse(ctx, entry, "option \"autotune\" forces a launch shape this family does not have");
+    *e = run(forced >= 0 ? forced : tune_family(ctx, family, n_cands, big, stream, run));
+    if (forced >= 0 && *e == hipSuccess) count_forced(ctx, family, forced);
+    return X266HIP_OK;
+}
+
+// the autotune paths only: calls whose buffers overlap take the default shape (the entry points' own rules: x266_args.hpp)
 static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return a && b && x < y + nb && y < x + na;
-}
-
-bool bad_ptrs(const void *a, const void *b, size_t n)
-{
-    if (n == 0) return false;
-    if (!a || !b) return true;
-    return (((uintptr_t)a | (uintptr_t)b) & 15u) != 0;
 }
 
 // Scratch of kind `kind` for `stream`, at least `need` bytes.  Allocation happens here, i.e. on the first call of a stream or
@@ -595,11 +621,13 @@ int xHipAutotuneReport(const x266hip_ctx *ctx, char *buf, size_t cap)
     return X266HIP_OK;
 }
 
-// ---- device-pointer batch API ------------------------------------------------
+// ---- device-pointer API --------------------------------------------------------
+// Every entry point: NULL context, the call's rule function (x266_args.hpp: a refused call launches nothing), context state,
+// the device, the launch, `launched`.
 int xDct32FwdBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (bad_ptrs(d_in, d_out, n)) return fail(ctx, X266HIP_EINVAL, "xDct32FwdBatchDev: NULL or unaligned buffer");
+    if (const char *why = args::batch(d_in, d_out, 16, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
     return launch_op(ctx, 0, d_in, d_out, n, (hipStream_t)stream);
 }
@@ -607,7 +635,7 @@ int xDct32FwdBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out, siz
 int xDct32InvBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (bad_ptrs(d_in, d_out, n)) return fail(ctx, X266HIP_EINVAL, "xDct32InvBatchDev: NULL or unaligned buffer");
+    if (const char *why = args::batch(d_in, d_out, 16, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
     return launch_op(ctx, 1, d_in, d_out, n, (hipStream_t)stream);
 }
@@ -616,30 +644,24 @@ int xDct32SatdFrameDev(x266hip_ctx *ctx, const int16_t *d_dct_in, int16_t *d_dct
                        const int16_t *d_diff, uint32_t *d_satd_out, size_t n_satd_blocks, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (bad_ptrs(d_dct_in, d_dct_out, n_dct_blocks) || bad_ptrs(d_diff, d_satd_out, n_satd_blocks))
-        return fail(ctx, X266HIP_EINVAL, "xDct32SatdFrameDev: NULL or unaligned buffer");
+    if (const char *why = args::dct32_satd_frame(d_dct_in, d_dct_out, n_dct_blocks, d_diff, d_satd_out, n_satd_blocks)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    const hipError_t e = launch_frame_lanes(d_dct_in, d_dct_out, n_dct_blocks, ctx->d_fwd, d_diff, d_satd_out, n_satd_blocks, cfg_for(ctx, 2), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "frame lanes launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "frame lanes launch",
+                    launch_frame_lanes(d_dct_in, d_dct_out, n_dct_blocks, ctx->d_fwd, d_diff, d_satd_out, n_satd_blocks, cfg_for(ctx, 2), (hipStream_t)stream));
 }
 
 int xDct32PassDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_out, size_t n, int shift, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (bad_ptrs(d_in, d_out, n)) return fail(ctx, X266HIP_EINVAL, "xDct32PassDev: NULL or unaligned buffer");
-    if (shift < 1 || shift > 15) return fail(ctx, X266HIP_EINVAL, "xDct32PassDev: shift must be 1..15");
+    if (const char *why = args::dct32_pass(d_in, d_out, n, shift)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    const hipError_t e = launch_dct32_pass(d_in, d_out, n, shift, ctx->d_fwd, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "1-D pass launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "1-D pass launch", launch_dct32_pass(d_in, d_out, n, shift, ctx->d_fwd, (hipStream_t)stream));
 }
 
 int xDct32FwdInvBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_coef, int16_t *d_recon, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (bad_ptrs(d_in, d_recon, n) || (n && d_coef && ((uintptr_t)d_coef & 15u)))
-        return fail(ctx, X266HIP_EINVAL, "xDct32FwdInvBatchDev: NULL or unaligned buffer");
+    if (const char *why = args::dct32_fwd_inv_batch(d_in, d_coef, d_recon, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
     LaunchCfg cfg = cfg_for(ctx, 1);
     // 2 blocks per wave with both outputs (the shape that held 0.73-0.76 of 8 TB/s on every box); without the coefficient output the wave's traffic is a
@@ -651,46 +673,29 @@ int xDct32FwdInvBatchDev(x266hip_ctx *ctx, const int16_t *d_in, int16_t *d_coef,
     hipError_t e;
     const bool knobs_untouched = !ctx->dct_fwdinv_blocks_per_wave && !ctx->dct_wg_threads;
     const bool disjoint = !ranges_overlap(d_in, n * 2048, d_recon, n * 2048) && !ranges_overlap(d_in, n * 2048, d_coef, n * 2048);
-    const int forced = forced_cand(ctx);
     if (ctx->autotune && n && knobs_untouched && disjoint) {
         const ShapeCand *cands = d_coef ? kFwdInvCands : kReconCands;
         const int n_cands = d_coef ? (int)(sizeof kFwdInvCands / sizeof kFwdInvCands[0]) : (int)(sizeof kReconCands / sizeof kReconCands[0]);
-        const int family = d_coef ? x266hip_ctx::kTuneFwdInv : x266hip_ctx::kTuneRecon;
-        if (forced >= n_cands) return fail(ctx, X266HIP_EINVAL, "xDct32FwdInvBatchDev: option \"autotune\" forces a launch shape this family does not have");
-        auto run = [&](int c) {
-            LaunchCfg k = cfg;
-            k.units_per_wave = cands[c].units_per_wave; k.wg_threads = cands[c].wg_threads; k.lds_bytes_per_wave = cands[c].lds_bytes_per_wave; k.shape = cands[c].shape;
-            return launch_dct32_fwdinv(d_in, d_coef, d_recon, n, ctx->d_fwd, ctx->d_inv_acc, k, (hipStream_t)stream);
-        };
-        e = run(forced >= 0 ? forced : tune_family(ctx, family, n_cands, n >= ((size_t)1 << 18), (hipStream_t)stream, run));
-        if (forced >= 0 && e == hipSuccess) count_forced(ctx, family, forced);
+        auto run = [&](int c) { return launch_dct32_fwdinv(d_in, d_coef, d_recon, n, ctx->d_fwd, ctx->d_inv_acc, cands[c].over(cfg), (hipStream_t)stream); };
+        if (const int rc = run_family(ctx, __func__, d_coef ? x266hip_ctx::kTuneFwdInv : x266hip_ctx::kTuneRecon, n_cands, n >= ((size_t)1 << 18), (hipStream_t)stream, run, &e)) return rc;
     } else {
         e = launch_dct32_fwdinv(d_in, d_coef, d_recon, n, ctx->d_fwd, ctx->d_inv_acc, cfg, (hipStream_t)stream);
     }
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fwd+inv launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fwd+inv launch", e);
 }
 
 int xSatd8x8BatchDev(x266hip_ctx *ctx, const int16_t *d_diff, uint32_t *d_out, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (n && (!d_diff || !d_out || ((uintptr_t)d_diff & 15u) || ((uintptr_t)d_out & 3u)))
-        return fail(ctx, X266HIP_EINVAL, "xSatd8x8BatchDev: NULL or unaligned buffer");
+    if (const char *why = args::batch(d_diff, d_out, 4, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
     const bool knobs_untouched = !ctx->satd_variant && !ctx->satd_groups_per_wave && !ctx->satd_wg_threads && !ctx->satd_lds_per_wave;
-    const int forced = forced_cand(ctx);                                      // forcing: at any size (the LDS-DMA kernel runs from one block on, as under "satd_variant" 3)
-    if (ctx->autotune && knobs_untouched && (forced >= 0 ? n > 0 : n >= kSatdDmaMinBlocks) && !ranges_overlap(d_diff, n * 128, d_out, n * 4)) {
-        const int n_cands = (int)(sizeof kSatdCands / sizeof kSatdCands[0]);
-        if (forced >= n_cands) return fail(ctx, X266HIP_EINVAL, "xSatd8x8BatchDev: option \"autotune\" forces a launch shape this family does not have");
-        auto run = [&](int c) {
-            LaunchCfg k = cfg_for(ctx, 2);
-            k.units_per_wave = kSatdCands[c].units_per_wave; k.wg_threads = kSatdCands[c].wg_threads; k.lds_bytes_per_wave = kSatdCands[c].lds_bytes_per_wave; k.shape = kSatdCands[c].shape;
-            return launch_satd8x8(d_diff, d_out, n, k, (hipStream_t)stream);
-        };
-        const hipError_t e = run(forced >= 0 ? forced : tune_family(ctx, x266hip_ctx::kTuneSatd, n_cands, n >= ((size_t)1 << 23), (hipStream_t)stream, run));
-        if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "kernel launch", e);
-        if (forced >= 0) count_forced(ctx, x266hip_ctx::kTuneSatd, forced);
-        return X266HIP_OK;
+    // forcing: at any size (the LDS-DMA kernel runs from one block on, as under "satd_variant" 3)
+    if (ctx->autotune && knobs_untouched && (forced_cand(ctx) >= 0 ? n > 0 : n >= kSatdDmaMinBlocks) && !ranges_overlap(d_diff, n * 128, d_out, n * 4)) {
+        auto run = [&](int c) { return launch_satd8x8(d_diff, d_out, n, kSatdCands[c].over(cfg_for(ctx, 2)), (hipStream_t)stream); };
+        hipError_t e;
+        if (const int rc = run_family(ctx, __func__, x266hip_ctx::kTuneSatd, (int)(sizeof kSatdCands / sizeof kSatdCands[0]), n >= ((size_t)1 << 23), (hipStream_t)stream, run, &e)) return rc;
+        return launched(ctx, "kernel launch", e);
     }
     return launch_op(ctx, 2, d_diff, d_out, n, (hipStream_t)stream);
 }
@@ -698,81 +703,62 @@ int xSatd8x8BatchDev(x266hip_ctx *ctx, const int16_t *d_diff, uint32_t *d_out, s
 int xHipMemCeilingDev(x266hip_ctx *ctx, int kind, const void *d_src, void *d_dst, size_t bytes, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (kind < X266_MEM_COPY || kind > X266_MEM_READ_PROBE) return fail(ctx, X266HIP_EINVAL, "xHipMemCeilingDev: kind must be X266_MEM_COPY, _READ, _WRITE or _READ_PROBE");
-    if ((bytes & 15u) || bad_ptrs(kind == X266_MEM_WRITE ? d_dst : d_src, d_dst, bytes)) return fail(ctx, X266HIP_EINVAL, "xHipMemCeilingDev: NULL or unaligned buffer, or bytes not a multiple of 16");
+    if (const char *why = args::mem_ceiling(kind, d_src, d_dst, bytes)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    const hipError_t e = launch_mem_ceiling(kind, d_src, d_dst, bytes, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "memory ceiling launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "memory ceiling launch", launch_mem_ceiling(kind, d_src, d_dst, bytes, (hipStream_t)stream));
 }
 
 int xIntra32PredictDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_modes,
                        const uint32_t *d_ref_index, uint8_t *d_pred, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (n && (!d_refs || !d_modes || !d_pred || (((uintptr_t)d_refs | (uintptr_t)d_pred) & 15u) || ((uintptr_t)d_ref_index & 3u)))
-        return fail(ctx, X266HIP_EINVAL, "xIntra32PredictDev: NULL or unaligned buffer");
+    if (const char *why = args::intra32_predict(d_refs, d_modes, d_ref_index, d_pred, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_intra32_predict(d_refs, d_modes, d_ref_index, d_pred, n, x266hip_ctx::kIntraRounds, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "intra launch", launch_intra32_predict(d_refs, d_modes, d_ref_index, d_pred, n, x266hip_ctx::kIntraRounds, (hipStream_t)stream));
 }
 
 int xIntra32ResidualDct32Dev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_modes, const uint32_t *d_ref_index,
                              const uint8_t *d_src, int16_t *d_coef, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (n && (!d_refs || !d_modes || !d_src || !d_coef || (((uintptr_t)d_refs | (uintptr_t)d_src | (uintptr_t)d_coef) & 15u) || ((uintptr_t)d_ref_index & 3u)))
-        return fail(ctx, X266HIP_EINVAL, "xIntra32ResidualDct32Dev: NULL or unaligned buffer");
+    if (const char *why = args::intra32_residual_dct32(d_refs, d_modes, d_ref_index, d_src, d_coef, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_intra32_residual_dct32(d_refs, d_modes, d_ref_index, d_src, d_coef, n, ctx->d_fwd, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra residual + transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "intra residual + transform launch", launch_intra32_residual_dct32(d_refs, d_modes, d_ref_index, d_src, d_coef, n, ctx->d_fwd, (hipStream_t)stream));
 }
 
 int xIntra32CostsDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uint8_t *d_src,
                      uint32_t *d_costs, uint8_t *d_best_mode, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (n && (!d_refs || !d_src || !d_costs || (((uintptr_t)d_refs | (uintptr_t)d_src) & 15u) || ((uintptr_t)d_costs & 3u)))
-        return fail(ctx, X266HIP_EINVAL, "xIntra32CostsDev: NULL or unaligned buffer");
+    if (const char *why = args::intra32_costs(d_refs, d_src, d_costs, d_best_mode, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_intra32_costs(d_refs, d_src, d_costs, d_best_mode, n, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra decision launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "intra decision launch", launch_intra32_costs(d_refs, d_src, d_costs, d_best_mode, n, (hipStream_t)stream));
 }
 
 int xFillResidualDev(x266hip_ctx *ctx, int16_t *d_dst, size_t n_samples, uint64_t seed, uint64_t first_index,
                      void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (n_samples && (!d_dst || ((uintptr_t)d_dst & 15u)))
-        return fail(ctx, X266HIP_EINVAL, "xFillResidualDev: NULL or unaligned buffer");
+    if (const char *why = args::fill_residual(d_dst, n_samples)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_fill_residual(d_dst, n_samples, seed, first_index, cfg_for(ctx, 0), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fill launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fill launch", launch_fill_residual(d_dst, n_samples, seed, first_index, cfg_for(ctx, 0), (hipStream_t)stream));
 }
+
+static_assert(args::kTransformTypes == x266hip_ctx::kTypes, "the rule set and the context count the same transform types");
 
 int xTransformFwdBatchDev(x266hip_ctx *ctx, int type, int size, const int16_t *d_in, int16_t *d_out, size_t n,
                           const uint32_t *d_offsets, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (type < 0 || type >= x266hip_ctx::kTypes) return fail(ctx, X266HIP_EINVAL, "xTransformFwdBatchDev: unknown transform type");
-    if (size != 4 && size != 8 && size != 16 && !(size == 32 && type == X266_TR_DCT2))
-        return fail(ctx, X266HIP_EINVAL, "xTransformFwdBatchDev: size must be 4, 8, 16 (or 32 for DCT-II)");
-    if (bad_ptrs(d_in, d_out, n)) return fail(ctx, X266HIP_EINVAL, "xTransformFwdBatchDev: NULL or unaligned buffer");
-    if (n && ((uintptr_t)d_offsets & 3u)) return fail(ctx, X266HIP_EINVAL, "xTransformFwdBatchDev: unaligned offset table");
-    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformFwdBatchDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    if (const char *why = args::transform_batch(type, size, d_in, d_out, n, d_offsets)) return refuse(ctx, __func__, why);
+    if (!ctx->tr_tables_valid) return tables_invalid(ctx, __func__);
     X_DEV(ctx);
     if (size == 32 && !d_offsets) return launch_op(ctx, 0, d_in, d_out, n, (hipStream_t)stream);
     const int l = size == 4 ? 0 : (size == 8 ? 1 : 2);
     LaunchCfg cfg = cfg_for(ctx, 0);
     cfg.units_per_wave = 1;                                             // one 32x32 tile per wave (profiles/r01_launch_sweep.txt)
-    hipError_t e = size == 32 ? launch_transform_small(5, d_in, d_out, n, ctx->d_fwd, d_offsets, cfg, (hipStream_t)stream)
-                              : launch_transform_small(l + 2, d_in, d_out, n, ctx->d_tr[type][l], d_offsets, cfg, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "transform launch", size == 32 ? launch_transform_small(5, d_in, d_out, n, ctx->d_fwd, d_offsets, cfg, (hipStream_t)stream)
+                                                        : launch_transform_small(l + 2, d_in, d_out, n, ctx->d_tr[type][l], d_offsets, cfg, (hipStream_t)stream));
 }
 
 // All or nothing: the device tables are built from `next`, a COPY of the slot matrices with the wanted changes, and the context's
@@ -849,265 +835,140 @@ int xTransformTilesDev(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16
                        const uint32_t *d_tile_offsets, const uint8_t *d_tile_class, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (bad_ptrs(d_in, d_out, n_tiles) || (n_tiles && !d_tile_class)) return fail(ctx, X266HIP_EINVAL, "xTransformTilesDev: NULL or unaligned buffer");
-    if (n_tiles && ((uintptr_t)d_tile_offsets & 3u)) return fail(ctx, X266HIP_EINVAL, "xTransformTilesDev: unaligned offset table");
-    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformTilesDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    if (const char *why = args::transform_tiles(d_in, d_out, n_tiles, d_tile_offsets, d_tile_class)) return refuse(ctx, __func__, why);
+    if (!ctx->tr_tables_valid) return tables_invalid(ctx, __func__);
     X_DEV(ctx);
     LaunchCfg cfg = cfg_for(ctx, inverse ? 1 : 0);
     cfg.lds_bytes_per_wave = x266hip_ctx::kTileLdsPerWave;
     cfg.units_per_wave = ctx->tile_tiles_per_wave ? ctx->tile_tiles_per_wave : 2;   // measured optimum (profiles/r03_tiles_one_launch.txt): the wave's table copy serves two tiles
-    hipError_t e = launch_transform_tiles(inverse != 0, d_in, d_out, n_tiles, d_tile_offsets, d_tile_class,
-                                          inverse ? ctx->d_tile_inv : ctx->d_tile_fwd, cfg, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "tile transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "tile transform launch", launch_transform_tiles(inverse != 0, d_in, d_out, n_tiles, d_tile_offsets, d_tile_class,
+                                                                         inverse ? ctx->d_tile_inv : ctx->d_tile_fwd, cfg, (hipStream_t)stream));
 }
 
 int xConvInputFmtDev(x266hip_ctx *ctx, x266_ref_block_t *d_tiles, const uint8_t *d_y, const uint8_t *d_u, const uint8_t *d_v,
                      intptr_t strdY, int width, int height, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return fail(ctx, X266HIP_EINVAL, "xConvInputFmtDev: width/height must be multiples of 16");
-    if (!d_tiles || !d_y || !d_u || !d_v) return fail(ctx, X266HIP_EINVAL, "xConvInputFmtDev: NULL buffer");
-    if (strdY < width || (strdY & 15) || (((uintptr_t)d_y | (uintptr_t)d_tiles) & 15u) || (((uintptr_t)d_u | (uintptr_t)d_v) & 7u))
-        return fail(ctx, X266HIP_EINVAL, "xConvInputFmtDev: stride / alignment");
+    if (const char *why = args::tile_convert(true, d_tiles, d_y, d_u, d_v, strdY, 0, width, height)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_tile_convert(true, d_tiles, const_cast<uint8_t *>(d_y), const_cast<uint8_t *>(d_u), const_cast<uint8_t *>(d_v),
-                                       (long long)strdY, (long long)(strdY >> 1), width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "tile pack launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "tile pack launch", launch_tile_convert(true, d_tiles, const_cast<uint8_t *>(d_y), const_cast<uint8_t *>(d_u), const_cast<uint8_t *>(d_v),
+                                                                 (long long)strdY, (long long)(strdY >> 1), width, height, (hipStream_t)stream));
 }
 
 int xConvOutput420Dev(x266hip_ctx *ctx, const x266_ref_block_t *d_tiles, uint8_t *d_y, intptr_t strdY, uint8_t *d_u, uint8_t *d_v,
                       intptr_t strdC, int width, int height, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return fail(ctx, X266HIP_EINVAL, "xConvOutput420Dev: width/height must be multiples of 16");
-    if (!d_tiles || !d_y || !d_u || !d_v) return fail(ctx, X266HIP_EINVAL, "xConvOutput420Dev: NULL buffer");
-    if (strdY < width || strdC < width / 2 || (strdY & 15) || (strdC & 7) || (((uintptr_t)d_y | (uintptr_t)d_tiles) & 15u) ||
-        (((uintptr_t)d_u | (uintptr_t)d_v) & 7u))
-        return fail(ctx, X266HIP_EINVAL, "xConvOutput420Dev: stride / alignment");
+    if (const char *why = args::tile_convert(false, d_tiles, d_y, d_u, d_v, strdY, strdC, width, height)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_tile_convert(false, const_cast<x266_ref_block_t *>(d_tiles), d_y, d_u, d_v, (long long)strdY, (long long)strdC,
-                                       width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "tile unpack launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "tile unpack launch", launch_tile_convert(false, const_cast<x266_ref_block_t *>(d_tiles), d_y, d_u, d_v, (long long)strdY, (long long)strdC,
+                                                                   width, height, (hipStream_t)stream));
 }
 
 int xResidualLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                      int block_edge, int16_t *d_residual, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (block_edge != 8 && block_edge != 32) return fail(ctx, X266HIP_EINVAL, "xResidualLumaDev: block_edge must be 8 or 32");
-    const int mask = block_edge == 32 ? 31 : 15;
-    if (width <= 0 || height <= 0 || (width & mask) || (height & mask)) return fail(ctx, X266HIP_EINVAL, "xResidualLumaDev: frame size");
-    if (!d_cur || !d_pred || !d_residual || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_residual)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xResidualLumaDev: NULL or unaligned buffer");
+    if (const char *why = args::residual_luma(d_cur, d_pred, width, height, block_edge, d_residual)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_residual_luma(block_edge, d_cur, d_pred, d_residual, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "residual launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "residual launch", launch_residual_luma(block_edge, d_cur, d_pred, d_residual, width, height, (hipStream_t)stream));
 }
 
 int xDct32FwdFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                           int16_t *d_coef, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 31) || (height & 31)) return fail(ctx, X266HIP_EINVAL, "xDct32FwdFromTilesDev: width/height must be multiples of 32");
-    if (!d_cur || !d_pred || !d_coef || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_coef)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xDct32FwdFromTilesDev: NULL or unaligned buffer");
+    if (const char *why = args::from_tiles(d_cur, d_pred, width, height, 32, d_coef, 16)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_dct32_from_tiles(d_cur, d_pred, d_coef, width, height, ctx->d_fwd, cfg_for(ctx, 0), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused transform launch", launch_dct32_from_tiles(d_cur, d_pred, d_coef, width, height, ctx->d_fwd, cfg_for(ctx, 0), (hipStream_t)stream));
 }
 
 int xSatd8x8FromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                          uint32_t *d_out, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return fail(ctx, X266HIP_EINVAL, "xSatd8x8FromTilesDev: width/height must be multiples of 16");
-    if (!d_cur || !d_pred || !d_out || ((((uintptr_t)d_cur | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_out & 3u))
-        return fail(ctx, X266HIP_EINVAL, "xSatd8x8FromTilesDev: NULL or unaligned buffer");
+    if (const char *why = args::from_tiles(d_cur, d_pred, width, height, 16, d_out, 4)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_satd8x8_from_tiles(d_cur, d_pred, d_out, width, height, ctx->satd_variant == 1 || ctx->satd_variant == 3 ? ctx->satd_variant : 0, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused satd launch", e);
-    return X266HIP_OK;
-}
-
-// the two output streams of a chroma call must not overlap: plane V starts at or after U's first block ends (interleaved
-// form) or anywhere else outside [U, U + span)
-static bool chroma_outputs_ok(const void *u, const void *v, size_t block_bytes, size_t n_blocks, size_t pitch)
-{
-    if (!u || !v || pitch < 1 || n_blocks == 0) return u && v && pitch >= 1;
-    const uintptr_t a = (uintptr_t)u, b = (uintptr_t)v;
-    const uintptr_t lo = a < b ? a : b, hi = a < b ? b : a;
-    const size_t gap = (size_t)(hi - lo);
-    if (gap >= ((n_blocks - 1) * pitch + 1) * block_bytes) return true;     // disjoint spans
-    // interleaved: the other plane's blocks sit in the holes of this one's pitch
-    return pitch >= 2 && gap % block_bytes == 0 && gap / block_bytes >= 1 && gap / block_bytes <= pitch - 1;
+    return launched(ctx, "fused satd launch", launch_satd8x8_from_tiles(d_cur, d_pred, d_out, width, height,
+                                                                        ctx->satd_variant == 1 || ctx->satd_variant == 3 ? ctx->satd_variant : 0, (hipStream_t)stream));
 }
 
 int xResidualChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                        int block_edge, int16_t *d_res_u, int16_t *d_res_v, size_t block_pitch, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (block_edge != 8 && block_edge != 32) return fail(ctx, X266HIP_EINVAL, "xResidualChromaDev: block_edge must be 8 or 32");
-    const int mask = block_edge == 32 ? 63 : 15;                             // luma dimensions: a 32x32 chroma block is a 64x64 CTU's
-    if (width <= 0 || height <= 0 || (width & mask) || (height & mask)) return fail(ctx, X266HIP_EINVAL, "xResidualChromaDev: frame size");
-    if (!d_cur || !d_pred || !d_res_u || !d_res_v || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_res_u | (uintptr_t)d_res_v)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xResidualChromaDev: NULL or unaligned buffer");
-    const size_t n_blocks = (size_t)(width / 2 / block_edge) * (size_t)(height / 2 / block_edge);
-    if (!chroma_outputs_ok(d_res_u, d_res_v, (size_t)block_edge * block_edge * 2, n_blocks, block_pitch))
-        return fail(ctx, X266HIP_EINVAL, "xResidualChromaDev: block_pitch < 1 or overlapping U / V outputs");
+    if (const char *why = args::chroma_from_tiles(d_cur, d_pred, width, height, block_edge, d_res_u, d_res_v, 16, (size_t)block_edge * block_edge * 2, block_pitch))
+        return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_residual_chroma(block_edge, d_cur, d_pred, d_res_u, d_res_v, block_pitch, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "chroma residual launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "chroma residual launch", launch_residual_chroma(block_edge, d_cur, d_pred, d_res_u, d_res_v, block_pitch, width, height, (hipStream_t)stream));
 }
 
 int xDct32FwdChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                                 int16_t *d_coef_u, int16_t *d_coef_v, size_t block_pitch, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 63) || (height & 63)) return fail(ctx, X266HIP_EINVAL, "xDct32FwdChromaFromTilesDev: width/height must be multiples of 64");
-    if (!d_cur || !d_pred || !d_coef_u || !d_coef_v || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_coef_u | (uintptr_t)d_coef_v)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xDct32FwdChromaFromTilesDev: NULL or unaligned buffer");
-    if (!chroma_outputs_ok(d_coef_u, d_coef_v, 2048, (size_t)(width / 64) * (size_t)(height / 64), block_pitch))
-        return fail(ctx, X266HIP_EINVAL, "xDct32FwdChromaFromTilesDev: block_pitch < 1 or overlapping U / V outputs");
+    if (const char *why = args::chroma_from_tiles(d_cur, d_pred, width, height, 32, d_coef_u, d_coef_v, 16, 2048, block_pitch)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_dct32_chroma_from_tiles(d_cur, d_pred, d_coef_u, d_coef_v, block_pitch, width, height, ctx->d_fwd, cfg_for(ctx, 0), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused chroma transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused chroma transform launch",
+                    launch_dct32_chroma_from_tiles(d_cur, d_pred, d_coef_u, d_coef_v, block_pitch, width, height, ctx->d_fwd, cfg_for(ctx, 0), (hipStream_t)stream));
 }
 
 int xDct32FwdCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                              int16_t *d_coef, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 63) || (height & 63)) return fail(ctx, X266HIP_EINVAL, "xDct32FwdCtuFromTilesDev: width/height must be multiples of 64");
-    if (!d_cur || !d_pred || !d_coef || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_coef)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xDct32FwdCtuFromTilesDev: NULL or unaligned buffer");
+    if (const char *why = args::from_tiles(d_cur, d_pred, width, height, 64, d_coef, 16)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_dct32_ctu_from_tiles(d_cur, d_pred, d_coef, width, height, ctx->d_fwd, cfg_for(ctx, 0), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused CTU transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused CTU transform launch", launch_dct32_ctu_from_tiles(d_cur, d_pred, d_coef, width, height, ctx->d_fwd, cfg_for(ctx, 0), (hipStream_t)stream));
 }
 
 // ---- reconstruction into tiles: the way back from residuals / coefficients to a frame --------------------------------------
-// The output tile array may BE the pred array (an encoder reconstructs over its prediction) but must not otherwise overlap
-// it, nor any other input.
-static bool recon_in_place_or_disjoint(const void *recon, const void *pred, size_t tile_bytes)
-{
-    return recon == pred || !ranges_overlap(recon, tile_bytes, pred, tile_bytes);
-}
-
-// bytes from the first byte of block 0 to the last byte of block n - 1 of a stream with a pitch of `pitch` blocks, and the
-// stream must not run past the end of the address space: false where either does not fit (no wrap-around)
-static bool block_stream_span(const void *p, size_t n_blocks, size_t pitch, size_t block_bytes, size_t *span)
-{
-    size_t t = 0;
-    uintptr_t end = 0;
-    if (n_blocks == 0) { *span = 0; return true; }
-    return !__builtin_mul_overflow(n_blocks - 1, pitch, &t) && !__builtin_add_overflow(t, (size_t)1, &t) &&
-           !__builtin_mul_overflow(t, block_bytes, span) && !__builtin_add_overflow((uintptr_t)p, *span, &end);
-}
-
 int xReconLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_residual, int width, int height,
                   int block_edge, x266_ref_block_t *d_recon, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (block_edge != 8 && block_edge != 32) return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: block_edge must be 8 or 32");
-    const int mask = block_edge == 32 ? 31 : 15;
-    if (width <= 0 || height <= 0 || (width & mask) || (height & mask)) return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: frame size");
-    if (!d_pred || !d_residual || !d_recon || ((((uintptr_t)d_pred | (uintptr_t)d_residual | (uintptr_t)d_recon)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: NULL or unaligned buffer");
-    const size_t pixels = (size_t)width * (size_t)height, tile_bytes = pixels * 2;       // 512 bytes per 256 pixels
-    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_residual, pixels * 2))
-        return fail(ctx, X266HIP_EINVAL, "xReconLumaDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    if (const char *why = args::recon_luma(d_pred, d_residual, width, height, block_edge, d_recon)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_recon_luma(block_edge, d_pred, d_residual, d_recon, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "recon launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "recon launch", launch_recon_luma(block_edge, d_pred, d_residual, d_recon, width, height, (hipStream_t)stream));
 }
 
 int xReconChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_pred, const int16_t *d_res_u, const int16_t *d_res_v, size_t block_pitch,
                     int width, int height, int block_edge, x266_ref_block_t *d_recon, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (block_edge != 8 && block_edge != 32) return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: block_edge must be 8 or 32");
-    const int mask = block_edge == 32 ? 63 : 15;
-    if (width <= 0 || height <= 0 || (width & mask) || (height & mask)) return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: frame size");
-    if (!d_pred || !d_res_u || !d_res_v || !d_recon ||
-        ((((uintptr_t)d_pred | (uintptr_t)d_res_u | (uintptr_t)d_res_v | (uintptr_t)d_recon)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: NULL or unaligned buffer");
-    const size_t n_blocks = (size_t)(width / 2 / block_edge) * (size_t)(height / 2 / block_edge), block_bytes = (size_t)block_edge * block_edge * 2;
-    size_t span_u = 0, span_v = 0;
-    if (block_pitch < 1 || !block_stream_span(d_res_u, n_blocks, block_pitch, block_bytes, &span_u) ||
-        !block_stream_span(d_res_v, n_blocks, block_pitch, block_bytes, &span_v))
-        return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: block_pitch < 1, or the residual streams do not fit in the address space");
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2;
-    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_res_u, span_u) ||
-        ranges_overlap(d_recon, tile_bytes, d_res_v, span_v))
-        return fail(ctx, X266HIP_EINVAL, "xReconChromaDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    if (const char *why = args::recon_chroma(d_pred, d_res_u, d_res_v, block_pitch, width, height, block_edge, d_recon)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_recon_chroma(block_edge, d_pred, d_res_u, d_res_v, block_pitch, d_recon, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "chroma recon launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "chroma recon launch", launch_recon_chroma(block_edge, d_pred, d_res_u, d_res_v, block_pitch, d_recon, width, height, (hipStream_t)stream));
+}
+
+static LaunchCfg inv_to_tiles_cfg(const x266hip_ctx *ctx)
+{
+    LaunchCfg cfg = cfg_for(ctx, 1);
+    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
+    return cfg;
 }
 
 int xDct32InvToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
                         x266_ref_block_t *d_recon, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 31) || (height & 31)) return fail(ctx, X266HIP_EINVAL, "xDct32InvToTilesDev: width/height must be multiples of 32");
-    if (!d_coef || !d_pred || !d_recon || ((((uintptr_t)d_coef | (uintptr_t)d_pred | (uintptr_t)d_recon)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xDct32InvToTilesDev: NULL or unaligned buffer");
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2;                      // and as many bytes of coefficients
-    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_coef, tile_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xDct32InvToTilesDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    if (const char *why = args::inv_to_tiles(d_coef, d_pred, width, height, 32, d_recon)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    LaunchCfg cfg = cfg_for(ctx, 1);
-    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
-    hipError_t e = launch_dct32_inv_to_tiles(d_coef, d_pred, d_recon, width, height, ctx->d_inv_lds, cfg, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused inverse transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused inverse transform launch",
+                    launch_dct32_inv_to_tiles(d_coef, d_pred, d_recon, width, height, ctx->d_inv_lds, inv_to_tiles_cfg(ctx), (hipStream_t)stream));
 }
 
 int xDct32InvCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const x266_ref_block_t *d_pred, int width, int height,
                            x266_ref_block_t *d_recon, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 63) || (height & 63)) return fail(ctx, X266HIP_EINVAL, "xDct32InvCtuToTilesDev: width/height must be multiples of 64");
-    if (!d_coef || !d_pred || !d_recon || ((((uintptr_t)d_coef | (uintptr_t)d_pred | (uintptr_t)d_recon)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xDct32InvCtuToTilesDev: NULL or unaligned buffer");
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, coef_bytes = (size_t)(width / 64) * (size_t)(height / 64) * 12288;
-    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_coef, coef_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xDct32InvCtuToTilesDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
+    if (const char *why = args::inv_to_tiles(d_coef, d_pred, width, height, 64, d_recon)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    LaunchCfg cfg = cfg_for(ctx, 1);
-    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
-    hipError_t e = launch_dct32_inv_ctu_to_tiles(d_coef, d_pred, d_recon, width, height, ctx->d_inv_lds, cfg, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused CTU inverse launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused CTU inverse launch",
+                    launch_dct32_inv_ctu_to_tiles(d_coef, d_pred, d_recon, width, height, ctx->d_inv_lds, inv_to_tiles_cfg(ctx), (hipStream_t)stream));
 }
 
 // ---- the mixed transform set from and into tiles, per CTU ----------------------------------------------------------------------
-// Byte spans of the CTU calls' buffers for a frame of width x height (multiples of 16, positive): the tile arrays, the coefficient
-// stream (12 KiB per CTU) and the class bytes (6 per CTU).  Every product is checked before it is formed, and so is every buffer's
-// end against the address space; false where anything would not fit.
-static bool ctu_spans(int width, int height, const void *tiles_a, const void *tiles_b, const void *coef, const void *cls,
-                      size_t *tile_bytes, size_t *coef_bytes, size_t *class_bytes)
-{
-    const size_t ctus_x = ((size_t)width + 63) / 64, ctus_y = ((size_t)height + 63) / 64;
-    size_t n = 0;
-    uintptr_t end = 0;
-    return !__builtin_mul_overflow((size_t)width, (size_t)height, tile_bytes) && !__builtin_mul_overflow(*tile_bytes, (size_t)2, tile_bytes) &&
-           !__builtin_mul_overflow(ctus_x, ctus_y, &n) && !__builtin_mul_overflow(n, (size_t)12288, coef_bytes) &&
-           !__builtin_mul_overflow(n, (size_t)6, class_bytes) &&
-           !__builtin_add_overflow((uintptr_t)tiles_a, *tile_bytes, &end) && !__builtin_add_overflow((uintptr_t)tiles_b, *tile_bytes, &end) &&
-           !__builtin_add_overflow((uintptr_t)coef, *coef_bytes, &end) && !__builtin_add_overflow((uintptr_t)cls, *class_bytes, &end);
-}
-
 static LaunchCfg ctu_tiles_cfg(const x266hip_ctx *ctx, int inverse)
 {
     LaunchCfg cfg = cfg_for(ctx, inverse);
@@ -1119,173 +980,83 @@ int xTransformCtuFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, c
                               const uint8_t *d_class, int16_t *d_coef, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: width/height must be positive multiples of 16");
-    if (!d_cur || !d_pred || !d_class || !d_coef || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_coef)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: NULL or unaligned buffer");
-    size_t tile_bytes = 0, coef_bytes = 0, class_bytes = 0;
-    if (!ctu_spans(width, height, d_cur, d_pred, d_coef, d_class, &tile_bytes, &coef_bytes, &class_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: a buffer does not fit in the address space");
-    if (ranges_overlap(d_coef, coef_bytes, d_cur, tile_bytes) || ranges_overlap(d_coef, coef_bytes, d_pred, tile_bytes) ||
-        ranges_overlap(d_coef, coef_bytes, d_class, class_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuFromTilesDev: d_coef overlaps an input");
-    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformCtuFromTilesDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    if (const char *why = args::transform_ctu_from_tiles(d_cur, d_pred, width, height, d_class, d_coef)) return refuse(ctx, __func__, why);
+    if (!ctx->tr_tables_valid) return tables_invalid(ctx, __func__);
     X_DEV(ctx);
-    hipError_t e = launch_transform_ctu_tiles(false, d_cur, nullptr, d_pred, d_class, d_coef, nullptr, width, height, ctx->d_tile_fwd,
-                                              ctu_tiles_cfg(ctx, 0), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "CTU transform from tiles launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "CTU transform from tiles launch", launch_transform_ctu_tiles(false, d_cur, nullptr, d_pred, d_class, d_coef, nullptr, width, height, ctx->d_tile_fwd,
+                                                                                       ctu_tiles_cfg(ctx, 0), (hipStream_t)stream));
 }
 
 int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8_t *d_class, const x266_ref_block_t *d_pred, int width,
                             int height, x266_ref_block_t *d_recon, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: width/height must be positive multiples of 16");
-    if (!d_coef || !d_class || !d_pred || !d_recon || ((((uintptr_t)d_coef | (uintptr_t)d_pred | (uintptr_t)d_recon)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: NULL or unaligned buffer");
-    size_t tile_bytes = 0, coef_bytes = 0, class_bytes = 0;
-    if (!ctu_spans(width, height, d_pred, d_recon, d_coef, d_class, &tile_bytes, &coef_bytes, &class_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: a buffer does not fit in the address space");
-    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || ranges_overlap(d_recon, tile_bytes, d_coef, coef_bytes) ||
-        ranges_overlap(d_recon, tile_bytes, d_class, class_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xTransformCtuToTilesDev: d_recon overlaps an input (only d_recon == d_pred is allowed)");
-    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformCtuToTilesDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    if (const char *why = args::transform_ctu_to_tiles(d_coef, d_class, d_pred, width, height, d_recon)) return refuse(ctx, __func__, why);
+    if (!ctx->tr_tables_valid) return tables_invalid(ctx, __func__);
     X_DEV(ctx);
-    hipError_t e = launch_transform_ctu_tiles(true, nullptr, d_coef, d_pred, d_class, nullptr, d_recon, width, height, ctx->d_tile_inv,
-                                              ctu_tiles_cfg(ctx, 1), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "CTU transform into tiles launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "CTU transform into tiles launch", launch_transform_ctu_tiles(true, nullptr, d_coef, d_pred, d_class, nullptr, d_recon, width, height, ctx->d_tile_inv,
+                                                                                       ctu_tiles_cfg(ctx, 1), (hipStream_t)stream));
 }
 
 // ---- the quantiser (x266_quant.hpp) -----------------------------------------------------------------------------------------------
-// n * unit bytes from p on, where both the product and the buffer's end fit in the address space
-static bool span_fits(const void *p, size_t n, size_t unit, size_t *bytes)
-{
-    uintptr_t end = 0;
-    return !__builtin_mul_overflow(n, unit, bytes) && !__builtin_add_overflow((uintptr_t)p, *bytes, &end);
-}
-
-static bool quant_scalars_ok(const uint8_t *d_qp, int qp, int rounding)
-{
-    return (d_qp || (qp >= 0 && qp <= 51)) && rounding >= 0 && rounding <= 511;
-}
-
 int xQuantRegionsGpu(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16_t *d_out, size_t n_regions, const uint8_t *d_class,
                      const uint8_t *d_qp, int qp, int rounding, uint32_t *d_nnz, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (!quant_scalars_ok(d_qp, qp, rounding)) return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: qp must be 0..51 (without d_qp) and rounding 0..511");
-    if (inverse && d_nnz) return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: d_nnz must be NULL with inverse = 1");
+    if (const char *why = args::quant_regions(inverse, d_in, d_out, n_regions, d_class, d_qp, qp, rounding, d_nnz)) return refuse(ctx, __func__, why);
     if (n_regions == 0) return X266HIP_OK;
-    if (bad_ptrs(d_in, d_out, n_regions) || ((uintptr_t)d_nnz & 3u)) return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: NULL or unaligned buffer");
-    size_t bytes = 0, nnz_bytes = 0, tab_bytes = 0;
-    if (!span_fits(d_in, n_regions, 2048, &bytes) || !span_fits(d_out, n_regions, 2048, &bytes) || !span_fits(d_nnz, n_regions, 4, &nnz_bytes) ||
-        !span_fits(d_class, n_regions, 1, &tab_bytes) || !span_fits(d_qp, n_regions, 1, &tab_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: a buffer does not fit in the address space");
-    if ((d_out != d_in && ranges_overlap(d_out, bytes, d_in, bytes)) || ranges_overlap(d_out, bytes, d_class, tab_bytes) ||
-        ranges_overlap(d_out, bytes, d_qp, tab_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: d_out overlaps an input (only d_out == d_in is allowed)");
-    if (ranges_overlap(d_nnz, nnz_bytes, d_in, bytes) || ranges_overlap(d_nnz, nnz_bytes, d_out, bytes) ||
-        ranges_overlap(d_nnz, nnz_bytes, d_class, tab_bytes) || ranges_overlap(d_nnz, nnz_bytes, d_qp, tab_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xQuantRegionsGpu: d_nnz overlaps another buffer");
     X_DEV(ctx);
-    hipError_t e = launch_quant_regions(inverse != 0, d_in, d_out, n_regions, d_class, d_qp, qp, rounding, d_nnz, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "quantiser launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "quantiser launch", launch_quant_regions(inverse != 0, d_in, d_out, n_regions, d_class, d_qp, qp, rounding, d_nnz, (hipStream_t)stream));
 }
 
 int xDct32CodeCtuTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                           const uint8_t *d_qp, int qp, int rounding, int16_t *d_level, uint32_t *d_nnz, x266_ref_block_t *d_recon, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 63) || (height & 63)) return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: width/height must be multiples of 64");
-    if (!quant_scalars_ok(d_qp, qp, rounding)) return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: qp must be 0..51 (without d_qp) and rounding 0..511");
-    if (!d_cur || !d_pred || !d_level || !d_recon || ((((uintptr_t)d_cur | (uintptr_t)d_pred | (uintptr_t)d_level | (uintptr_t)d_recon)) & 15u) ||
-        ((uintptr_t)d_nnz & 3u))
-        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: NULL or unaligned buffer");
-    const size_t n_ctus = (size_t)(width / 64) * (size_t)(height / 64);
-    size_t tile_bytes = 0, level_bytes = 0, nnz_bytes = 0, qp_bytes = 0;
-    if (!span_fits(d_cur, (size_t)width * 2, (size_t)height, &tile_bytes) || !span_fits(d_pred, (size_t)width * 2, (size_t)height, &tile_bytes) ||
-        !span_fits(d_recon, (size_t)width * 2, (size_t)height, &tile_bytes) || !span_fits(d_level, n_ctus, 12288, &level_bytes) ||
-        !span_fits(d_nnz, n_ctus, 24, &nnz_bytes) || !span_fits(d_qp, n_ctus, 6, &qp_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: a buffer does not fit in the address space");
-    if (!recon_in_place_or_disjoint(d_recon, d_pred, tile_bytes) || (d_cur != d_pred && ranges_overlap(d_recon, tile_bytes, d_cur, tile_bytes)) ||
-        ranges_overlap(d_recon, tile_bytes, d_qp, qp_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: d_recon overlaps an input (only d_recon == d_pred is allowed)");
-    if (ranges_overlap(d_level, level_bytes, d_cur, tile_bytes) || ranges_overlap(d_level, level_bytes, d_pred, tile_bytes) ||
-        ranges_overlap(d_level, level_bytes, d_recon, tile_bytes) || ranges_overlap(d_level, level_bytes, d_qp, qp_bytes) ||
-        ranges_overlap(d_nnz, nnz_bytes, d_cur, tile_bytes) || ranges_overlap(d_nnz, nnz_bytes, d_pred, tile_bytes) ||
-        ranges_overlap(d_nnz, nnz_bytes, d_recon, tile_bytes) || ranges_overlap(d_nnz, nnz_bytes, d_qp, qp_bytes) ||
-        ranges_overlap(d_nnz, nnz_bytes, d_level, level_bytes))
-        return fail(ctx, X266HIP_EINVAL, "xDct32CodeCtuTilesGpu: d_level or d_nnz overlaps another buffer");
+    if (const char *why = args::dct32_code_ctu_tiles(d_cur, d_pred, width, height, d_qp, qp, rounding, d_level, d_nnz, d_recon)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    LaunchCfg cfg = cfg_for(ctx, 1);
-    cfg.lds_bytes_per_wave = x266hip_ctx::kDctInvLdsPerWave;
-    hipError_t e = launch_dct32_code_ctu_tiles(d_cur, d_pred, d_recon, d_level, d_nnz, d_qp, qp, rounding, width, height, ctx->d_fwd, ctx->d_inv_acc, cfg,
-                                               (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused CTU coding launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused CTU coding launch", launch_dct32_code_ctu_tiles(d_cur, d_pred, d_recon, d_level, d_nnz, d_qp, qp, rounding, width, height, ctx->d_fwd,
+                                                                               ctx->d_inv_acc, inv_to_tiles_cfg(ctx), (hipStream_t)stream));
 }
 
 int xSatd8x8ChromaFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width, int height,
                                uint32_t *d_out_u, uint32_t *d_out_v, size_t pitch, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return fail(ctx, X266HIP_EINVAL, "xSatd8x8ChromaFromTilesDev: width/height must be multiples of 16");
-    if (!d_cur || !d_pred || !d_out_u || !d_out_v || ((((uintptr_t)d_cur | (uintptr_t)d_pred)) & 15u) || (((uintptr_t)d_out_u | (uintptr_t)d_out_v) & 3u))
-        return fail(ctx, X266HIP_EINVAL, "xSatd8x8ChromaFromTilesDev: NULL or unaligned buffer");
-    if (!chroma_outputs_ok(d_out_u, d_out_v, 4, (size_t)(width / 16) * (size_t)(height / 16), pitch))
-        return fail(ctx, X266HIP_EINVAL, "xSatd8x8ChromaFromTilesDev: pitch < 1 or overlapping U / V outputs");
+    if (const char *why = args::chroma_from_tiles(d_cur, d_pred, width, height, 8, d_out_u, d_out_v, 4, 4, pitch)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_satd8x8_chroma_from_tiles(d_cur, d_pred, d_out_u, d_out_v, pitch, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "fused chroma satd launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "fused chroma satd launch", launch_satd8x8_chroma_from_tiles(d_cur, d_pred, d_out_u, d_out_v, pitch, width, height, (hipStream_t)stream));
 }
 
 int xSadBatchDev(x266hip_ctx *ctx, int edge, const uint8_t *d_a, const uint8_t *d_b, uint32_t *d_out, size_t n, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (edge != 4 && edge != 8 && edge != 16 && edge != 32 && edge != 64) return fail(ctx, X266HIP_EINVAL, "xSadBatchDev: edge must be 4, 8, 16, 32 or 64");
-    if (n && (!d_a || !d_b || !d_out || (((uintptr_t)d_a | (uintptr_t)d_b) & 15u) || ((uintptr_t)d_out & 3u)))
-        return fail(ctx, X266HIP_EINVAL, "xSadBatchDev: NULL or unaligned buffer");
+    if (const char *why = args::sad_batch(edge, d_a, d_b, d_out, n)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
     hipError_t e;
     const size_t in_bytes = n * (size_t)(edge * edge);
-    const int forced = forced_cand(ctx);
     if (ctx->autotune && n && edge >= 8 && !ranges_overlap(d_a, in_bytes, d_out, n * 4) && !ranges_overlap(d_b, in_bytes, d_out, n * 4)) {
-        const int n_cands = (int)(sizeof kSadCands / sizeof kSadCands[0]);
-        if (forced >= n_cands) return fail(ctx, X266HIP_EINVAL, "xSadBatchDev: option \"autotune\" forces a launch shape this family does not have");
         auto run = [&](int c) { return launch_sad(edge, d_a, d_b, d_out, n, kSadCands[c].wg_threads / 64, kSadCands[c].lds_bytes_per_wave, (hipStream_t)stream); };
         const int family = edge == 8 ? x266hip_ctx::kTuneSad8 : edge == 16 ? x266hip_ctx::kTuneSad16 : edge == 32 ? x266hip_ctx::kTuneSad32 : x266hip_ctx::kTuneSad64;
-        e = run(forced >= 0 ? forced : tune_family(ctx, family, n_cands, in_bytes >= ((size_t)128 << 20), (hipStream_t)stream, run));
-        if (forced >= 0 && e == hipSuccess) count_forced(ctx, family, forced);
+        if (const int rc = run_family(ctx, __func__, family, (int)(sizeof kSadCands / sizeof kSadCands[0]), in_bytes >= ((size_t)128 << 20), (hipStream_t)stream, run, &e)) return rc;
     } else {
         e = launch_sad(edge, d_a, d_b, d_out, n, 0, 0, (hipStream_t)stream);
     }
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "sad launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "sad launch", e);
 }
 
 int xTransformInvBatchDev(x266hip_ctx *ctx, int type, int size, const int16_t *d_in, int16_t *d_out, size_t n,
                           const uint32_t *d_offsets, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (type < 0 || type >= x266hip_ctx::kTypes) return fail(ctx, X266HIP_EINVAL, "xTransformInvBatchDev: unknown transform type");
-    if (size != 4 && size != 8 && size != 16 && !(size == 32 && type == X266_TR_DCT2))
-        return fail(ctx, X266HIP_EINVAL, "xTransformInvBatchDev: size must be 4, 8, 16 (or 32 for DCT-II)");
-    if (bad_ptrs(d_in, d_out, n)) return fail(ctx, X266HIP_EINVAL, "xTransformInvBatchDev: NULL or unaligned buffer");
-    if (n && ((uintptr_t)d_offsets & 3u)) return fail(ctx, X266HIP_EINVAL, "xTransformInvBatchDev: unaligned offset table");
-    if (!ctx->tr_tables_valid) return fail(ctx, X266HIP_EDEVICE, "xTransformInvBatchDev: the transform tables of this context are invalid (a failed xTransformSetMatrix)");
+    if (const char *why = args::transform_batch(type, size, d_in, d_out, n, d_offsets)) return refuse(ctx, __func__, why);
+    if (!ctx->tr_tables_valid) return tables_invalid(ctx, __func__);
     X_DEV(ctx);
     if (size == 32 && !d_offsets) return launch_op(ctx, 1, d_in, d_out, n, (hipStream_t)stream);
     const int l = size == 4 ? 0 : (size == 8 ? 1 : 2);
     const LaunchCfg cfg = cfg_for(ctx, 1);
-    hipError_t e = size == 32 ? launch_transform_small_inv(5, d_in, d_out, n, ctx->d_inv_lds, d_offsets, cfg, (hipStream_t)stream)
-                              : launch_transform_small_inv(l + 2, d_in, d_out, n, ctx->d_tr_inv[type][l], d_offsets, cfg, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "inverse transform launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "inverse transform launch", size == 32 ? launch_transform_small_inv(5, d_in, d_out, n, ctx->d_inv_lds, d_offsets, cfg, (hipStream_t)stream)
+                                                                : launch_transform_small_inv(l + 2, d_in, d_out, n, ctx->d_tr_inv[type][l], d_offsets, cfg, (hipStream_t)stream));
 }
 
 int xHipMeScratchReserve(x266hip_ctx *ctx, void *stream, int width, int height)
@@ -1297,27 +1068,28 @@ int xHipMeScratchReserve(x266hip_ctx *ctx, void *stream, int width, int height)
     return me_scratch_for(ctx, (hipStream_t)stream, width, height, &slot);
 }
 
+// ---- motion search and compensation ---------------------------------------------------------------------------------------------
+// The SATD searches keep their transformed current frame in the stream's scratch; planar = strides given, else frames of tiles.
+static int satd_search_call(x266hip_ctx *ctx, bool tiles, const uint8_t *d_cur, intptr_t cur_stride, const uint8_t *d_ref, intptr_t ref_stride, int width, int height,
+                            int range, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
+{
+    X_DEV(ctx);
+    x266hip_ctx::MeScratch *slot = nullptr;
+    if (const int rc = me_scratch_for(ctx, (hipStream_t)stream, width, height, &slot)) return rc;
+    (void)hipGetLastError();
+    const hipError_t e = launch_satd_search(d_cur, (long long)cur_stride, d_ref, (long long)ref_stride, width, height, range, d_best, d_costs, ctx->me_tile_rows, slot->p,
+                                            ctx->prop.multiProcessorCount, tiles, (hipStream_t)stream);
+    if (e == hipSuccess && slot->last_use && !slot->capturing_now) (void)hipEventRecord(slot->last_use, (hipStream_t)stream);   // what an eviction waits for
+    return launched(ctx, "search launch", e);
+}
+
 int xSatd8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_stride, const uint8_t *d_ref,
                       intptr_t ref_stride, int width, int height, int range, x266_me_result_t *d_best,
                       uint32_t *d_costs, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (!d_cur || !d_ref || !d_best) return fail(ctx, X266HIP_EINVAL, "xSatd8x8SearchDev: NULL buffer");
-    if (width < 8 || height < 8 || (width & 7) || (height & 7)) return fail(ctx, X266HIP_EINVAL, "xSatd8x8SearchDev: frame size must be a multiple of 8");
-    if (range < 1 || range > 64) return fail(ctx, X266HIP_EINVAL, "xSatd8x8SearchDev: range must be 1..64");
-    if (cur_stride < width || ref_stride < width + 2 * range) return fail(ctx, X266HIP_EINVAL, "xSatd8x8SearchDev: stride too small");
-    if (((uintptr_t)d_best & 7u) || ((uintptr_t)d_costs & 3u)) return fail(ctx, X266HIP_EINVAL, "xSatd8x8SearchDev: unaligned output");
-    X_DEV(ctx);
-    uint32_t *d_me_coef = nullptr;
-    x266hip_ctx::MeScratch *slot = nullptr;
-    if (const int rc = me_scratch_for(ctx, (hipStream_t)stream, width, height, &slot)) return rc;
-    d_me_coef = slot->p;
-    (void)hipGetLastError();
-    hipError_t e = launch_satd_search(d_cur, (long long)cur_stride, d_ref, (long long)ref_stride, width, height, range,
-                                      d_best, d_costs, ctx->me_tile_rows, d_me_coef, ctx->prop.multiProcessorCount, false, (hipStream_t)stream);
-    if (e == hipSuccess && slot->last_use && !slot->capturing_now) (void)hipEventRecord(slot->last_use, (hipStream_t)stream);   // what an eviction waits for
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "search launch", e);
-    return X266HIP_OK;
+    if (const char *why = args::plane_search(false, d_cur, cur_stride, d_ref, ref_stride, width, height, range, d_best, d_costs)) return refuse(ctx, __func__, why);
+    return satd_search_call(ctx, false, d_cur, cur_stride, d_ref, ref_stride, width, height, range, d_best, d_costs, stream);
 }
 
 int xSad8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_stride, const uint8_t *d_ref,
@@ -1325,178 +1097,86 @@ int xSad8x8SearchDev(x266hip_ctx *ctx, const uint8_t *d_cur, intptr_t cur_stride
                      uint32_t *d_costs, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (!d_cur || !d_ref || !d_best) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: NULL buffer");
-    if (width < 8 || height < 8 || (width & 7) || (height & 7)) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: frame size must be a multiple of 8");
-    if (range < 1 || range > 64) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: range must be 1..64");
-    if (cur_stride < width || ref_stride < width + 2 * range) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: stride too small");
-    if (((uintptr_t)d_cur & 3u) || (cur_stride & 3)) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: current frame must be 4-byte aligned with a stride multiple of 4");
-    if (((uintptr_t)d_best & 7u) || ((uintptr_t)d_costs & 3u)) return fail(ctx, X266HIP_EINVAL, "xSad8x8SearchDev: unaligned output");
+    if (const char *why = args::plane_search(true, d_cur, cur_stride, d_ref, ref_stride, width, height, range, d_best, d_costs)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_sad_search(d_cur, (long long)cur_stride, d_ref, (long long)ref_stride, width, height, range,
-                                     d_best, d_costs, ctx->me_tile_rows, false, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAD search launch", e);
-    return X266HIP_OK;
-}
-
-// ---- motion search and compensation on tiled frames ---------------------------------------------------------------------------
-// The searches' arguments: "" when they are valid, else what is wrong.  The inputs are read-only, so d_cur == d_ref is fine; the
-// outputs must not overlap either input frame, and the cost map's size must neither wrap size_t nor run past the address space.
-static const char *search_tiles_args(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height, int range,
-                                     const x266_me_result_t *d_best, const uint32_t *d_costs)
-{
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15)) return "width/height must be multiples of 16";
-    if (range < 1 || range > 64) return "range must be 1..64";
-    if (!d_cur || !d_ref || !d_best) return "NULL buffer";
-    if ((((uintptr_t)d_cur | (uintptr_t)d_ref) & 15u) || ((uintptr_t)d_best & 7u) || ((uintptr_t)d_costs & 3u)) return "unaligned buffer";
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_blocks = (size_t)(width / 8) * (size_t)(height / 8);
-    const size_t span = (size_t)(2 * range + 1);
-    size_t cost_bytes = 0;
-    uintptr_t end = 0;
-    if (d_costs && (__builtin_mul_overflow(n_blocks, span * span * 4, &cost_bytes) || __builtin_add_overflow((uintptr_t)d_costs, cost_bytes, &end)))
-        return "the cost map does not fit in the address space";
-    if (ranges_overlap(d_best, n_blocks * 8, d_cur, tile_bytes) || ranges_overlap(d_best, n_blocks * 8, d_ref, tile_bytes) ||
-        ranges_overlap(d_costs, cost_bytes, d_cur, tile_bytes) || ranges_overlap(d_costs, cost_bytes, d_ref, tile_bytes))
-        return "d_best / d_costs overlaps an input frame";
-    return "";
+    return launched(ctx, "SAD search launch", launch_sad_search(d_cur, (long long)cur_stride, d_ref, (long long)ref_stride, width, height, range,
+                                                                d_best, d_costs, ctx->me_tile_rows, false, (hipStream_t)stream));
 }
 
 int xSatd8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
                                int range, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (const char *why = search_tiles_args(d_cur, d_ref, width, height, range, d_best, d_costs); *why)
-        return fail(ctx, X266HIP_EINVAL, (std::string("xSatd8x8SearchFromTilesDev: ") + why).c_str());
-    X_DEV(ctx);
-    x266hip_ctx::MeScratch *slot = nullptr;
-    if (const int rc = me_scratch_for(ctx, (hipStream_t)stream, width, height, &slot)) return rc;
-    (void)hipGetLastError();
-    hipError_t e = launch_satd_search(reinterpret_cast<const uint8_t *>(d_cur), 0, reinterpret_cast<const uint8_t *>(d_ref), 0, width, height,
-                                      range, d_best, d_costs, ctx->me_tile_rows, slot->p, ctx->prop.multiProcessorCount, true, (hipStream_t)stream);
-    if (e == hipSuccess && slot->last_use && !slot->capturing_now) (void)hipEventRecord(slot->last_use, (hipStream_t)stream);   // what an eviction waits for
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "search launch", e);
-    return X266HIP_OK;
+    if (const char *why = args::tile_search(d_cur, d_ref, width, height, range, d_best, d_costs)) return refuse(ctx, __func__, why);
+    return satd_search_call(ctx, true, reinterpret_cast<const uint8_t *>(d_cur), 0, reinterpret_cast<const uint8_t *>(d_ref), 0, width, height, range, d_best, d_costs, stream);
 }
 
 int xSad8x8SearchFromTilesDev(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
                               int range, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (const char *why = search_tiles_args(d_cur, d_ref, width, height, range, d_best, d_costs); *why)
-        return fail(ctx, X266HIP_EINVAL, (std::string("xSad8x8SearchFromTilesDev: ") + why).c_str());
+    if (const char *why = args::tile_search(d_cur, d_ref, width, height, range, d_best, d_costs)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_sad_search(reinterpret_cast<const uint8_t *>(d_cur), 0, reinterpret_cast<const uint8_t *>(d_ref), 0, width, height,
-                                     range, d_best, d_costs, ctx->me_tile_rows, true, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAD search launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "SAD search launch", launch_sad_search(reinterpret_cast<const uint8_t *>(d_cur), 0, reinterpret_cast<const uint8_t *>(d_ref), 0, width, height,
+                                                                range, d_best, d_costs, ctx->me_tile_rows, true, (hipStream_t)stream));
 }
 
-// The three motion compensation calls share their argument rules and differ in the planes they write.
+// The six motion compensation calls share their argument rules and differ in the planes they write; the quarter-sample ones
+// (qpel) also hold every span against the end of the address space.
 typedef hipError_t (*mc_launch_fn)(const x266_ref_block_t *, const x266_me_result_t *, x266_ref_block_t *, int, int, hipStream_t);
 
-static int motion_comp_call(x266hip_ctx *ctx, const char *name, mc_launch_fn launch, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
+static int motion_comp_call(x266hip_ctx *ctx, const char *name, bool qpel, mc_launch_fn launch, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                             int width, int height, x266_ref_block_t *d_pred, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
-    if (!d_ref || !d_mv || !d_pred || ((((uintptr_t)d_ref | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_mv & 7u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
-    if (ranges_overlap(d_pred, tile_bytes, d_ref, tile_bytes) || ranges_overlap(d_pred, tile_bytes, d_mv, mv_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": d_pred overlaps d_ref or d_mv").c_str());
+    if (const char *why = args::motion_comp(qpel, d_ref, d_mv, width, height, d_pred)) return refuse(ctx, name, why);
     X_DEV(ctx);
-    hipError_t e = launch(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "motion compensation launch", e);
-    return X266HIP_OK;
+    return launched(ctx, qpel ? "quarter-sample motion compensation launch" : "motion compensation launch", launch(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream));
 }
 
 int xMotionCompLumaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                        x266_ref_block_t *d_pred, void *stream)
 {
-    return motion_comp_call(ctx, "xMotionCompLumaDev", launch_motion_comp_luma, d_ref, d_mv, width, height, d_pred, stream);
+    return motion_comp_call(ctx, __func__, false, launch_motion_comp_luma, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 int xMotionCompChromaDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                          x266_ref_block_t *d_pred, void *stream)
 {
-    return motion_comp_call(ctx, "xMotionCompChromaDev", launch_motion_comp_chroma, d_ref, d_mv, width, height, d_pred, stream);
+    return motion_comp_call(ctx, __func__, false, launch_motion_comp_chroma, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                    x266_ref_block_t *d_pred, void *stream)
 {
-    return motion_comp_call(ctx, "xMotionCompDev", launch_motion_comp, d_ref, d_mv, width, height, d_pred, stream);
-}
-
-// ---- quarter-sample prediction on tiled frames ---------------------------------------------------------------------------------------
-static bool span_fits(const void *p, size_t bytes)
-{
-    uintptr_t end;
-    return !__builtin_add_overflow((uintptr_t)p, bytes, &end);
-}
-
-// The argument rules of the integer calls, plus: a frame or record span must not run past the end of the address space.
-static int motion_comp_qpel_call(x266hip_ctx *ctx, const char *name, mc_launch_fn launch, const x266_ref_block_t *d_ref,
-                                 const x266_me_result_t *d_mv, int width, int height, x266_ref_block_t *d_pred, void *stream)
-{
-    if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
-    if (!d_ref || !d_mv || !d_pred || ((((uintptr_t)d_ref | (uintptr_t)d_pred)) & 15u) || ((uintptr_t)d_mv & 7u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
-    if (!span_fits(d_ref, tile_bytes) || !span_fits(d_pred, tile_bytes) || !span_fits(d_mv, mv_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": a buffer does not fit in the address space").c_str());
-    if (ranges_overlap(d_pred, tile_bytes, d_ref, tile_bytes) || ranges_overlap(d_pred, tile_bytes, d_mv, mv_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": d_pred overlaps d_ref or d_mv").c_str());
-    X_DEV(ctx);
-    hipError_t e = launch(d_ref, d_mv, d_pred, width, height, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "quarter-sample motion compensation launch", e);
-    return X266HIP_OK;
+    return motion_comp_call(ctx, __func__, false, launch_motion_comp, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 int xMotionCompQpelLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                            x266_ref_block_t *d_pred, void *stream)
 {
-    return motion_comp_qpel_call(ctx, "xMotionCompQpelLumaGpu", launch_mc_qpel_luma, d_ref, d_mv, width, height, d_pred, stream);
+    return motion_comp_call(ctx, __func__, true, launch_mc_qpel_luma, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 int xMotionCompQpelChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                              x266_ref_block_t *d_pred, void *stream)
 {
-    return motion_comp_qpel_call(ctx, "xMotionCompQpelChromaGpu", launch_mc_qpel_chroma, d_ref, d_mv, width, height, d_pred, stream);
+    return motion_comp_call(ctx, __func__, true, launch_mc_qpel_chroma, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv, int width, int height,
                        x266_ref_block_t *d_pred, void *stream)
 {
-    return motion_comp_qpel_call(ctx, "xMotionCompQpelGpu", launch_mc_qpel, d_ref, d_mv, width, height, d_pred, stream);
+    return motion_comp_call(ctx, __func__, true, launch_mc_qpel, d_ref, d_mv, width, height, d_pred, stream);
 }
 
 int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
                                    const x266_me_result_t *d_int, x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
 {
-    const char *name = "xSatd8x8RefineQpelFromTilesGpu: ";
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be multiples of 16").c_str());
-    if (!d_cur || !d_ref || !d_int || !d_best) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL buffer").c_str());
-    if ((((uintptr_t)d_cur | (uintptr_t)d_ref) & 15u) || (((uintptr_t)d_int | (uintptr_t)d_best) & 7u) || ((uintptr_t)d_costs & 3u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "unaligned buffer").c_str());
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_blocks = (size_t)(width / 8) * (size_t)(height / 8);
-    const size_t rec_bytes = n_blocks * 8, cost_bytes = d_costs ? n_blocks * 49 * 4 : 0;      // n_blocks < 2^56: no product wraps
-    if (!span_fits(d_cur, tile_bytes) || !span_fits(d_ref, tile_bytes) || !span_fits(d_int, rec_bytes) || !span_fits(d_best, rec_bytes) ||
-        !span_fits(d_costs, cost_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
-    if (ranges_overlap(d_best, rec_bytes, d_cur, tile_bytes) || ranges_overlap(d_best, rec_bytes, d_ref, tile_bytes) ||
-        (d_best != d_int && ranges_overlap(d_best, rec_bytes, d_int, rec_bytes)) ||
-        ranges_overlap(d_costs, cost_bytes, d_cur, tile_bytes) || ranges_overlap(d_costs, cost_bytes, d_ref, tile_bytes) ||
-        ranges_overlap(d_costs, cost_bytes, d_int, rec_bytes) || ranges_overlap(d_costs, cost_bytes, d_best, rec_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "an output overlaps another buffer (only d_best == d_int is allowed)").c_str());
+    if (const char *why = args::refine_qpel(d_cur, d_ref, width, height, d_int, d_best, d_costs)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_satd_refine_qpel(d_cur, d_ref, width, height, d_int, d_best, d_costs, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "quarter-sample refinement launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "quarter-sample refinement launch", launch_satd_refine_qpel(d_cur, d_ref, width, height, d_int, d_best, d_costs, (hipStream_t)stream));
 }
 
 // ---- in-loop deblocking of tiled frames (x266_deblock.hpp) ---------------------------------------------------------------------------
@@ -1505,179 +1185,86 @@ static int deblock_call(x266hip_ctx *ctx, const char *name, int planes, const x2
                         const x266_deblock_t *p, x266_ref_block_t *d_out, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (!p) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL parameter struct").c_str());
-    if (width <= 0 || height <= 0 || (width & 15) || (height & 15))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
-    if ((!p->d_qp && (p->qp < 0 || p->qp > 51)) || p->beta_offset_div2 < -6 || p->beta_offset_div2 > 6 || p->tc_offset_div2 < -6 || p->tc_offset_div2 > 6)
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": qp must be 0..51 (without d_qp) and the offsets -6..6").c_str());
-    if (!d_in || !d_out || ((((uintptr_t)d_in | (uintptr_t)d_out)) & 15u) || ((uintptr_t)p->d_mv & 7u) || ((uintptr_t)p->d_nnz & 3u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, mv_bytes = (size_t)(width / 8) * (size_t)(height / 8) * 8;
-    const size_t n_ctus = (size_t)((width + 63) / 64) * (size_t)((height + 63) / 64), tab_bytes = n_ctus * 6, nnz_bytes = n_ctus * 24;
-    if (!span_fits(d_in, tile_bytes) || !span_fits(d_out, tile_bytes) || !span_fits(p->d_mv, mv_bytes) || !span_fits(p->d_nnz, nnz_bytes) ||
-        !span_fits(p->d_class, tab_bytes) || !span_fits(p->d_intra, tab_bytes) || !span_fits(p->d_qp, tab_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": a buffer does not fit in the address space").c_str());
-    if ((d_out != d_in && ranges_overlap(d_out, tile_bytes, d_in, tile_bytes)) || ranges_overlap(d_out, tile_bytes, p->d_mv, mv_bytes) ||
-        ranges_overlap(d_out, tile_bytes, p->d_nnz, nnz_bytes) || ranges_overlap(d_out, tile_bytes, p->d_class, tab_bytes) ||
-        ranges_overlap(d_out, tile_bytes, p->d_intra, tab_bytes) || ranges_overlap(d_out, tile_bytes, p->d_qp, tab_bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": d_out overlaps an input (only d_out == d_in is allowed)").c_str());
+    if (const char *why = args::deblock(d_in, width, height, p, d_out)) return refuse(ctx, name, why);
     X_DEV(ctx);
-    hipError_t e = launch_deblock(planes, d_in, d_out, width, height, *p, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "deblocking launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "deblocking launch", launch_deblock(planes, d_in, d_out, width, height, *p, (hipStream_t)stream));
 }
 
 int xDeblockLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p, x266_ref_block_t *d_out,
                     void *stream)
 {
-    return deblock_call(ctx, "xDeblockLumaGpu", 1, d_in, width, height, p, d_out, stream);
+    return deblock_call(ctx, __func__, 1, d_in, width, height, p, d_out, stream);
 }
 
 int xDeblockChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p, x266_ref_block_t *d_out,
                       void *stream)
 {
-    return deblock_call(ctx, "xDeblockChromaGpu", 2, d_in, width, height, p, d_out, stream);
+    return deblock_call(ctx, __func__, 2, d_in, width, height, p, d_out, stream);
 }
 
 int xDeblockGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p, x266_ref_block_t *d_out,
                 void *stream)
 {
-    return deblock_call(ctx, "xDeblockGpu", 3, d_in, width, height, p, d_out, stream);
+    return deblock_call(ctx, __func__, 3, d_in, width, height, p, d_out, stream);
 }
 
 // ---- sample adaptive offset on tiled frames (x266_sao.hpp) -----------------------------------------------------------------------------
-struct SaoSpan {
-    const void *p;
-    size_t bytes;
-};
-
-static bool sao_frame_ok(int width, int height) { return width > 0 && height > 0 && !(width & 15) && !(height & 15); }
-
-// every output against every other buffer of the call; `n_out` leading entries of `spans` are the outputs (a NULL one has 0 bytes)
-static bool sao_outputs_overlap(const SaoSpan *spans, int n, int n_out)
-{
-    for (int o = 0; o < n_out; ++o)
-        for (int i = 0; i < n; ++i)
-            if (i != o && ranges_overlap(spans[o].p, spans[o].bytes, spans[i].p, spans[i].bytes)) return true;
-    return false;
-}
-
 static int sao_stats_call(x266hip_ctx *ctx, const char *name, bool decide, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width,
                           int height, int lambda_q4, x266_sao_t *d_param, int32_t *d_stats, void *stream)
 {
     if (!ctx) return X266HIP_EINVAL;
-    if (!sao_frame_ok(width, height)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": width/height must be multiples of 16").c_str());
-    if (lambda_q4 < 0 || lambda_q4 > 65535) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": lambda_q4 must be 0..65535").c_str());
-    if (!d_org || !d_dec || (decide ? !d_param : !d_stats) || ((((uintptr_t)d_org | (uintptr_t)d_dec)) & 15u) || ((uintptr_t)d_param & 7u) ||
-        ((uintptr_t)d_stats & 3u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": NULL or unaligned buffer").c_str());
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_ctus = (size_t)((width + 63) / 64) * (size_t)((height + 63) / 64);
-    const SaoSpan spans[4] = {{d_param, d_param ? n_ctus * 24 : 0}, {d_stats, d_stats ? n_ctus * 1152 : 0}, {d_org, tile_bytes}, {d_dec, tile_bytes}};
-    for (const SaoSpan &s : spans)
-        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": a buffer does not fit in the address space").c_str());
-    if (sao_outputs_overlap(spans, 4, 2)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + ": an output overlaps another buffer").c_str());
+    if (const char *why = args::sao_stats(decide, d_org, d_dec, width, height, lambda_q4, d_param, d_stats)) return refuse(ctx, name, why);
     X_DEV(ctx);
-    hipError_t e = launch_sao_stats(d_org, d_dec, width, height, lambda_q4, d_stats, d_param, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAO statistics launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "SAO statistics launch", launch_sao_stats(d_org, d_dec, width, height, lambda_q4, d_stats, d_param, (hipStream_t)stream));
 }
 
 int xSaoStatsGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, int32_t *d_stats, void *stream)
 {
-    return sao_stats_call(ctx, "xSaoStatsGpu", false, d_org, d_dec, width, height, 0, nullptr, d_stats, stream);
+    return sao_stats_call(ctx, __func__, false, d_org, d_dec, width, height, 0, nullptr, d_stats, stream);
 }
 
 int xSaoSearchGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, int lambda_q4,
                   x266_sao_t *d_param, int32_t *d_stats, void *stream)
 {
-    return sao_stats_call(ctx, "xSaoSearchGpu", true, d_org, d_dec, width, height, lambda_q4, d_param, d_stats, stream);
+    return sao_stats_call(ctx, __func__, true, d_org, d_dec, width, height, lambda_q4, d_param, d_stats, stream);
 }
 
 int xSaoDecideGpu(x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, int lambda_q4, x266_sao_t *d_param, void *stream)
 {
-    const char *name = "xSaoDecideGpu: ";
     if (!ctx) return X266HIP_EINVAL;
-    if (lambda_q4 < 0 || lambda_q4 > 65535) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "lambda_q4 must be 0..65535").c_str());
-    if (!d_stats || !d_param || ((uintptr_t)d_stats & 3u) || ((uintptr_t)d_param & 7u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
-    if (n_ctu > 0x7FFFFFFFull) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "n_ctu must be below 2^31").c_str());
-    const SaoSpan spans[2] = {{d_param, n_ctu * 24}, {d_stats, n_ctu * 1152}};
-    if (!span_fits(spans[0].p, spans[0].bytes) || !span_fits(spans[1].p, spans[1].bytes))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
-    if (sao_outputs_overlap(spans, 2, 1)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "d_param overlaps d_stats").c_str());
+    if (const char *why = args::sao_decide(d_stats, n_ctu, lambda_q4, d_param)) return refuse(ctx, __func__, why);
     if (n_ctu == 0) return X266HIP_OK;
     X_DEV(ctx);
-    hipError_t e = launch_sao_decide(d_stats, n_ctu, lambda_q4, d_param, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAO decision launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "SAO decision launch", launch_sao_decide(d_stats, n_ctu, lambda_q4, d_param, (hipStream_t)stream));
 }
 
 int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_sao_t *d_param, x266_ref_block_t *d_out,
                  void *stream)
 {
-    const char *name = "xSaoApplyGpu: ";
     if (!ctx) return X266HIP_EINVAL;
-    if (!sao_frame_ok(width, height)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be multiples of 16").c_str());
-    if (!d_in || !d_out || !d_param || ((((uintptr_t)d_in | (uintptr_t)d_out)) & 15u) || ((uintptr_t)d_param & 7u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
-    const size_t tile_bytes = (size_t)width * (size_t)height * 2, n_ctus = (size_t)((width + 63) / 64) * (size_t)((height + 63) / 64);
-    const SaoSpan spans[3] = {{d_out, tile_bytes}, {d_in, tile_bytes}, {d_param, n_ctus * 24}};
-    for (const SaoSpan &s : spans)
-        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
-    if (sao_outputs_overlap(spans, 3, 1))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "d_out overlaps d_in or d_param (in place is not possible)").c_str());
+    if (const char *why = args::sao_apply(d_in, width, height, d_param, d_out)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_sao_apply(d_in, d_out, width, height, d_param, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "SAO apply launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "SAO apply launch", launch_sao_apply(d_in, d_out, width, height, d_param, (hipStream_t)stream));
 }
 
 // ---- intra coding of tiled frames (intra_frame_kernels.hip) ------------------------------------------------------------------------------
 int xIntra32RefsFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_frame, int width, int height, int component, x266_intra_ref_t *d_refs,
                              void *stream)
 {
-    const char *name = "xIntra32RefsFromTilesGpu: ";
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 63) || (height & 63))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be positive multiples of 64").c_str());
-    if (component < 0 || component > 2) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "component must be 0, 1 or 2").c_str());
-    if (!d_frame || !d_refs || ((((uintptr_t)d_frame | (uintptr_t)d_refs)) & 15u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
-    const size_t n_sets = (size_t)(width / 64) * (size_t)(height / 64) * (component == 0 ? 4u : 1u);
-    const SaoSpan spans[2] = {{d_refs, n_sets * sizeof(x266_intra_ref_t)}, {d_frame, (size_t)width * (size_t)height * 2}};
-    for (const SaoSpan &s : spans)
-        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
-    if (sao_outputs_overlap(spans, 2, 1)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "d_refs overlaps d_frame").c_str());
+    if (const char *why = args::intra32_refs_from_tiles(d_frame, width, height, component, d_refs)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_intra32_refs_from_tiles(d_frame, width, height, component, d_refs, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra reference gather launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "intra reference gather launch", launch_intra32_refs_from_tiles(d_frame, width, height, component, d_refs, (hipStream_t)stream));
 }
 
 int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int width, int height, const uint8_t *d_qp, int qp, int rounding,
                          const uint8_t *d_mode_in, int16_t *d_level, uint32_t *d_nnz, uint8_t *d_mode, x266_ref_block_t *d_recon, void *stream)
 {
-    const char *name = "xIntra32CodeFrameGpu: ";
     if (!ctx) return X266HIP_EINVAL;
-    if (width <= 0 || height <= 0 || (width & 63) || (height & 63))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "width/height must be positive multiples of 64").c_str());
-    if (!quant_scalars_ok(d_qp, qp, rounding)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "qp must be 0..51 (without d_qp) and rounding 0..511").c_str());
-    if (!d_cur || !d_level || !d_mode || !d_recon || ((((uintptr_t)d_cur | (uintptr_t)d_level | (uintptr_t)d_recon)) & 15u) || ((uintptr_t)d_nnz & 3u))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "NULL or unaligned buffer").c_str());
-    const size_t n_ctus = (size_t)(width / 64) * (size_t)(height / 64), tile_bytes = (size_t)width * (size_t)height * 2;
-    // the four outputs first; d_mode_in may be d_mode itself (then it is not a buffer of its own) and d_nnz, d_qp, d_mode_in may be NULL
-    const bool in_place = d_mode_in == d_mode;
-    const SaoSpan spans[7] = {{d_recon, tile_bytes}, {d_level, n_ctus * 12288}, {d_mode, n_ctus * 6}, {d_nnz, d_nnz ? n_ctus * 24 : 0},
-                              {d_cur, tile_bytes}, {d_qp, d_qp ? n_ctus * 6 : 0}, {d_mode_in, d_mode_in && !in_place ? n_ctus * 6 : 0}};
-    for (const SaoSpan &s : spans)
-        if (!span_fits(s.p, s.bytes)) return fail(ctx, X266HIP_EINVAL, (std::string(name) + "a buffer does not fit in the address space").c_str());
-    if (sao_outputs_overlap(spans, 7, 4))
-        return fail(ctx, X266HIP_EINVAL, (std::string(name) + "an output overlaps another buffer (only d_mode == d_mode_in is allowed)").c_str());
+    if (const char *why = args::intra32_code_frame(d_cur, width, height, d_qp, qp, rounding, d_mode_in, d_level, d_nnz, d_mode, d_recon)) return refuse(ctx, __func__, why);
     X_DEV(ctx);
-    hipError_t e = launch_intra32_code_frame(d_cur, d_recon, d_level, d_nnz, d_qp, qp, rounding, d_mode_in, d_mode, width, height, ctx->d_fwd, ctx->d_inv_acc,
-                                             (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, X266HIP_EDEVICE, "intra frame coding launch", e);
-    return X266HIP_OK;
+    return launched(ctx, "intra frame coding launch", launch_intra32_code_frame(d_cur, d_recon, d_level, d_nnz, d_qp, qp, rounding, d_mode_in, d_mode, width, height, ctx->d_fwd,
+                                                                               ctx->d_inv_acc, (hipStream_t)stream));
 }
 
 // ---- host-pointer batch API --------------------------------------------------
