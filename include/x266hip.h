@@ -524,6 +524,58 @@ int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x2
 int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
                                    int width, int height, const x266_me_result_t *d_int, x266_me_result_t *d_best,
                                    uint32_t *d_costs, void *stream);
+/* Bi-directional inter prediction: a block predicted from TWO references (list 0 and list 1), one quarter-sample vector each,
+ * averaged at the intermediate precision, with explicit weights for fades.  8-bit 4:2:0 on tiled frames with the inter stage's
+ * edge rule; the filters, TL / TC, lg, o and the vector split are those of the quarter-sample calls above (the constants as
+ * recalled, unverified offline; the arithmetic here is the contract).
+ * Intermediate.  For one plane, one reference and one quarter-sample vector, with h the unshifted horizontal sum,
+ *   V(y, x) = (sum_k T[fy][k] * h(y + iy + k - o)) >> 6        (arithmetic shift)
+ * for all four phase classes alike: phase 0 multiplies by 64, so an integer vector gives V = 64 S, and the prediction of the uni
+ * calls above is clip8((V + 32) >> 6).  Luma V lies in -16830..33150 (both reached at phase (2, 2) on a 0 / 255 pattern that
+ * follows the sign of TL[2][k] * TL[2][j]) and chroma V in -5897..22217 (the largest value reached is 22216): V does NOT fit int16.
+ * Weights.  w and o are indexed [list][Y, U, V], log2_denom [luma, chroma]; w and o are -128..127, log2_denom 0..7.  The struct is
+ * read on the host at call time and passed by value into the launch: a captured graph replays the values it was captured with.
+ * wp == NULL means default weights.  With D = log2_denom + 6:
+ *   uni, list l:  clip8(((V_l * w_l + (1 << (D - 1))) >> D) + o_l)
+ *   bi:           clip8((V0 * w0 + V1 * w1 + ((o0 + o1 + 1) << D)) >> (D + 1))
+ *   default:      uni clip8((V + 32) >> 6), bi clip8((V0 + V1 + 64) >> 7)
+ * w = 1 << log2_denom with o = 0 reproduces the default for every input: V * 2^d + 2^(d+5) = 2^d (V + 32) and likewise for bi.
+ * All sums fit int32: |V * w| < 4.3e6 and the offset term is below 2^21.
+ * Pointers: tiles 16-byte aligned, records 8, uint32 outputs 4, direction bytes 1.  width, height positive multiples of 16.
+ * Nothing allocates; every call can be captured into a graph.  X266HIP_EINVAL as for the quarter-sample calls (NULL, alignment,
+ * size, a span that does not fit in the address space, an output overlapping anything) plus a wp field out of range and the
+ * scalars named below. */
+typedef struct x266_wp_t {
+    int16_t w[2][3];
+    int16_t o[2][3];
+    uint8_t log2_denom[2];
+} x266_wp_t;
+/* Motion compensation from two references.  d_dir[b] & 3 is the direction of 8x8 luma block b (raster order): 1 = list 0 only,
+ * 2 = list 1 only, 3 = both, 0 = the block's bytes of d_pred are left untouched (an intra block of a B-frame).  d_dir == NULL: every
+ * block is 3.  planes: 1 = m_Y, 2 = m_C, 3 = both in one launch, bit-identical to the two single-plane calls; m_I is never written.
+ * The luma block's vectors and direction also move its 4x4 U and V blocks.  d_ref0 == d_ref1 is allowed; d_pred must overlap
+ * nothing.  Both vector arrays are required whatever d_dir says (an unused record is read and ignored).  With wp == NULL a block
+ * of direction 1 is the uni quarter-sample prediction of (d_ref0, d_mv0) bit for bit, direction 2 likewise for list 1. */
+int xMotionCompBiQpelTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1,
+                           const x266_me_result_t *d_mv0, const x266_me_result_t *d_mv1, const uint8_t *d_dir,
+                           const x266_wp_t *wp, int planes, int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* The per-block choice between list 0, list 1 and both.  d_costs[3 b + k] = satd8x8(cur_block - P_k), P_0, P_1, P_2 the luma
+ * predictions of the call above under direction 1, 2, 3; satd8x8 is the metric of the searches.  d_dir[b] = the direction of the
+ * least of (c0, c1, c2 + bi_penalty), among equal values the earlier in that order.  bi_penalty is 0..65535, the caller's price for
+ * the second vector.  Either output may be NULL, not both; an output must overlap nothing. */
+int xSatd8x8BiCostsFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref0,
+                             const x266_ref_block_t *d_ref1, int width, int height, const x266_me_result_t *d_mv0,
+                             const x266_me_result_t *d_mv1, const x266_wp_t *wp, int bi_penalty, uint32_t *d_costs,
+                             uint8_t *d_dir, void *stream);
+/* Re-refinement of one list's vector with the other list's prediction held fixed.  The geometry of the quarter-sample refinement
+ * above: integer records d_int clamped to +-8191, 49 candidates q = 4m + (dx, dy), the same tie rule, the same d_costs[49 b + ...]
+ * layout (NULL allowed), d_best == d_int allowed.  cost(q) = satd8x8(cur_block - Bi), Bi the bi formula between the fixed list's V
+ * under d_mv_fix[b] (quarter samples, any int16 vector) on d_ref_fix and the candidate's V on d_ref.  list is 0 or 1 and names
+ * the list being refined: the candidate takes w[list], o[list], the fixed term the other list's. */
+int xSatd8x8RefineBiQpelFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref_fix,
+                                  const x266_me_result_t *d_mv_fix, const x266_ref_block_t *d_ref,
+                                  const x266_me_result_t *d_int, int list, const x266_wp_t *wp, int width, int height,
+                                  x266_me_result_t *d_best, uint32_t *d_costs, void *stream);
 /* In-loop deblocking of a tiled reconstructed frame (no upstream counterpart, as for the quantiser): HEVC's deblocking filter at
  * 8-bit depth, as recalled, unverified offline; the arithmetic here is the contract, not a standard text.  clip8 = clamp to 0..255,
  * clamp(v, lo, hi) as usual, shifts arithmetic.

@@ -20,6 +20,11 @@ class DeblockParams(ctypes.Structure):
                 ("qp", ctypes.c_int), ("beta_offset_div2", ctypes.c_int), ("tc_offset_div2", ctypes.c_int)]
 
 
+class WpParams(ctypes.Structure):
+    """x266_wp_t of include/x266hip.h"""
+    _fields_ = [("w", (ctypes.c_int16 * 3) * 2), ("o", (ctypes.c_int16 * 3) * 2), ("log2_denom", ctypes.c_uint8 * 2)]
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -114,6 +119,9 @@ def load_library(path=None):
     for name in ("xMotionCompQpelLumaGpu", "xMotionCompQpelChromaGpu", "xMotionCompQpelGpu"):
         getattr(L, name).argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xSatd8x8RefineQpelFromTilesGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]
+    L.xMotionCompBiQpelTiles.argtypes = [_P, _P, _P, _P, _P, _P, ctypes.POINTER(WpParams), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xSatd8x8BiCostsFromTiles.argtypes = [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.POINTER(WpParams), ctypes.c_int, _P, _P, _P]
+    L.xSatd8x8RefineBiQpelFromTiles.argtypes = [_P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.POINTER(WpParams), ctypes.c_int, ctypes.c_int, _P, _P, _P]
     for name in ("xDeblockLumaGpu", "xDeblockChromaGpu", "xDeblockGpu"):
         getattr(L, name).argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeblockParams), _P, _P]
     L.xSaoStatsGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -725,6 +733,81 @@ class Codec:
         cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
         costs = dcost.download(np.uint32, nb * 49).reshape(nb, 49) if want_costs else None
         return mv, cost, costs
+
+    @staticmethod
+    def wp_params(w=((1, 1, 1), (1, 1, 1)), o=((0, 0, 0), (0, 0, 0)), log2_denom=(0, 0)):
+        """an x266_wp_t: w and o indexed [list][Y, U, V], log2_denom [luma, chroma]; the defaults are the default weights"""
+        p = WpParams()
+        for l in range(2):
+            for c in range(3):
+                p.w[l][c], p.o[l][c] = int(w[l][c]), int(o[l][c])
+        p.log2_denom[0], p.log2_denom[1] = int(log2_denom[0]), int(log2_denom[1])
+        return p
+
+    def motion_comp_bi_qpel_dev(self, d_ref0, d_ref1, d_mv0, d_mv1, width, height, d_pred, d_dir=0, wp=None, planes=3, stream=0):
+        self._check(self.L.xMotionCompBiQpelTiles(self.ctx, d_ref0, d_ref1, d_mv0, d_mv1, d_dir or None, ctypes.byref(wp) if wp is not None else None,
+                                                  planes, width, height, d_pred, stream), "xMotionCompBiQpelTiles")
+
+    def satd8x8_bi_costs_dev(self, d_cur, d_ref0, d_ref1, width, height, d_mv0, d_mv1, d_costs=0, d_dir=0, wp=None, bi_penalty=0, stream=0):
+        self._check(self.L.xSatd8x8BiCostsFromTiles(self.ctx, d_cur, d_ref0, d_ref1, width, height, d_mv0, d_mv1, ctypes.byref(wp) if wp is not None else None,
+                                                    int(bi_penalty), d_costs or None, d_dir or None, stream), "xSatd8x8BiCostsFromTiles")
+
+    def satd8x8_refine_bi_qpel_dev(self, d_cur, d_ref_fix, d_mv_fix, d_ref, d_int, lst, width, height, d_best, d_costs=0, wp=None, stream=0):
+        self._check(self.L.xSatd8x8RefineBiQpelFromTiles(self.ctx, d_cur, d_ref_fix, d_mv_fix, d_ref, d_int, int(lst),
+                                                         ctypes.byref(wp) if wp is not None else None, width, height, d_best, d_costs or None, stream),
+                    "xSatd8x8RefineBiQpelFromTiles")
+
+    def _upload(self, a):
+        a = np.ascontiguousarray(a)
+        d = self.alloc(max(a.nbytes, 16))
+        d.upload(a)
+        return d
+
+    @staticmethod
+    def _records(mv, nb):
+        rec = np.zeros((nb, 4), np.int16)
+        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
+        return rec
+
+    def motion_comp_bi_qpel(self, ref0_tiles, ref1_tiles, mv0, mv1, w, h, direction=None, wp=None, planes=3, base=None):
+        """numpy convenience around xMotionCompBiQpelTiles: two reference tile arrays (ref1_tiles None: the same buffer as list 0), mv0 /
+        mv1 [nb, 2] int16 in quarter luma samples, direction uint8 [nb] or None (every block 3), wp from wp_params() or None ->
+        the predicted tile array; what the call does not write comes from `base` (a tile array; None: zeros)."""
+        ref0 = np.ascontiguousarray(ref0_tiles, np.uint8).ravel()
+        assert ref0.size == w * h * 2
+        nb = (h // 8) * (w // 8)
+        pred = np.zeros(ref0.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
+        d0 = self._upload(ref0)
+        d1 = d0 if ref1_tiles is None else self._upload(np.ascontiguousarray(ref1_tiles, np.uint8).ravel())
+        dm0, dm1, dp = self._upload(self._records(mv0, nb)), self._upload(self._records(mv1, nb)), self._upload(pred)
+        dd = None if direction is None else self._upload(np.asarray(direction, np.uint8).reshape(nb))
+        self.motion_comp_bi_qpel_dev(d0.ptr, d1.ptr, dm0.ptr, dm1.ptr, w, h, dp.ptr, 0 if dd is None else dd.ptr, wp, planes)
+        self.stream_sync()
+        return dp.download(np.uint8, pred.size)
+
+    def satd8x8_bi_costs(self, cur_tiles, ref0_tiles, ref1_tiles, w, h, mv0, mv1, wp=None, bi_penalty=0):
+        """numpy convenience around xSatd8x8BiCostsFromTiles -> (costs [nb, 3] uint32, direction [nb] uint8)"""
+        nb = (h // 8) * (w // 8)
+        dc, d0, d1 = (self._upload(np.ascontiguousarray(t, np.uint8).ravel()) for t in (cur_tiles, ref0_tiles, ref1_tiles))
+        dm0, dm1 = self._upload(self._records(mv0, nb)), self._upload(self._records(mv1, nb))
+        dk, dd = self.alloc(nb * 12), self.alloc(max(nb, 16))
+        self.satd8x8_bi_costs_dev(dc.ptr, d0.ptr, d1.ptr, w, h, dm0.ptr, dm1.ptr, dk.ptr, dd.ptr, wp, bi_penalty)
+        self.stream_sync()
+        return dk.download(np.uint32, nb * 3).reshape(nb, 3), dd.download(np.uint8, nb)
+
+    def satd8x8_refine_bi_qpel(self, cur_tiles, ref_fix_tiles, mv_fix, ref_tiles, mv_int, lst, w, h, wp=None, want_costs=False):
+        """numpy convenience around xSatd8x8RefineBiQpelFromTiles: mv_fix [nb, 2] int16 in quarter samples, mv_int [nb, 2] integer vectors
+        of the list `lst` being refined -> (mv [nb, 2] int16 in quarter samples, cost [nb] uint32, costs [nb, 49] or None)."""
+        nb = (h // 8) * (w // 8)
+        dc, df, dr = (self._upload(np.ascontiguousarray(t, np.uint8).ravel()) for t in (cur_tiles, ref_fix_tiles, ref_tiles))
+        dmf, di, db = self._upload(self._records(mv_fix, nb)), self._upload(self._records(mv_int, nb)), self.alloc(nb * 8)
+        dcost = self.alloc(nb * 49 * 4) if want_costs else None
+        self.satd8x8_refine_bi_qpel_dev(dc.ptr, df.ptr, dmf.ptr, dr.ptr, di.ptr, lst, w, h, db.ptr, dcost.ptr if want_costs else 0, wp)
+        self.stream_sync()
+        raw = db.download(np.uint8, nb * 8)
+        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
+        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
+        return mv, cost, dcost.download(np.uint32, nb * 49).reshape(nb, 49) if want_costs else None
 
     @staticmethod
     def deblock_params(d_class=0, d_intra=0, d_nnz=0, d_qp=0, d_mv=0, qp=0, beta_offset_div2=0, tc_offset_div2=0):

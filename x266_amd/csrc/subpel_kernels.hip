@@ -1,6 +1,7 @@
 // subpel_kernels.hip -- quarter-sample inter prediction on tiled frames (the convention of include/x266hip.h): fractional motion
 // compensation of luma and 4:2:0 chroma (xMotionCompQpelLumaGpu / ChromaGpu / Gpu) and the quarter-sample SATD refinement of
-// integer vectors (xSatd8x8RefineQpelFromTilesGpu).  The filters and their rounding are x266_interp.hpp's, one copy for all four.
+// integer vectors (xSatd8x8RefineQpelFromTilesGpu), and their bi-directional counterparts from two references (xMotionCompBiQpelTiles,
+// xSatd8x8BiCostsFromTiles, xSatd8x8RefineBiQpelFromTiles).  The filters and their rounding are x266_interp.hpp's, one copy for all.
 //
 // Both stages are separable and run the same way: the lanes of a group each form the unshifted horizontal sums of ONE row of the
 // block's window (one load deep, not a chain of dependent row gathers per lane), park them as int16 in a wave-private LDS slot, and
@@ -134,6 +135,211 @@ __global__ __launch_bounds__(192) void mc_qpel_kernel(const x266_ref_block_t *__
     }
 }
 
+// ---- bi-directional motion compensation ---------------------------------------------------------------------------------------------
+// The unrounded V (x266_interp.hpp) of a lane's four outputs from BOTH references: the group's lanes as in mc_qpel_block, one slot
+// per list.  Both lists' row loads are issued before the first horizontal stage, so the two fetches overlap.
+template <bool CHROMA>
+struct WindowRow { const uint8_t *row; int xs, fx, fy; };
+
+template <bool CHROMA>
+__device__ __forceinline__ WindowRow<CHROMA> window_row(const x266_ref_block_t *ref, x266_me_result_t r, int height, int tiles_x, int tx, int ty, int blk, int l)
+{
+    typedef Interp<CHROMA> I;
+    constexpr int edge = CHROMA ? 4 : 8, lg = I::kLog2Phases;
+    const int ph = CHROMA ? height >> 1 : height;
+    int sy = (ty * 2 + (blk >> 1)) * edge + (r.mvy >> lg) - I::kBefore + l;
+    sy = sy < 0 ? 0 : (sy > ph - 1 ? ph - 1 : sy);
+    WindowRow<CHROMA> s;
+    s.row = reinterpret_cast<const uint8_t *>(ref) + (CHROMA ? 256 : 0) + (size_t)(sy >> (CHROMA ? 3 : 4)) * (size_t)tiles_x * 512 + (sy & (CHROMA ? 7 : 15)) * 16;
+    s.xs = (tx * 2 + (blk & 1)) * edge + (r.mvx >> lg) - I::kBefore;
+    s.fx = r.mvx & ((1 << lg) - 1);
+    s.fy = r.mvy & ((1 << lg) - 1);
+    return s;
+}
+
+// the vertical stage of the lane's four outputs (row l >> 1, half l & 1 of the block) over the group's slot, unrounded
+template <bool CHROMA>
+__device__ __forceinline__ void vertical_v4(const v4i *slot, int fy, int l, int (&v)[4])
+{
+    typedef Interp<CHROMA> I;
+    int t[8];
+    interp_taps<CHROMA>(fy, t);
+    const int y = l >> 1, half = l & 1;
+    uint2 rows[I::kTaps];
+#pragma unroll
+    for (int k = 0; k < I::kTaps; ++k) {
+        const v4i r = slot[y + k];
+        rows[k] = half ? make_uint2((uint32_t)r[2], (uint32_t)r[3]) : make_uint2((uint32_t)r[0], (uint32_t)r[1]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        int col[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < I::kTaps; ++k) col[k] = hsum_of(c < 2 ? rows[k].x : rows[k].y, c & 1);
+        v[c] = interp_vertical_v<CHROMA>(col, t);
+    }
+}
+
+// index of 8x8 luma block `blk` of tile `tile` in the raster order of blocks
+__device__ __forceinline__ size_t block_of_tile(size_t tile, int tiles_x, int blk, int *tx, int *ty)
+{
+    const size_t y = tile / (size_t)tiles_x, x = tile - y * (size_t)tiles_x;
+    *tx = (int)x;
+    *ty = (int)y;
+    return (y * 2 + (size_t)(blk >> 1)) * (size_t)(2 * tiles_x) + x * 2 + (size_t)(blk & 1);
+}
+
+template <bool CHROMA>
+__device__ __forceinline__ void bi_block_v(const x266_ref_block_t *__restrict__ ref0, const x266_ref_block_t *__restrict__ ref1, x266_me_result_t r0,
+                                           x266_me_result_t r1, int width, int height, int tiles_x, int tx, int ty, int blk, int l, v4i *slot0, v4i *slot1,
+                                           int (&v0)[4], int (&v1)[4])
+{
+    const WindowRow<CHROMA> s0 = window_row<CHROMA>(ref0, r0, height, tiles_x, tx, ty, blk, l), s1 = window_row<CHROMA>(ref1, r1, height, tiles_x, tx, ty, blk, l);
+    uint32_t w0[4], w1[4];
+    load_window_row<CHROMA>(s0.row, s0.xs, width, w0);
+    load_window_row<CHROMA>(s1.row, s1.xs, width, w1);
+    int t[8], h[8];
+    interp_taps<CHROMA>(s0.fx, t);
+    interp_hsums<CHROMA>(w0, t, h);
+    slot0[l] = pack_hsums(h);
+    interp_taps<CHROMA>(s1.fx, t);
+    interp_hsums<CHROMA>(w1, t, h);
+    slot1[l] = pack_hsums(h);
+    wave_lds_sync();
+    vertical_v4<CHROMA>(slot0, s0.fy, l, v0);
+    vertical_v4<CHROMA>(slot1, s1.fy, l, v1);
+}
+
+// One block of one plane from two references: the lanes, slots and stores of mc_qpel_block, two slots per group.  A block of
+// direction 0 stores nothing (its lanes still take part in the stages: an unused list's record is any int16 vector, and every
+// read is clamped into the frame).
+template <bool CHROMA>
+__device__ __forceinline__ void mc_bi_block(const x266_ref_block_t *__restrict__ ref0, const x266_ref_block_t *__restrict__ ref1,
+                                            const x266_me_result_t *__restrict__ mv0, const x266_me_result_t *__restrict__ mv1, const uint8_t *__restrict__ dir,
+                                            const x266_wp_t &wp, x266_ref_block_t *__restrict__ pred, int width, int height, int tiles_x, size_t tile, int blk,
+                                            int l, v4i *slot0, v4i *slot1)
+{
+    constexpr int edge = CHROMA ? 4 : 8;
+    int tx, ty;
+    const size_t b = block_of_tile(tile, tiles_x, blk, &tx, &ty);
+    int v0[4], v1[4];
+    bi_block_v<CHROMA>(ref0, ref1, mv0[b], mv1[b], width, height, tiles_x, tx, ty, blk, l, slot0, slot1, v0, v1);
+    const int d = dir ? dir[b] & 3 : 3;
+    if (d == 0) return;
+    uint32_t out = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out |= (uint32_t)bi_combine(bi_terms(wp, d, CHROMA ? 1 + (c & 1) : 0), v0[c], v1[c]) << (8 * c);
+    const int y = l >> 1, half = l & 1;
+    uint8_t *dst = reinterpret_cast<uint8_t *>(pred + tile) + (CHROMA ? 256 : 0) + ((blk >> 1) * edge + y) * 16 + (blk & 1) * 8 + half * 4;
+    __builtin_nontemporal_store(out, reinterpret_cast<uint32_t *>(dst));
+}
+
+// the three launch shapes of the uni kernels above, with two slots per group
+__global__ __launch_bounds__(256) void mc_bi_luma_kernel(const x266_ref_block_t *__restrict__ ref0, const x266_ref_block_t *__restrict__ ref1,
+                                                         const x266_me_result_t *__restrict__ mv0, const x266_me_result_t *__restrict__ mv1,
+                                                         const uint8_t *__restrict__ dir, x266_wp_t wp, x266_ref_block_t *__restrict__ pred, int width, int height,
+                                                         int tiles_x, size_t n_tiles)
+{
+    __shared__ v4i slots[16][2][16];
+    const size_t tile = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= n_tiles) return;
+    const unsigned g = threadIdx.x >> 4;
+    mc_bi_block<false>(ref0, ref1, mv0, mv1, dir, wp, pred, width, height, tiles_x, tile, g & 3, threadIdx.x & 15, slots[g][0], slots[g][1]);
+}
+
+__global__ __launch_bounds__(256) void mc_bi_chroma_kernel(const x266_ref_block_t *__restrict__ ref0, const x266_ref_block_t *__restrict__ ref1,
+                                                           const x266_me_result_t *__restrict__ mv0, const x266_me_result_t *__restrict__ mv1,
+                                                           const uint8_t *__restrict__ dir, x266_wp_t wp, x266_ref_block_t *__restrict__ pred, int width, int height,
+                                                           int tiles_x, size_t n_tiles)
+{
+    __shared__ v4i slots[32][2][8];
+    const size_t tile = (size_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (tile >= n_tiles) return;
+    const unsigned g = threadIdx.x >> 3;
+    mc_bi_block<true>(ref0, ref1, mv0, mv1, dir, wp, pred, width, height, tiles_x, tile, g & 3, threadIdx.x & 7, slots[g][0], slots[g][1]);
+}
+
+__global__ __launch_bounds__(192) void mc_bi_kernel(const x266_ref_block_t *__restrict__ ref0, const x266_ref_block_t *__restrict__ ref1,
+                                                    const x266_me_result_t *__restrict__ mv0, const x266_me_result_t *__restrict__ mv1,
+                                                    const uint8_t *__restrict__ dir, x266_wp_t wp, x266_ref_block_t *__restrict__ pred, int width, int height,
+                                                    int tiles_x, size_t n_tiles)
+{
+    __shared__ v4i luma_slots[8][2][16];
+    __shared__ v4i chroma_slots[8][2][8];
+    if (threadIdx.x < 128) {
+        const size_t tile = (size_t)blockIdx.x * 2 + (threadIdx.x >> 6);
+        if (tile >= n_tiles) return;
+        const unsigned g = threadIdx.x >> 4;
+        mc_bi_block<false>(ref0, ref1, mv0, mv1, dir, wp, pred, width, height, tiles_x, tile, g & 3, threadIdx.x & 15, luma_slots[g][0], luma_slots[g][1]);
+    } else {
+        const unsigned t = threadIdx.x - 128, g = t >> 3;
+        const size_t tile = (size_t)blockIdx.x * 2 + (t >> 5);
+        if (tile >= n_tiles) return;
+        mc_bi_block<true>(ref0, ref1, mv0, mv1, dir, wp, pred, width, height, tiles_x, tile, g & 3, t & 7, chroma_slots[g][0], chroma_slots[g][1]);
+    }
+}
+
+// ---- the three costs of a block: list 0, list 1, both --------------------------------------------------------------------------------
+// The luma lanes of mc_bi_luma_kernel.  Each lane holds four differences cur - P_k of one row half; the 8x8 Hadamard runs over the
+// group's 16 lanes: two stages inside the lane, one with lane ^ 1 (the other half of the row), three with lane ^ 2, 4, 8 (the
+// rows).  The sum of |coefficients| depends on neither the order nor the signs of the butterflies; cost = (sum + 2) >> 2 as
+// satd8x8.  The group's lane 0 writes the three costs and the direction of the least of (c0, c1, c2 + penalty), the earlier on a tie.
+__global__ __launch_bounds__(256) void satd_bi_costs_kernel(const x266_ref_block_t *__restrict__ cur, const x266_ref_block_t *__restrict__ ref0,
+                                                            const x266_ref_block_t *__restrict__ ref1, const x266_me_result_t *__restrict__ mv0,
+                                                            const x266_me_result_t *__restrict__ mv1, x266_wp_t wp, uint32_t penalty, uint32_t *__restrict__ costs,
+                                                            uint8_t *__restrict__ dir, int width, int height, int tiles_x, size_t n_tiles)
+{
+    __shared__ v4i slots[16][2][16];
+    const size_t tile = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= n_tiles) return;
+    const unsigned g = threadIdx.x >> 4;
+    const int blk = (int)(g & 3), l = (int)(threadIdx.x & 15);
+    int tx, ty;
+    const size_t b = block_of_tile(tile, tiles_x, blk, &tx, &ty);
+    int v0[4], v1[4];
+    bi_block_v<false>(ref0, ref1, mv0[b], mv1[b], width, height, tiles_x, tx, ty, blk, l, slots[g][0], slots[g][1], v0, v1);
+    const uint32_t cw = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(cur + tile) + ((blk >> 1) * 8 + (l >> 1)) * 16 + (blk & 1) * 8 + (l & 1) * 4);
+    uint32_t cost[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const BiTerms t = bi_terms(wp, k + 1, 0);
+        int d[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[c] = (int)((cw >> (8 * c)) & 255u) - bi_combine(t, v0[c], v1[c]);
+        const int a0 = d[0] + d[1], a1 = d[0] - d[1], a2 = d[2] + d[3], a3 = d[2] - d[3];
+        d[0] = a0 + a2;
+        d[1] = a1 + a3;
+        d[2] = a0 - a2;
+        d[3] = a1 - a3;
+#pragma unroll
+        for (int m = 1; m <= 8; m <<= 1)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int o = __shfl_xor(d[c], m);
+                d[c] = (l & m) ? o - d[c] : d[c] + o;
+            }
+        uint32_t sum = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sum += (uint32_t)(d[c] < 0 ? -d[c] : d[c]);
+#pragma unroll
+        for (int m = 1; m <= 8; m <<= 1) sum += (uint32_t)__shfl_xor((int)sum, m);
+        cost[k] = (sum + 2) >> 2;
+    }
+    if (l == 0) {
+        if (costs) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) store_result4(costs + b * 3 + k, cost[k]);
+        }
+        if (dir) {
+            uint32_t least = cost[0];
+            uint8_t best = 1;
+            if (cost[1] < least) { least = cost[1]; best = 2; }
+            if (cost[2] + penalty < least) best = 3;
+            dir[b] = best;
+        }
+    }
+}
+
 // ---- quarter-sample refinement ------------------------------------------------------------------------------------------------------
 // One wave per 8x8 block.  All 49 candidates q = 4 m + (dx, dy), dx, dy in -3..3, read one 16x16 window of the reference, rows
 // and columns -4..11 around the block moved by m: dx < 0 has integer part m - 1 and phase dx + 4, dx >= 0 integer part m and
@@ -152,20 +358,43 @@ struct RefineSlot {
     v4i hs[7][16];              // [dx + 3][window row]: 8 int16 sums
 };
 
-__global__ __launch_bounds__(64 * kRefineWavesPerWg) void satd_refine_qpel_kernel(const x266_ref_block_t *cur,
-                                                                                   const x266_ref_block_t *ref, int width, int height,
-                                                                                   int tiles_x, const x266_me_result_t *mv_int,
-                                                                                   x266_me_result_t *best, uint32_t *__restrict__ costs, size_t n_blocks)
+// The body of both refinements.  BI: the cost is that of the bi prediction between the candidate and the fixed list's block
+// (ref_fix under mv_fix[b], any int16 quarter-sample vector).  Step 0 forms the fixed list's 8x8 V block: lanes 0..14 each form the
+// sums of one window row into hs[0] (which step 2 overwrites later), then lane L takes sample (L >> 3, L & 7) and parks
+// V_fix * w_fix + add in 32 bits (V does not fit int16) in fixed[L], so that step 3 adds V_cand * w_cand and rounds.
+template <bool BI>
+__device__ __forceinline__ void refine_qpel_body(const x266_ref_block_t *cur, const x266_ref_block_t *ref, int width, int height, int tiles_x,
+                                                 const x266_me_result_t *mv_int, x266_me_result_t *best, uint32_t *__restrict__ costs, size_t b, int lane,
+                                                 RefineSlot &s, const x266_ref_block_t *ref_fix, const x266_me_result_t *mv_fix, const x266_wp_t &wp, int list,
+                                                 int *fixed)
 {
-    __shared__ RefineSlot slots[kRefineWavesPerWg];
-    const int lane = threadIdx.x & 63;
-    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const size_t b = (size_t)blockIdx.x * kRefineWavesPerWg + wave_in_wg;
-    if (b >= n_blocks) return;
-    RefineSlot &s = slots[wave_in_wg];
     const size_t bxn = (size_t)tiles_x * 2, by = b / bxn, bx = b - by * bxn;
     const x266_me_result_t r = mv_int[b];
     const int mx = r.mvx < -8191 ? -8191 : (r.mvx > 8191 ? 8191 : r.mvx), my = r.mvy < -8191 ? -8191 : (r.mvy > 8191 ? 8191 : r.mvy);
+    int a_cand = 0, shift = 0;
+    if (BI) {                                                               // 0.
+        const BiTerms bt = bi_terms(wp, 3, 0);
+        a_cand = list ? bt.a1 : bt.a0;
+        shift = bt.shift;
+        const x266_me_result_t f = mv_fix[b];
+        if (lane < 15) {
+            const WindowRow<false> src = window_row<false>(ref_fix, f, height, tiles_x, (int)(bx >> 1), (int)(by >> 1), (int)((by & 1) * 2 + (bx & 1)), lane);
+            uint32_t w[4];
+            load_window_row<false>(src.row, src.xs, width, w);
+            int t[8], h[8];
+            interp_taps<false>(src.fx, t);
+            interp_hsums<false>(w, t, h);
+            s.hs[0][lane] = pack_hsums(h);
+        }
+        wave_lds_sync();
+        int t[8], col[8];
+        interp_taps<false>(f.mvy & 3, t);
+        const int16_t *hs16 = reinterpret_cast<const int16_t *>(s.hs[0]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) col[k] = hs16[((lane >> 3) + k) * 8 + (lane & 7)];
+        fixed[lane] = interp_vertical_v<false>(col, t) * (list ? bt.a0 : bt.a1) + bt.add;
+        wave_lds_sync();                                                    // step 2 overwrites hs[0]
+    }
     {   // 1.
         int sy = (int)by * 8 + my - 4 + (lane >> 2);
         sy = sy < 0 ? 0 : (sy > height - 1 ? height - 1 : sy);
@@ -214,7 +443,8 @@ __global__ __launch_bounds__(64 * kRefineWavesPerWg) void satd_refine_qpel_kerne
             int col[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) col[k] = hsum_of((uint32_t)rows[y + k][x >> 1], x & 1);
-            d[y][x] = (int)(((x < 4 ? cw.x : cw.y) >> (8 * (x & 3))) & 255u) - interp_vertical<false>(col, t);
+            const int pred = BI ? bi_round(interp_vertical_v<false>(col, t) * a_cand + fixed[y * 8 + x], shift) : interp_vertical<false>(col, t);
+            d[y][x] = (int)(((x < 4 ? cw.x : cw.y) >> (8 * (x & 3))) & 255u) - pred;
         }
     }
 #pragma unroll
@@ -257,6 +487,34 @@ __global__ __launch_bounds__(64 * kRefineWavesPerWg) void satd_refine_qpel_kerne
         const uint32_t q = (uint32_t)(uint16_t)(4 * mx + win % 7 - 3) | (uint32_t)(uint16_t)(4 * my + win / 7 - 3) << 16;
         *reinterpret_cast<uint2 *>(best + b) = make_uint2(q, key >> 6);
     }
+}
+
+__global__ __launch_bounds__(64 * kRefineWavesPerWg) void satd_refine_qpel_kernel(const x266_ref_block_t *cur,
+                                                                                   const x266_ref_block_t *ref, int width, int height,
+                                                                                   int tiles_x, const x266_me_result_t *mv_int,
+                                                                                   x266_me_result_t *best, uint32_t *__restrict__ costs, size_t n_blocks)
+{
+    __shared__ RefineSlot slots[kRefineWavesPerWg];
+    const int lane = threadIdx.x & 63;
+    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const size_t b = (size_t)blockIdx.x * kRefineWavesPerWg + wave_in_wg;
+    if (b >= n_blocks) return;
+    refine_qpel_body<false>(cur, ref, width, height, tiles_x, mv_int, best, costs, b, lane, slots[wave_in_wg], nullptr, nullptr, x266_wp_t{}, 0, nullptr);
+}
+
+__global__ __launch_bounds__(64 * kRefineWavesPerWg) void satd_refine_bi_qpel_kernel(const x266_ref_block_t *cur, const x266_ref_block_t *ref_fix,
+                                                                                      const x266_me_result_t *mv_fix, const x266_ref_block_t *ref, int list,
+                                                                                      x266_wp_t wp, int width, int height, int tiles_x,
+                                                                                      const x266_me_result_t *mv_int, x266_me_result_t *best,
+                                                                                      uint32_t *__restrict__ costs, size_t n_blocks)
+{
+    __shared__ RefineSlot slots[kRefineWavesPerWg];
+    __shared__ int fixed[kRefineWavesPerWg][64];
+    const int lane = threadIdx.x & 63;
+    const unsigned wave_in_wg = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const size_t b = (size_t)blockIdx.x * kRefineWavesPerWg + wave_in_wg;
+    if (b >= n_blocks) return;
+    refine_qpel_body<true>(cur, ref, width, height, tiles_x, mv_int, best, costs, b, lane, slots[wave_in_wg], ref_fix, mv_fix, wp, list, fixed[wave_in_wg]);
 }
 
 typedef void (*mc_qpel_kernel_fn)(const x266_ref_block_t *, const x266_me_result_t *, x266_ref_block_t *, int, int, int, size_t);
@@ -303,6 +561,49 @@ hipError_t launch_satd_refine_qpel(const x266_ref_block_t *d_cur, const x266_ref
     if (hipError_t e = wave_grid(n_blocks, kRefineWavesPerWg, &wgs)) return e;
     hipLaunchKernelGGL(satd_refine_qpel_kernel, dim3(wgs), dim3(64 * kRefineWavesPerWg), 0, stream, d_cur, d_ref, width, height, tiles_x,
                        d_int, d_best, d_costs, n_blocks);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_bi_qpel(int planes, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1, const x266_me_result_t *d_mv0,
+                             const x266_me_result_t *d_mv1, const uint8_t *d_dir, const x266_wp_t &wp, x266_ref_block_t *d_pred, int width, int height,
+                             hipStream_t stream)
+{
+    const int tiles_x = width / 16;
+    const size_t n_tiles = (size_t)tiles_x * (size_t)(height / 16);
+    if (n_tiles == 0) return hipSuccess;
+    const unsigned tiles_per_wg = planes == 1 ? 4 : planes == 2 ? 8 : 2, threads = planes == 3 ? 192 : 256;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_tiles, tiles_per_wg, &wgs)) return e;
+    hipLaunchKernelGGL(planes == 1 ? mc_bi_luma_kernel : planes == 2 ? mc_bi_chroma_kernel : mc_bi_kernel, dim3(wgs), dim3(threads), 0, stream, d_ref0, d_ref1,
+                       d_mv0, d_mv1, d_dir, wp, d_pred, width, height, tiles_x, n_tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_satd_bi_costs(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1, int width, int height,
+                                const x266_me_result_t *d_mv0, const x266_me_result_t *d_mv1, const x266_wp_t &wp, int bi_penalty, uint32_t *d_costs,
+                                uint8_t *d_dir, hipStream_t stream)
+{
+    const int tiles_x = width / 16;
+    const size_t n_tiles = (size_t)tiles_x * (size_t)(height / 16);
+    if (n_tiles == 0) return hipSuccess;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_tiles, 4, &wgs)) return e;
+    hipLaunchKernelGGL(satd_bi_costs_kernel, dim3(wgs), dim3(256), 0, stream, d_cur, d_ref0, d_ref1, d_mv0, d_mv1, wp, (uint32_t)bi_penalty, d_costs, d_dir, width,
+                       height, tiles_x, n_tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_satd_refine_bi_qpel(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref_fix, const x266_me_result_t *d_mv_fix,
+                                      const x266_ref_block_t *d_ref, const x266_me_result_t *d_int, int list, const x266_wp_t &wp, int width, int height,
+                                      x266_me_result_t *d_best, uint32_t *d_costs, hipStream_t stream)
+{
+    const int tiles_x = width / 16;
+    const size_t n_blocks = (size_t)(width / 8) * (size_t)(height / 8);
+    if (n_blocks == 0) return hipSuccess;
+    unsigned wgs;
+    if (hipError_t e = wave_grid(n_blocks, kRefineWavesPerWg, &wgs)) return e;
+    hipLaunchKernelGGL(satd_refine_bi_qpel_kernel, dim3(wgs), dim3(64 * kRefineWavesPerWg), 0, stream, d_cur, d_ref_fix, d_mv_fix, d_ref, list, wp, width, height,
+                       tiles_x, d_int, d_best, d_costs, n_blocks);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // x266_args.hpp -- the argument rules of the device entry points of include/x266hip.h, host-only: plain C++17, no HIP, no context.
 //
-// Every `...Dev` / `...Gpu` call has one rule function here (calls with the same rules share one).  It takes the call's arguments
+// Every device entry point has one rule function here (calls with the same rules share one).  It takes the call's arguments
 // and returns the reason the call is refused, or nullptr when it is accepted; it reads nothing through the pointers and touches
 // no state, so tests/cpp/arg_rules_check.cpp holds the rules without a device.  x266hip_abi.hip turns a reason into
 // X266HIP_EINVAL and the text "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here.
@@ -312,6 +312,53 @@ inline const char *refine_qpel(const void *d_cur, const void *d_ref, int w, int 
     if (const char *why = frame(w, h, 16)) return why;
     const Buf b[] = {in("d_cur", d_cur, 16, tile_bytes(w, h)), in("d_ref", d_ref, 16, tile_bytes(w, h)), in("d_int", d_int, 8, blocks8(w, h) * 8),
                      out("d_best", d_best, 8, blocks8(w, h) * 8, "d_int"), opt(out("d_costs", d_costs, 4, blocks8(w, h) * 49 * 4))};   // n_blocks < 2^56: no product wraps
+    return check(b);
+}
+
+// the three bi-directional calls: wp NULL is the default, otherwise every field is held to its range
+constexpr const char *kWp = "a wp field is out of range (w, o -128..127, log2_denom 0..7)";
+inline bool wp_ok(const x266_wp_t *wp)
+{
+    if (!wp) return true;
+    for (int l = 0; l < 2; ++l)
+        for (int c = 0; c < 3; ++c)
+            if (wp->w[l][c] < -128 || wp->w[l][c] > 127 || wp->o[l][c] < -128 || wp->o[l][c] > 127) return false;
+    return wp->log2_denom[0] <= 7 && wp->log2_denom[1] <= 7;
+}
+// xMotionCompBiQpelTiles: the two references are read-only and may be one frame
+inline const char *mc_bi_qpel(const void *d_ref0, const void *d_ref1, const void *d_mv0, const void *d_mv1, const void *d_dir, const x266_wp_t *wp, int planes,
+                              int w, int h, const void *d_pred)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (planes < 1 || planes > 3) return "planes must be 1, 2 or 3";
+    if (!wp_ok(wp)) return kWp;
+    const Buf b[] = {in("d_ref0", d_ref0, 16, tile_bytes(w, h)), in("d_ref1", d_ref1, 16, tile_bytes(w, h)), in("d_mv0", d_mv0, 8, blocks8(w, h) * 8),
+                     in("d_mv1", d_mv1, 8, blocks8(w, h) * 8), opt(in("d_dir", d_dir, 1, blocks8(w, h))), out("d_pred", d_pred, 16, tile_bytes(w, h))};
+    return check(b);
+}
+// xSatd8x8BiCostsFromTiles: either output may be NULL, not both
+inline const char *bi_costs(const void *d_cur, const void *d_ref0, const void *d_ref1, int w, int h, const void *d_mv0, const void *d_mv1, const x266_wp_t *wp,
+                            int bi_penalty, const void *d_costs, const void *d_dir)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (bi_penalty < 0 || bi_penalty > 65535) return "bi_penalty must be 0..65535";
+    if (!wp_ok(wp)) return kWp;
+    if (!d_costs && !d_dir) return "d_costs and d_dir are both NULL";
+    const Buf b[] = {in("d_cur", d_cur, 16, tile_bytes(w, h)), in("d_ref0", d_ref0, 16, tile_bytes(w, h)), in("d_ref1", d_ref1, 16, tile_bytes(w, h)),
+                     in("d_mv0", d_mv0, 8, blocks8(w, h) * 8), in("d_mv1", d_mv1, 8, blocks8(w, h) * 8),
+                     opt(out("d_costs", d_costs, 4, blocks8(w, h) * 12)), opt(out("d_dir", d_dir, 1, blocks8(w, h)))};
+    return check(b);
+}
+// xSatd8x8RefineBiQpelFromTiles
+inline const char *refine_bi_qpel(const void *d_cur, const void *d_ref_fix, const void *d_mv_fix, const void *d_ref, const void *d_int, int list,
+                                  const x266_wp_t *wp, int w, int h, const void *d_best, const void *d_costs)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (list < 0 || list > 1) return "list must be 0 or 1";
+    if (!wp_ok(wp)) return kWp;
+    const Buf b[] = {in("d_cur", d_cur, 16, tile_bytes(w, h)), in("d_ref_fix", d_ref_fix, 16, tile_bytes(w, h)), in("d_mv_fix", d_mv_fix, 8, blocks8(w, h) * 8),
+                     in("d_ref", d_ref, 16, tile_bytes(w, h)), in("d_int", d_int, 8, blocks8(w, h) * 8),
+                     out("d_best", d_best, 8, blocks8(w, h) * 8, "d_int"), opt(out("d_costs", d_costs, 4, blocks8(w, h) * 49 * 4))};
     return check(b);
 }
 

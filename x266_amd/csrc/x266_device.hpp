@@ -245,6 +245,16 @@ hipError_t launch_mc_qpel(const x266_ref_block_t *d_ref, const x266_me_result_t 
                           hipStream_t stream);
 hipError_t launch_satd_refine_qpel(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref, int width, int height,
                                    const x266_me_result_t *d_int, x266_me_result_t *d_best, uint32_t *d_costs, hipStream_t stream);
+// bi-directional: planes 1 = m_Y, 2 = m_C, 3 = both; wp is never NULL here (the entry points fill in the default weights)
+hipError_t launch_mc_bi_qpel(int planes, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1, const x266_me_result_t *d_mv0,
+                             const x266_me_result_t *d_mv1, const uint8_t *d_dir, const x266_wp_t &wp, x266_ref_block_t *d_pred, int width, int height,
+                             hipStream_t stream);
+hipError_t launch_satd_bi_costs(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1, int width, int height,
+                                const x266_me_result_t *d_mv0, const x266_me_result_t *d_mv1, const x266_wp_t &wp, int bi_penalty, uint32_t *d_costs,
+                                uint8_t *d_dir, hipStream_t stream);
+hipError_t launch_satd_refine_bi_qpel(const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref_fix, const x266_me_result_t *d_mv_fix,
+                                      const x266_ref_block_t *d_ref, const x266_me_result_t *d_int, int list, const x266_wp_t &wp, int width, int height,
+                                      x266_me_result_t *d_best, uint32_t *d_costs, hipStream_t stream);
 // planes: 1 = m_Y, 2 = m_C, 3 = both in one launch
 hipError_t launch_deblock(int planes, const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const x266_deblock_t &p,
                           hipStream_t stream);

@@ -62,19 +62,54 @@ __device__ __forceinline__ void interp_hsums(const uint32_t (&w)[4], const int (
     }
 }
 
-// The vertical stage and the rounding of one sample: col[k] = the horizontal sum of the row under tap k.
+// The vertical stage of one sample, unrounded: col[k] = the horizontal sum of the row under tap k.  This is the header's
+// intermediate V (luma -16830..33150, chroma -5897..22217: it does NOT fit int16), what bi-prediction averages.
 template <bool CHROMA>
-__device__ __forceinline__ int interp_vertical(const int (&col)[8], const int (&t)[8])
+__device__ __forceinline__ int interp_vertical_v(const int (&col)[8], const int (&t)[8])
 {
     int s = 0;
 #pragma unroll
     for (int k = 0; k < Interp<CHROMA>::kTaps; ++k) s += t[k] * col[k];
-    const int v = (s >> 6) + 32;                                            // arithmetic: floors a negative sum
+    return s >> 6;                                                          // arithmetic: floors a negative sum
+}
+
+// The vertical stage and the rounding of one sample.
+template <bool CHROMA>
+__device__ __forceinline__ int interp_vertical(const int (&col)[8], const int (&t)[8])
+{
+    const int v = interp_vertical_v<CHROMA>(col, t) + 32;
     // clip8(v >> 6) with the clamp in front of the shift: v >> 6 < 0 exactly when v < 0, > 255 exactly when v > 255 * 64 + 63.  (A
     // clamp behind the shift is what the compiler packs two results at a time with v_ashr_pk_u8_i32, which writes one half of its
     // destination and keeps the other: on an MI355X the kept half carried the bits of a negative sum into the neighbouring bytes.)
     return (v < 0 ? 0 : (v > 16383 ? 16383 : v)) >> 6;
 }
+
+// The uni / bi combine of the header's x266_wp_t, ONE copy for the three bi-directional calls.  All three forms are
+//   clip8((V0 * a0 + V1 * a1 + add) >> shift)
+// with D = log2_denom + 6:   list 0 only  a0 = w0, a1 = 0,  add = 2^(D-1) + o0 * 2^D,      shift = D
+//                            list 1 only  a0 = 0,  a1 = w1, add = 2^(D-1) + o1 * 2^D,      shift = D
+//                            both         a0 = w0, a1 = w1, add = (o0 + o1 + 1) * 2^D,     shift = D + 1
+// ("+ o" behind a ">> D" is "+ o * 2^D" in front of it, exactly).  |V * w| < 4.3e6 and |add| < 2^21: everything fits int32.
+// comp = 0, 1, 2 for Y, U, V; dir = 1, 2, 3 as in d_dir.
+struct BiTerms { int a0, a1, add, shift; };
+
+__device__ __forceinline__ BiTerms bi_terms(const x266_wp_t &wp, int dir, int comp)
+{
+    const int D = (int)wp.log2_denom[comp != 0] + 6, w0 = wp.w[0][comp], w1 = wp.w[1][comp], o0 = wp.o[0][comp], o1 = wp.o[1][comp];
+    BiTerms t;
+    t.a0 = dir & 1 ? w0 : 0;
+    t.a1 = dir & 2 ? w1 : 0;
+    t.add = dir == 3 ? (o0 + o1 + 1) * (1 << D) : (1 << (D - 1)) + (dir & 1 ? o0 : o1) * (1 << D);
+    t.shift = dir == 3 ? D + 1 : D;
+    return t;
+}
+// the clamp in front of the shift, as in interp_vertical: x >> s < 0 exactly when x < 0, > 255 exactly when x > (256 << s) - 1
+__device__ __forceinline__ int bi_round(int x, int shift)
+{
+    const int top = (256 << shift) - 1;
+    return (x < 0 ? 0 : (x > top ? top : x)) >> shift;
+}
+__device__ __forceinline__ int bi_combine(const BiTerms &t, int v0, int v1) { return bi_round(v0 * t.a0 + v1 * t.a1 + t.add, t.shift); }
 
 // eight horizontal sums (they fit int16: luma -6120..22440, chroma -2550..18870) as four dwords of pairs, and one of them back
 __device__ __forceinline__ v4i pack_hsums(const int (&h)[8])

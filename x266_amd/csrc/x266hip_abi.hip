@@ -1179,6 +1179,47 @@ int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_c
     return launched(ctx, "quarter-sample refinement launch", launch_satd_refine_qpel(d_cur, d_ref, width, height, d_int, d_best, d_costs, (hipStream_t)stream));
 }
 
+// The bi-directional calls: wp is read here, on the host, and travels by value into the launch; NULL is w = 1, o = 0, log2_denom = 0,
+// which IS the default formula.
+static x266_wp_t wp_or_default(const x266_wp_t *wp)
+{
+    const x266_wp_t unit = {{{1, 1, 1}, {1, 1, 1}}, {{0, 0, 0}, {0, 0, 0}}, {0, 0}};
+    return wp ? *wp : unit;
+}
+
+int xMotionCompBiQpelTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1, const x266_me_result_t *d_mv0,
+                           const x266_me_result_t *d_mv1, const uint8_t *d_dir, const x266_wp_t *wp, int planes, int width, int height,
+                           x266_ref_block_t *d_pred, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::mc_bi_qpel(d_ref0, d_ref1, d_mv0, d_mv1, d_dir, wp, planes, width, height, d_pred)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "bi-directional motion compensation launch",
+                    launch_mc_bi_qpel(planes, d_ref0, d_ref1, d_mv0, d_mv1, d_dir, wp_or_default(wp), d_pred, width, height, (hipStream_t)stream));
+}
+
+int xSatd8x8BiCostsFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1, int width,
+                             int height, const x266_me_result_t *d_mv0, const x266_me_result_t *d_mv1, const x266_wp_t *wp, int bi_penalty,
+                             uint32_t *d_costs, uint8_t *d_dir, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::bi_costs(d_cur, d_ref0, d_ref1, width, height, d_mv0, d_mv1, wp, bi_penalty, d_costs, d_dir)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "bi-directional cost launch",
+                    launch_satd_bi_costs(d_cur, d_ref0, d_ref1, width, height, d_mv0, d_mv1, wp_or_default(wp), bi_penalty, d_costs, d_dir, (hipStream_t)stream));
+}
+
+int xSatd8x8RefineBiQpelFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref_fix, const x266_me_result_t *d_mv_fix,
+                                  const x266_ref_block_t *d_ref, const x266_me_result_t *d_int, int list, const x266_wp_t *wp, int width, int height,
+                                  x266_me_result_t *d_best, uint32_t *d_costs, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::refine_bi_qpel(d_cur, d_ref_fix, d_mv_fix, d_ref, d_int, list, wp, width, height, d_best, d_costs)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "bi-directional refinement launch",
+                    launch_satd_refine_bi_qpel(d_cur, d_ref_fix, d_mv_fix, d_ref, d_int, list, wp_or_default(wp), width, height, d_best, d_costs, (hipStream_t)stream));
+}
+
 // ---- in-loop deblocking of tiled frames (x266_deblock.hpp) ---------------------------------------------------------------------------
 // The three calls share their argument rules and differ in the planes they write (1 = m_Y, 2 = m_C, 3 = both).
 static int deblock_call(x266hip_ctx *ctx, const char *name, int planes, const x266_ref_block_t *d_in, int width, int height,
