@@ -692,6 +692,91 @@ int xSaoSearchGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_re
                   int lambda_q4, x266_sao_t *d_param, int32_t *d_stats, void *stream);
 int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_sao_t *d_param,
                  x266_ref_block_t *d_out, void *stream);
+/* Adaptive loop filter (ALF) of a tiled frame, the third in-loop filter (no upstream counterpart, as for the quantiser, the deblocking
+ * filter and SAO): VVC's ALF at 8-bit depth -- block classification, the clipped diamond filters, the encoder's statistics and a
+ * per-CTU decision --, as recalled, unverified offline; the arithmetic here is the contract, not a standard text.  clip8 = clamp to
+ * 0..255, clamp(v, lo, hi) as usual, shifts arithmetic.  Out of scope: the virtual boundaries of VVC's line-buffer rule, the 64
+ * fixed filter sets, the cross-component filter, the solve that turns statistics into coefficients (it stays on the host:
+ * xAlfSumStatsGpu gives it the frame totals), and any coefficient or clip-index rate beyond the per-CTU term of the decision.
+ * Planes.  width, height positive multiples of 16; luma is width x height (m_Y), U and V are width / 2 x height / 2 (the even and
+ * odd bytes of m_C); ceil(width / 64) x ceil(height / 64) CTUs in raster order, the right and bottom ones cut by the frame exactly
+ * as in xSaoStatsGpu; CTU t has up to 64 x 64 luma and 32 x 32 U and V samples.  r(x, y) of a PW x PH plane is the sample at
+ * (clamp(x, 0, PW - 1), clamp(y, 0, PH - 1)): every fetch clamps its own coordinates, x and y each on its own (edge replication).
+ * A neighbour in another CTU is an ordinary sample of the input frame.  m_I is never read or written.
+ * Classification.  Luma only.  One byte per 4x4 block, block (bx, by) at d_class[by (width / 4) + bx]: (width / 4) (height / 4)
+ * bytes.  The four sums run over the 32 positions (x, y) with 4 bx - 2 <= x <= 4 bx + 5, 4 by - 2 <= y <= 4 by + 5 and x + y even
+ * (the parity of the unclamped coordinates); with c = r(x, y):
+ *   V  += |2 c - r(x, y-1) - r(x, y+1)|          H  += |2 c - r(x-1, y) - r(x+1, y)|
+ *   D0 += |2 c - r(x-1, y-1) - r(x+1, y+1)|      D1 += |2 c - r(x+1, y-1) - r(x-1, y+1)|
+ * Each sum is at most 32 * 510 = 16320, so 32 bits hold every product below.  Then, in this order:
+ *   V > H:  (hv1, hv0, dirHV) = (V, H, 1),  otherwise (H, V, 3)
+ *   D0 > D1:  (d1, d0, dirD) = (D0, D1, 0),  otherwise (D1, D0, 2)
+ *   d1 hv0 > hv1 d0:  (m1, m0, dir1, dir2) = (d1, d0, dirD, dirHV),  otherwise (hv1, hv0, dirHV, dirD)
+ *   dirS = 2 if 2 m1 > 9 m0, else 1 if m1 > 2 m0, else 0
+ *   act = VAR[min(15, (H + V) >> 5)],  VAR[16] = {0, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 3, 4}
+ *   class = act + (dirS ? 5 (((dir1 & 1) << 1) + dirS) : 0), in 0..24
+ *   tr = TT[2 dir1 + (dir2 >> 1)],  TT[8] = {0, 1, 0, 2, 2, 3, 1, 3}
+ * The byte is class | tr << 5.  A byte read from a caller's d_class is decoded as class = min(b & 31, 24), tr = (b >> 5) & 3; no
+ * device byte is validated.
+ * Taps.  Tap i sits at P[i] = (dx, dy) and also covers its mirror (-dx, -dy).  Luma, the 7x7 diamond, 12 taps:
+ *   P[0..11] = (0,-3) (-1,-2) (0,-2) (1,-2) (-2,-1) (-1,-1) (0,-1) (1,-1) (2,-1) (-3,0) (-2,0) (-1,0)
+ * Chroma, the 5x5 diamond, 6 taps:  P[0..5] = (0,-2) (-1,-1) (0,-1) (1,-1) (-2,0) (-1,0).
+ * In a luma block with transposition tr, tap i sits at g_i = G_tr(P[i]): G_0 = (dx, dy), G_1 = (dy, dx), G_2 = (dx, -dy),
+ * G_3 = (dy, -dx).  Chroma has no classes and no transposition: g_i = P[i].
+ * Filters.  Coefficients are int8 with 7 fractional bits; a clip byte selects K[clip & 3], K[4] = {256, 32, 8, 2}; zero[] is not read.
+ * The caller passes device arrays of n_luma (0..8) luma sets -- one filter per class -- and of n_chroma (0..8) chroma alternatives.
+ * d_ctrl[3 t + m] is one byte per CTU t and component m (0 = Y, 1 = U, 2 = V): 0 copies; k >= 1 uses luma set k - 1 (m = 0) or
+ * chroma alternative k - 1 (m = 1, 2); k above the count copies.
+ * Apply.  Per sample c = r(p), with the set, class and transposition of its CTU and 4x4 block (chroma: the alternative of its CTU):
+ *   s = sum_i coef[i] (clamp(r(p + g_i) - c, -K_i, K_i) + clamp(r(p - g_i) - c, -K_i, K_i)),   out = clip8(c + ((s + 64) >> 7))
+ * |s| <= 12 * 128 * 512: 32 bits suffice.  Every in-frame sample of m_Y and m_C of d_out is written, filtered or copied.  Apply reads
+ * neighbours that other workgroups write: d_out overlapping d_in in any way is refused, as for xSaoApplyGpu.
+ * Statistics.  `org` is the source, `dec` the frame ALF will filter.  Per sample of dec: y = org - dec and
+ * E_i = r(p + g_i) + r(p - g_i) - 2 c, the unclipped tap, so the statistics are those of clip index 0.  Per CTU t the record at
+ * d_stats[2358 t] is 2358 int32 (9432 bytes): 25 luma class records of 92 words, then a U and a V record of 29 words.  A record
+ * holds, in this order: count; sum y^2; b_i = sum E_i y (12 or 6 words); A_ij = sum E_i E_j for i <= j, the upper triangle row by row
+ * (78 or 21 words).  The sums run over the CTU's in-frame samples of that class (luma, each block with its own transposition) or
+ * plane.  Every word of every record is written, zeros where nothing falls.  int32 is exact: |A| <= 4096 * 510^2 < 2^31,
+ * |b| <= 4096 * 510 * 255, sum y^2 <= 4096 * 255^2.
+ * Totals.  xAlfSumStatsGpu adds, word by word, the records of the CTUs whose d_mask byte is non-zero (d_mask NULL: all n_ctu) into
+ * the 2358 int64 words of d_total -- what the host downloads to solve for filters.  Integer sums: the result depends on nothing
+ * but its inputs.
+ * Decision.  The change of a record's squared error under coefficients c, in Q14 (coefficient units squared), read off the statistics:
+ *   cost(record, c) = sum_i c_i^2 A_ii + 2 sum_{i<j} c_i c_j A_ij - 256 sum_i c_i b_i
+ * Clip indices are ignored: the estimate is exact only for clip index 0 and before the rounding of (s + 64) >> 7.  All arithmetic is
+ * int64: whatever int32 words the record holds, a record's cost is below 2^14 * 2^31 * 144 + 2^15 * 2^31 * 12 < 2^53, 25 of them
+ * and the rate term (at most 65535 * 2^10 * 3) stay below 2^58.  lambda_q4 in 0..65535 as for SAO; ceil_log2(1) = 0, (2) = 1,
+ * (3, 4) = 2, (5..8) = 3.
+ *   Luma: J(off) = 0; J(set s) = sum over the 25 classes of cost(class record, coef[class] of set s) + (lambda_q4 << 10) ceil_log2(n_luma).
+ *   The least J wins; among equal J, off first, then the smaller s.  d_ctrl[3 t] = 0 for off, s + 1 for set s.
+ *   U and V: the same, each on its own record, over the chroma alternatives with ceil_log2(n_chroma), into d_ctrl[3 t + 1], [3 t + 2].
+ *   A component whose count is 0 (luma: the sum of the 25 counts) gets 0.
+ * With d_class == NULL xAlfStatsGpu and xAlfApplyGpu classify inside, bit-identical to xAlfClassifyGpu followed by the same call on
+ * its output.  Frames are 16-byte aligned, d_stats 4, d_total 8, d_luma and d_chroma 4, the byte arrays (d_class, d_mask, d_ctrl) 1.
+ * A set array is not looked at, and may be NULL, when its count is 0.  d_org == d_dec is allowed (both are read-only).
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError, for a NULL or misaligned pointer (d_mask, and d_class of
+ * the statistics and of apply, may be NULL), a bad size, a count outside 0..8, lambda_q4 outside 0..65535, n_ctu >= 2^31, a span that
+ * does not fit in the address space, or an output overlapping any other buffer of its call.  n_ctu == 0 returns 0 and launches
+ * nothing (d_total is then left as it was).  Nothing is allocated; every call can be captured into a graph. */
+typedef struct x266_alf_luma_t {
+    int8_t  coef[25][12];
+    uint8_t clip[25][12];
+} x266_alf_luma_t;                       /* 600 bytes */
+typedef struct x266_alf_chroma_t {
+    int8_t  coef[6];
+    uint8_t clip[6];
+    uint8_t zero[4];
+} x266_alf_chroma_t;                     /* 16 bytes */
+int xAlfClassifyGpu (x266hip_ctx *ctx, const x266_ref_block_t *d_dec, int width, int height, uint8_t *d_class, void *stream);
+int xAlfStatsGpu    (x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height,
+                     const uint8_t *d_class, int32_t *d_stats, void *stream);
+int xAlfSumStatsGpu (x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, const uint8_t *d_mask, int64_t *d_total,
+                     void *stream);
+int xAlfDecideGpu   (x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, const x266_alf_luma_t *d_luma, int n_luma,
+                     const x266_alf_chroma_t *d_chroma, int n_chroma, int lambda_q4, uint8_t *d_ctrl, void *stream);
+int xAlfApplyGpu    (x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const uint8_t *d_class,
+                     const x266_alf_luma_t *d_luma, int n_luma, const x266_alf_chroma_t *d_chroma, int n_chroma,
+                     const uint8_t *d_ctrl, x266_ref_block_t *d_out, void *stream);
 /* Sum of absolute differences of n_blocks pairs of edge x edge 8-bit blocks (edge in
  * {4, 8, 16, 32, 64}; each block edge*edge contiguous bytes, row-major; d_a and d_b 16-byte,
  * d_out 4-byte aligned): d_out[b] = sum |a - b|, exactly sad() of

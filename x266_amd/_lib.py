@@ -128,6 +128,11 @@ def load_library(path=None):
     L.xSaoDecideGpu.argtypes = [_P, _P, _SZ, ctypes.c_int, _P, _P]
     L.xSaoSearchGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]
     L.xSaoApplyGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
+    L.xAlfClassifyGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xAlfStatsGpu.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
+    L.xAlfSumStatsGpu.argtypes = [_P, _P, _SZ, _P, _P, _P]
+    L.xAlfDecideGpu.argtypes = [_P, _P, _SZ, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P]
+    L.xAlfApplyGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P]
     L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xIntra32CodeFrameGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
@@ -920,6 +925,111 @@ class Codec:
         d_par.upload(rec)
         d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
         self.sao_apply_dev(d_in.ptr, w, h, d_par.ptr, d_out.ptr)
+        self.stream_sync()
+        return d_out.download(np.uint8, src.size)
+
+    # ---- adaptive loop filter: 2358 int32 of statistics per CTU, one class byte per 4x4 luma block, 3 control bytes per CTU
+    ALF_CTU_WORDS = 2358
+
+    def alf_classify_dev(self, d_dec, width, height, d_class, stream=0):
+        self._check(self.L.xAlfClassifyGpu(self.ctx, d_dec, width, height, d_class, stream), "xAlfClassifyGpu")
+
+    def alf_stats_dev(self, d_org, d_dec, width, height, d_class, d_stats, stream=0):
+        self._check(self.L.xAlfStatsGpu(self.ctx, d_org, d_dec, width, height, d_class or None, d_stats, stream), "xAlfStatsGpu")
+
+    def alf_sum_stats_dev(self, d_stats, n_ctu, d_mask, d_total, stream=0):
+        self._check(self.L.xAlfSumStatsGpu(self.ctx, d_stats, n_ctu, d_mask or None, d_total, stream), "xAlfSumStatsGpu")
+
+    def alf_decide_dev(self, d_stats, n_ctu, d_luma, n_luma, d_chroma, n_chroma, lambda_q4, d_ctrl, stream=0):
+        self._check(self.L.xAlfDecideGpu(self.ctx, d_stats, n_ctu, d_luma or None, int(n_luma), d_chroma or None, int(n_chroma), int(lambda_q4), d_ctrl,
+                                         stream), "xAlfDecideGpu")
+
+    def alf_apply_dev(self, d_in, width, height, d_class, d_luma, n_luma, d_chroma, n_chroma, d_ctrl, d_out, stream=0):
+        self._check(self.L.xAlfApplyGpu(self.ctx, d_in, width, height, d_class or None, d_luma or None, int(n_luma), d_chroma or None, int(n_chroma),
+                                        d_ctrl, d_out, stream), "xAlfApplyGpu")
+
+    @staticmethod
+    def alf_pack_filters(luma_coef=None, luma_clip=None, chroma_coef=None, chroma_clip=None):
+        """filter sets from numpy arrays -> (x266_alf_luma_t array as uint8 [n_luma, 600], x266_alf_chroma_t array as uint8 [n_chroma, 16]).
+        luma_coef: int [n_luma, 25, 12] in -128..127, luma_clip: the clip indices 0..3 of the same shape (None: 0); chroma_coef:
+        int [n_chroma, 6], chroma_clip likewise; a missing kind gives an array of no sets."""
+        def pack(coef, clip, shape, size):
+            if coef is None:
+                return np.zeros((0, size), np.uint8)
+            c = np.asarray(coef, np.int64).reshape((-1,) + shape)
+            k = np.zeros_like(c) if clip is None else np.asarray(clip, np.int64).reshape(c.shape)
+            assert c.shape[0] <= 8 and c.min() >= -128 and c.max() <= 127 and k.min() >= 0 and k.max() <= 255
+            n, taps = c.shape[0], int(np.prod(shape))
+            out = np.zeros((n, size), np.uint8)
+            out[:, :taps] = c.astype(np.int8).reshape(n, taps).view(np.uint8)
+            out[:, taps:2 * taps] = k.astype(np.uint8).reshape(n, taps)
+            return out
+        return pack(luma_coef, luma_clip, (25, 12), 600), pack(chroma_coef, chroma_clip, (6,), 16)
+
+    def _alf_sets(self, luma, chroma):
+        luma = np.zeros((0, 600), np.uint8) if luma is None else np.ascontiguousarray(luma, np.uint8).reshape(-1, 600)
+        chroma = np.zeros((0, 16), np.uint8) if chroma is None else np.ascontiguousarray(chroma, np.uint8).reshape(-1, 16)
+        d_luma, d_chroma = self.alloc(max(luma.nbytes, 16)), self.alloc(max(chroma.nbytes, 16))
+        d_luma.upload(luma if luma.size else np.zeros(16, np.uint8))
+        d_chroma.upload(chroma if chroma.size else np.zeros(16, np.uint8))
+        return d_luma, luma.shape[0], d_chroma, chroma.shape[0]
+
+    def alf_classify(self, tiles, w, h):
+        """numpy convenience around xAlfClassifyGpu: a tile array -> the class bytes uint8 [h / 4, w / 4] (class | tr << 5)"""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        assert src.size == w * h * 2
+        d_in, d_cls = self.alloc(src.nbytes), self.alloc(max((w // 4) * (h // 4), 16))
+        d_in.upload(src)
+        self.alf_classify_dev(d_in.ptr, w, h, d_cls.ptr)
+        self.stream_sync()
+        return d_cls.download(np.uint8, (w // 4) * (h // 4)).reshape(h // 4, w // 4)
+
+    def alf_stats(self, org_tiles, dec_tiles, w, h, classes=None):
+        """numpy convenience around xAlfStatsGpu: the source and the decoded tile array (and a class map, None: classified inside)
+        -> int32 [n_ctu, 2358]"""
+        n = self.ctu_count(w, h)
+        d_org, d_dec = self._sao_frames(org_tiles, dec_tiles, w, h)
+        d_cls = None if classes is None else self._upload(np.ascontiguousarray(classes, np.uint8).ravel())
+        d_stats = self.alloc(n * self.ALF_CTU_WORDS * 4)
+        self.alf_stats_dev(d_org.ptr, d_dec.ptr, w, h, 0 if d_cls is None else d_cls.ptr, d_stats.ptr)
+        self.stream_sync()
+        return d_stats.download(np.int32, n * self.ALF_CTU_WORDS).reshape(n, self.ALF_CTU_WORDS)
+
+    def alf_sum_stats(self, stats, mask=None):
+        """numpy convenience around xAlfSumStatsGpu: int32 [n_ctu, 2358] (and a byte per CTU, None: all) -> int64 [2358]"""
+        st = np.ascontiguousarray(stats, np.int32).reshape(-1, self.ALF_CTU_WORDS)
+        n = st.shape[0]
+        d_stats, d_total = self.alloc(max(st.nbytes, 16)), self.alloc(self.ALF_CTU_WORDS * 8)
+        d_stats.upload(st)
+        d_total.upload(np.zeros(self.ALF_CTU_WORDS, np.int64))
+        d_mask = None if mask is None else self._upload(np.ascontiguousarray(mask, np.uint8).reshape(n))
+        self.alf_sum_stats_dev(d_stats.ptr, n, 0 if d_mask is None else d_mask.ptr, d_total.ptr)
+        self.stream_sync()
+        return d_total.download(np.int64, self.ALF_CTU_WORDS)
+
+    def alf_decide(self, stats, luma, chroma, lambda_q4):
+        """numpy convenience around xAlfDecideGpu: int32 [n_ctu, 2358] and the packed sets of alf_pack_filters -> d_ctrl uint8 [n_ctu, 3]"""
+        st = np.ascontiguousarray(stats, np.int32).reshape(-1, self.ALF_CTU_WORDS)
+        n = st.shape[0]
+        d_stats, d_ctrl = self.alloc(max(st.nbytes, 16)), self.alloc(max(3 * n, 16))
+        d_stats.upload(st)
+        d_luma, n_luma, d_chroma, n_chroma = self._alf_sets(luma, chroma)
+        self.alf_decide_dev(d_stats.ptr, n, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, lambda_q4, d_ctrl.ptr)
+        self.stream_sync()
+        return d_ctrl.download(np.uint8, 3 * n).reshape(n, 3)
+
+    def alf_apply(self, tiles, w, h, luma, chroma, ctrl, classes=None, base=None):
+        """numpy convenience around xAlfApplyGpu: a tile array, the packed sets, d_ctrl (uint8 [n_ctu, 3]) and a class map (None:
+        classified inside) -> the filtered tile array; m_I, which the call does not write, comes from `base` (None: zeros)"""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        ctl = np.ascontiguousarray(ctrl, np.uint8).ravel()
+        assert src.size == w * h * 2 and ctl.size == self.ctu_count(w, h) * 3
+        d_in, d_out, d_ctl = self.alloc(src.nbytes), self.alloc(src.nbytes), self._upload(ctl)
+        d_in.upload(src)
+        d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        d_cls = None if classes is None else self._upload(np.ascontiguousarray(classes, np.uint8).ravel())
+        d_luma, n_luma, d_chroma, n_chroma = self._alf_sets(luma, chroma)
+        self.alf_apply_dev(d_in.ptr, w, h, 0 if d_cls is None else d_cls.ptr, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, d_ctl.ptr, d_out.ptr)
         self.stream_sync()
         return d_out.download(np.uint8, src.size)
 

@@ -400,6 +400,54 @@ inline const char *sao_apply(const void *d_in, int w, int h, const void *d_param
     return check(b);                                                        // in place is not possible
 }
 
+// The adaptive loop filter.  A CTU's statistics are 2358 int32, a class map one byte per 4x4 luma block, d_ctrl 3 bytes per CTU; a
+// set array is not looked at when its count is 0.
+constexpr size_t kAlfCtuBytes = 2358 * 4;
+constexpr const char *kAlfCounts = "n_luma and n_chroma must be 0..8";
+inline size_t blocks4(int w, int h) { return (size_t)(w / 4) * (size_t)(h / 4); }
+inline bool alf_counts_ok(int n_luma, int n_chroma) { return n_luma >= 0 && n_luma <= 8 && n_chroma >= 0 && n_chroma <= 8; }
+inline Buf alf_sets(const char *name, const void *p, int count, size_t each) { return count > 0 ? in(name, p, 4, (size_t)count * each) : opt(in(name, nullptr, 4)); }
+inline const char *alf_classify(const void *d_dec, int w, int h, const void *d_class)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    const Buf b[] = {out("d_class", d_class, 1, blocks4(w, h)), in("d_dec", d_dec, 16, tile_bytes(w, h))};
+    return check(b);
+}
+inline const char *alf_stats(const void *d_org, const void *d_dec, int w, int h, const void *d_class, const void *d_stats)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    const Buf b[] = {out("d_stats", d_stats, 4, ctus(w, h) * kAlfCtuBytes), in("d_org", d_org, 16, tile_bytes(w, h)), in("d_dec", d_dec, 16, tile_bytes(w, h)),
+                     opt(in("d_class", d_class, 1, blocks4(w, h)))};
+    return check(b);
+}
+// the entry point then accepts n_ctu == 0 without a launch, as for the next one
+inline const char *alf_sum_stats(const void *d_stats, size_t n_ctu, const void *d_mask, const void *d_total)
+{
+    if (n_ctu > 0x7FFFFFFFull) return "n_ctu must be below 2^31";
+    const Buf b[] = {out("d_total", d_total, 8, 2358 * 8), in("d_stats", d_stats, 4, n_ctu * kAlfCtuBytes), opt(in("d_mask", d_mask, 1, n_ctu))};
+    return check(b);
+}
+inline const char *alf_decide(const void *d_stats, size_t n_ctu, const void *d_luma, int n_luma, const void *d_chroma, int n_chroma, int lambda_q4,
+                              const void *d_ctrl)
+{
+    if (!alf_counts_ok(n_luma, n_chroma)) return kAlfCounts;
+    if (!lambda_ok(lambda_q4)) return "lambda_q4 must be 0..65535";
+    if (n_ctu > 0x7FFFFFFFull) return "n_ctu must be below 2^31";
+    const Buf b[] = {out("d_ctrl", d_ctrl, 1, n_ctu * 3), in("d_stats", d_stats, 4, n_ctu * kAlfCtuBytes), alf_sets("d_luma", d_luma, n_luma, sizeof(x266_alf_luma_t)),
+                     alf_sets("d_chroma", d_chroma, n_chroma, sizeof(x266_alf_chroma_t))};
+    return check(b);
+}
+inline const char *alf_apply(const void *d_in, int w, int h, const void *d_class, const void *d_luma, int n_luma, const void *d_chroma, int n_chroma,
+                             const void *d_ctrl, const void *d_out)
+{
+    if (const char *why = frame(w, h, 16)) return why;
+    if (!alf_counts_ok(n_luma, n_chroma)) return kAlfCounts;
+    const Buf b[] = {out("d_out", d_out, 16, tile_bytes(w, h)), in("d_in", d_in, 16, tile_bytes(w, h)), opt(in("d_class", d_class, 1, blocks4(w, h))),
+                     alf_sets("d_luma", d_luma, n_luma, sizeof(x266_alf_luma_t)), alf_sets("d_chroma", d_chroma, n_chroma, sizeof(x266_alf_chroma_t)),
+                     in("d_ctrl", d_ctrl, 1, ctus(w, h) * 3)};
+    return check(b);                                                        // in place is not possible
+}
+
 // ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------
 inline const char *intra32_refs_from_tiles(const void *d_frame, int w, int h, int component, const void *d_refs)
 {

@@ -263,6 +263,15 @@ hipError_t launch_sao_stats(const x266_ref_block_t *d_org, const x266_ref_block_
                             x266_sao_t *d_param, hipStream_t stream);
 hipError_t launch_sao_decide(const int32_t *d_stats, size_t n_ctu, int lambda_q4, x266_sao_t *d_param, hipStream_t stream);
 hipError_t launch_sao_apply(const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const x266_sao_t *d_param, hipStream_t stream);
+// adaptive loop filter (alf_kernels.hip); d_class NULL in the statistics and in apply: classified inside
+hipError_t launch_alf_classify(const x266_ref_block_t *d_dec, int width, int height, uint8_t *d_class, hipStream_t stream);
+hipError_t launch_alf_stats(const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, const uint8_t *d_class, int32_t *d_stats,
+                            hipStream_t stream);
+hipError_t launch_alf_sum_stats(const int32_t *d_stats, size_t n_ctu, const uint8_t *d_mask, int64_t *d_total, hipStream_t stream);
+hipError_t launch_alf_decide(const int32_t *d_stats, size_t n_ctu, const x266_alf_luma_t *d_luma, int n_luma, const x266_alf_chroma_t *d_chroma, int n_chroma,
+                             int lambda_q4, uint8_t *d_ctrl, hipStream_t stream);
+hipError_t launch_alf_apply(const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const uint8_t *d_class, const x266_alf_luma_t *d_luma,
+                            int n_luma, const x266_alf_chroma_t *d_chroma, int n_chroma, const uint8_t *d_ctrl, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

@@ -1288,6 +1288,52 @@ int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int 
     return launched(ctx, "SAO apply launch", launch_sao_apply(d_in, d_out, width, height, d_param, (hipStream_t)stream));
 }
 
+// ---- adaptive loop filter on tiled frames (x266_alf.hpp) -------------------------------------------------------------------------------
+int xAlfClassifyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_dec, int width, int height, uint8_t *d_class, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::alf_classify(d_dec, width, height, d_class)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "ALF classification launch", launch_alf_classify(d_dec, width, height, d_class, (hipStream_t)stream));
+}
+
+int xAlfStatsGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height, const uint8_t *d_class,
+                 int32_t *d_stats, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::alf_stats(d_org, d_dec, width, height, d_class, d_stats)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "ALF statistics launch", launch_alf_stats(d_org, d_dec, width, height, d_class, d_stats, (hipStream_t)stream));
+}
+
+int xAlfSumStatsGpu(x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, const uint8_t *d_mask, int64_t *d_total, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::alf_sum_stats(d_stats, n_ctu, d_mask, d_total)) return refuse(ctx, __func__, why);
+    if (n_ctu == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "ALF totals launch", launch_alf_sum_stats(d_stats, n_ctu, d_mask, d_total, (hipStream_t)stream));
+}
+
+int xAlfDecideGpu(x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, const x266_alf_luma_t *d_luma, int n_luma, const x266_alf_chroma_t *d_chroma,
+                  int n_chroma, int lambda_q4, uint8_t *d_ctrl, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::alf_decide(d_stats, n_ctu, d_luma, n_luma, d_chroma, n_chroma, lambda_q4, d_ctrl)) return refuse(ctx, __func__, why);
+    if (n_ctu == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "ALF decision launch", launch_alf_decide(d_stats, n_ctu, d_luma, n_luma, d_chroma, n_chroma, lambda_q4, d_ctrl, (hipStream_t)stream));
+}
+
+int xAlfApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const uint8_t *d_class, const x266_alf_luma_t *d_luma, int n_luma,
+                 const x266_alf_chroma_t *d_chroma, int n_chroma, const uint8_t *d_ctrl, x266_ref_block_t *d_out, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::alf_apply(d_in, width, height, d_class, d_luma, n_luma, d_chroma, n_chroma, d_ctrl, d_out)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "ALF apply launch", launch_alf_apply(d_in, d_out, width, height, d_class, d_luma, n_luma, d_chroma, n_chroma, d_ctrl, (hipStream_t)stream));
+}
+
 // ---- intra coding of tiled frames (intra_frame_kernels.hip) ------------------------------------------------------------------------------
 int xIntra32RefsFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_frame, int width, int height, int component, x266_intra_ref_t *d_refs,
                              void *stream)
