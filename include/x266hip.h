@@ -118,13 +118,15 @@ int  xHipAutotuneReport(const x266hip_ctx *ctx, char *buf, size_t cap);
 /* returns after enqueueing; use xHipStreamSync or the caller's own stream   */
 /* API to wait.  Inputs and outputs must not overlap unless a call says so.   */
 /* ------------------------------------------------------------------------ */
-/* Alignment: every ...Dev declaration below is preceded by an "Alignment in bytes" line that names each of its pointer
- * arguments with the alignment the call's argument check enforces (1 = none); a pointer aligned to less returns
+/* Alignment: every device entry point below -- a call that takes the context first, the stream last and device buffers in
+ * between -- is preceded by an "Alignment in bytes" line that names each of its device pointers (for the deblocking calls:
+ * d_in, d_out and the pointer fields of x266_deblock_t) with the alignment the call's argument check enforces (1 = none;
+ * tests/test_arg_rules.py holds every line against the rules); a pointer aligned to less returns
  * X266HIP_EINVAL and launches nothing, and nothing MORE than that alignment is needed -- sample, coefficient and tile buffers
  * 16, x266_me_result_t records and the chroma planes of the two conversion calls 8, uint32_t outputs and index / offset
  * tables 4 (the SATD output of xDct32SatdFrameDev: 16), mode and class bytes and the pixel planes of the planar searches none
  * (the current plane of xSad8x8SearchDev: 4).
- * tests/test_gpu_placement.py runs every call at exactly these alignments and checks these lines against its table.
+ * tests/test_gpu_placement.py runs every ...Dev call at exactly these alignments and checks their lines against its table.
  * A call reads nothing whose value can reach its result outside the documented extent of its inputs, and writes nothing
  * outside the documented extent of its outputs. */
 /* 2-D forward 32x32 DCT-II, shifts 4 then 11, truncating int16 stores:
@@ -415,6 +417,7 @@ int xTransformCtuToTilesDev(x266hip_ctx *ctx, const int16_t *d_coef, const uint8
  * X266HIP_EINVAL for a NULL or misaligned buffer, a scalar qp outside 0..51 when d_qp == NULL, rounding outside 0..511, or a
  * span that does not fit in the address space.  n_regions == 0 returns 0 and launches nothing.  The call allocates nothing and
  * can be captured into a graph. */
+/* Alignment in bytes: d_in 16, d_out 16, d_class 1, d_qp 1, d_nnz 4. */
 int xQuantRegionsGpu(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16_t *d_out, size_t n_regions,
                      const uint8_t *d_class, const uint8_t *d_qp, int qp, int rounding, uint32_t *d_nnz, void *stream);
 /* The coding loop of a frame in one launch.  width, height multiples of 64.  For every 64x64 CTU in raster order and its six
@@ -426,6 +429,7 @@ int xQuantRegionsGpu(x266hip_ctx *ctx, int inverse, const int16_t *d_in, int16_t
  * allowed, as in the calls it fuses; d_level and d_nnz must overlap nothing.
  * The tile buffers d_cur, d_pred, d_recon and the level buffer d_level are 16-byte aligned, d_nnz is 4-byte aligned, d_qp needs
  * no alignment.  X266HIP_EINVAL as for the calls above.  The call allocates nothing and can be captured into a graph. */
+/* Alignment in bytes: d_cur 16, d_pred 16, d_qp 1, d_level 16, d_nnz 4, d_recon 16. */
 int xDct32CodeCtuTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_pred, int width,
                           int height, const uint8_t *d_qp, int qp, int rounding, int16_t *d_level, uint32_t *d_nnz,
                           x266_ref_block_t *d_recon, void *stream);
@@ -505,10 +509,13 @@ int xMotionCompDev(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_m
  * d_ref and d_pred 16-byte aligned, d_mv 8-byte aligned; X266HIP_EINVAL for a NULL or misaligned pointer, a bad size, a buffer whose
  * span does not fit in the address space, or d_pred overlapping d_ref or d_mv.  Nothing is allocated; the calls can be captured
  * into a graph.  Tile offsets are size_t as in the integer calls, but frames beyond 2^32 bytes are untested for these four calls. */
+/* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompQpelLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                            int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompQpelChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                              int width, int height, x266_ref_block_t *d_pred, void *stream);
+/* Alignment in bytes: d_ref 16, d_mv 8, d_pred 16. */
 int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x266_me_result_t *d_mv,
                        int width, int height, x266_ref_block_t *d_pred, void *stream);
 /* Quarter-sample refinement of integer vectors.  d_int holds one integer record per 8x8 luma block (the searches' d_best; its cost
@@ -521,6 +528,7 @@ int xMotionCompQpelGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_ref, const x2
  * with anything returns X266HIP_EINVAL.  d_cur and d_ref are 16-byte aligned, d_int and d_best 8-byte, d_costs 4-byte; other
  * arguments and errors as above.  No per-stream scratch is used (unlike the SATD search): the call allocates nothing, needs no
  * xHipMeScratchReserve and can be captured into a graph. */
+/* Alignment in bytes: d_cur 16, d_ref 16, d_int 8, d_best 8, d_costs 4. */
 int xSatd8x8RefineQpelFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref,
                                    int width, int height, const x266_me_result_t *d_int, x266_me_result_t *d_best,
                                    uint32_t *d_costs, void *stream);
@@ -556,6 +564,7 @@ typedef struct x266_wp_t {
  * The luma block's vectors and direction also move its 4x4 U and V blocks.  d_ref0 == d_ref1 is allowed; d_pred must overlap
  * nothing.  Both vector arrays are required whatever d_dir says (an unused record is read and ignored).  With wp == NULL a block
  * of direction 1 is the uni quarter-sample prediction of (d_ref0, d_mv0) bit for bit, direction 2 likewise for list 1. */
+/* Alignment in bytes: d_ref0 16, d_ref1 16, d_mv0 8, d_mv1 8, d_dir 1, d_pred 16. */
 int xMotionCompBiQpelTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_ref0, const x266_ref_block_t *d_ref1,
                            const x266_me_result_t *d_mv0, const x266_me_result_t *d_mv1, const uint8_t *d_dir,
                            const x266_wp_t *wp, int planes, int width, int height, x266_ref_block_t *d_pred, void *stream);
@@ -563,6 +572,7 @@ int xMotionCompBiQpelTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_ref0, con
  * predictions of the call above under direction 1, 2, 3; satd8x8 is the metric of the searches.  d_dir[b] = the direction of the
  * least of (c0, c1, c2 + bi_penalty), among equal values the earlier in that order.  bi_penalty is 0..65535, the caller's price for
  * the second vector.  Either output may be NULL, not both; an output must overlap nothing. */
+/* Alignment in bytes: d_cur 16, d_ref0 16, d_ref1 16, d_mv0 8, d_mv1 8, d_costs 4, d_dir 1. */
 int xSatd8x8BiCostsFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref0,
                              const x266_ref_block_t *d_ref1, int width, int height, const x266_me_result_t *d_mv0,
                              const x266_me_result_t *d_mv1, const x266_wp_t *wp, int bi_penalty, uint32_t *d_costs,
@@ -572,6 +582,7 @@ int xSatd8x8BiCostsFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, co
  * layout (NULL allowed), d_best == d_int allowed.  cost(q) = satd8x8(cur_block - Bi), Bi the bi formula between the fixed list's V
  * under d_mv_fix[b] (quarter samples, any int16 vector) on d_ref_fix and the candidate's V on d_ref.  list is 0 or 1 and names
  * the list being refined: the candidate takes w[list], o[list], the fixed term the other list's. */
+/* Alignment in bytes: d_cur 16, d_ref_fix 16, d_mv_fix 8, d_ref 16, d_int 8, d_best 8, d_costs 4. */
 int xSatd8x8RefineBiQpelFromTiles(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, const x266_ref_block_t *d_ref_fix,
                                   const x266_me_result_t *d_mv_fix, const x266_ref_block_t *d_ref,
                                   const x266_me_result_t *d_int, int list, const x266_wp_t *wp, int width, int height,
@@ -632,10 +643,13 @@ typedef struct x266_deblock_t {
     const x266_me_result_t *d_mv;        /* quarter luma samples, one per 8x8 block, raster order; NULL: the motion term never fires */
     int qp, beta_offset_div2, tc_offset_div2;   /* offsets -6..6 */
 } x266_deblock_t;
+/* Alignment in bytes: d_in 16, d_out 16, d_class 1, d_intra 1, d_nnz 4, d_qp 1, d_mv 8. */
 int xDeblockLumaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
                     x266_ref_block_t *d_out, void *stream);
+/* Alignment in bytes: d_in 16, d_out 16, d_class 1, d_intra 1, d_nnz 4, d_qp 1, d_mv 8. */
 int xDeblockChromaGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
                       x266_ref_block_t *d_out, void *stream);
+/* Alignment in bytes: d_in 16, d_out 16, d_class 1, d_intra 1, d_nnz 4, d_qp 1, d_mv 8. */
 int xDeblockGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_deblock_t *p,
                 x266_ref_block_t *d_out, void *stream);
 /* Sample adaptive offset (SAO) of a tiled frame, the second in-loop filter (no upstream counterpart, as for the quantiser and the
@@ -685,11 +699,15 @@ typedef struct x266_sao_t {
     int8_t  off[4];
     uint8_t zero[2];
 } x266_sao_t;                            /* 8 bytes */
+/* Alignment in bytes: d_org 16, d_dec 16, d_stats 4. */
 int xSaoStatsGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height,
                  int32_t *d_stats, void *stream);
+/* Alignment in bytes: d_stats 4, d_param 8. */
 int xSaoDecideGpu(x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, int lambda_q4, x266_sao_t *d_param, void *stream);
+/* Alignment in bytes: d_org 16, d_dec 16, d_param 8, d_stats 4. */
 int xSaoSearchGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height,
                   int lambda_q4, x266_sao_t *d_param, int32_t *d_stats, void *stream);
+/* Alignment in bytes: d_in 16, d_param 8, d_out 16. */
 int xSaoApplyGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const x266_sao_t *d_param,
                  x266_ref_block_t *d_out, void *stream);
 /* Adaptive loop filter (ALF) of a tiled frame, the third in-loop filter (no upstream counterpart, as for the quantiser, the deblocking
@@ -767,13 +785,18 @@ typedef struct x266_alf_chroma_t {
     uint8_t clip[6];
     uint8_t zero[4];
 } x266_alf_chroma_t;                     /* 16 bytes */
+/* Alignment in bytes: d_dec 16, d_class 1. */
 int xAlfClassifyGpu (x266hip_ctx *ctx, const x266_ref_block_t *d_dec, int width, int height, uint8_t *d_class, void *stream);
+/* Alignment in bytes: d_org 16, d_dec 16, d_class 1, d_stats 4. */
 int xAlfStatsGpu    (x266hip_ctx *ctx, const x266_ref_block_t *d_org, const x266_ref_block_t *d_dec, int width, int height,
                      const uint8_t *d_class, int32_t *d_stats, void *stream);
+/* Alignment in bytes: d_stats 4, d_mask 1, d_total 8. */
 int xAlfSumStatsGpu (x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, const uint8_t *d_mask, int64_t *d_total,
                      void *stream);
+/* Alignment in bytes: d_stats 4, d_luma 4, d_chroma 4, d_ctrl 1. */
 int xAlfDecideGpu   (x266hip_ctx *ctx, const int32_t *d_stats, size_t n_ctu, const x266_alf_luma_t *d_luma, int n_luma,
                      const x266_alf_chroma_t *d_chroma, int n_chroma, int lambda_q4, uint8_t *d_ctrl, void *stream);
+/* Alignment in bytes: d_in 16, d_class 1, d_luma 4, d_chroma 4, d_ctrl 1, d_out 16. */
 int xAlfApplyGpu    (x266hip_ctx *ctx, const x266_ref_block_t *d_in, int width, int height, const uint8_t *d_class,
                      const x266_alf_luma_t *d_luma, int n_luma, const x266_alf_chroma_t *d_chroma, int n_chroma,
                      const uint8_t *d_ctrl, x266_ref_block_t *d_out, void *stream);
@@ -867,8 +890,10 @@ int xIntra32CostsDev(x266hip_ctx *ctx, const x266_intra_ref_t *d_refs, const uin
  * X266HIP_EINVAL for a NULL (d_cur, d_level, d_mode, d_recon) or misaligned pointer, a bad size, a scalar qp outside 0..51 when
  * d_qp == NULL, rounding outside 0..511, or a span that does not fit in the address space.
  * Both calls allocate nothing and can be captured into a graph; a refused call launches nothing and names itself in xHipLastError. */
+/* Alignment in bytes: d_frame 16, d_refs 16. */
 int xIntra32RefsFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_frame, int width, int height, int component,
                              x266_intra_ref_t *d_refs, void *stream);
+/* Alignment in bytes: d_cur 16, d_qp 1, d_mode_in 1, d_level 16, d_nnz 4, d_mode 1, d_recon 16. */
 int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int width, int height, const uint8_t *d_qp, int qp,
                          int rounding, const uint8_t *d_mode_in, int16_t *d_level, uint32_t *d_nnz, uint8_t *d_mode,
                          x266_ref_block_t *d_recon, void *stream);

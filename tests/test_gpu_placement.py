@@ -641,11 +641,35 @@ def test_every_dev_entry_point_has_a_row():
     assert set(ROWS) | EXCLUDED == declared, (sorted(declared - set(ROWS) - EXCLUDED), sorted((set(ROWS) | EXCLUDED) - declared))
 
 
-def header_alignments():
-    """{entry point: {pointer: alignment}} from the `Alignment in bytes: ...` comment in front of every ...Dev declaration"""
+def header_alignments(every=False):
+    """{entry point: {pointer: alignment}} from the `Alignment in bytes: ...` comment in front of every ...Dev declaration (the
+    placement table's calls), or with `every` in front of any declaration at all"""
     out = {}
-    for items, name in re.findall(r"/\* Alignment in bytes: ([^*]+?)\. \*/\s*int (x\w+Dev)\(", _header()):
-        out[name] = {k: int(v) for k, v in (i.split() for i in items.replace("\n", " ").split(","))}
+    for items, name in re.findall(r"/\* Alignment in bytes: ([^*]+?)\. \*/\s*int (x\w+)\s*\(", _header()):
+        if every or name.endswith("Dev"):
+            out[name] = {k: int(v) for k, v in (i.split() for i in items.replace("\n", " ").split(","))}
+    return out
+
+
+def device_entry_points():
+    """{entry point: [device pointer, ...]} by the form of the header's declarations, whatever the names and the layout: the context
+    first, the stream last, and in between at least one device buffer -- a pointer argument d_..., or for the deblocking calls
+    the pointer fields of the host-read x266_deblock_t `p`; the host-read weights `wp` are no device buffer"""
+    hdr = _header()
+    fields = re.findall(r"\*\s*(d_\w+)\s*;", re.search(r"typedef struct x266_deblock_t \{(.*?)\}", hdr, re.S).group(1))
+    out = {}
+    for name, middle in re.findall(r"^\s*int\s+(x\w+)\s*\(\s*x266hip_ctx \*ctx,([^;()]*),\s*void \*stream\s*\)\s*;", hdr, re.M):
+        ptrs, other = [], []
+        for type_, arg in re.findall(r"([\w ]+?)\s*\*\s*(\w+)", middle):
+            if arg.startswith("d_"):
+                ptrs.append(arg)
+            elif "x266_deblock_t" in type_:
+                ptrs += fields
+            elif "x266_wp_t" not in type_:
+                other.append(arg)                                         # a handle (a graph, an event)
+        if ptrs:
+            assert not other, (name, other)                               # a new kind of pointer: say here what it is
+            out[name] = ptrs
     return out
 
 

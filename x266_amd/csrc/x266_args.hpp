@@ -2,8 +2,9 @@
 //
 // Every device entry point has one rule function here (calls with the same rules share one).  It takes the call's arguments
 // and returns the reason the call is refused, or nullptr when it is accepted; it reads nothing through the pointers and touches
-// no state, so tests/cpp/arg_rules_check.cpp holds the rules without a device.  x266hip_abi.hip turns a reason into
-// X266HIP_EINVAL and the text "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here.
+// no state, so tests/cpp/arg_rules_check.cpp -- one table with a row per entry point, one walk over it -- holds the rules of
+// every one of them without a device.  x266hip_abi.hip turns a reason into X266HIP_EINVAL and the text
+// "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
