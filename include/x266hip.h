@@ -897,6 +897,70 @@ int xIntra32RefsFromTilesGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_frame, 
 int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int width, int height, const uint8_t *d_qp, int qp,
                          int rounding, const uint8_t *d_mode_in, int16_t *d_level, uint32_t *d_nnz, uint8_t *d_mode,
                          x266_ref_block_t *d_recon, void *stream);
+
+/* ---- the compact level stream: what leaves the device for the host's entropy coder, and what a host decoder hands back ----
+ * xDct32CodeCtuTilesGpu, xIntra32CodeFrameGpu and xQuantRegionsGpu(0) emit levels dense, 2 KiB per region, nearly all zeros at
+ * any useful qp.  xLevelsPackGpu turns them into coded-group flags, significance maps and the non-zero levels in the order a
+ * coefficient coder walks them; xLevelsUnpackGpu is the exact inverse and the entry of a decoder into xQuantRegionsGpu(1).
+ *
+ * Units.  A region is 1024 int16 levels (the unit of xQuantRegionsGpu and of the 12 KiB-per-CTU layouts).  Region r has the block
+ * size N = 4 << (d_class[r] & 3) -- the class byte read exactly as xQuantRegionsGpu and xTransformTilesDev read it; d_class ==
+ * NULL: N = 32 -- and is (32 / N)^2 blocks, block-major in raster order, each block row-major N x N: level (blk, v, u) is
+ * d_level[r * 1024 + blk * N * N + v * N + u], u the horizontal and v the vertical frequency.
+ * Diagonal scan of an M x M grid: the positions (x, y) ordered by x + y ascending, then by x ascending (the up-right diagonal of
+ * HEVC and VVC).  For M = 4, scan index -> y * 4 + x is 0 4 1 8 5 2 12 9 6 3 13 10 7 14 11 15.
+ * Coefficient groups.  A block is (N / 4)^2 CGs of 4x4; CG (cgx, cgy) covers u = 4 cgx .. 4 cgx + 3, v = 4 cgy .. 4 cgy + 3.  The CGs
+ * of a block are ordered by the diagonal scan of the (N / 4) x (N / 4) grid, the 16 levels of a CG by the 4x4 scan.  A region always
+ * has 64 CGs; CG bit g = blk * (N / 4)^2 + s, s the CG's scan position in its block.
+ *
+ * Per region one 32-byte record (below).  The payload of region r is d_stream[offset .. offset + n_words), in 16-bit words:
+ * first one 16-bit significance map per coded CG, in ascending bit order of cg_mask -- bit i of a map is set when scan position i
+ * of that CG is non-zero --, then the non-zero levels of those CGs as int16, CG by CG in the same order, in ascending scan position
+ * inside each CG.  (Maps first: an unpacking lane finds its map from cg_mask alone and its levels from a prefix sum of popcounts.)
+ * At most 64 + 1024 = 1088 words per region.  offset[r] is the exclusive prefix sum of n_words over regions 0 .. r - 1, in 64 bits:
+ * a region's place depends on the data alone, and the same input gives the same bytes on every run.
+ *
+ * Both calls take one host struct, read during the call; the pointers in it are device pointers (alignments: the field comments).
+ *
+ * xLevelsPackGpu writes every record.  d_total[0] = the total number of words, d_total[1] = the number of leading regions whose
+ * payload lies completely inside cap_words (n_regions exactly when the stream fits).  The payload of region r is written if and only
+ * if offset + n_words <= cap_words; no word at or beyond cap_words is ever written.  cap_words == 0 with d_stream == NULL is the
+ * count-only call: records and totals to size a buffer with.  With d_nnz != NULL a region with d_nnz[r] == 0 counts as all zero and
+ * its levels are not read (the coding calls produce that array).  n_regions == 0 writes d_total = {0, 0} and nothing else.
+ * Three launches on the caller's stream: count and records, the offsets (one workgroup, xLevelsScanChunk() regions per step), write.
+ *
+ * xLevelsUnpackGpu writes all 1024 levels of every region, absent ones as zeros, and with d_nnz != NULL the region's non-zero count
+ * (what xDeblockGpu reads).  It trusts nothing in a record except cg_mask and offset: it reads the maps from the stream and derives
+ * every count from them.  With end = offset + popcount(cg_mask) + the sum of popcount(map), a region with end > cap_words, or whose
+ * maps alone already pass cap_words, is written as all zero with d_nnz[r] = 0.  A map of 0 under a set mask bit is legal and
+ * contributes no level.  Nothing outside [0, cap_words) of the stream is ever read: the stream comes from a host decoder.
+ * d_total is ignored; d_stream may be NULL when cap_words == 0.
+ *
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned required buffer, a span
+ * that does not fit in the address space, an output overlapping any other buffer.  The extents are n_regions * 2048 (d_level),
+ * n_regions (d_class), n_regions * 4 (d_nnz), n_regions * 32 (d_region), cap_words * 2 (d_stream) and 16 bytes (d_total).  With
+ * n_regions == 0 only d_total of the pack call is looked at.  Neither call allocates; both can be captured into a graph. */
+typedef struct x266_level_region_t {
+    uint64_t cg_mask;   /* bit g set: CG g has a non-zero level                      */
+    uint64_t offset;    /* start of the region's payload in d_stream, in 16-bit words */
+    uint32_t n_words;   /* popcount(cg_mask) + n_nz                                   */
+    uint32_t n_nz;      /* non-zero levels of the region (what d_nnz holds)           */
+    uint32_t sum_abs;   /* sum of |level|: the rate proxy a rate control wants        */
+    uint32_t max_abs;   /* 0..32768: tells the host which binarisation range it needs */
+} x266_level_region_t;
+typedef struct x266_levels_t {
+    int16_t  *d_level;                 /* [n_regions * 1024], 16-byte aligned; pack reads, unpack writes            */
+    const uint8_t *d_class;            /* [n_regions] or NULL (every region 32x32), any alignment                   */
+    uint32_t *d_nnz;                   /* [n_regions] or NULL, 4-byte aligned; pack reads, unpack writes (above)    */
+    x266_level_region_t *d_region;     /* [n_regions], 8-byte aligned; pack writes, unpack reads                    */
+    uint16_t *d_stream;                /* [cap_words], 16-byte aligned; pack writes, unpack reads                   */
+    uint64_t *d_total;                 /* [2], 8-byte aligned; pack writes, unpack ignores (may be NULL there)      */
+    size_t    n_regions;
+    uint64_t  cap_words;
+} x266_levels_t;
+int xLevelsPackGpu  (x266hip_ctx *ctx, const x266_levels_t *p, void *stream);
+int xLevelsUnpackGpu(x266hip_ctx *ctx, const x266_levels_t *p, void *stream);
+
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */
@@ -1102,6 +1166,11 @@ uint64_t xDct32PackDctWord(const int16_t *dct, int idx);
  * first N columns: the taps of src/mkDct32.bsv:132-141), 1 = DST-VII; N in {4, 8, 16} (and 32 for DCT-II).
  * m[k*N + n], row k = frequency.  Lets a host (and the CPU tests) check the product's own tables. */
 int      xTransformMatrix(int type, int size, int16_t *m);
+/* The order in which a host coder walks a size x size block of the compact level stream (xLevelsPackGpu): for size in {4, 8, 16, 32}
+ * pos[s * 16 + i] = v * size + u of scan position i of CG s, size * size entries; X266HIP_EINVAL for any other size or a NULL pos. */
+int      xLevelScan(int size, uint16_t *pos);
+/* Regions the offset scan of xLevelsPackGpu takes per step (a test walks region counts around it). */
+unsigned xLevelsScanChunk(void);
 const char *xHipVersion(void);
 
 /* ------------------------------------------------------------------------ */

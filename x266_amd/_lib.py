@@ -25,6 +25,16 @@ class WpParams(ctypes.Structure):
     _fields_ = [("w", (ctypes.c_int16 * 3) * 2), ("o", (ctypes.c_int16 * 3) * 2), ("log2_denom", ctypes.c_uint8 * 2)]
 
 
+class LevelsParams(ctypes.Structure):
+    """x266_levels_t of include/x266hip.h"""
+    _fields_ = [("d_level", _P), ("d_class", _P), ("d_nnz", _P), ("d_region", _P), ("d_stream", _P), ("d_total", _P),
+                ("n_regions", ctypes.c_size_t), ("cap_words", ctypes.c_uint64)]
+
+
+# x266_level_region_t of include/x266hip.h
+LEVEL_REGION_DTYPE = np.dtype([("cg_mask", "<u8"), ("offset", "<u8"), ("n_words", "<u4"), ("n_nz", "<u4"), ("sum_abs", "<u4"), ("max_abs", "<u4")])
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -133,6 +143,11 @@ def load_library(path=None):
     L.xAlfSumStatsGpu.argtypes = [_P, _P, _SZ, _P, _P, _P]
     L.xAlfDecideGpu.argtypes = [_P, _P, _SZ, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xAlfApplyGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P, _P, _P]
+    L.xLevelsPackGpu.argtypes = [_P, ctypes.POINTER(LevelsParams), _P]
+    L.xLevelsUnpackGpu.argtypes = [_P, ctypes.POINTER(LevelsParams), _P]
+    L.xLevelScan.argtypes = [ctypes.c_int, _P]
+    L.xLevelsScanChunk.argtypes = []
+    L.xLevelsScanChunk.restype = ctypes.c_uint
     L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xIntra32CodeFrameGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
@@ -164,6 +179,20 @@ def load_library(path=None):
     if default:
         _lib = L
     return L
+
+
+def level_scan(size):
+    """xLevelScan: the order in which a host coder walks a size x size block of the compact level stream, int64 [size * size]
+    (entry s * 16 + i = v * size + u of scan position i of CG s).  No device."""
+    pos = np.empty(max(int(size), 0) ** 2 if int(size) <= 32 else 0, np.uint16)
+    if load_library().xLevelScan(int(size), _P(pos.ctypes.data if pos.size else 0)) != 0:
+        raise X266Error("xLevelScan: size must be 4, 8, 16 or 32")
+    return pos.astype(np.int64)
+
+
+def levels_scan_chunk():
+    """xLevelsScanChunk: regions the offset scan of xLevelsPackGpu takes per step"""
+    return int(load_library().xLevelsScanChunk())
 
 
 def pack_diff_rows(mat, first_row):
@@ -1132,6 +1161,79 @@ class Codec:
         self.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, dq.ptr if dq else 0, qp, rounding, dl.ptr, dn.ptr, dr.ptr)
         self.stream_sync()
         return dl.download(np.int16, n * 6144).reshape(n, 6, 1024), dn.download(np.uint32, n * 6).reshape(n, 6), dr.download(np.uint8, out.size)
+
+    # -- the compact level stream -------------------------------------------------------------------
+    @staticmethod
+    def levels_params(d_level=0, d_class=0, d_nnz=0, d_region=0, d_stream=0, d_total=0, n_regions=0, cap_words=0):
+        """an x266_levels_t from device addresses (0: NULL)"""
+        return LevelsParams(d_level or None, d_class or None, d_nnz or None, d_region or None, d_stream or None, d_total or None, int(n_regions),
+                            int(cap_words))
+
+    def levels_pack_dev(self, params, stream=0):
+        self._check(self.L.xLevelsPackGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xLevelsPackGpu")
+
+    def levels_unpack_dev(self, params, stream=0):
+        self._check(self.L.xLevelsUnpackGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xLevelsUnpackGpu")
+
+    level_scan = staticmethod(level_scan)
+
+    def _levels_tabs(self, n, classes, nnz):
+        d_cls = d_nnz = None
+        if classes is not None:
+            c = np.ascontiguousarray(classes, np.uint8).ravel()
+            assert c.size == n
+            d_cls = self.alloc(max(n, 16))
+            d_cls.upload(c)
+        if nnz is not None:
+            z = np.ascontiguousarray(nnz, np.uint32).ravel()
+            assert z.size == n
+            d_nnz = self.alloc(max(4 * n, 16))
+            d_nnz.upload(z)
+        return d_cls, d_nnz
+
+    def levels_pack(self, levels, classes=None, nnz=None, cap_words=None):
+        """numpy convenience around xLevelsPackGpu: [n_regions, 1024] int16 (and a class byte and a non-zero count per region, None:
+        NULL) -> (records [n_regions] of LEVEL_REGION_DTYPE, stream uint16 [cap_words], total uint64 [2]).  cap_words None: a count-only
+        call sizes the stream exactly; words the call does not write are 0."""
+        x = np.ascontiguousarray(levels, np.int16).reshape(-1, 1024)
+        n = x.shape[0]
+        d_lv, d_rec, d_tot = self.alloc(max(x.nbytes, 16)), self.alloc(max(32 * n, 32)), self.alloc(16)
+        d_lv.upload(x)
+        d_cls, d_nnz = self._levels_tabs(n, classes, nnz)
+        p = self.levels_params(d_lv.ptr, d_cls.ptr if d_cls else 0, d_nnz.ptr if d_nnz else 0, d_rec.ptr, 0, d_tot.ptr, n, 0)
+        if cap_words is None:
+            self.levels_pack_dev(p)
+            self.stream_sync()
+            cap_words = int(d_tot.download(np.uint64, 2)[0])
+        cap_words = int(cap_words)
+        d_str = None
+        if cap_words:
+            d_str = self.alloc(2 * cap_words)
+            d_str.upload(np.zeros(cap_words, np.uint16))
+            p.d_stream, p.cap_words = d_str.ptr, cap_words
+        self.levels_pack_dev(p)
+        self.stream_sync()
+        rec = d_rec.download(np.uint8, 32 * n).view(LEVEL_REGION_DTYPE) if n else np.zeros(0, LEVEL_REGION_DTYPE)
+        return rec, d_str.download(np.uint16, cap_words) if d_str else np.zeros(0, np.uint16), d_tot.download(np.uint64, 2)
+
+    def levels_unpack(self, records, stream, n_regions, classes=None):
+        """numpy convenience around xLevelsUnpackGpu: records (LEVEL_REGION_DTYPE), the stream's words and a class byte per region
+        (None: NULL) -> (levels int16 [n_regions, 1024], non-zero counts uint32 [n_regions])"""
+        n = int(n_regions)
+        rec = np.ascontiguousarray(records, LEVEL_REGION_DTYPE).ravel()
+        words = np.ascontiguousarray(stream, np.uint16).ravel()
+        assert rec.size == n
+        d_lv, d_rec, d_nnz = self.alloc(max(2048 * n, 16)), self.alloc(max(32 * n, 32)), self.alloc(max(4 * n, 16))
+        d_rec.upload(rec.view(np.uint8))
+        d_str = None
+        if words.size:
+            d_str = self.alloc(words.nbytes)
+            d_str.upload(words)
+        d_cls, _ = self._levels_tabs(n, classes, None)
+        p = self.levels_params(d_lv.ptr, d_cls.ptr if d_cls else 0, d_nnz.ptr, d_rec.ptr, d_str.ptr if d_str else 0, 0, n, words.size)
+        self.levels_unpack_dev(p)
+        self.stream_sync()
+        return d_lv.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n)
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

@@ -4,7 +4,9 @@
 // and returns the reason the call is refused, or nullptr when it is accepted; it reads nothing through the pointers and touches
 // no state, so tests/cpp/arg_rules_check.cpp -- one table with a row per entry point, one walk over it -- holds the rules of
 // every one of them without a device.  x266hip_abi.hip turns a reason into X266HIP_EINVAL and the text
-// "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.
+// "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.  The two calls of
+// the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
+// driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -447,6 +449,34 @@ inline const char *alf_apply(const void *d_in, int w, int h, const void *d_class
                      alf_sets("d_luma", d_luma, n_luma, sizeof(x266_alf_luma_t)), alf_sets("d_chroma", d_chroma, n_chroma, sizeof(x266_alf_chroma_t)),
                      in("d_ctrl", d_ctrl, 1, ctus(w, h) * 3)};
     return check(b);                                                        // in place is not possible
+}
+
+// ---- the compact level stream ------------------------------------------------------------------------------------------------------
+// xLevelsPackGpu, xLevelsUnpackGpu: the device pointers are the fields of the host-read x266_levels_t.  d_stream may be NULL when
+// cap_words is 0 (pack: the count-only call); with n_regions == 0 pack looks at d_total alone and unpack at nothing.
+inline size_t levels_stream_bytes(uint64_t cap_words) { return cap_words > SIZE_MAX / 2 ? SIZE_MAX : (size_t)cap_words * 2; }
+inline const char *levels_pack(const x266_levels_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    const size_t n = p->n_regions;
+    if (n == 0) {
+        const Buf b[] = {out("d_total", p->d_total, 8, 16)};
+        return check(b);
+    }
+    Buf b[] = {out("d_region", p->d_region, 8, mul(n, 32)), out("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), out("d_total", p->d_total, 8, 16),
+               in("d_level", p->d_level, 16, mul(n, 2048)), opt(in("d_class", p->d_class, 1, n)), opt(in("d_nnz", p->d_nnz, 4, mul(n, 4)))};
+    b[1].optional = p->cap_words == 0;
+    return check(b);
+}
+inline const char *levels_unpack(const x266_levels_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    const size_t n = p->n_regions;
+    if (n == 0) return nullptr;
+    Buf b[] = {out("d_level", p->d_level, 16, mul(n, 2048)), opt(out("d_nnz", p->d_nnz, 4, mul(n, 4))), in("d_region", p->d_region, 8, mul(n, 32)),
+               in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), opt(in("d_class", p->d_class, 1, n))};
+    b[3].optional = p->cap_words == 0;
+    return check(b);
 }
 
 // ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------

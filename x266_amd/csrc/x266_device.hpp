@@ -272,6 +272,10 @@ hipError_t launch_alf_decide(const int32_t *d_stats, size_t n_ctu, const x266_al
                              int lambda_q4, uint8_t *d_ctrl, hipStream_t stream);
 hipError_t launch_alf_apply(const x266_ref_block_t *d_in, x266_ref_block_t *d_out, int width, int height, const uint8_t *d_class, const x266_alf_luma_t *d_luma,
                             int n_luma, const x266_alf_chroma_t *d_chroma, int n_chroma, const uint8_t *d_ctrl, hipStream_t stream);
+// the compact level stream (levels_kernels.hip): pack = count, scan, write on one stream; the scan's step is levels_scan_chunk() regions
+hipError_t launch_levels_pack(const x266_levels_t &p, hipStream_t stream);
+hipError_t launch_levels_unpack(const x266_levels_t &p, hipStream_t stream);
+unsigned levels_scan_chunk();
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

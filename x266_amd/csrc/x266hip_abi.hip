@@ -22,6 +22,7 @@
 #include "../../include/x266hip.h"
 #include "x266_args.hpp"
 #include "x266_device.hpp"
+#include "x266_levels.hpp"
 #include "x266_tables.hpp"
 
 using namespace x266;
@@ -1353,6 +1354,35 @@ int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int wi
     return launched(ctx, "intra frame coding launch", launch_intra32_code_frame(d_cur, d_recon, d_level, d_nnz, d_qp, qp, rounding, d_mode_in, d_mode, width, height, ctx->d_fwd,
                                                                                ctx->d_inv_acc, (hipStream_t)stream));
 }
+
+// ---- the compact level stream (levels_kernels.hip, x266_levels.hpp) ------------------------------------------------------------------------
+int xLevelsPackGpu(x266hip_ctx *ctx, const x266_levels_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::levels_pack(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "level pack launch", launch_levels_pack(*p, (hipStream_t)stream));
+}
+
+int xLevelsUnpackGpu(x266hip_ctx *ctx, const x266_levels_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::levels_unpack(p)) return refuse(ctx, __func__, why);
+    if (p->n_regions == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "level unpack launch", launch_levels_unpack(*p, (hipStream_t)stream));
+}
+
+int xLevelScan(int size, uint16_t *pos)
+{
+    if (!pos || (size != 4 && size != 8 && size != 16 && size != 32)) return X266HIP_EINVAL;
+    const unsigned n = (unsigned)size, k = size == 4 ? 0u : size == 8 ? 1u : size == 16 ? 2u : 3u;
+    for (unsigned s = 0; s < n * n / 16; ++s)                               // block 0 of a region of this class: CG bit s is scan position s
+        for (unsigned i = 0; i < 16; ++i) pos[s * 16 + i] = (uint16_t)(level_cg_origin(k, s) + (level_scan4(i) >> 2) * n + (level_scan4(i) & 3u));
+    return X266HIP_OK;
+}
+
+unsigned xLevelsScanChunk(void) { return levels_scan_chunk(); }
 
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
