@@ -961,6 +961,68 @@ typedef struct x266_levels_t {
 int xLevelsPackGpu  (x266hip_ctx *ctx, const x266_levels_t *p, void *stream);
 int xLevelsUnpackGpu(x266hip_ctx *ctx, const x266_levels_t *p, void *stream);
 
+/* ---- source analysis: tile activity, the adaptive qp map and fade weights, in front of the searches and the coding calls ----
+ * One pass over the tiled source frame gives per-tile sums and sums of squares; from them come the qp byte per region that
+ * xQuantRegionsGpu, xDct32CodeCtuTilesGpu, xIntra32CodeFrameGpu and x266_deblock_t take as d_qp, and the x266_wp_t of the
+ * bi-directional calls.  No upstream counterpart: x264's adaptive quantisation and weight analysis, as recalled; the arithmetic here
+ * is the contract.  Frame sides are positive multiples of 16; tiles are 16x16 in raster order, width / 16 per row.
+ *
+ * Per tile (m_Y 256 bytes; m_C even bytes U, odd bytes V, 64 each; m_I is never read), all uint32 and all products unsigned
+ * (sum_y * sum_y reaches 65280^2, which fits uint32 and not int32):
+ *   sum_y, ssq_y, sum_u, ssq_u, sum_v, ssq_v                  the sums of the samples and of their squares
+ *   energy  = (ssq_y - ((sum_y * sum_y) >> 8)) + (ssq_u - ((sum_u * sum_u) >> 6)) + (ssq_v - ((sum_v * sum_v) >> 6))   <= 6242400
+ *   log2_q8 = L(energy)
+ * L(e) = floor(256 log2(max(e, 1))), defined by: e = max(e, 1); k = 31 - clz(e); m = (uint64)e << (31 - k); f = 0; eight times
+ * { m = (m * m) >> 31; f <<= 1; if (m >> 32) { f |= 1; m >>= 1; } }; L = (k << 8) | f.  L(0) = L(1) = 0, L(2) = 256, L(3) = 405,
+ * L(1000) = 2551, L(6242400) = 5778.
+ * Frame totals d_total[8]: the six sums over all tiles, then the sum of log2_q8, then the number of tiles.
+ *
+ * Per-tile offset in Q8: off = clamp((strength_q8 * (log2_q8 - ref_q8)) >> 8, -3072, 3072), the shift arithmetic.  mode 1 (fixed
+ * reference): ref_q8 = 3693.  mode 2 (frame mean): ref_q8 = (d_total[6] + n_tiles / 2) / n_tiles, n_tiles the frame's.
+ * Per-region qp d_qp[6 ctu + q]: CTUs are ceil(width / 64) x ceil(height / 64) in raster order; tile (tx, ty) lies in CTU
+ * (tx >> 2, ty >> 2), quadrant q = ((ty >> 1) & 1) * 2 + ((tx >> 1) & 1).  For q = 0..3, S is the sum of off over the quadrant's
+ * in-frame tiles and n their number; for q = 4, 5 both run over all in-frame tiles of the CTU.  delta = floor((2 S + 256 n) / (512 n))
+ * (floor division: a mean offset of -128 gives 0, -129 gives -1, 128 gives 1), 0 when n = 0, and
+ * qp = clamp(base qp + delta + (q >= 4 ? chroma_qp_offset : 0), 0, 51).  A region wholly outside the frame still gets its byte.
+ *
+ * Both device calls take one host struct, read during the call; the pointers in it are device pointers (alignments: the field
+ * comments).  xAqStatsGpu reads d_src and writes every record of d_tile, then d_total: two launches on the caller's stream, the
+ * second ONE workgroup that adds the records xAqTotalsChunk() at a time -- integer sums, no atomics, the same bytes on every run.
+ * It looks at d_src, d_tile, d_total, width and height only.  xAqDecideGpu reads d_tile and d_total on the device (no host round
+ * trip) and writes d_offset and d_qp, either of which may be NULL, not both; one launch.  Neither call allocates; both can be
+ * captured into one graph.
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned required buffer, a
+ * side that is not a positive multiple of 16, a span that does not fit in the address space, an output overlapping any other
+ * buffer of the call, and in xAqDecideGpu a mode other than 1 or 2 or a scalar outside the ranges below.  The extents are
+ * width * height * 2 (d_src), n_tiles * 32 (d_tile), 64 bytes (d_total), n_tiles * 2 (d_offset) and 6 n_ctu (d_qp). */
+typedef struct x266_aq_tile_t {
+    uint32_t sum_y, ssq_y, sum_u, ssq_u, sum_v, ssq_v, energy, log2_q8;
+} x266_aq_tile_t; /* 32 bytes */
+typedef struct x266_aq_t {
+    const x266_ref_block_t *d_src;     /* [n_tiles], 16-byte aligned; stats reads, decide ignores (may be NULL there)  */
+    x266_aq_tile_t *d_tile;            /* [n_tiles], 16-byte aligned; stats writes, decide reads                       */
+    int64_t  *d_total;                 /* [8], 8-byte aligned; stats writes, decide reads                              */
+    int16_t  *d_offset;                /* [n_tiles] Q8 or NULL, 2-byte aligned; decide writes                          */
+    uint8_t  *d_qp;                    /* [6 n_ctu] or NULL, any alignment; decide writes; one of the two is required  */
+    int width, height;
+    int mode;                          /* 1 or 2                                                                       */
+    int strength_q8;                   /* 0..1024                                                                      */
+    int qp;                            /* 0..51, the base qp                                                           */
+    int chroma_qp_offset;              /* -12..12                                                                      */
+} x266_aq_t;
+int xAqStatsGpu (x266hip_ctx *ctx, const x266_aq_t *p, void *stream);
+int xAqDecideGpu(x266hip_ctx *ctx, const x266_aq_t *p, void *stream);
+/* Records the totals' workgroup of xAqStatsGpu takes per step (a test walks tile counts around it). */
+int xAqTotalsChunk(void);
+/* Fade weights from the totals of two frames of one size (host only; reads 8 int64 each, host memory).  list is 0 or 1: the call
+ * writes wp->w[list][*] and wp->o[list][*] and reads wp->log2_denom, which the caller sets.  Per plane p of Y, U, V: N = the plane's
+ * sample count (n_tiles * 256 for Y, n_tiles * 64 for U and V), var = ssq * N - sum^2, d = log2_denom[p ? 1 : 0],
+ *   w = var_ref == 0 ? 1 << d : (isqrt((var_cur << (2 d + 2)) / var_ref) + 1) >> 1, then clamped to 1..127
+ *   o = clamp(floor((2 (sum_cur 2^d - sum_ref w) + N 2^d) / (2 N 2^d)), -128, 127)
+ * in exact integers (the variance products pass 2^63 at 8K).  X266HIP_EINVAL: list not 0 or 1, a NULL pointer, a log2_denom above
+ * 7, cur[7] != ref[7], a tile count outside 1..2^24 or a negative total. */
+int xWeightsFromTotals(const int64_t cur[8], const int64_t ref[8], int list, x266_wp_t *wp);
+
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */

@@ -7,7 +7,9 @@ C/C++ host would.  It contains no arithmetic and no fallback: if the library
 or a gfx950 device is missing, calls raise.
 """
 from ._lib import (X266Error, Codec, lib_path, load_library, build_library,  # noqa: F401
-                   pack_diff_rows, pack_dct_word, LevelsParams, LEVEL_REGION_DTYPE, level_scan, levels_scan_chunk)
+                   pack_diff_rows, pack_dct_word, LevelsParams, LEVEL_REGION_DTYPE, level_scan, levels_scan_chunk,
+                   AqParams, AQ_TILE_DTYPE, aq_totals_chunk)
 
 __all__ = ["X266Error", "Codec", "lib_path", "load_library", "build_library",
-           "pack_diff_rows", "pack_dct_word", "LevelsParams", "LEVEL_REGION_DTYPE", "level_scan", "levels_scan_chunk"]
+           "pack_diff_rows", "pack_dct_word", "LevelsParams", "LEVEL_REGION_DTYPE", "level_scan", "levels_scan_chunk",
+           "AqParams", "AQ_TILE_DTYPE", "aq_totals_chunk"]

@@ -35,6 +35,16 @@ class LevelsParams(ctypes.Structure):
 LEVEL_REGION_DTYPE = np.dtype([("cg_mask", "<u8"), ("offset", "<u8"), ("n_words", "<u4"), ("n_nz", "<u4"), ("sum_abs", "<u4"), ("max_abs", "<u4")])
 
 
+class AqParams(ctypes.Structure):
+    """x266_aq_t of include/x266hip.h"""
+    _fields_ = [("d_src", _P), ("d_tile", _P), ("d_total", _P), ("d_offset", _P), ("d_qp", _P), ("width", ctypes.c_int), ("height", ctypes.c_int),
+                ("mode", ctypes.c_int), ("strength_q8", ctypes.c_int), ("qp", ctypes.c_int), ("chroma_qp_offset", ctypes.c_int)]
+
+
+# x266_aq_tile_t of include/x266hip.h
+AQ_TILE_DTYPE = np.dtype([(name, "<u4") for name in ("sum_y", "ssq_y", "sum_u", "ssq_u", "sum_v", "ssq_v", "energy", "log2_q8")])
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -148,6 +158,10 @@ def load_library(path=None):
     L.xLevelScan.argtypes = [ctypes.c_int, _P]
     L.xLevelsScanChunk.argtypes = []
     L.xLevelsScanChunk.restype = ctypes.c_uint
+    L.xAqStatsGpu.argtypes = [_P, ctypes.POINTER(AqParams), _P]
+    L.xAqDecideGpu.argtypes = [_P, ctypes.POINTER(AqParams), _P]
+    L.xAqTotalsChunk.argtypes = []
+    L.xWeightsFromTotals.argtypes = [_P, _P, ctypes.c_int, ctypes.POINTER(WpParams)]
     L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xIntra32CodeFrameGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
@@ -193,6 +207,11 @@ def level_scan(size):
 def levels_scan_chunk():
     """xLevelsScanChunk: regions the offset scan of xLevelsPackGpu takes per step"""
     return int(load_library().xLevelsScanChunk())
+
+
+def aq_totals_chunk():
+    """xAqTotalsChunk: tile records the totals' workgroup of xAqStatsGpu takes per step"""
+    return int(load_library().xAqTotalsChunk())
 
 
 def pack_diff_rows(mat, first_row):
@@ -1234,6 +1253,53 @@ class Codec:
         self.levels_unpack_dev(p)
         self.stream_sync()
         return d_lv.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n)
+
+    # -- source analysis: tile activity, the qp map, fade weights ---------------------------------------
+    @staticmethod
+    def aq_params(d_src=0, d_tile=0, d_total=0, d_offset=0, d_qp=0, width=0, height=0, mode=1, strength_q8=256, qp=0, chroma_qp_offset=0):
+        """an x266_aq_t from device addresses (0: NULL)"""
+        return AqParams(d_src or None, d_tile or None, d_total or None, d_offset or None, d_qp or None, int(width), int(height), int(mode), int(strength_q8),
+                        int(qp), int(chroma_qp_offset))
+
+    def aq_stats_dev(self, params, stream=0):
+        self._check(self.L.xAqStatsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xAqStatsGpu")
+
+    def aq_decide_dev(self, params, stream=0):
+        self._check(self.L.xAqDecideGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xAqDecideGpu")
+
+    def aq_stats(self, tiles, w, h):
+        """numpy convenience around xAqStatsGpu: the tile array of a w x h frame -> (records [n_tiles] of AQ_TILE_DTYPE, totals int64 [8])"""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        assert src.size == w * h * 2
+        n = (w // 16) * (h // 16)
+        d_src, d_tile, d_total = self._upload(src), self.alloc(32 * n), self.alloc(64)
+        self.aq_stats_dev(self.aq_params(d_src.ptr, d_tile.ptr, d_total.ptr, width=w, height=h))
+        self.stream_sync()
+        return d_tile.download(np.uint8, 32 * n).view(AQ_TILE_DTYPE), d_total.download(np.int64, 8)
+
+    def aq_decide(self, records, totals, w, h, mode=1, strength_q8=256, qp=32, chroma_qp_offset=0):
+        """numpy convenience around xAqDecideGpu: the records and totals of aq_stats -> (Q8 offsets int16 [n_tiles], qp bytes uint8 [n_ctus, 6])"""
+        rec = np.ascontiguousarray(records, AQ_TILE_DTYPE).ravel()
+        n, n_ctu = (w // 16) * (h // 16), self.ctu_count(w, h)
+        assert rec.size == n
+        d_tile, d_total = self._upload(rec.view(np.uint8)), self._upload(np.ascontiguousarray(totals, np.int64).reshape(8))
+        d_off, d_qp = self.alloc(max(2 * n, 16)), self.alloc(max(6 * n_ctu, 16))
+        self.aq_decide_dev(self.aq_params(0, d_tile.ptr, d_total.ptr, d_off.ptr, d_qp.ptr, w, h, mode, strength_q8, qp, chroma_qp_offset))
+        self.stream_sync()
+        return d_off.download(np.int16, n), d_qp.download(np.uint8, 6 * n_ctu).reshape(n_ctu, 6)
+
+    @staticmethod
+    def weights_from_totals(cur, ref, lst=0, log2_denom=(7, 7), wp=None):
+        """xWeightsFromTotals (host, no device): the totals of the current and of the reference frame -> the wp_params object of the
+        bi-directional methods with w[lst] and o[lst] estimated; wp None: a fresh one whose other list holds the default weights at
+        log2_denom (127, the largest weight, at a denominator of 7)"""
+        if wp is None:
+            one = [min(1 << min(int(log2_denom[0]), 7), 127)] + [min(1 << min(int(log2_denom[1]), 7), 127)] * 2
+            wp = Codec.wp_params(w=(one, one), log2_denom=log2_denom)
+        c, r = np.ascontiguousarray(cur, np.int64), np.ascontiguousarray(ref, np.int64)
+        if c.size != 8 or r.size != 8 or load_library().xWeightsFromTotals(_P(c.ctypes.data), _P(r.ctypes.data), int(lst), ctypes.byref(wp)) != 0:
+            raise X266Error("xWeightsFromTotals: list must be 0 or 1, log2_denom 0..7, and the totals those of two frames of one size")
+        return wp
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

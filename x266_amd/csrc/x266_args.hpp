@@ -6,7 +6,8 @@
 // every one of them without a device.  x266hip_abi.hip turns a reason into X266HIP_EINVAL and the text
 // "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.  The two calls of
 // the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
-// driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow.
+// driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow; the two of the source analysis (aq_stats, aq_decide)
+// likewise by tests/cpp/aq_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -477,6 +478,44 @@ inline const char *levels_unpack(const x266_levels_t *p)
                in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), opt(in("d_class", p->d_class, 1, n))};
     b[3].optional = p->cap_words == 0;
     return check(b);
+}
+
+// ---- source analysis ----------------------------------------------------------------------------------------------------------------
+// xAqStatsGpu, xAqDecideGpu: the device pointers are the fields of the host-read x266_aq_t, held by tests/cpp/aq_rules_check.cpp.  Stats
+// looks at d_src, d_tile, d_total and the frame size alone; decide at everything but d_src, and needs one of its two outputs.
+constexpr const char *kAqScalars = "mode must be 1 or 2, strength_q8 0..1024, qp 0..51 and chroma_qp_offset -12..12";
+inline size_t tiles16(int w, int h) { return (size_t)(w / 16) * (size_t)(h / 16); }
+inline const char *aq_stats(const x266_aq_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    const Buf b[] = {out("d_tile", p->d_tile, 16, tiles16(p->width, p->height) * 32), out("d_total", p->d_total, 8, 64),
+                     in("d_src", p->d_src, 16, tile_bytes(p->width, p->height))};
+    return check(b);
+}
+inline const char *aq_decide(const x266_aq_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (p->mode < 1 || p->mode > 2 || p->strength_q8 < 0 || p->strength_q8 > 1024 || p->qp < 0 || p->qp > 51 || p->chroma_qp_offset < -12 ||
+        p->chroma_qp_offset > 12)
+        return kAqScalars;
+    if (!p->d_offset && !p->d_qp) return "d_offset and d_qp are both NULL";
+    const Buf b[] = {opt(out("d_offset", p->d_offset, 2, tiles16(p->width, p->height) * 2)), opt(out("d_qp", p->d_qp, 1, ctus(p->width, p->height) * 6)),
+                     in("d_tile", p->d_tile, 16, tiles16(p->width, p->height) * 32), in("d_total", p->d_total, 8, 64)};
+    return check(b);
+}
+// xWeightsFromTotals (host pointers): the totals of two frames of one size, as xAqStatsGpu writes them
+inline const char *weights_from_totals(const int64_t *cur, const int64_t *ref, int list, const x266_wp_t *wp)
+{
+    if (!cur || !ref || !wp) return kNull;
+    if (list < 0 || list > 1) return "list must be 0 or 1";
+    if (wp->log2_denom[0] > 7 || wp->log2_denom[1] > 7) return "log2_denom must be 0..7";
+    if (cur[7] != ref[7]) return "the two frames differ in size";
+    if (cur[7] < 1 || cur[7] > ((int64_t)1 << 24)) return "the tile count must be 1..2^24";
+    for (int i = 0; i < 7; ++i)
+        if (cur[i] < 0 || ref[i] < 0) return "a total is negative";
+    return nullptr;
 }
 
 // ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------

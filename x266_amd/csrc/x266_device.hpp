@@ -276,6 +276,10 @@ hipError_t launch_alf_apply(const x266_ref_block_t *d_in, x266_ref_block_t *d_ou
 hipError_t launch_levels_pack(const x266_levels_t &p, hipStream_t stream);
 hipError_t launch_levels_unpack(const x266_levels_t &p, hipStream_t stream);
 unsigned levels_scan_chunk();
+// source analysis (aq_kernels.hip): stats = the tile records, then the totals' one workgroup of aq_totals_chunk() records per step
+hipError_t launch_aq_stats(const x266_aq_t &p, hipStream_t stream);
+hipError_t launch_aq_decide(const x266_aq_t &p, hipStream_t stream);
+int aq_totals_chunk();
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

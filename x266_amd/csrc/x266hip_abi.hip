@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/x266hip.h"
+#include "x266_aq.hpp"
 #include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_levels.hpp"
@@ -1383,6 +1384,32 @@ int xLevelScan(int size, uint16_t *pos)
 }
 
 unsigned xLevelsScanChunk(void) { return levels_scan_chunk(); }
+
+// ---- source analysis (aq_kernels.hip, x266_aq.hpp) ---------------------------------------------------------------------------------------------
+int xAqStatsGpu(x266hip_ctx *ctx, const x266_aq_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::aq_stats(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "source statistics launch", launch_aq_stats(*p, (hipStream_t)stream));
+}
+
+int xAqDecideGpu(x266hip_ctx *ctx, const x266_aq_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::aq_decide(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "qp map launch", launch_aq_decide(*p, (hipStream_t)stream));
+}
+
+int xAqTotalsChunk(void) { return aq_totals_chunk(); }
+
+int xWeightsFromTotals(const int64_t cur[8], const int64_t ref[8], int list, x266_wp_t *wp)
+{
+    if (args::weights_from_totals(cur, ref, list, wp)) return X266HIP_EINVAL;
+    for (int plane = 0; plane < 3; ++plane) aq_plane_weight(cur, ref, plane, wp->log2_denom[plane ? 1 : 0], &wp->w[list][plane], &wp->o[list][plane]);
+    return X266HIP_OK;
+}
 
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
