@@ -1023,6 +1023,123 @@ int xAqTotalsChunk(void);
  * 7, cur[7] != ref[7], a tile count outside 1..2^24 or a negative total. */
 int xWeightsFromTotals(const int64_t cur[8], const int64_t ref[8], int list, x266_wp_t *wp);
 
+/* ---- lookahead: half-size frames, frame costs, scene cuts and the propagation tree ----
+ * What a host needs to choose frame types and to weigh a block by what later frames predict from it, on data the device
+ * already holds.  No upstream counterpart: x264's lookahead, as recalled; the arithmetic here is the contract.
+ *
+ * Geometry.  width, height: the full-resolution sides, positive multiples of 32.  The lowres frame is width / 2 x height / 2 (sides
+ * W', H' multiples of 16), an ordinary tiled frame of n / 4 tiles that xSatd8x8SearchFromTilesDev searches as it is (called with
+ * width / 2, height / 2).  n = (width / 16) * (height / 16) is the number of full-resolution tiles AND of lowres 8x8 blocks, both
+ * in raster order, width / 16 per row: block b of the lowres frame (bx = b % (width / 16), by = b / (width / 16), at lowres
+ * sample (8 bx, 8 by)) is tile b of the full-resolution frame.  n_ctu = ceil(width / 64) * ceil(height / 64).
+ *
+ * 1. xLaDownscaleGpu reads d_src and writes m_Y and m_C of every tile of d_low; m_I is neither read nor written.
+ *    low(x, y) = (s(2x, 2y) + s(2x+1, 2y) + s(2x, 2y+1) + s(2x+1, 2y+1) + 2) >> 2 on the luma plane, and on the U plane (the even
+ *    bytes of m_C) and the V plane (the odd bytes) separately: samples 1, 2, 3, 4 give 3; 0, 0, 0, 1 give 0; 0, 0, 1, 1 give 1;
+ *    255, 255, 255, 254 give 255.  One launch.
+ *
+ * 2. xLaIntraCostsGpu reads m_Y of d_low and writes d_intra[b] and, when non-NULL, d_mode[b].  Neighbours of the block at
+ *    (x0, y0) = (8 bx, 8 by), from the lowres frame's own samples p: top[x] = p(min(x0 + x, W' - 1), y0 - 1) and
+ *    left[y] = p(x0 - 1, min(y0 + y, H' - 1)) for 0..8; TR = top[8], BL = left[8].  y0 == 0 and x0 == 0: all 18 are 128; only
+ *    y0 == 0: every top[x] = left[0]; only x0 == 0: every left[y] = top[0].  Candidates, tried in this order, with the library's
+ *    mode numbers:
+ *       0 planar      ((7 - x) left[y] + (x + 1) TR + (7 - y) top[x] + (y + 1) BL + 8) >> 4
+ *       1 DC          (sum top[0..7] + sum left[0..7] + 8) >> 4, no edge filter
+ *      10 horizontal  left[y]
+ *      26 vertical    top[x]
+ *    With top = 10, 20, .., 90 and left = 100, 110, .., 180: planar(0, 0) = 65, planar(x = 3, y = 5) = 133, planar(7, 7) = 135,
+ *    DC = 90.  cost(m) = satd8x8(cur - pred_m), the library's one SATD, (sum |H| + 2) >> 2 over the 8x8 Hadamard transform of the
+ *    difference, at most 32640: a difference of 1 everywhere costs 16, one of +-255 in a checkerboard 4080, a block of 0 / 255
+ *    in a checkerboard against 128 costs 2048.  The least cost wins, the first candidate of equal ones (a constant frame: cost 0,
+ *    mode 0).  One launch.
+ *
+ * 3. xLaFrameCostGpu reads d_intra, d_mode (NULL: every mode counts as 0), d_inter0 and d_inter1 -- x266_me_result_t[n], what a
+ *    search of two lowres frames writes; either or both may be NULL, with both NULL the call gives an I frame's cost -- and
+ *    writes d_block[b], then d_total.  ci = d_intra[b] + intra_penalty (uint32; every cost is expected below 2^31).  best = list
+ *    0 if present; list 1 replaces it only if its cost is strictly lower; intra replaces it only if ci is strictly lower, or if
+ *    no list is present: ties go to list 0, then list 1, then intra.  Costs (l0, l1, d_intra) = (500, 500, 400) with penalty
+ *    100: kind 1, cost 500; (500, 499, 400): kind 2, cost 499; (500, 500, 399): kind 0, cost 499.
+ *    d_total (int64[8]): 0 sum of cost, 1 sum of intra, 2 / 3 / 4 the numbers of kind-0 / 1 / 2 blocks, 5 the sum of d_inter0's
+ *    costs over ALL blocks (0 if NULL), 6 the same for d_inter1, 7 n.  Two launches on the caller's stream, the second ONE
+ *    workgroup that adds xLaTotalsChunk() blocks per step: integer sums, no atomics, the same bytes on every run.
+ *
+ * 4. xSceneCutFromTotals (host only, plain integers; total: host memory, the result of a P decision against the previous frame).
+ *    p = total[0], i = total[1], tmax = threshold_q8 << 8 (Q16), tmin = tmax >> 2, g = frames_since_key.  bias (Q16):
+ *    4 g <= min_keyint: tmin >> 2; else g <= min_keyint: tmin * g / min_keyint; else tmin + (tmax - tmin) * (g - min_keyint) /
+ *    (max_keyint - min_keyint), which is tmax when max_keyint == min_keyint.  Returns 1 when p * 65536 >= (65536 - bias) * i, else
+ *    0.  threshold_q8 102, keyints 25 / 250: g = 5 gives bias 1632, g = 10 gives 2611, g = 100 gives 13056, and there p = 90000
+ *    against i = 100000 is a cut, p = 80000 is none; keyints 25 / 25 at g = 30: 26112.  Returns -1 for a NULL total, threshold_q8
+ *    outside 0..256, g < 0, min_keyint < 1, max_keyint < min_keyint, a negative total, total[7] outside 1..2^24, or p or i
+ *    above 2^40 (every product fits int64).
+ *
+ * 5. xLaPropagateGpu, one step of the propagation tree: reads d_block and d_prop (uint64[n], what this frame has received so
+ *    far; NULL counts as zeros) and ADDS into d_prop_ref0 and d_prop_ref1 (uint64[n], the accumulators of the list-0 and list-1
+ *    reference frames), which the caller zeroes once, before the first frame that refers to them.  Either target may be NULL:
+ *    blocks of that kind are skipped (both NULL: nothing is launched).  Per block: skipped when kind == 0 or intra == 0;
+ *    q = min(d_prop[b], 2^32 - 1); inter = min(cost, intra); amount = ((intra + q) * (intra - inter)) / intra, floor, in
+ *    unsigned 64 bits (intra is expected below 2^31); px = 8 bx + mvx, py = 8 by + mvy; X = floor(px / 8), dx = px - 8 X in
+ *    0..7, Y and dy likewise.  Targets and weights w: (X, Y) (8 - dx)(8 - dy); (X + 1, Y) dx (8 - dy); (X, Y + 1) (8 - dx) dy;
+ *    (X + 1, Y + 1) dx dy.  A target with w > 0 inside the block grid receives (amount * w + 32) >> 6; one outside is dropped and no
+ *    byte is touched for it.  intra 1000, cost 600, d_prop 5000: amount 2400 (cost 1200: 0).  Block (1, 3) with mv (-11, 5): px = -3,
+ *    X = -1, dx = 5, py = 29, Y = 3, dy = 5, weights 9, 15, 15, 25; (-1, 3) and (-1, 4) are dropped, (0, 3) receives 563 and (0, 4)
+ *    938 (and 338 and 563 would have gone to the other two).  The adds are 64-bit integer atomic adds: they commute, so the result is
+ *    the same bytes on every run whatever the schedule; one add is below 2^39 and n at most 2^24, so no sum overflows.  One launch.
+ *
+ * 6. xLaTreeQpGpu reads d_block (intra only), d_prop (NULL counts as zeros) and d_aq_offset (int16 Q8 per tile as xAqDecideGpu
+ *    writes d_offset; NULL counts as zeros) and writes d_offset and / or d_qp: either may be NULL, not both.  Per tile t:
+ *    P = min(d_prop[t], 2^32 - 1 - intra); gain = intra == 0 ? 0 : (strength_q8 * (L(intra + P) - L(intra))) >> 8 with L the
+ *    source analysis' (never negative); off = clamp(aq - gain, -3072, 3072).  intra 1000 (L = 2551) with P = 3000 (L(4000) =
+ *    3063): gain 1024 at strength 512, 2048 at 1024; intra 1 with d_prop 2^40 at 1024: 32764.  d_qp[6 ctu + q] comes from these
+ *    offsets, the base qp and chroma_qp_offset by exactly the rule of xAqDecideGpu above (CTU and quadrant of a tile, delta, the
+ *    clamp; a region wholly outside the frame still gets its byte).  One launch.
+ *
+ * All device calls take one host struct, read during the call; the pointers in it are device pointers (alignments: the field
+ * comments).  Each call looks only at the fields named for it, width and height.  No call allocates; all can be captured into
+ * one graph (the search between them needs xHipMeScratchReserve first).
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned required buffer, a
+ * side that is not a positive multiple of 32, a span that does not fit in the address space, a scalar outside the range its
+ * field comment states, xLaTreeQpGpu without an output, and an output -- or an accumulator being added into -- that overlaps
+ * any other buffer of the call (d_prop_ref0 == d_prop_ref1 included).  The extents are width * height * 2 (d_src), width * height
+ * / 2 (d_low), 4 n (d_intra), n (d_mode), 8 n (d_inter0, d_inter1, d_prop, d_prop_ref0, d_prop_ref1), 16 n (d_block), 64 bytes
+ * (d_total), 2 n (d_aq_offset, d_offset) and 6 n_ctu (d_qp). */
+typedef struct x266_la_block_t {
+    uint32_t cost;        /* the minimum; with the penalty when intra        */
+    uint32_t intra;       /* d_intra[b], without the penalty                 */
+    int16_t  mvx, mvy;    /* the chosen list's vector, lowres pels; 0,0 intra */
+    uint8_t  kind;        /* 0 intra, 1 list 0, 2 list 1                     */
+    uint8_t  mode;        /* the intra mode (always, also for inter blocks)  */
+    uint16_t reserved;    /* written as 0                                    */
+} x266_la_block_t; /* 16 bytes */
+typedef struct x266_la_t {
+    const x266_ref_block_t *d_src;         /* [n], 16-byte aligned; downscale reads                                             */
+    x266_ref_block_t *d_low;               /* [n / 4], 16-byte aligned; downscale writes, intra costs reads                     */
+    uint32_t *d_intra;                     /* [n], 4-byte aligned; intra costs writes, frame cost reads                         */
+    uint8_t  *d_mode;                      /* [n] or NULL, any alignment; intra costs writes, frame cost reads                  */
+    const x266_me_result_t *d_inter0;      /* [n] or NULL, 8-byte aligned; frame cost reads                                     */
+    const x266_me_result_t *d_inter1;      /* [n] or NULL, 8-byte aligned; frame cost reads                                     */
+    x266_la_block_t *d_block;              /* [n], 16-byte aligned; frame cost writes, propagate and tree qp read               */
+    int64_t  *d_total;                     /* [8], 8-byte aligned; frame cost writes                                            */
+    const uint64_t *d_prop;                /* [n] or NULL, 8-byte aligned; propagate and tree qp read                           */
+    uint64_t *d_prop_ref0;                 /* [n] or NULL, 8-byte aligned; propagate adds into                                  */
+    uint64_t *d_prop_ref1;                 /* [n] or NULL, 8-byte aligned; propagate adds into                                  */
+    const int16_t *d_aq_offset;            /* [n] Q8 or NULL, 2-byte aligned; tree qp reads                                     */
+    int16_t  *d_offset;                    /* [n] Q8 or NULL, 2-byte aligned; tree qp writes                                    */
+    uint8_t  *d_qp;                        /* [6 n_ctu] or NULL, any alignment; tree qp writes; one of the two is required      */
+    int width, height;                     /* the full-resolution sides, positive multiples of 32                               */
+    int intra_penalty;                     /* 0..65535; frame cost                                                              */
+    int strength_q8;                       /* 0..1024; tree qp                                                                  */
+    int qp;                                /* 0..51, the base qp; tree qp                                                       */
+    int chroma_qp_offset;                  /* -12..12; tree qp                                                                  */
+} x266_la_t;
+int xLaDownscaleGpu (x266hip_ctx *ctx, const x266_la_t *p, void *stream);
+int xLaIntraCostsGpu(x266hip_ctx *ctx, const x266_la_t *p, void *stream);
+int xLaFrameCostGpu (x266hip_ctx *ctx, const x266_la_t *p, void *stream);
+int xLaPropagateGpu (x266hip_ctx *ctx, const x266_la_t *p, void *stream);
+int xLaTreeQpGpu    (x266hip_ctx *ctx, const x266_la_t *p, void *stream);
+/* Blocks the totals' workgroup of xLaFrameCostGpu takes per step (a test walks block counts around it). */
+int xLaTotalsChunk(void);
+int xSceneCutFromTotals(const int64_t total[8], int threshold_q8, int frames_since_key, int min_keyint, int max_keyint);
+
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */

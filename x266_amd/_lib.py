@@ -45,6 +45,19 @@ class AqParams(ctypes.Structure):
 AQ_TILE_DTYPE = np.dtype([(name, "<u4") for name in ("sum_y", "ssq_y", "sum_u", "ssq_u", "sum_v", "ssq_v", "energy", "log2_q8")])
 
 
+class LaParams(ctypes.Structure):
+    """x266_la_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_src", "d_low", "d_intra", "d_mode", "d_inter0", "d_inter1", "d_block", "d_total", "d_prop", "d_prop_ref0",
+                                        "d_prop_ref1", "d_aq_offset", "d_offset", "d_qp")] + \
+               [(name, ctypes.c_int) for name in ("width", "height", "intra_penalty", "strength_q8", "qp", "chroma_qp_offset")]
+
+
+# x266_la_block_t of include/x266hip.h
+LA_BLOCK_DTYPE = np.dtype([("cost", "<u4"), ("intra", "<u4"), ("mvx", "<i2"), ("mvy", "<i2"), ("kind", "u1"), ("mode", "u1"), ("reserved", "<u2")])
+LA_CALLS = {"downscale": "xLaDownscaleGpu", "intra_costs": "xLaIntraCostsGpu", "frame_cost": "xLaFrameCostGpu", "propagate": "xLaPropagateGpu",
+            "tree_qp": "xLaTreeQpGpu"}
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -162,6 +175,10 @@ def load_library(path=None):
     L.xAqDecideGpu.argtypes = [_P, ctypes.POINTER(AqParams), _P]
     L.xAqTotalsChunk.argtypes = []
     L.xWeightsFromTotals.argtypes = [_P, _P, ctypes.c_int, ctypes.POINTER(WpParams)]
+    for name in LA_CALLS.values():
+        getattr(L, name).argtypes = [_P, ctypes.POINTER(LaParams), _P]
+    L.xLaTotalsChunk.argtypes = []
+    L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
     L.xIntra32CodeFrameGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
     L.xTransformCtuFromTilesDev.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]
@@ -212,6 +229,21 @@ def levels_scan_chunk():
 def aq_totals_chunk():
     """xAqTotalsChunk: tile records the totals' workgroup of xAqStatsGpu takes per step"""
     return int(load_library().xAqTotalsChunk())
+
+
+def la_totals_chunk():
+    """xLaTotalsChunk: blocks the totals' workgroup of xLaFrameCostGpu takes per step"""
+    return int(load_library().xLaTotalsChunk())
+
+
+def scene_cut_from_totals(total, threshold_q8, frames_since_key, min_keyint, max_keyint):
+    """xSceneCutFromTotals (host, no device): the totals of a P decision against the previous frame -> True for a scene cut"""
+    t = np.ascontiguousarray(total, np.int64)
+    rc = -1 if t.size != 8 else load_library().xSceneCutFromTotals(_P(t.ctypes.data), int(threshold_q8), int(frames_since_key), int(min_keyint), int(max_keyint))
+    if rc < 0:
+        raise X266Error("xSceneCutFromTotals: threshold_q8 must be 0..256, frames_since_key >= 0, 1 <= min_keyint <= max_keyint, and the totals those of "
+                        "xLaFrameCostGpu")
+    return bool(rc)
 
 
 def pack_diff_rows(mat, first_row):
@@ -1300,6 +1332,90 @@ class Codec:
         if c.size != 8 or r.size != 8 or load_library().xWeightsFromTotals(_P(c.ctypes.data), _P(r.ctypes.data), int(lst), ctypes.byref(wp)) != 0:
             raise X266Error("xWeightsFromTotals: list must be 0 or 1, log2_denom 0..7, and the totals those of two frames of one size")
         return wp
+
+    # -- the lookahead: half-size frames, frame costs, the propagation tree --------------------------------
+    @staticmethod
+    def la_params(width=0, height=0, intra_penalty=0, strength_q8=256, qp=0, chroma_qp_offset=0, **pointers):
+        """an x266_la_t from device addresses by field name (absent or 0: NULL)"""
+        names = [f[0] for f in LaParams._fields_[:14]]
+        unknown = set(pointers) - set(names)
+        if unknown:
+            raise TypeError("la_params: no such field: %s" % sorted(unknown))
+        return LaParams(*([pointers.get(n) or None for n in names] + [int(width), int(height), int(intra_penalty), int(strength_q8), int(qp), int(chroma_qp_offset)]))
+
+    def _la_dev(self, call, params, stream):
+        self._check(getattr(self.L, LA_CALLS[call])(self.ctx, ctypes.byref(params) if params is not None else None, stream), LA_CALLS[call])
+
+    def la_downscale_dev(self, params, stream=0):
+        self._la_dev("downscale", params, stream)
+
+    def la_intra_costs_dev(self, params, stream=0):
+        self._la_dev("intra_costs", params, stream)
+
+    def la_frame_cost_dev(self, params, stream=0):
+        self._la_dev("frame_cost", params, stream)
+
+    def la_propagate_dev(self, params, stream=0):
+        self._la_dev("propagate", params, stream)
+
+    def la_tree_qp_dev(self, params, stream=0):
+        self._la_dev("tree_qp", params, stream)
+
+    def la_downscale(self, tiles, w, h):
+        """numpy convenience around xLaDownscaleGpu: the tile array of a w x h frame -> the lowres tile array [n / 4, 512] (m_I zero)"""
+        src = np.ascontiguousarray(tiles, np.uint8).ravel()
+        assert src.size == w * h * 2
+        d_src, d_low = self._upload(src), self._upload(np.zeros(w * h // 2, np.uint8))
+        self.la_downscale_dev(self.la_params(w, h, d_src=d_src.ptr, d_low=d_low.ptr))
+        self.stream_sync()
+        return d_low.download(np.uint8, w * h // 2).reshape(-1, 512)
+
+    def la_intra_costs(self, low_tiles, w, h):
+        """numpy convenience around xLaIntraCostsGpu: the lowres tile array of a w x h frame -> (costs uint32 [n], modes uint8 [n])"""
+        low = np.ascontiguousarray(low_tiles, np.uint8).ravel()
+        n = (w // 16) * (h // 16)
+        assert low.size == w * h // 2
+        d_low, d_intra, d_mode = self._upload(low), self.alloc(4 * n), self.alloc(max(n, 16))
+        self.la_intra_costs_dev(self.la_params(w, h, d_low=d_low.ptr, d_intra=d_intra.ptr, d_mode=d_mode.ptr))
+        self.stream_sync()
+        return d_intra.download(np.uint32, n), d_mode.download(np.uint8, n)
+
+    def la_frame_cost(self, intra, mode, inter0, inter1, w, h, intra_penalty=0):
+        """numpy convenience around xLaFrameCostGpu: intra costs, modes (or None) and the lists' search records (8 bytes each, or None)
+        -> (records [n] of LA_BLOCK_DTYPE, totals int64 [8])"""
+        n = (w // 16) * (h // 16)
+        up = lambda a, dtype: 0 if a is None else self._upload(np.ascontiguousarray(a, dtype).view(np.uint8).ravel())
+        bufs = [up(intra, np.uint32), up(mode, np.uint8), up(inter0, None), up(inter1, None)]
+        assert bufs[0] and bufs[0].nbytes >= 4 * n
+        d_block, d_total = self.alloc(16 * n), self.alloc(64)
+        ptr = [b.ptr if b else 0 for b in bufs]
+        self.la_frame_cost_dev(self.la_params(w, h, intra_penalty, d_intra=ptr[0], d_mode=ptr[1], d_inter0=ptr[2], d_inter1=ptr[3], d_block=d_block.ptr,
+                                              d_total=d_total.ptr))
+        self.stream_sync()
+        return d_block.download(np.uint8, 16 * n).view(LA_BLOCK_DTYPE), d_total.download(np.int64, 8)
+
+    def la_propagate(self, records, prop, ref0, ref1, w, h):
+        """numpy convenience around xLaPropagateGpu: the records, what the frame received (uint64 [n] or None) and the two
+        accumulators as they stand (uint64 [n] or None) -> the two accumulators after the step (None stays None)"""
+        n = (w // 16) * (h // 16)
+        up = lambda a, dtype: 0 if a is None else self._upload(np.ascontiguousarray(a, dtype).view(np.uint8).ravel())
+        d_block, d_prop, d_r0, d_r1 = up(records, LA_BLOCK_DTYPE), up(prop, np.uint64), up(ref0, np.uint64), up(ref1, np.uint64)
+        self.la_propagate_dev(self.la_params(w, h, d_block=d_block.ptr, d_prop=d_prop and d_prop.ptr, d_prop_ref0=d_r0 and d_r0.ptr,
+                                             d_prop_ref1=d_r1 and d_r1.ptr))
+        self.stream_sync()
+        return [d.download(np.uint64, n) if d else None for d in (d_r0, d_r1)]
+
+    def la_tree_qp(self, records, prop, aq_offset, w, h, strength_q8=256, qp=32, chroma_qp_offset=0):
+        """numpy convenience around xLaTreeQpGpu: the records, what the frame received and the AQ offsets (either may be None)
+        -> (Q8 offsets int16 [n], qp bytes uint8 [n_ctus, 6])"""
+        n, n_ctu = (w // 16) * (h // 16), self.ctu_count(w, h)
+        up = lambda a, dtype: 0 if a is None else self._upload(np.ascontiguousarray(a, dtype).view(np.uint8).ravel())
+        d_block, d_prop, d_aq = up(records, LA_BLOCK_DTYPE), up(prop, np.uint64), up(aq_offset, np.int16)
+        d_off, d_qp = self.alloc(max(2 * n, 16)), self.alloc(max(6 * n_ctu, 16))
+        self.la_tree_qp_dev(self.la_params(w, h, 0, strength_q8, qp, chroma_qp_offset, d_block=d_block.ptr, d_prop=d_prop and d_prop.ptr,
+                                           d_aq_offset=d_aq and d_aq.ptr, d_offset=d_off.ptr, d_qp=d_qp.ptr))
+        self.stream_sync()
+        return d_off.download(np.int16, n), d_qp.download(np.uint8, 6 * n_ctu).reshape(n_ctu, 6)
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

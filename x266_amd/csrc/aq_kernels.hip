@@ -6,7 +6,7 @@
 // half j & 1 (8 bytes: four (U, V) pairs) -- 384 of the tile's 512 bytes, m_I is never touched.  Sums are v_sad_u8 against 0, squares
 // v_dot4_u32_u8 of a dword with itself, U and V split by their byte masks; the row of 16 lanes is summed by DPP and its first lane
 // writes the 32-byte record.  Totals: ONE workgroup walks the records kAqTotalsChunk at a time, as a linear stream of 16-byte halves --
-// integer sums in a fixed order, no atomics.  Decide: 16 lanes per CTU, one per tile; the quadrant and CTU sums are four xor-shuffles inside the row.
+// integer sums in a fixed order, no atomics.  Decide: 16 lanes per CTU, one per tile; the quadrant and CTU sums are four xor-shuffles inside the row (aq_ctu_qp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -135,20 +135,7 @@ __global__ __launch_bounds__(64 * kAqWavesPerWg) void aq_decide_kernel(const x26
         n = 1;
         if (offset) offset[t] = (int16_t)s;
     }
-    // quadrant q = ((i >> 3) & 1) * 2 + ((i >> 1) & 1): its four tiles differ in bits 0 and 2 of i; the CTU's in all four bits
-    int packed = s * 32 + n;                                                // |s| <= 16 * 3072 and n <= 16 over a CTU: one register, s = packed >> 5 after
-    packed += __shfl_xor(packed, 1, 64);                                    // the sums (n < 32, and the shift is arithmetic)
-    packed += __shfl_xor(packed, 4, 64);
-    int all = packed + __shfl_xor(packed, 2, 64);
-    all += __shfl_xor(all, 8, 64);
-    // lanes 0..3 of the row take quadrant i from its first lane, lanes 4 and 5 the whole CTU
-    const int from = (int)(lane & 48u) + (int)((i & 1) * 2 + ((i >> 1) & 1) * 8);
-    const int quad = __shfl(packed, from, 64);
-    if (ctu_ok && i < 6 && qp) {
-        const int v = i < 4 ? quad : all;
-        const int count = v & 31, sum = (v - count) / 32;
-        qp[ctu * 6 + i] = (uint8_t)aq_region_qp(base_qp, aq_delta(sum, count), (int)i, chroma_qp_offset);
-    }
+    aq_ctu_qp(s, n, lane, ctu_ok, ctu, base_qp, chroma_qp_offset, qp);
 }
 
 }  // namespace

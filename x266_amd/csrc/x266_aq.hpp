@@ -67,6 +67,29 @@ __host__ __device__ inline unsigned aq_region_qp(int base_qp, int delta, int q, 
     return (unsigned)(qp < 0 ? 0 : qp > 51 ? 51 : qp);
 }
 
+#ifdef __HIPCC__
+// The six qp bytes of a CTU from its tiles' offsets (xAqDecideGpu, xLaTreeQpGpu): a row of 16 lanes per CTU, lane i = lane & 15 its tile
+// (i & 3, i >> 2) with offset s and n = 1, or s = n = 0 for a tile outside the frame.  Every lane of the wave calls it.
+__device__ __forceinline__ void aq_ctu_qp(int s, int n, unsigned lane, bool ctu_ok, size_t ctu, int base_qp, int chroma_qp_offset, uint8_t *qp)
+{
+    const unsigned i = lane & 15;
+    // quadrant q = ((i >> 3) & 1) * 2 + ((i >> 1) & 1): its four tiles differ in bits 0 and 2 of i; the CTU's in all four bits
+    int packed = s * 32 + n;                                                // |s| <= 16 * 3072 and n <= 16 over a CTU: one register, s = packed >> 5 after
+    packed += __shfl_xor(packed, 1, 64);                                    // the sums (n < 32, and the shift is arithmetic)
+    packed += __shfl_xor(packed, 4, 64);
+    int all = packed + __shfl_xor(packed, 2, 64);
+    all += __shfl_xor(all, 8, 64);
+    // lanes 0..3 of the row take quadrant i from its first lane, lanes 4 and 5 the whole CTU
+    const int from = (int)(lane & 48u) + (int)((i & 1) * 2 + ((i >> 1) & 1) * 8);
+    const int quad = __shfl(packed, from, 64);
+    if (ctu_ok && i < 6 && qp) {
+        const int v = i < 4 ? quad : all;
+        const int count = v & 31, sum = (v - count) / 32;
+        qp[ctu * 6 + i] = (uint8_t)aq_region_qp(base_qp, aq_delta(sum, count), (int)i, chroma_qp_offset);
+    }
+}
+#endif
+
 // ---- fade weights from two frames' totals (host only: the variance products pass 2^63 at 8K) -----------------------------------------------
 typedef unsigned __int128 aq_u128;
 typedef __int128 aq_i128;

@@ -7,7 +7,7 @@
 // "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.  The two calls of
 // the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
 // driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow; the two of the source analysis (aq_stats, aq_decide)
-// likewise by tests/cpp/aq_rules_check.cpp.
+// likewise by tests/cpp/aq_rules_check.cpp, the five of the lookahead (la_*) by tests/cpp/la_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -515,6 +515,70 @@ inline const char *weights_from_totals(const int64_t *cur, const int64_t *ref, i
     if (cur[7] < 1 || cur[7] > ((int64_t)1 << 24)) return "the tile count must be 1..2^24";
     for (int i = 0; i < 7; ++i)
         if (cur[i] < 0 || ref[i] < 0) return "a total is negative";
+    return nullptr;
+}
+
+// ---- lookahead ------------------------------------------------------------------------------------------------------------------------
+// xLaDownscaleGpu, xLaIntraCostsGpu, xLaFrameCostGpu, xLaPropagateGpu, xLaTreeQpGpu: the device pointers are the fields of the host-read
+// x266_la_t, held by tests/cpp/la_rules_check.cpp.  Each call looks at the fields the header names for it; the sides are the
+// full-resolution frame's, multiples of 32; n = tiles16 is the number of lowres blocks.  An accumulator added into counts as an output.
+constexpr const char *kLaPenalty = "intra_penalty must be 0..65535";
+constexpr const char *kLaScalars = "strength_q8 must be 0..1024, qp 0..51 and chroma_qp_offset -12..12";
+inline const char *la_frame(const x266_la_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    return frame(p->width, p->height, 32);
+}
+inline const char *la_downscale(const x266_la_t *p)
+{
+    if (const char *why = la_frame(p)) return why;
+    const Buf b[] = {out("d_low", p->d_low, 16, tile_bytes(p->width, p->height) / 4), in("d_src", p->d_src, 16, tile_bytes(p->width, p->height))};
+    return check(b);
+}
+inline const char *la_intra_costs(const x266_la_t *p)
+{
+    if (const char *why = la_frame(p)) return why;
+    const size_t n = tiles16(p->width, p->height);
+    const Buf b[] = {out("d_intra", p->d_intra, 4, n * 4), opt(out("d_mode", p->d_mode, 1, n)), in("d_low", p->d_low, 16, tile_bytes(p->width, p->height) / 4)};
+    return check(b);
+}
+inline const char *la_frame_cost(const x266_la_t *p)
+{
+    if (const char *why = la_frame(p)) return why;
+    if (p->intra_penalty < 0 || p->intra_penalty > 65535) return kLaPenalty;
+    const size_t n = tiles16(p->width, p->height);
+    const Buf b[] = {out("d_block", p->d_block, 16, n * 16), out("d_total", p->d_total, 8, 64), in("d_intra", p->d_intra, 4, n * 4), opt(in("d_mode", p->d_mode, 1, n)),
+                     opt(in("d_inter0", p->d_inter0, 8, n * 8)), opt(in("d_inter1", p->d_inter1, 8, n * 8))};
+    return check(b);
+}
+inline const char *la_propagate(const x266_la_t *p)
+{
+    if (const char *why = la_frame(p)) return why;
+    const size_t n = tiles16(p->width, p->height);
+    const Buf b[] = {opt(out("d_prop_ref0", p->d_prop_ref0, 8, n * 8)), opt(out("d_prop_ref1", p->d_prop_ref1, 8, n * 8)), in("d_block", p->d_block, 16, n * 16),
+                     opt(in("d_prop", p->d_prop, 8, n * 8))};
+    return check(b);
+}
+inline const char *la_tree_qp(const x266_la_t *p)
+{
+    if (const char *why = la_frame(p)) return why;
+    if (p->strength_q8 < 0 || p->strength_q8 > 1024 || p->qp < 0 || p->qp > 51 || p->chroma_qp_offset < -12 || p->chroma_qp_offset > 12) return kLaScalars;
+    if (!p->d_offset && !p->d_qp) return "d_offset and d_qp are both NULL";
+    const size_t n = tiles16(p->width, p->height);
+    const Buf b[] = {opt(out("d_offset", p->d_offset, 2, n * 2)), opt(out("d_qp", p->d_qp, 1, ctus(p->width, p->height) * 6)), in("d_block", p->d_block, 16, n * 16),
+                     opt(in("d_prop", p->d_prop, 8, n * 8)), opt(in("d_aq_offset", p->d_aq_offset, 2, n * 2))};
+    return check(b);
+}
+// xSceneCutFromTotals (a host pointer): p and i above 2^40 are refused so that every product fits int64
+inline const char *scene_cut_from_totals(const int64_t *total, int threshold_q8, int frames_since_key, int min_keyint, int max_keyint)
+{
+    if (!total) return kNull;
+    if (threshold_q8 < 0 || threshold_q8 > 256) return "threshold_q8 must be 0..256";
+    if (frames_since_key < 0 || min_keyint < 1 || max_keyint < min_keyint) return "frames_since_key must be >= 0 and 1 <= min_keyint <= max_keyint";
+    for (int i = 0; i < 8; ++i)
+        if (total[i] < 0) return "a total is negative";
+    if (total[7] < 1 || total[7] > ((int64_t)1 << 24)) return "the block count must be 1..2^24";
+    if (total[0] > ((int64_t)1 << 40) || total[1] > ((int64_t)1 << 40)) return "a cost total is above 2^40";
     return nullptr;
 }
 

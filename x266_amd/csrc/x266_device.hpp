@@ -280,6 +280,13 @@ unsigned levels_scan_chunk();
 hipError_t launch_aq_stats(const x266_aq_t &p, hipStream_t stream);
 hipError_t launch_aq_decide(const x266_aq_t &p, hipStream_t stream);
 int aq_totals_chunk();
+// the lookahead (lookahead_kernels.hip): frame cost = the block records, then the totals' one workgroup of la_totals_chunk() blocks per step
+hipError_t launch_la_downscale(const x266_la_t &p, hipStream_t stream);
+hipError_t launch_la_intra_costs(const x266_la_t &p, hipStream_t stream);
+hipError_t launch_la_frame_cost(const x266_la_t &p, hipStream_t stream);
+hipError_t launch_la_propagate(const x266_la_t &p, hipStream_t stream);
+hipError_t launch_la_tree_qp(const x266_la_t &p, hipStream_t stream);
+int la_totals_chunk();
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

@@ -24,6 +24,7 @@
 #include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_levels.hpp"
+#include "x266_lookahead.hpp"
 #include "x266_tables.hpp"
 
 using namespace x266;
@@ -1409,6 +1410,55 @@ int xWeightsFromTotals(const int64_t cur[8], const int64_t ref[8], int list, x26
     if (args::weights_from_totals(cur, ref, list, wp)) return X266HIP_EINVAL;
     for (int plane = 0; plane < 3; ++plane) aq_plane_weight(cur, ref, plane, wp->log2_denom[plane ? 1 : 0], &wp->w[list][plane], &wp->o[list][plane]);
     return X266HIP_OK;
+}
+
+// ---- the lookahead (lookahead_kernels.hip, x266_lookahead.hpp) -----------------------------------------------------------------------------------
+int xLaDownscaleGpu(x266hip_ctx *ctx, const x266_la_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::la_downscale(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "lowres frame launch", launch_la_downscale(*p, (hipStream_t)stream));
+}
+
+int xLaIntraCostsGpu(x266hip_ctx *ctx, const x266_la_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::la_intra_costs(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "lowres intra cost launch", launch_la_intra_costs(*p, (hipStream_t)stream));
+}
+
+int xLaFrameCostGpu(x266hip_ctx *ctx, const x266_la_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::la_frame_cost(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "frame cost launch", launch_la_frame_cost(*p, (hipStream_t)stream));
+}
+
+int xLaPropagateGpu(x266hip_ctx *ctx, const x266_la_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::la_propagate(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "propagation launch", launch_la_propagate(*p, (hipStream_t)stream));
+}
+
+int xLaTreeQpGpu(x266hip_ctx *ctx, const x266_la_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::la_tree_qp(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "tree qp launch", launch_la_tree_qp(*p, (hipStream_t)stream));
+}
+
+int xLaTotalsChunk(void) { return la_totals_chunk(); }
+
+int xSceneCutFromTotals(const int64_t total[8], int threshold_q8, int frames_since_key, int min_keyint, int max_keyint)
+{
+    if (args::scene_cut_from_totals(total, threshold_q8, frames_since_key, min_keyint, max_keyint)) return X266HIP_EINVAL;
+    return la_scene_cut(total, threshold_q8, frames_since_key, min_keyint, max_keyint);
 }
 
 // ---- host-pointer batch API --------------------------------------------------
