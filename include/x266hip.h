@@ -1140,6 +1140,66 @@ int xLaTreeQpGpu    (x266hip_ctx *ctx, const x266_la_t *p, void *stream);
 int xLaTotalsChunk(void);
 int xSceneCutFromTotals(const int64_t total[8], int threshold_q8, int frames_since_key, int min_keyint, int max_keyint);
 
+/* ---- hierarchical motion search: a seeded SATD search around per-block starting vectors ----
+ * The exhaustive searches score (2 range + 1)^2 candidates per block and stop at range 64.  This call scores a few small squares
+ * around vectors the caller already has -- the winners of a search of the two half-size frames (xLaDownscaleGpu, then
+ * xSatd8x8SearchFromTilesDev on them: a lowres range of 64 reaches 128 full-resolution samples), the previous frame's field, the other
+ * list's field -- and charges every candidate the bits of its difference to the block's own seed, so that the field it hands to
+ * xSatd8x8RefineQpelFromTilesGpu and the bi-directional calls is regularised.  No upstream counterpart; the arithmetic here is the
+ * contract.  Whole samples, 8x8 luma blocks, the inter stage's edge rule (a reference sample outside the frame takes the nearest
+ * in-frame one, any displacement is legal) and its one metric satd8x8 (src_tb/satd.c:31-118).
+ *
+ * Seed cell.  Block (bx, by) is the 8x8 luma block at (8 bx, 8 by), b = by * (width / 8) + bx.  Its seed cell is (sx, sy) =
+ * (bx >> seed_scale, by >> seed_scale) of a grid of (width / 8 >> seed_scale) x (height / 8 >> seed_scale) cells, d_seed in raster
+ * order.  seed_scale 0: one seed per block, in full-resolution samples (a previous field, the other list).  seed_scale 1: one seed per
+ * 16x16 tile, in lowres samples -- exactly the d_best of a search of the two half-size frames.
+ * Centre vectors.  S(sx, sy) = clamp(seed << seed_scale, -8183, 8183) per component, computed in 32 bits: a seed of -32768 gives
+ * -8183 and 32767 gives 8183 at either scale, 4091 at scale 1 gives 8182, 4092 gives 8183.  Every candidate then lies inside
+ * +-8191, which is what the quarter-sample refinement takes unclamped.
+ * Ordered centre list of a block.  0 own: S(sx, sy), always.  Added only when its bit of `centres` is set: 1 (0, 0), bit 0;
+ * 2 left: S(sx - 1, sy), bit 1; 3 top: S(sx, sy - 1), bit 2; 4 right: S(sx + 1, sy), bit 3; 5 bottom: S(sx, sy + 1), bit 4.  A
+ * neighbour outside the seed grid is skipped, not substituted: with centres 31 the top-left cell of a grid of 3 x 2 has the list own,
+ * (0, 0), right, bottom; a grid of one cell has own, (0, 0).
+ * Candidates.  Walk the centres in list order; for each centre C take dy = -r..r ascending, then dx = -r..r ascending: v = C +
+ * (dx, dy).  Duplicates are allowed.  r = 1 and the list (5, -3), (0, 0): (4, -4), (5, -4), (6, -4), (4, -3), .. (6, -2), (-1, -1),
+ * (0, -1), .. (1, 1) -- walk index 4 is (5, -3), 9 is (-1, -1), 13 is (0, 0).
+ * Cost.  With P = centre 0 as the predictor,
+ *   J(v) = satd8x8(cur_block - ref_block_at(x + vx, y + vy)) + ((lambda_q4 * (L(vx - Px) + L(vy - Py))) >> 4)
+ * where L(d) is the length of d as a signed Exp-Golomb code: k = 2 |d| - (d > 0), L = 2 floor(log2(k + 1)) + 1.  L(0) = 1,
+ * L(1) = L(-1) = 3, L(2) = L(-2) = L(3) = L(-3) = 5, L(4) = 7, L(-7) = 7, L(8) = 9; |d| <= 16382 gives L <= 29, so J fits uint32.  With
+ * lambda_q4 16 the predictor itself costs 2 beside its SATD, (Px + 1, Py) 4, (Px + 2, Py - 4) 12.
+ * Winner.  The least J wins; among equal J the first candidate of the walk.  d_best[b] = {vx, vy, the winner's SATD (without the
+ * vector cost)}; d_j[b] = its J.
+ *
+ * What follows from it:
+ *   1. a zero seed with seed_scale 0, centres 0, lambda_q4 0 and range 8 gives bit for bit the d_best of xSatd8x8SearchFromTilesDev
+ *      at range 8;
+ *   2. range 0 with centres 0 gives the clamped seed and its SATD: for |seed << seed_scale| <= 8183 that is entry [49 b + 24] of
+ *      xSatd8x8RefineQpelFromTilesGpu's d_costs for the same vector;
+ *   3. a constant frame pair: every SATD ties, so with lambda_q4 0 the first entry of the walk wins, own + (-r, -r), and with
+ *      lambda_q4 > 0 the predictor does.
+ *
+ * One host struct, read during the call; the pointers in it are device pointers (alignments: the field comments).  d_cur == d_ref
+ * is allowed.  The outputs overlap nothing: in place (d_best == d_seed) is NOT allowed, blocks read their neighbours' seeds.  One
+ * launch; the call allocates nothing, needs no xHipMeScratchReserve and can be captured into a graph; its result does not depend on
+ * any launch option.  X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned
+ * required buffer, a side that is not a positive multiple of 16, a scalar outside the range its field comment states, a span that
+ * does not fit in the address space, and an output that overlaps any other buffer of the call.  The extents are width * height * 2
+ * (d_cur, d_ref), 8 bytes per seed cell (d_seed), 8 bytes (d_best) and 4 bytes (d_j) per 8x8 block. */
+typedef struct x266_seed_t {
+    const x266_ref_block_t *d_cur;         /* [(width / 16) * (height / 16)], 16-byte aligned; only m_Y is read                 */
+    const x266_ref_block_t *d_ref;         /* the same size, 16-byte aligned; only m_Y is read; may be d_cur                    */
+    const x266_me_result_t *d_seed;        /* one per seed cell, 8-byte aligned; cost is ignored                                */
+    x266_me_result_t *d_best;              /* [(width / 8) * (height / 8)], 8-byte aligned; output                              */
+    uint32_t *d_j;                         /* one per 8x8 block or NULL, 4-byte aligned; output: the winner's J                 */
+    int width, height;                     /* positive multiples of 16                                                          */
+    int seed_scale;                        /* 0: a seed per 8x8 block, full-resolution samples; 1: per 16x16 tile, lowres ones  */
+    int centres;                           /* 0..31, bits 0..4: add (0, 0), left, top, right, bottom                            */
+    int range;                             /* r, 0..8                                                                           */
+    int lambda_q4;                         /* 0..65535                                                                          */
+} x266_seed_t;
+int xSatd8x8SeededSearchGpu(x266hip_ctx *ctx, const x266_seed_t *p, void *stream);
+
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */

@@ -58,6 +58,12 @@ LA_CALLS = {"downscale": "xLaDownscaleGpu", "intra_costs": "xLaIntraCostsGpu", "
             "tree_qp": "xLaTreeQpGpu"}
 
 
+class SeedParams(ctypes.Structure):
+    """x266_seed_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_cur", "d_ref", "d_seed", "d_best", "d_j")] + \
+               [(name, ctypes.c_int) for name in ("width", "height", "seed_scale", "centres", "range", "lambda_q4")]
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -177,6 +183,7 @@ def load_library(path=None):
     L.xWeightsFromTotals.argtypes = [_P, _P, ctypes.c_int, ctypes.POINTER(WpParams)]
     for name in LA_CALLS.values():
         getattr(L, name).argtypes = [_P, ctypes.POINTER(LaParams), _P]
+    L.xSatd8x8SeededSearchGpu.argtypes = [_P, ctypes.POINTER(SeedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -1416,6 +1423,33 @@ class Codec:
                                            d_aq_offset=d_aq and d_aq.ptr, d_offset=d_off.ptr, d_qp=d_qp.ptr))
         self.stream_sync()
         return d_off.download(np.int16, n), d_qp.download(np.uint8, 6 * n_ctu).reshape(n_ctu, 6)
+
+    # -- the seeded search: a small SATD search around per-block starting vectors ------------------------------
+    @staticmethod
+    def seed_params(width=0, height=0, seed_scale=0, centres=0, range=0, lambda_q4=0, **pointers):
+        """an x266_seed_t from device addresses by field name (absent or 0: NULL)"""
+        names = [f[0] for f in SeedParams._fields_[:5]]
+        unknown = set(pointers) - set(names)
+        if unknown:
+            raise TypeError("seed_params: no such field: %s" % sorted(unknown))
+        return SeedParams(*([pointers.get(n) or None for n in names] + [int(width), int(height), int(seed_scale), int(centres), int(range), int(lambda_q4)]))
+
+    def satd_seeded_search_dev(self, params, stream=0):
+        self._check(self.L.xSatd8x8SeededSearchGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xSatd8x8SeededSearchGpu")
+
+    def seeded_search_tiles(self, cur_tiles, ref_tiles, w, h, seeds, seed_scale=0, centres=0, rng=0, lambda_q4=0):
+        """numpy convenience around xSatd8x8SeededSearchGpu: two tile arrays of a w x h frame and the seed vectors [cells, 2] int16
+        -> (mv [nb, 2] int16, satd [nb] uint32, j [nb] uint32)"""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
+        assert cur.size == w * h * 2 and ref.size == w * h * 2
+        nb = (h // 8) * (w // 8)
+        dc, dr, ds = self._upload(cur), self._upload(ref), self._upload(self._records(seeds, nb >> (2 * seed_scale)))
+        db, dj = self.alloc(nb * 8), self.alloc(max(nb * 4, 16))
+        self.satd_seeded_search_dev(self.seed_params(w, h, seed_scale, centres, rng, lambda_q4, d_cur=dc.ptr, d_ref=dr.ptr, d_seed=ds.ptr, d_best=db.ptr, d_j=dj.ptr))
+        self.stream_sync()
+        raw = db.download(np.uint8, nb * 8)
+        return raw.view(np.int16).reshape(nb, 4)[:, :2].copy(), raw.view(np.uint32).reshape(nb, 2)[:, 1].copy(), dj.download(np.uint32, nb)
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

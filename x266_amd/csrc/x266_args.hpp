@@ -7,7 +7,8 @@
 // "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.  The two calls of
 // the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
 // driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow; the two of the source analysis (aq_stats, aq_decide)
-// likewise by tests/cpp/aq_rules_check.cpp, the five of the lookahead (la_*) by tests/cpp/la_rules_check.cpp.
+// likewise by tests/cpp/aq_rules_check.cpp, the five of the lookahead (la_*) by tests/cpp/la_rules_check.cpp, the seeded search
+// (seeded_search) by tests/cpp/seed_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -19,6 +20,7 @@
 #include <cstring>
 
 #include "../../include/x266hip.h"
+#include "x266_seed.hpp"
 
 namespace x266 {
 namespace args {
@@ -580,6 +582,23 @@ inline const char *scene_cut_from_totals(const int64_t *total, int threshold_q8,
     if (total[7] < 1 || total[7] > ((int64_t)1 << 24)) return "the block count must be 1..2^24";
     if (total[0] > ((int64_t)1 << 40) || total[1] > ((int64_t)1 << 40)) return "a cost total is above 2^40";
     return nullptr;
+}
+
+// ---- the seeded search ----------------------------------------------------------------------------------------------------------------
+// xSatd8x8SeededSearchGpu: the device pointers are the fields of the host-read x266_seed_t, held by tests/cpp/seed_rules_check.cpp.  The
+// seed grid and the scalars' ranges are x266_seed.hpp's, the kernel's own.  The two frames are read-only and may be one; an output
+// overlaps nothing, the seeds included: blocks read their neighbours' seeds.
+constexpr const char *kSeedScalars = "seed_scale must be 0 or 1, centres 0..31, range 0..8 and lambda_q4 0..65535";
+inline const char *seeded_search(const x266_seed_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (p->seed_scale < 0 || p->seed_scale > 1 || p->centres < 0 || p->centres > kSeedCentreBits || p->range < 0 || p->range > kSeedMaxRange || !lambda_ok(p->lambda_q4))
+        return kSeedScalars;
+    const size_t n = blocks8(p->width, p->height);
+    const Buf b[] = {out("d_best", p->d_best, 8, n * 8), opt(out("d_j", p->d_j, 4, n * 4)), in("d_cur", p->d_cur, 16, tile_bytes(p->width, p->height)),
+                     in("d_ref", p->d_ref, 16, tile_bytes(p->width, p->height)), in("d_seed", p->d_seed, 8, seed_cells(p->width, p->height, p->seed_scale) * 8)};
+    return check(b);
 }
 
 // ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------

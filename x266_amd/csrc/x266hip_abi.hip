@@ -1461,6 +1461,15 @@ int xSceneCutFromTotals(const int64_t total[8], int threshold_q8, int frames_sin
     return la_scene_cut(total, threshold_q8, frames_since_key, min_keyint, max_keyint);
 }
 
+// ---- the seeded search (seeded_search_kernels.hip, x266_seed.hpp) ----------------------------------------------------------------------------------
+int xSatd8x8SeededSearchGpu(x266hip_ctx *ctx, const x266_seed_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::seeded_search(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "seeded search launch", launch_seeded_search(*p, (hipStream_t)stream));
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).
