@@ -898,6 +898,71 @@ int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int wi
                          int rounding, const uint8_t *d_mode_in, int16_t *d_level, uint32_t *d_nnz, uint8_t *d_mode,
                          x266_ref_block_t *d_recon, void *stream);
 
+/* ---- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames ----
+ * xDct32CodeMixedFrameGpu codes a frame whose regions are predicted either from another frame (d_pred, as any xMotionComp* call
+ * writes m_Y and m_C) or from the frame itself (the 32x32 intra predictor on the reconstructed neighbours), region by region: where
+ * motion compensation fails -- uncovered background, a new object, a partial scene change -- the region falls back to intra and
+ * the frame stays on the device.  Regions are 6 ctu + q in the order Y0 Y1 Y2 Y3 U V, CTUs in raster order, the luma quadrants
+ * q = 0..3 inside each CTU; the coding order of the frame is the one xIntra32CodeFrameGpu defines.
+ *
+ * For every luma quadrant, r = 6 ctu + q:
+ *   1. k = d_kind_in ? min(d_kind_in[r], 2) : 2.  0 = inter, 1 = intra, 2 = the call decides.
+ *   2. If k >= 1 the reference set is gathered from m_Y of d_recon by the availability and substitution rule of
+ *      xIntra32CodeFrameGpu, unchanged: a neighbour of either kind counts as available once it precedes the block.
+ *   3. Costs, both the sum over the sixteen 8x8 sub-blocks of satd8x8(cur - prediction): inter_cost with the prediction of
+ *      d_pred; intra_cost the least cost over the candidate modes, the lowest index on ties.  The candidates are all 35 modes
+ *      when d_mode_in == NULL, otherwise the one mode d_mode_in[r] (modes above 34 are undefined input).
+ *   4. Decision.  k == 2: the region is intra iff intra_cost + intra_penalty < inter_cost; a tie is inter.  k == 0 or 1: the kind
+ *      is given.  intra_penalty is what intra has to beat inter by, the call's only rate term: with inter_cost 6087 and
+ *      intra_cost 4699 the region is intra at penalty 0 and at 1387, and inter at 1388 (the tie) and at 4096.
+ *   5. Coding.  Inter: level = Q(DCT32(cur - pred)), recon = clip8(pred + IDCT32(Q^-1(level))), exactly as xDct32CodeCtuTilesGpu.
+ *      Intra: steps 3 to 5 of xIntra32CodeFrameGpu with the chosen mode.
+ * Then U and V of the CTU, which share ONE kind and ONE mode: k from entry 4 (entry 5 is ignored); one set per plane from m_C of
+ * d_recon; with d_mode_in == NULL the intra candidates are (0, 26, 10, 1), followed by quadrant 0's mode only if quadrant 0 ended
+ * intra, otherwise the one mode d_mode_in[6 ctu + 4]; cost(m) = cost_U(m) + cost_V(m), the first in the list on ties; inter_cost =
+ * cost_U + cost_V against d_pred; the same comparison with the same intra_penalty decides.  U is coded with the qp of region 4 and V
+ * with that of region 5.
+ * Outputs.  d_level and d_nnz as the two existing coding calls write them.  d_kind[r] = the kind the region ended with, 0 or 1;
+ * d_mode[r] = the mode used, 255 for an inter region; entries 4 and 5 both hold the chroma kind and mode.  d_cost[2 r] = inter_cost,
+ * written for k == 2; d_cost[2 r + 1] = intra_cost, written for k == 2, and for k == 1 when d_mode_in == NULL; every other entry is
+ * 0xFFFFFFFF; entry 5 repeats entry 4.  m_Y and m_C of d_recon; m_I of d_recon is never read or written.
+ * Overlap.  d_recon == d_pred is allowed and is the form an encoder uses: a region reads its own prediction before it writes its own
+ * reconstruction and reads only earlier regions of d_recon.  d_kind == d_kind_in and d_mode == d_mode_in are allowed.  Any other
+ * overlap of an output with any buffer of the call returns X266HIP_EINVAL, d_recon == d_cur included.
+ *
+ * What follows from it:
+ *   (a) with every kind 0, d_level, d_nnz and d_recon are bit for bit those of xDct32CodeCtuTilesGpu on the same arguments;
+ *   (b) with every kind 1, d_level, d_nnz, d_mode and d_recon are bit for bit those of xIntra32CodeFrameGpu, and d_pred is never read;
+ *   (c) a region's result depends only on regions before it in coding order, so it does not depend on the schedule;
+ *   (d) entries 0..3 of every CTU of d_kind are exactly what x266_deblock_t.d_intra reads: d_kind is a valid d_intra.
+ * Schedule (not part of the contract): one launch codes every region whose d_kind_in byte is 0 -- they depend on nothing -- and the
+ * wavefront of xIntra32CodeFrameGpu follows, one launch per step on the caller's stream, in which a workgroup whose region was given
+ * as inter returns after reading that byte.  Stream order is the only synchronisation.  A caller that screens the regions (with
+ * xLaFrameCostGpu's decision, say) and marks only the doubtful ones 2 pays the steps in launch overhead plus those regions.
+ * One host struct, read during the call; the pointers in it are device pointers (alignments: the field comments).  The call
+ * allocates nothing and can be captured into a graph.  X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a
+ * NULL p, a NULL or misaligned required buffer, a side that is not a positive multiple of 64, a scalar qp outside 0..51 when
+ * d_qp == NULL, rounding outside 0..511, intra_penalty outside 0 .. 1 << 24, a span that does not fit in the address space, and
+ * an overlap other than the three above.  With n = 6 n_ctu the extents are width * height * 2 (the frames), n bytes (d_qp, the
+ * kinds, the modes), 2048 n (d_level), 4 n (d_nnz) and 8 n (d_cost). */
+typedef struct x266_mixed_t {
+    const x266_ref_block_t *d_cur;         /* the source frame, [(width / 16) * (height / 16)], 16-byte aligned                 */
+    const x266_ref_block_t *d_pred;        /* the inter prediction, the same size, 16-byte aligned; m_Y and m_C are read        */
+    const uint8_t *d_qp;                   /* [6 n_ctu] or NULL, 1-byte aligned; NULL: the scalar qp                            */
+    const uint8_t *d_kind_in;              /* [6 n_ctu] or NULL, 1-byte aligned; 0 inter, 1 intra, 2 and above decide           */
+    const uint8_t *d_mode_in;              /* [6 n_ctu] or NULL, 1-byte aligned; NULL: the call chooses the intra mode          */
+    int16_t *d_level;                      /* [6 n_ctu * 1024], 16-byte aligned; output                                         */
+    uint32_t *d_nnz;                       /* [6 n_ctu] or NULL, 4-byte aligned; output                                         */
+    uint8_t *d_kind;                       /* [6 n_ctu], 1-byte aligned; output, may be d_kind_in                               */
+    uint8_t *d_mode;                       /* [6 n_ctu], 1-byte aligned; output, may be d_mode_in                               */
+    uint32_t *d_cost;                      /* [2 * 6 n_ctu] or NULL, 4-byte aligned; output                                     */
+    x266_ref_block_t *d_recon;             /* the reconstruction, the frames' size, 16-byte aligned; output, may be d_pred      */
+    int width, height;                     /* positive multiples of 64                                                          */
+    int qp, rounding;                      /* qp 0..51, checked only when d_qp == NULL; rounding 0..511                         */
+    int intra_penalty;                     /* 0 .. 1 << 24                                                                      */
+} x266_mixed_t;
+int xDct32CodeMixedFrameGpu(x266hip_ctx *ctx, const x266_mixed_t *p, void *stream);
+
 /* ---- the compact level stream: what leaves the device for the host's entropy coder, and what a host decoder hands back ----
  * xDct32CodeCtuTilesGpu, xIntra32CodeFrameGpu and xQuantRegionsGpu(0) emit levels dense, 2 KiB per region, nearly all zeros at
  * any useful qp.  xLevelsPackGpu turns them into coded-group flags, significance maps and the non-zero levels in the order a

@@ -64,6 +64,12 @@ class SeedParams(ctypes.Structure):
                [(name, ctypes.c_int) for name in ("width", "height", "seed_scale", "centres", "range", "lambda_q4")]
 
 
+class MixedParams(ctypes.Structure):
+    """x266_mixed_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
+               [(name, ctypes.c_int) for name in ("width", "height", "qp", "rounding", "intra_penalty")]
+
+
 class X266Error(RuntimeError):
     pass
 
@@ -184,6 +190,7 @@ def load_library(path=None):
     for name in LA_CALLS.values():
         getattr(L, name).argtypes = [_P, ctypes.POINTER(LaParams), _P]
     L.xSatd8x8SeededSearchGpu.argtypes = [_P, ctypes.POINTER(SeedParams), _P]
+    L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.xIntra32RefsFromTilesGpu.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]
@@ -1450,6 +1457,44 @@ class Codec:
         self.stream_sync()
         raw = db.download(np.uint8, nb * 8)
         return raw.view(np.int16).reshape(nb, 4)[:, :2].copy(), raw.view(np.uint32).reshape(nb, 2)[:, 1].copy(), dj.download(np.uint32, nb)
+
+    # -- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames -------------------------
+    @staticmethod
+    def mixed_params(width=0, height=0, qp=0, rounding=0, intra_penalty=0, **pointers):
+        """an x266_mixed_t from device addresses by field name (absent or 0: NULL)"""
+        names = [f[0] for f in MixedParams._fields_[:11]]
+        unknown = set(pointers) - set(names)
+        if unknown:
+            raise TypeError("mixed_params: no such field: %s" % sorted(unknown))
+        return MixedParams(*([pointers.get(n) or None for n in names] + [int(width), int(height), int(qp), int(rounding), int(intra_penalty)]))
+
+    def dct32_code_mixed_frame_dev(self, params, stream=0):
+        self._check(self.L.xDct32CodeMixedFrameGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xDct32CodeMixedFrameGpu")
+
+    def code_mixed_frame(self, cur_tiles, pred_tiles, w, h, qps=None, qp=0, rounding=0, intra_penalty=0, kinds_in=None, modes_in=None, base=None):
+        """numpy convenience around xDct32CodeMixedFrameGpu: two tile arrays of a w x h frame (multiples of 64), optionally 6 qp, kind and
+        mode bytes per CTU -> a dict of levels [n_ctus, 6, 1024] int16, nnz [n_ctus, 6] uint32, kinds and modes [n_ctus, 6] uint8, costs
+        [n_ctus, 6, 2] uint32 (inter, intra) and the reconstructed tile array; m_I (never written) comes from `base` (None: zeros)"""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
+        n = self.ctu_count(w, h)
+        assert cur.size == w * h * 2 and pred.size == cur.size
+        dc, dp, dr = self._upload(cur), self._upload(pred), self.alloc(cur.nbytes)
+        dr.upload(np.zeros(cur.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        dl, dn, dk, dm, dcost = self.alloc(n * 12288), self.alloc(max(n * 24, 16)), self.alloc(max(n * 6, 16)), self.alloc(max(n * 6, 16)), self.alloc(n * 48)
+        tabs = []
+        for t in (qps, kinds_in, modes_in):
+            if t is not None:
+                t = np.ascontiguousarray(t, np.uint8).ravel()
+                assert t.size == 6 * n
+            tabs.append(None if t is None else self._upload(np.concatenate([t, np.zeros(16, np.uint8)])))
+        self.dct32_code_mixed_frame_dev(self.mixed_params(w, h, qp, rounding, intra_penalty, d_cur=dc.ptr, d_pred=dp.ptr, d_qp=tabs[0] and tabs[0].ptr,
+                                                          d_kind_in=tabs[1] and tabs[1].ptr, d_mode_in=tabs[2] and tabs[2].ptr, d_level=dl.ptr, d_nnz=dn.ptr,
+                                                          d_kind=dk.ptr, d_mode=dm.ptr, d_cost=dcost.ptr, d_recon=dr.ptr))
+        self.stream_sync()
+        return {"levels": dl.download(np.int16, n * 6144).reshape(n, 6, 1024), "nnz": dn.download(np.uint32, n * 6).reshape(n, 6),
+                "kinds": dk.download(np.uint8, n * 6).reshape(n, 6), "modes": dm.download(np.uint8, n * 6).reshape(n, 6),
+                "costs": dcost.download(np.uint32, n * 12).reshape(n, 6, 2), "recon": dr.download(np.uint8, cur.size)}
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),

@@ -8,7 +8,7 @@
 // the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
 // driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow; the two of the source analysis (aq_stats, aq_decide)
 // likewise by tests/cpp/aq_rules_check.cpp, the five of the lookahead (la_*) by tests/cpp/la_rules_check.cpp, the seeded search
-// (seeded_search) by tests/cpp/seed_rules_check.cpp.
+// (seeded_search) by tests/cpp/seed_rules_check.cpp, the mixed inter / intra frame (mixed_code_frame) by tests/cpp/mixed_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -617,6 +617,23 @@ inline const char *intra32_code_frame(const void *d_cur, int w, int h, const voi
     const Buf b[] = {out("d_recon", d_recon, 16, tile_bytes(w, h)), out("d_level", d_level, 16, ctus(w, h) * 12288), out("d_mode", d_mode, 1, ctus(w, h) * 6, "d_mode_in"),
                      opt(out("d_nnz", d_nnz, 4, ctus(w, h) * 24)), in("d_cur", d_cur, 16, tile_bytes(w, h)), opt(in("d_qp", d_qp, 1, ctus(w, h) * 6)),
                      opt(in("d_mode_in", d_mode_in, 1, ctus(w, h) * 6))};
+    return check(b);
+}
+// xDct32CodeMixedFrameGpu: the device pointers are the fields of the host-read x266_mixed_t, held by tests/cpp/mixed_rules_check.cpp.  Three
+// outputs may BE one input each (the reconstruction the inter prediction, the kinds and the modes their inputs); d_cur == d_pred are two inputs.
+constexpr const char *kMixedPenalty = "intra_penalty must be 0..16777216";
+inline const char *mixed_code_frame(const x266_mixed_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    const int w = p->width, h = p->height;
+    if (const char *why = frame(w, h, 64)) return why;
+    if (!qp_ok(p->d_qp, p->qp) || !rounding_ok(p->rounding)) return kQuantScalars;
+    if (p->intra_penalty < 0 || p->intra_penalty > (1 << 24)) return kMixedPenalty;
+    const size_t n = ctus(w, h) * 6;
+    const Buf b[] = {out("d_recon", p->d_recon, 16, tile_bytes(w, h), "d_pred"), out("d_level", p->d_level, 16, n * 2048), out("d_kind", p->d_kind, 1, n, "d_kind_in"),
+                     out("d_mode", p->d_mode, 1, n, "d_mode_in"), opt(out("d_nnz", p->d_nnz, 4, n * 4)), opt(out("d_cost", p->d_cost, 4, n * 8)),
+                     in("d_cur", p->d_cur, 16, tile_bytes(w, h)), in("d_pred", p->d_pred, 16, tile_bytes(w, h)), opt(in("d_qp", p->d_qp, 1, n)),
+                     opt(in("d_kind_in", p->d_kind_in, 1, n)), opt(in("d_mode_in", p->d_mode_in, 1, n))};
     return check(b);
 }
 

@@ -175,6 +175,8 @@ int intra32_frame_steps(int width, int height);
 hipError_t launch_intra32_code_frame(const x266_ref_block_t *d_cur, x266_ref_block_t *d_recon, int16_t *d_level, uint32_t *d_nnz, const uint8_t *d_qp,
                                      int qp, int rounding, const uint8_t *d_mode_in, uint8_t *d_mode, int width, int height,
                                      const DctOps *d_fwd_ops, const DctOps *d_inv_acc_ops, hipStream_t stream);
+// mixed inter / intra coding of a frame: one launch for the regions given as inter, then the steps of the intra frame
+hipError_t launch_mixed_code_frame(const x266_mixed_t &p, const DctOps *d_fwd_ops, const DctOps *d_inv_acc_ops, hipStream_t stream);
 hipError_t launch_satd8x8_butterfly(const int16_t *d_diff, uint32_t *d_out, size_t n_blocks, const LaunchCfg &cfg, hipStream_t stream);
 hipError_t launch_transform_tiles(bool inverse, const int16_t *d_in, int16_t *d_out, size_t n_tiles, const uint32_t *d_tile_offsets,
                                   const uint8_t *d_tile_class, const TileTab *d_tab, const LaunchCfg &cfg, hipStream_t stream);

@@ -221,6 +221,27 @@ __device__ __forceinline__ void cost_stage_source(unsigned char *stile, int lane
     *reinterpret_cast<uint2 *>(d + 8) = make_uint2((uint32_t)sv[2], (uint32_t)sv[3]);
 }
 
+// c_a / c_b = sum over the sixteen 8x8 sub-blocks of satd8x8(src - tile) for the two signed pitched tiles at ptile and ptile + kTileB, which the
+// wave has written and fenced with a wave barrier; cs = hadamard_pack of the source windows of the lane (lanes 16 .. 31 and 48 .. 63 score the
+// second tile: their cs may come from a second source tile).  Any prediction is scored here: the intra modes below, an inter prediction staged
+// with cost_stage_source.
+__device__ __forceinline__ void score_tiles(const unsigned char *ptile, const HadamardOps &H, const uint32_t (&cs)[16], int lane, unsigned frag,
+                                            uint32_t &c_a, uint32_t &c_b)
+{
+    v4i w0, w1;
+    cost_window(ptile + ((lane & 31) >> 4) * kTileB, frag, w0, w1);
+    uint32_t p[16];
+    hadamard_pack(H, w0, w1, p);
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s = __builtin_amdgcn_sad_u16(p[k], cs[k], s);
+    s = sum_with_other_half(s);                          // the other half of the coefficient rows
+    const uint32_t c = sum_over_row16((s + 2u) >> 2);    // satd8x8 of this sub-block, summed over the sixteen sub-blocks (one row of lanes per tile)
+    __builtin_amdgcn_wave_barrier();
+    c_a = (uint32_t)__builtin_amdgcn_readlane((int)c, 0);
+    c_b = (uint32_t)__builtin_amdgcn_readlane((int)c, 16);
+}
+
 // c_a / c_b = sum over the sixteen 8x8 sub-blocks of satd8x8(src - prediction mode_a / mode_b), cs = hadamard_pack of the source tile's
 // windows.  The two predictions go to the tiles ptile and ptile + kTileB; without have_b the second tile keeps what it held and c_b means nothing.
 __device__ __forceinline__ void intra_score_modes(int mode_a, int mode_b, bool have_b, const unsigned char *left, const unsigned char *top,
@@ -245,18 +266,7 @@ __device__ __forceinline__ void intra_score_modes(int mode_a, int mode_b, bool h
         *reinterpret_cast<uint2 *>(tile + at + 8) = make_uint2(px[2], px[3]);
     }
     __builtin_amdgcn_wave_barrier();
-    v4i w0, w1;
-    cost_window(ptile + ((lane & 31) >> 4) * kTileB, frag, w0, w1);
-    uint32_t p[16];
-    hadamard_pack(H, w0, w1, p);
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s = __builtin_amdgcn_sad_u16(p[k], cs[k], s);
-    s = sum_with_other_half(s);                          // the other half of the coefficient rows
-    const uint32_t c = sum_over_row16((s + 2u) >> 2);    // satd8x8 of this sub-block, summed over the sixteen sub-blocks (one row of lanes per tile)
-    __builtin_amdgcn_wave_barrier();
-    c_a = (uint32_t)__builtin_amdgcn_readlane((int)c, 0);
-    c_b = (uint32_t)__builtin_amdgcn_readlane((int)c, 16);
+    score_tiles(ptile, H, cs, lane, frag, c_a, c_b);
 }
 
 }  // namespace x266

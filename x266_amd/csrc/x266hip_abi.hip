@@ -1357,6 +1357,14 @@ int xIntra32CodeFrameGpu(x266hip_ctx *ctx, const x266_ref_block_t *d_cur, int wi
                                                                                ctx->d_inv_acc, (hipStream_t)stream));
 }
 
+int xDct32CodeMixedFrameGpu(x266hip_ctx *ctx, const x266_mixed_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::mixed_code_frame(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "mixed frame coding launch", launch_mixed_code_frame(*p, ctx->d_fwd, ctx->d_inv_acc, (hipStream_t)stream));
+}
+
 // ---- the compact level stream (levels_kernels.hip, x266_levels.hpp) ------------------------------------------------------------------------
 int xLevelsPackGpu(x266hip_ctx *ctx, const x266_levels_t *p, void *stream)
 {
