@@ -9,6 +9,8 @@ rounding in 0..511:
 Nothing here is derived from the library under test."""
 import numpy as np
 
+from _util import splitmix64
+
 F = np.array([26214, 23302, 20560, 18396, 16384, 14564], np.int64)
 G = np.array([40, 45, 51, 57, 64, 72], np.int64)
 
@@ -123,3 +125,47 @@ def code_ctu_tiles(oracle, cur, pred, w, h, qps=None, qp=0, rounding=0, base=Non
     coef = quant_regions(level, True, None, qps, qp)
     recon = recon_of_coefficients(oracle, coef, pred, pred if base is None else base, w, h)
     return level.reshape(-1, 6, 1024), nnz.reshape(-1, 6), recon
+
+
+# ---- data recipes of the GPU tests ----------------------------------------------------------------------------------------------------
+EXTREMES = np.array([32767, -32767, -32768, 255, -255, 256, -256, 0], np.int16)
+
+
+def _res_mix(n, seed):
+    """int16 samples: a quarter each full range, the extremes of EXTREMES, small (-256..255) and +-1 / 0"""
+    r = splitmix64(seed, 0, n)
+    kind = r & np.uint64(3)
+    full = (r >> np.uint64(16)).astype(np.uint16).view(np.int16)
+    ext = EXTREMES[((r >> np.uint64(48)) % np.uint64(len(EXTREMES))).astype(np.int64)]
+    small = ((r >> np.uint64(32)) & np.uint64(0x1FF)).astype(np.int16) - np.int16(256)
+    tiny = ((r >> np.uint64(40)) % np.uint64(3)).astype(np.int16) - np.int16(1)
+    return np.select([kind == 0, kind == 1, kind == 2], [full, ext, small], tiny).astype(np.int16)
+
+
+def _tiles_mix(w, h, seed):
+    """m_Y / m_C: a third 0, a third 255, a third random; m_I random bytes"""
+    t = (splitmix64(seed, 0, w * h * 2) & np.uint64(255)).astype(np.uint8).reshape(-1, 512)
+    r = splitmix64(seed + 1, 0, t.shape[0] * 384)
+    kind = r % np.uint64(3)
+    pix = np.select([kind == 0, kind == 1], [np.uint64(0), np.uint64(255)], (r >> np.uint64(8)) & np.uint64(255)).astype(np.uint8)
+    t[:, :384] = pix.reshape(-1, 384)
+    return t.ravel()
+
+
+def _coefficients(n_regions, seed):
+    """_res_mix with an all-zero region where there is more than one"""
+    x = _res_mix(n_regions * 1024, seed).reshape(n_regions, 1024)
+    if n_regions > 1:
+        x[1] = 0
+    return x
+
+
+def _levels(n_regions, seed):
+    """_res_mix plus the levels that reach the dequantiser's clip: the largest a forward call emits and the int16 extremes"""
+    x = _res_mix(n_regions * 1024, seed).reshape(n_regions, 1024)
+    x[:, 3:11] = np.array([13108, -13108, 32767, -32767, -32768, 13107, -13107, 0], np.int16)
+    return x
+
+
+def _bytes(n, seed, mask):
+    return (splitmix64(seed, 0, n) & np.uint64(mask)).astype(np.uint8)

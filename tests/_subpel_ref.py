@@ -168,3 +168,15 @@ def vectors(w, h, seed):
     if (w, h) == (64, 64):                                                  # chroma phase (b & 7, b >> 3): all 64 chroma classes
         return np.stack([8 * (b * 5 % 7 - 3) + (b & 7), 8 * (b * 3 % 5 - 2) + (b >> 3)], axis=1).astype(np.int16)
     return mv_mix_q(nb, w, h, seed)
+
+
+def _mv_mix(nb, w, h, seed):
+    """int16 vectors: small ones (-32..31: all four parity classes, negative odd values), the int16 extremes, vectors pointing
+    wholly outside the frame, and zero"""
+    r = splitmix64(seed, 0, 2 * nb).reshape(nb, 2)
+    kind = (r >> np.uint64(60)).astype(np.int64)
+    small = (r & np.uint64(63)).astype(np.int64) - 32
+    ext = np.array([32767, -32768, -32767, 32766], np.int64)[((r >> np.uint64(20)) & np.uint64(3)).astype(np.int64)]
+    far = np.where((r >> np.uint64(30)) & np.uint64(1), 1, -1) * (np.array([w, h], np.int64) + 8 + (r >> np.uint64(40) & np.uint64(255)).astype(np.int64))
+    mv = np.select([kind < 8, kind < 11, kind < 14], [small, ext, far], 0)
+    return np.clip(mv, -32768, 32767).astype(np.int16)

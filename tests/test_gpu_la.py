@@ -57,19 +57,7 @@ def ref(kind, w, h):
     return tiles, low, cost, mode
 
 
-def lists(intra, seed):
-    """two lists' records built around the intra costs so that every branch of the decision occurs, ties included"""
-    n, r = intra.size, np.random.RandomState(seed)
-    l0, l1 = np.zeros(n, R.ME_DTYPE), np.zeros(n, R.ME_DTYPE)
-    for a in (l0, l1):
-        a["mvx"], a["mvy"] = r.randint(-64, 65, n), r.randint(-64, 65, n)
-        a["cost"] = np.maximum(intra.astype(np.int64) + r.randint(-300, 901, n), 0)   # around intra + the penalty of 300
-    k = np.arange(n) % 8
-    l1["cost"][k == 1] = l0["cost"][k == 1]                                  # list 1 ties with list 0
-    l0["cost"][k == 2] = intra[k == 2] + 300                                # intra (penalty 300) ties with list 0 ...
-    l1["cost"][k == 3] = intra[k == 3] + 300                                # ... and with list 1
-    l0["cost"][k == 4] = l1["cost"][k == 4] = intra[k == 4] + 300          # all three tie
-    return l0, l1
+lists = R.lists                                                             # the recipe lives with the frames the CPU and GPU tests share
 
 
 # ---- the calls inside an arena, each held against the reference ---------------------------------------------------------------------------------

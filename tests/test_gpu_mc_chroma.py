@@ -7,6 +7,7 @@ itself is checked against a plain Python loop by the one test here that needs no
 import numpy as np
 import pytest
 
+from _subpel_ref import _mv_mix                                          # the vector mix, shared with tests/_frame_cases.py
 from _util import me_frames, splitmix64
 
 gpu = pytest.mark.gpu
@@ -99,18 +100,6 @@ def _tiles(oracle, y, u, v, seed):
 
 def _luma(w, h, seed):
     return (splitmix64(seed, 0, w * h) & np.uint64(255)).astype(np.uint8).reshape(h, w)
-
-
-def _mv_mix(nb, w, h, seed):
-    """int16 vectors: small ones (-32..31: all four parity classes, negative odd values), the int16 extremes, vectors pointing
-    wholly outside the frame, and zero"""
-    r = splitmix64(seed, 0, 2 * nb).reshape(nb, 2)
-    kind = (r >> np.uint64(60)).astype(np.int64)
-    small = (r & np.uint64(63)).astype(np.int64) - 32
-    ext = np.array([32767, -32768, -32767, 32766], np.int64)[((r >> np.uint64(20)) & np.uint64(3)).astype(np.int64)]
-    far = np.where((r >> np.uint64(30)) & np.uint64(1), 1, -1) * (np.array([w, h], np.int64) + 8 + (r >> np.uint64(40) & np.uint64(255)).astype(np.int64))
-    mv = np.select([kind < 8, kind < 11, kind < 14], [small, ext, far], 0)
-    return np.clip(mv, -32768, 32767).astype(np.int16)
 
 
 def _vectors(w, h, seed):

@@ -8,57 +8,17 @@ import numpy as np
 import pytest
 
 import _quant_ref as Q
+from _quant_ref import EXTREMES, _bytes, _coefficients, _levels, _res_mix, _tiles_mix   # the data recipes, shared with tests/_frame_cases.py
 from _arena import Arena
 from _util import me_frames, splitmix64
 
 pytestmark = pytest.mark.gpu
 
-EXTREMES = np.array([32767, -32767, -32768, 255, -255, 256, -256, 0], np.int16)
 EINVAL = -1
 ROUNDINGS = [0, 171, 511]
 
 
 # ---- data ---------------------------------------------------------------------------------------------------------------------------
-def _res_mix(n, seed):
-    """int16 samples: a quarter each full range, the extremes of EXTREMES, small (-256..255) and +-1 / 0"""
-    r = splitmix64(seed, 0, n)
-    kind = r & np.uint64(3)
-    full = (r >> np.uint64(16)).astype(np.uint16).view(np.int16)
-    ext = EXTREMES[((r >> np.uint64(48)) % np.uint64(len(EXTREMES))).astype(np.int64)]
-    small = ((r >> np.uint64(32)) & np.uint64(0x1FF)).astype(np.int16) - np.int16(256)
-    tiny = ((r >> np.uint64(40)) % np.uint64(3)).astype(np.int16) - np.int16(1)
-    return np.select([kind == 0, kind == 1, kind == 2], [full, ext, small], tiny).astype(np.int16)
-
-
-def _tiles_mix(w, h, seed):
-    """m_Y / m_C: a third 0, a third 255, a third random; m_I random bytes"""
-    t = (splitmix64(seed, 0, w * h * 2) & np.uint64(255)).astype(np.uint8).reshape(-1, 512)
-    r = splitmix64(seed + 1, 0, t.shape[0] * 384)
-    kind = r % np.uint64(3)
-    pix = np.select([kind == 0, kind == 1], [np.uint64(0), np.uint64(255)], (r >> np.uint64(8)) & np.uint64(255)).astype(np.uint8)
-    t[:, :384] = pix.reshape(-1, 384)
-    return t.ravel()
-
-
-def _coefficients(n_regions, seed):
-    """_res_mix with an all-zero region where there is more than one"""
-    x = _res_mix(n_regions * 1024, seed).reshape(n_regions, 1024)
-    if n_regions > 1:
-        x[1] = 0
-    return x
-
-
-def _levels(n_regions, seed):
-    """_res_mix plus the levels that reach the dequantiser's clip: the largest a forward call emits and the int16 extremes"""
-    x = _res_mix(n_regions * 1024, seed).reshape(n_regions, 1024)
-    x[:, 3:11] = np.array([13108, -13108, 32767, -32767, -32768, 13107, -13107, 0], np.int16)
-    return x
-
-
-def _bytes(n, seed, mask):
-    return (splitmix64(seed, 0, n) & np.uint64(mask)).astype(np.uint8)
-
-
 def _dev(codec, arr):
     arr = np.ascontiguousarray(arr)
     d = codec.alloc(max(arr.nbytes, 16))
