@@ -1026,6 +1026,77 @@ typedef struct x266_levels_t {
 int xLevelsPackGpu  (x266hip_ctx *ctx, const x266_levels_t *p, void *stream);
 int xLevelsUnpackGpu(x266hip_ctx *ctx, const x266_levels_t *p, void *stream);
 
+/* ---- rate-distortion optimised quantisation (RDOQ) and a rate estimate of a region's levels ----
+ * xQuantRegionsGpu(0) rounds every coefficient on its own.  xRdoQuantRegionsGpu weighs each level's distortion against what the level
+ * costs to code, drops coefficient groups and trailing levels that do not pay, and reports distortion and estimated bits per region;
+ * xLevelsBitsGpu gives the same estimate for levels from any producer.  No upstream counterpart: the RDOQ of HM, VTM and x265 in
+ * outline, as recalled, with a static rate model; the arithmetic here is the contract.  All values are mathematical integers, every
+ * one fits in int64.
+ *
+ * Region and block.  Region, class byte and block layout exactly as xQuantRegionsGpu and xLevelsPackGpu read them: N = 4 << (class &
+ * 3), n = log2 N, d_class == NULL: N = 32; qp = min(d_qp[r], 51), or the scalar qp when d_qp == NULL.  The scan of a block is
+ * xLevelsPackGpu's (xLevelScan): index i is a position in that order, s = i / 16 its CG, (u, v) its frequency.
+ *
+ * Rate, in 1/16 bit, a static model: no adaptive contexts, so regions and CGs are independent.
+ *     position class: 0 at u = v = 0; 1 elsewhere in CG 0 (u < 4 and v < 4); 2 otherwise
+ *     sig[class][0/1] = {24,10}, {12,22}, {6,36}     gt1[0/1] = {10,24}     gt2[0/1] = {11,22}     cgf[0/1] = {9,26}     a sign: 16
+ *     rem(r), r >= 0:  r + 1 for r < 3, otherwise 3 + 2 ilog2(r - 2) + 1
+ *     R(l, class), l a level magnitude:
+ *         l = 0: sig[class][0]                                  l = 1: sig[class][1] + 16 + gt1[0]
+ *         l = 2: sig[class][1] + 16 + gt1[1] + gt2[0]           l >= 3: sig[class][1] + 16 + gt1[1] + gt2[1] + 16 rem(l - 3)
+ *     Rlast(u, v) = 16 (pos(u) + pos(v)),  pos(t) = min(g + 1, 2n - 1) + (g >= 4 ? (g >> 1) - 1 : 0),
+ *         g = t for t < 4, otherwise g = 2 ilog2(t) + ((t >> (ilog2(t) - 1)) & 1)
+ * Distortion.  a = |c|, x = a * f[qp % 6], f and qbits the quantiser's (above).  For a level magnitude l:
+ *     err = |x - (l << qbits)|,   e = (err + (1 << (qbits - 9))) >> (qbits - 8)   (1/256 of a level),   D(l) = e * e
+ *     J(l) = D(l) + lambda * R(l, class),   lambda an integer 0..8192, in 1/4096 of a squared level per bit.
+ * The conventional 0.57 * 2^((qp - 12) / 3) in sample units comes to about 368 in these units at every qp; nobody has measured
+ * which lambda serves this rate model best.
+ *
+ * Step 1, per coefficient.  h = (x + (1 << (qbits - 1))) >> qbits.  Candidates: h; h - 1 if h >= 1; 0 if h <= 2.  q[i] is the
+ * candidate of least J; on a tie the smallest level wins.
+ * Step 2, per CG with s >= 1 that has a non-zero q.  Jc = sum J(q[i]) + lambda * cgf[1], Jz = sum D(0) + lambda * cgf[0] over its 16
+ * positions; the CG becomes all zero iff Jz < Jc.  CG 0 of a block is never touched here.
+ * Step 3, per block that still has a non-zero level.  C(s), the cost of CG s: sum J(q[i]) for s = 0; sum J(q[i]) + lambda * cgf[1]
+ * for a later CG with a non-zero level; sum D(0) + lambda * cgf[0] for a later CG with none.  For every p with q[p] != 0, s_p its CG,
+ *     Total(p) = sum over s < s_p of C(s)  +  sum over i in CG s_p with i < p of J(q[i])
+ *              + D(q[p]) + lambda * (R(q[p], class_p) - sig[class_p][1])  +  sum over all i > p of D(0)  +  lambda * Rlast(u_p, v_p)
+ *     Total(none) = sum over all i of D(0).
+ * The block's last position is the p of least Total; on a tie the larger p wins, and any p wins over none.  Every level after the
+ * chosen p becomes 0; if none is chosen, every level becomes 0.  Signs are the coefficients'.
+ *
+ * Per region (x266_rdoq_region_t): dist = sum of D(final level) over its 1024 positions.  bits = the sum, over its blocks with a
+ * non-zero level, p the block's last non-zero position, of Rlast(p) + cgf[coded] for every CG with 0 < s < s_p + R(level) for every
+ * i <= p inside CG 0, CG s_p and the non-empty CGs between - sig[class_p][1].  bits is a function of the levels alone (not of
+ * lambda); n_nz is the number of non-zero levels.
+ *
+ * xRdoQuantRegionsGpu turns d_coef into d_level by steps 1 to 3 (in place, d_level == d_coef, is allowed) and writes d_nnz and d_stat
+ * when given.  Its levels feed xQuantRegionsGpu(1), xLevelsPackGpu and the deblocking calls exactly as the plain quantiser's do.
+ * xLevelsBitsGpu reads d_level and writes d_stat with bits and n_nz as above and dist = 0; with d_nnz != NULL a region with d_nnz[r]
+ * == 0 is not read and reports zeros.  It ignores d_coef, d_qp, qp and lambda.
+ * One launch each on the caller's stream; neither call allocates, both can be captured into a graph, and the same input gives the
+ * same bytes on every run.  n_regions == 0 returns 0 and launches nothing.  X266HIP_EINVAL, with nothing launched and the call
+ * named in xHipLastError: a NULL p, a NULL or misaligned required buffer, qp (without d_qp) or lambda out of range
+ * (xRdoQuantRegionsGpu), a span that does not fit in the address space, any overlap of an output with another buffer other than
+ * d_level == d_coef.  The extents are n_regions * 2048 (d_coef, d_level), n_regions (d_class, d_qp), n_regions * 4 (d_nnz) and
+ * n_regions * 16 (d_stat). */
+typedef struct x266_rdoq_region_t {
+    uint64_t dist;      /* sum of D(final level), 1/65536 of a squared level; 0 from xLevelsBitsGpu */
+    uint32_t bits;      /* estimated rate of the region's levels, 1/16 bit                         */
+    uint32_t n_nz;      /* non-zero levels of the region (what d_nnz holds)                        */
+} x266_rdoq_region_t;
+typedef struct x266_rdoq_t {
+    const int16_t *d_coef;             /* [n_regions * 1024], 16-byte aligned; NULL for xLevelsBitsGpu                       */
+    int16_t *d_level;                  /* [n_regions * 1024], 16-byte aligned; rdoq writes (may be d_coef), bits reads       */
+    const uint8_t *d_class;            /* [n_regions] or NULL (every region 32x32), any alignment                            */
+    const uint8_t *d_qp;               /* [n_regions] or NULL, any alignment                                                 */
+    uint32_t *d_nnz;                   /* [n_regions] or NULL, 4-byte aligned; rdoq writes, bits reads (0 = skip the region) */
+    x266_rdoq_region_t *d_stat;        /* [n_regions], 8-byte aligned; rdoq: may be NULL; bits: required                     */
+    size_t n_regions;
+    int qp, lambda;                    /* qp 0..51 checked only when d_qp == NULL; lambda 0..8192                            */
+} x266_rdoq_t;
+int xRdoQuantRegionsGpu(x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream);
+int xLevelsBitsGpu     (x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream);
+
 /* ---- source analysis: tile activity, the adaptive qp map and fade weights, in front of the searches and the coding calls ----
  * One pass over the tiled source frame gives per-tile sums and sums of squares; from them come the qp byte per region that
  * xQuantRegionsGpu, xDct32CodeCtuTilesGpu, xIntra32CodeFrameGpu and x266_deblock_t take as d_qp, and the x266_wp_t of the
@@ -1475,6 +1546,13 @@ int      xTransformMatrix(int type, int size, int16_t *m);
 int      xLevelScan(int size, uint16_t *pos);
 /* Regions the offset scan of xLevelsPackGpu takes per step (a test walks region counts around it). */
 unsigned xLevelsScanChunk(void);
+/* The rate model of xRdoQuantRegionsGpu / xLevelsBitsGpu, in 1/16 bit, from the very functions the kernels use: with them a host
+ * coder or a rate control reproduces `bits`.  xLevelBits: R(abs_level, pos_class), abs_level 0..32768, pos_class 0..2.  xLastPosBits:
+ * Rlast(u, v) of a block of 1 << log2_size, log2_size 2..5, u and v below the size.  xCgFlagBits: cgf[coded], coded 0 or 1.  Each
+ * returns -1 for any other argument. */
+int      xLevelBits(int abs_level, int pos_class);
+int      xLastPosBits(int u, int v, int log2_size);
+int      xCgFlagBits(int coded);
 const char *xHipVersion(void);
 
 /* ------------------------------------------------------------------------ */

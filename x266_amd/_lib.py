@@ -35,6 +35,16 @@ class LevelsParams(ctypes.Structure):
 LEVEL_REGION_DTYPE = np.dtype([("cg_mask", "<u8"), ("offset", "<u8"), ("n_words", "<u4"), ("n_nz", "<u4"), ("sum_abs", "<u4"), ("max_abs", "<u4")])
 
 
+class RdoqParams(ctypes.Structure):
+    """x266_rdoq_t of include/x266hip.h"""
+    _fields_ = [("d_coef", _P), ("d_level", _P), ("d_class", _P), ("d_qp", _P), ("d_nnz", _P), ("d_stat", _P), ("n_regions", ctypes.c_size_t),
+                ("qp", ctypes.c_int), ("lambda_", ctypes.c_int)]
+
+
+# x266_rdoq_region_t of include/x266hip.h
+RDOQ_REGION_DTYPE = np.dtype([("dist", "<u8"), ("bits", "<u4"), ("n_nz", "<u4")])
+
+
 class AqParams(ctypes.Structure):
     """x266_aq_t of include/x266hip.h"""
     _fields_ = [("d_src", _P), ("d_tile", _P), ("d_total", _P), ("d_offset", _P), ("d_qp", _P), ("width", ctypes.c_int), ("height", ctypes.c_int),
@@ -183,6 +193,11 @@ def load_library(path=None):
     L.xLevelScan.argtypes = [ctypes.c_int, _P]
     L.xLevelsScanChunk.argtypes = []
     L.xLevelsScanChunk.restype = ctypes.c_uint
+    L.xRdoQuantRegionsGpu.argtypes = [_P, ctypes.POINTER(RdoqParams), _P]
+    L.xLevelsBitsGpu.argtypes = [_P, ctypes.POINTER(RdoqParams), _P]
+    L.xLevelBits.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.xLastPosBits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.xCgFlagBits.argtypes = [ctypes.c_int]
     L.xAqStatsGpu.argtypes = [_P, ctypes.POINTER(AqParams), _P]
     L.xAqDecideGpu.argtypes = [_P, ctypes.POINTER(AqParams), _P]
     L.xAqTotalsChunk.argtypes = []
@@ -238,6 +253,30 @@ def level_scan(size):
 def levels_scan_chunk():
     """xLevelsScanChunk: regions the offset scan of xLevelsPackGpu takes per step"""
     return int(load_library().xLevelsScanChunk())
+
+
+def level_bits(abs_level, pos_class):
+    """xLevelBits: R(abs_level, pos_class) of the rate model of xRdoQuantRegionsGpu, in 1/16 bit.  No device."""
+    v = int(load_library().xLevelBits(int(abs_level), int(pos_class)))
+    if v < 0:
+        raise X266Error("xLevelBits: abs_level must be 0..32768 and pos_class 0..2")
+    return v
+
+
+def last_pos_bits(u, v, log2_size):
+    """xLastPosBits: Rlast(u, v) of a block of 1 << log2_size, in 1/16 bit.  No device."""
+    r = int(load_library().xLastPosBits(int(u), int(v), int(log2_size)))
+    if r < 0:
+        raise X266Error("xLastPosBits: log2_size must be 2..5, u and v below the size")
+    return r
+
+
+def cg_flag_bits(coded):
+    """xCgFlagBits: the cost of a coefficient group's coded flag, in 1/16 bit.  No device."""
+    r = int(load_library().xCgFlagBits(int(coded)))
+    if r < 0:
+        raise X266Error("xCgFlagBits: coded must be 0 or 1")
+    return r
 
 
 def aq_totals_chunk():
@@ -1299,6 +1338,56 @@ class Codec:
         self.levels_unpack_dev(p)
         self.stream_sync()
         return d_lv.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n)
+
+    # -- RDOQ and the level rate estimate -----------------------------------------------------------------
+    @staticmethod
+    def rdoq_params(d_coef=0, d_level=0, d_class=0, d_qp=0, d_nnz=0, d_stat=0, n_regions=0, qp=0, lam=0):
+        """an x266_rdoq_t from device addresses (0: NULL)"""
+        return RdoqParams(d_coef or None, d_level or None, d_class or None, d_qp or None, d_nnz or None, d_stat or None, int(n_regions), int(qp), int(lam))
+
+    def rdo_quant_dev(self, params, stream=0):
+        self._check(self.L.xRdoQuantRegionsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xRdoQuantRegionsGpu")
+
+    def levels_bits_dev(self, params, stream=0):
+        self._check(self.L.xLevelsBitsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xLevelsBitsGpu")
+
+    level_bits = staticmethod(level_bits)
+    last_pos_bits = staticmethod(last_pos_bits)
+    cg_flag_bits = staticmethod(cg_flag_bits)
+
+    def _byte_tab(self, n, t):
+        if t is None:
+            return None
+        t = np.ascontiguousarray(t, np.uint8).ravel()
+        assert t.size == n
+        d = self.alloc(max(n, 16))
+        d.upload(t)
+        return d
+
+    def rdo_quant(self, coef, classes=None, qps=None, qp=0, lam=368):
+        """numpy convenience around xRdoQuantRegionsGpu: [n_regions, 1024] int16, optional class and qp bytes per region -> (levels int16
+        [n_regions, 1024], non-zero counts uint32 [n_regions], records [n_regions] of RDOQ_REGION_DTYPE)"""
+        x = np.ascontiguousarray(coef, np.int16).reshape(-1, 1024)
+        n = x.shape[0]
+        d_in, d_out, d_nnz, d_stat = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16)), self.alloc(max(4 * n, 16)), self.alloc(max(16 * n, 16))
+        d_in.upload(x)
+        d_cls, d_qp = self._byte_tab(n, classes), self._byte_tab(n, qps)
+        self.rdo_quant_dev(self.rdoq_params(d_in.ptr, d_out.ptr, d_cls.ptr if d_cls else 0, d_qp.ptr if d_qp else 0, d_nnz.ptr, d_stat.ptr, n, qp, lam))
+        self.stream_sync()
+        return (d_out.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n),
+                d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE) if n else np.zeros(0, RDOQ_REGION_DTYPE))
+
+    def levels_bits(self, levels, classes=None, nnz=None):
+        """numpy convenience around xLevelsBitsGpu: [n_regions, 1024] int16 (and a class byte and a non-zero count per region, None: NULL)
+        -> records [n_regions] of RDOQ_REGION_DTYPE (dist 0)"""
+        x = np.ascontiguousarray(levels, np.int16).reshape(-1, 1024)
+        n = x.shape[0]
+        d_lv, d_stat = self.alloc(max(x.nbytes, 16)), self.alloc(max(16 * n, 16))
+        d_lv.upload(x)
+        d_cls, d_nnz = self._levels_tabs(n, classes, nnz)
+        self.levels_bits_dev(self.rdoq_params(0, d_lv.ptr, d_cls.ptr if d_cls else 0, 0, d_nnz.ptr if d_nnz else 0, d_stat.ptr, n))
+        self.stream_sync()
+        return d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE) if n else np.zeros(0, RDOQ_REGION_DTYPE)
 
     # -- source analysis: tile activity, the qp map, fade weights ---------------------------------------
     @staticmethod

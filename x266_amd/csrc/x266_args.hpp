@@ -8,7 +8,8 @@
 // the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
 // driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow; the two of the source analysis (aq_stats, aq_decide)
 // likewise by tests/cpp/aq_rules_check.cpp, the five of the lookahead (la_*) by tests/cpp/la_rules_check.cpp, the seeded search
-// (seeded_search) by tests/cpp/seed_rules_check.cpp, the mixed inter / intra frame (mixed_code_frame) by tests/cpp/mixed_rules_check.cpp.
+// (seeded_search) by tests/cpp/seed_rules_check.cpp, the mixed inter / intra frame (mixed_code_frame) by tests/cpp/mixed_rules_check.cpp,
+// RDOQ and the level rate estimate (rdoq_regions, levels_bits) by tests/cpp/rdoq_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -479,6 +480,31 @@ inline const char *levels_unpack(const x266_levels_t *p)
     Buf b[] = {out("d_level", p->d_level, 16, mul(n, 2048)), opt(out("d_nnz", p->d_nnz, 4, mul(n, 4))), in("d_region", p->d_region, 8, mul(n, 32)),
                in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), opt(in("d_class", p->d_class, 1, n))};
     b[3].optional = p->cap_words == 0;
+    return check(b);
+}
+
+// ---- rate-distortion optimised quantisation and the level rate estimate -------------------------------------------------------------
+// xRdoQuantRegionsGpu, xLevelsBitsGpu: the device pointers are the fields of the host-read x266_rdoq_t, held by
+// tests/cpp/rdoq_rules_check.cpp.  rdoq reads d_coef and writes d_level (which may BE d_coef), d_nnz and d_stat; bits reads d_level and
+// d_nnz, writes d_stat and looks at neither d_coef, d_qp, qp nor lambda.  With n_regions == 0 neither looks at anything.
+constexpr const char *kRdoqScalars = "qp must be 0..51 (without d_qp) and lambda 0..8192";
+inline const char *rdoq_regions(const x266_rdoq_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    const size_t n = p->n_regions;
+    if (n == 0) return nullptr;
+    if (!qp_ok(p->d_qp, p->qp) || p->lambda < 0 || p->lambda > 8192) return kRdoqScalars;
+    const Buf b[] = {out("d_level", p->d_level, 16, mul(n, 2048), "d_coef"), opt(out("d_nnz", p->d_nnz, 4, mul(n, 4))), opt(out("d_stat", p->d_stat, 8, mul(n, 16))),
+                     in("d_coef", p->d_coef, 16, mul(n, 2048)), opt(in("d_class", p->d_class, 1, n)), opt(in("d_qp", p->d_qp, 1, n))};
+    return check(b);
+}
+inline const char *levels_bits(const x266_rdoq_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    const size_t n = p->n_regions;
+    if (n == 0) return nullptr;
+    const Buf b[] = {out("d_stat", p->d_stat, 8, mul(n, 16)), in("d_level", p->d_level, 16, mul(n, 2048)), opt(in("d_class", p->d_class, 1, n)),
+                     opt(in("d_nnz", p->d_nnz, 4, mul(n, 4)))};
     return check(b);
 }
 

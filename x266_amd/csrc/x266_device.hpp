@@ -278,6 +278,9 @@ hipError_t launch_alf_apply(const x266_ref_block_t *d_in, x266_ref_block_t *d_ou
 hipError_t launch_levels_pack(const x266_levels_t &p, hipStream_t stream);
 hipError_t launch_levels_unpack(const x266_levels_t &p, hipStream_t stream);
 unsigned levels_scan_chunk();
+// RDOQ and the level rate estimate (rdoq_kernels.hip): one launch each
+hipError_t launch_rdo_quant_regions(const x266_rdoq_t &p, hipStream_t stream);
+hipError_t launch_levels_bits(const x266_rdoq_t &p, hipStream_t stream);
 // source analysis (aq_kernels.hip): stats = the tile records, then the totals' one workgroup of aq_totals_chunk() records per step
 hipError_t launch_aq_stats(const x266_aq_t &p, hipStream_t stream);
 hipError_t launch_aq_decide(const x266_aq_t &p, hipStream_t stream);

@@ -24,6 +24,7 @@
 #include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_levels.hpp"
+#include "x266_rdoq.hpp"
 #include "x266_lookahead.hpp"
 #include "x266_tables.hpp"
 
@@ -1393,6 +1394,39 @@ int xLevelScan(int size, uint16_t *pos)
 }
 
 unsigned xLevelsScanChunk(void) { return levels_scan_chunk(); }
+
+// ---- RDOQ and the level rate estimate (rdoq_kernels.hip, x266_rdoq.hpp) --------------------------------------------------------------------
+int xRdoQuantRegionsGpu(x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::rdoq_regions(p)) return refuse(ctx, __func__, why);
+    if (p->n_regions == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "RDOQ launch", launch_rdo_quant_regions(*p, (hipStream_t)stream));
+}
+
+int xLevelsBitsGpu(x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::levels_bits(p)) return refuse(ctx, __func__, why);
+    if (p->n_regions == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "level rate launch", launch_levels_bits(*p, (hipStream_t)stream));
+}
+
+int xLevelBits(int abs_level, int pos_class)
+{
+    if (abs_level < 0 || abs_level > 32768 || pos_class < 0 || pos_class > 2) return -1;
+    return (int)rdoq_level_bits((unsigned)abs_level, rdoq_sig_bits((unsigned)pos_class, 0), rdoq_sig_bits((unsigned)pos_class, 1));
+}
+
+int xLastPosBits(int u, int v, int log2_size)
+{
+    if (log2_size < 2 || log2_size > 5 || u < 0 || v < 0 || u >= (1 << log2_size) || v >= (1 << log2_size)) return -1;
+    return (int)(16u * (rdoq_last_pos((unsigned)u, (unsigned)log2_size) + rdoq_last_pos((unsigned)v, (unsigned)log2_size)));
+}
+
+int xCgFlagBits(int coded) { return coded == 0 || coded == 1 ? (int)rdoq_cg_flag_bits((unsigned)coded) : -1; }
 
 // ---- source analysis (aq_kernels.hip, x266_aq.hpp) ---------------------------------------------------------------------------------------------
 int xAqStatsGpu(x266hip_ctx *ctx, const x266_aq_t *p, void *stream)
