@@ -10,19 +10,16 @@
 // are a call's own follow in own_rules.  The expected verdict of every perturbation follows from that table and from the
 // literals in the per-call checks, never from the functions under test.  A new entry point adds a row.
 // Test infrastructure; built and run by tests/test_arg_rules.py (g++, plain and with sanitizers; no GPU, no HIP).
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <functional>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "rules_expect.hpp"
 #include "x266_args.hpp"
 
 using namespace x266;
 
-typedef uintptr_t U;
 struct Args {
     std::vector<U> p;
     int w = 0, h = 0;       // frame calls
@@ -53,25 +50,6 @@ struct Call {
     bool uv_rule = false;         // the last two pointers are the U / V output streams, which have a rule of their own
 };
 
-static int g_checks = 0, g_failures = 0;
-static std::map<std::string, int> g_per_call;
-static void expect(const char *call, const std::string &what, const char *got, bool refuse, const char *reason = nullptr)
-{
-    ++g_checks;
-    ++g_per_call[call];
-    if ((got != nullptr) == refuse && (!reason || !got || !std::strcmp(got, reason))) return;
-    ++g_failures;
-    std::printf("FAIL %s: %s: expected %s%s%s, got %s\n", call, what.c_str(), refuse ? "refuse" : "accept", reason ? " for " : "", reason ? reason : "",
-                got ? got : "accept");
-}
-static void range(const char *call, const char *what, int lo, int hi, const std::function<const char *(int)> &f, const char *reason = nullptr)
-{
-    expect(call, std::string(what) + " below", f(lo - 1), true, reason);
-    expect(call, std::string(what) + " lowest", f(lo), false);
-    expect(call, std::string(what) + " highest", f(hi), false);
-    expect(call, std::string(what) + " above", f(hi + 1), true, reason);
-}
-
 // extents, as include/x266hip.h states them
 static size_t BLK(const Args &a, size_t edge) { return ((size_t)a.w / edge) * ((size_t)a.h / edge); }
 static size_t CT(const Args &a) { return (((size_t)a.w + 63) / 64) * (((size_t)a.h + 63) / 64); }
@@ -100,9 +78,6 @@ static size_t N9432(const Args &a) { return a.n * 9432; }
 static size_t TOTAL(const Args &) { return 2358 * 8; }
 static size_t LUMA(const Args &a) { return (size_t)a.n_luma * 600; }
 static size_t CHROMA(const Args &a) { return (size_t)a.n_chroma * 16; }
-
-static U down(U x, unsigned a) { return x - x % a; }
-static U up(U x, unsigned a) { return down(x + a - 1, a); }
 
 // every pointer in a region of its own, at exactly its alignment times an odd number
 static Args base(const Call &c, int mult_w = 1, int mult_h = 1)

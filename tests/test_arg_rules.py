@@ -8,35 +8,20 @@ The surface tests need the built library and no GPU: every entry point is export
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
-import pytest
+
+import _cpp_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra"] + extra + ["-I", os.path.join(ROOT, "x266_amd", "csrc"),
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "arg_rules_check.cpp")], capture_output=True, text=True)
-    return exe, r
-
-
-def _run(exe):
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, (out.stdout[-4000:], out.stderr[-4000:])
-    assert "the argument rules hold" in out.stdout
-    return out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@_cpp_driver.needs_gxx
 def test_the_rules_hold_and_state_the_headers_alignments(tmp_path):
-    exe, r = _build(tmp_path, "arg_rules_check", [])
+    exe, r = _cpp_driver.build(tmp_path, "arg_rules_check")
     assert r.returncode == 0, r.stderr[-4000:]
-    text = _run(exe)
+    text = _cpp_driver.run(exe)
     lines = dict(re.findall(r"^(x\w+): (.*)$", text, re.M))
     got = {name: {k: int(v) for k, v in (i.split() for i in items.split(", "))} for name, items in lines.items()}
     from test_gpu_placement import device_entry_points, header_alignments
@@ -55,15 +40,9 @@ def test_the_rules_hold_and_state_the_headers_alignments(tmp_path):
         os.path.join(ROOT, "include", "x266hip.h")).read()
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@_cpp_driver.needs_gxx
 def test_the_rules_hold_under_the_sanitizers(tmp_path):
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run(["g++"] + SANITIZE + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime")
-    exe, r = _build(tmp_path, "arg_rules_check_san", SANITIZE + ["-fno-omit-frame-pointer", "-g"])
-    assert r.returncode == 0, r.stderr[-4000:]
-    _run(exe)
+    _cpp_driver.build_and_run_sanitized(tmp_path, "arg_rules_check")
 
 
 def test_the_library_exports_every_entry_point_and_a_null_context_is_refused():

@@ -1,20 +1,18 @@
-"""CPU: the argument rules of the five lookahead calls (x266_amd/csrc/x266_args.hpp: la_downscale, la_intra_costs, la_frame_cost,
-la_propagate, la_tree_qp) and of xSceneCutFromTotals against the contract as tests/cpp/la_rules_check.cpp writes it down: a base tuple,
-single perturbations, made-up addresses, the largest frame an int describes.  The driver is a stand-alone program, built twice -- plain,
-and with the address and undefined-behaviour sanitizers.  The calls keep their device pointers in a host-read struct, so the table of
-tests/cpp/arg_rules_check.cpp does not count them; the surface tests here do what tests/test_arg_rules.py does for the calls of that
-table.  g++ only: no GPU, no HIP."""
+"""CPU: the surface of the five lookahead calls and of xSceneCutFromTotals: header, struct layout, exports, bindings, and the scene cut's
+refusals and decisions through the ABI.  The calls keep their device pointers in a host-read struct; tests/cpp/struct_rules_check.cpp
+holds their argument rules (x266_amd/csrc/x266_args.hpp: la_downscale, la_intra_costs, la_frame_cost, la_propagate, la_tree_qp,
+scene_cut_from_totals) and tests/test_struct_arg_rules.py runs it.  No GPU, no HIP."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import _cpp_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 CALLS = ("xLaDownscaleGpu", "xLaIntraCostsGpu", "xLaFrameCostGpu", "xLaPropagateGpu", "xLaTreeQpGpu")
 ALIGN = {"d_src": 16, "d_low": 16, "d_intra": 4, "d_inter0": 8, "d_inter1": 8, "d_block": 16, "d_total": 8, "d_prop": 8, "d_prop_ref0": 8, "d_prop_ref1": 8,
          "d_aq_offset": 2, "d_offset": 2}
@@ -22,40 +20,7 @@ FIELDS = ["d_src", "d_low", "d_intra", "d_mode", "d_inter0", "d_inter1", "d_bloc
           "d_qp", "width", "height", "intra_penalty", "strength_q8", "qp", "chroma_qp_offset"]
 
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra"] + extra + ["-I", os.path.join(ROOT, "x266_amd", "csrc"),
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "la_rules_check.cpp")], capture_output=True, text=True)
-    return exe, r
-
-
-def _run(exe):
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, (out.stdout[-4000:], out.stderr[-4000:])
-    assert "the argument rules hold" in out.stdout
-    return out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold(tmp_path):
-    exe, r = _build(tmp_path, "la_rules_check", [])
-    assert r.returncode == 0, r.stderr[-4000:]
-    text = _run(exe)
-    checks = int(re.search(r"(\d+) checks, 0 failures", text).group(1))
-    assert checks >= 3000, checks                                             # a walk that shrank must not pass quietly
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold_under_the_sanitizers(tmp_path):
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run(["g++"] + SANITIZE + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime")
-    exe, r = _build(tmp_path, "la_rules_check_san", SANITIZE + ["-fno-omit-frame-pointer", "-g"])
-    assert r.returncode == 0, r.stderr[-4000:]
-    _run(exe)
-
-
+@_cpp_driver.needs_gxx
 def test_the_header_declares_the_calls_outside_the_one_table():
     """context first, stream last, the device pointers in the struct: the parser of the one table must not count them, and the
     struct's field comments state the alignments the driver holds"""
@@ -78,9 +43,7 @@ def test_the_header_declares_the_calls_outside_the_one_table():
         assert re.search(r"\*\s*%s;[^\n]*or NULL" % field, body), field            # ... and which fields may be NULL
     for field in ("d_src", "d_low", "d_intra", "d_block", "d_total"):
         assert not re.search(r"\*\s*%s;[^\n]*NULL" % field, body), field
-    driver = open(os.path.join(ROOT, "tests", "cpp", "la_rules_check.cpp")).read()
-    for field, align in list(ALIGN.items()) + [("d_mode", 1), ("d_qp", 1)]:
-        assert re.search(r'\{"%s", %d,' % (field, align), driver), field
+    _cpp_driver.assert_driver_follows_header("x266_la_t", CALLS)
     rec = re.search(r"typedef struct x266_la_block_t \{(.*?)\} x266_la_block_t;", hdr, re.S).group(1)
     assert re.findall(r"\b([a-z0-9_]+)[,;]", re.sub(r"/\*.*?\*/", "", rec)) == ["cost", "intra", "mvx", "mvy", "kind", "mode", "reserved"]
 

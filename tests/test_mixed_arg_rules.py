@@ -1,61 +1,23 @@
-"""CPU: the argument rules of mixed inter / intra frame coding, xDct32CodeMixedFrameGpu (x266_amd/csrc/x266_args.hpp: mixed_code_frame),
-against the contract as tests/cpp/mixed_rules_check.cpp writes it down: a base tuple with and without the optional buffers, single
-perturbations of every field, every allowed and every refused overlap, made-up addresses, the largest frame an int describes.  The driver
-is a stand-alone program, built twice -- plain, and with the address and undefined-behaviour sanitizers.  The call keeps its device
-pointers in a host-read struct, so the table of tests/cpp/arg_rules_check.cpp does not count it; the surface tests here do what
-tests/test_arg_rules.py does for the calls of that table.  g++ only: no GPU, no HIP."""
+"""CPU: the surface of mixed inter / intra frame coding, xDct32CodeMixedFrameGpu: header, struct layout, bindings, and that the per-wave
+pieces exist once.  The call keeps its device pointers in a host-read struct; tests/cpp/struct_rules_check.cpp holds its argument rules
+(x266_amd/csrc/x266_args.hpp: mixed_code_frame) and tests/test_struct_arg_rules.py runs it.  No GPU, no HIP."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import _cpp_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 CALL = "xDct32CodeMixedFrameGpu"
 ALIGN = {"d_cur": 16, "d_pred": 16, "d_qp": 1, "d_kind_in": 1, "d_mode_in": 1, "d_level": 16, "d_nnz": 4, "d_kind": 1, "d_mode": 1, "d_cost": 4, "d_recon": 16}
 OPTIONAL = ("d_qp", "d_kind_in", "d_mode_in", "d_nnz", "d_cost")
 FIELDS = list(ALIGN) + ["width", "height", "qp", "rounding", "intra_penalty"]
-CHECK_FLOOR = 2400                                                            # the finished driver prints 2493
 
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra"] + extra + ["-I", os.path.join(ROOT, "x266_amd", "csrc"),
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "mixed_rules_check.cpp")], capture_output=True, text=True)
-    return exe, r
-
-
-def _run(exe):
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, (out.stdout[-4000:], out.stderr[-4000:])
-    assert "the argument rules hold" in out.stdout
-    return out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold(tmp_path):
-    exe, r = _build(tmp_path, "mixed_rules_check", [])
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert not r.stderr.strip(), r.stderr[-4000:]                              # the shared arithmetic compiles without a warning as plain C++
-    text = _run(exe)
-    checks = int(re.search(r"(\d+) checks, 0 failures", text).group(1))
-    assert checks >= CHECK_FLOOR, checks                                      # a walk that shrank must not pass quietly
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold_under_the_sanitizers(tmp_path):
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run(["g++"] + SANITIZE + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime")
-    exe, r = _build(tmp_path, "mixed_rules_check_san", SANITIZE + ["-fno-omit-frame-pointer", "-g"])
-    assert r.returncode == 0, r.stderr[-4000:]
-    _run(exe)
-
-
+@_cpp_driver.needs_gxx
 def test_the_header_declares_the_call_outside_the_one_table():
     """context first, stream last, the device pointers in the struct: the parser of the one table must not count it, and the struct's
     field comments state the alignments the driver holds and "or NULL" where that applies"""
@@ -70,10 +32,8 @@ def test_the_header_declares_the_call_outside_the_one_table():
     assert stated == ALIGN, stated
     for field in ALIGN:
         assert bool(re.search(r"\*\s*%s;[^\n]*or NULL" % field, body)) == (field in OPTIONAL), field
-    driver = open(os.path.join(ROOT, "tests", "cpp", "mixed_rules_check.cpp")).read()
-    for field, align in ALIGN.items():
-        assert re.search(r'\{"%s", %d, (OPT \| )?(IN|OUT),' % (field, align), driver), field
-        assert bool(re.search(r'\{"%s", %d, OPT \| ' % (field, align), driver)) == (field in OPTIONAL), field
+    _cpp_driver.assert_driver_follows_header("x266_mixed_t", (CALL,), outputs_marked=True)
+    assert {f for f, (_, optional, _) in _cpp_driver.struct_call_lines()[CALL].items() if optional} == set(OPTIONAL)
     for consequence in ("(a) with every kind 0", "(b) with every kind 1", "(c) a region's result depends only on regions before it",
                         "(d) entries 0..3 of every CTU of d_kind"):                # the consequences the tests rely on
         assert consequence in hdr, consequence

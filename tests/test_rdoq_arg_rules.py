@@ -1,56 +1,20 @@
-"""CPU: the argument rules of xRdoQuantRegionsGpu and xLevelsBitsGpu (x266_amd/csrc/x266_args.hpp: rdoq_regions, levels_bits) against
-the contract as tests/cpp/rdoq_rules_check.cpp writes it down: a base tuple, single perturbations, made-up addresses, extents that
-saturate.  The driver is a stand-alone program, built twice -- plain, and with the address and undefined-behaviour sanitizers.  Then
-the surface: header, exports, bindings, NULL refusal, and that the rate tables stand in one file only.  g++ only: no GPU, no HIP."""
+"""CPU: the surface of xRdoQuantRegionsGpu and xLevelsBitsGpu: header, struct layout, exports, bindings, and that the rate tables stand
+in one file only.  The two calls keep their device pointers in a host-read struct; tests/cpp/struct_rules_check.cpp holds their argument
+rules (x266_amd/csrc/x266_args.hpp: rdoq_regions, levels_bits) and tests/test_struct_arg_rules.py runs it.  No GPU, no HIP."""
 import ctypes
 import glob
 import os
 import re
-import shutil
 import subprocess
 
-import pytest
+import _cpp_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 CALLS = ("xRdoQuantRegionsGpu", "xLevelsBitsGpu")
 HELPERS = ("xLevelBits", "xLastPosBits", "xCgFlagBits")
 
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra"] + extra + ["-I", os.path.join(ROOT, "x266_amd", "csrc"),
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "rdoq_rules_check.cpp")], capture_output=True, text=True)
-    return exe, r
-
-
-def _run(exe):
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, (out.stdout[-4000:], out.stderr[-4000:])
-    assert "the argument rules hold" in out.stdout
-    return out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold(tmp_path):
-    exe, r = _build(tmp_path, "rdoq_rules_check", [])
-    assert r.returncode == 0, r.stderr[-4000:]
-    text = _run(exe)
-    checks = int(re.search(r"(\d+) checks, 0 failures", text).group(1))
-    assert checks >= 250, checks                                              # a walk that shrank must not pass quietly
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold_under_the_sanitizers(tmp_path):
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run(["g++"] + SANITIZE + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime")
-    exe, r = _build(tmp_path, "rdoq_rules_check_san", SANITIZE + ["-fno-omit-frame-pointer", "-g"])
-    assert r.returncode == 0, r.stderr[-4000:]
-    _run(exe)
-
-
+@_cpp_driver.needs_gxx
 def test_the_header_declares_the_two_calls_outside_the_one_table():
     """context first, stream last, the device pointers in the struct: the parser of the one table must not count them, and the
     struct's field comments state the alignments the driver holds"""
@@ -65,9 +29,8 @@ def test_the_header_declares_the_two_calls_outside_the_one_table():
     assert stated == {"d_coef": 16, "d_level": 16, "d_nnz": 4, "d_stat": 8}, stated
     for field in ("d_class", "d_qp"):
         assert re.search(r"\*\s*%s;[^\n]*any alignment" % field, body)
-    driver = open(os.path.join(ROOT, "tests", "cpp", "rdoq_rules_check.cpp")).read()
-    for field, align in list(stated.items()) + [("d_class", 1), ("d_qp", 1)]:
-        assert re.search(r'\{"%s", %d,' % (field, align), driver), field
+    assert "rdoq: may be NULL; bits: required" in body                        # d_stat, the one field whose comment does not say "or NULL"
+    _cpp_driver.assert_driver_follows_header("x266_rdoq_t", CALLS, may_be_null={("xRdoQuantRegionsGpu", "d_stat")})
     for name in HELPERS:
         assert re.search(r"int\s+%s\(" % name, hdr), name
 

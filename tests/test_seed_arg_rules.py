@@ -1,58 +1,23 @@
-"""CPU: the argument rules of the seeded search, xSatd8x8SeededSearchGpu (x266_amd/csrc/x266_args.hpp: seeded_search), against the
-contract as tests/cpp/seed_rules_check.cpp writes it down: a base tuple at both seed scales, single perturbations, made-up addresses, the
-largest frame an int describes.  The driver is a stand-alone program, built twice -- plain, and with the address and
-undefined-behaviour sanitizers.  The call keeps its device pointers in a host-read struct, so the table of tests/cpp/arg_rules_check.cpp
-does not count it; the surface tests here do what tests/test_arg_rules.py does for the calls of that table.  g++ only: no GPU, no HIP."""
+"""CPU: the surface of the seeded search, xSatd8x8SeededSearchGpu: header, struct layout, bindings, and that the kernel and the rules
+share one copy of the arithmetic.  The call keeps its device pointers in a host-read struct; tests/cpp/struct_rules_check.cpp holds its
+argument rules (x266_amd/csrc/x266_args.hpp: seeded_search) at both seed scales and tests/test_struct_arg_rules.py runs it.  No GPU, no
+HIP."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import _cpp_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 CALL = "xSatd8x8SeededSearchGpu"
 ALIGN = {"d_cur": 16, "d_ref": 16, "d_seed": 8, "d_best": 8, "d_j": 4}
 FIELDS = ["d_cur", "d_ref", "d_seed", "d_best", "d_j", "width", "height", "seed_scale", "centres", "range", "lambda_q4"]
 
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra"] + extra + ["-I", os.path.join(ROOT, "x266_amd", "csrc"),
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "seed_rules_check.cpp")], capture_output=True, text=True)
-    return exe, r
-
-
-def _run(exe):
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, (out.stdout[-4000:], out.stderr[-4000:])
-    assert "the argument rules hold" in out.stdout
-    return out.stdout
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold(tmp_path):
-    exe, r = _build(tmp_path, "seed_rules_check", [])
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert not r.stderr.strip(), r.stderr[-4000:]                              # the shared arithmetic compiles without a warning as plain C++
-    text = _run(exe)
-    checks = int(re.search(r"(\d+) checks, 0 failures", text).group(1))
-    assert checks >= 880, checks                                             # a walk that shrank must not pass quietly
-
-
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-def test_the_rules_hold_under_the_sanitizers(tmp_path):
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run(["g++"] + SANITIZE + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime")
-    exe, r = _build(tmp_path, "seed_rules_check_san", SANITIZE + ["-fno-omit-frame-pointer", "-g"])
-    assert r.returncode == 0, r.stderr[-4000:]
-    _run(exe)
-
-
+@_cpp_driver.needs_gxx
 def test_the_header_declares_the_call_outside_the_one_table():
     """context first, stream last, the device pointers in the struct: the parser of the one table must not count it, and the struct's
     field comments state the alignments the driver holds"""
@@ -68,9 +33,7 @@ def test_the_header_declares_the_call_outside_the_one_table():
     assert re.search(r"\*\s*d_j;[^\n]*or NULL", body)
     for field in ("d_cur", "d_ref", "d_seed", "d_best"):
         assert not re.search(r"\*\s*%s;[^\n]*NULL" % field, body), field
-    driver = open(os.path.join(ROOT, "tests", "cpp", "seed_rules_check.cpp")).read()
-    for field, align in ALIGN.items():
-        assert re.search(r'\{"%s", %d,' % (field, align), driver), field
+    _cpp_driver.assert_driver_follows_header("x266_seed_t", (CALL,), outputs_marked=True)
     for consequence in ("at range 8", "entry [49 b + 24]"):                   # the two consequences the GPU tests rely on
         assert consequence in hdr, consequence
 

@@ -4,12 +4,12 @@
 // and returns the reason the call is refused, or nullptr when it is accepted; it reads nothing through the pointers and touches
 // no state, so tests/cpp/arg_rules_check.cpp -- one table with a row per entry point, one walk over it -- holds the rules of
 // every one of them without a device.  x266hip_abi.hip turns a reason into X266HIP_EINVAL and the text
-// "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.  The two calls of
-// the compact level stream (levels_pack, levels_unpack), whose device pointers are fields of a host-read struct, are held by a
-// driver of their own, tests/cpp/levels_rules_check.cpp, until that table can grow; the two of the source analysis (aq_stats, aq_decide)
-// likewise by tests/cpp/aq_rules_check.cpp, the five of the lookahead (la_*) by tests/cpp/la_rules_check.cpp, the seeded search
-// (seeded_search) by tests/cpp/seed_rules_check.cpp, the mixed inter / intra frame (mixed_code_frame) by tests/cpp/mixed_rules_check.cpp,
-// RDOQ and the level rate estimate (rdoq_regions, levels_bits) by tests/cpp/rdoq_rules_check.cpp.
+// "<entry point>: <reason>" and launches nothing.  A new entry point declares its rules here and adds a row there.  The calls whose
+// device pointers are fields of a host-read struct -- the compact level stream (levels_pack, levels_unpack), the source analysis
+// (aq_stats, aq_decide), the lookahead (la_*), the seeded search (seeded_search), the mixed inter / intra frame (mixed_code_frame), RDOQ
+// and the level rate estimate (rdoq_regions, levels_bits) -- are held the same way by tests/cpp/struct_rules_check.cpp: one description
+// per struct, one walk over every call of every one; a new struct call adds a row to its struct's description there, a new struct a
+// description.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -456,8 +456,8 @@ inline const char *alf_apply(const void *d_in, int w, int h, const void *d_class
 }
 
 // ---- the compact level stream ------------------------------------------------------------------------------------------------------
-// xLevelsPackGpu, xLevelsUnpackGpu: the device pointers are the fields of the host-read x266_levels_t.  d_stream may be NULL when
-// cap_words is 0 (pack: the count-only call); with n_regions == 0 pack looks at d_total alone and unpack at nothing.
+// xLevelsPackGpu, xLevelsUnpackGpu: the device pointers are the fields of the host-read x266_levels_t, held by tests/cpp/struct_rules_check.cpp.
+// d_stream may be NULL when cap_words is 0 (pack: the count-only call); with n_regions == 0 pack looks at d_total alone and unpack at nothing.
 inline size_t levels_stream_bytes(uint64_t cap_words) { return cap_words > SIZE_MAX / 2 ? SIZE_MAX : (size_t)cap_words * 2; }
 inline const char *levels_pack(const x266_levels_t *p)
 {
@@ -485,7 +485,7 @@ inline const char *levels_unpack(const x266_levels_t *p)
 
 // ---- rate-distortion optimised quantisation and the level rate estimate -------------------------------------------------------------
 // xRdoQuantRegionsGpu, xLevelsBitsGpu: the device pointers are the fields of the host-read x266_rdoq_t, held by
-// tests/cpp/rdoq_rules_check.cpp.  rdoq reads d_coef and writes d_level (which may BE d_coef), d_nnz and d_stat; bits reads d_level and
+// tests/cpp/struct_rules_check.cpp.  rdoq reads d_coef and writes d_level (which may BE d_coef), d_nnz and d_stat; bits reads d_level and
 // d_nnz, writes d_stat and looks at neither d_coef, d_qp, qp nor lambda.  With n_regions == 0 neither looks at anything.
 constexpr const char *kRdoqScalars = "qp must be 0..51 (without d_qp) and lambda 0..8192";
 inline const char *rdoq_regions(const x266_rdoq_t *p)
@@ -509,7 +509,7 @@ inline const char *levels_bits(const x266_rdoq_t *p)
 }
 
 // ---- source analysis ----------------------------------------------------------------------------------------------------------------
-// xAqStatsGpu, xAqDecideGpu: the device pointers are the fields of the host-read x266_aq_t, held by tests/cpp/aq_rules_check.cpp.  Stats
+// xAqStatsGpu, xAqDecideGpu: the device pointers are the fields of the host-read x266_aq_t, held by tests/cpp/struct_rules_check.cpp.  Stats
 // looks at d_src, d_tile, d_total and the frame size alone; decide at everything but d_src, and needs one of its two outputs.
 constexpr const char *kAqScalars = "mode must be 1 or 2, strength_q8 0..1024, qp 0..51 and chroma_qp_offset -12..12";
 inline size_t tiles16(int w, int h) { return (size_t)(w / 16) * (size_t)(h / 16); }
@@ -548,7 +548,7 @@ inline const char *weights_from_totals(const int64_t *cur, const int64_t *ref, i
 
 // ---- lookahead ------------------------------------------------------------------------------------------------------------------------
 // xLaDownscaleGpu, xLaIntraCostsGpu, xLaFrameCostGpu, xLaPropagateGpu, xLaTreeQpGpu: the device pointers are the fields of the host-read
-// x266_la_t, held by tests/cpp/la_rules_check.cpp.  Each call looks at the fields the header names for it; the sides are the
+// x266_la_t, held by tests/cpp/struct_rules_check.cpp.  Each call looks at the fields the header names for it; the sides are the
 // full-resolution frame's, multiples of 32; n = tiles16 is the number of lowres blocks.  An accumulator added into counts as an output.
 constexpr const char *kLaPenalty = "intra_penalty must be 0..65535";
 constexpr const char *kLaScalars = "strength_q8 must be 0..1024, qp 0..51 and chroma_qp_offset -12..12";
@@ -611,7 +611,7 @@ inline const char *scene_cut_from_totals(const int64_t *total, int threshold_q8,
 }
 
 // ---- the seeded search ----------------------------------------------------------------------------------------------------------------
-// xSatd8x8SeededSearchGpu: the device pointers are the fields of the host-read x266_seed_t, held by tests/cpp/seed_rules_check.cpp.  The
+// xSatd8x8SeededSearchGpu: the device pointers are the fields of the host-read x266_seed_t, held by tests/cpp/struct_rules_check.cpp.  The
 // seed grid and the scalars' ranges are x266_seed.hpp's, the kernel's own.  The two frames are read-only and may be one; an output
 // overlaps nothing, the seeds included: blocks read their neighbours' seeds.
 constexpr const char *kSeedScalars = "seed_scale must be 0 or 1, centres 0..31, range 0..8 and lambda_q4 0..65535";
@@ -645,7 +645,7 @@ inline const char *intra32_code_frame(const void *d_cur, int w, int h, const voi
                      opt(in("d_mode_in", d_mode_in, 1, ctus(w, h) * 6))};
     return check(b);
 }
-// xDct32CodeMixedFrameGpu: the device pointers are the fields of the host-read x266_mixed_t, held by tests/cpp/mixed_rules_check.cpp.  Three
+// xDct32CodeMixedFrameGpu: the device pointers are the fields of the host-read x266_mixed_t, held by tests/cpp/struct_rules_check.cpp.  Three
 // outputs may BE one input each (the reconstruction the inter prediction, the kinds and the modes their inputs); d_cur == d_pred are two inputs.
 constexpr const char *kMixedPenalty = "intra_penalty must be 0..16777216";
 inline const char *mixed_code_frame(const x266_mixed_t *p)
