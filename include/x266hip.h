@@ -1097,6 +1097,58 @@ typedef struct x266_rdoq_t {
 int xRdoQuantRegionsGpu(x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream);
 int xLevelsBitsGpu     (x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream);
 
+/* ---- transform decision: each region's class byte by rate-distortion cost ----
+ * The source of d_class.  xTransformCtuFromTilesDev / ToTilesDev, xQuantRegionsGpu, xRdoQuantRegionsGpu, xLevelsBitsGpu and
+ * xLevelsPackGpu / UnpackGpu read a class byte X266_TILE_CLASS(type, size) per 32x32 region; xTransformDecideCtuTilesGpu chooses it, per
+ * region, among the caller's candidates and writes the winner's levels with it.  dist and bits of x266_rdoq_region_t are in
+ * quantiser-step units for every class (the transforms' shifts and qbits = 14 + qp/6 + (7 - n) cancel N), so they compare across sizes.
+ * No upstream counterpart; the composition of the calls above is the contract.  All values are mathematical integers.
+ *
+ * Frame, CTUs and regions exactly as xTransformCtuFromTilesDev: width and height positive multiples of 16, n_ctu = ceil(width / 64) *
+ * ceil(height / 64), n = 6 n_ctu regions in the order 6 ctu + q (q: Y0 Y1 Y2 Y3 U V), samples outside the frame are residual 0 and
+ * every region slot is written.  qp = min(d_qp[r], 51), or the scalar qp when d_qp == NULL; lambda as in x266_rdoq_t.
+ * Candidates are uint16 masks over class byte values, bit k = class byte k; the valid bits are X266_TDECIDE_CLASSES: the 13 distinct
+ * classes, size 32 only as class 3 (DCT-II; the set has one 32-point matrix).  The effective mask of region r is d_cand[r] &
+ * X266_TDECIDE_CLASSES when d_cand != NULL and that is non-zero, otherwise cand_luma for q = 0..3 and cand_chroma for q = 4, 5.  The
+ * call applies no divisibility rule of its own, as the transform calls check no class byte: an encoder that wants no block to
+ * straddle the frame edge in a cut region says so in d_cand.  class_bits[k] is the caller's cost of signalling class k, in 1/16 bit.
+ *
+ * For region r and every class k of its effective mask:
+ *     C_k        = region r of xTransformCtuFromTilesDev run with every class byte equal to k
+ *     (L_k, S_k) = what xRdoQuantRegionsGpu gives for C_k with class k, the region's qp and lambda
+ *     J_k        = S_k.dist + lambda * (S_k.bits + class_bits[k])        (dist < 2^54, lambda * (...) < 2^34: J_k fits uint64)
+ * The winner is the k of least J_k; on a tie the smallest class byte wins.  d_class[r] = the winner, a value in 0..14; d_level gets
+ * the winner's L_k, block-major for its class; d_nnz and d_stat get the winner's S_k; d_cost[16 r + k] = J_k for the candidates and
+ * all ones for every other k.  A region wholly outside the frame follows the same rule: its residual is 0, every J_k = lambda *
+ * class_bits[k].  The outputs feed xQuantRegionsGpu(1, d_class), xTransformCtuToTilesDev(d_class), the deblocking calls (d_nnz) and
+ * xLevelsPackGpu(d_class) unchanged.
+ *
+ * One launch on the caller's stream, one region per wave, no atomics and no ordering between waves: the same input gives the same
+ * bytes on every run.  The call allocates nothing and can be captured into a graph.  It uses the context's installed transform
+ * matrices and returns X266HIP_EDEVICE when the tables are invalid.  X266HIP_EINVAL, with nothing launched and the call named in
+ * xHipLastError: a NULL p, a NULL or misaligned required buffer, a width or height that is not a positive multiple of 16, qp (without
+ * d_qp) or lambda out of range, a mask with a bit outside X266_TDECIDE_CLASSES or with no bit set, a span that does not fit in the
+ * address space, any overlap of an output with any other buffer of the call (d_cur == d_pred, two inputs, is allowed).  The extents
+ * are width * height * 2 (d_cur, d_pred), n (d_qp, d_class), n * 2 (d_cand), n * 2048 (d_level), n * 4 (d_nnz), n * 16 (d_stat) and
+ * n * 128 (d_cost). */
+#define X266_TDECIDE_CLASSES 0x777F
+typedef struct x266_tdecide_t {
+    const x266_ref_block_t *d_cur;     /* tiled frame, width * height * 2 bytes, 16-byte aligned                              */
+    const x266_ref_block_t *d_pred;    /* tiled frame, width * height * 2 bytes, 16-byte aligned; may be d_cur                */
+    const uint8_t *d_qp;               /* [n] or NULL, any alignment                                                          */
+    const uint16_t *d_cand;            /* [n] or NULL, 2-byte aligned; the per-region candidate masks                         */
+    uint8_t *d_class;                  /* [n], any alignment; the winners                                                     */
+    int16_t *d_level;                  /* [n * 1024], 16-byte aligned; the winners' levels                                    */
+    uint32_t *d_nnz;                   /* [n] or NULL, 4-byte aligned                                                         */
+    x266_rdoq_region_t *d_stat;        /* [n] or NULL, 8-byte aligned                                                         */
+    uint64_t *d_cost;                  /* [n * 16] or NULL, 8-byte aligned; J_k, all ones where k is no candidate             */
+    int width, height;                 /* positive multiples of 16                                                            */
+    int qp, lambda;                    /* qp 0..51 checked only when d_qp == NULL; lambda 0..8192                             */
+    uint16_t cand_luma, cand_chroma;   /* masks within X266_TDECIDE_CLASSES, at least one bit each                            */
+    uint16_t class_bits[16];           /* side-information cost of class k, 1/16 bit                                          */
+} x266_tdecide_t;
+int xTransformDecideCtuTilesGpu(x266hip_ctx *ctx, const x266_tdecide_t *p, void *stream);
+
 /* ---- source analysis: tile activity, the adaptive qp map and fade weights, in front of the searches and the coding calls ----
  * One pass over the tiled source frame gives per-tile sums and sums of squares; from them come the qp byte per region that
  * xQuantRegionsGpu, xDct32CodeCtuTilesGpu, xIntra32CodeFrameGpu and x266_deblock_t take as d_qp, and the x266_wp_t of the

@@ -45,6 +45,16 @@ class RdoqParams(ctypes.Structure):
 RDOQ_REGION_DTYPE = np.dtype([("dist", "<u8"), ("bits", "<u4"), ("n_nz", "<u4")])
 
 
+class TDecideParams(ctypes.Structure):
+    """x266_tdecide_t of include/x266hip.h"""
+    _fields_ = [("d_cur", _P), ("d_pred", _P), ("d_qp", _P), ("d_cand", _P), ("d_class", _P), ("d_level", _P), ("d_nnz", _P), ("d_stat", _P),
+                ("d_cost", _P), ("width", ctypes.c_int), ("height", ctypes.c_int), ("qp", ctypes.c_int), ("lambda_", ctypes.c_int),
+                ("cand_luma", ctypes.c_uint16), ("cand_chroma", ctypes.c_uint16), ("class_bits", ctypes.c_uint16 * 16)]
+
+
+TDECIDE_CLASSES = 0x777F        # X266_TDECIDE_CLASSES: the 13 distinct classes as a mask over class byte values
+
+
 class AqParams(ctypes.Structure):
     """x266_aq_t of include/x266hip.h"""
     _fields_ = [("d_src", _P), ("d_tile", _P), ("d_total", _P), ("d_offset", _P), ("d_qp", _P), ("width", ctypes.c_int), ("height", ctypes.c_int),
@@ -195,6 +205,7 @@ def load_library(path=None):
     L.xLevelsScanChunk.restype = ctypes.c_uint
     L.xRdoQuantRegionsGpu.argtypes = [_P, ctypes.POINTER(RdoqParams), _P]
     L.xLevelsBitsGpu.argtypes = [_P, ctypes.POINTER(RdoqParams), _P]
+    L.xTransformDecideCtuTilesGpu.argtypes = [_P, ctypes.POINTER(TDecideParams), _P]
     L.xLevelBits.argtypes = [ctypes.c_int, ctypes.c_int]
     L.xLastPosBits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.xCgFlagBits.argtypes = [ctypes.c_int]
@@ -1388,6 +1399,45 @@ class Codec:
         self.levels_bits_dev(self.rdoq_params(0, d_lv.ptr, d_cls.ptr if d_cls else 0, 0, d_nnz.ptr if d_nnz else 0, d_stat.ptr, n))
         self.stream_sync()
         return d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE) if n else np.zeros(0, RDOQ_REGION_DTYPE)
+
+    # -- the transform decision: each region's class byte by rate-distortion cost ------------------------
+    @staticmethod
+    def tdecide_params(d_cur=0, d_pred=0, d_qp=0, d_cand=0, d_class=0, d_level=0, d_nnz=0, d_stat=0, d_cost=0, width=0, height=0, qp=0, lam=0,
+                       cand_luma=TDECIDE_CLASSES, cand_chroma=TDECIDE_CLASSES, class_bits=None):
+        """an x266_tdecide_t from device addresses (0: NULL); class_bits: up to 16 values in 1/16 bit (None: zeros)"""
+        bits = (ctypes.c_uint16 * 16)(*[int(b) for b in (class_bits if class_bits is not None else ())])
+        return TDecideParams(d_cur or None, d_pred or None, d_qp or None, d_cand or None, d_class or None, d_level or None, d_nnz or None,
+                             d_stat or None, d_cost or None, int(width), int(height), int(qp), int(lam), int(cand_luma), int(cand_chroma), bits)
+
+    def transform_decide_dev(self, params, stream=0):
+        self._check(self.L.xTransformDecideCtuTilesGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream),
+                    "xTransformDecideCtuTilesGpu")
+
+    def transform_decide(self, cur_tiles, pred_tiles, w, h, qps=None, qp=0, lam=368, cand_luma=TDECIDE_CLASSES, cand_chroma=TDECIDE_CLASSES,
+                         cand=None, class_bits=None):
+        """numpy convenience around xTransformDecideCtuTilesGpu: two tile arrays of a w x h frame (uint8, 512 bytes per tile), optional qp
+        bytes and candidate masks (uint16) per region -> (class bytes uint8 [n], levels int16 [n, 1024], non-zero counts uint32 [n],
+        records [n] of RDOQ_REGION_DTYPE, costs uint64 [n, 16]) with n = 6 CTUs' regions."""
+        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
+        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
+        n = 6 * self.ctu_count(w, h)
+        assert cur.size == w * h * 2 and pred.size == w * h * 2
+        dc, dp = self.alloc(cur.nbytes), self.alloc(pred.nbytes)
+        dc.upload(cur)
+        dp.upload(pred)
+        d_qp = self._byte_tab(n, qps)
+        d_cand = None
+        if cand is not None:
+            m = np.ascontiguousarray(cand, np.uint16).ravel()
+            assert m.size == n
+            d_cand = self.alloc(max(2 * n, 16))
+            d_cand.upload(m)
+        d_cls, d_lv, d_nnz, d_stat, d_cost = self.alloc(max(n, 16)), self.alloc(n * 2048), self.alloc(max(4 * n, 16)), self.alloc(16 * n), self.alloc(128 * n)
+        self.transform_decide_dev(self.tdecide_params(dc.ptr, dp.ptr, d_qp.ptr if d_qp else 0, d_cand.ptr if d_cand else 0, d_cls.ptr, d_lv.ptr, d_nnz.ptr,
+                                                      d_stat.ptr, d_cost.ptr, w, h, qp, lam, cand_luma, cand_chroma, class_bits))
+        self.stream_sync()
+        return (d_cls.download(np.uint8, n), d_lv.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n),
+                d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE), d_cost.download(np.uint64, 16 * n).reshape(n, 16))
 
     # -- source analysis: tile activity, the qp map, fade weights ---------------------------------------
     @staticmethod

@@ -9,7 +9,8 @@
 // (aq_stats, aq_decide), the lookahead (la_*), the seeded search (seeded_search), the mixed inter / intra frame (mixed_code_frame), RDOQ
 // and the level rate estimate (rdoq_regions, levels_bits) -- are held the same way by tests/cpp/struct_rules_check.cpp: one description
 // per struct, one walk over every call of every one; a new struct call adds a row to its struct's description there, a new struct a
-// description.
+// description.  The transform decision (transform_decide, x266_tdecide_t) has a stand-alone driver of the same form,
+// tests/cpp/tdecide_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -505,6 +506,25 @@ inline const char *levels_bits(const x266_rdoq_t *p)
     if (n == 0) return nullptr;
     const Buf b[] = {out("d_stat", p->d_stat, 8, mul(n, 16)), in("d_level", p->d_level, 16, mul(n, 2048)), opt(in("d_class", p->d_class, 1, n)),
                      opt(in("d_nnz", p->d_nnz, 4, mul(n, 4)))};
+    return check(b);
+}
+
+// ---- the transform decision ---------------------------------------------------------------------------------------------------------
+// xTransformDecideCtuTilesGpu: the device pointers are the fields of the host-read x266_tdecide_t, held by tests/cpp/tdecide_rules_check.cpp.
+// It reads d_cur and d_pred (which may be the same frame), d_qp and d_cand, and writes d_class, d_level, d_nnz, d_stat and d_cost: no
+// output may overlap anything.
+constexpr const char *kTDecideMasks = "cand_luma and cand_chroma must have a bit set and none outside 0x777F";
+inline bool tdecide_mask_ok(unsigned m) { return m != 0 && (m & ~(unsigned)X266_TDECIDE_CLASSES) == 0; }
+inline const char *transform_decide(const x266_tdecide_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (!qp_ok(p->d_qp, p->qp) || p->lambda < 0 || p->lambda > 8192) return kRdoqScalars;
+    if (!tdecide_mask_ok(p->cand_luma) || !tdecide_mask_ok(p->cand_chroma)) return kTDecideMasks;
+    const size_t n = mul(ctus(p->width, p->height), 6), frame_bytes = tile_bytes(p->width, p->height);
+    const Buf b[] = {out("d_class", p->d_class, 1, n), out("d_level", p->d_level, 16, mul(n, 2048)), opt(out("d_nnz", p->d_nnz, 4, mul(n, 4))),
+                     opt(out("d_stat", p->d_stat, 8, mul(n, 16))), opt(out("d_cost", p->d_cost, 8, mul(n, 128))), in("d_cur", p->d_cur, 16, frame_bytes),
+                     in("d_pred", p->d_pred, 16, frame_bytes), opt(in("d_qp", p->d_qp, 1, n)), opt(in("d_cand", p->d_cand, 2, mul(n, 2)))};
     return check(b);
 }
 

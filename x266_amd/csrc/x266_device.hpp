@@ -281,6 +281,8 @@ unsigned levels_scan_chunk();
 // RDOQ and the level rate estimate (rdoq_kernels.hip): one launch each
 hipError_t launch_rdo_quant_regions(const x266_rdoq_t &p, hipStream_t stream);
 hipError_t launch_levels_bits(const x266_rdoq_t &p, hipStream_t stream);
+// the transform decision (rdoq_kernels.hip): one launch, one region per wave; d_tab is the forward TileTab
+hipError_t launch_transform_decide(const x266_tdecide_t &p, const TileTab *d_tab, hipStream_t stream);
 // source analysis (aq_kernels.hip): stats = the tile records, then the totals' one workgroup of aq_totals_chunk() records per step
 hipError_t launch_aq_stats(const x266_aq_t &p, hipStream_t stream);
 hipError_t launch_aq_decide(const x266_aq_t &p, hipStream_t stream);

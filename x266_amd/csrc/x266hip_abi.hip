@@ -1414,6 +1414,16 @@ int xLevelsBitsGpu(x266hip_ctx *ctx, const x266_rdoq_t *p, void *stream)
     return launched(ctx, "level rate launch", launch_levels_bits(*p, (hipStream_t)stream));
 }
 
+// the transform decision: the forward tables of the mixed set, like xTransformCtuFromTilesDev
+int xTransformDecideCtuTilesGpu(x266hip_ctx *ctx, const x266_tdecide_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::transform_decide(p)) return refuse(ctx, __func__, why);
+    if (!ctx->tr_tables_valid) return tables_invalid(ctx, __func__);
+    X_DEV(ctx);
+    return launched(ctx, "transform decision launch", launch_transform_decide(*p, ctx->d_tile_fwd, (hipStream_t)stream));
+}
+
 int xLevelBits(int abs_level, int pos_class)
 {
     if (abs_level < 0 || abs_level > 32768 || pos_class < 0 || pos_class > 2) return -1;
