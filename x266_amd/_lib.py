@@ -358,6 +358,17 @@ class DeviceBuffer:
             pass
 
 
+class _Null:
+    """The buffer that stands for an absent array: NULL to the call, nothing to download."""
+    ptr = 0
+
+    def __bool__(self):
+        return False
+
+
+_NULL = _Null()
+
+
 class Codec:
     """Context object mirroring x266hip_ctx (xHipCodecInit / xHipCodecFree)."""
 
@@ -421,6 +432,68 @@ class Codec:
             if not getattr(self, "ctx", None):
                 raise X266Error("%s: the codec is closed" % what)
             raise X266Error("%s failed (%d): %s" % (what, rc, self.L.xHipLastError(self.ctx).decode()))
+
+    # -- the pieces of the numpy convenience methods: each method is its inputs, one *_dev call, one _fetch ------------------
+    def _upload(self, a, dtype=None):
+        a = np.ascontiguousarray(a, dtype)
+        d = self.alloc(max(a.nbytes, 16))
+        d.upload(a)
+        return d
+
+    def _frame(self, tiles, w, h):
+        """upload the tile array of a w x h frame (uint8, 2 bytes per luma sample)"""
+        t = np.ascontiguousarray(tiles, np.uint8).ravel()
+        assert t.size == w * h * 2
+        return self._upload(t)
+
+    def _out_frame(self, base, default):
+        """upload what an output holds before the call: `base`, or for None `default` (zeros, or the prediction's tiles)"""
+        return self._upload(np.ascontiguousarray(default if base is None else base, np.uint8).ravel())
+
+    def _table(self, t, dtype, count=None, tail=0):
+        """upload a side table of `count` elements (None: any number) and `tail` zero elements behind them; for None, _NULL"""
+        if t is None:
+            return _NULL
+        t = np.ascontiguousarray(t, dtype).ravel()
+        assert count is None or t.size == count
+        return self._upload(np.concatenate([t, np.zeros(tail, t.dtype)]) if tail else t)
+
+    def _ref_sets(self, refs):
+        """upload intra reference sets [n, 129] uint8 (left | top), each padded to the 144 bytes a set takes on the device"""
+        refs = np.ascontiguousarray(refs, np.uint8).reshape(-1, 129)
+        padded = np.zeros((refs.shape[0], 144), np.uint8)
+        padded[:, :129] = refs
+        return self._upload(padded)
+
+    @staticmethod
+    def _records(mv, nb):
+        """vectors [nb, 2] -> the 8-byte records (mvx, mvy, 4 bytes of cost) the motion calls read"""
+        rec = np.zeros((nb, 4), np.int16)
+        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
+        return rec
+
+    def _fetch(self, *outs):
+        """one sync, then every (buffer, dtype, shape) downloaded: a tuple, or the array itself where there is one.  Nothing is
+        downloaded for an empty shape; a NULL buffer (_NULL, an output that was not asked for) gives None"""
+        self.stream_sync()
+        got = tuple(np.zeros(shape, dtype) if 0 in shape else d.download(dtype, int(np.prod(shape))).reshape(shape) if d else None
+                    for d, dtype, shape in outs)
+        return got if len(got) > 1 else got[0]
+
+    def _fetch_best(self, d_best, nb, d_more, shape):
+        """_fetch of the search calls: their 8-byte best records and a uint32 array beside them (or _NULL)
+        -> (mv [nb, 2] int16, cost [nb] uint32, that array or None)"""
+        raw, more = self._fetch((d_best, np.uint8, (nb * 8,)), (d_more, np.uint32, shape))
+        return raw.view(np.int16).reshape(nb, 4)[:, :2].copy(), raw.view(np.uint32).reshape(nb, 2)[:, 1].copy(), more
+
+    @staticmethod
+    def _keyword_params(struct, what, pointers, scalars):
+        """a struct whose fields are pointers, given by field name (absent or 0: NULL), and then `scalars`"""
+        names = [f[0] for f in struct._fields_[:-len(scalars)]]
+        unknown = set(pointers) - set(names)
+        if unknown:
+            raise TypeError("%s: no such field: %s" % (what, sorted(unknown)))
+        return struct(*([pointers.get(n) or None for n in names] + [int(s) for s in scalars]))
 
     # -- info / options ----------------------------------------------------
     def device_info(self):
@@ -487,62 +560,34 @@ class Codec:
 
     def intra32_predict(self, refs, modes, ref_index=None):
         """Host convenience: refs [n_refs,129] uint8 (left | top) -> predictions [n,1024] uint8."""
-        refs = np.ascontiguousarray(refs, np.uint8).reshape(-1, 129)
         modes = np.ascontiguousarray(modes, np.uint8)
         n = modes.shape[0]
-        padded = np.zeros((refs.shape[0], 144), np.uint8)
-        padded[:, :129] = refs
-        d_r, d_m, d_p = self.alloc(max(padded.nbytes, 16)), self.alloc(max(n, 16)), self.alloc(max(n * 1024, 16))
-        d_r.upload(padded)
-        d_m.upload(modes)
-        d_i = None
-        if ref_index is not None:
-            d_i = self.alloc(max(4 * n, 16))
-            d_i.upload(np.ascontiguousarray(ref_index, np.uint32))
-        self.intra32_predict_dev(d_r.ptr, d_m.ptr, d_i.ptr if d_i else 0, d_p.ptr, n)
-        self.stream_sync()
-        return d_p.download(np.uint8, n * 1024).reshape(n, 1024)
+        d_r, d_m, d_i, d_p = self._ref_sets(refs), self._upload(modes), self._table(ref_index, np.uint32), self.alloc(max(n * 1024, 16))
+        self.intra32_predict_dev(d_r.ptr, d_m.ptr, d_i.ptr, d_p.ptr, n)
+        return self._fetch((d_p, np.uint8, (n, 1024)))
 
     def intra32_residual_dct32_dev(self, d_refs, d_modes, d_ref_index, d_src, d_coef, n, stream=0):
         self._check(self.L.xIntra32ResidualDct32Dev(self.ctx, d_refs, d_modes, d_ref_index or None, d_src, d_coef, n, stream), "xIntra32ResidualDct32Dev")
 
     def intra32_residual_dct32(self, refs, modes, src, ref_index=None):
         """Host convenience: refs [n_refs,129] uint8, modes [n], src [n,1024] uint8 -> coefficients [n,1024] int16."""
-        refs = np.ascontiguousarray(refs, np.uint8).reshape(-1, 129)
         modes = np.ascontiguousarray(modes, np.uint8)
-        src = np.ascontiguousarray(src, np.uint8).reshape(-1, 1024)
         n = modes.shape[0]
-        padded = np.zeros((refs.shape[0], 144), np.uint8)
-        padded[:, :129] = refs
-        d_r, d_m, d_s, d_c = self.alloc(max(padded.nbytes, 16)), self.alloc(max(n, 16)), self.alloc(max(n * 1024, 16)), self.alloc(max(n * 2048, 16))
-        d_r.upload(padded)
-        d_m.upload(modes)
-        d_s.upload(src)
-        d_i = None
-        if ref_index is not None:
-            d_i = self.alloc(max(4 * n, 16))
-            d_i.upload(np.ascontiguousarray(ref_index, np.uint32))
-        self.intra32_residual_dct32_dev(d_r.ptr, d_m.ptr, d_i.ptr if d_i else 0, d_s.ptr, d_c.ptr, n)
-        self.stream_sync()
-        return d_c.download(np.int16, n * 1024).reshape(n, 1024)
+        d_r, d_m, d_i = self._ref_sets(refs), self._upload(modes), self._table(ref_index, np.uint32)
+        d_s, d_c = self._upload(np.ascontiguousarray(src, np.uint8).reshape(-1, 1024)), self.alloc(max(n * 2048, 16))
+        self.intra32_residual_dct32_dev(d_r.ptr, d_m.ptr, d_i.ptr, d_s.ptr, d_c.ptr, n)
+        return self._fetch((d_c, np.int16, (n, 1024)))
 
     def intra32_costs_dev(self, d_refs, d_src, d_costs, d_best_mode, n, stream=0):
         self._check(self.L.xIntra32CostsDev(self.ctx, d_refs, d_src, d_costs, d_best_mode or None, n, stream), "xIntra32CostsDev")
 
     def intra32_costs(self, refs, src):
         """Host convenience: refs [n,129], src [n,1024] uint8 -> (costs [n,35] uint32, best_mode [n] uint8)."""
-        refs = np.ascontiguousarray(refs, np.uint8).reshape(-1, 129)
-        src = np.ascontiguousarray(src, np.uint8).reshape(-1, 1024)
-        n = refs.shape[0]
-        padded = np.zeros((n, 144), np.uint8)
-        padded[:, :129] = refs
-        d_r, d_s = self.alloc(max(padded.nbytes, 16)), self.alloc(max(src.nbytes, 16))
+        n = np.size(refs) // 129
+        d_r, d_s = self._ref_sets(refs), self._upload(np.ascontiguousarray(src, np.uint8).reshape(-1, 1024))
         d_c, d_b = self.alloc(max(n * 35 * 4, 16)), self.alloc(max(n, 16))
-        d_r.upload(padded)
-        d_s.upload(src)
         self.intra32_costs_dev(d_r.ptr, d_s.ptr, d_c.ptr, d_b.ptr, n)
-        self.stream_sync()
-        return d_c.download(np.uint32, n * 35).reshape(n, 35), d_b.download(np.uint8, n)
+        return self._fetch((d_c, np.uint32, (n, 35)), (d_b, np.uint8, (n,)))
 
     def intra32_refs_from_tiles_dev(self, d_frame, w, h, component, d_refs, stream=0):
         self._check(self.L.xIntra32RefsFromTilesGpu(self.ctx, d_frame, w, h, int(component), d_refs, stream), "xIntra32RefsFromTilesGpu")
@@ -551,15 +596,10 @@ class Codec:
         """numpy convenience around xIntra32RefsFromTilesGpu: a tile array of a w x h frame (multiples of 64) -> the reference sets of
         its own samples as uint8 [n_sets, 144] (left[64] | top[65] | 15 reserved bytes): 4 per CTU for component 0, 1 for U (1) / V (2).
         `base` pre-fills the output (None: zeros)"""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
         n = self.ctu_count(w, h) * (4 if component == 0 else 1)
-        assert src.size == w * h * 2
-        d_in, d_out = self.alloc(src.nbytes), self.alloc(n * 144)
-        d_in.upload(src)
-        d_out.upload(np.zeros(n * 144, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        d_in, d_out = self._frame(tiles, w, h), self._out_frame(base, np.zeros(n * 144, np.uint8))
         self.intra32_refs_from_tiles_dev(d_in.ptr, w, h, component, d_out.ptr)
-        self.stream_sync()
-        return d_out.download(np.uint8, n * 144).reshape(n, 144)
+        return self._fetch((d_out, np.uint8, (n, 144)))
 
     def intra32_code_frame_dev(self, d_cur, w, h, d_qp, qp, rounding, d_mode_in, d_level, d_nnz, d_mode, d_recon, stream=0):
         self._check(self.L.xIntra32CodeFrameGpu(self.ctx, d_cur, w, h, d_qp or None, int(qp), int(rounding), d_mode_in or None, d_level, d_nnz or None,
@@ -569,26 +609,12 @@ class Codec:
         """numpy convenience around xIntra32CodeFrameGpu: the tile array of a w x h frame (multiples of 64), optionally 6 qp bytes and 6
         mode bytes per CTU -> (levels [n_ctus, 6, 1024] int16, non-zero counts [n_ctus, 6] uint32, modes [n_ctus, 6] uint8, the
         reconstructed tile array); m_I (never written) comes from `base` (a tile array; None: zeros)"""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
         n = self.ctu_count(w, h)
-        assert cur.size == w * h * 2
-        dc, dr = self.alloc(cur.nbytes), self.alloc(cur.nbytes)
+        dc, dr = self._frame(cur_tiles, w, h), self._out_frame(base, np.zeros(w * h * 2, np.uint8))
+        dq, dmi = self._table(qps, np.uint8, 6 * n), self._table(modes_in, np.uint8, 6 * n)
         dl, dn, dm = self.alloc(n * 12288), self.alloc(max(n * 24, 16)), self.alloc(max(n * 6, 16))
-        dc.upload(cur)
-        dr.upload(np.zeros(cur.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
-        tabs = []
-        for t in (qps, modes_in):
-            if t is None:
-                tabs.append(None)
-                continue
-            t = np.ascontiguousarray(t, np.uint8).ravel()
-            assert t.size == 6 * n
-            tabs.append(self.alloc(max(t.nbytes, 16)))
-            tabs[-1].upload(t)
-        self.intra32_code_frame_dev(dc.ptr, w, h, tabs[0].ptr if tabs[0] else 0, qp, rounding, tabs[1].ptr if tabs[1] else 0, dl.ptr, dn.ptr, dm.ptr, dr.ptr)
-        self.stream_sync()
-        return (dl.download(np.int16, n * 6144).reshape(n, 6, 1024), dn.download(np.uint32, n * 6).reshape(n, 6),
-                dm.download(np.uint8, n * 6).reshape(n, 6), dr.download(np.uint8, cur.size))
+        self.intra32_code_frame_dev(dc.ptr, w, h, dq.ptr, qp, rounding, dmi.ptr, dl.ptr, dn.ptr, dm.ptr, dr.ptr)
+        return self._fetch((dl, np.int16, (n, 6, 1024)), (dn, np.uint32, (n, 6)), (dm, np.uint8, (n, 6)), (dr, np.uint8, (w * h * 2,)))
 
     def mem_ceiling_dev(self, kind, d_src, d_dst, nbytes, stream=0):
         """kind 0 = streaming copy, 1 = read-only stream (one uint32 XOR per 2 KiB into d_dst): this box's memory ceilings"""
@@ -607,19 +633,13 @@ class Codec:
         x = np.ascontiguousarray(x, np.int16)
         if offsets is None:
             n = x.size // (size * size)
-            din, dout = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16))
-            din.upload(x)
+            din, dout = self._upload(x), self.alloc(max(x.nbytes, 16))
             self.transform_fwd_dev(ttype, size, din.ptr, dout.ptr, n)
-            self.stream_sync()
-            return dout.download(np.int16, x.size).reshape(n, size * size)
+            return self._fetch((dout, np.int16, (n, size * size)))
         offsets = np.ascontiguousarray(offsets, np.uint32)
-        din, dout, doff = self.alloc(x.nbytes), self.alloc(x.nbytes), self.alloc(max(offsets.nbytes, 16))
-        din.upload(x)
-        dout.upload(np.zeros_like(x))
-        doff.upload(offsets)
+        din, dout, doff = self._upload(x), self._upload(np.zeros_like(x)), self._upload(offsets)
         self.transform_fwd_dev(ttype, size, din.ptr, dout.ptr, offsets.size, doff.ptr)
-        self.stream_sync()
-        return dout.download(np.int16, x.size)
+        return self._fetch((dout, np.int16, (x.size,)))
 
     def conv_input_fmt_dev(self, d_tiles, d_y, d_u, d_v, strd_y, w, h, stream=0):
         self._check(self.L.xConvInputFmtDev(self.ctx, d_tiles, d_y, d_u, d_v, strd_y, w, h, stream), "xConvInputFmtDev")
@@ -669,12 +689,9 @@ class Codec:
         a = np.ascontiguousarray(a, np.uint8).reshape(-1, edge * edge)
         b = np.ascontiguousarray(b, np.uint8).reshape(-1, edge * edge)
         n = a.shape[0]
-        da, db, do = self.alloc(max(a.nbytes, 16)), self.alloc(max(b.nbytes, 16)), self.alloc(max(4 * n, 16))
-        da.upload(a)
-        db.upload(b)
+        da, db, do = self._upload(a), self._upload(b), self.alloc(max(4 * n, 16))
         self.sad_dev(edge, da.ptr, db.ptr, do.ptr, n)
-        self.stream_sync()
-        return do.download(np.uint32, n)
+        return self._fetch((do, np.uint32, (n,)))
 
     def transform_tiles_dev(self, inverse, d_in, d_out, n_tiles, d_tile_offsets, d_tile_class, stream=0):
         self._check(self.L.xTransformTilesDev(self.ctx, int(inverse), d_in, d_out, n_tiles, d_tile_offsets or None, d_tile_class, stream),
@@ -686,11 +703,9 @@ class Codec:
     def dct32_pass(self, x, shift):
         """numpy convenience around xDct32PassDev: [n, 1024] int16 -> the 1-D pass of every block, stored transposed."""
         x = np.ascontiguousarray(x, np.int16).reshape(-1, 1024)
-        din, dout = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16))
-        din.upload(x)
+        din, dout = self._upload(x), self.alloc(max(x.nbytes, 16))
         self._check(self.L.xDct32PassDev(self.ctx, din.ptr, dout.ptr, x.shape[0], int(shift), None), "xDct32PassDev")
-        self.stream_sync()
-        return dout.download(np.int16, x.size).reshape(-1, 1024)
+        return self._fetch((dout, np.int16, x.shape))
 
     def set_transform_matrix(self, slot, size, m=None):
         """Install an N x N int8 matrix (row k = basis function) in 1-D transform slot 0 / 1; None restores the built-in."""
@@ -719,11 +734,9 @@ class Codec:
     def transform_inv(self, ttype, size, x):
         x = np.ascontiguousarray(x, np.int16)
         n = x.size // (size * size)
-        din, dout = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16))
-        din.upload(x)
+        din, dout = self._upload(x), self.alloc(max(x.nbytes, 16))
         self.transform_inv_dev(ttype, size, din.ptr, dout.ptr, n)
-        self.stream_sync()
-        return dout.download(np.int16, x.size).reshape(n, size * size)
+        return self._fetch((dout, np.int16, (n, size * size)))
 
     def satd_search_dev(self, d_cur, cur_stride, d_ref_origin, ref_stride, width, height, rng, d_best, d_costs=0,
                         stream=0):
@@ -740,21 +753,12 @@ class Codec:
         cur = np.ascontiguousarray(cur, np.uint8)
         refp = np.ascontiguousarray(ref_padded, np.uint8)
         h, w = cur.shape
-        nb = (h // 8) * (w // 8)
-        ncand = (2 * rng + 1) ** 2
-        dc, dr, db = self.alloc(cur.nbytes), self.alloc(refp.nbytes), self.alloc(nb * 8)
-        dcost = self.alloc(nb * ncand * 4) if want_costs else None
-        dc.upload(cur)
-        dr.upload(refp)
+        nb, ncand = (h // 8) * (w // 8), (2 * rng + 1) ** 2
+        dc, dr, db = self._upload(cur), self._upload(refp), self.alloc(nb * 8)
+        dcost = self.alloc(nb * ncand * 4) if want_costs else _NULL
         fn = self.satd_search_dev if metric == "satd" else self.sad_search_dev
-        fn(dc.ptr, cur.strides[0], dr.ptr + pad * refp.strides[0] + pad, refp.strides[0], w, h, rng,
-           db.ptr, dcost.ptr if want_costs else 0)
-        self.stream_sync()
-        raw = db.download(np.uint8, nb * 8)
-        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
-        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
-        costs = dcost.download(np.uint32, nb * ncand).reshape(nb, ncand) if want_costs else None
-        return mv, cost, costs
+        fn(dc.ptr, cur.strides[0], dr.ptr + pad * refp.strides[0] + pad, refp.strides[0], w, h, rng, db.ptr, dcost.ptr)
+        return self._fetch_best(db, nb, dcost, (nb, ncand))
 
     def satd_search_from_tiles_dev(self, d_cur, d_ref, width, height, rng, d_best, d_costs=0, stream=0):
         self._check(self.L.xSatd8x8SearchFromTilesDev(self.ctx, d_cur, d_ref, width, height, rng, d_best, d_costs or None, stream),
@@ -776,58 +780,28 @@ class Codec:
     def search_tiles(self, cur_tiles, ref_tiles, w, h, rng, want_costs=False, metric="satd"):
         """numpy convenience around xSatd8x8SearchFromTilesDev / xSad8x8SearchFromTilesDev: two tile arrays of a w x h frame
         (uint8, 512 bytes per tile) -> (mv [nb, 2] int16, cost [nb] uint32, costs [nb, (2R+1)^2] or None), as satd_search."""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
-        assert cur.size == w * h * 2 and ref.size == w * h * 2
-        nb = (h // 8) * (w // 8)
-        ncand = (2 * rng + 1) ** 2
-        dc, dr, db = self.alloc(cur.nbytes), self.alloc(ref.nbytes), self.alloc(nb * 8)
-        dcost = self.alloc(nb * ncand * 4) if want_costs else None
-        dc.upload(cur)
-        dr.upload(ref)
+        nb, ncand = (h // 8) * (w // 8), (2 * rng + 1) ** 2
+        dc, dr, db = self._frame(cur_tiles, w, h), self._frame(ref_tiles, w, h), self.alloc(nb * 8)
+        dcost = self.alloc(nb * ncand * 4) if want_costs else _NULL
         fn = self.satd_search_from_tiles_dev if metric == "satd" else self.sad_search_from_tiles_dev
-        fn(dc.ptr, dr.ptr, w, h, rng, db.ptr, dcost.ptr if want_costs else 0)
-        self.stream_sync()
-        raw = db.download(np.uint8, nb * 8)
-        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
-        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
-        costs = dcost.download(np.uint32, nb * ncand).reshape(nb, ncand) if want_costs else None
-        return mv, cost, costs
+        fn(dc.ptr, dr.ptr, w, h, rng, db.ptr, dcost.ptr)
+        return self._fetch_best(db, nb, dcost, (nb, ncand))
+
+    def _motion_comp(self, fn, ref_tiles, mv, w, h, base):
+        dr, dm = self._frame(ref_tiles, w, h), self._upload(self._records(mv, (h // 8) * (w // 8)))
+        dp = self._out_frame(base, np.zeros(w * h * 2, np.uint8))
+        fn(dr.ptr, dm.ptr, w, h, dp.ptr)
+        return self._fetch((dp, np.uint8, (w * h * 2,)))
 
     def motion_comp_luma(self, ref_tiles, mv, w, h, base=None):
         """numpy convenience around xMotionCompLumaDev: ref tile array, mv [nb, 2] int16 (mvx, mvy per 8x8 block, raster order)
         -> the predicted tile array; m_C / m_I come from `base` (a tile array; None: zeros), as the call leaves them."""
-        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
-        assert ref.size == w * h * 2
-        nb = (h // 8) * (w // 8)
-        rec = np.zeros((nb, 4), np.int16)
-        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
-        pred = np.zeros(ref.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
-        dr, dm, dp = self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(pred.nbytes)
-        dr.upload(ref)
-        dm.upload(rec)
-        dp.upload(pred)
-        self.motion_comp_luma_dev(dr.ptr, dm.ptr, w, h, dp.ptr)
-        self.stream_sync()
-        return dp.download(np.uint8, pred.size)
+        return self._motion_comp(self.motion_comp_luma_dev, ref_tiles, mv, w, h, base)
 
     def motion_comp(self, ref_tiles, mv, w, h, base=None, planes="both"):
         """numpy convenience around xMotionCompDev (planes="both") / xMotionCompChromaDev (planes="chroma"): as motion_comp_luma;
         what the call does not write (m_I, and m_Y for "chroma") comes from `base`."""
-        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
-        assert ref.size == w * h * 2
-        fn = {"both": self.motion_comp_dev, "chroma": self.motion_comp_chroma_dev}[planes]
-        nb = (h // 8) * (w // 8)
-        rec = np.zeros((nb, 4), np.int16)
-        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
-        pred = np.zeros(ref.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
-        dr, dm, dp = self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(pred.nbytes)
-        dr.upload(ref)
-        dm.upload(rec)
-        dp.upload(pred)
-        fn(dr.ptr, dm.ptr, w, h, dp.ptr)
-        self.stream_sync()
-        return dp.download(np.uint8, pred.size)
+        return self._motion_comp({"both": self.motion_comp_dev, "chroma": self.motion_comp_chroma_dev}[planes], ref_tiles, mv, w, h, base)
 
     def motion_comp_qpel_luma_dev(self, d_ref, d_mv, width, height, d_pred, stream=0):
         self._check(self.L.xMotionCompQpelLumaGpu(self.ctx, d_ref, d_mv, width, height, d_pred, stream), "xMotionCompQpelLumaGpu")
@@ -846,42 +820,17 @@ class Codec:
         """numpy convenience around xMotionCompQpelGpu (planes="both") / ...LumaGpu ("luma") / ...ChromaGpu ("chroma"): ref tile
         array, mv [nb, 2] int16 in quarter luma samples per 8x8 block -> the predicted tile array; what the call does not write
         comes from `base` (a tile array; None: zeros)."""
-        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
-        assert ref.size == w * h * 2
         fn = {"both": self.motion_comp_qpel_dev, "luma": self.motion_comp_qpel_luma_dev, "chroma": self.motion_comp_qpel_chroma_dev}[planes]
-        nb = (h // 8) * (w // 8)
-        rec = np.zeros((nb, 4), np.int16)
-        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
-        pred = np.zeros(ref.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
-        dr, dm, dp = self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(pred.nbytes)
-        dr.upload(ref)
-        dm.upload(rec)
-        dp.upload(pred)
-        fn(dr.ptr, dm.ptr, w, h, dp.ptr)
-        self.stream_sync()
-        return dp.download(np.uint8, pred.size)
+        return self._motion_comp(fn, ref_tiles, mv, w, h, base)
 
     def refine_qpel_tiles(self, cur_tiles, ref_tiles, w, h, mv_int, want_costs=False):
         """numpy convenience around xSatd8x8RefineQpelFromTilesGpu: two tile arrays and integer vectors [nb, 2] int16 ->
         (mv [nb, 2] int16 in quarter samples, cost [nb] uint32, costs [nb, 49] or None)."""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
-        assert cur.size == w * h * 2 and ref.size == w * h * 2
         nb = (h // 8) * (w // 8)
-        rec = np.zeros((nb, 4), np.int16)
-        rec[:, :2] = np.asarray(mv_int, np.int16).reshape(nb, 2)
-        dc, dr, di, db = self.alloc(cur.nbytes), self.alloc(ref.nbytes), self.alloc(rec.nbytes), self.alloc(nb * 8)
-        dcost = self.alloc(nb * 49 * 4) if want_costs else None
-        dc.upload(cur)
-        dr.upload(ref)
-        di.upload(rec)
-        self.satd_refine_qpel_from_tiles_dev(dc.ptr, dr.ptr, w, h, di.ptr, db.ptr, dcost.ptr if want_costs else 0)
-        self.stream_sync()
-        raw = db.download(np.uint8, nb * 8)
-        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
-        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
-        costs = dcost.download(np.uint32, nb * 49).reshape(nb, 49) if want_costs else None
-        return mv, cost, costs
+        dc, dr, di, db = self._frame(cur_tiles, w, h), self._frame(ref_tiles, w, h), self._upload(self._records(mv_int, nb)), self.alloc(nb * 8)
+        dcost = self.alloc(nb * 49 * 4) if want_costs else _NULL
+        self.satd_refine_qpel_from_tiles_dev(dc.ptr, dr.ptr, w, h, di.ptr, db.ptr, dcost.ptr)
+        return self._fetch_best(db, nb, dcost, (nb, 49))
 
     @staticmethod
     def wp_params(w=((1, 1, 1), (1, 1, 1)), o=((0, 0, 0), (0, 0, 0)), log2_denom=(0, 0)):
@@ -906,57 +855,36 @@ class Codec:
                                                          ctypes.byref(wp) if wp is not None else None, width, height, d_best, d_costs or None, stream),
                     "xSatd8x8RefineBiQpelFromTiles")
 
-    def _upload(self, a):
-        a = np.ascontiguousarray(a)
-        d = self.alloc(max(a.nbytes, 16))
-        d.upload(a)
-        return d
-
-    @staticmethod
-    def _records(mv, nb):
-        rec = np.zeros((nb, 4), np.int16)
-        rec[:, :2] = np.asarray(mv, np.int16).reshape(nb, 2)
-        return rec
-
     def motion_comp_bi_qpel(self, ref0_tiles, ref1_tiles, mv0, mv1, w, h, direction=None, wp=None, planes=3, base=None):
         """numpy convenience around xMotionCompBiQpelTiles: two reference tile arrays (ref1_tiles None: the same buffer as list 0), mv0 /
         mv1 [nb, 2] int16 in quarter luma samples, direction uint8 [nb] or None (every block 3), wp from wp_params() or None ->
         the predicted tile array; what the call does not write comes from `base` (a tile array; None: zeros)."""
-        ref0 = np.ascontiguousarray(ref0_tiles, np.uint8).ravel()
-        assert ref0.size == w * h * 2
         nb = (h // 8) * (w // 8)
-        pred = np.zeros(ref0.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel()
-        d0 = self._upload(ref0)
-        d1 = d0 if ref1_tiles is None else self._upload(np.ascontiguousarray(ref1_tiles, np.uint8).ravel())
-        dm0, dm1, dp = self._upload(self._records(mv0, nb)), self._upload(self._records(mv1, nb)), self._upload(pred)
-        dd = None if direction is None else self._upload(np.asarray(direction, np.uint8).reshape(nb))
-        self.motion_comp_bi_qpel_dev(d0.ptr, d1.ptr, dm0.ptr, dm1.ptr, w, h, dp.ptr, 0 if dd is None else dd.ptr, wp, planes)
-        self.stream_sync()
-        return dp.download(np.uint8, pred.size)
+        d0 = self._frame(ref0_tiles, w, h)
+        d1 = d0 if ref1_tiles is None else self._frame(ref1_tiles, w, h)
+        dm0, dm1, dd = self._upload(self._records(mv0, nb)), self._upload(self._records(mv1, nb)), self._table(direction, np.uint8, nb)
+        dp = self._out_frame(base, np.zeros(w * h * 2, np.uint8))
+        self.motion_comp_bi_qpel_dev(d0.ptr, d1.ptr, dm0.ptr, dm1.ptr, w, h, dp.ptr, dd.ptr, wp, planes)
+        return self._fetch((dp, np.uint8, (w * h * 2,)))
 
     def satd8x8_bi_costs(self, cur_tiles, ref0_tiles, ref1_tiles, w, h, mv0, mv1, wp=None, bi_penalty=0):
         """numpy convenience around xSatd8x8BiCostsFromTiles -> (costs [nb, 3] uint32, direction [nb] uint8)"""
         nb = (h // 8) * (w // 8)
-        dc, d0, d1 = (self._upload(np.ascontiguousarray(t, np.uint8).ravel()) for t in (cur_tiles, ref0_tiles, ref1_tiles))
+        dc, d0, d1 = (self._frame(t, w, h) for t in (cur_tiles, ref0_tiles, ref1_tiles))
         dm0, dm1 = self._upload(self._records(mv0, nb)), self._upload(self._records(mv1, nb))
         dk, dd = self.alloc(nb * 12), self.alloc(max(nb, 16))
         self.satd8x8_bi_costs_dev(dc.ptr, d0.ptr, d1.ptr, w, h, dm0.ptr, dm1.ptr, dk.ptr, dd.ptr, wp, bi_penalty)
-        self.stream_sync()
-        return dk.download(np.uint32, nb * 3).reshape(nb, 3), dd.download(np.uint8, nb)
+        return self._fetch((dk, np.uint32, (nb, 3)), (dd, np.uint8, (nb,)))
 
     def satd8x8_refine_bi_qpel(self, cur_tiles, ref_fix_tiles, mv_fix, ref_tiles, mv_int, lst, w, h, wp=None, want_costs=False):
         """numpy convenience around xSatd8x8RefineBiQpelFromTiles: mv_fix [nb, 2] int16 in quarter samples, mv_int [nb, 2] integer vectors
         of the list `lst` being refined -> (mv [nb, 2] int16 in quarter samples, cost [nb] uint32, costs [nb, 49] or None)."""
         nb = (h // 8) * (w // 8)
-        dc, df, dr = (self._upload(np.ascontiguousarray(t, np.uint8).ravel()) for t in (cur_tiles, ref_fix_tiles, ref_tiles))
+        dc, df, dr = (self._frame(t, w, h) for t in (cur_tiles, ref_fix_tiles, ref_tiles))
         dmf, di, db = self._upload(self._records(mv_fix, nb)), self._upload(self._records(mv_int, nb)), self.alloc(nb * 8)
-        dcost = self.alloc(nb * 49 * 4) if want_costs else None
-        self.satd8x8_refine_bi_qpel_dev(dc.ptr, df.ptr, dmf.ptr, dr.ptr, di.ptr, lst, w, h, db.ptr, dcost.ptr if want_costs else 0, wp)
-        self.stream_sync()
-        raw = db.download(np.uint8, nb * 8)
-        mv = raw.view(np.int16).reshape(nb, 4)[:, :2].copy()
-        cost = raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
-        return mv, cost, dcost.download(np.uint32, nb * 49).reshape(nb, 49) if want_costs else None
+        dcost = self.alloc(nb * 49 * 4) if want_costs else _NULL
+        self.satd8x8_refine_bi_qpel_dev(dc.ptr, df.ptr, dmf.ptr, dr.ptr, di.ptr, lst, w, h, db.ptr, dcost.ptr, wp)
+        return self._fetch_best(db, nb, dcost, (nb, 49))
 
     @staticmethod
     def deblock_params(d_class=0, d_intra=0, d_nnz=0, d_qp=0, d_mv=0, qp=0, beta_offset_div2=0, tc_offset_div2=0):
@@ -978,34 +906,14 @@ class Codec:
         array and the side arrays of x266_deblock_t (cls, intra, qps: uint8 [6 n_ctu]; nnz: uint32 [6 n_ctu]; mv: int16 [nb, 2] in
         quarter samples; None: NULL) -> the deblocked tile array.  in_place: d_out == d_in; otherwise what the call does not write
         comes from `base` (a tile array; None: zeros)."""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
-        assert src.size == w * h * 2
         fn = {"both": self.deblock_dev, "luma": self.deblock_luma_dev, "chroma": self.deblock_chroma_dev}[planes]
-        keep = []
-
-        def up(a, dtype):
-            if a is None:
-                return 0
-            a = np.ascontiguousarray(a, dtype)
-            keep.append(self.alloc(max(a.nbytes, 16)))
-            keep[-1].upload(a)
-            return keep[-1].ptr
-
-        rec = None
-        if mv is not None:
-            rec = np.zeros(((h // 8) * (w // 8), 4), np.int16)
-            rec[:, :2] = np.asarray(mv, np.int16).reshape(-1, 2)
-        params = self.deblock_params(up(cls, np.uint8), up(intra, np.uint8), up(nnz, np.uint32), up(qps, np.uint8), up(rec, np.int16),
-                                     qp, beta_offset_div2, tc_offset_div2)
-        d_in = self.alloc(src.nbytes)
-        d_in.upload(src)
-        d_out = d_in
-        if not in_place:
-            d_out = self.alloc(src.nbytes)
-            d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        rec = None if mv is None else self._records(mv, (h // 8) * (w // 8))
+        side = [self._table(t, dtype) for t, dtype in ((cls, np.uint8), (intra, np.uint8), (nnz, np.uint32), (qps, np.uint8), (rec, np.int16))]
+        params = self.deblock_params(*[d.ptr for d in side], qp, beta_offset_div2, tc_offset_div2)
+        d_in = self._frame(tiles, w, h)
+        d_out = d_in if in_place else self._out_frame(base, np.zeros(w * h * 2, np.uint8))
         fn(d_in.ptr, w, h, params, d_out.ptr)
-        self.stream_sync()
-        return d_out.download(np.uint8, src.size)
+        return self._fetch((d_out, np.uint8, (w * h * 2,)))
 
     def sao_stats_dev(self, d_org, d_dec, width, height, d_stats, stream=0):
         self._check(self.L.xSaoStatsGpu(self.ctx, d_org, d_dec, width, height, d_stats, stream), "xSaoStatsGpu")
@@ -1019,58 +927,36 @@ class Codec:
     def sao_apply_dev(self, d_in, width, height, d_param, d_out, stream=0):
         self._check(self.L.xSaoApplyGpu(self.ctx, d_in, width, height, d_param, d_out, stream), "xSaoApplyGpu")
 
-    def _sao_frames(self, org_tiles, dec_tiles, w, h):
-        org = np.ascontiguousarray(org_tiles, np.uint8).ravel()
-        dec = np.ascontiguousarray(dec_tiles, np.uint8).ravel()
-        assert org.size == w * h * 2 and dec.size == w * h * 2
-        d_org, d_dec = self.alloc(org.nbytes), self.alloc(dec.nbytes)
-        d_org.upload(org)
-        d_dec.upload(dec)
-        return d_org, d_dec
-
     def sao_stats(self, org_tiles, dec_tiles, w, h):
         """numpy convenience around xSaoStatsGpu: the source and the decoded tile array -> int32 [n_ctu, 3, 48, 2] (count, sum)"""
         n = self.ctu_count(w, h)
-        d_org, d_dec = self._sao_frames(org_tiles, dec_tiles, w, h)
-        d_stats = self.alloc(n * 1152)
+        d_org, d_dec, d_stats = self._frame(org_tiles, w, h), self._frame(dec_tiles, w, h), self.alloc(n * 1152)
         self.sao_stats_dev(d_org.ptr, d_dec.ptr, w, h, d_stats.ptr)
-        self.stream_sync()
-        return d_stats.download(np.int32, n * 288).reshape(n, 3, 48, 2)
+        return self._fetch((d_stats, np.int32, (n, 3, 48, 2)))
 
     def sao_decide(self, stats, lambda_q4):
         """numpy convenience around xSaoDecideGpu: int32 [n_ctu, 3, 48, 2] -> the x266_sao_t records as uint8 [n_ctu, 3, 8]"""
         st = np.ascontiguousarray(stats, np.int32).reshape(-1, 3, 48, 2)
         n = st.shape[0]
-        d_stats, d_param = self.alloc(max(st.nbytes, 16)), self.alloc(max(n * 24, 16))
-        d_stats.upload(st)
+        d_stats, d_param = self._upload(st), self.alloc(max(n * 24, 16))
         self.sao_decide_dev(d_stats.ptr, n, lambda_q4, d_param.ptr)
-        self.stream_sync()
-        return d_param.download(np.uint8, n * 24).reshape(n, 3, 8)
+        return self._fetch((d_param, np.uint8, (n, 3, 8)))
 
     def sao_search(self, org_tiles, dec_tiles, w, h, lambda_q4, want_stats=False):
         """numpy convenience around xSaoSearchGpu: two tile arrays -> (records uint8 [n_ctu, 3, 8], statistics or None)"""
         n = self.ctu_count(w, h)
-        d_org, d_dec = self._sao_frames(org_tiles, dec_tiles, w, h)
-        d_param = self.alloc(n * 24)
-        d_stats = self.alloc(n * 1152) if want_stats else None
-        self.sao_search_dev(d_org.ptr, d_dec.ptr, w, h, lambda_q4, d_param.ptr, d_stats.ptr if want_stats else 0)
-        self.stream_sync()
-        return (d_param.download(np.uint8, n * 24).reshape(n, 3, 8),
-                d_stats.download(np.int32, n * 288).reshape(n, 3, 48, 2) if want_stats else None)
+        d_org, d_dec, d_param = self._frame(org_tiles, w, h), self._frame(dec_tiles, w, h), self.alloc(n * 24)
+        d_stats = self.alloc(n * 1152) if want_stats else _NULL
+        self.sao_search_dev(d_org.ptr, d_dec.ptr, w, h, lambda_q4, d_param.ptr, d_stats.ptr)
+        return self._fetch((d_param, np.uint8, (n, 3, 8)), (d_stats, np.int32, (n, 3, 48, 2)))
 
     def sao_apply(self, tiles, w, h, params, base=None):
         """numpy convenience around xSaoApplyGpu: a tile array and the records (uint8 [n_ctu, 3, 8]) -> the filtered tile array; m_I,
         which the call does not write, comes from `base` (a tile array; None: zeros)"""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
-        rec = np.ascontiguousarray(params, np.uint8).ravel()
-        assert src.size == w * h * 2 and rec.size == self.ctu_count(w, h) * 24
-        d_in, d_par, d_out = self.alloc(src.nbytes), self.alloc(rec.nbytes), self.alloc(src.nbytes)
-        d_in.upload(src)
-        d_par.upload(rec)
-        d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        d_in, d_par = self._frame(tiles, w, h), self._table(params, np.uint8, self.ctu_count(w, h) * 24)
+        d_out = self._out_frame(base, np.zeros(w * h * 2, np.uint8))
         self.sao_apply_dev(d_in.ptr, w, h, d_par.ptr, d_out.ptr)
-        self.stream_sync()
-        return d_out.download(np.uint8, src.size)
+        return self._fetch((d_out, np.uint8, (w * h * 2,)))
 
     # ---- adaptive loop filter: 2358 int32 of statistics per CTU, one class byte per 4x4 luma block, 3 control bytes per CTU
     ALF_CTU_WORDS = 2358
@@ -1113,69 +999,49 @@ class Codec:
     def _alf_sets(self, luma, chroma):
         luma = np.zeros((0, 600), np.uint8) if luma is None else np.ascontiguousarray(luma, np.uint8).reshape(-1, 600)
         chroma = np.zeros((0, 16), np.uint8) if chroma is None else np.ascontiguousarray(chroma, np.uint8).reshape(-1, 16)
-        d_luma, d_chroma = self.alloc(max(luma.nbytes, 16)), self.alloc(max(chroma.nbytes, 16))
-        d_luma.upload(luma if luma.size else np.zeros(16, np.uint8))
-        d_chroma.upload(chroma if chroma.size else np.zeros(16, np.uint8))
+        d_luma, d_chroma = (self._upload(s if s.size else np.zeros(16, np.uint8)) for s in (luma, chroma))
         return d_luma, luma.shape[0], d_chroma, chroma.shape[0]
 
     def alf_classify(self, tiles, w, h):
         """numpy convenience around xAlfClassifyGpu: a tile array -> the class bytes uint8 [h / 4, w / 4] (class | tr << 5)"""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
-        assert src.size == w * h * 2
-        d_in, d_cls = self.alloc(src.nbytes), self.alloc(max((w // 4) * (h // 4), 16))
-        d_in.upload(src)
+        d_in, d_cls = self._frame(tiles, w, h), self.alloc(max((w // 4) * (h // 4), 16))
         self.alf_classify_dev(d_in.ptr, w, h, d_cls.ptr)
-        self.stream_sync()
-        return d_cls.download(np.uint8, (w // 4) * (h // 4)).reshape(h // 4, w // 4)
+        return self._fetch((d_cls, np.uint8, (h // 4, w // 4)))
 
     def alf_stats(self, org_tiles, dec_tiles, w, h, classes=None):
         """numpy convenience around xAlfStatsGpu: the source and the decoded tile array (and a class map, None: classified inside)
         -> int32 [n_ctu, 2358]"""
         n = self.ctu_count(w, h)
-        d_org, d_dec = self._sao_frames(org_tiles, dec_tiles, w, h)
-        d_cls = None if classes is None else self._upload(np.ascontiguousarray(classes, np.uint8).ravel())
+        d_org, d_dec, d_cls = self._frame(org_tiles, w, h), self._frame(dec_tiles, w, h), self._table(classes, np.uint8)
         d_stats = self.alloc(n * self.ALF_CTU_WORDS * 4)
-        self.alf_stats_dev(d_org.ptr, d_dec.ptr, w, h, 0 if d_cls is None else d_cls.ptr, d_stats.ptr)
-        self.stream_sync()
-        return d_stats.download(np.int32, n * self.ALF_CTU_WORDS).reshape(n, self.ALF_CTU_WORDS)
+        self.alf_stats_dev(d_org.ptr, d_dec.ptr, w, h, d_cls.ptr, d_stats.ptr)
+        return self._fetch((d_stats, np.int32, (n, self.ALF_CTU_WORDS)))
 
     def alf_sum_stats(self, stats, mask=None):
         """numpy convenience around xAlfSumStatsGpu: int32 [n_ctu, 2358] (and a byte per CTU, None: all) -> int64 [2358]"""
         st = np.ascontiguousarray(stats, np.int32).reshape(-1, self.ALF_CTU_WORDS)
         n = st.shape[0]
-        d_stats, d_total = self.alloc(max(st.nbytes, 16)), self.alloc(self.ALF_CTU_WORDS * 8)
-        d_stats.upload(st)
-        d_total.upload(np.zeros(self.ALF_CTU_WORDS, np.int64))
-        d_mask = None if mask is None else self._upload(np.ascontiguousarray(mask, np.uint8).reshape(n))
-        self.alf_sum_stats_dev(d_stats.ptr, n, 0 if d_mask is None else d_mask.ptr, d_total.ptr)
-        self.stream_sync()
-        return d_total.download(np.int64, self.ALF_CTU_WORDS)
+        d_stats, d_total, d_mask = self._upload(st), self._upload(np.zeros(self.ALF_CTU_WORDS, np.int64)), self._table(mask, np.uint8, n)
+        self.alf_sum_stats_dev(d_stats.ptr, n, d_mask.ptr, d_total.ptr)
+        return self._fetch((d_total, np.int64, (self.ALF_CTU_WORDS,)))
 
     def alf_decide(self, stats, luma, chroma, lambda_q4):
         """numpy convenience around xAlfDecideGpu: int32 [n_ctu, 2358] and the packed sets of alf_pack_filters -> d_ctrl uint8 [n_ctu, 3]"""
         st = np.ascontiguousarray(stats, np.int32).reshape(-1, self.ALF_CTU_WORDS)
         n = st.shape[0]
-        d_stats, d_ctrl = self.alloc(max(st.nbytes, 16)), self.alloc(max(3 * n, 16))
-        d_stats.upload(st)
+        d_stats, d_ctrl = self._upload(st), self.alloc(max(3 * n, 16))
         d_luma, n_luma, d_chroma, n_chroma = self._alf_sets(luma, chroma)
         self.alf_decide_dev(d_stats.ptr, n, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, lambda_q4, d_ctrl.ptr)
-        self.stream_sync()
-        return d_ctrl.download(np.uint8, 3 * n).reshape(n, 3)
+        return self._fetch((d_ctrl, np.uint8, (n, 3)))
 
     def alf_apply(self, tiles, w, h, luma, chroma, ctrl, classes=None, base=None):
         """numpy convenience around xAlfApplyGpu: a tile array, the packed sets, d_ctrl (uint8 [n_ctu, 3]) and a class map (None:
         classified inside) -> the filtered tile array; m_I, which the call does not write, comes from `base` (None: zeros)"""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
-        ctl = np.ascontiguousarray(ctrl, np.uint8).ravel()
-        assert src.size == w * h * 2 and ctl.size == self.ctu_count(w, h) * 3
-        d_in, d_out, d_ctl = self.alloc(src.nbytes), self.alloc(src.nbytes), self._upload(ctl)
-        d_in.upload(src)
-        d_out.upload(np.zeros(src.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
-        d_cls = None if classes is None else self._upload(np.ascontiguousarray(classes, np.uint8).ravel())
+        d_in, d_out = self._frame(tiles, w, h), self._out_frame(base, np.zeros(w * h * 2, np.uint8))
+        d_ctl, d_cls = self._table(ctrl, np.uint8, self.ctu_count(w, h) * 3), self._table(classes, np.uint8)
         d_luma, n_luma, d_chroma, n_chroma = self._alf_sets(luma, chroma)
-        self.alf_apply_dev(d_in.ptr, w, h, 0 if d_cls is None else d_cls.ptr, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, d_ctl.ptr, d_out.ptr)
-        self.stream_sync()
-        return d_out.download(np.uint8, src.size)
+        self.alf_apply_dev(d_in.ptr, w, h, d_cls.ptr, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, d_ctl.ptr, d_out.ptr)
+        return self._fetch((d_out, np.uint8, (w * h * 2,)))
 
     def transform_ctu_from_tiles_dev(self, d_cur, d_pred, w, h, d_class, d_coef, stream=0):
         self._check(self.L.xTransformCtuFromTilesDev(self.ctx, d_cur, d_pred, w, h, d_class, d_coef, stream), "xTransformCtuFromTilesDev")
@@ -1191,36 +1057,19 @@ class Codec:
     def transform_ctu_from_tiles(self, cur_tiles, pred_tiles, w, h, classes):
         """numpy convenience around xTransformCtuFromTilesDev: two tile arrays of a w x h frame (uint8, 512 bytes per tile) and
         6 class bytes per CTU -> coefficients [n_ctus, 6, 1024] int16 (Y0 Y1 Y2 Y3 U V, each block-major for its class)."""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
-        cls = np.ascontiguousarray(classes, np.uint8).ravel()
         n = self.ctu_count(w, h)
-        assert cur.size == w * h * 2 and pred.size == w * h * 2 and cls.size == 6 * n
-        dc, dp, dk, dz = self.alloc(cur.nbytes), self.alloc(pred.nbytes), self.alloc(max(cls.nbytes, 16)), self.alloc(n * 12288)
-        dc.upload(cur)
-        dp.upload(pred)
-        dk.upload(cls)
+        dc, dp, dk, dz = self._frame(cur_tiles, w, h), self._frame(pred_tiles, w, h), self._table(classes, np.uint8, 6 * n), self.alloc(n * 12288)
         self.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr, dz.ptr)
-        self.stream_sync()
-        return dz.download(np.int16, n * 6144).reshape(n, 6, 1024)
+        return self._fetch((dz, np.int16, (n, 6, 1024)))
 
     def transform_ctu_to_tiles(self, coef, classes, pred_tiles, w, h, base=None):
         """numpy convenience around xTransformCtuToTilesDev: coefficients [n_ctus, 6, 1024] int16, their class bytes and the pred
         tile array -> the reconstructed tile array; m_I (never written) comes from `base` (a tile array; None: pred's)."""
         n = self.ctu_count(w, h)
-        z = np.ascontiguousarray(coef, np.int16).ravel()
-        cls = np.ascontiguousarray(classes, np.uint8).ravel()
-        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
-        assert z.size == n * 6144 and cls.size == 6 * n and pred.size == w * h * 2
-        out = pred if base is None else np.ascontiguousarray(base, np.uint8).ravel()
-        dz, dk, dp, dr = self.alloc(z.nbytes), self.alloc(max(cls.nbytes, 16)), self.alloc(pred.nbytes), self.alloc(out.nbytes)
-        dz.upload(z)
-        dk.upload(cls)
-        dp.upload(pred)
-        dr.upload(out)
+        dz, dk = self._table(coef, np.int16, n * 6144), self._table(classes, np.uint8, 6 * n)
+        dp, dr = self._frame(pred_tiles, w, h), self._out_frame(base, pred_tiles)
         self.transform_ctu_to_tiles_dev(dz.ptr, dk.ptr, dp.ptr, w, h, dr.ptr)
-        self.stream_sync()
-        return dr.download(np.uint8, out.size)
+        return self._fetch((dr, np.uint8, (w * h * 2,)))
 
     def quant_regions_dev(self, inverse, d_in, d_out, n_regions, d_class=0, d_qp=0, qp=0, rounding=0, d_nnz=0, stream=0):
         self._check(self.L.xQuantRegionsGpu(self.ctx, int(inverse), d_in, d_out, n_regions, d_class or None, d_qp or None, int(qp), int(rounding),
@@ -1235,47 +1084,21 @@ class Codec:
         and their non-zero counts per region (inverse=False), or the coefficients (inverse=True)."""
         x = np.ascontiguousarray(x, np.int16).reshape(-1, 1024)
         n = x.shape[0]
-        din, dout = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16))
-        din.upload(x)
-        tabs = []
-        for t in (classes, qps):
-            if t is None:
-                tabs.append(None)
-                continue
-            t = np.ascontiguousarray(t, np.uint8).ravel()
-            assert t.size == n
-            tabs.append(self.alloc(max(n, 16)))
-            tabs[-1].upload(t)
-        dn = None if inverse else self.alloc(max(4 * n, 16))
-        self.quant_regions_dev(inverse, din.ptr, dout.ptr, n, tabs[0].ptr if tabs[0] else 0, tabs[1].ptr if tabs[1] else 0, qp, rounding,
-                               dn.ptr if dn else 0)
-        self.stream_sync()
-        out = dout.download(np.int16, n * 1024).reshape(n, 1024)
-        return out if inverse else (out, dn.download(np.uint32, n))
+        din, dout, dk, dq = self._upload(x), self.alloc(max(x.nbytes, 16)), self._table(classes, np.uint8, n), self._table(qps, np.uint8, n)
+        dn = _NULL if inverse else self.alloc(max(4 * n, 16))
+        self.quant_regions_dev(inverse, din.ptr, dout.ptr, n, dk.ptr, dq.ptr, qp, rounding, dn.ptr)
+        out, nnz = self._fetch((dout, np.int16, (n, 1024)), (dn, np.uint32, (n,)))
+        return out if inverse else (out, nnz)
 
     def code_ctu_tiles(self, cur_tiles, pred_tiles, w, h, qps=None, qp=0, rounding=0, base=None):
         """numpy convenience around xDct32CodeCtuTilesGpu: two tile arrays of a w x h frame (multiples of 64) and optionally 6 qp bytes per
         CTU -> (levels [n_ctus, 6, 1024] int16, non-zero counts [n_ctus, 6] uint32, the reconstructed tile array); m_I (never
         written) comes from `base` (a tile array; None: pred's)."""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
         n = self.ctu_count(w, h)
-        assert cur.size == w * h * 2 and pred.size == w * h * 2
-        out = pred if base is None else np.ascontiguousarray(base, np.uint8).ravel()
-        dc, dp, dr = self.alloc(cur.nbytes), self.alloc(pred.nbytes), self.alloc(out.nbytes)
-        dl, dn = self.alloc(n * 12288), self.alloc(max(n * 24, 16))
-        dc.upload(cur)
-        dp.upload(pred)
-        dr.upload(out)
-        dq = None
-        if qps is not None:
-            q = np.ascontiguousarray(qps, np.uint8).ravel()
-            assert q.size == 6 * n
-            dq = self.alloc(max(q.nbytes, 16))
-            dq.upload(q)
-        self.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, dq.ptr if dq else 0, qp, rounding, dl.ptr, dn.ptr, dr.ptr)
-        self.stream_sync()
-        return dl.download(np.int16, n * 6144).reshape(n, 6, 1024), dn.download(np.uint32, n * 6).reshape(n, 6), dr.download(np.uint8, out.size)
+        dc, dp, dr = self._frame(cur_tiles, w, h), self._frame(pred_tiles, w, h), self._out_frame(base, pred_tiles)
+        dq, dl, dn = self._table(qps, np.uint8, 6 * n), self.alloc(n * 12288), self.alloc(max(n * 24, 16))
+        self.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, dq.ptr, qp, rounding, dl.ptr, dn.ptr, dr.ptr)
+        return self._fetch((dl, np.int16, (n, 6, 1024)), (dn, np.uint32, (n, 6)), (dr, np.uint8, (w * h * 2,)))
 
     # -- the compact level stream -------------------------------------------------------------------
     @staticmethod
@@ -1292,63 +1115,34 @@ class Codec:
 
     level_scan = staticmethod(level_scan)
 
-    def _levels_tabs(self, n, classes, nnz):
-        d_cls = d_nnz = None
-        if classes is not None:
-            c = np.ascontiguousarray(classes, np.uint8).ravel()
-            assert c.size == n
-            d_cls = self.alloc(max(n, 16))
-            d_cls.upload(c)
-        if nnz is not None:
-            z = np.ascontiguousarray(nnz, np.uint32).ravel()
-            assert z.size == n
-            d_nnz = self.alloc(max(4 * n, 16))
-            d_nnz.upload(z)
-        return d_cls, d_nnz
-
     def levels_pack(self, levels, classes=None, nnz=None, cap_words=None):
         """numpy convenience around xLevelsPackGpu: [n_regions, 1024] int16 (and a class byte and a non-zero count per region, None:
         NULL) -> (records [n_regions] of LEVEL_REGION_DTYPE, stream uint16 [cap_words], total uint64 [2]).  cap_words None: a count-only
         call sizes the stream exactly; words the call does not write are 0."""
         x = np.ascontiguousarray(levels, np.int16).reshape(-1, 1024)
         n = x.shape[0]
-        d_lv, d_rec, d_tot = self.alloc(max(x.nbytes, 16)), self.alloc(max(32 * n, 32)), self.alloc(16)
-        d_lv.upload(x)
-        d_cls, d_nnz = self._levels_tabs(n, classes, nnz)
-        p = self.levels_params(d_lv.ptr, d_cls.ptr if d_cls else 0, d_nnz.ptr if d_nnz else 0, d_rec.ptr, 0, d_tot.ptr, n, 0)
+        d_lv, d_rec, d_tot = self._upload(x), self.alloc(max(32 * n, 32)), self.alloc(16)
+        d_cls, d_nnz = self._table(classes, np.uint8, n), self._table(nnz, np.uint32, n)
+        p = self.levels_params(d_lv.ptr, d_cls.ptr, d_nnz.ptr, d_rec.ptr, 0, d_tot.ptr, n, 0)
         if cap_words is None:
             self.levels_pack_dev(p)
-            self.stream_sync()
-            cap_words = int(d_tot.download(np.uint64, 2)[0])
+            cap_words = self._fetch((d_tot, np.uint64, (2,)))[0]
         cap_words = int(cap_words)
-        d_str = None
-        if cap_words:
-            d_str = self.alloc(2 * cap_words)
-            d_str.upload(np.zeros(cap_words, np.uint16))
-            p.d_stream, p.cap_words = d_str.ptr, cap_words
+        d_str = self._upload(np.zeros(cap_words, np.uint16)) if cap_words else _NULL
+        p.d_stream, p.cap_words = d_str.ptr or None, cap_words
         self.levels_pack_dev(p)
-        self.stream_sync()
-        rec = d_rec.download(np.uint8, 32 * n).view(LEVEL_REGION_DTYPE) if n else np.zeros(0, LEVEL_REGION_DTYPE)
-        return rec, d_str.download(np.uint16, cap_words) if d_str else np.zeros(0, np.uint16), d_tot.download(np.uint64, 2)
+        return self._fetch((d_rec, LEVEL_REGION_DTYPE, (n,)), (d_str, np.uint16, (cap_words,)), (d_tot, np.uint64, (2,)))
 
     def levels_unpack(self, records, stream, n_regions, classes=None):
         """numpy convenience around xLevelsUnpackGpu: records (LEVEL_REGION_DTYPE), the stream's words and a class byte per region
         (None: NULL) -> (levels int16 [n_regions, 1024], non-zero counts uint32 [n_regions])"""
         n = int(n_regions)
-        rec = np.ascontiguousarray(records, LEVEL_REGION_DTYPE).ravel()
         words = np.ascontiguousarray(stream, np.uint16).ravel()
-        assert rec.size == n
-        d_lv, d_rec, d_nnz = self.alloc(max(2048 * n, 16)), self.alloc(max(32 * n, 32)), self.alloc(max(4 * n, 16))
-        d_rec.upload(rec.view(np.uint8))
-        d_str = None
-        if words.size:
-            d_str = self.alloc(words.nbytes)
-            d_str.upload(words)
-        d_cls, _ = self._levels_tabs(n, classes, None)
-        p = self.levels_params(d_lv.ptr, d_cls.ptr if d_cls else 0, d_nnz.ptr, d_rec.ptr, d_str.ptr if d_str else 0, 0, n, words.size)
-        self.levels_unpack_dev(p)
-        self.stream_sync()
-        return d_lv.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n)
+        d_rec, d_cls = self._table(records, LEVEL_REGION_DTYPE, n),self._table(classes, np.uint8, n)
+        d_str = self._upload(words) if words.size else _NULL
+        d_lv, d_nnz = self.alloc(max(2048 * n, 16)), self.alloc(max(4 * n, 16))
+        self.levels_unpack_dev(self.levels_params(d_lv.ptr, d_cls.ptr, d_nnz.ptr, d_rec.ptr, d_str.ptr, 0, n, words.size))
+        return self._fetch((d_lv, np.int16, (n, 1024)), (d_nnz, np.uint32, (n,)))
 
     # -- RDOQ and the level rate estimate -----------------------------------------------------------------
     @staticmethod
@@ -1366,39 +1160,24 @@ class Codec:
     last_pos_bits = staticmethod(last_pos_bits)
     cg_flag_bits = staticmethod(cg_flag_bits)
 
-    def _byte_tab(self, n, t):
-        if t is None:
-            return None
-        t = np.ascontiguousarray(t, np.uint8).ravel()
-        assert t.size == n
-        d = self.alloc(max(n, 16))
-        d.upload(t)
-        return d
-
     def rdo_quant(self, coef, classes=None, qps=None, qp=0, lam=368):
         """numpy convenience around xRdoQuantRegionsGpu: [n_regions, 1024] int16, optional class and qp bytes per region -> (levels int16
         [n_regions, 1024], non-zero counts uint32 [n_regions], records [n_regions] of RDOQ_REGION_DTYPE)"""
         x = np.ascontiguousarray(coef, np.int16).reshape(-1, 1024)
         n = x.shape[0]
-        d_in, d_out, d_nnz, d_stat = self.alloc(max(x.nbytes, 16)), self.alloc(max(x.nbytes, 16)), self.alloc(max(4 * n, 16)), self.alloc(max(16 * n, 16))
-        d_in.upload(x)
-        d_cls, d_qp = self._byte_tab(n, classes), self._byte_tab(n, qps)
-        self.rdo_quant_dev(self.rdoq_params(d_in.ptr, d_out.ptr, d_cls.ptr if d_cls else 0, d_qp.ptr if d_qp else 0, d_nnz.ptr, d_stat.ptr, n, qp, lam))
-        self.stream_sync()
-        return (d_out.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n),
-                d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE) if n else np.zeros(0, RDOQ_REGION_DTYPE))
+        d_in, d_cls, d_qp = self._upload(x), self._table(classes, np.uint8, n), self._table(qps, np.uint8, n)
+        d_out, d_nnz, d_stat = self.alloc(max(x.nbytes, 16)), self.alloc(max(4 * n, 16)), self.alloc(max(16 * n, 16))
+        self.rdo_quant_dev(self.rdoq_params(d_in.ptr, d_out.ptr, d_cls.ptr, d_qp.ptr, d_nnz.ptr, d_stat.ptr, n, qp, lam))
+        return self._fetch((d_out, np.int16, (n, 1024)), (d_nnz, np.uint32, (n,)), (d_stat, RDOQ_REGION_DTYPE, (n,)))
 
     def levels_bits(self, levels, classes=None, nnz=None):
         """numpy convenience around xLevelsBitsGpu: [n_regions, 1024] int16 (and a class byte and a non-zero count per region, None: NULL)
         -> records [n_regions] of RDOQ_REGION_DTYPE (dist 0)"""
         x = np.ascontiguousarray(levels, np.int16).reshape(-1, 1024)
         n = x.shape[0]
-        d_lv, d_stat = self.alloc(max(x.nbytes, 16)), self.alloc(max(16 * n, 16))
-        d_lv.upload(x)
-        d_cls, d_nnz = self._levels_tabs(n, classes, nnz)
-        self.levels_bits_dev(self.rdoq_params(0, d_lv.ptr, d_cls.ptr if d_cls else 0, 0, d_nnz.ptr if d_nnz else 0, d_stat.ptr, n))
-        self.stream_sync()
-        return d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE) if n else np.zeros(0, RDOQ_REGION_DTYPE)
+        d_lv, d_cls, d_nnz, d_stat = self._upload(x), self._table(classes, np.uint8, n), self._table(nnz, np.uint32, n), self.alloc(max(16 * n, 16))
+        self.levels_bits_dev(self.rdoq_params(0, d_lv.ptr, d_cls.ptr, 0, d_nnz.ptr, d_stat.ptr, n))
+        return self._fetch((d_stat, RDOQ_REGION_DTYPE, (n,)))
 
     # -- the transform decision: each region's class byte by rate-distortion cost ------------------------
     @staticmethod
@@ -1418,26 +1197,13 @@ class Codec:
         """numpy convenience around xTransformDecideCtuTilesGpu: two tile arrays of a w x h frame (uint8, 512 bytes per tile), optional qp
         bytes and candidate masks (uint16) per region -> (class bytes uint8 [n], levels int16 [n, 1024], non-zero counts uint32 [n],
         records [n] of RDOQ_REGION_DTYPE, costs uint64 [n, 16]) with n = 6 CTUs' regions."""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
         n = 6 * self.ctu_count(w, h)
-        assert cur.size == w * h * 2 and pred.size == w * h * 2
-        dc, dp = self.alloc(cur.nbytes), self.alloc(pred.nbytes)
-        dc.upload(cur)
-        dp.upload(pred)
-        d_qp = self._byte_tab(n, qps)
-        d_cand = None
-        if cand is not None:
-            m = np.ascontiguousarray(cand, np.uint16).ravel()
-            assert m.size == n
-            d_cand = self.alloc(max(2 * n, 16))
-            d_cand.upload(m)
+        dc, dp, d_qp, d_cand = self._frame(cur_tiles, w, h), self._frame(pred_tiles, w, h), self._table(qps, np.uint8, n), self._table(cand, np.uint16, n)
         d_cls, d_lv, d_nnz, d_stat, d_cost = self.alloc(max(n, 16)), self.alloc(n * 2048), self.alloc(max(4 * n, 16)), self.alloc(16 * n), self.alloc(128 * n)
-        self.transform_decide_dev(self.tdecide_params(dc.ptr, dp.ptr, d_qp.ptr if d_qp else 0, d_cand.ptr if d_cand else 0, d_cls.ptr, d_lv.ptr, d_nnz.ptr,
-                                                      d_stat.ptr, d_cost.ptr, w, h, qp, lam, cand_luma, cand_chroma, class_bits))
-        self.stream_sync()
-        return (d_cls.download(np.uint8, n), d_lv.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n),
-                d_stat.download(np.uint8, 16 * n).view(RDOQ_REGION_DTYPE), d_cost.download(np.uint64, 16 * n).reshape(n, 16))
+        self.transform_decide_dev(self.tdecide_params(dc.ptr, dp.ptr, d_qp.ptr, d_cand.ptr, d_cls.ptr, d_lv.ptr, d_nnz.ptr, d_stat.ptr, d_cost.ptr,
+                                                      w, h, qp, lam, cand_luma, cand_chroma, class_bits))
+        return self._fetch((d_cls, np.uint8, (n,)), (d_lv, np.int16, (n, 1024)), (d_nnz, np.uint32, (n,)), (d_stat, RDOQ_REGION_DTYPE, (n,)),
+                           (d_cost, np.uint64, (n, 16)))
 
     # -- source analysis: tile activity, the qp map, fade weights ---------------------------------------
     @staticmethod
@@ -1454,24 +1220,18 @@ class Codec:
 
     def aq_stats(self, tiles, w, h):
         """numpy convenience around xAqStatsGpu: the tile array of a w x h frame -> (records [n_tiles] of AQ_TILE_DTYPE, totals int64 [8])"""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
-        assert src.size == w * h * 2
         n = (w // 16) * (h // 16)
-        d_src, d_tile, d_total = self._upload(src), self.alloc(32 * n), self.alloc(64)
+        d_src, d_tile, d_total = self._frame(tiles, w, h), self.alloc(32 * n), self.alloc(64)
         self.aq_stats_dev(self.aq_params(d_src.ptr, d_tile.ptr, d_total.ptr, width=w, height=h))
-        self.stream_sync()
-        return d_tile.download(np.uint8, 32 * n).view(AQ_TILE_DTYPE), d_total.download(np.int64, 8)
+        return self._fetch((d_tile, AQ_TILE_DTYPE, (n,)), (d_total, np.int64, (8,)))
 
     def aq_decide(self, records, totals, w, h, mode=1, strength_q8=256, qp=32, chroma_qp_offset=0):
         """numpy convenience around xAqDecideGpu: the records and totals of aq_stats -> (Q8 offsets int16 [n_tiles], qp bytes uint8 [n_ctus, 6])"""
-        rec = np.ascontiguousarray(records, AQ_TILE_DTYPE).ravel()
         n, n_ctu = (w // 16) * (h // 16), self.ctu_count(w, h)
-        assert rec.size == n
-        d_tile, d_total = self._upload(rec.view(np.uint8)), self._upload(np.ascontiguousarray(totals, np.int64).reshape(8))
+        d_tile, d_total = self._table(records, AQ_TILE_DTYPE, n), self._table(totals, np.int64, 8)
         d_off, d_qp = self.alloc(max(2 * n, 16)), self.alloc(max(6 * n_ctu, 16))
         self.aq_decide_dev(self.aq_params(0, d_tile.ptr, d_total.ptr, d_off.ptr, d_qp.ptr, w, h, mode, strength_q8, qp, chroma_qp_offset))
-        self.stream_sync()
-        return d_off.download(np.int16, n), d_qp.download(np.uint8, 6 * n_ctu).reshape(n_ctu, 6)
+        return self._fetch((d_off, np.int16, (n,)), (d_qp, np.uint8, (n_ctu, 6)))
 
     @staticmethod
     def weights_from_totals(cur, ref, lst=0, log2_denom=(7, 7), wp=None):
@@ -1490,11 +1250,7 @@ class Codec:
     @staticmethod
     def la_params(width=0, height=0, intra_penalty=0, strength_q8=256, qp=0, chroma_qp_offset=0, **pointers):
         """an x266_la_t from device addresses by field name (absent or 0: NULL)"""
-        names = [f[0] for f in LaParams._fields_[:14]]
-        unknown = set(pointers) - set(names)
-        if unknown:
-            raise TypeError("la_params: no such field: %s" % sorted(unknown))
-        return LaParams(*([pointers.get(n) or None for n in names] + [int(width), int(height), int(intra_penalty), int(strength_q8), int(qp), int(chroma_qp_offset)]))
+        return Codec._keyword_params(LaParams, "la_params", pointers, (width, height, intra_penalty, strength_q8, qp, chroma_qp_offset))
 
     def _la_dev(self, call, params, stream):
         self._check(getattr(self.L, LA_CALLS[call])(self.ctx, ctypes.byref(params) if params is not None else None, stream), LA_CALLS[call])
@@ -1516,69 +1272,51 @@ class Codec:
 
     def la_downscale(self, tiles, w, h):
         """numpy convenience around xLaDownscaleGpu: the tile array of a w x h frame -> the lowres tile array [n / 4, 512] (m_I zero)"""
-        src = np.ascontiguousarray(tiles, np.uint8).ravel()
-        assert src.size == w * h * 2
-        d_src, d_low = self._upload(src), self._upload(np.zeros(w * h // 2, np.uint8))
+        d_src, d_low = self._frame(tiles, w, h), self._upload(np.zeros(w * h // 2, np.uint8))
         self.la_downscale_dev(self.la_params(w, h, d_src=d_src.ptr, d_low=d_low.ptr))
-        self.stream_sync()
-        return d_low.download(np.uint8, w * h // 2).reshape(-1, 512)
+        return self._fetch((d_low, np.uint8, (w * h // 1024, 512)))
 
     def la_intra_costs(self, low_tiles, w, h):
         """numpy convenience around xLaIntraCostsGpu: the lowres tile array of a w x h frame -> (costs uint32 [n], modes uint8 [n])"""
-        low = np.ascontiguousarray(low_tiles, np.uint8).ravel()
         n = (w // 16) * (h // 16)
-        assert low.size == w * h // 2
-        d_low, d_intra, d_mode = self._upload(low), self.alloc(4 * n), self.alloc(max(n, 16))
+        d_low, d_intra, d_mode = self._table(low_tiles, np.uint8, w * h // 2), self.alloc(4 * n), self.alloc(max(n, 16))
         self.la_intra_costs_dev(self.la_params(w, h, d_low=d_low.ptr, d_intra=d_intra.ptr, d_mode=d_mode.ptr))
-        self.stream_sync()
-        return d_intra.download(np.uint32, n), d_mode.download(np.uint8, n)
+        return self._fetch((d_intra, np.uint32, (n,)), (d_mode, np.uint8, (n,)))
 
     def la_frame_cost(self, intra, mode, inter0, inter1, w, h, intra_penalty=0):
         """numpy convenience around xLaFrameCostGpu: intra costs, modes (or None) and the lists' search records (8 bytes each, or None)
         -> (records [n] of LA_BLOCK_DTYPE, totals int64 [8])"""
         n = (w // 16) * (h // 16)
-        up = lambda a, dtype: 0 if a is None else self._upload(np.ascontiguousarray(a, dtype).view(np.uint8).ravel())
-        bufs = [up(intra, np.uint32), up(mode, np.uint8), up(inter0, None), up(inter1, None)]
-        assert bufs[0] and bufs[0].nbytes >= 4 * n
+        d_intra, d_mode, d_in0, d_in1 = self._table(intra, np.uint32), self._table(mode, np.uint8), self._table(inter0, None), self._table(inter1, None)
+        assert d_intra and d_intra.nbytes >= 4 * n
         d_block, d_total = self.alloc(16 * n), self.alloc(64)
-        ptr = [b.ptr if b else 0 for b in bufs]
-        self.la_frame_cost_dev(self.la_params(w, h, intra_penalty, d_intra=ptr[0], d_mode=ptr[1], d_inter0=ptr[2], d_inter1=ptr[3], d_block=d_block.ptr,
-                                              d_total=d_total.ptr))
-        self.stream_sync()
-        return d_block.download(np.uint8, 16 * n).view(LA_BLOCK_DTYPE), d_total.download(np.int64, 8)
+        self.la_frame_cost_dev(self.la_params(w, h, intra_penalty, d_intra=d_intra.ptr, d_mode=d_mode.ptr, d_inter0=d_in0.ptr, d_inter1=d_in1.ptr,
+                                              d_block=d_block.ptr, d_total=d_total.ptr))
+        return self._fetch((d_block, LA_BLOCK_DTYPE, (n,)), (d_total, np.int64, (8,)))
 
     def la_propagate(self, records, prop, ref0, ref1, w, h):
         """numpy convenience around xLaPropagateGpu: the records, what the frame received (uint64 [n] or None) and the two
         accumulators as they stand (uint64 [n] or None) -> the two accumulators after the step (None stays None)"""
         n = (w // 16) * (h // 16)
-        up = lambda a, dtype: 0 if a is None else self._upload(np.ascontiguousarray(a, dtype).view(np.uint8).ravel())
-        d_block, d_prop, d_r0, d_r1 = up(records, LA_BLOCK_DTYPE), up(prop, np.uint64), up(ref0, np.uint64), up(ref1, np.uint64)
-        self.la_propagate_dev(self.la_params(w, h, d_block=d_block.ptr, d_prop=d_prop and d_prop.ptr, d_prop_ref0=d_r0 and d_r0.ptr,
-                                             d_prop_ref1=d_r1 and d_r1.ptr))
-        self.stream_sync()
-        return [d.download(np.uint64, n) if d else None for d in (d_r0, d_r1)]
+        d_block, (d_prop, d_r0, d_r1) = self._table(records, LA_BLOCK_DTYPE), (self._table(a, np.uint64) for a in (prop, ref0, ref1))
+        self.la_propagate_dev(self.la_params(w, h, d_block=d_block.ptr, d_prop=d_prop.ptr, d_prop_ref0=d_r0.ptr, d_prop_ref1=d_r1.ptr))
+        return list(self._fetch((d_r0, np.uint64, (n,)), (d_r1, np.uint64, (n,))))
 
     def la_tree_qp(self, records, prop, aq_offset, w, h, strength_q8=256, qp=32, chroma_qp_offset=0):
         """numpy convenience around xLaTreeQpGpu: the records, what the frame received and the AQ offsets (either may be None)
         -> (Q8 offsets int16 [n], qp bytes uint8 [n_ctus, 6])"""
         n, n_ctu = (w // 16) * (h // 16), self.ctu_count(w, h)
-        up = lambda a, dtype: 0 if a is None else self._upload(np.ascontiguousarray(a, dtype).view(np.uint8).ravel())
-        d_block, d_prop, d_aq = up(records, LA_BLOCK_DTYPE), up(prop, np.uint64), up(aq_offset, np.int16)
+        d_block, d_prop, d_aq = self._table(records, LA_BLOCK_DTYPE), self._table(prop, np.uint64), self._table(aq_offset, np.int16)
         d_off, d_qp = self.alloc(max(2 * n, 16)), self.alloc(max(6 * n_ctu, 16))
-        self.la_tree_qp_dev(self.la_params(w, h, 0, strength_q8, qp, chroma_qp_offset, d_block=d_block.ptr, d_prop=d_prop and d_prop.ptr,
-                                           d_aq_offset=d_aq and d_aq.ptr, d_offset=d_off.ptr, d_qp=d_qp.ptr))
-        self.stream_sync()
-        return d_off.download(np.int16, n), d_qp.download(np.uint8, 6 * n_ctu).reshape(n_ctu, 6)
+        self.la_tree_qp_dev(self.la_params(w, h, 0, strength_q8, qp, chroma_qp_offset, d_block=d_block.ptr, d_prop=d_prop.ptr, d_aq_offset=d_aq.ptr,
+                                           d_offset=d_off.ptr, d_qp=d_qp.ptr))
+        return self._fetch((d_off, np.int16, (n,)), (d_qp, np.uint8, (n_ctu, 6)))
 
     # -- the seeded search: a small SATD search around per-block starting vectors ------------------------------
     @staticmethod
     def seed_params(width=0, height=0, seed_scale=0, centres=0, range=0, lambda_q4=0, **pointers):
         """an x266_seed_t from device addresses by field name (absent or 0: NULL)"""
-        names = [f[0] for f in SeedParams._fields_[:5]]
-        unknown = set(pointers) - set(names)
-        if unknown:
-            raise TypeError("seed_params: no such field: %s" % sorted(unknown))
-        return SeedParams(*([pointers.get(n) or None for n in names] + [int(width), int(height), int(seed_scale), int(centres), int(range), int(lambda_q4)]))
+        return Codec._keyword_params(SeedParams, "seed_params", pointers, (width, height, seed_scale, centres, range, lambda_q4))
 
     def satd_seeded_search_dev(self, params, stream=0):
         self._check(self.L.xSatd8x8SeededSearchGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xSatd8x8SeededSearchGpu")
@@ -1586,26 +1324,17 @@ class Codec:
     def seeded_search_tiles(self, cur_tiles, ref_tiles, w, h, seeds, seed_scale=0, centres=0, rng=0, lambda_q4=0):
         """numpy convenience around xSatd8x8SeededSearchGpu: two tile arrays of a w x h frame and the seed vectors [cells, 2] int16
         -> (mv [nb, 2] int16, satd [nb] uint32, j [nb] uint32)"""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        ref = np.ascontiguousarray(ref_tiles, np.uint8).ravel()
-        assert cur.size == w * h * 2 and ref.size == w * h * 2
         nb = (h // 8) * (w // 8)
-        dc, dr, ds = self._upload(cur), self._upload(ref), self._upload(self._records(seeds, nb >> (2 * seed_scale)))
+        dc, dr, ds = self._frame(cur_tiles, w, h), self._frame(ref_tiles, w, h), self._upload(self._records(seeds, nb >> (2 * seed_scale)))
         db, dj = self.alloc(nb * 8), self.alloc(max(nb * 4, 16))
         self.satd_seeded_search_dev(self.seed_params(w, h, seed_scale, centres, rng, lambda_q4, d_cur=dc.ptr, d_ref=dr.ptr, d_seed=ds.ptr, d_best=db.ptr, d_j=dj.ptr))
-        self.stream_sync()
-        raw = db.download(np.uint8, nb * 8)
-        return raw.view(np.int16).reshape(nb, 4)[:, :2].copy(), raw.view(np.uint32).reshape(nb, 2)[:, 1].copy(), dj.download(np.uint32, nb)
+        return self._fetch_best(db, nb, dj, (nb,))
 
     # -- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames -------------------------
     @staticmethod
     def mixed_params(width=0, height=0, qp=0, rounding=0, intra_penalty=0, **pointers):
         """an x266_mixed_t from device addresses by field name (absent or 0: NULL)"""
-        names = [f[0] for f in MixedParams._fields_[:11]]
-        unknown = set(pointers) - set(names)
-        if unknown:
-            raise TypeError("mixed_params: no such field: %s" % sorted(unknown))
-        return MixedParams(*([pointers.get(n) or None for n in names] + [int(width), int(height), int(qp), int(rounding), int(intra_penalty)]))
+        return Codec._keyword_params(MixedParams, "mixed_params", pointers, (width, height, qp, rounding, intra_penalty))
 
     def dct32_code_mixed_frame_dev(self, params, stream=0):
         self._check(self.L.xDct32CodeMixedFrameGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xDct32CodeMixedFrameGpu")
@@ -1614,26 +1343,16 @@ class Codec:
         """numpy convenience around xDct32CodeMixedFrameGpu: two tile arrays of a w x h frame (multiples of 64), optionally 6 qp, kind and
         mode bytes per CTU -> a dict of levels [n_ctus, 6, 1024] int16, nnz [n_ctus, 6] uint32, kinds and modes [n_ctus, 6] uint8, costs
         [n_ctus, 6, 2] uint32 (inter, intra) and the reconstructed tile array; m_I (never written) comes from `base` (None: zeros)"""
-        cur = np.ascontiguousarray(cur_tiles, np.uint8).ravel()
-        pred = np.ascontiguousarray(pred_tiles, np.uint8).ravel()
         n = self.ctu_count(w, h)
-        assert cur.size == w * h * 2 and pred.size == cur.size
-        dc, dp, dr = self._upload(cur), self._upload(pred), self.alloc(cur.nbytes)
-        dr.upload(np.zeros(cur.size, np.uint8) if base is None else np.ascontiguousarray(base, np.uint8).ravel())
+        dc, dp, dr = self._frame(cur_tiles, w, h), self._frame(pred_tiles, w, h), self._out_frame(base, np.zeros(w * h * 2, np.uint8))
+        dq, dki, dmi = (self._table(t, np.uint8, 6 * n, tail=16) for t in (qps, kinds_in, modes_in))
         dl, dn, dk, dm, dcost = self.alloc(n * 12288), self.alloc(max(n * 24, 16)), self.alloc(max(n * 6, 16)), self.alloc(max(n * 6, 16)), self.alloc(n * 48)
-        tabs = []
-        for t in (qps, kinds_in, modes_in):
-            if t is not None:
-                t = np.ascontiguousarray(t, np.uint8).ravel()
-                assert t.size == 6 * n
-            tabs.append(None if t is None else self._upload(np.concatenate([t, np.zeros(16, np.uint8)])))
-        self.dct32_code_mixed_frame_dev(self.mixed_params(w, h, qp, rounding, intra_penalty, d_cur=dc.ptr, d_pred=dp.ptr, d_qp=tabs[0] and tabs[0].ptr,
-                                                          d_kind_in=tabs[1] and tabs[1].ptr, d_mode_in=tabs[2] and tabs[2].ptr, d_level=dl.ptr, d_nnz=dn.ptr,
-                                                          d_kind=dk.ptr, d_mode=dm.ptr, d_cost=dcost.ptr, d_recon=dr.ptr))
-        self.stream_sync()
-        return {"levels": dl.download(np.int16, n * 6144).reshape(n, 6, 1024), "nnz": dn.download(np.uint32, n * 6).reshape(n, 6),
-                "kinds": dk.download(np.uint8, n * 6).reshape(n, 6), "modes": dm.download(np.uint8, n * 6).reshape(n, 6),
-                "costs": dcost.download(np.uint32, n * 12).reshape(n, 6, 2), "recon": dr.download(np.uint8, cur.size)}
+        self.dct32_code_mixed_frame_dev(self.mixed_params(w, h, qp, rounding, intra_penalty, d_cur=dc.ptr, d_pred=dp.ptr, d_qp=dq.ptr, d_kind_in=dki.ptr,
+                                                          d_mode_in=dmi.ptr, d_level=dl.ptr, d_nnz=dn.ptr, d_kind=dk.ptr, d_mode=dm.ptr, d_cost=dcost.ptr,
+                                                          d_recon=dr.ptr))
+        got = self._fetch((dl, np.int16, (n, 6, 1024)), (dn, np.uint32, (n, 6)), (dk, np.uint8, (n, 6)), (dm, np.uint8, (n, 6)), (dcost, np.uint32, (n, 6, 2)),
+                          (dr, np.uint8, (w * h * 2,)))
+        return dict(zip(("levels", "nnz", "kinds", "modes", "costs", "recon"), got))
 
     def fill_residual_dev(self, d_dst, n_samples, seed, first_index=0, stream=0):
         self._check(self.L.xFillResidualDev(self.ctx, d_dst, n_samples, seed, first_index, stream),
