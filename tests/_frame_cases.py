@@ -14,9 +14,12 @@ for the calls that take whole CTUs):
   just below, at and just above 256 in frames at least ten units wide.
 
 The rest of a list is random: sides up to 24 x 16 tiles, everything else drawn jointly from a RandomState seeded by (family, index), the
-documented ends of a range a quarter of the time each.  The region calls of "quant" and "levels" take 6 n_ctu - drop regions, drop in
-0..5 being part of the case.  The two refinements, whose statement forms 49 whole-frame predictions, run on a stated subset of the
+documented ends of a range a quarter of the time each.  The region calls of "quant", "levels" and "rdoq" take 6 n_ctu - drop regions,
+drop in 0..5 being part of the case.  "rdoq" and "tdecide" draw their random frames within 12 x 8 tiles (their statements walk every block
+of every region in python); "rdoq" has content whose 64-bit sums pass 2^32 (rdoq_content), and the statement of "tdecide" runs on the
+regions of tdecide_sample.  The two refinements, whose statement forms 49 whole-frame predictions, run on a stated subset of the
 shapes (_refines: every shape class but the larger cut-both and residue frames, and every second random frame).  X266_FUZZ_SCALE=k lengthens every list k-fold by continuing the index; nothing else depends on the environment."""
+import functools
 import os
 import zlib
 
@@ -91,6 +94,17 @@ GEOMETRY = {
                                                ("satd_bi_costs_kernel", tiles, 4)], threads=None, random=6),                                  # 24 cases, 3.8 s
     # seeded_search_kernel: cell = blockIdx.x * kSeedWavesPerWg + wave, a cell being a 16x16 tile
     "seeded": dict(long=(1104, 16), salt=2, unit=16, cut=True, kernels=[("seeded_search_kernel", tiles, 4)], threads=None, random=5),                 # 20 cases, 0.4 s
+    # rdoq_regions_kernel, levels_bits_kernel: r = blockIdx.x * kRdoqWavesPerWg + wave, over 6 n_ctu - drop regions.  `within`: the random
+    # frames are drawn within 12 x 8 tiles (at most 36 regions), eighteen of them: three of every content kind
+    "rdoq": dict(long=(320, 64), unit=64, cut=False, drop=True, salt=2, within=(12, 8), kernels=[("rdoq_regions_kernel", regions, 4)], threads=None, random=18),   # 26 cases, 1.3 s
+    # tdecide_kernel: r = blockIdx.x * kRdoqWavesPerWg + wave over the 6 n_ctu regions of the frame: the count is even, so of the four
+    # residues only 0 and 2 exist (`residues`; _smallest would raise on 1 and 3).  The long row is 16 whole CTUs and one cut in width.
+    # No J of this call reaches 2^32: J = dist + lambda (bits + side cost).  Where levels are kept dist is a few 2^22 a region; the rate
+    # grows with the logarithm of a level and the residual's energy is bounded, so the dearest region is a residual of +-255 at every
+    # sample at qp 0: 405 000 sixteenths of a bit in the statement, and J <= 8192 (405 000 + 65535) = 2^31.85.  The list must reach
+    # 2^31, the upper half of the low dword, instead (tests/test_frame_cases.py)
+    "tdecide": dict(long=(1040, 64), unit=16, cut=True, salt=0, within=(12, 8), kernels=[("tdecide_kernel", lambda w, h: 6 * ctu_count(w, h), 4)], residues=(0, 2),
+                    threads=None, random=5),                                                                                  # 19 cases, 3.1 s
 }
 FAMILIES = tuple(GEOMETRY)
 THREADS_PER_WG = 256
@@ -141,7 +155,7 @@ def mandatory_shapes(family):
     if g.get("refines"):
         out.append(("cut both 16, refined", 80, 80))
     for name, count, modulus in g["kernels"]:
-        for r in range(modulus):
+        for r in g.get("residues", range(modulus)):
             if not g.get("drop") and any(count(*x[1:]) % modulus == r and count(*x[1:]) > 2 * modulus for x in out):
                 continue                                                    # a shape of the list has it already
             out.append(("%s residue %d" % (name, r),) + _smallest(count, modulus, r, u, range(6) if g.get("drop") else (None,)))
@@ -197,8 +211,46 @@ INTRA_KINDS = ("oriented", "noise", "flat", "extreme")                          
 MIXED_TIE_PENALTY = 28768
 
 
+RDOQ_KINDS = ("laplacian", "heavy_head", "heavy_cg", "fullrange", "ends", "zeros")
+RDOQ_WIDE_KINDS = ("heavy_head", "heavy_cg")                                          # every block (of N >= 8 for "heavy_cg") has a sum of D(0) of 2^32 and more
+RDOQ_LAMBDAS = (0, 0, 1, 368, 8191, 8192)
+TDECIDE_KINDS = ("five", "noise", "ends_flat", "ends_ends")                           # _tdecide_ref's five residuals, uniform, {0, 255} against 128 and against {0, 255}
+TDECIDE_BITS = ("zero", "equal", "random", "cheap")
+TDECIDE_CLASSES = 0x777F
+
+
+@functools.lru_cache(None)
+def wide_qp(n, magnitude):
+    """the largest qp at which one coefficient of `magnitude` in a block of 1 << n has D(0) >= 2^32 (D(0) falls as qp grows: f falls
+    within six steps and halves against 2^qbits over them), from the statement's own D; -1 where there is none"""
+    from _quant_ref import F as f_of, qbits
+    from _rdoq_ref import dist
+    wide = [int(dist(np.int64(magnitude) * f_of[qp % 6], 0, int(qbits(n, qp)))) >= 1 << 32 for qp in range(52)]
+    assert wide == sorted(wide, reverse=True)
+    return sum(wide) - 1
+
+
+def _mask(r):
+    """a non-empty subset of the 13 classes: all of them, a single one, or each with probability 1/2"""
+    valid = [k for k in range(16) if (TDECIDE_CLASSES >> k) & 1]
+    how = r.randint(0, 4)
+    m = TDECIDE_CLASSES if how == 0 else 0 if how == 1 else sum(1 << k for k in valid if r.randint(0, 2))
+    return int(m if m else 1 << _pick(r, valid))
+
+
 def _draw(family, r, index, w, h):
     """everything of a case but its size"""
+    if family == "rdoq":
+        kind = RDOQ_KINDS[index % len(RDOQ_KINDS)]
+        lo = _pick(r, (12000, 20000, 28000))                                # the magnitudes of the wide kinds
+        mag = (lo, _pick(r, (lo + 4000, 32767)))
+        top = wide_qp(2, lo) if kind in RDOQ_WIDE_KINDS else 51             # the scalar qp serves every class: a 4x4 block has the lowest bound
+        return dict(kind=kind, qp=_ends(r, 0, top), lam=_pick(r, RDOQ_LAMBDAS + (int(r.randint(0, 8193)),)), heads=int(r.randint(1, 5)), mag=mag,
+                    null=_subset(r, ("d_class", "d_qp", "d_nnz", "d_stat"), 0.3), inplace=bool(r.randint(0, 2)))
+    if family == "tdecide":
+        return dict(kind=TDECIDE_KINDS[index % len(TDECIDE_KINDS)], qp=_ends(r, 0, 51), lam=_pick(r, RDOQ_LAMBDAS + (int(r.randint(0, 8193)),)),
+                    cand_luma=_mask(r), cand_chroma=_mask(r), bits=TDECIDE_BITS[(index // 2) % len(TDECIDE_BITS)],
+                    null=_subset(r, ("d_qp", "d_cand", "d_nnz", "d_stat", "d_cost"), 0.35), inplace=False, same_frame=bool(r.randint(0, 6) == 0))
     if family == "deblock":
         from _deblock_ref import OFFSETS
         kind = DEBLOCK_KINDS[index % len(DEBLOCK_KINDS)]
@@ -267,6 +319,8 @@ def cases(family, scale=None):
             cls, w, h = "random", g["unit"] * int(r.randint(1, 384 // g["unit"] + 1)), g["unit"] * int(r.randint(1, 256 // g["unit"] + 1))
             if g.get("refines") and (index - len(shapes)) % 2 == 0:          # within 6 x 4 tiles: a random frame that the refinements run on too
                 w, h = 16 * (1 + (w // 16 - 1) % 6), 16 * (1 + (h // 16 - 1) % 4)
+            if g.get("within"):
+                w, h = 16 * (1 + (w // 16 - 1) % g["within"][0]), 16 * (1 + (h // 16 - 1) % g["within"][1])
         case = dict(family=family, index=index, shape=cls, w=w, h=h, seed=int(r.randint(1, 1 << 30)))
         if g.get("drop"):
             case["drop"] = int(r.randint(0, 6)) if drop is None else drop
@@ -509,3 +563,124 @@ def seeded_content(case):
     w, h = case["w"], case["h"]
     cur, ref = E.frame_pair(case["kind"], w, h, case["seed"])
     return cur, ref, E.seed_vectors(case["seed_kind"], w, h, case["seed_scale"], case["seed"])
+
+
+# ---- RDOQ and the transform decision -----------------------------------------------------------------------------------------------------------
+def rdoq_content(case):
+    """(coefficients [n, 1024] int16, class bytes [n], qp bytes [n]), n = 6 n_ctu - drop; the coefficients are made for the classes and
+    qps the call will use (N = 32 where d_class is NULL, the scalar qp where d_qp is).  The class bytes carry garbage above the low two
+    bits, half of them are 32x32; a sixth of the qp bytes is above 51.  The wide kinds lie on Laplacian regions of 3 steps at DC and
+    have every qp byte within wide_qp of the region's class:
+      "heavy_head": the first case["heads"] scan positions of every block at a magnitude within case["mag"], random signs
+      "heavy_cg":   one whole CG other than CG 0 of every block of N >= 8 at such magnitudes, the last four of the 16 chosen within
+                    case["mag"] so that the CG's sum of D(0) is as little above a multiple of 2^32 as the last one can bring it (the
+                    three before it bring the sum within its reach of one): Jz has a high dword and a small low one, and a
+                    comparison of low dwords zeroes the CG (4x4 regions stay Laplacian)"""
+    import _levels_ref as V
+    import _rdoq_ref as R
+    from _quant_ref import F as f_of, qbits, region_n, region_qp
+    n, seed, kind, (lo, hi) = regions(case["w"], case["h"], case["drop"]), case["seed"], case["kind"], case["mag"]
+    r = np.random.RandomState(seed)
+    cls = (r.choice(4, n, p=(0.125, 0.125, 0.25, 0.5)) | r.randint(0, 64, n) << 2).astype(np.uint8)
+    used_cls = None if "d_class" in case["null"] else cls
+    n_of = region_n(used_cls, n)
+    if kind in RDOQ_WIDE_KINDS:
+        qps = np.array([_ends(r, 0, wide_qp(int(m), lo)) for m in n_of], np.uint8)
+    else:
+        qps = np.where(r.randint(0, 6, n) == 0, r.randint(52, 256, n), r.randint(0, 52, n)).astype(np.uint8)
+    used_qps = None if "d_qp" in case["null"] else qps
+    qp_of = region_qp(used_qps, case["qp"], n)
+    if kind == "fullrange":
+        return r.randint(-32768, 32768, (n, 1024)).astype(np.int16), cls, qps
+    if kind == "ends":
+        return np.array([-32768, 0, 32767], np.int16)[r.randint(0, 3, (n, 1024))], cls, qps
+    if kind == "zeros":
+        return np.zeros((n, 1024), np.int16), cls, qps
+    coef = R.laplacian(n, used_cls, used_qps, case["qp"], 10.0 if kind == "laplacian" and case["lam"] > 368 else 3.0, seed % 100000)
+    if kind == "laplacian":
+        return coef, cls, qps
+    for reg in range(n):
+        k, qp = int(n_of[reg]) - 2, int(qp_of[reg])
+        assert qp <= wide_qp(k + 2, lo), (case, reg)
+        idx = V.region_order(k).reshape(-1, 16 << 2 * k)                    # [block, scan position] -> index in the region
+        if kind == "heavy_head":
+            shape = (idx.shape[0], case["heads"])
+            coef[reg, idx[:, :case["heads"]]] = r.randint(lo, hi + 1, shape) * (1 - 2 * r.randint(0, 2, shape))
+            continue
+        if k == 0:
+            continue
+        f, qb = int(f_of[qp % 6]), int(qbits(k + 2, qp))
+        every = np.arange(lo, hi + 1, dtype=np.int64)
+        d0 = R.dist(every * f, 0, qb)
+        for b in range(idx.shape[0]):
+            s = int(r.randint(1, 1 << 2 * k))
+            m = r.randint(lo, hi + 1, 16).astype(np.int64)
+            for i in (12, 13, 14):                                          # the sum with the rest at `lo` as little below a multiple of 2^32 as i can bring it
+                m[i] = every[np.argmax((int(R.dist(m[:i] * f, 0, qb).sum()) + d0 + (15 - i) * int(d0[0])) & 0xFFFFFFFF)]
+            m[15] = every[np.argmin((int(R.dist(m[:15] * f, 0, qb).sum()) + d0) & 0xFFFFFFFF)]
+            coef[reg, idx[b, 16 * s:16 * s + 16]] = m * (1 - 2 * r.randint(0, 2, 16))
+    return coef, cls, qps
+
+
+def region_extents(w, h):
+    """[6 n_ctu, 2]: how many columns and rows of each region lie inside the frame (0: the region is wholly outside)"""
+    nx, ny = (w + 63) // 64, (h + 63) // 64
+    out = np.zeros((ny, nx, 6, 2), np.int64)
+    for cy in range(ny):
+        for cx in range(nx):
+            for q in range(4):
+                out[cy, cx, q] = np.clip(w - (cx * 64 + (q & 1) * 32), 0, 32), np.clip(h - (cy * 64 + (q >> 1) * 32), 0, 32)
+            out[cy, cx, 4:] = np.clip(w // 2 - cx * 32, 0, 32), np.clip(h // 2 - cy * 32, 0, 32)
+    out = out.reshape(-1, 2)
+    out[(out == 0).any(1)] = 0
+    return out
+
+
+def tdecide_sample(w, h):
+    """the regions the python statement decides (13 transforms and quantisations a region): all of them in frames up to two CTUs, else
+    every cut region, the first region wholly outside the frame, and the first whole region of every q"""
+    ext = region_extents(w, h)
+    n = ext.shape[0]
+    if n <= 12:
+        return np.arange(n)
+    whole, outside = (ext == 32).all(1), (ext == 0).all(1)
+    keep = ~whole & ~outside
+    keep[np.flatnonzero(outside)[:1]] = True
+    for q in range(6):
+        keep[np.flatnonzero(whole & (np.arange(n) % 6 == q))[:1]] = True
+    return np.flatnonzero(keep)
+
+
+def tdecide_content(case, oracle):
+    """a dict: cur and pred tile arrays; qp bytes [n] up to 69 (clamped at 51); d_cand [n] uint16 -- a quarter each 0, bits outside
+    0x777F alone (both fall back to the scalar masks), one class, a random subset, the last two under garbage outside 0x777F; and the
+    16 side costs: all 0, all equal, random, or 40000 but for one cheap class"""
+    import _tdecide_ref as T
+    w, h, seed, kind = case["w"], case["h"], case["seed"], case["kind"]
+    n = 6 * ctu_count(w, h)
+    r = np.random.RandomState(seed)
+    if kind == "five":
+        cur, pred = T.content_frames(oracle, w, h, seed % 1000)
+    else:
+        cur = T.tiles_of_planes(oracle, *_three(_uniform if kind == "noise" else _ends_plane, w, h, seed))
+        if kind == "ends_flat":
+            pred = T.tiles_of_planes(oracle, *(np.full((ph, pw), 128, np.uint8) for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2))))
+        else:
+            pred = T.tiles_of_planes(oracle, *_three(_uniform if kind == "noise" else _ends_plane, w, h, seed + 10))
+    valid = np.array(T.CLASS_LIST)
+    how = r.randint(0, 4, n)
+    one = 1 << valid[r.randint(0, valid.size, n)]
+    some = (r.randint(0, 2, (n, valid.size)) << valid).sum(1)
+    garbage = r.randint(0, 1 << 16, n) & ~T.CLASSES & 0xFFFF
+    cand = np.select([how == 0, how == 1, how == 2], [0, garbage | (garbage == 0) * 0x8000, one | garbage], some | garbage).astype(np.uint16)
+    bits = {"zero": [0] * 16, "equal": [int(r.randint(1, 65536))] * 16, "random": [int(v) for v in r.randint(0, 65536, 16)], "cheap": [40000] * 16}[case["bits"]]
+    if case["bits"] == "cheap":
+        bits[int(valid[r.randint(0, valid.size)])] = int(r.randint(0, 64))
+    return dict(cur=cur, pred=pred, qps=r.randint(0, 70, n).astype(np.uint8), cand=cand, class_bits=bits)
+
+
+def tdecide_args(case, d):
+    """the keyword arguments that the statement, the composition and the device driver share"""
+    null = case["null"]
+    return dict(qps=None if "d_qp" in null else d["qps"], qp=case["qp"], lam=case["lam"], cand_luma=case["cand_luma"], cand_chroma=case["cand_chroma"],
+                cand=None if "d_cand" in null else d["cand"], class_bits=d["class_bits"])

@@ -1,7 +1,7 @@
 """Rate-distortion optimised quantisation and the level rate estimate of include/x266hip.h (xRdoQuantRegionsGpu, xLevelsBitsGpu,
 xLevelBits, xLastPosBits, xCgFlagBits) in plain numpy int64, written from the header's text: the tables, R, Rlast, D, J, steps 1 to 3
-block by block with every sum of the statement taken as the sum it names.  Nothing here is derived from the library under test; f and
-qbits come from _quant_ref, the scan from _levels_ref."""
+block by block with every sum of the statement taken as the sum it names (step 3's Totals as differences of running sums).  Nothing
+here is derived from the library under test; f and qbits come from _quant_ref, the scan from _levels_ref."""
 import functools
 
 import numpy as np
@@ -93,15 +93,14 @@ def block_bits(mag, n):
         if 0 < s < sp:
             bits += CGF[coded]
         if s == 0 or s == sp or coded:
-            for i in range(lo, hi + 1):
-                bits += int(rate[cls[i], mag[i]])
+            bits += int(rate[cls[lo:hi + 1], mag[lo:hi + 1]].sum())
     return bits
 
 
-def rdoq_block(c, n, qp, lam, steps=3, totals=None):
+def rdoq_block(c, n, qp, lam, steps=3, totals=None, cgs=None):
     """one block's coefficients in scan order -> (levels in scan order, dist, bits, changed from h, CGs zeroed, last moved or gone).
     steps < 3 stops after that step (the hand-worked cases look at one rule at a time); totals: a dict that receives Total(p) of
-    step 3, Total(none) under the key None."""
+    step 3, Total(none) under the key None; cgs: a dict that receives (Jz, Jc) of every CG that step 2 weighs."""
     _, cls, rlast = _block_geometry(n)
     rate = _rate_table()
     c = np.asarray(c, np.int64)
@@ -123,12 +122,15 @@ def rdoq_block(c, n, qp, lam, steps=3, totals=None):
     n_cg = c.size // 16
     # step 2
     zeroed = 0
+    j1 = jq()                                                                   # a CG is weighed before any of its levels goes
     for s in range(1, n_cg if steps >= 2 else 0):
         sl = slice(16 * s, 16 * s + 16)
         if not q[sl].any():
             continue
-        jc = int(jq()[sl].sum()) + lam * CGF[1]
+        jc = int(j1[sl].sum()) + lam * CGF[1]
         jz = int(d0[sl].sum()) + lam * CGF[0]
+        if cgs is not None:
+            cgs[s] = (jz, jc)
         if jz < jc:
             q[sl] = 0
             zeroed += 1
@@ -146,12 +148,17 @@ def rdoq_block(c, n, qp, lam, steps=3, totals=None):
                 cost.append(int(j[sl].sum()) + lam * CGF[1])
             else:
                 cost.append(int(d0[sl].sum()) + lam * CGF[0])
+        # Total(p) = the CGs before p's + J of p's CG before p + D(q[p]) + lambda (R - sig1) + D(0) behind p + lambda Rlast(p), each sum
+        # as a difference of two running sums (int64 holds them: a block's D(0) stays below 2^55)
+        nz = np.flatnonzero(q)
+        sp = nz // 16
+        cg_before = np.concatenate(([0], np.cumsum(np.array(cost, np.int64))))
+        j_before = np.concatenate(([0], np.cumsum(j)))
+        d0_behind = int(d0.sum()) - np.cumsum(d0)
+        sig1 = np.array([sig[1] for sig in SIG], np.int64)
+        total_of = cg_before[sp] + j_before[nz] - j_before[16 * sp] + dq[nz] + lam * (rate[cls[nz], q[nz]] - sig1[cls[nz]]) + d0_behind[nz] + lam * rlast[nz]
         best_p, best_total = None, int(d0.sum())                                # Total(none)
-        for p in np.flatnonzero(q):
-            p = int(p)
-            sp = p // 16
-            total = sum(cost[:sp]) + int(j[16 * sp:p].sum()) + int(dq[p]) + lam * (int(rate[cls[p], q[p]]) - SIG[cls[p]][1]) \
-                + int(d0[p + 1:].sum()) + lam * int(rlast[p])
+        for p, total in zip(nz.tolist(), total_of.tolist()):
             if totals is not None:
                 totals[p], totals[None] = total, int(d0.sum())
             if total <= best_total:                                            # ascending p: the larger wins a tie, any p wins over none
@@ -163,6 +170,17 @@ def rdoq_block(c, n, qp, lam, steps=3, totals=None):
             moved = int(best_p != int(np.flatnonzero(q)[-1]))
             q[best_p + 1:] = 0
     return np.sign(c) * q, int(dist(x, q, qb).sum()), block_bits(q, n), changed, zeroed, moved
+
+
+def step3_choice(totals, bits=64):
+    """the position step 3 keeps as the last one (None: no level stays), from the Totals that rdoq_block hands out, each taken modulo
+    2^bits: 64 is the statement, 32 what a comparison of the low dwords alone would choose"""
+    mask = (1 << bits) - 1
+    best_p, best_total = None, totals[None] & mask
+    for p in sorted(k for k in totals if k is not None):
+        if totals[p] & mask <= best_total:
+            best_p, best_total = p, totals[p] & mask
+    return best_p
 
 
 def _region_blocks(k):

@@ -17,9 +17,11 @@ import _la_ref as L
 import _levels_ref as V
 import _mixed_frame_ref as M
 import _quant_ref as QR
+import _rdoq_ref as RQ
 import _sao_ref as S
 import _seeded_ref as E
 import _subpel_ref as P
+import _tdecide_ref as TD
 
 
 # ---- the lists themselves -----------------------------------------------------------------------------------------------------------------
@@ -48,7 +50,7 @@ def test_mandatory_shape_classes(family):
         assert any(w % 64 == 0 and h % 64 == r for w, h in sizes), r
         assert any(w % 64 == r and h % 64 for w, h in sizes) and any(w % 64 and h % 64 == r for w, h in sizes), r
     for name, count, modulus in g["kernels"]:
-        for r in range(modulus):
+        for r in g.get("residues", range(modulus)):                        # the residues the family's counts can have
             assert any(F.count_of(count, c) % modulus == r and F.count_of(count, c) > 2 * modulus for c in cs), (name, r)
     assert any(w // u > (64 if u == 16 else 32 if u == 32 else 4) for w, h in sizes)
     if g["threads"]:
@@ -69,7 +71,8 @@ def test_parameters_reach_both_ends_and_every_null_form(family):
               "intra_frame": dict(qp=(0, 51), rounding=(0, 511)),
               "mixed": dict(qp=(0, 51), rounding=(0, 511), intra_penalty=(0, 1 << 24), flip=(0, 1)),
               "qpel": dict(), "bipred": dict(bi_penalty=(0, 65535), list=(0, 1)),
-              "seeded": dict(seed_scale=(0, 1), centres=(0, 31), range=(0, 8), lam=(0, 65535))}[family]
+              "seeded": dict(seed_scale=(0, 1), centres=(0, 31), range=(0, 8), lam=(0, 65535)),
+              "rdoq": dict(qp=(0, 51), lam=(0, 8192), drop=(0, 5), heads=(1, 4)), "tdecide": dict(qp=(0, 51), lam=(0, 8192), same_frame=(False, True))}[family]
     for name, (lo, hi) in ranges.items():
         vals = [c[name] for c in cs]
         assert min(vals) == lo and max(vals) == hi, (name, min(vals), max(vals))
@@ -77,14 +80,14 @@ def test_parameters_reach_both_ends_and_every_null_form(family):
              "la": ("d_mode", "d_inter0", "d_inter1", "d_prop", "d_prop_ref0", "d_prop_ref1", "d_aq_offset", "d_offset", "d_qp"),
              "quant": ("d_class", "d_qp", "d_nnz"), "levels": ("d_class", "d_nnz", "d_nnz of unpack"), "intra_frame": ("d_qp", "d_nnz", "d_mode_in"),
              "mixed": ("d_qp", "d_kind_in", "d_mode_in", "d_nnz", "d_cost"), "qpel": ("d_costs",), "bipred": ("d_dir", "d_costs", "d_costs of the cost call", "d_dir of the cost call"),
-             "seeded": ("d_j",)}[family]
+             "seeded": ("d_j",), "rdoq": ("d_class", "d_qp", "d_nnz", "d_stat"), "tdecide": ("d_qp", "d_cand", "d_nnz", "d_stat", "d_cost")}[family]
     for name in nulls:
         assert any(name in c["null"] for c in cs) and any(name not in c["null"] for c in cs), name
-    if family in ("deblock", "quant", "intra_frame", "mixed", "qpel", "bipred"):              # the families with a call that may run in place
+    if family in ("deblock", "quant", "intra_frame", "mixed", "qpel", "bipred", "rdoq"):              # the families with a call that may run in place
         assert {c["inplace"] for c in cs} == {False, True}
     kinds = {"deblock": F.DEBLOCK_KINDS, "sao": F.SAO_KINDS, "alf": F.ALF_KINDS, "aq": F.AQ_KINDS, "la": F.LA_KINDS, "quant": F.QUANT_KINDS,
              "levels": F.LEVELS_KINDS, "intra_frame": F.INTRA_KINDS, "mixed": F.INTRA_KINDS, "qpel": F.QPEL_KINDS, "bipred": F.QPEL_KINDS,
-             "seeded": F.SEEDED_FRAMES}[family]
+             "seeded": F.SEEDED_FRAMES, "rdoq": F.RDOQ_KINDS, "tdecide": F.TDECIDE_KINDS}[family]
     assert {c["kind"] for c in cs} == set(kinds)
     if family == "seeded":                                                  # the interior of the search range too
         assert len({c["range"] for c in cs}) >= 6
@@ -285,3 +288,94 @@ def test_seeded_list_has_winners_on_the_seed_and_off_it(oracle):
         centre = index == (2 * r + 1) * r + r                               # the walk's entry of the own centre itself
         on, off = on + int(centre.sum()), off + int((~centre).sum())
     assert on > 0 and off > 0, (on, off)
+
+
+# ---- RDOQ: sums at and above 2^32 ---------------------------------------------------------------------------------------------------------
+WIDE = 1 << 32
+
+
+def rdoq_blocks(c, coef, cls, qps):
+    """the statement block by block over a case of "rdoq" and its content -> [(class k, sum of D(0) or None where no level survives
+    step 2, Totals, {CG: (Jz, Jc)}, changed, CGs zeroed, last moved)]"""
+    n_of = QR.region_n(None if "d_class" in c["null"] else cls, coef.shape[0])
+    qp_of = QR.region_qp(None if "d_qp" in c["null"] else qps, c["qp"], coef.shape[0])
+    out = []
+    for reg in range(coef.shape[0]):
+        n = int(n_of[reg])
+        for idx in RQ._region_blocks(n - 2):
+            totals, cgs = {}, {}
+            _, _, _, changed, zeroed, moved = RQ.rdoq_block(coef[reg, idx].astype(np.int64), n, int(qp_of[reg]), c["lam"], totals=totals, cgs=cgs)
+            out.append((n - 2, totals.get(None), totals, cgs, changed, zeroed, moved))
+    return out
+
+
+def test_rdoq_list_decides_on_sums_past_2_to_the_32():
+    """A block is wide when its sum of D(0) is 2^32 or more.  Per class: wide blocks in which step 3 moved or removed the last position,
+    and (N >= 8) in which step 2 zeroed a CG; wide blocks whose step-3 choice differs when the Totals are compared by their low dwords,
+    and step-2 decisions that differ when Jz and Jc are: a kernel that drops, swaps or truncates the high half of a 64-bit sum gives
+    other levels than the statement on this list.  The narrow blocks still fire all three steps, and the bytes the call clamps or
+    masks are among those it is given."""
+    seen = collections.Counter()
+    for c in F.cases("rdoq", 1):
+        coef, cls, qps = F.rdoq_content(c)
+        assert coef.dtype == np.int16 and coef.shape == (F.regions(c["w"], c["h"], c["drop"]), 1024) and cls.shape == qps.shape == coef.shape[:1], F.tag(c)
+        seen["a qp byte above 51"] += int("d_qp" not in c["null"] and (qps > 51).any())
+        seen["a class byte with high bits"] += int("d_class" not in c["null"] and (cls > 3).any())
+        for k, d0, totals, cgs, changed, zeroed, moved in rdoq_blocks(c, coef, cls, qps):
+            wide = d0 is not None and d0 >= WIDE
+            if wide:
+                seen["wide", k] += 1
+                seen["wide, step 3 acts", k] += moved
+                seen["wide, step 2 acts", k] += zeroed > 0
+                seen["step 3 by low dwords differs", k] += RQ.step3_choice(totals) != RQ.step3_choice(totals, 32)
+            elif c["lam"] > 0:
+                seen.update(changed=changed, cg_zeroed=zeroed, last_moved=moved)
+            seen["step 2 by low dwords differs", k] += sum((jz < jc) != (jz % WIDE < jc % WIDE) for jz, jc in cgs.values())
+    for k in range(4):
+        assert seen["wide, step 3 acts", k] >= 8 and seen["step 3 by low dwords differs", k] >= 4, (k, seen)
+        assert k == 0 or (seen["wide, step 2 acts", k] >= 8 and seen["step 2 by low dwords differs", k] >= 4), (k, seen)
+    assert seen["changed"] > 0 and seen["cg_zeroed"] > 0 and seen["last_moved"] > 0, seen
+    assert seen["a qp byte above 51"] > 0 and seen["a class byte with high bits"] > 0, seen
+
+
+# ---- the transform decision -----------------------------------------------------------------------------------------------------------------
+def tdecide_statement(oracle, c, d):
+    """the statement on the regions of F.tdecide_sample -> (regions, class bytes, levels, records, costs)"""
+    sel = F.tdecide_sample(c["w"], c["h"])
+    return (sel,) + TD.decide(oracle, d["cur"], d["cur"] if c["same_frame"] else d["pred"], c["w"], c["h"], regions=sel, **F.tdecide_args(c, d))
+
+
+def test_tdecide_list_lets_every_class_win_and_ties_and_cuts(oracle):
+    """every class wins a region; two candidates tie exactly; the side costs move a winner; cut regions and regions wholly outside the
+    frame; the scalar masks, d_cand, the side costs and the qp bytes in every form they are drawn in.  J stays below 2^32 whatever the
+    content (see GEOMETRY): the list must reach 2^31, the upper half of the low dword."""
+    seen, winners, largest = collections.Counter(), set(), 0
+    for c in F.cases("tdecide", 1):
+        d = F.tdecide_content(c, oracle)
+        sel, cls, level, stat, cost = tdecide_statement(oracle, c, d)
+        bits = d["class_bits"]
+        ext = F.region_extents(c["w"], c["h"])[sel]
+        winners |= set(cls.tolist())
+        seen.update(cut=int(((ext != 32).any(1) & (ext != 0).all(1)).sum()), outside=int((ext == 0).all(1).sum()), whole=int((ext == 32).all(1).sum()))
+        seen["side costs: " + c["bits"]] += 1
+        for m in (c["cand_luma"], c["cand_chroma"]):
+            assert m and m & ~TD.CLASSES == 0, F.tag(c)
+            seen["a scalar mask of one class"] += bin(m).count("1") == 1
+            seen["a scalar mask of every class"] += m == TD.CLASSES
+        if "d_cand" not in c["null"]:
+            valid, invalid = d["cand"].astype(np.int64) & TD.CLASSES, d["cand"].astype(np.int64) & ~TD.CLASSES
+            seen["d_cand of 0"] += int((d["cand"] == 0).any())
+            seen["d_cand of invalid bits alone"] += int(((valid == 0) & (invalid != 0)).any())
+            seen["d_cand of valid bits under invalid ones"] += int(((valid != 0) & (invalid != 0)).any())
+        seen["a qp byte above 51"] += int("d_qp" not in c["null"] and (d["qps"] > 51).any())
+        for i in range(sel.size):
+            js = sorted((int(cost[i, k]), k) for k in TD.CLASS_LIST if cost[i, k] != TD.ALL_ONES)
+            assert js[0][0] == int(cost[i, cls[i]]), F.tag(c)
+            seen["winner moved by the side costs"] += min((j - c["lam"] * bits[k], k) for j, k in js)[1] != int(cls[i])
+            seen["tie of the two best"] += len(js) > 1 and js[0][0] == js[1][0]
+            largest = max(largest, js[-1][0])
+    assert winners == set(TD.CLASS_LIST), sorted(winners)
+    for name in ["cut", "outside", "whole", "tie of the two best", "winner moved by the side costs", "a scalar mask of one class", "a scalar mask of every class", "d_cand of 0",
+                 "d_cand of invalid bits alone", "d_cand of valid bits under invalid ones", "a qp byte above 51"] + ["side costs: " + b for b in F.TDECIDE_BITS]:
+        assert seen[name] > 0, (name, seen)
+    assert 1 << 31 <= largest < WIDE, largest

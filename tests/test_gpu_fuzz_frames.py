@@ -5,6 +5,8 @@ its outputs (m_I included) still the pre-fill, the inputs unchanged.  Where a ca
 runs.  The drivers are the family tests' own (imported from their modules); a device error ends the session, and no case is retried.
 Two more tests decode the packed level stream of the two frame coding calls
 with tests/_decode_ref.py and compare the rebuilt frame with d_recon.  X266_FUZZ_SCALE=k runs k-fold lists."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -18,6 +20,7 @@ import _intra_frame_ref as I
 import _la_ref as L
 import _mixed_frame_ref as M
 import _quant_ref as QR
+import _rdoq_ref as RQ
 import _sao_ref as S
 import _seeded_ref as E
 import _subpel_ref as P
@@ -28,10 +31,12 @@ import test_gpu_intra_frame as TI
 import test_gpu_la as TL
 import test_gpu_levels as TV
 import test_gpu_mixed_frame as TM
+import test_gpu_rdoq as TR
 import test_gpu_bipred as TB
 import test_gpu_sao as TS
 import test_gpu_seeded as TE
 import test_gpu_subpel as TP
+import test_gpu_tdecide as TT
 
 pytestmark = pytest.mark.gpu
 TAIL = 64                                                                   # bytes behind an output array that must stay the pre-fill
@@ -446,3 +451,57 @@ def test_seeded(codec, oracle):
         TE._same(got, best, (what, "d_best"))
         if got_j is not None:
             TE._same(got_j, j, (what, "d_j"))
+
+
+# ---- RDOQ and the level rate ----------------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _case(what):
+    """names the case in a failure of a family driver's own comparison"""
+    try:
+        yield
+    except AssertionError as e:
+        raise AssertionError((what,) + e.args) from None
+
+
+def _same_stat(got, want, what, fields=("dist", "bits", "n_nz")):
+    for field in fields:
+        _same(got[field], want[field], (what, field))
+
+
+def test_rdoq(codec):
+    """the family's drivers hold every buffer between guard bands at its minimum alignment and check the guards and the inputs"""
+    for c in F.cases("rdoq"):
+        null, what = c["null"], F.tag(c)
+        coef, cls, qps = F.rdoq_content(c)
+        cls, qps = (None if "d_class" in null else cls), (None if "d_qp" in null else qps)
+        want, want_stat, _ = RQ.rdo_quant(coef, cls, qps, c["qp"], c["lam"])
+        with _case(what):
+            level, nnz, stat = TR.rdoq(codec, coef, cls, qps, c["qp"], c["lam"], in_place=c["inplace"], with_nnz="d_nnz" not in null, with_stat="d_stat" not in null)
+        _same(level, want, (what, "levels"))
+        if nnz is not None:
+            _same(nnz, want_stat["n_nz"], (what, "d_nnz"))
+        if stat is not None:
+            _same_stat(stat, want_stat, what)
+        # the rate estimate on the levels the call produced: without counts, and with counts of which every fifth is zero over whatever levels
+        counts = want_stat["n_nz"].copy()
+        counts[c["seed"] % 5::5] = 0
+        arbitrary = [(coef, None)] if c["kind"] in ("fullrange", "ends") else []      # the coefficients taken as levels: any int16
+        for lv, given in [(level, None), (level, counts)] + arbitrary:
+            with _case(what):
+                got = TR.levels_bits(codec, lv, cls, given)
+            _same_stat(got, RQ.levels_bits(lv, cls, given), (what, "xLevelsBitsGpu", "its own levels" if lv is level else "any int16", given is not None))
+
+
+# ---- the transform decision -----------------------------------------------------------------------------------------------------------------
+def test_tdecide(codec, oracle):
+    """all five outputs against the composition of the two device calls it replaces on every region, and against the statement on the
+    regions of F.tdecide_sample; the family's driver holds every buffer between guard bands at its minimum alignment"""
+    for c in F.cases("tdecide"):
+        w, h, what = c["w"], c["h"], F.tag(c)
+        d = F.tdecide_content(c, oracle)
+        cur, pred, kw = d["cur"], (d["cur"] if c["same_frame"] else d["pred"]), F.tdecide_args(c, d)
+        sel = F.tdecide_sample(w, h)
+        with _case(what):
+            got = TT.decide(codec, cur, pred, w, h, without=tuple(n for n in ("d_nnz", "d_stat", "d_cost") if n in c["null"]), same_frame=c["same_frame"], **kw)
+            TT._same(got, TT.compose(codec, cur, pred, w, h, **kw))
+            TT._same(got, TT._ref(oracle, cur, pred, w, h, sel, **kw), sel)

@@ -116,15 +116,16 @@ def test_rdoq_against_the_reference(codec, n, tables, qp, lam):
 @pytest.mark.parametrize("k", [0, 1, 2, 3])
 def test_edge_regions(codec, k):
     """all zero, every coefficient -32768, every coefficient +32767, a single non-zero at u = v = N - 1, a single non-zero at DC: at qp 0,
-    30 and 51"""
+    30 and 51, and at lambda 368, 0 and 8192"""
     coef = np.concatenate([R.edge_regions(k)] * 3)
     cls = np.full(15, k, np.uint8)
     qps = np.repeat(np.array([0, 30, 51], np.uint8), 5)
-    want, want_stat, _ = R.rdo_quant(coef, cls, qps, 0, 368)
-    assert not want[0].any() and want[1].any() and want[2].any()
-    assert want[3].any() and want[4].any() and int(want_stat["n_nz"][3]) == 1 and int(want_stat["n_nz"][4]) == 1
-    level, nnz, stat = rdoq(codec, coef, cls, qps, 0, 368)
-    _same(level, nnz, stat, want, want_stat)
+    for lam in (368, 0, 8192):
+        want, want_stat, _ = R.rdo_quant(coef, cls, qps, 0, lam)
+        assert not want[0].any() and want[1].any() and want[2].any()
+        assert want[3].any() and want[4].any() and int(want_stat["n_nz"][3]) == 1 and int(want_stat["n_nz"][4]) == 1
+        level, nnz, stat = rdoq(codec, coef, cls, qps, 0, lam)
+        _same(level, nnz, stat, want, want_stat)
 
 
 def test_ties_worked_by_hand(codec):

@@ -201,3 +201,38 @@ def test_host_helpers_reproduce_bits():
                 if s == 0 or s == p // 16 or coded:
                     total += sum(x266_amd.level_bits(int(mag[i]), pos_class(i)) for i in range(16 * s, min(16 * s + 15, p) + 1))
         assert total == int(stat["bits"][r])
+
+
+# ---- the wide content of the fuzz list ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["heavy_head", "heavy_cg"])
+def test_wide_content_is_int16_wide_at_its_qp_and_seeded(kind):
+    """tests/_frame_cases.py's two recipes: every block they make heavy has a sum of D(0) of 2^32 and more at the class and qp the call
+    will use for its region; "heavy_cg" puts the low dword of its CG's sum as low as the CG's last magnitude can"""
+    import _frame_cases as F
+    import _quant_ref as qref
+    cases = [c for c in F.cases("rdoq", 1) if c["kind"] == kind]
+    assert len(cases) >= 4 and all(0 <= c["qp"] <= F.wide_qp(2, c["mag"][0]) for c in cases)
+    assert [F.wide_qp(n, 20000) for n in (2, 3, 4, 5)] == [11, 17, 23, 29]      # D(0) = ((20000 f + 2^(qbits - 9)) >> (qbits - 8))^2 >= 2^32
+    for c in cases:
+        coef, cls, qps = F.rdoq_content(c)
+        again = F.rdoq_content(c)
+        assert coef.dtype == np.int16 and all(np.array_equal(a, b) for a, b in zip((coef, cls, qps), again))
+        assert not np.array_equal(coef, F.rdoq_content(dict(c, seed=c["seed"] + 1))[0])
+        n_of = qref.region_n(None if "d_class" in c["null"] else cls, coef.shape[0])
+        qp_of = qref.region_qp(None if "d_qp" in c["null"] else qps, c["qp"], coef.shape[0])
+        lo, hi = c["mag"]
+        for r in range(coef.shape[0]):
+            n, qb, f = int(n_of[r]), int(qref.qbits(n_of[r], qp_of[r])), int(qref.F[qp_of[r] % 6])
+            if kind == "heavy_cg" and n == 2:
+                continue
+            for idx in ref._region_blocks(n - 2):
+                d0 = ref.dist(np.abs(coef[r, idx].astype(np.int64)) * f, 0, qb)
+                assert int(d0.sum()) >= 1 << 32, (F.tag(c), r)
+                heavy = np.flatnonzero((np.abs(coef[r, idx].astype(np.int64)) >= lo) & (np.abs(coef[r, idx].astype(np.int64)) <= hi))
+                if kind == "heavy_head":
+                    assert set(range(c["heads"])) <= set(heavy.tolist()) and int(d0[:c["heads"]].min()) >= 1 << 32
+                else:
+                    cg = [s for s in range(1, idx.size // 16) if set(range(16 * s, 16 * s + 16)) <= set(heavy.tolist())]
+                    assert len(cg) == 1, (F.tag(c), r)
+                    rest = int(d0[16 * cg[0]:16 * cg[0] + 15].sum())                 # no other last magnitude brings the low dword of the sum lower
+                    assert (rest + int(d0[16 * cg[0] + 15])) % (1 << 32) == int(((rest + ref.dist(np.arange(lo, hi + 1, dtype=np.int64) * f, 0, qb)) % (1 << 32)).min())
