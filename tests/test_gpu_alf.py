@@ -9,10 +9,10 @@ import pytest
 
 import _alf_ref as R
 import x266_amd
+from _dev import EINVAL, dev, noise, run, sync_or_exit, tiles
 from _util import splitmix64
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 NAMES = ("xAlfClassifyGpu", "xAlfStatsGpu", "xAlfSumStatsGpu", "xAlfDecideGpu", "xAlfApplyGpu")
 WORDS = R.CTU_WORDS
 
@@ -32,41 +32,6 @@ def test_library_exports_and_binds_the_five_calls():
     assert (luma[:, :300] == 0x80).all() and (luma[:, 300:] == 3).all() and chroma[0].tolist() == [253, 254, 255, 0, 1, 2] + [0] * 10
 
 
-# ---- data -----------------------------------------------------------------------------------------------------------------------------
-def _noise(n, seed):
-    return (splitmix64(seed, 0, n) & np.uint64(255)).astype(np.uint8)
-
-
-def _tiles(oracle, planes, seed):
-    """the tile array of three planes with random m_I bytes (which no call may read)"""
-    t = oracle.conv_input_fmt(*planes).reshape(-1, 512)
-    t[:, 384:] = _noise(t.shape[0] * 128, seed).reshape(-1, 128)
-    return t.ravel()
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
-def _sync_or_exit(codec, rc):
-    sync = codec.L.xHipStreamSync(codec.ctx, None)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _run(codec, fn, *args):
-    """a ..._dev call that must succeed, then a sync; a device error ends the session"""
-    try:
-        fn(*args)
-    except x266_amd.X266Error:
-        _sync_or_exit(codec, -2)
-        raise
-    _sync_or_exit(codec, 0)
-
-
 @pytest.fixture(scope="module")
 def cases(oracle):
     """per (kind, w, h): planes, tile arrays and the statement's class map and statistics, computed once"""
@@ -75,7 +40,7 @@ def cases(oracle):
     def get(kind, w, h):
         if (kind, w, h) not in cache:
             org_p, dec_p = R.case(kind, w, h)
-            c = {"org_p": org_p, "dec_p": dec_p, "org": _tiles(oracle, org_p, 40 + h), "dec": _tiles(oracle, dec_p, 41 + h), "classes": R.classify(dec_p[0])}
+            c = {"org_p": org_p, "dec_p": dec_p, "org": tiles(oracle, org_p, 40 + h), "dec": tiles(oracle, dec_p, 41 + h), "classes": R.classify(dec_p[0])}
             c["stats"] = R.stats(org_p, dec_p, c["classes"]) if kind in R.STATS_KINDS else None
             cache[(kind, w, h)] = c
         return cache[(kind, w, h)]
@@ -86,7 +51,7 @@ def _class_map(w, h, seed):
     """seeded random bytes over the whole byte range; 100 seeded places carry the 25 x 4 (class, transposition) pairs, so that all occur
     at every size, class 24 also as 25..31"""
     nb = (w // 4) * (h // 4)
-    cmap = _noise(nb, seed)
+    cmap = noise(nb, seed)
     order = np.argsort(splitmix64(seed + 1, 0, nb), kind="stable")[:100]
     pairs = np.arange(100)
     cmap[order] = (cmap[order] & 0x80) | ((pairs % 4) << 5).astype(np.uint8) | np.where(pairs // 4 == 24, 24 | (cmap[order] & 7), pairs // 4).astype(np.uint8)
@@ -106,11 +71,11 @@ def test_classification(codec, cases, w, h):
     nb = (w // 4) * (h // 4)
     for kind in R.CLASSIFY_KINDS + ("spikes",):
         c = cases(kind, w, h)
-        d_dec, d_cls = _dev(codec, c["dec"]), _dev(codec, _noise(nb + 64, 50))
-        _run(codec, codec.alf_classify_dev, d_dec.ptr, w, h, d_cls.ptr)
+        d_dec, d_cls = dev(codec, c["dec"]), dev(codec, noise(nb + 64, 50))
+        run(codec, codec.alf_classify_dev, d_dec.ptr, w, h, d_cls.ptr)
         got = d_cls.download(np.uint8, nb + 64)
         assert np.array_equal(got[:nb], c["classes"].ravel()), kind
-        assert np.array_equal(got[nb:], _noise(nb + 64, 50)[nb:]), kind      # nothing behind the map
+        assert np.array_equal(got[nb:], noise(nb + 64, 50)[nb:]), kind      # nothing behind the map
         assert np.array_equal(d_dec.download(np.uint8, c["dec"].size), c["dec"]), kind
     assert np.array_equal(codec.alf_classify(c["dec"], w, h), c["classes"])
 
@@ -125,23 +90,23 @@ def test_apply_with_a_callers_class_map(codec, oracle, cases, w, h):
     cmap = _class_map(w, h, 60 + w)
     cls, tr = R.decode(cmap)
     assert len(set((cls * 4 + tr).ravel().tolist())) == 100 and (cmap & 31).max() > 24
-    base = _noise(w * h * 2, 61)
-    d_in, d_cls = _dev(codec, c["dec"]), _dev(codec, cmap)
+    base = noise(w * h * 2, 61)
+    d_in, d_cls = dev(codec, c["dec"]), dev(codec, cmap)
     for n_luma, n_chroma in ((1, 1), (3, 8), (8, 1)):
         luma, chroma = R.random_filters(n_luma, n_chroma, 62 + n_luma)
         assert {0x80, 0x7F} <= set(luma[:, :300].ravel().tolist()) and set((luma[:, 300:] & 3).ravel().tolist()) == {0, 1, 2, 3}
         for seed in range(-(-(max(n_luma, n_chroma) + 4) // n)):                # over the seeds every CTU-independent value of d_ctrl occurs
             ctrl = _ctrl_cycle(n, n_luma, n_chroma, seed)
-            d_luma, d_chroma, d_ctrl, d_out = _dev(codec, luma), _dev(codec, chroma), _dev(codec, ctrl), _dev(codec, base)
-            _run(codec, codec.alf_apply_dev, d_in.ptr, w, h, d_cls.ptr, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, d_ctrl.ptr, d_out.ptr)
+            d_luma, d_chroma, d_ctrl, d_out = dev(codec, luma), dev(codec, chroma), dev(codec, ctrl), dev(codec, base)
+            run(codec, codec.alf_apply_dev, d_in.ptr, w, h, d_cls.ptr, d_luma.ptr, n_luma, d_chroma.ptr, n_chroma, d_ctrl.ptr, d_out.ptr)
             want = R.apply_tiles(oracle, c["dec"], w, h, cmap, luma, chroma, ctrl, base)
             assert np.array_equal(d_out.download(np.uint8, base.size), want), (n_luma, n_chroma, seed)
             for d, a in ((d_luma, luma), (d_chroma, chroma), (d_ctrl, ctrl), (d_cls, cmap), (d_in, c["dec"])):
                 assert np.array_equal(d.download(np.uint8, a.size), a.ravel())
     assert np.array_equal(codec.alf_apply(c["dec"], w, h, luma, chroma, ctrl, classes=cmap, base=base), want)
     # no sets at all, with NULL arrays: a copy of the two planes
-    d_out = _dev(codec, base)
-    _run(codec, codec.alf_apply_dev, d_in.ptr, w, h, d_cls.ptr, 0, 0, 0, 0, d_ctrl.ptr, d_out.ptr)
+    d_out = dev(codec, base)
+    run(codec, codec.alf_apply_dev, d_in.ptr, w, h, d_cls.ptr, 0, 0, 0, 0, d_ctrl.ptr, d_out.ptr)
     got = d_out.download(np.uint8, base.size).reshape(-1, 512)
     assert np.array_equal(got[:, :384], c["dec"].reshape(-1, 512)[:, :384]) and np.array_equal(got[:, 384:], base.reshape(-1, 512)[:, 384:])
 
@@ -154,17 +119,17 @@ def test_internal_classification_is_the_two_step_path(codec, oracle, cases, w, h
     luma, chroma = R.random_filters(2, 2, 70)
     ctrl = _ctrl_cycle(n, 2, 2, 1)
     ctrl[:, 0] = 1 + np.arange(n) % 2                                       # every CTU filters its luma
-    base = _noise(w * h * 2, 71)
+    base = noise(w * h * 2, 71)
     for kind in ("quad", "blur"):
         c = cases(kind, w, h)
-        d_org, d_dec, d_cls = _dev(codec, c["org"]), _dev(codec, c["dec"]), codec.alloc(max(nb, 16))
-        d_luma, d_chroma, d_ctrl = _dev(codec, luma), _dev(codec, chroma), _dev(codec, ctrl)
-        _run(codec, codec.alf_classify_dev, d_dec.ptr, w, h, d_cls.ptr)
+        d_org, d_dec, d_cls = dev(codec, c["org"]), dev(codec, c["dec"]), codec.alloc(max(nb, 16))
+        d_luma, d_chroma, d_ctrl = dev(codec, luma), dev(codec, chroma), dev(codec, ctrl)
+        run(codec, codec.alf_classify_dev, d_dec.ptr, w, h, d_cls.ptr)
         outs, stats = [], []
         for d_map in (d_cls.ptr, 0):
-            d_out, d_stats = _dev(codec, base), _dev(codec, _noise(n * WORDS * 4, 72))
-            _run(codec, codec.alf_apply_dev, d_dec.ptr, w, h, d_map, d_luma.ptr, 2, d_chroma.ptr, 2, d_ctrl.ptr, d_out.ptr)
-            _run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_map, d_stats.ptr)
+            d_out, d_stats = dev(codec, base), dev(codec, noise(n * WORDS * 4, 72))
+            run(codec, codec.alf_apply_dev, d_dec.ptr, w, h, d_map, d_luma.ptr, 2, d_chroma.ptr, 2, d_ctrl.ptr, d_out.ptr)
+            run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_map, d_stats.ptr)
             outs.append(d_out.download(np.uint8, base.size))
             stats.append(d_stats.download(np.int32, n * WORDS))
         assert np.array_equal(outs[0], outs[1]) and np.array_equal(stats[0], stats[1]), kind
@@ -181,16 +146,16 @@ def test_statistics_and_totals(codec, cases, w, h):
         c = cases(kind, w, h)
         words = R.stats_words(c["stats"])
         assert np.array_equal(words.astype(np.int64), c["stats"].ravel())   # the statement's sums fit int32
-        d_org, d_dec, d_cls, d_stats = _dev(codec, c["org"]), _dev(codec, c["dec"]), _dev(codec, c["classes"]), _dev(codec, _noise(n * WORDS * 4 + 64, 80))
-        _run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_cls.ptr, d_stats.ptr)
+        d_org, d_dec, d_cls, d_stats = dev(codec, c["org"]), dev(codec, c["dec"]), dev(codec, c["classes"]), dev(codec, noise(n * WORDS * 4 + 64, 80))
+        run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_cls.ptr, d_stats.ptr)
         assert np.array_equal(d_stats.download(np.int32, n * WORDS), words), kind
-        assert np.array_equal(d_stats.download(np.uint8, n * WORDS * 4 + 64)[n * WORDS * 4:], _noise(n * WORDS * 4 + 64, 80)[n * WORDS * 4:]), kind
+        assert np.array_equal(d_stats.download(np.uint8, n * WORDS * 4 + 64)[n * WORDS * 4:], noise(n * WORDS * 4 + 64, 80)[n * WORDS * 4:]), kind
         assert np.array_equal(d_org.download(np.uint8, c["org"].size), c["org"]) and np.array_equal(d_dec.download(np.uint8, c["dec"].size), c["dec"]), kind
-        masks = [None, np.zeros(n, np.uint8), (_noise(n, 81 + w) & 1) * (1 + _noise(n, 82) % 255).astype(np.uint8), np.ones(n, np.uint8)]
+        masks = [None, np.zeros(n, np.uint8), (noise(n, 81 + w) & 1) * (1 + noise(n, 82) % 255).astype(np.uint8), np.ones(n, np.uint8)]
         for mask in masks:
-            d_total = _dev(codec, _noise(WORDS * 8, 83))
-            d_mask = None if mask is None else _dev(codec, mask)
-            _run(codec, codec.alf_sum_stats_dev, d_stats.ptr, n, 0 if mask is None else d_mask.ptr, d_total.ptr)
+            d_total = dev(codec, noise(WORDS * 8, 83))
+            d_mask = None if mask is None else dev(codec, mask)
+            run(codec, codec.alf_sum_stats_dev, d_stats.ptr, n, 0 if mask is None else d_mask.ptr, d_total.ptr)
             assert np.array_equal(d_total.download(np.int64, WORDS), R.sum_stats(c["stats"], mask)), (kind, mask)
         assert np.array_equal(d_stats.download(np.int32, n * WORDS), words), kind
     # a caller's map with every (class, transposition) pair, and the host-array forms
@@ -222,15 +187,15 @@ def test_decision(codec, cases, w, h):
         if n > 1:
             st[n - 1, 0:2300:92] = 0                                        # a CTU without luma samples, and one without V samples
             st[0, 2329] = 0
-        d_stats, d_luma, d_chroma = _dev(codec, R.stats_words(st)), _dev(codec, luma), _dev(codec, chroma)
+        d_stats, d_luma, d_chroma = dev(codec, R.stats_words(st)), dev(codec, luma), dev(codec, chroma)
         for lam in R.LAMBDAS:
             for n_luma, n_chroma in ((3, 4), (1, 1), (2, 3), (0, 0)):
-                d_ctrl = _dev(codec, _noise(3 * n + 16, 90))
-                _run(codec, codec.alf_decide_dev, d_stats.ptr, n, d_luma.ptr if n_luma else 0, n_luma, d_chroma.ptr if n_chroma else 0, n_chroma, lam, d_ctrl.ptr)
+                d_ctrl = dev(codec, noise(3 * n + 16, 90))
+                run(codec, codec.alf_decide_dev, d_stats.ptr, n, d_luma.ptr if n_luma else 0, n_luma, d_chroma.ptr if n_chroma else 0, n_chroma, lam, d_ctrl.ptr)
                 want = R.decide(st, luma[:n_luma], chroma[:n_chroma], lam)
                 got = d_ctrl.download(np.uint8, 3 * n + 16)
                 assert np.array_equal(got[:3 * n], want.ravel()), (kind, lam, n_luma, n_chroma)
-                assert np.array_equal(got[3 * n:], _noise(3 * n + 16, 90)[3 * n:])
+                assert np.array_equal(got[3 * n:], noise(3 * n + 16, 90)[3 * n:])
                 picked |= {(kind, int(v)) for v in want.ravel()}
         assert np.array_equal(d_stats.download(np.int32, n * WORDS), R.stats_words(st))
     assert ("blur", 2) in picked and ("blur", 0) in picked                 # the solved filters win somewhere and something stays off
@@ -248,11 +213,11 @@ def test_frame_edges_and_ctu_seams(codec, oracle, cases, w, h):
     luma, chroma = R.random_filters(2, 2, 95)
     luma[:, 300:], chroma[:, 6:12] = 0, 0                                   # clip index 0: a spike reaches every tap unclipped
     ctrl = np.tile(np.array([1, 2, 1], np.uint8), (n, 1))
-    base = _noise(w * h * 2, 96)
-    d_org, d_dec, d_out, d_stats = _dev(codec, c["org"]), _dev(codec, c["dec"]), _dev(codec, base), codec.alloc(n * WORDS * 4)
-    d_luma, d_chroma, d_ctrl = _dev(codec, luma), _dev(codec, chroma), _dev(codec, ctrl)
-    _run(codec, codec.alf_apply_dev, d_dec.ptr, w, h, 0, d_luma.ptr, 2, d_chroma.ptr, 2, d_ctrl.ptr, d_out.ptr)
-    _run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, 0, d_stats.ptr)
+    base = noise(w * h * 2, 96)
+    d_org, d_dec, d_out, d_stats = dev(codec, c["org"]), dev(codec, c["dec"]), dev(codec, base), codec.alloc(n * WORDS * 4)
+    d_luma, d_chroma, d_ctrl = dev(codec, luma), dev(codec, chroma), dev(codec, ctrl)
+    run(codec, codec.alf_apply_dev, d_dec.ptr, w, h, 0, d_luma.ptr, 2, d_chroma.ptr, 2, d_ctrl.ptr, d_out.ptr)
+    run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, 0, d_stats.ptr)
     want = R.apply_tiles(oracle, c["dec"], w, h, None, luma, chroma, ctrl, base)
     assert not np.array_equal(want.reshape(-1, 512)[:, :384], c["dec"].reshape(-1, 512)[:, :384])
     assert np.array_equal(d_out.download(np.uint8, base.size), want)
@@ -268,7 +233,7 @@ def test_classify_stats_decide_and_apply_in_one_graph(codec, oracle, cases):
     frames = [cases(kind, w, h) for kind in ("quad", "blur", "noise")]
     d_org, d_dec, d_cls, d_stats = codec.alloc(w * h * 2), codec.alloc(w * h * 2), codec.alloc(nb), codec.alloc(n * WORDS * 4)
     d_total, d_ctrl, d_out = codec.alloc(WORDS * 8), codec.alloc(max(3 * n, 16)), codec.alloc(w * h * 2)
-    d_luma, d_chroma = _dev(codec, luma), _dev(codec, chroma)
+    d_luma, d_chroma = dev(codec, luma), dev(codec, chroma)
     st = codec.stream_create()
     try:
         def enqueue():
@@ -284,9 +249,7 @@ def test_classify_stats_decide_and_apply_in_one_graph(codec, oracle, cases):
             d_out.upload(np.zeros(w * h * 2, np.uint8))
 
         def results():
-            rc = codec.L.xHipStreamSync(codec.ctx, st)
-            if rc != 0:
-                pytest.exit("device error (sync %d): %s" % (rc, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
+            sync_or_exit(codec, 0, st)
             return d_out.download(np.uint8, w * h * 2), d_ctrl.download(np.uint8, 3 * n), d_total.download(np.int64, WORDS)
 
         load(0)
@@ -317,7 +280,7 @@ def test_argument_errors(codec):
     """one refused call per rule, for every call; a refused call launches nothing and names itself"""
     L, ctx = codec.L, codec.ctx
     buf = codec.alloc(8 << 20)
-    fill = _noise(8 << 20, 97)
+    fill = noise(8 << 20, 97)
     buf.upload(fill)
     M = 1 << 20
     o, d, out, st, cls, lu, ch, ctl, tot, msk = (buf.ptr + i * M // 2 for i in range(1, 11))   # 64x64: 8 KiB of tiles, 9432 bytes of statistics
@@ -366,5 +329,5 @@ def test_argument_errors(codec):
                L.xAlfDecideGpu(ctx, V(st), 1, V(lu), 8, V(ch), 8, 65535, V(ctl), None), L.xAlfDecideGpu(ctx, V(st), 1, None, 0, None, 0, 0, V(ctl), None),
                L.xAlfStatsGpu(ctx, V(o), V(o), 64, 64, None, V(st), None), L.xAlfApplyGpu(ctx, V(d), 64, 64, None, None, 0, None, 0, V(ctl), V(out), None),
                L.xAlfApplyGpu(ctx, V(d), 64, 64, V(cls), V(lu), 8, V(ch), 8, V(ctl), V(out), None), L.xAlfClassifyGpu(ctx, V(d), 64, 64, V(cls), None)):
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)

@@ -10,10 +10,10 @@ import pytest
 import _aq_ref as R
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, call_struct, dev, sync_or_exit
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 try:
     CHUNK = x266_amd.aq_totals_chunk()                                      # the totals' step, as the implementation exposes it
 except (x266_amd.X266Error, AttributeError):                                # collected without a built library: the GPU tests then fail on their own
@@ -22,12 +22,6 @@ PTRS = {"d_src": 16, "d_tile": 16, "d_total": 8, "d_offset": 2, "d_qp": 1}
 DISP = {name: align * (2 * i + 1) for i, (name, align) in enumerate(PTRS.items())}          # exactly the documented alignment, no more
 SIZES = [(16, 16), (48, 80), (64, 64), (144, 80)]
 TALL = [(16, 16 * n) for n in (CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 3)]
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
 
 
 @functools.lru_cache(None)
@@ -59,9 +53,7 @@ def stats(codec, tiles, w, h, want, stream=None, guard_seed=41):
     tile = a.output("d_tile", 32 * n, 16, DISP["d_tile"])
     total = a.output("d_total", 64, 8, DISP["d_total"])
     p = codec.aq_params(src.ptr, tile.ptr, total.ptr, 0, 0, w, h, mode=0, strength_q8=-1, qp=99, chroma_qp_offset=99)   # stats reads no scalar
-    rc = codec.L.xAqStatsGpu(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, codec.L.xHipLastError(codec.ctx)
+    call_struct(codec, "xAqStatsGpu", p, stream)
     got = a.check()                                                         # guard bands and the input
     rec, tot = got["d_tile"].view(R.TILE_DTYPE), got["d_total"].view(np.int64)
     bad = np.flatnonzero(rec != want)
@@ -81,9 +73,7 @@ def decide(codec, rec, tot, w, h, mode, strength, qp=30, chroma=0, offset=True, 
     if qps:
         s["d_qp"] = a.output("d_qp", want_qp.nbytes, 1, DISP["d_qp"])
     p = codec.aq_params(0, s["d_tile"].ptr, s["d_total"].ptr, s["d_offset"].ptr if offset else 0, s["d_qp"].ptr if qps else 0, w, h, mode, strength, qp, chroma)
-    rc = codec.L.xAqDecideGpu(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, codec.L.xHipLastError(codec.ctx)
+    call_struct(codec, "xAqDecideGpu", p, stream)
     got = a.check()
     if offset:
         off = got["d_offset"].view(np.int16)
@@ -200,7 +190,7 @@ def test_stats_and_decide_in_one_graph(codec):
                 d_tile.upload(np.full(n * 32, 0x5A, np.uint8))
                 d_off.upload(np.full(n, 0x5A5A, np.int16))
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 want_off, want_qp = R.decide(rec, tot, w, h, 2, 256, 30, -1)
                 assert d_tot.download(np.int64, 8).tolist() == tot.tolist()
                 assert np.array_equal(d_tile.download(np.uint8, n * 32).view(R.TILE_DTYPE), rec)
@@ -256,19 +246,19 @@ def test_argument_errors(codec):
     for field, other in (("d_offset", "d_tile"), ("d_offset", "d_total"), ("d_offset", "d_qp"), ("d_qp", "d_tile"), ("d_qp", "d_total"), ("d_qp", "d_offset")):
         refused("xAqDecideGpu", **{field: good[other] + (extent[other] - 1) // PTRS[field] * PTRS[field]})
         refused("xAqDecideGpu", **{field: good[other]})
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     assert np.array_equal(buf.download(np.uint8, 6 * M), fill)             # nothing was launched
     # the edges of what is accepted: decide without d_src and with one output, every scalar at either end of its range
     tiles, rec, total = frame("halves", w, h)
     buf.upload(np.concatenate([fill[:M], tiles.ravel()]))
     for p in (codec.aq_params(**dict(good, d_offset=0, d_qp=0, mode=7)), ):
         rc = L.xAqStatsGpu(ctx, ctypes.byref(p), None)
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)
     for change in (dict(d_src=0, d_qp=0, mode=1, strength_q8=0, qp=0, chroma_qp_offset=-12), dict(d_src=3, d_offset=0, mode=2, strength_q8=1024, qp=51, chroma_qp_offset=12)):
         p = codec.aq_params(**dict(good, **change))
         rc = L.xAqDecideGpu(ctx, ctypes.byref(p), None)
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, (change, L.xHipLastError(ctx))
     now = buf.download(np.uint8, 6 * M)
     assert np.array_equal(now[2 * M:2 * M + n * 32].view(R.TILE_DTYPE), rec) and now[3 * M:3 * M + 64].view(np.int64).tolist() == total.tolist()
@@ -282,19 +272,19 @@ def test_argument_errors(codec):
 # ---- 6. end to end ------------------------------------------------------------------------------------------------------------------------------
 def test_the_qp_map_feeds_the_fused_coding_call(codec):
     """aq_decide's d_qp goes into xDct32CodeCtuTilesGpu without leaving the device; the result is that of the reference's qp bytes"""
-    from test_gpu_quant import _dev, _tiles_mix
+    from test_gpu_quant import _tiles_mix
     w, h = 128, 64
     n, n_ctu = 32, 2
     cur, _, _ = frame("halves", w, h)
     pred, base = _tiles_mix(w, h, 0x7A00), _tiles_mix(w, h, 0x7A01)
-    dc, dp, dr = _dev(codec, cur), _dev(codec, pred), _dev(codec, base)
+    dc, dp, dr = dev(codec, cur), dev(codec, pred), dev(codec, base)
     d_tile, d_tot, d_qp = codec.alloc(n * 32), codec.alloc(64), codec.alloc(16)
     dl, dn = codec.alloc(n_ctu * 12288), codec.alloc(n_ctu * 24)
     p = codec.aq_params(dc.ptr, d_tile.ptr, d_tot.ptr, 0, d_qp.ptr, w, h, 2, 256, 30, 2)
     codec.aq_stats_dev(p)
     codec.aq_decide_dev(p)
     codec.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, d_qp.ptr, 0, 171, dl.ptr, dn.ptr, dr.ptr)
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     rec = R.tile_stats(cur)
     want_qp = R.decide(rec, R.totals(rec), w, h, 2, 256, 30, 2)[1]
     assert len(set(want_qp.tolist())) > 2                                    # a map, not a flat qp

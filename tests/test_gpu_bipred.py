@@ -12,13 +12,12 @@ import pytest
 
 import _bipred_ref as B
 import _subpel_ref as R
-from _arena import Arena
+from _dev import EINVAL, arena_slots, dev, displacements, records, sentinels, sync_or_exit, tiles
 from _util import me_frames
 from test_gpu_mc_chroma import _mv_mix
-from test_gpu_subpel import _dev, _displacements, _records, _sentinels, _sync_or_exit, _tiles, _unpack
+from test_gpu_subpel import _unpack
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 SLICES = {1: [slice(0, 256)], 2: [slice(256, 384)], 3: [slice(0, 384)]}
 
 
@@ -42,10 +41,10 @@ def test_mc_against_the_statement(codec, oracle, w, h):
     planes a call owns equal the statement, blocks of direction 0, m_I and the unselected plane are the random pre-fill"""
     mv0, mv1 = B.vectors(w, h, w * h)
     direction = B.directions(len(mv0), w + h)
-    base = _sentinels(w, h)
+    base = sentinels(w, h)
     for n, kind in enumerate(B.KINDS):
         p0, p1 = B.case_planes(kind, w, h)
-        t0, t1 = _tiles(oracle, *p0, 40 + h), _tiles(oracle, *p1, 41 + h)
+        t0, t1 = tiles(oracle, p0, 40 + h), tiles(oracle, p1, 41 + h)
         for d in (None, direction):
             for name, wp in [("default", None)] + list(B.WEIGHTS.items()):
                 if wp is not None and (d is None) != (n == 0):              # weighted: d_dir NULL on one content kind, mixed on the other
@@ -61,8 +60,8 @@ def test_direction_zero_leaves_the_prediction_untouched(codec, oracle):
     w, h = 48, 32
     mv0, mv1 = B.vectors(w, h, 70)
     p0, p1 = B.case_planes("random", w, h)
-    t0, t1 = _tiles(oracle, *p0, 71), _tiles(oracle, *p1, 72)
-    base = _sentinels(w, h, 73)
+    t0, t1 = tiles(oracle, p0, 71), tiles(oracle, p1, 72)
+    base = sentinels(w, h, 73)
     zero = np.full(len(mv0), 0xFC, np.uint8)                                # & 3 == 0
     for planes in (1, 2, 3):
         assert np.array_equal(codec.motion_comp_bi_qpel(t0, t1, mv0, mv1, w, h, zero, None, planes, base), base)
@@ -73,8 +72,8 @@ def test_one_frame_as_both_references(codec, oracle):
     """d_ref0 == d_ref1: with equal vectors the bi prediction is the uni prediction, with different ones the statement's"""
     w, h = 48, 32
     mv0, mv1 = B.vectors(w, h, 80)
-    t0 = _tiles(oracle, *B.case_planes("extreme", w, h)[0], 81)
-    base = _sentinels(w, h, 82)
+    t0 = tiles(oracle, B.case_planes("extreme", w, h)[0], 81)
+    base = sentinels(w, h, 82)
     assert np.array_equal(codec.motion_comp_bi_qpel(t0, None, mv0, mv1, w, h, base=base), B.bi_tiles(oracle, t0, t0, mv0, mv1, None, None, w, h, base))
     assert np.array_equal(codec.motion_comp_bi_qpel(t0, None, mv0, mv0, w, h, base=base), codec.motion_comp_qpel(t0, mv0, w, h, base=base))
 
@@ -84,8 +83,8 @@ def test_directions_1_and_2_are_the_uni_call_on_the_device(codec, oracle):
     w, h = 144, 80
     mv0, mv1 = B.vectors(w, h, w * h)
     p0, p1 = B.case_planes("extreme", w, h)
-    t0, t1 = _tiles(oracle, *p0, 90), _tiles(oracle, *p1, 91)
-    base = _sentinels(w, h, 92)
+    t0, t1 = tiles(oracle, p0, 90), tiles(oracle, p1, 91)
+    base = sentinels(w, h, 92)
     nb = len(mv0)
     assert np.array_equal(codec.motion_comp_bi_qpel(t0, t1, mv0, mv1, w, h, np.full(nb, 1, np.uint8), base=base), codec.motion_comp_qpel(t0, mv0, w, h, base=base))
     assert np.array_equal(codec.motion_comp_bi_qpel(t0, t1, mv0, mv1, w, h, np.full(nb, 2, np.uint8), base=base), codec.motion_comp_qpel(t1, mv1, w, h, base=base))
@@ -97,11 +96,11 @@ def test_crafted_extremes_of_v(codec, oracle):
     hi, lo = B.crafted_extremes()
     u = R.plane("random", 16, 16, 95)
     mv = np.tile(np.int16([[2, 2]]), (16, 1))
-    base = _sentinels(32, 32, 96)
+    base = sentinels(32, 32, 96)
     big = B.WP([[127, 1, 1], [127, 1, 1]], [[127, 0, 0], [127, 0, 0]], (0, 0))
     small = B.WP([[-128, 1, 1], [-128, 1, 1]], [[-128, 0, 0], [-128, 0, 0]], (7, 0))
     for a, b in ((hi, hi), (lo, lo), (hi, lo)):
-        ta, tb = _tiles(oracle, a, u, u, 97), _tiles(oracle, b, u, u, 98)
+        ta, tb = tiles(oracle, (a, u, u), 97), tiles(oracle, (b, u, u), 98)
         for wp in (None, big, small):
             for d in (1, 2, 3):
                 direction = np.full(16, d, np.uint8)
@@ -121,7 +120,7 @@ def test_costs_and_direction_of_the_decision_recipe(codec, oracle, penalty):
     large penalty prices direction 3 out"""
     w, h = 144, 80
     cur, ref0, ref1, mv0, mv1 = B.decision_case(oracle, w, h, 900)
-    ct, t0, t1 = (_tiles(oracle, p, *_chroma_for(w, h, 100 + i), 110 + i) for i, p in enumerate((cur, ref0, ref1)))
+    ct, t0, t1 = (tiles(oracle, (p, *_chroma_for(w, h, 100 + i)), 110 + i) for i, p in enumerate((cur, ref0, ref1)))
     want_costs, want_dir = B.costs3(oracle, cur, ref0, ref1, mv0, mv1, None, penalty)
     costs, direction = codec.satd8x8_bi_costs(ct, t0, t1, w, h, mv0, mv1, None, penalty)
     assert np.array_equal(costs, want_costs) and np.array_equal(direction, want_dir)
@@ -140,13 +139,13 @@ def test_costs_against_the_statement(codec, oracle, w, h):
     for n, kind in enumerate(B.KINDS):
         p0, p1 = B.case_planes(kind, w, h)
         cur = me_frames(w, h, 0, 120 + n)[0]
-        ct, t0, t1 = _tiles(oracle, cur, *_chroma_for(w, h, 121), 122), _tiles(oracle, *p0, 123), _tiles(oracle, *p1, 124)
+        ct, t0, t1 = tiles(oracle, (cur, *_chroma_for(w, h, 121)), 122), tiles(oracle, p0, 123), tiles(oracle, p1, 124)
         for wp in (None, list(B.WEIGHTS.values())[n]):
             want_costs, want_dir = B.costs3(oracle, cur, p0[0], p1[0], mv0, mv1, wp, 9)
             costs, direction = codec.satd8x8_bi_costs(ct, t0, t1, w, h, mv0, mv1, _wp(codec, wp), 9)
             assert np.array_equal(costs, want_costs) and np.array_equal(direction, want_dir), (kind, wp is None)
-    dc, d0, d1, dm0, dm1 = _dev(codec, ct), _dev(codec, t0), _dev(codec, t1), _dev(codec, _records(mv0)), _dev(codec, _records(mv1))
-    dk, dd = _dev(codec, np.full(nb * 3, 0xA5A5A5A5, np.uint32)), _dev(codec, np.full(max(nb, 16), 0xA5, np.uint8))
+    dc, d0, d1, dm0, dm1 = dev(codec, ct), dev(codec, t0), dev(codec, t1), dev(codec, records(mv0)), dev(codec, records(mv1))
+    dk, dd = dev(codec, np.full(nb * 3, 0xA5A5A5A5, np.uint32)), dev(codec, np.full(max(nb, 16), 0xA5, np.uint8))
     wpc = _wp(codec, wp)
     codec.satd8x8_bi_costs_dev(dc.ptr, d0.ptr, d1.ptr, w, h, dm0.ptr, dm1.ptr, dk.ptr, 0, wpc, 9)
     codec.satd8x8_bi_costs_dev(dc.ptr, d0.ptr, d1.ptr, w, h, dm0.ptr, dm1.ptr, 0, dd.ptr, wpc, 9)
@@ -158,7 +157,7 @@ def test_costs_against_the_statement(codec, oracle, w, h):
 def test_identical_lists_tie_and_list_0_wins(codec, oracle):
     w, h = 48, 32
     cur, ref = me_frames(w, h, 0, 130, mv=(1, -2), noise=4)
-    ct, rt = _tiles(oracle, cur, *_chroma_for(w, h, 131), 132), _tiles(oracle, ref, *_chroma_for(w, h, 133), 134)
+    ct, rt = tiles(oracle, (cur, *_chroma_for(w, h, 131)), 132), tiles(oracle, (ref, *_chroma_for(w, h, 133)), 134)
     mv = R.mv_mix_q((w // 8) * (h // 8), w, h, 135)
     costs, direction = codec.satd8x8_bi_costs(ct, rt, rt, w, h, mv, mv)
     assert (costs[:, 0] == costs[:, 1]).all() and (costs[:, 0] == costs[:, 2]).all() and (direction == 1).all()
@@ -170,7 +169,7 @@ def test_c0_is_the_cost_the_uni_refinement_reported(codec, oracle):
     nb = (w // 8) * (h // 8)
     cur, ref0 = me_frames(w, h, 0, 140, mv=(-3, 2), noise=5)
     ref1 = R.plane("random", w, h, 141)
-    ct, t0, t1 = (_tiles(oracle, p, *_chroma_for(w, h, 142 + i), 146 + i) for i, p in enumerate((cur, ref0, ref1)))
+    ct, t0, t1 = (tiles(oracle, (p, *_chroma_for(w, h, 142 + i)), 146 + i) for i, p in enumerate((cur, ref0, ref1)))
     q, q_cost, _ = codec.refine_qpel_tiles(ct, t0, w, h, _mv_mix(nb, w, h, 149))
     costs, _ = codec.satd8x8_bi_costs(ct, t0, t1, w, h, q, R.mv_mix_q(nb, w, h, 150))
     assert np.array_equal(costs[:, 0], q_cost)
@@ -209,7 +208,7 @@ def refine_refs(oracle):
 def test_refinement_against_the_reference(codec, oracle, refine_refs, w, h, lst, weights):
     cur, fix, ref, mv_fix, mv_int = _refine_case(w, h)
     want_mv, want_cost, want_costs = refine_refs(w, h, lst, weights)
-    ct, ft, rt = (_tiles(oracle, p, *_chroma_for(w, h, 210 + i), 214 + i) for i, p in enumerate((cur, fix, ref)))
+    ct, ft, rt = (tiles(oracle, (p, *_chroma_for(w, h, 210 + i)), 214 + i) for i, p in enumerate((cur, fix, ref)))
     wp = _wp(codec, B.WEIGHTS[weights] if weights else None)
     mv, cost, costs = codec.satd8x8_refine_bi_qpel(ct, ft, mv_fix, rt, mv_int, lst, w, h, wp, want_costs=True)
     assert np.array_equal(costs, want_costs)
@@ -223,12 +222,12 @@ def test_refinement_in_place_without_costs_and_its_centre_is_c2(codec, oracle, r
     w, h = 48, 32
     nb = (w // 8) * (h // 8)
     cur, fix, ref, mv_fix, mv_int = _refine_case(w, h)
-    ct, ft, rt = (_tiles(oracle, p, *_chroma_for(w, h, 220 + i), 224 + i) for i, p in enumerate((cur, fix, ref)))
+    ct, ft, rt = (tiles(oracle, (p, *_chroma_for(w, h, 220 + i)), 224 + i) for i, p in enumerate((cur, fix, ref)))
     centre = (4 * np.clip(mv_int.astype(np.int64), -8191, 8191)).astype(np.int16)
     wp = _wp(codec, B.WEIGHTS["fade"])
     for lst in (0, 1):
         want_mv, want_cost, want_costs = refine_refs(w, h, lst, "fade")
-        dc, df, dr, dmf, di = _dev(codec, ct), _dev(codec, ft), _dev(codec, rt), _dev(codec, _records(mv_fix)), _dev(codec, _records(mv_int, 0xFFFFFFFF))
+        dc, df, dr, dmf, di = dev(codec, ct), dev(codec, ft), dev(codec, rt), dev(codec, records(mv_fix)), dev(codec, records(mv_int, 0xFFFFFFFF))
         codec.satd8x8_refine_bi_qpel_dev(dc.ptr, df.ptr, dmf.ptr, dr.ptr, di.ptr, lst, w, h, di.ptr, 0, wp)
         codec.stream_sync()
         mv, cost = _unpack(di.download(np.uint8, nb * 8), nb)
@@ -248,16 +247,16 @@ def test_the_three_calls_eagerly_and_in_a_graph(codec, oracle):
     w, h = 48, 32
     nb = (w // 8) * (h // 8)
     cur, fix, ref, mv_fix, mv_int = _refine_case(w, h)
-    ct, ft, rt = (_tiles(oracle, p, *_chroma_for(w, h, 230 + i), 234 + i) for i, p in enumerate((cur, fix, ref)))
+    ct, ft, rt = (tiles(oracle, (p, *_chroma_for(w, h, 230 + i)), 234 + i) for i, p in enumerate((cur, fix, ref)))
     weights = B.WEIGHTS["fade"]
     wp = _wp(codec, weights)
-    start = _sentinels(w, h, 237)
+    start = sentinels(w, h, 237)
     q, _, _ = B.refine_bi(oracle, cur, fix, mv_fix, ref, mv_int, 0, weights)
     want_costs, want_dir = B.costs3(oracle, cur, ref, fix, q, mv_fix, weights, 25)
     want_pred = B.bi_tiles(oracle, rt, ft, q, mv_fix, want_dir, weights, w, h, start)
 
-    dc, df, dr, dmf, di = _dev(codec, ct), _dev(codec, ft), _dev(codec, rt), _dev(codec, _records(mv_fix)), _dev(codec, _records(mv_int))
-    db, dk, dd, dp = codec.alloc(nb * 8), codec.alloc(nb * 12), codec.alloc(max(nb, 16)), _dev(codec, start)
+    dc, df, dr, dmf, di = dev(codec, ct), dev(codec, ft), dev(codec, rt), dev(codec, records(mv_fix)), dev(codec, records(mv_int))
+    db, dk, dd, dp = codec.alloc(nb * 8), codec.alloc(nb * 12), codec.alloc(max(nb, 16)), dev(codec, start)
     st = codec.stream_create()
     try:
         def enqueue():
@@ -302,39 +301,34 @@ NAMES = {"mc": b"xMotionCompBiQpelTiles", "costs": b"xSatd8x8BiCostsFromTiles", 
 @pytest.fixture(scope="module")
 def arena_data(oracle):
     cur, fix, ref, mv_fix, mv_int = _refine_case(AW, AH)
-    ct, ft, rt = (_tiles(oracle, p, *_chroma_for(AW, AH, 300 + i), 304 + i) for i, p in enumerate((cur, fix, ref)))
+    ct, ft, rt = (tiles(oracle, (p, *_chroma_for(AW, AH, 300 + i)), 304 + i) for i, p in enumerate((cur, fix, ref)))
     return dict(planes=(cur, fix, ref), ct=ct, t0=rt, t1=ft, mv0=R.mv_mix_q(ANB, AW, AH, 307), mv1=mv_fix, mv_int=mv_int, direction=B.directions(ANB, 308))
 
 
 def _arena(codec, oracle, data, call, disp, guard_seed):
     """the call's buffers placed by `disp`, and the call itself on them"""
-    a = Arena(codec)
     wp = _wp(codec, B.WEIGHTS["fade"])
-
-    def place(name, payload):
-        return a.input(name, payload, disp[name][1], disp[name][0], guard_seed + len(a.slots))
-
-    def result(name, nbytes, written=None):
-        return a.output(name, nbytes, disp[name][1], disp[name][0], written=written)
-
+    L, c = codec.L, codec.ctx
     if call == "mc":
         skip = (data["direction"].reshape(AH // 8, AW // 8) & 3) == 0          # blocks of direction 0 are holes: marked planes, in tile order
         marks = oracle.conv_input_fmt(*(np.repeat(np.repeat(skip, e, 0), e, 1).astype(np.uint8) for e in (8, 4, 4))).reshape(-1, 512)
         written = np.zeros(marks.shape, bool)
         written[:, :384] = marks[:, :384] == 0
-        s = [place("d_ref0", data["t0"]), place("d_ref1", data["t1"]), place("d_mv0", _records(data["mv0"])), place("d_mv1", _records(data["mv1"])),
-             place("d_dir", data["direction"]), result("d_pred", AW * AH * 2, written.ravel())]
-        fn = lambda: codec.L.xMotionCompBiQpelTiles(codec.ctx, s[0].ptr, s[1].ptr, s[2].ptr, s[3].ptr, s[4].ptr, ctypes.byref(wp), 3, AW, AH, s[5].ptr, None)
+        payload = {"d_ref0": data["t0"], "d_ref1": data["t1"], "d_mv0": records(data["mv0"]), "d_mv1": records(data["mv1"]), "d_dir": data["direction"]}
+        a, s = arena_slots(codec, PTRS[call], ("d_pred",), payload, disp, guard_seed, written={"d_pred": written.ravel()}, sizes={"d_pred": AW * AH * 2})
+        fn = lambda: L.xMotionCompBiQpelTiles(c, s["d_ref0"].ptr, s["d_ref1"].ptr, s["d_mv0"].ptr, s["d_mv1"].ptr, s["d_dir"].ptr, ctypes.byref(wp), 3, AW, AH,
+                                              s["d_pred"].ptr, None)
     elif call == "costs":
-        s = [place("d_cur", data["ct"]), place("d_ref0", data["t0"]), place("d_ref1", data["t1"]), place("d_mv0", _records(data["mv0"])),
-             place("d_mv1", _records(data["mv1"])), result("d_costs", ANB * 12), result("d_dir", ANB)]
-        fn = lambda: codec.L.xSatd8x8BiCostsFromTiles(codec.ctx, s[0].ptr, s[1].ptr, s[2].ptr, AW, AH, s[3].ptr, s[4].ptr, ctypes.byref(wp), 11, s[5].ptr, s[6].ptr, None)
+        payload = {"d_cur": data["ct"], "d_ref0": data["t0"], "d_ref1": data["t1"], "d_mv0": records(data["mv0"]), "d_mv1": records(data["mv1"])}
+        a, s = arena_slots(codec, PTRS[call], ("d_costs", "d_dir"), payload, disp, guard_seed, sizes={"d_costs": ANB * 12, "d_dir": ANB})
+        fn = lambda: L.xSatd8x8BiCostsFromTiles(c, s["d_cur"].ptr, s["d_ref0"].ptr, s["d_ref1"].ptr, AW, AH, s["d_mv0"].ptr, s["d_mv1"].ptr, ctypes.byref(wp), 11,
+                                                s["d_costs"].ptr, s["d_dir"].ptr, None)
     else:
-        s = [place("d_cur", data["ct"]), place("d_ref_fix", data["t1"]), place("d_mv_fix", _records(data["mv1"])), place("d_ref", data["t0"]),
-             place("d_int", _records(data["mv_int"])), result("d_best", ANB * 8), result("d_costs", ANB * 196)]
-        fn = lambda: codec.L.xSatd8x8RefineBiQpelFromTiles(codec.ctx, s[0].ptr, s[1].ptr, s[2].ptr, s[3].ptr, s[4].ptr, 1, ctypes.byref(wp), AW, AH, s[5].ptr, s[6].ptr,
-                                                            None)
-    return a, {x.name: x for x in s}, fn
+        payload = {"d_cur": data["ct"], "d_ref_fix": data["t1"], "d_mv_fix": records(data["mv1"]), "d_ref": data["t0"], "d_int": records(data["mv_int"])}
+        a, s = arena_slots(codec, PTRS[call], ("d_best", "d_costs"), payload, disp, guard_seed, sizes={"d_best": ANB * 8, "d_costs": ANB * 196})
+        fn = lambda: L.xSatd8x8RefineBiQpelFromTiles(c, s["d_cur"].ptr, s["d_ref_fix"].ptr, s["d_mv_fix"].ptr, s["d_ref"].ptr, s["d_int"].ptr, 1, ctypes.byref(wp),
+                                                     AW, AH, s["d_best"].ptr, s["d_costs"].ptr, None)
+    return a, s, fn
 
 
 @gpu
@@ -346,9 +340,9 @@ def test_at_minimum_alignment(codec, oracle, arena_data, call):
     weights = B.WEIGHTS["fade"]
     results = []
     for guard_seed in (51, 61):
-        a, s, fn = _arena(codec, oracle, arena_data, call, _displacements(PTRS[call]), guard_seed)
+        a, s, fn = _arena(codec, oracle, arena_data, call, displacements(PTRS[call]), guard_seed)
         rc = fn()
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()
         if call == "mc":
@@ -373,9 +367,9 @@ def test_at_minimum_alignment(codec, oracle, arena_data, call):
 @gpu
 @pytest.mark.parametrize("call,ptr", [(c, p) for c in PTRS for p, align in PTRS[c].items() if align > 1])
 def test_half_alignment_is_rejected(codec, oracle, arena_data, call, ptr):
-    a, _, fn = _arena(codec, oracle, arena_data, call, _displacements(PTRS[call], halved=ptr), 71)
+    a, _, fn = _arena(codec, oracle, arena_data, call, displacements(PTRS[call], halved=ptr), 71)
     rc = fn()
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     assert rc == EINVAL and NAMES[call] in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
 

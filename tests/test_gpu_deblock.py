@@ -7,39 +7,18 @@ import numpy as np
 import pytest
 
 import _deblock_ref as R
-from _arena import Arena
-from _util import me_frames, splitmix64
+from _dev import EINVAL, arena_slots, dev, displacements, records, sentinels, sync_or_exit, tile_written
+from _dev import tiles as _tiles                                       # `tiles` is what the tests here call their tile arrays
+from _util import me_frames
 from x266_amd._lib import DeblockParams
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 CALLS = {"xDeblockLumaGpu": "luma", "xDeblockChromaGpu": "chroma", "xDeblockGpu": "both"}
 
 
 # ---- data -------------------------------------------------------------------------------------------------------------------------------
-def _tiles(oracle, y, u, v, seed):
-    """the tile array of three planes with random m_I bytes (which no call may read)"""
-    t = oracle.conv_input_fmt(y, u, v).reshape(-1, 512)
-    t[:, 384:] = (splitmix64(seed, 0, t.shape[0] * 128) & np.uint64(255)).astype(np.uint8).reshape(-1, 128)
-    return t.ravel()
-
-
-def _prefill(w, h, seed=77):
-    return (splitmix64(seed, 0, w * h * 2) & np.uint64(255)).astype(np.uint8)
-
-
 def _records(mv):
-    rec = np.zeros((len(mv), 4), np.int16)
-    rec[:, :2] = mv
-    rec.view(np.uint32)[:, 1] = 0xFFFFFFFF                                  # the cost field is ignored
-    return rec
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
+    return records(mv, cost=0xFFFFFFFF)                                     # the cost field is ignored
 
 
 class DevSide:
@@ -49,7 +28,7 @@ class DevSide:
         self.host = {"d_class": side.cls, "d_intra": side.intra, "d_nnz": side.nnz, "d_qp": side.qps,
                      "d_mv": None if side.mv is None else _records(side.mv)}
         self.host = {k: None if a is None else np.ascontiguousarray(a).view(np.uint8).ravel() for k, a in self.host.items()}
-        self.dev = {k: None if a is None else _dev(codec, a) for k, a in self.host.items()}
+        self.dev = {k: None if a is None else dev(codec, a) for k, a in self.host.items()}
         self.params = DeblockParams(*[self.dev[k].ptr if self.dev[k] else None for k in ("d_class", "d_intra", "d_nnz", "d_qp", "d_mv")],
                                     side.qp, side.beta_offset_div2, side.tc_offset_div2)
 
@@ -66,7 +45,7 @@ def _call(codec, planes, d_in, w, h, ds, d_out, stream=0):
 def _both_ways(codec, oracle, tiles, w, h, side, planes, base, tag):
     """out of place over a pre-fill, then in place: the result, the bytes the call does not own, the inputs"""
     ds = DevSide(codec, side)
-    d_in, d_out = _dev(codec, tiles), _dev(codec, base)
+    d_in, d_out = dev(codec, tiles), dev(codec, base)
     _call(codec, planes, d_in, w, h, ds, d_out)
     codec.stream_sync()
     got = d_out.download(np.uint8, tiles.size)
@@ -85,10 +64,10 @@ def test_each_call_against_the_statement(codec, oracle, w, h):
     """every data kind with mixed classes, a mixed intra / coded / qp pattern and mixed vectors: the plane a call owns equals the
     statement, every other byte of d_out is the pre-fill, d_in and the side arrays are unchanged; in place gives the same planes"""
     total = R.new_counts()
-    base = _prefill(w, h)
+    base = sentinels(w, h)
     for kind in R.KINDS:
         y, u, v, side = R.case(kind, w, h)
-        tiles = _tiles(oracle, y, u, v, 40 + h)
+        tiles = _tiles(oracle, (y, u, v), 40 + h)
         R.deblock_tiles(oracle, tiles, w, h, side, None, "both", total)
         for planes in ("luma", "chroma", "both"):
             _both_ways(codec, oracle, tiles, w, h, side, planes, base, (kind, planes))
@@ -100,12 +79,12 @@ def test_each_call_against_the_statement(codec, oracle, w, h):
 @gpu
 @pytest.mark.parametrize("w,h", R.COMPOSITE)
 def test_fused_call_is_luma_then_chroma(codec, oracle, w, h):
-    base = _prefill(w, h, 78)
+    base = sentinels(w, h, 78)
     for kind in ("blocks", "extreme"):
         y, u, v, side = R.case(kind, w, h)
-        tiles = _tiles(oracle, y, u, v, 41 + h)
+        tiles = _tiles(oracle, (y, u, v), 41 + h)
         ds = DevSide(codec, side)
-        d_in, d_two, d_one, d_two_ip, d_one_ip = (_dev(codec, a) for a in (tiles, base, base, tiles, tiles))
+        d_in, d_two, d_one, d_two_ip, d_one_ip = (dev(codec, a) for a in (tiles, base, base, tiles, tiles))
         _call(codec, "luma", d_in, w, h, ds, d_two)
         _call(codec, "chroma", d_in, w, h, ds, d_two)
         _call(codec, "both", d_in, w, h, ds, d_one)
@@ -128,9 +107,9 @@ def test_fused_call_is_luma_then_chroma(codec, oracle, w, h):
 def test_null_side_array_takes_its_default(codec, oracle, name):
     w, h = 80, 48
     y, u, v, side = R.case("blocks", w, h)
-    tiles = _tiles(oracle, y, u, v, 42)
+    tiles = _tiles(oracle, (y, u, v), 42)
     s = side.replace(**{name: None, "qp": 33})
-    _both_ways(codec, oracle, tiles, w, h, s, "both", _prefill(w, h, 79), name)
+    _both_ways(codec, oracle, tiles, w, h, s, "both", sentinels(w, h, 79), name)
     if name == "qps":                                                       # ... and NULL equals an array filled with qp
         filled = side.replace(qps=np.full_like(side.qps, 33), qp=7)
         assert np.array_equal(codec.deblock(tiles, w, h, **s.kwargs()), codec.deblock(tiles, w, h, **filled.kwargs()))
@@ -141,8 +120,8 @@ def test_null_side_array_takes_its_default(codec, oracle, name):
 def test_offsets_at_the_ends_of_the_qp_range(codec, oracle, qp):
     w, h = 64, 64
     y, u, v, side = R.case("blocks", w, h)
-    tiles = _tiles(oracle, y, u, v, 43)
-    base = _prefill(w, h, 80)
+    tiles = _tiles(oracle, (y, u, v), 43)
+    base = sentinels(w, h, 80)
     changed = 0
     for bo in (-6, 0, 6):
         for to in (-6, 0, 6):
@@ -158,7 +137,7 @@ def _coding_inputs(oracle, w, h, seed):
     cur_y, ref_y = me_frames(w, h, 0, seed, mv=(-3, 2), noise=5)
     cur_u, ref_u = me_frames(w // 2, h // 2, 0, seed + 1, mv=(-1, 1), noise=5)
     cur_v, ref_v = me_frames(w // 2, h // 2, 0, seed + 2, mv=(-1, 1), noise=5)
-    return _tiles(oracle, cur_y, cur_u, cur_v, seed + 3), _tiles(oracle, ref_y, ref_u, ref_v, seed + 4)
+    return _tiles(oracle, (cur_y, cur_u, cur_v), seed + 3), _tiles(oracle, (ref_y, ref_u, ref_v), seed + 4)
 
 
 @gpu
@@ -169,12 +148,12 @@ def test_chain_behind_the_coding_call(codec, oracle):
     cur, pred = _coding_inputs(oracle, w, h, 900)
     side = R.case("blocks", w, h)[3]
     qps = np.array([[38, 30, 45, 70, 33, 41], [29, 44, 36, 51, 47, 40]], np.uint8)
-    dc, dp, dq, dl, dn = _dev(codec, cur), _dev(codec, pred), _dev(codec, qps), codec.alloc(n * 12288), codec.alloc(n * 24)
+    dc, dp, dq, dl, dn = dev(codec, cur), dev(codec, pred), dev(codec, qps), codec.alloc(n * 12288), codec.alloc(n * 24)
     codec.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, dq.ptr, 0, 171, dl.ptr, dn.ptr, dp.ptr)
     codec.stream_sync()
     recon, nnz = dp.download(np.uint8, w * h * 2), dn.download(np.uint32, n * 6).reshape(n, 6)
     assert (nnz != 0).any() and not np.array_equal(recon, pred)
-    d_intra, d_mv = _dev(codec, side.intra), _dev(codec, _records(side.mv))
+    d_intra, d_mv = dev(codec, side.intra), dev(codec, _records(side.mv))
     params = codec.deblock_params(0, d_intra.ptr, dn.ptr, dq.ptr, d_mv.ptr, 0, 1, -1)
     codec.deblock_dev(dp.ptr, w, h, params, dp.ptr)
     codec.stream_sync()
@@ -194,7 +173,7 @@ def test_code_and_deblock_in_one_graph(codec, oracle):
     w, h, n = 128, 64, codec.ctu_count(128, 64)
     frames = [_coding_inputs(oracle, w, h, 910 + 10 * i) for i in range(3)]
     side = R.case("steps", w, h)[3]
-    d_intra, d_mv, d_cls = _dev(codec, side.intra), _dev(codec, _records(side.mv)), _dev(codec, np.full((n, 6), 3, np.uint8))
+    d_intra, d_mv, d_cls = dev(codec, side.intra), dev(codec, _records(side.mv)), dev(codec, np.full((n, 6), 3, np.uint8))
     dc, dp, dl, dn = codec.alloc(w * h * 2), codec.alloc(w * h * 2), codec.alloc(n * 12288), codec.alloc(n * 24)
     params = codec.deblock_params(d_cls.ptr, d_intra.ptr, dn.ptr, 0, d_mv.ptr, 34, 0, 0)
     st = codec.stream_create()
@@ -234,47 +213,27 @@ def test_code_and_deblock_in_one_graph(codec, oracle):
 
 
 # ---- 5. arguments and alignment ----------------------------------------------------------------------------------------------------------
-def _sync_or_exit(codec, rc):
-    sync = codec.L.xHipStreamSync(codec.ctx, None)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
 PTRS = {"d_in": 16, "d_class": 1, "d_intra": 1, "d_nnz": 4, "d_qp": 1, "d_mv": 8, "d_out": 16}
 AW, AH = 80, 48
-
-
-def _displacements(halved=None):
-    """every pointer at exactly its documented alignment and no more (odd multiples, varying between the buffers); `halved`: that one
-    at half its alignment"""
-    out = {}
-    for i, (name, align) in enumerate(PTRS.items()):
-        out[name] = (align // 2, align // 2) if name == halved else (align * (2 * i + 1), align)
-    return out
 
 
 @pytest.fixture(scope="module")
 def arena_case(oracle):
     y, u, v, side = R.case("blocks", AW, AH)
-    return _tiles(oracle, y, u, v, 804), side
+    return _tiles(oracle, (y, u, v), 804), side
 
 
 def _arena(codec, arena_case, planes, disp, guard_seed):
-    tiles, side = arena_case
-    written = np.zeros((AW * AH * 2 // 512, 512), bool)
-    written[:, {"luma": slice(0, 256), "chroma": slice(256, 384), "both": slice(0, 384)}[planes]] = True
-    a = Arena(codec)
-    arrays = {"d_in": tiles, "d_class": side.cls, "d_intra": side.intra, "d_nnz": side.nnz, "d_qp": side.qps, "d_mv": _records(side.mv)}
-    s = {k: a.input(k, arr, disp[k][1], disp[k][0], guard_seed + i) for i, (k, arr) in enumerate(arrays.items())}
-    s["d_out"] = a.output("d_out", tiles.size, disp["d_out"][1], disp["d_out"][0], written=written.ravel())
-    return a, s
+    tiles_, side = arena_case
+    data = {"d_in": tiles_, "d_class": side.cls, "d_intra": side.intra, "d_nnz": side.nnz, "d_qp": side.qps, "d_mv": _records(side.mv)}
+    return arena_slots(codec, PTRS, ("d_out",), data, disp, guard_seed, written={"d_out": tile_written(AW * AH // 256, planes)}, sizes={"d_out": tiles_.size})
 
 
 def _call_arena(codec, name, s, side):
     params = DeblockParams(s["d_class"].ptr, s["d_intra"].ptr, s["d_nnz"].ptr, s["d_qp"].ptr, s["d_mv"].ptr, side.qp,
                            side.beta_offset_div2, side.tc_offset_div2)
     rc = getattr(codec.L, name)(codec.ctx, s["d_in"].ptr, AW, AH, ctypes.byref(params), s["d_out"].ptr, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -284,7 +243,7 @@ def test_minimum_alignment(codec, oracle, arena_case, name):
     tiles, side = arena_case
     results = []
     for guard_seed in (31, 51):
-        a, s = _arena(codec, arena_case, CALLS[name], _displacements(), guard_seed)
+        a, s = _arena(codec, arena_case, CALLS[name], displacements(PTRS), guard_seed)
         assert _call_arena(codec, name, s, side) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()["d_out"]                                            # guards, the planes the call does not own, inputs
         base = s["d_out"].image[s["d_out"].start:][:tiles.size]
@@ -297,7 +256,7 @@ def test_minimum_alignment(codec, oracle, arena_case, name):
 @pytest.mark.parametrize("ptr", [p for p, align in PTRS.items() if align > 1])
 @pytest.mark.parametrize("name", list(CALLS))
 def test_half_alignment_is_rejected(codec, arena_case, name, ptr):
-    a, s = _arena(codec, arena_case, CALLS[name], _displacements(halved=ptr), 33)
+    a, s = _arena(codec, arena_case, CALLS[name], displacements(PTRS, halved=ptr), 33)
     assert _call_arena(codec, name, s, arena_case[1]) == EINVAL
     assert name.encode() in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()

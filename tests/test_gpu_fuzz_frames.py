@@ -24,7 +24,8 @@ import _rdoq_ref as RQ
 import _sao_ref as S
 import _seeded_ref as E
 import _subpel_ref as P
-import test_gpu_alf as TA
+from _dev import dev, noise, records, run, same, sentinels
+from _dev import tiles as _tiles                                       # `tiles` is what the tests here call their tile arrays
 import test_gpu_aq as TQ
 import test_gpu_deblock as TD
 import test_gpu_intra_frame as TI
@@ -33,7 +34,6 @@ import test_gpu_levels as TV
 import test_gpu_mixed_frame as TM
 import test_gpu_rdoq as TR
 import test_gpu_bipred as TB
-import test_gpu_sao as TS
 import test_gpu_seeded as TE
 import test_gpu_subpel as TP
 import test_gpu_tdecide as TT
@@ -41,7 +41,6 @@ import test_gpu_tdecide as TT
 pytestmark = pytest.mark.gpu
 TAIL = 64                                                                   # bytes behind an output array that must stay the pre-fill
 
-_noise, _dev, _run = TS._noise, TS._dev, TS._run
 
 
 def _same(got, want, what):
@@ -51,8 +50,8 @@ def _same(got, want, what):
 
 def _output(codec, nbytes, seed):
     """a device array of nbytes + TAIL seeded bytes, and those bytes"""
-    fill = _noise(nbytes + TAIL, seed)
-    return _dev(codec, fill), fill
+    fill = noise(nbytes + TAIL, seed)
+    return dev(codec, fill), fill
 
 
 def _owned(d, fill, nbytes, dtype, want, what):
@@ -73,13 +72,13 @@ def test_deblock(codec, oracle):
     for c in F.cases("deblock"):
         w, h, what = c["w"], c["h"], F.tag(c)
         y, u, v, side = F.deblock_content(c)
-        tiles = TD._tiles(oracle, y, u, v, c["seed"] + 1)
-        base = TD._prefill(w, h, c["seed"] + 2)
+        tiles = _tiles(oracle, (y, u, v), c["seed"] + 1)
+        base = sentinels(w, h, c["seed"] + 2)
         ds = TD.DevSide(codec, side)
         for planes in ("luma", "chroma", "both"):
-            d_in = _dev(codec, tiles)
-            d_out = d_in if c["inplace"] else _dev(codec, base)
-            _run(codec, TD._call, codec, planes, d_in, w, h, ds, d_out)
+            d_in = dev(codec, tiles)
+            d_out = d_in if c["inplace"] else dev(codec, base)
+            run(codec, TD._call, codec, planes, d_in, w, h, ds, d_out)
             _same(d_out.download(np.uint8, tiles.size), D.deblock_tiles(oracle, tiles, w, h, side, None if c["inplace"] else base, planes), (what, planes))
             if not c["inplace"]:
                 _unchanged([(d_in, tiles)], (what, planes))
@@ -93,25 +92,25 @@ def test_sao(codec, oracle):
         n = codec.ctu_count(w, h)
         assert n == F.ctu_count(w, h)
         org_p, dec_p = F.sao_content(c)
-        org, dec = TS._tiles(oracle, org_p, seed + 1), TS._tiles(oracle, dec_p, seed + 2)
+        org, dec = _tiles(oracle, org_p, seed + 1), _tiles(oracle, dec_p, seed + 2)
         st = S.stats(org_p, dec_p)
         words, want = S.stats_words(st), S.decide(st, lam).ravel()
-        d_org, d_dec = _dev(codec, org), _dev(codec, dec)
+        d_org, d_dec = dev(codec, org), dev(codec, dec)
         d_stats, f_stats = _output(codec, n * 1152, seed + 3)
-        _run(codec, codec.sao_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_stats.ptr)
+        run(codec, codec.sao_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_stats.ptr)
         _owned(d_stats, f_stats, n * 1152, np.int32, words, (what, "stats"))
         d_par, f_par = _output(codec, n * 24, seed + 4)
-        _run(codec, codec.sao_decide_dev, d_stats.ptr, n, lam, d_par.ptr)
+        run(codec, codec.sao_decide_dev, d_stats.ptr, n, lam, d_par.ptr)
         _owned(d_par, f_par, n * 24, np.uint8, want, (what, "decide"))
         d_par2, f_par2 = _output(codec, n * 24, seed + 5)
         d_stats2, f_stats2 = _output(codec, n * 1152, seed + 6)
         with_stats = "d_stats" not in c["null"]
-        _run(codec, codec.sao_search_dev, d_org.ptr, d_dec.ptr, w, h, lam, d_par2.ptr, d_stats2.ptr if with_stats else 0)
+        run(codec, codec.sao_search_dev, d_org.ptr, d_dec.ptr, w, h, lam, d_par2.ptr, d_stats2.ptr if with_stats else 0)
         _owned(d_par2, f_par2, n * 24, np.uint8, want, (what, "search"))
         _owned(d_stats2, f_stats2, n * 1152 if with_stats else 0, np.int32, words if with_stats else words[:0], (what, "search's stats"))
-        base = _noise(w * h * 2, seed + 7)
-        d_out = _dev(codec, base)
-        _run(codec, codec.sao_apply_dev, d_dec.ptr, w, h, d_par.ptr, d_out.ptr)
+        base = noise(w * h * 2, seed + 7)
+        d_out = dev(codec, base)
+        run(codec, codec.sao_apply_dev, d_dec.ptr, w, h, d_par.ptr, d_out.ptr)
         _same(d_out.download(np.uint8, base.size), S.apply_tiles(oracle, dec, want, w, h, base), (what, "apply"))
         _owned(d_stats, f_stats, n * 1152, np.int32, words, (what, "stats after decide"))
         _owned(d_par, f_par, n * 24, np.uint8, want, (what, "params after apply"))
@@ -125,34 +124,34 @@ def test_alf(codec, oracle):
         w, h, lam, seed, what = c["w"], c["h"], c["lam"], c["seed"], F.tag(c)
         n, nb = codec.ctu_count(w, h), (w // 4) * (h // 4)
         org_p, dec_p = F.alf_content(c)
-        org, dec = TA._tiles(oracle, org_p, seed + 1), TA._tiles(oracle, dec_p, seed + 2)
+        org, dec = _tiles(oracle, org_p, seed + 1), _tiles(oracle, dec_p, seed + 2)
         own_map = "d_class" not in c["null"]
         cmap = F.alf_class_map(c) if own_map else None
         st = A.stats(org_p, dec_p, cmap)
         luma, chroma, ctrl, mask = F.alf_sets(c, st)
         n_luma, n_chroma = c["n_luma"], c["n_chroma"]
-        d_org, d_dec = _dev(codec, org), _dev(codec, dec)
+        d_org, d_dec = dev(codec, org), dev(codec, dec)
         d_cls, f_cls = _output(codec, nb, seed + 3)
-        _run(codec, codec.alf_classify_dev, d_dec.ptr, w, h, d_cls.ptr)
+        run(codec, codec.alf_classify_dev, d_dec.ptr, w, h, d_cls.ptr)
         _owned(d_cls, f_cls, nb, np.uint8, A.classify(dec_p[0]), (what, "classify"))
-        d_map = _dev(codec, cmap) if own_map else None
+        d_map = dev(codec, cmap) if own_map else None
         d_stats, f_stats = _output(codec, n * words_per_ctu * 4, seed + 4)
-        _run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_map.ptr if own_map else 0, d_stats.ptr)
+        run(codec, codec.alf_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_map.ptr if own_map else 0, d_stats.ptr)
         words = A.stats_words(st)
         assert np.array_equal(words.astype(np.int64), st.ravel()), what       # the statement's sums fit int32
         _owned(d_stats, f_stats, n * words_per_ctu * 4, np.int32, words, (what, "stats"))
         d_total, f_total = _output(codec, words_per_ctu * 8, seed + 5)
-        d_mask = None if mask is None else _dev(codec, mask)
-        _run(codec, codec.alf_sum_stats_dev, d_stats.ptr, n, 0 if mask is None else d_mask.ptr, d_total.ptr)
+        d_mask = None if mask is None else dev(codec, mask)
+        run(codec, codec.alf_sum_stats_dev, d_stats.ptr, n, 0 if mask is None else d_mask.ptr, d_total.ptr)
         _owned(d_total, f_total, words_per_ctu * 8, np.int64, A.sum_stats(st, mask), (what, "sum"))
-        d_luma, d_chroma = (_dev(codec, luma) if n_luma else None), (_dev(codec, chroma) if n_chroma else None)
+        d_luma, d_chroma = (dev(codec, luma) if n_luma else None), (dev(codec, chroma) if n_chroma else None)
         p_luma, p_chroma = d_luma.ptr if n_luma else 0, d_chroma.ptr if n_chroma else 0
         d_pick, f_pick = _output(codec, 3 * n, seed + 6)
-        _run(codec, codec.alf_decide_dev, d_stats.ptr, n, p_luma, n_luma, p_chroma, n_chroma, lam, d_pick.ptr)
+        run(codec, codec.alf_decide_dev, d_stats.ptr, n, p_luma, n_luma, p_chroma, n_chroma, lam, d_pick.ptr)
         _owned(d_pick, f_pick, 3 * n, np.uint8, A.decide(st, luma, chroma, lam), (what, "decide"))
-        base = _noise(w * h * 2, seed + 7)
-        d_ctrl, d_out = _dev(codec, ctrl), _dev(codec, base)
-        _run(codec, codec.alf_apply_dev, d_dec.ptr, w, h, d_map.ptr if own_map else 0, p_luma, n_luma, p_chroma, n_chroma, d_ctrl.ptr, d_out.ptr)
+        base = noise(w * h * 2, seed + 7)
+        d_ctrl, d_out = dev(codec, ctrl), dev(codec, base)
+        run(codec, codec.alf_apply_dev, d_dec.ptr, w, h, d_map.ptr if own_map else 0, p_luma, n_luma, p_chroma, n_chroma, d_ctrl.ptr, d_out.ptr)
         _same(d_out.download(np.uint8, base.size), A.apply_tiles(oracle, dec, w, h, cmap, luma, chroma, ctrl, base), (what, "apply"))
         _owned(d_stats, f_stats, n * words_per_ctu * 4, np.int32, words, (what, "stats after the calls that read them"))
         inputs = [(d_org, org), (d_dec, dec), (d_ctrl, ctrl)] + ([(d_map, cmap)] if own_map else []) + ([(d_mask, mask)] if mask is not None else [])
@@ -193,16 +192,16 @@ def test_quant(codec, oracle):
         coef, lev, cls, qps = F.quant_content(c)
         n = coef.shape[0]
         cls, qps = (None if "d_class" in null else cls), (None if "d_qp" in null else qps)
-        d_cls, d_qps = (None if cls is None else _dev(codec, cls)), (None if qps is None else _dev(codec, qps))
+        d_cls, d_qps = (None if cls is None else dev(codec, cls)), (None if qps is None else dev(codec, qps))
         p_cls, p_qps = (d_cls.ptr if d_cls else 0), (d_qps.ptr if d_qps else 0)
         for inverse, x in ((0, coef), (1, lev)):
             want = QR.quant_regions(x, bool(inverse), cls, qps, qp, rounding)
             want, want_nnz = (want, None) if inverse else want
-            d_in = _dev(codec, x)
+            d_in = dev(codec, x)
             d_out, f_out = (d_in, None) if c["inplace"] else _output(codec, n * 2048, seed + 10 + inverse)
             with_nnz = not inverse and "d_nnz" not in null
             d_nnz, f_nnz = _output(codec, 4 * n, seed + 12)
-            _run(codec, codec.quant_regions_dev, inverse, d_in.ptr, d_out.ptr, n, p_cls, p_qps, qp, rounding, d_nnz.ptr if with_nnz else 0)
+            run(codec, codec.quant_regions_dev, inverse, d_in.ptr, d_out.ptr, n, p_cls, p_qps, qp, rounding, d_nnz.ptr if with_nnz else 0)
             if c["inplace"]:
                 _same(d_in.download(np.int16, n * 1024), want, (what, inverse, "in place"))
             else:
@@ -215,12 +214,12 @@ def test_quant(codec, oracle):
         nc = codec.ctu_count(w, h)
         frame_qps = None if "d_qp" in null else frame_qps
         want_level, want_nnz, want_recon = QR.code_ctu_tiles(oracle, cur, pred, w, h, frame_qps, qp, rounding, base=pred if c["inplace"] else base)
-        d_cur, d_pred, d_fq = _dev(codec, cur), _dev(codec, pred), (None if frame_qps is None else _dev(codec, frame_qps))
-        d_recon = d_pred if c["inplace"] else _dev(codec, base)
+        d_cur, d_pred, d_fq = dev(codec, cur), dev(codec, pred), (None if frame_qps is None else dev(codec, frame_qps))
+        d_recon = d_pred if c["inplace"] else dev(codec, base)
         d_level, f_level = _output(codec, nc * 12288, seed + 13)
         d_nnz, f_nnz = _output(codec, nc * 24, seed + 14)
         with_nnz = "d_nnz" not in null
-        _run(codec, codec.dct32_code_ctu_tiles_dev, d_cur.ptr, d_pred.ptr, w, h, d_fq.ptr if d_fq else 0, qp, rounding, d_level.ptr, d_nnz.ptr if with_nnz else 0,
+        run(codec, codec.dct32_code_ctu_tiles_dev, d_cur.ptr, d_pred.ptr, w, h, d_fq.ptr if d_fq else 0, qp, rounding, d_level.ptr, d_nnz.ptr if with_nnz else 0,
              d_recon.ptr)
         _owned(d_level, f_level, nc * 12288, np.int16, want_level, (what, "fused levels"))
         _owned(d_nnz, f_nnz, nc * 24 if with_nnz else 0, np.uint32, want_nnz if with_nnz else np.zeros(0, np.uint32), (what, "fused nnz"))
@@ -268,21 +267,21 @@ def test_intra_frame(codec, oracle):
     for c in F.cases("intra_frame"):
         w, h, what = c["w"], c["h"], F.tag(c)
         planes, cur, qps, modes = _intra_case(oracle, c)
-        d_cur = _dev(codec, cur)
+        d_cur = dev(codec, cur)
         for comp in range(3):
             want = I.refs_from_planes(planes, w, h, comp)
             d_refs, f_refs = _output(codec, want.size, c["seed"] + 2 + comp)
-            _run(codec, codec.intra32_refs_from_tiles_dev, d_cur.ptr, w, h, comp, d_refs.ptr)
+            run(codec, codec.intra32_refs_from_tiles_dev, d_cur.ptr, w, h, comp, d_refs.ptr)
             _owned(d_refs, f_refs, want.size, np.uint8, want, (what, "refs", comp))
         _unchanged([(d_cur, cur)], what)
         want = I.code_frame(oracle, planes, w, h, qps, c["qp"], c["rounding"], modes)
         f = TI.Frame(codec, cur, w, h, c["seed"] % 1000)
-        d_qps, d_modes = (None if qps is None else _dev(codec, qps)), (None if modes is None else _dev(codec, modes))
+        d_qps, d_modes = (None if qps is None else dev(codec, qps)), (None if modes is None else dev(codec, modes))
         kw = dict(qps=d_qps.ptr if d_qps else 0, qp=c["qp"], rounding=c["rounding"], nnz="d_nnz" not in c["null"])
         if modes is not None and c["inplace"]:                              # d_mode == d_mode_in
             f.reset()
             f.d_mode.upload(modes)
-            TI._run(codec, f.enqueue, mode_in=f.d_mode.ptr, **kw)
+            run(codec, f.enqueue, mode_in=f.d_mode.ptr, **kw)
             f.check(oracle, f.results(), want, what, nnz=kw["nnz"])
         else:
             f.check(oracle, f.code(mode_in=d_modes.ptr if d_modes else 0, **kw), want, what, nnz=kw["nnz"])
@@ -305,7 +304,7 @@ def test_mixed(codec, oracle):
         what, null = F.tag(c), c["null"]
         f, stated, (qps, modes, kinds) = _mixed_case(codec, oracle, c)
         want = f.want(**stated)
-        d_qps, d_modes, d_kinds = (None if a is None else _dev(codec, a) for a in (qps, modes, kinds))
+        d_qps, d_modes, d_kinds = (None if a is None else dev(codec, a) for a in (qps, modes, kinds))
         kw = dict(qps=d_qps.ptr if d_qps else 0, qp=c["qp"], rounding=c["rounding"], penalty=c["intra_penalty"], nnz="d_nnz" not in null, cost="d_cost" not in null)
         if c["inplace"]:                                                    # d_recon == d_pred, d_kind == d_kind_in, d_mode == d_mode_in
             f.reset()
@@ -313,7 +312,7 @@ def test_mixed(codec, oracle):
                 f.d["kind"].upload(kinds)
             if modes is not None:
                 f.d["mode"].upload(modes)
-            TM._run(codec, f.enqueue, kind_in=f.d["kind"].ptr if kinds is not None else 0, mode_in=f.d["mode"].ptr if modes is not None else 0, recon=f.d_pred.ptr, **kw)
+            run(codec, f.enqueue, kind_in=f.d["kind"].ptr if kinds is not None else 0, mode_in=f.d["mode"].ptr if modes is not None else 0, recon=f.d_pred.ptr, **kw)
             f.check(f.results(recon=f.d_pred), want, what, nnz=kw["nnz"], cost=kw["cost"], base=f.pred, pred_kept=False)
             _same(f.d_recon.download(np.uint8, f.base.size), f.base, (what, "the separate reconstruction buffer"))
         else:
@@ -336,7 +335,7 @@ def _decodes(codec, oracle, c, level, nnz, kinds, modes, qps, pred_planes, recon
 def test_mixed_level_stream_decodes_to_the_reconstruction(codec, oracle):
     for c in F.cases("mixed"):
         f, _, (qps, modes, kinds) = _mixed_case(codec, oracle, c)
-        d_qps, d_modes, d_kinds = (None if a is None else _dev(codec, a) for a in (qps, modes, kinds))
+        d_qps, d_modes, d_kinds = (None if a is None else dev(codec, a) for a in (qps, modes, kinds))
         got = f.code(qps=d_qps.ptr if d_qps else 0, qp=c["qp"], rounding=c["rounding"], penalty=c["intra_penalty"], kind_in=d_kinds.ptr if d_kinds else 0,
                      mode_in=d_modes.ptr if d_modes else 0)
         _decodes(codec, oracle, c, got["level"], got["nnz"] if c["index"] % 2 else None, got["kind"], got["mode"], qps, f.pred_planes, got["recon"])
@@ -346,7 +345,7 @@ def test_intra_level_stream_decodes_to_the_reconstruction(codec, oracle):
     for c in F.cases("intra_frame"):
         planes, cur, qps, modes = _intra_case(oracle, c)
         f = TI.Frame(codec, cur, c["w"], c["h"], c["seed"] % 1000)
-        d_qps, d_modes = (None if qps is None else _dev(codec, qps)), (None if modes is None else _dev(codec, modes))
+        d_qps, d_modes = (None if qps is None else dev(codec, qps)), (None if modes is None else dev(codec, modes))
         level, nnz, mode, recon = f.code(qps=d_qps.ptr if d_qps else 0, qp=c["qp"], rounding=c["rounding"], mode_in=d_modes.ptr if d_modes else 0)
         _decodes(codec, oracle, c, level, nnz.ravel() if c["index"] % 2 else None, np.ones_like(mode), mode, qps, None, recon)
 
@@ -357,24 +356,24 @@ def test_qpel(codec, oracle):
         w, h, seed, what = c["w"], c["h"], c["seed"], F.tag(c)
         nb = (w // 8) * (h // 8)
         (planes, mv), refine = F.qpel_content(c, oracle)
-        rt, base, rec = TP._tiles(oracle, *planes, seed + 1), TP._sentinels(w, h, seed + 2), TP._records(mv, 0xFFFFFFFF)   # the cost field is ignored
-        d_ref, d_mv = _dev(codec, rt), _dev(codec, rec)
+        rt, base, rec = _tiles(oracle, planes, seed + 1), sentinels(w, h, seed + 2), records(mv, 0xFFFFFFFF)   # the cost field is ignored
+        d_ref, d_mv = dev(codec, rt), dev(codec, rec)
         for name, fn in (("luma", codec.motion_comp_qpel_luma_dev), ("chroma", codec.motion_comp_qpel_chroma_dev), ("both", codec.motion_comp_qpel_dev)):
-            d_out = _dev(codec, base)
-            _run(codec, fn, d_ref.ptr, d_mv.ptr, w, h, d_out.ptr)
+            d_out = dev(codec, base)
+            run(codec, fn, d_ref.ptr, d_mv.ptr, w, h, d_out.ptr)
             _same(d_out.download(np.uint8, base.size), P.mc_tiles(oracle, rt, mv, w, h, base, name), (what, name))
         _unchanged([(d_ref, rt), (d_mv, rec)], what)
         if refine is None:
             continue
         cur, ref, mv_int = refine
         want_mv, want_cost, want_costs = P.refine(oracle, cur, ref, mv_int)
-        ct, rt = TP._tiles(oracle, cur, *TP._chroma_for(w, h, seed + 3), seed + 4), TP._tiles(oracle, ref, *TP._chroma_for(w, h, seed + 5), seed + 6)
-        rec = TP._records(mv_int, 0xFFFFFFFF)
-        d_cur, d_ref, d_int = _dev(codec, ct), _dev(codec, rt), _dev(codec, rec)
+        ct, rt = _tiles(oracle, (cur, *TP._chroma_for(w, h, seed + 3)), seed + 4), _tiles(oracle, (ref, *TP._chroma_for(w, h, seed + 5)), seed + 6)
+        rec = records(mv_int, 0xFFFFFFFF)
+        d_cur, d_ref, d_int = dev(codec, ct), dev(codec, rt), dev(codec, rec)
         d_best, f_best = (d_int, None) if c["inplace"] else _output(codec, nb * 8, seed + 7)
         d_costs, f_costs = _output(codec, nb * 196, seed + 8)
         with_costs = "d_costs" not in c["null"]
-        _run(codec, codec.satd_refine_qpel_from_tiles_dev, d_cur.ptr, d_ref.ptr, w, h, d_int.ptr, d_best.ptr, d_costs.ptr if with_costs else 0)
+        run(codec, codec.satd_refine_qpel_from_tiles_dev, d_cur.ptr, d_ref.ptr, w, h, d_int.ptr, d_best.ptr, d_costs.ptr if with_costs else 0)
         got_mv, got_cost = TP._unpack(d_best.download(np.uint8, nb * 8), nb)
         _same(got_mv, want_mv, (what, "refined vectors"))
         _same(got_cost, want_cost, (what, "refined costs"))
@@ -393,26 +392,26 @@ def test_bipred(codec, oracle):
         d = F.bipred_content(c)
         wp = TB._wp(codec, d["wp"])
         # motion compensation from two references: each plane selection over a seeded pre-fill
-        t0, t1, base = TP._tiles(oracle, *d["p0"], seed + 1), TP._tiles(oracle, *d["p1"], seed + 2), TP._sentinels(w, h, seed + 3)
-        rec0, rec1 = TP._records(d["mv0"], 0xFFFFFFFF), TP._records(d["mv1"], 0xFFFFFFFF)          # the cost field is ignored
-        d_t0, d_t1, d_m0, d_m1 = (_dev(codec, a) for a in (t0, t1, rec0, rec1))
-        d_dir = None if d["direction"] is None else _dev(codec, d["direction"])
+        t0, t1, base = _tiles(oracle, d["p0"], seed + 1), _tiles(oracle, d["p1"], seed + 2), sentinels(w, h, seed + 3)
+        rec0, rec1 = records(d["mv0"], 0xFFFFFFFF), records(d["mv1"], 0xFFFFFFFF)          # the cost field is ignored
+        d_t0, d_t1, d_m0, d_m1 = (dev(codec, a) for a in (t0, t1, rec0, rec1))
+        d_dir = None if d["direction"] is None else dev(codec, d["direction"])
         full = B.bi_tiles(oracle, t0, t1, d["mv0"], d["mv1"], d["direction"], d["wp"], w, h, base)
         for planes in (1, 2, 3):
-            d_pred = _dev(codec, base)
-            _run(codec, codec.motion_comp_bi_qpel_dev, d_t0.ptr, d_t1.ptr, d_m0.ptr, d_m1.ptr, w, h, d_pred.ptr, d_dir.ptr if d_dir else 0, wp, planes)
+            d_pred = dev(codec, base)
+            run(codec, codec.motion_comp_bi_qpel_dev, d_t0.ptr, d_t1.ptr, d_m0.ptr, d_m1.ptr, w, h, d_pred.ptr, d_dir.ptr if d_dir else 0, wp, planes)
             _same(d_pred.download(np.uint8, base.size), TB._only(full, base, planes), (what, "planes", planes))
         _unchanged([(d_t0, t0), (d_t1, t1), (d_m0, rec0), (d_m1, rec1)] + ([(d_dir, d["direction"])] if d_dir else []), (what, "mc"))
         # the three costs and the direction; either output alone where the case draws it
         cur, ref0, ref1, mv0, mv1 = d["decision"]
-        ct, r0, r1 = (TP._tiles(oracle, p, *TB._chroma_for(w, h, seed + 4 + i), seed + 7 + i) for i, p in enumerate((cur, ref0, ref1)))
-        rec0, rec1 = TP._records(mv0, 0xFFFFFFFF), TP._records(mv1, 0xFFFFFFFF)
+        ct, r0, r1 = (_tiles(oracle, (p, *TB._chroma_for(w, h, seed + 4 + i)), seed + 7 + i) for i, p in enumerate((cur, ref0, ref1)))
+        rec0, rec1 = records(mv0, 0xFFFFFFFF), records(mv1, 0xFFFFFFFF)
         want_costs, want_dir = B.costs3(oracle, cur, ref0, ref1, mv0, mv1, d["wp"], c["bi_penalty"])
-        d_c, d_r0, d_r1, d_m0, d_m1 = (_dev(codec, a) for a in (ct, r0, r1, rec0, rec1))
+        d_c, d_r0, d_r1, d_m0, d_m1 = (dev(codec, a) for a in (ct, r0, r1, rec0, rec1))
         with_costs, with_dir = "d_costs of the cost call" not in null, "d_dir of the cost call" not in null
         d_k, f_k = _output(codec, nb * 12, seed + 10)
         d_d, f_d = _output(codec, nb, seed + 11)
-        _run(codec, codec.satd8x8_bi_costs_dev, d_c.ptr, d_r0.ptr, d_r1.ptr, w, h, d_m0.ptr, d_m1.ptr, d_k.ptr if with_costs else 0, d_d.ptr if with_dir else 0, wp,
+        run(codec, codec.satd8x8_bi_costs_dev, d_c.ptr, d_r0.ptr, d_r1.ptr, w, h, d_m0.ptr, d_m1.ptr, d_k.ptr if with_costs else 0, d_d.ptr if with_dir else 0, wp,
              c["bi_penalty"])
         _owned(d_k, f_k, nb * 12 if with_costs else 0, np.uint32, want_costs if with_costs else np.zeros(0, np.uint32), (what, "costs"))
         _owned(d_d, f_d, nb if with_dir else 0, np.uint8, want_dir if with_dir else np.zeros(0, np.uint8), (what, "direction"))
@@ -422,13 +421,13 @@ def test_bipred(codec, oracle):
         # the refinement of one list against the other; in place (d_best == d_int) where the case draws it
         cur, fix, ref, mv_fix, mv_int = d["refine"]
         want_mv, want_cost, want_all = B.refine_bi(oracle, cur, fix, mv_fix, ref, mv_int, c["list"], d["wp"])
-        ct, ft, rt = (TP._tiles(oracle, p, *TB._chroma_for(w, h, seed + 12 + i), seed + 15 + i) for i, p in enumerate((cur, fix, ref)))
-        rec_fix, rec_int = TP._records(mv_fix, 0xFFFFFFFF), TP._records(mv_int, 0xFFFFFFFF)
-        d_c, d_f, d_r, d_mf, d_int = (_dev(codec, a) for a in (ct, ft, rt, rec_fix, rec_int))
+        ct, ft, rt = (_tiles(oracle, (p, *TB._chroma_for(w, h, seed + 12 + i)), seed + 15 + i) for i, p in enumerate((cur, fix, ref)))
+        rec_fix, rec_int = records(mv_fix, 0xFFFFFFFF), records(mv_int, 0xFFFFFFFF)
+        d_c, d_f, d_r, d_mf, d_int = (dev(codec, a) for a in (ct, ft, rt, rec_fix, rec_int))
         d_best, f_best = (d_int, None) if c["inplace"] else _output(codec, nb * 8, seed + 18)
         d_all, f_all = _output(codec, nb * 196, seed + 19)
         with_all = "d_costs" not in null
-        _run(codec, codec.satd8x8_refine_bi_qpel_dev, d_c.ptr, d_f.ptr, d_mf.ptr, d_r.ptr, d_int.ptr, c["list"], w, h, d_best.ptr, d_all.ptr if with_all else 0, wp)
+        run(codec, codec.satd8x8_refine_bi_qpel_dev, d_c.ptr, d_f.ptr, d_mf.ptr, d_r.ptr, d_int.ptr, c["list"], w, h, d_best.ptr, d_all.ptr if with_all else 0, wp)
         got_mv, got_cost = TP._unpack(d_best.download(np.uint8, nb * 8), nb)
         _same(got_mv, want_mv, (what, "refined vectors"))
         _same(got_cost, want_cost, (what, "refined costs"))
@@ -448,9 +447,9 @@ def test_seeded(codec, oracle):
         best, j, _ = E.search(oracle, cur, ref, seeds, c["seed_scale"], c["centres"], c["range"], c["lam"])
         got, got_j = TE.seeded(codec, E.tiles_of(oracle, cur, 1), E.tiles_of(oracle, ref, 2), w, h, seeds, c["seed_scale"], c["centres"], c["range"], c["lam"],
                                with_j="d_j" not in c["null"], guard_seed=c["seed"] % 1000)
-        TE._same(got, best, (what, "d_best"))
+        same(got, best, (what, "d_best"))
         if got_j is not None:
-            TE._same(got_j, j, (what, "d_j"))
+            same(got_j, j, (what, "d_j"))
 
 
 # ---- RDOQ and the level rate ----------------------------------------------------------------------------------------------------------------

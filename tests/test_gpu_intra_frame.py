@@ -10,11 +10,10 @@ import pytest
 import _intra_frame_ref as R
 import _quant_ref as Q
 import x266_amd
-from _arena import Arena
+from _dev import EINVAL, arena_slots, dev, displacements, noise, run, sync_or_exit, tile_written
 from _util import splitmix64
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 NAMES = ("xIntra32RefsFromTilesGpu", "xIntra32CodeFrameGpu")
 
 
@@ -31,41 +30,14 @@ def test_library_exports_and_binds_the_two_calls():
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------------------------------
-def _noise(n, seed):
-    return (splitmix64(seed, 0, n) & np.uint64(255)).astype(np.uint8)
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _run(codec, fn, *args, **kw):
-    """a ..._dev call that must succeed, then a sync; a device error ends the session"""
-    try:
-        fn(*args, **kw)
-    except x266_amd.X266Error:
-        _sync_or_exit(codec, -2)
-        raise
-    _sync_or_exit(codec, 0, kw.get("stream") or None)
-
-
 class Frame:
     """the device buffers of one xIntra32CodeFrameGpu call over a random pre-fill, and what they hold afterwards"""
 
     def __init__(self, codec, cur, w, h, seed=700):
         self.codec, self.w, self.h, self.n = codec, w, h, codec.ctu_count(w, h)
-        self.cur, self.base = np.ascontiguousarray(cur, np.uint8), _noise(w * h * 2, seed)
-        self.fill = {"level": _noise(self.n * 12288, seed + 1), "nnz": _noise(self.n * 24, seed + 2), "mode": _noise(self.n * 6, seed + 3)}
-        self.d_cur = _dev(codec, self.cur)
+        self.cur, self.base = np.ascontiguousarray(cur, np.uint8), noise(w * h * 2, seed)
+        self.fill = {"level": noise(self.n * 12288, seed + 1), "nnz": noise(self.n * 24, seed + 2), "mode": noise(self.n * 6, seed + 3)}
+        self.d_cur = dev(codec, self.cur)
         self.d_recon, self.d_level = codec.alloc(w * h * 2), codec.alloc(self.n * 12288)
         self.d_nnz, self.d_mode = codec.alloc(max(self.n * 24, 16)), codec.alloc(max(self.n * 6, 16))
         self.reset()
@@ -82,7 +54,7 @@ class Frame:
 
     def code(self, **kw):
         self.reset()
-        _run(self.codec, self.enqueue, **kw)
+        run(self.codec, self.enqueue, **kw)
         return self.results()
 
     def results(self):
@@ -108,15 +80,15 @@ class Frame:
 def test_gather_against_the_statement(codec, oracle, w, h):
     planes = R.case("noise", w, h, seed=w + h)
     t = R.tiles(oracle, planes, 50 + w)
-    d_t = _dev(codec, t)
+    d_t = dev(codec, t)
     for comp in range(3):
         want = R.refs_from_planes(planes, w, h, comp)
-        d_refs = _dev(codec, _noise(want.size, 51 + comp))
-        _run(codec, codec.intra32_refs_from_tiles_dev, d_t.ptr, w, h, comp, d_refs.ptr)
+        d_refs = dev(codec, noise(want.size, 51 + comp))
+        run(codec, codec.intra32_refs_from_tiles_dev, d_t.ptr, w, h, comp, d_refs.ptr)
         got = d_refs.download(np.uint8, want.size).reshape(want.shape)
         assert not got[:, 129:].any(), comp                                 # the reserved bytes are written as 0
         assert np.array_equal(got, want), comp
-        assert np.array_equal(codec.intra32_refs_from_tiles(t, w, h, comp, base=_noise(want.size, 3)), want), comp
+        assert np.array_equal(codec.intra32_refs_from_tiles(t, w, h, comp, base=noise(want.size, 3)), want), comp
     assert np.array_equal(d_t.download(np.uint8, t.size), t)
 
 
@@ -133,7 +105,7 @@ def test_code_frame_against_the_statement(codec, oracle, w, h, kind):
     qps = (splitmix64(61 + w, 0, 6 * f.n) % np.uint64(70)).astype(np.uint8)    # bytes above 51 are clamped
     qps[0] = 69
     want = R.code_frame(oracle, planes, w, h, qps, 0, 256)
-    d_qps = _dev(codec, qps)
+    d_qps = dev(codec, qps)
     f.check(oracle, f.code(qps=d_qps.ptr, qp=99, rounding=256), want, "d_qp")      # the scalar qp is not looked at
     f.check(oracle, f.code(qps=d_qps.ptr, qp=0, rounding=256, nnz=False), want, "d_nnz NULL", nnz=False)
     assert np.array_equal(d_qps.download(np.uint8, qps.size), qps)
@@ -152,7 +124,7 @@ def test_modes_given(codec, oracle, w, h):
     decided = R.coded(oracle, "oriented", w, h, 22, 171)
     given = decided.modes.copy()
     given[:, 5] = 35 + (np.arange(f.n) % 200)                               # entry 5 is ignored
-    d_in = _dev(codec, given)
+    d_in = dev(codec, given)
     f.check(oracle, f.code(mode_in=d_in.ptr), decided, "decided modes")
     assert np.array_equal(d_in.download(np.uint8, given.size), given.ravel())
     rnd = (splitmix64(63 + w, 0, 6 * f.n) % np.uint64(35)).astype(np.uint8).reshape(f.n, 6)
@@ -163,7 +135,7 @@ def test_modes_given(codec, oracle, w, h):
     # in place: d_mode == d_mode_in
     f.reset()
     f.d_mode.upload(rnd)
-    _run(codec, f.enqueue, qp=37, rounding=256, mode_in=f.d_mode.ptr)
+    run(codec, f.enqueue, qp=37, rounding=256, mode_in=f.d_mode.ptr)
     f.check(oracle, f.results(), want, "in place")
 
 
@@ -176,23 +148,23 @@ def test_cross_check_on_the_device(codec, oracle, kind):
     w, h = 192, 128
     f = Frame(codec, R.tiles(oracle, R.case(kind, w, h), 64), w, h)
     qps = (splitmix64(65, 0, 6 * f.n) % np.uint64(56)).astype(np.uint8)
-    d_qps = _dev(codec, qps)
+    d_qps = dev(codec, qps)
     level, cnt, mode, recon = f.code(qps=d_qps.ptr, qp=0, rounding=171)
     n = f.n
     pred = np.zeros((n, 6, 1024), np.uint8)
     for comp in range(3):
         sets = n * (4 if comp == 0 else 1)
-        d_refs, d_modes, d_pred = codec.alloc(sets * 144), _dev(codec, mode[:, :4] if comp == 0 else mode[:, 3 + comp]), codec.alloc(sets * 1024)
-        _run(codec, codec.intra32_refs_from_tiles_dev, f.d_recon.ptr, w, h, comp, d_refs.ptr)
-        _run(codec, codec.intra32_predict_dev, d_refs.ptr, d_modes.ptr, 0, d_pred.ptr, sets)
+        d_refs, d_modes, d_pred = codec.alloc(sets * 144), dev(codec, mode[:, :4] if comp == 0 else mode[:, 3 + comp]), codec.alloc(sets * 1024)
+        run(codec, codec.intra32_refs_from_tiles_dev, f.d_recon.ptr, w, h, comp, d_refs.ptr)
+        run(codec, codec.intra32_predict_dev, d_refs.ptr, d_modes.ptr, 0, d_pred.ptr, sets)
         p = d_pred.download(np.uint8, sets * 1024)
         if comp == 0:
             pred[:, :4] = p.reshape(n, 4, 1024)
         else:
             pred[:, 3 + comp] = p.reshape(n, 1024)
-    d_predframe = _dev(codec, oracle.conv_input_fmt(*Q._planes_of_regions(pred.reshape(-1, 6, 32, 32), w, h)))
-    d_l, d_n, d_r = codec.alloc(n * 12288), codec.alloc(n * 24), _dev(codec, f.base)
-    _run(codec, codec.dct32_code_ctu_tiles_dev, f.d_cur.ptr, d_predframe.ptr, w, h, d_qps.ptr, 0, 171, d_l.ptr, d_n.ptr, d_r.ptr)
+    d_predframe = dev(codec, oracle.conv_input_fmt(*Q._planes_of_regions(pred.reshape(-1, 6, 32, 32), w, h)))
+    d_l, d_n, d_r = codec.alloc(n * 12288), codec.alloc(n * 24), dev(codec, f.base)
+    run(codec, codec.dct32_code_ctu_tiles_dev, f.d_cur.ptr, d_predframe.ptr, w, h, d_qps.ptr, 0, 171, d_l.ptr, d_n.ptr, d_r.ptr)
     assert np.array_equal(d_l.download(np.int16, n * 6144).reshape(n, 6, 1024), level)
     assert np.array_equal(d_n.download(np.uint32, n * 6).reshape(n, 6), cnt)
     assert np.array_equal(d_r.download(np.uint8, w * h * 2), recon)
@@ -206,7 +178,7 @@ def test_graph_replay_and_created_stream(codec, oracle, given):
     f = Frame(codec, R.tiles(oracle, R.case("oriented", w, h), 66), w, h)
     eager = f.code(qp=22, rounding=171)
     f.check(oracle, eager, R.coded(oracle, "oriented", w, h, 22, 171), "eager")
-    d_in = _dev(codec, eager[2])
+    d_in = dev(codec, eager[2])
     kw = dict(qp=22, rounding=171, mode_in=d_in.ptr if given else 0)
     st = codec.stream_create()
     try:
@@ -220,7 +192,7 @@ def test_graph_replay_and_created_stream(codec, oracle, given):
             for _ in range(2):
                 f.reset()
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 for x, y in zip(eager, f.results()):
                     assert np.array_equal(x, y)
         finally:
@@ -248,23 +220,9 @@ def arena_case(oracle):
             "d_level": want.levels.ravel(), "d_nnz": want.nnz.ravel(), "d_mode": want.modes.ravel(), "coded": want, "oracle": oracle}
 
 
-def _displacements(name, halved=None):
-    """every pointer at exactly its documented alignment and no more (odd multiples, varying between the buffers); `halved`: that one
-    at half its alignment"""
-    return {p: (align // 2, align // 2) if p == halved else (align * (2 * i + 1), align) for i, (p, align) in enumerate(PTRS[name].items())}
-
-
 def _arena(codec, arena_case, name, disp, guard_seed):
-    a, s = Arena(codec), {}
-    for i, p in enumerate(PTRS[name]):
-        if p in OUTPUTS[name]:
-            nbytes, written = (AW * AH * 2, np.zeros((AW * AH * 2 // 512, 512), bool)) if p == "d_recon" else (arena_case[p].nbytes, None)
-            if written is not None:
-                written[:, :384] = True
-            s[p] = a.output(p, nbytes, disp[p][1], disp[p][0], written=None if written is None else written.ravel())
-        else:
-            s[p] = a.input(p, arena_case[p], disp[p][1], disp[p][0], guard_seed + i)
-    return a, s
+    return arena_slots(codec, PTRS[name], OUTPUTS[name], arena_case, disp, guard_seed, written={"d_recon": tile_written(AW * AH // 256, "both")},
+                       sizes={"d_recon": AW * AH * 2})
 
 
 def _call_arena(codec, name, s):
@@ -274,7 +232,7 @@ def _call_arena(codec, name, s):
     else:
         rc = L.xIntra32CodeFrameGpu(codec.ctx, s["d_cur"].ptr, AW, AH, s["d_qp"].ptr, 0, 171, s["d_mode_in"].ptr, s["d_level"].ptr, s["d_nnz"].ptr,
                                     s["d_mode"].ptr, s["d_recon"].ptr, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -283,7 +241,7 @@ def _call_arena(codec, name, s):
 def test_minimum_alignment(codec, arena_case, name):
     results = []
     for guard_seed in (31, 51):
-        a, s = _arena(codec, arena_case, name, _displacements(name), guard_seed)
+        a, s = _arena(codec, arena_case, name, displacements(PTRS[name]), guard_seed)
         assert _call_arena(codec, name, s) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()                                                     # guards, m_I of d_recon, inputs
         for p in OUTPUTS[name]:
@@ -300,7 +258,7 @@ def test_minimum_alignment(codec, arena_case, name):
 @gpu
 @pytest.mark.parametrize("name,ptr", [(n, p) for n in NAMES for p in PTRS[n] if PTRS[n][p] > 1])
 def test_half_alignment_is_rejected(codec, arena_case, name, ptr):
-    a, s = _arena(codec, arena_case, name, _displacements(name, halved=ptr), 33)
+    a, s = _arena(codec, arena_case, name, displacements(PTRS[name], halved=ptr), 33)
     assert _call_arena(codec, name, s) == EINVAL
     assert name.encode() in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
@@ -312,7 +270,7 @@ def test_argument_errors(codec):
     """one refused call per rule, for both calls; a refused call launches nothing and names itself"""
     L, ctx = codec.L, codec.ctx
     buf = codec.alloc(8 << 20)
-    fill = _noise(8 << 20, 95)
+    fill = noise(8 << 20, 95)
     buf.upload(fill)
     cur, rec, lvl = buf.ptr + (1 << 20), buf.ptr + (2 << 20), buf.ptr + (3 << 20)   # 64x64: tile arrays of 8 KiB, 12 KiB of levels
     nnz, mode, min_, qps, refs = (buf.ptr + (4 << 20) + 4096 * i for i in range(5))  # 24, 6, 6, 6 bytes; 4 sets of 144
@@ -349,5 +307,5 @@ def test_argument_errors(codec):
     for rc in (L.xIntra32RefsFromTilesGpu(ctx, cur, 64, 64, 2, refs, None),
                L.xIntra32CodeFrameGpu(ctx, *code(qp=0, rounding=0, nnz=None), None), L.xIntra32CodeFrameGpu(ctx, *code(qp=51, rounding=511), None),
                L.xIntra32CodeFrameGpu(ctx, *code(qps=qps, qp=99, min_=min_), None), L.xIntra32CodeFrameGpu(ctx, *code(min_=mode), None)):
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)

@@ -11,10 +11,10 @@ import _aq_ref as A
 import _la_ref as R
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, call_struct, dev, same, sync_or_exit
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 try:
     CHUNK = x266_amd.la_totals_chunk()                                      # the totals' step, as the implementation exposes it
 except (x266_amd.X266Error, AttributeError):                                # collected without a built library: the GPU tests then fail on their own
@@ -27,23 +27,6 @@ SIZES = [(32, 32), (64, 32), (32, 64), (96, 160), (160, 96)]
 TALL = (32, 8 * (CHUNK + 4))
 KINDS = ["zeros", "ones", "random", "hramp", "vramp", "checker"]
 M_I = np.arange(512) >= 384                                                 # a tile's info bytes: no lookahead call reads or writes them
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _call(codec, name, p, stream=None):
-    rc = getattr(codec.L, name)(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, (name, codec.L.xHipLastError(codec.ctx))
-
-
-def _same(got, want, what):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad[:8], got[bad[:8]], want[bad[:8]])
 
 
 @functools.lru_cache(None)
@@ -65,9 +48,9 @@ def downscale(codec, tiles, w, h, want, stream=None, guard_seed=41):
     a = Arena(codec)
     src = a.input("d_src", tiles, 16, DISP["d_src"], guard_seed)
     low = a.output("d_low", want.size, 16, DISP["d_low"], written=~np.tile(M_I, want.size // 512))
-    _call(codec, "xLaDownscaleGpu", codec.la_params(w, h, -1, -1, 99, 99, d_src=src.ptr, d_low=low.ptr), stream)    # it reads no scalar
+    call_struct(codec, "xLaDownscaleGpu", codec.la_params(w, h, -1, -1, 99, 99, d_src=src.ptr, d_low=low.ptr), stream)    # it reads no scalar
     got = a.check()["d_low"].reshape(-1, 512)                               # guard bands, the input, and m_I untouched
-    _same(got[:, :384], want.reshape(-1, 512)[:, :384], "d_low")
+    same(got[:, :384], want.reshape(-1, 512)[:, :384], "d_low")
     return got
 
 
@@ -76,11 +59,11 @@ def intra_costs(codec, low, w, h, want_cost, want_mode, with_mode=True, guard_se
     d_low = a.input("d_low", low, 16, DISP["d_low"], guard_seed)
     d_intra = a.output("d_intra", 4 * want_cost.size, 4, DISP["d_intra"])
     d_mode = a.output("d_mode", want_cost.size, 1, DISP["d_mode"]) if with_mode else None
-    _call(codec, "xLaIntraCostsGpu", codec.la_params(w, h, -1, -1, 99, 99, d_low=d_low.ptr, d_intra=d_intra.ptr, d_mode=d_mode.ptr if with_mode else 0))
+    call_struct(codec, "xLaIntraCostsGpu", codec.la_params(w, h, -1, -1, 99, 99, d_low=d_low.ptr, d_intra=d_intra.ptr, d_mode=d_mode.ptr if with_mode else 0))
     got = a.check()
-    _same(got["d_intra"].view(np.uint32), want_cost, "d_intra")
+    same(got["d_intra"].view(np.uint32), want_cost, "d_intra")
     if with_mode:
-        _same(got["d_mode"], want_mode, "d_mode")
+        same(got["d_mode"], want_mode, "d_mode")
 
 
 def frame_cost(codec, intra, mode, l0, l1, w, h, penalty, stream=None, guard_seed=45):
@@ -90,9 +73,9 @@ def frame_cost(codec, intra, mode, l0, l1, w, h, penalty, stream=None, guard_see
         s[name] = 0 if data is None else a.input(name, np.ascontiguousarray(data).view(np.uint8), PTRS[name], DISP[name], guard_seed + len(s)).ptr
     block = a.output("d_block", 16 * intra.size, 16, DISP["d_block"])
     total = a.output("d_total", 64, 8, DISP["d_total"])
-    _call(codec, "xLaFrameCostGpu", codec.la_params(w, h, penalty, -1, 99, 99, d_block=block.ptr, d_total=total.ptr, **s), stream)
+    call_struct(codec, "xLaFrameCostGpu", codec.la_params(w, h, penalty, -1, 99, 99, d_block=block.ptr, d_total=total.ptr, **s), stream)
     got = a.check()
-    _same(got["d_block"].view(R.BLOCK_DTYPE), want, "d_block")
+    same(got["d_block"].view(R.BLOCK_DTYPE), want, "d_block")
     assert got["d_total"].view(np.int64).tolist() == want_tot.tolist(), (got["d_total"].view(np.int64), want_tot)
     return want, want_tot
 
@@ -112,11 +95,11 @@ def propagate(codec, rec, prop, ref0, ref1, w, h, stream=None, guard_seed=47):
             slots[name].image[start:start + 8 * rec.size] = np.ascontiguousarray(acc, np.uint64).view(np.uint8)
             slots[name].buf.upload(slots[name].image)
             s[name] = slots[name].ptr
-    _call(codec, "xLaPropagateGpu", codec.la_params(w, h, -1, -1, 99, 99, **s), stream)
+    call_struct(codec, "xLaPropagateGpu", codec.la_params(w, h, -1, -1, 99, 99, **s), stream)
     got = a.check()                                                         # the guard bands prove that nothing outside the grid was written
     for name, acc in zip(("d_prop_ref0", "d_prop_ref1"), want):
         if acc is not None:
-            _same(got[name].view(np.uint64), acc, name)
+            same(got[name].view(np.uint64), acc, name)
     return want
 
 
@@ -132,12 +115,12 @@ def tree_qp(codec, rec, prop, aq, w, h, strength, qp=30, chroma=0, offset=True, 
         s["d_offset"] = a.output("d_offset", want_off.nbytes, 2, DISP["d_offset"]).ptr
     if qps:
         s["d_qp"] = a.output("d_qp", want_qp.nbytes, 1, DISP["d_qp"]).ptr
-    _call(codec, "xLaTreeQpGpu", codec.la_params(w, h, -1, strength, qp, chroma, **s))
+    call_struct(codec, "xLaTreeQpGpu", codec.la_params(w, h, -1, strength, qp, chroma, **s))
     got = a.check()
     if offset:
-        _same(got["d_offset"].view(np.int16), want_off, "d_offset")
+        same(got["d_offset"].view(np.int16), want_off, "d_offset")
     if qps:
-        _same(got["d_qp"], want_qp, "d_qp")
+        same(got["d_qp"], want_qp, "d_qp")
     return want_off, want_qp
 
 
@@ -206,9 +189,9 @@ def test_propagate_with_the_vectors_of_a_real_search(codec, w, h):
     n = want.size
     d_cur, d_ref, d_best = codec._upload(cur_low), codec._upload(ref_low), codec.alloc(8 * n)
     codec.satd_search_from_tiles_dev(d_cur.ptr, d_ref.ptr, w // 2, h // 2, 3, d_best.ptr)   # the lowres frame is an ordinary tiled frame
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     got = d_best.download(np.uint8, 8 * n).view(R.ME_DTYPE)
-    _same(got, want, "the search of the lowres frames")
+    same(got, want, "the search of the lowres frames")
     assert (got["mvx"] != 0).any() and (got["mvy"] != 0).any()
     cost, mode = R.intra_costs(cur_low, w, h)
     rec, tot = frame_cost(codec, cost, mode, got, None, w, h, 0)
@@ -248,7 +231,7 @@ def test_propagate_contention_edges_and_large_values(codec):
     none0, only1 = propagate(codec, rec, prop, None, start, w, h)
     assert none0 is None and none1 is None and np.array_equal(only0, a[0]) and np.array_equal(only1, a[1])
     p = codec.la_params(w, h, d_block=codec._upload(rec.view(np.uint8)).ptr)
-    _call(codec, "xLaPropagateGpu", p)                                       # both NULL: accepted, nothing to do
+    call_struct(codec, "xLaPropagateGpu", p)                                       # both NULL: accepted, nothing to do
 
 
 def test_two_runs_on_two_streams_give_identical_bytes(codec):
@@ -339,21 +322,21 @@ def test_the_chain_in_one_graph(codec):
                 d["ref0"].upload(np.zeros(n, np.uint64))                     # the caller zeroes an accumulator
                 d["block"].upload(np.full(16 * n, 0x5A, np.uint8))
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 cur_low, ref_low = R.downscale(cur, w, h), R.downscale(other, w, h)
                 cost, mode = R.intra_costs(cur_low, w, h)
                 best = R.search(cur_low, ref_low, w, h, rng)
                 rec, tot = R.frame_cost(cost, mode, best, None, 200)
                 ref0, _ = R.propagate(rec, prop, np.zeros(n, np.uint64), None, w, h)
                 off, qp = R.tree_qp(rec, prop, None, w, h, 512, 30, -1)
-                _same(d["cur_low"].download(np.uint8, n * 128).reshape(-1, 512)[:, :384], cur_low[:, :384], "cur_low")
-                _same(d["intra"].download(np.uint32, n), cost, "intra")
-                _same(d["best"].download(np.uint8, 8 * n).view(R.ME_DTYPE), best, "best")
-                _same(d["block"].download(np.uint8, 16 * n).view(R.BLOCK_DTYPE), rec, "block")
+                same(d["cur_low"].download(np.uint8, n * 128).reshape(-1, 512)[:, :384], cur_low[:, :384], "cur_low")
+                same(d["intra"].download(np.uint32, n), cost, "intra")
+                same(d["best"].download(np.uint8, 8 * n).view(R.ME_DTYPE), best, "best")
+                same(d["block"].download(np.uint8, 16 * n).view(R.BLOCK_DTYPE), rec, "block")
                 assert d["total"].download(np.int64, 8).tolist() == tot.tolist()
-                _same(d["ref0"].download(np.uint64, n), ref0, "ref0")
-                _same(d["off"].download(np.int16, n), off, "off")
-                _same(d["qp"].download(np.uint8, 6 * n_ctu), qp, "qp")
+                same(d["ref0"].download(np.uint64, n), ref0, "ref0")
+                same(d["off"].download(np.int16, n), off, "off")
+                same(d["qp"].download(np.uint8, 6 * n_ctu), qp, "qp")
         finally:
             codec.graph_free(graph)
     finally:
@@ -363,7 +346,7 @@ def test_the_chain_in_one_graph(codec):
 # ---- 6. end to end ----------------------------------------------------------------------------------------------------------------------------
 def test_the_tree_qp_map_feeds_the_fused_coding_call(codec):
     """xLaTreeQpGpu's d_qp goes into xDct32CodeCtuTilesGpu without leaving the device; the levels are those of the restatement's bytes"""
-    from test_gpu_quant import _dev, _tiles_mix
+    from test_gpu_quant import _tiles_mix
     w, h = 64, 64
     n, n_ctu = 16, 1
     cur = R.frame("smooth", w, h, 4)
@@ -371,7 +354,7 @@ def test_the_tree_qp_map_feeds_the_fused_coding_call(codec):
     low = R.downscale(cur, w, h)
     cost, mode = R.intra_costs(low, w, h)
     prop = (np.arange(n, dtype=np.uint64) % np.uint64(4)) * np.uint64(400000)        # the right columns were referred to a lot
-    dc, dp, dr = _dev(codec, cur.ravel()), _dev(codec, pred), _dev(codec, base)
+    dc, dp, dr = dev(codec, cur.ravel()), dev(codec, pred), dev(codec, base)
     al = lambda nbytes: codec.alloc(max(nbytes, 16))
     d_low, d_intra, d_block, d_total, d_prop, d_qp = al(n * 128), al(4 * n), al(16 * n), al(64), codec._upload(prop), al(6)
     dl, dn = al(n_ctu * 12288), al(n_ctu * 24)
@@ -382,7 +365,7 @@ def test_the_tree_qp_map_feeds_the_fused_coding_call(codec):
     codec.la_frame_cost_dev(p)
     codec.la_tree_qp_dev(p)
     codec.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, d_qp.ptr, 0, 171, dl.ptr, dn.ptr, dr.ptr)
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     rec, _ = R.frame_cost(cost, None, None, None, 0)
     want_qp = R.tree_qp(rec, prop, None, w, h, 1024, 30, 2)[1]
     assert len(set(want_qp.tolist())) > 2 and want_qp.min() < 30                 # a map, and the tree lowered it
@@ -428,7 +411,7 @@ def test_scene_cut_end_to_end(codec):
         if want:
             assert tot[3] > 0 and tot[2] > 0                                 # the penalty leaves list-0 blocks winning somewhere
         got_rec, got_tot = _p_totals(codec, cur, prev, w, h, penalty)
-        _same(got_rec, rec, "d_block")
+        same(got_rec, rec, "d_block")
         assert got_tot.tolist() == tot.tolist()
         assert x266_amd.scene_cut_from_totals(got_tot, 102, 100, 25, 250) == bool(want)
 
@@ -502,7 +485,7 @@ def test_argument_errors(codec):
     refused("xLaTreeQpGpu", d_offset=0, d_qp=0)
     for change in (dict(strength_q8=-1), dict(strength_q8=1025), dict(qp=-1), dict(qp=52), dict(chroma_qp_offset=-13), dict(chroma_qp_offset=13)):
         refused("xLaTreeQpGpu", **change)
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     assert np.array_equal(buf.download(np.uint8, fill.size), fill)          # nothing was launched
     # the edges of what is accepted: every optional field NULL, every scalar at either end of its range, the fields a call does not read garbage
     junk = dict(d_src=3, d_inter0=5, d_aq_offset=1, intra_penalty=-7, strength_q8=-7, qp=99, chroma_qp_offset=99)
@@ -510,19 +493,19 @@ def test_argument_errors(codec):
     image = fill.copy()
     image[M:M + n * 512] = tiles.ravel()
     buf.upload(image)
-    _call(codec, "xLaDownscaleGpu", codec.la_params(**dict(good, **{k: v for k, v in junk.items() if k != "d_src"})))
-    _call(codec, "xLaIntraCostsGpu", codec.la_params(**dict(good, d_mode=0, **{k: v for k, v in junk.items() if k != "d_mode"})))
+    call_struct(codec, "xLaDownscaleGpu", codec.la_params(**dict(good, **{k: v for k, v in junk.items() if k != "d_src"})))
+    call_struct(codec, "xLaIntraCostsGpu", codec.la_params(**dict(good, d_mode=0, **{k: v for k, v in junk.items() if k != "d_mode"})))
     for penalty in (0, 65535):
-        _call(codec, "xLaFrameCostGpu", codec.la_params(**dict(good, d_mode=0, d_inter0=0, d_inter1=0, d_src=3, intra_penalty=penalty, strength_q8=-7, qp=99)))
-    _call(codec, "xLaPropagateGpu", codec.la_params(**dict(good, d_prop=0, d_prop_ref1=0, **junk)))
-    _call(codec, "xLaTreeQpGpu", codec.la_params(**dict(good, d_prop=0, d_aq_offset=0, d_offset=0, d_src=3, strength_q8=0, qp=0, chroma_qp_offset=-12)))
-    _call(codec, "xLaTreeQpGpu", codec.la_params(**dict(good, d_prop=0, d_aq_offset=0, d_qp=0, d_src=3, strength_q8=1024, qp=51, chroma_qp_offset=12)))
+        call_struct(codec, "xLaFrameCostGpu", codec.la_params(**dict(good, d_mode=0, d_inter0=0, d_inter1=0, d_src=3, intra_penalty=penalty, strength_q8=-7, qp=99)))
+    call_struct(codec, "xLaPropagateGpu", codec.la_params(**dict(good, d_prop=0, d_prop_ref1=0, **junk)))
+    call_struct(codec, "xLaTreeQpGpu", codec.la_params(**dict(good, d_prop=0, d_aq_offset=0, d_offset=0, d_src=3, strength_q8=0, qp=0, chroma_qp_offset=-12)))
+    call_struct(codec, "xLaTreeQpGpu", codec.la_params(**dict(good, d_prop=0, d_aq_offset=0, d_qp=0, d_src=3, strength_q8=1024, qp=51, chroma_qp_offset=12)))
     now = buf.download(np.uint8, fill.size)
     at = lambda name, dtype=np.uint8: now[(names.index(name) + 1) * M:(names.index(name) + 1) * M + extent[name]].view(dtype)
-    _same(at("d_low").reshape(-1, 512)[:, :384], low[:, :384], "d_low")
-    _same(at("d_intra", np.uint32), cost, "d_intra")
+    same(at("d_low").reshape(-1, 512)[:, :384], low[:, :384], "d_low")
+    same(at("d_intra", np.uint32), cost, "d_intra")
     rec, tot = R.frame_cost(cost, None, None, None, 65535)
-    _same(at("d_block", R.BLOCK_DTYPE), rec, "d_block")
+    same(at("d_block", R.BLOCK_DTYPE), rec, "d_block")
     assert at("d_total", np.int64).tolist() == tot.tolist()
     assert np.array_equal(at("d_prop_ref0"), image[(names.index("d_prop_ref0") + 1) * M:][:8 * n])     # every block is intra: nothing is handed on
     assert not at("d_offset", np.int16).any() and (at("d_qp")[:4 * n_ctu] == 0).all()

@@ -21,11 +21,11 @@ import pytest
 
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, sync_or_exit
 from _util import ROOT, extremes_np, fullrange_np, residual_np
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 MIXES = (residual_np, fullrange_np, extremes_np)
 N_BIG = 3077                                   # "a few thousand blocks with a ragged tail": 3077 = 5 mod 6, 8, 12, 16, 24 and odd
 N_SATD = 2400                                  # blocks of SATD data per mix (the largest case: 2 x 4 waves x 8 groups x 32 + 225 = 2273)
@@ -47,11 +47,6 @@ SATD, SAD = TABLES["kSatdCands"], TABLES["kSadCands"]
 SAD_EDGES = (8, 16, 32, 64)
 # forced launches per (family, candidate) as read back from the library by the cases of this file
 TALLY = collections.Counter()
-
-
-def _sync(cd, stream=0):
-    if cd.L.xHipStreamSync(cd.ctx, stream) != 0:                         # a device error: nothing more is started on this GPU
-        pytest.exit("device error: %s" % cd.L.xHipLastError(cd.ctx).decode(), returncode=3)
 
 
 def _launches(cd, family):
@@ -120,7 +115,7 @@ def _fused_case(cd, data, family, k, n, mix, salt):
     s_re = arena.output("d_recon", n * 2048, 16, 0)
     before = _launches(cd, family)
     cd.dct32_fwd_inv_dev(s_in.ptr, s_co.ptr if with_coef else 0, s_re.ptr, n)
-    _sync(cd)
+    sync_or_exit(cd, 0)
     _counted(cd, family, k, before)
     got = arena.check()                                                  # guard bands of all three, the input unchanged
     where = (family, k, FUSED[family][k], "n", n, "mix", mix)
@@ -166,7 +161,7 @@ def _satd_case(cd, data, k, n, mix, salt):
     s_out = arena.output("d_out", n * 4, 4, 0)
     before = _launches(cd, "satd8x8")
     cd.satd8x8_dev(s_in.ptr, s_out.ptr, n)
-    _sync(cd)
+    sync_or_exit(cd, 0)
     _counted(cd, "satd8x8", k, before)
     got = arena.check()["d_out"].view(np.uint32)
     assert np.array_equal(got, want), ("satd8x8", k, SATD[k], "n", n, "mix", mix, np.flatnonzero(got != want)[:8].tolist())
@@ -198,7 +193,7 @@ def _sad_case(cd, edge, a, b):
     s_b = arena.input("d_b", b, 16, 0, 0x3E00 + n)
     s_out = arena.output("d_out", n * 4, 4, 0)
     cd.sad_dev(edge, s_a.ptr, s_b.ptr, s_out.ptr, n)
-    _sync(cd)
+    sync_or_exit(cd, 0)
     return arena.check()["d_out"].view(np.uint32)
 
 
@@ -252,7 +247,7 @@ def test_callers_knobs_and_overlap_keep_the_default_shape(forced, dct_data, satd
             s_co = arena.output("d_coef", n * 2048, 16, 0) if with_coef else None
             s_re = arena.output("d_recon", n * 2048, 16, 0)
             cd.dct32_fwd_inv_dev(s_in.ptr, s_co.ptr if with_coef else 0, s_re.ptr, n)
-            _sync(cd)
+            sync_or_exit(cd, 0)
             got = arena.check()
             assert np.array_equal(got["d_recon"].view(np.int16).reshape(n, 1024), r)
             assert not with_coef or np.array_equal(got["d_coef"].view(np.int16).reshape(n, 1024), z)
@@ -265,7 +260,7 @@ def test_callers_knobs_and_overlap_keep_the_default_shape(forced, dct_data, satd
     for with_coef in (True, False):
         buf.upload(x)
         cd.dct32_fwd_inv_dev(buf.ptr, co.ptr if with_coef else 0, buf.ptr, n)
-        _sync(cd)
+        sync_or_exit(cd, 0)
         assert {f: _launches(cd, f) for f in FUSED} == {f: 1 for f in FUSED}
     # SATD: "satd_variant" 2 (and 1, 3) and the family's launch knobs
     d, want = (a[:777] for a in satd_data[0])
@@ -278,7 +273,7 @@ def test_callers_knobs_and_overlap_keep_the_default_shape(forced, dct_data, satd
             s_in = arena.input("d_diff", d, 16, 0, 0x4E00)
             s_out = arena.output("d_out", 777 * 4, 4, 0)
             cd.satd8x8_dev(s_in.ptr, s_out.ptr, 777)
-            _sync(cd)
+            sync_or_exit(cd, 0)
             assert np.array_equal(arena.check()["d_out"].view(np.uint32), want), (key, value)
             assert _launches(cd, "satd8x8") == 1, (key, value)
         finally:
@@ -322,7 +317,7 @@ def test_refused_past_the_table(forced, dct_data, satd_data):
         _force(cd, k)
         for family, count, call in calls:
             arena, rc = call()
-            _sync(cd)
+            sync_or_exit(cd, 0)
             if k < count:
                 assert rc == 0, (family, k, cd.L.xHipLastError(cd.ctx).decode())
                 arena.check()
@@ -352,7 +347,7 @@ def test_deep_shapes_replayed_from_a_graph(forced, dct_data, k):
     s_co, s_re = arena.output("d_coef", n * 2048, 16, 0), arena.output("d_recon", n * 2048, 16, 0)
     st = cd.stream_create()
     try:
-        _sync(cd)
+        sync_or_exit(cd, 0)
         cd.graph_begin(st)
         cd.dct32_fwd_inv_dev(s_in.ptr, s_co.ptr, s_re.ptr, n, st)          # no timing: the forced shape is what the capture records
         graph = cd.graph_end(st)
@@ -364,7 +359,7 @@ def test_deep_shapes_replayed_from_a_graph(forced, dct_data, k):
                 for s in (s_in, s_co, s_re):
                     s.buf.upload(s.image)                                # fresh input, outputs back to the fill
                 cd.graph_launch(graph, st)
-                _sync(cd, st)
+                sync_or_exit(cd, 0, st)
                 got = arena.check()
                 assert np.array_equal(got["d_coef"].view(np.int16).reshape(n, 1024), z), (k, mix)
                 assert np.array_equal(got["d_recon"].view(np.int16).reshape(n, 1024), r), (k, mix)

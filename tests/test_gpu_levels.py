@@ -9,22 +9,16 @@ import pytest
 import _levels_ref as R
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, call_struct, dev, sync_or_exit
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 try:
     CHUNK = x266_amd.levels_scan_chunk()                                   # the scan's step, as the implementation exposes it
 except x266_amd.X266Error:                                                  # collected without a built library: the GPU tests then fail on their own
     CHUNK = 1024
 PTRS = {"d_level": 16, "d_class": 1, "d_nnz": 4, "d_region": 8, "d_stream": 16, "d_total": 8}
 DISP = {name: align * (2 * i + 1) for i, (name, align) in enumerate(PTRS.items())}          # exactly the documented alignment, no more
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
 
 
 def _ptr(slots, name):
@@ -57,9 +51,7 @@ def pack(codec, lv, cls=None, nnz=None, cap=None, null_stream=False, stream=None
         s["d_stream"] = a.output("d_stream", 2 * cap, 16, DISP["d_stream"], written=np.repeat(written, 2))
     s["d_total"] = a.output("d_total", 16, 8, DISP["d_total"])
     p = codec.levels_params(*[_ptr(s, name) for name in PTRS], n_regions=n, cap_words=0 if null_stream else cap)
-    rc = codec.L.xLevelsPackGpu(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, codec.L.xHipLastError(codec.ctx)
+    call_struct(codec, "xLevelsPackGpu", p, stream)
     got = a.check()                                                         # guard bands, unwritten words, inputs
     rec = got["d_region"].view(R.RECORD_DTYPE)
     total = got["d_total"].view(np.uint64)
@@ -88,7 +80,7 @@ def unpack(codec, rec, words, n, cls=None, cap=None, with_nnz=True, guard_seed=3
         s["d_nnz"] = a.output("d_nnz", 4 * n, 4, DISP["d_nnz"])
     p = codec.levels_params(*[_ptr(s, name) for name in PTRS], n_regions=n, cap_words=cap)
     rc = codec.L.xLevelsUnpackGpu(codec.ctx, ctypes.byref(p), None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     assert rc == 0, codec.L.xHipLastError(codec.ctx)
     got = a.check()
     lv = got["d_level"].view(np.int16).reshape(n, 1024)
@@ -218,10 +210,10 @@ def test_unpack_of_hostile_streams(codec):
 @pytest.mark.parametrize("qp", [22, 37])
 @pytest.mark.parametrize("w,h", [(64, 64), (128, 64)])
 def test_end_to_end_with_the_fused_coding_call(codec, w, h, qp):
-    from test_gpu_quant import _dev, _tiles_mix
+    from test_gpu_quant import _tiles_mix
     n = codec.ctu_count(w, h)
     cur, pred, base = _tiles_mix(w, h, 0x7000 + w), _tiles_mix(w, h, 0x7100 + w), _tiles_mix(w, h, 0x7200 + w)
-    dc, dp, dr = _dev(codec, cur), _dev(codec, pred), _dev(codec, base)
+    dc, dp, dr = dev(codec, cur), dev(codec, pred), dev(codec, base)
     dl, dn = codec.alloc(n * 12288), codec.alloc(n * 24)
     codec.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, 0, qp, 171, dl.ptr, dn.ptr, dr.ptr)
     codec.stream_sync()
@@ -230,7 +222,7 @@ def test_end_to_end_with_the_fused_coding_call(codec, w, h, qp):
     rec, words, total = pack(codec, level, None, nnz)
     assert np.array_equal(rec["n_nz"], nnz)
     back = unpack(codec, rec, words, 6 * n, want=(level, nnz))
-    dz, dr2 = _dev(codec, back), _dev(codec, base)
+    dz, dr2 = dev(codec, back), dev(codec, base)
     codec.quant_regions_dev(1, dz.ptr, dz.ptr, 6 * n, 0, 0, qp, 171)
     codec.dct32_inv_ctu_to_tiles_dev(dz.ptr, dp.ptr, w, h, dr2.ptr)
     codec.stream_sync()
@@ -238,15 +230,15 @@ def test_end_to_end_with_the_fused_coding_call(codec, w, h, qp):
 
 
 def test_end_to_end_with_the_mixed_transform_set(codec):
-    from test_gpu_quant import _bytes, _dev, _tiles_mix
+    from test_gpu_quant import _bytes, _tiles_mix
     w, h = 80, 48                                                            # cut CTUs
     n = codec.ctu_count(w, h)
     cur, pred, base = _tiles_mix(w, h, 0x7400), _tiles_mix(w, h, 0x7401), _tiles_mix(w, h, 0x7402)
     cls, qps = _bytes(6 * n, 0x7403, 15), 20 + _bytes(6 * n, 0x7404, 15)
     cls[[0, 4, 7, 11]] = (cls[[0, 4, 7, 11]] & 12) | np.arange(4, dtype=np.uint8)      # every block size, in luma and in chroma regions
     assert len(set((cls & 3).tolist())) == 4
-    dc, dp, dr, dk, dq = _dev(codec, cur), _dev(codec, pred), _dev(codec, base), _dev(codec, cls), _dev(codec, qps)
-    dz, dn = _dev(codec, np.zeros(n * 6144, np.int16)), codec.alloc(n * 24)
+    dc, dp, dr, dk, dq = dev(codec, cur), dev(codec, pred), dev(codec, base), dev(codec, cls), dev(codec, qps)
+    dz, dn = dev(codec, np.zeros(n * 6144, np.int16)), codec.alloc(n * 24)
     codec.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr, dz.ptr)
     codec.quant_regions_dev(0, dz.ptr, dz.ptr, 6 * n, dk.ptr, dq.ptr, 0, 171, dn.ptr)
     codec.stream_sync()
@@ -257,7 +249,7 @@ def test_end_to_end_with_the_mixed_transform_set(codec):
     recon = dr.download(np.uint8, w * h * 2)
     rec, words, total = pack(codec, level, cls, nnz)
     back = unpack(codec, rec, words, 6 * n, cls, want=(level, nnz))
-    dz2, dr2 = _dev(codec, back), _dev(codec, base)
+    dz2, dr2 = dev(codec, back), dev(codec, base)
     codec.quant_regions_dev(1, dz2.ptr, dz2.ptr, 6 * n, dk.ptr, dq.ptr, 0, 171)
     codec.transform_ctu_to_tiles_dev(dz2.ptr, dk.ptr, dp.ptr, w, h, dr2.ptr)
     codec.stream_sync()
@@ -291,7 +283,6 @@ def test_numpy_conveniences(codec):
 
 # ---- 7. one graph ---------------------------------------------------------------------------------------------------------------------------
 def test_pack_and_unpack_in_one_graph(codec):
-    from test_gpu_quant import _dev
     inputs = [R.mixed(70, seed=s) for s in (5, 6)]
     n, cap = 70, 70 * 1088
     d_lv, d_cls, d_rec, d_str, d_tot = codec.alloc(n * 2048), codec.alloc(n), codec.alloc(n * 32), codec.alloc(cap * 2), codec.alloc(16)
@@ -313,7 +304,7 @@ def test_pack_and_unpack_in_one_graph(codec):
                 d_cls.upload(cls)
                 d_back.upload(np.full(n * 1024, 0x5A5A, np.int16))
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 want_rec, want_stream, want_total = R.pack(lv, cls)
                 assert d_tot.download(np.uint64, 2).tolist() == want_total.tolist()
                 assert np.array_equal(d_rec.download(np.uint8, n * 32).view(R.RECORD_DTYPE), want_rec)
@@ -368,12 +359,12 @@ def test_argument_errors(codec):
                                  ("d_nnz", "d_stream", 2 * cap), ("d_nnz", "d_region", 32 * n), ("d_nnz", "d_class", n)):
         refused("xLevelsUnpackGpu", **{field: good[other] + (extent - 1) // PTRS[field] * PTRS[field]})
         refused("xLevelsUnpackGpu", **{field: good[other]})
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     assert np.array_equal(buf.download(np.uint8, 8 * M), fill)             # nothing was launched
     # the edges of what is accepted: no regions (pack writes the totals alone), optional arrays NULL, d_total NULL in unpack
     for rc in (L.xLevelsUnpackGpu(ctx, ctypes.byref(codec.levels_params(n_regions=0)), None),
                L.xLevelsPackGpu(ctx, ctypes.byref(codec.levels_params(d_total=tot, n_regions=0)), None)):
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)
     now = buf.download(np.uint8, 8 * M)
     assert not now[6 * M:6 * M + 16].any()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from _subpel_ref import _mv_mix                                          # the vector mix, shared with tests/_frame_cases.py
+from _dev import dev, records, sentinels, tiles
 from _util import me_frames, splitmix64
 
 gpu = pytest.mark.gpu
@@ -91,13 +92,6 @@ def _planes_of(kind, w, h, seed):
     return _plane(ku, w, h, seed), _plane(kv, w, h, seed + 1)
 
 
-def _tiles(oracle, y, u, v, seed):
-    """the tile array of three planes with random m_I bytes (which no call may read)"""
-    t = oracle.conv_input_fmt(y, u, v).reshape(-1, 512)
-    t[:, 384:] = (splitmix64(seed, 0, t.shape[0] * 128) & np.uint64(255)).astype(np.uint8).reshape(-1, 128)
-    return t.ravel()
-
-
 def _luma(w, h, seed):
     return (splitmix64(seed, 0, w * h) & np.uint64(255)).astype(np.uint8).reshape(h, w)
 
@@ -107,25 +101,6 @@ def _vectors(w, h, seed):
     if (w, h) == (16, 16):                                               # one tile, every tap clamps: the filtered classes explicitly
         return np.array([[1, 0], [0, 1], [1, 1], [-1, -3]], np.int16)
     return _mv_mix(nb, w, h, seed)
-
-
-def _records(mv, cost=None):
-    rec = np.zeros((len(mv), 4), np.int16)
-    rec[:, :2] = mv
-    if cost is not None:
-        rec.view(np.uint32)[:, 1] = cost
-    return rec
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
-def _sentinels(w, h, seed=77):
-    return (splitmix64(seed, 0, w * h * 2) & np.uint64(255)).astype(np.uint8)
 
 
 # ---- 7. the statement itself, no GPU ----------------------------------------------------------------------------------------------
@@ -170,8 +145,8 @@ def test_chroma_against_numpy(codec, oracle, w, h):
     for n, kind in enumerate(("split",) if w == 3840 else ("random", "extreme")):
         u, v = _planes_of(kind, w, h, 31 + w + n)
         y = _luma(w, h, 5 + n)
-        rt = _tiles(oracle, y, u, v, 40 + h)
-        base = _sentinels(w, h)                                          # m_Y and m_I must survive
+        rt = tiles(oracle, (y, u, v), 40 + h)
+        base = sentinels(w, h)                                          # m_Y and m_I must survive
         pred = codec.motion_comp(rt, mv, w, h, base=base, planes="chroma")
         wu, wv, counts = _mcc_np(u, v, mv, w, h)
         total += counts
@@ -181,8 +156,8 @@ def test_chroma_against_numpy(codec, oracle, w, h):
         assert np.array_equal(p[:, :256], b[:, :256]) and np.array_equal(p[:, 384:], b[:, 384:])
         assert (counts[3:] > 0).all() or nb < 24, counts
         # raw device pointers; the cost field of a record is ignored
-        rec = _records(mv, np.full(nb, 0xFFFFFFFF, np.uint32))
-        dr, dm, dp = _dev(codec, rt), _dev(codec, rec), _dev(codec, base)
+        rec = records(mv, np.full(nb, 0xFFFFFFFF, np.uint32))
+        dr, dm, dp = dev(codec, rt), dev(codec, rec), dev(codec, base)
         codec.motion_comp_chroma_dev(dr.ptr, dm.ptr, w, h, dp.ptr)
         codec.stream_sync()
         assert np.array_equal(dp.download(np.uint8, w * h * 2), pred)
@@ -200,13 +175,13 @@ def test_chroma_identities(codec, oracle):
     w, h = 96, 64
     nb = (w // 8) * (h // 8)
     u, v = _planes_of("split", w, h, 17)
-    rt = _tiles(oracle, _luma(w, h, 3), u, v, 6)
+    rt = tiles(oracle, (_luma(w, h, 3), u, v), 6)
     for planes in ("chroma", "both"):
         assert np.array_equal(codec.motion_comp(rt, np.zeros((nb, 2), np.int16), w, h, base=rt, planes=planes), rt)
         pred = codec.motion_comp(rt, np.tile(np.array([[32, 32]], np.int16), (nb, 1)), w, h, planes=planes)
         t, p = rt.reshape(h // 16, w // 16, 512), pred.reshape(h // 16, w // 16, 512)
         assert np.array_equal(p[:-2, :-2, 256:384], t[2:, 2:, 256:384])
-        flat = _tiles(oracle, _luma(w, h, 4), np.full_like(u, 255), np.full_like(v, 1), 7)
+        flat = tiles(oracle, (_luma(w, h, 4), np.full_like(u, 255), np.full_like(v, 1)), 7)
         got = codec.motion_comp(flat, _mv_mix(nb, w, h, 99), w, h, planes=planes).reshape(-1, 512)[:, 256:384].reshape(-1, 2)
         assert (got[:, 0] == 255).all() and (got[:, 1] == 1).all()
 
@@ -218,10 +193,10 @@ def test_fused_call_is_luma_then_chroma(codec, oracle, w, h):
     nb = (w // 8) * (h // 8)
     u, v = _planes_of("split", w, h, 300 + w)
     y, _ = me_frames(w, h, 0, 301 + w)
-    rt = _tiles(oracle, y, u, v, 302)
+    rt = tiles(oracle, (y, u, v), 302)
     mv = _mv_mix(nb, w, h, 303 + h)
-    base = _sentinels(w, h, 78)
-    dr, dm, d_two, d_one = _dev(codec, rt), _dev(codec, _records(mv)), _dev(codec, base), _dev(codec, base)
+    base = sentinels(w, h, 78)
+    dr, dm, d_two, d_one = dev(codec, rt), dev(codec, records(mv)), dev(codec, base), dev(codec, base)
     codec.motion_comp_luma_dev(dr.ptr, dm.ptr, w, h, d_two.ptr)
     codec.motion_comp_chroma_dev(dr.ptr, dm.ptr, w, h, d_two.ptr)
     codec.motion_comp_dev(dr.ptr, dm.ptr, w, h, d_one.ptr)
@@ -242,7 +217,7 @@ def loop_frames(oracle):
     cur_y, ref_y = me_frames(w, h, 0, 808, mv=(-4, 6), noise=5)
     cur_u, ref_u = me_frames(w // 2, h // 2, 0, 809, mv=(-2, 3), noise=5)
     cur_v, ref_v = me_frames(w // 2, h // 2, 0, 811, mv=(-2, 3), noise=5)
-    return w, h, (cur_y, cur_u, cur_v), (ref_y, ref_u, ref_v), _tiles(oracle, cur_y, cur_u, cur_v, 8), _tiles(oracle, ref_y, ref_u, ref_v, 9)
+    return w, h, (cur_y, cur_u, cur_v), (ref_y, ref_u, ref_v), tiles(oracle, (cur_y, cur_u, cur_v), 8), tiles(oracle, (ref_y, ref_u, ref_v), 9)
 
 
 @gpu
@@ -251,8 +226,8 @@ def test_search_mc_residual_recon_and_satd(codec, oracle, loop_frames):
     (cur, pred) is satd8x8 of numpy's cur - pred"""
     w, h, cur, ref, ct, rt = loop_frames
     rng, nb, nt, npl = 16, (w // 8) * (h // 8), (w // 16) * (h // 16), (w // 2) * (h // 2)
-    dc, dr = _dev(codec, ct), _dev(codec, rt)
-    db, dp, drec = codec.alloc(nb * 8), _dev(codec, _sentinels(w, h, 79)), _dev(codec, _sentinels(w, h, 80))
+    dc, dr = dev(codec, ct), dev(codec, rt)
+    db, dp, drec = codec.alloc(nb * 8), dev(codec, sentinels(w, h, 79)), dev(codec, sentinels(w, h, 80))
     dru, drv, dsu, dsv = codec.alloc(npl * 2), codec.alloc(npl * 2), codec.alloc(nt * 4), codec.alloc(nt * 4)
     codec.satd_search_from_tiles_dev(dc.ptr, dr.ptr, w, h, rng, db.ptr)
     codec.motion_comp_dev(dr.ptr, db.ptr, w, h, dp.ptr)
@@ -281,9 +256,9 @@ def test_inter_loop_in_a_graph(codec, oracle, loop_frames):
     w, h, cur, ref, ct, rt = loop_frames
     rng, nb, n = 16, (w // 8) * (h // 8), codec.ctu_count(w, h)
     cls = (np.arange(6 * n) % 4).astype(np.uint8)                         # DCT-II of sizes 4, 8, 16, 32 in turn
-    start = _sentinels(w, h, 81)
-    dc, dr, dk = _dev(codec, ct), _dev(codec, rt), _dev(codec, cls)
-    db, dp, dz = codec.alloc(nb * 8), _dev(codec, start), codec.alloc(n * 12288)
+    start = sentinels(w, h, 81)
+    dc, dr, dk = dev(codec, ct), dev(codec, rt), dev(codec, cls)
+    db, dp, dz = codec.alloc(nb * 8), dev(codec, start), codec.alloc(n * 12288)
     st = codec.stream_create()
     try:
         codec._check(codec.L.xHipMeScratchReserve(codec.ctx, st, w, h), "xHipMeScratchReserve")
@@ -337,7 +312,7 @@ def test_chroma_beyond_4_gib(codec):
     codec.fill_residual_dev(d_ref.ptr, nt * 256, 0xE4)
     codec.fill_residual_dev(d_pred.ptr, nt * 256, 0xE5)
     mv = _mv_mix(nb, w, h, 0xE6)
-    d_mv = _dev(codec, _records(mv))
+    d_mv = dev(codec, records(mv))
 
     def fetch(buf, byte_off, count):
         out = np.empty(count, np.uint8)

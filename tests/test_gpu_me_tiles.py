@@ -6,6 +6,7 @@ gather with clamped coordinates."""
 import numpy as np
 import pytest
 
+from _dev import dev, records, tiles
 from _util import me_frames, splitmix64
 
 pytestmark = pytest.mark.gpu
@@ -18,9 +19,7 @@ def _tiles(oracle, y, seed):
     r = splitmix64(seed, 0, (h // 2) * (w // 2) * 2)
     u = (r[: (h // 2) * (w // 2)] & np.uint64(255)).astype(np.uint8).reshape(h // 2, w // 2)
     v = ((r[(h // 2) * (w // 2):] >> np.uint64(8)) & np.uint64(255)).astype(np.uint8).reshape(h // 2, w // 2)
-    t = oracle.conv_input_fmt(y, u, v).reshape(-1, 512)
-    t[:, 384:] = (splitmix64(seed + 1, 0, t.shape[0] * 128) & np.uint64(255)).astype(np.uint8).reshape(-1, 128)
-    return t.ravel()
+    return tiles(oracle, (y, u, v), seed + 1)
 
 
 def _luma(oracle, tiles, w, h):
@@ -50,21 +49,6 @@ def _mv_mix(nb, w, h, seed):
     far = np.where((r >> np.uint64(30)) & np.uint64(1), 1, -1) * (np.array([w, h], np.int64) + 8 + (r >> np.uint64(40) & np.uint64(255)).astype(np.int64))
     mv = np.select([kind < 8, kind < 11, kind < 14], [small, ext, far], 0)
     return np.clip(mv, -32768, 32767).astype(np.int16)
-
-
-def _records(mv, cost=None):
-    rec = np.zeros((len(mv), 4), np.int16)
-    rec[:, :2] = mv
-    if cost is not None:
-        rec.view(np.uint32)[:, 1] = cost
-    return rec
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
 
 
 def _with_rows(codec, option, value, fn):
@@ -117,7 +101,7 @@ def test_same_frame_as_cur_and_ref(codec, oracle):
     w, h, rng = 80, 48, 7
     cur, _ = me_frames(w, h, 0, 55)
     ct = _tiles(oracle, cur, 3)
-    d = _dev(codec, ct)
+    d = dev(codec, ct)
     nb = (w // 8) * (h // 8)
     for metric, fn in (("satd", codec.satd_search_from_tiles_dev), ("sad", codec.sad_search_from_tiles_dev)):
         db = codec.alloc(nb * 8)
@@ -164,8 +148,8 @@ def test_motion_comp_against_numpy(codec, oracle, w, h):
     assert np.array_equal(_luma(oracle, pred, w, h), _mc_np(ref, mv, w, h))
     assert np.array_equal(pred.reshape(-1, 512)[:, 256:], base.reshape(-1, 512)[:, 256:])
     # the cost field of a record is ignored
-    rec = _records(mv, np.full(nb, 0xFFFFFFFF, np.uint32))
-    dr, dm, dp = _dev(codec, rt), _dev(codec, rec), _dev(codec, base)
+    rec = records(mv, np.full(nb, 0xFFFFFFFF, np.uint32))
+    dr, dm, dp = dev(codec, rt), dev(codec, rec), dev(codec, base)
     codec.motion_comp_luma_dev(dr.ptr, dm.ptr, w, h, dp.ptr)
     codec.stream_sync()
     assert np.array_equal(dp.download(np.uint8, w * h * 2), pred)
@@ -194,7 +178,7 @@ def test_motion_comp_beyond_4_gib(codec):
     codec.fill_residual_dev(d_ref.ptr, nt * 256, 0xE0)
     codec.fill_residual_dev(d_pred.ptr, nt * 256, 0xE1)
     mv = _mv_mix(nb, w, h, 0xE2)
-    d_mv = _dev(codec, _records(mv))
+    d_mv = dev(codec, records(mv))
 
     def fetch(buf, byte_off, count):
         out = np.empty(count, np.uint8)
@@ -234,7 +218,7 @@ def test_search_then_mc_agrees_with_the_tile_stage(codec, frame_4k):
     sum |cur - pred| is every block's SAD search cost"""
     w, h, cur, ref, ct, rt = frame_4k
     rng, nb = 64, (w // 8) * (h // 8)
-    dc, dr = _dev(codec, ct), _dev(codec, rt)
+    dc, dr = dev(codec, ct), dev(codec, rt)
     db, dp, dcost = codec.alloc(nb * 8), codec.alloc(w * h * 2), codec.alloc(nb * 4)
     for metric, fn in (("satd", codec.satd_search_from_tiles_dev), ("sad", codec.sad_search_from_tiles_dev)):
         fn(dc.ptr, dr.ptr, w, h, rng, db.ptr)
@@ -260,8 +244,8 @@ def test_inter_loop_in_a_graph(codec, oracle):
     cur, ref = me_frames(w, h, 0, 808, mv=(-4, 6), noise=5)
     ct, rt = _tiles(oracle, cur, 8), _tiles(oracle, ref, 9)
     nb = (w // 8) * (h // 8)
-    dc, dr = _dev(codec, ct), _dev(codec, rt)
-    db, dp, dcoef = codec.alloc(nb * 8), _dev(codec, rt), codec.alloc(w * h * 2)
+    dc, dr = dev(codec, ct), dev(codec, rt)
+    db, dp, dcoef = codec.alloc(nb * 8), dev(codec, rt), codec.alloc(w * h * 2)
     st = codec.stream_create()
     try:
         codec._check(codec.L.xHipMeScratchReserve(codec.ctx, st, w, h), "xHipMeScratchReserve")

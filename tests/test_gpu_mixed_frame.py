@@ -9,44 +9,15 @@ import _deblock_ref as D
 import _intra_frame_ref as R
 import _mixed_frame_ref as M
 import _quant_ref as Q
-import x266_amd
-from _arena import Arena
+from _dev import EINVAL, arena_slots, dev, displacements, noise, run, sync_or_exit, tile_written
 from _util import me_frames, splitmix64
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 CALL = "xDct32CodeMixedFrameGpu"
 QP, ROUNDING = 22, 171
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------------------------------
-def _noise(n, seed):
-    return (splitmix64(seed, 0, n) & np.uint64(255)).astype(np.uint8)
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _run(codec, fn, *args, **kw):
-    """a ..._dev call that must succeed, then a sync; a device error ends the session"""
-    try:
-        fn(*args, **kw)
-    except x266_amd.X266Error:
-        _sync_or_exit(codec, -2)
-        raise
-    _sync_or_exit(codec, 0, kw.get("stream") or None)
-
-
 def _qps(n, seed=61):
     q = (splitmix64(seed, 0, 6 * n) % np.uint64(70)).astype(np.uint8)       # bytes above 51 are clamped
     q[0] = 69
@@ -64,9 +35,9 @@ class Frame:
     def __init__(self, codec, oracle, cur, pred, w, h, seed=700):
         self.codec, self.oracle, self.w, self.h, self.n = codec, oracle, w, h, codec.ctu_count(w, h)
         self.cur_planes, self.pred_planes = cur, pred
-        self.cur, self.pred, self.base = R.tiles(oracle, cur, seed + 10), R.tiles(oracle, pred, seed + 11), _noise(w * h * 2, seed)
-        self.fill = {name: _noise(self.n * per, seed + 1 + i) for i, (name, per) in enumerate(self.OUT)}
-        self.d_cur, self.d_pred, self.d_recon = _dev(codec, self.cur), _dev(codec, self.pred), codec.alloc(w * h * 2)
+        self.cur, self.pred, self.base = R.tiles(oracle, cur, seed + 10), R.tiles(oracle, pred, seed + 11), noise(w * h * 2, seed)
+        self.fill = {name: noise(self.n * per, seed + 1 + i) for i, (name, per) in enumerate(self.OUT)}
+        self.d_cur, self.d_pred, self.d_recon = dev(codec, self.cur), dev(codec, self.pred), codec.alloc(w * h * 2)
         self.d = {name: codec.alloc(max(self.n * per, 16)) for name, per in self.OUT}
         self.reset()
 
@@ -87,7 +58,7 @@ class Frame:
 
     def code(self, **kw):
         self.reset()
-        _run(self.codec, self.enqueue, **kw)
+        run(self.codec, self.enqueue, **kw)
         return self.results()
 
     def results(self, recon=None):
@@ -129,10 +100,10 @@ def test_against_the_statement(codec, oracle, w, h, flip):
     f = Frame(codec, oracle, cur, pred, w, h, 600 + w + flip)
     n = f.n
     qps, modes = _qps(n, 61 + w), _modes(n, 63 + h)
-    d_qps, d_modes = _dev(codec, qps), _dev(codec, modes)
+    d_qps, d_modes = dev(codec, qps), dev(codec, modes)
     for penalty in (0, 4096):
         for name, kinds in _kind_inputs(n):
-            d_kinds = None if kinds is None else _dev(codec, kinds)
+            d_kinds = None if kinds is None else dev(codec, kinds)
             kp = d_kinds.ptr if d_kinds else 0
             # the scalar qp, the call chooses the modes (the statement of these is shared with the CPU tests where they have it)
             want = M.coded(oracle, w, h, flip, penalty, None) if kinds is None else f.want(qp=QP, rounding=ROUNDING, penalty=penalty, kinds_in=kinds)
@@ -143,7 +114,7 @@ def test_against_the_statement(codec, oracle, w, h, flip):
             if d_kinds:
                 assert np.array_equal(d_kinds.download(np.uint8, 6 * n), kinds.ravel())
     kinds = M.kinds_mixed(n)
-    d_kinds = _dev(codec, kinds)
+    d_kinds = dev(codec, kinds)
     f.check(f.code(qps=d_qps.ptr, kind_in=d_kinds.ptr, penalty=100), f.want(qps=qps, rounding=ROUNDING, penalty=100, kinds_in=kinds), "d_qp, modes chosen")
     f.check(f.code(mode_in=d_modes.ptr, kind_in=d_kinds.ptr, qp=37), f.want(qp=37, rounding=ROUNDING, kinds_in=kinds, modes_in=modes), "scalar qp, modes given")
     assert np.array_equal(d_qps.download(np.uint8, qps.size), qps) and np.array_equal(d_modes.download(np.uint8, modes.size), modes.ravel())
@@ -163,12 +134,12 @@ def test_every_kind_inter_is_the_fused_ctu_call(codec, oracle, w, h):
     cur, pred = M.pred_planes(w, h, 0)
     f = Frame(codec, oracle, cur, pred, w, h, 610 + w)
     n = f.n
-    d_kinds, d_qps = _dev(codec, np.zeros(6 * n, np.uint8)), _dev(codec, _qps(n, 64))
+    d_kinds, d_qps = dev(codec, np.zeros(6 * n, np.uint8)), dev(codec, _qps(n, 64))
     d_l, d_n, d_r = codec.alloc(n * 12288), codec.alloc(max(n * 24, 16)), codec.alloc(w * h * 2)
     for qps, qp in ((0, QP), (d_qps.ptr, 0)):
         got = f.code(qps=qps, qp=qp, kind_in=d_kinds.ptr)
         d_r.upload(f.base)
-        _run(codec, codec.dct32_code_ctu_tiles_dev, f.d_cur.ptr, f.d_pred.ptr, w, h, qps, qp, ROUNDING, d_l.ptr, d_n.ptr, d_r.ptr)
+        run(codec, codec.dct32_code_ctu_tiles_dev, f.d_cur.ptr, f.d_pred.ptr, w, h, qps, qp, ROUNDING, d_l.ptr, d_n.ptr, d_r.ptr)
         assert np.array_equal(got["level"], d_l.download(np.int16, n * 6144))
         assert np.array_equal(got["nnz"], d_n.download(np.uint32, n * 6))
         assert np.array_equal(got["recon"], d_r.download(np.uint8, w * h * 2))
@@ -184,7 +155,7 @@ def test_every_kind_intra_is_the_intra_frame(codec, oracle, w, h, given):
     poison = tuple(np.full_like(p, 0xA5) for p in cur)
     f = Frame(codec, oracle, cur, poison, w, h, 620 + w)
     n = f.n
-    d_kinds, d_qps, d_modes = _dev(codec, np.ones(6 * n, np.uint8)), _dev(codec, _qps(n, 65)), _dev(codec, _modes(n, 66))
+    d_kinds, d_qps, d_modes = dev(codec, np.ones(6 * n, np.uint8)), dev(codec, _qps(n, 65)), dev(codec, _modes(n, 66))
     d_l, d_n, d_m, d_r = codec.alloc(n * 12288), codec.alloc(max(n * 24, 16)), codec.alloc(max(n * 6, 16)), codec.alloc(w * h * 2)
     mp = d_modes.ptr if given else 0
     results = []
@@ -193,7 +164,7 @@ def test_every_kind_intra_is_the_intra_frame(codec, oracle, w, h, given):
         got = f.code(qps=d_qps.ptr, kind_in=d_kinds.ptr, mode_in=mp, penalty=1 << 24)
         results.append(got)
     d_r.upload(f.base)
-    _run(codec, codec.intra32_code_frame_dev, f.d_cur.ptr, w, h, d_qps.ptr, 0, ROUNDING, mp, d_l.ptr, d_n.ptr, d_m.ptr, d_r.ptr)
+    run(codec, codec.intra32_code_frame_dev, f.d_cur.ptr, w, h, d_qps.ptr, 0, ROUNDING, mp, d_l.ptr, d_n.ptr, d_m.ptr, d_r.ptr)
     for got in results:
         assert np.array_equal(got["level"], d_l.download(np.int16, n * 6144))
         assert np.array_equal(got["nnz"], d_n.download(np.uint32, n * 6))
@@ -213,8 +184,8 @@ def test_the_kinds_are_a_deblocking_d_intra(codec, oracle, w, h):
     want = M.coded(oracle, w, h, 1, 0, None, 37, ROUNDING)
     f.check(got, want, "coded")
     assert set(want.kinds[:, :4].ravel()) == {0, 1}
-    d_out = _dev(codec, f.base)
-    _run(codec, codec.deblock_dev, f.d_recon.ptr, w, h, codec.deblock_params(d_intra=f.d["kind"].ptr, d_nnz=f.d["nnz"].ptr, qp=37), d_out.ptr)
+    d_out = dev(codec, f.base)
+    run(codec, codec.deblock_dev, f.d_recon.ptr, w, h, codec.deblock_params(d_intra=f.d["kind"].ptr, d_nnz=f.d["nnz"].ptr, qp=37), d_out.ptr)
     side = D.Side(intra=want.kinds, nnz=want.nnz, qp=37)
     ref = D.deblock_tiles(oracle, got["recon"], w, h, side, base=f.base)
     assert np.array_equal(d_out.download(np.uint8, w * h * 2), ref)
@@ -231,14 +202,14 @@ def test_in_place_and_optional_outputs(codec, oracle, w, h, given):
     f = Frame(codec, oracle, cur, pred, w, h, 640 + w)
     n = f.n
     kinds, modes = M.kinds_mixed(n, 11), _modes(n, 67)
-    d_kinds, d_modes = _dev(codec, kinds), _dev(codec, modes)
+    d_kinds, d_modes = dev(codec, kinds), dev(codec, modes)
     separate = f.code(kind_in=d_kinds.ptr, mode_in=d_modes.ptr if given else 0, penalty=64)
     want = f.want(qp=QP, rounding=ROUNDING, penalty=64, kinds_in=kinds, modes_in=modes if given else None)
     f.check(separate, want, "separate")
     f.reset()
     f.d["kind"].upload(kinds)
     f.d["mode"].upload(modes)
-    _run(codec, f.enqueue, kind_in=f.d["kind"].ptr, mode_in=f.d["mode"].ptr if given else 0, penalty=64, recon=f.d_pred.ptr, nnz=False, cost=False)
+    run(codec, f.enqueue, kind_in=f.d["kind"].ptr, mode_in=f.d["mode"].ptr if given else 0, penalty=64, recon=f.d_pred.ptr, nnz=False, cost=False)
     got = f.results(recon=f.d_pred)
     f.check(got, want, "in place", nnz=False, cost=False, base=f.pred, pred_kept=False)
     for name in ("level", "kind", "mode"):
@@ -255,7 +226,7 @@ def test_contents(codec, oracle, kind):
     cur, pred = M.pred_planes(w, h, 0, kind)
     f = Frame(codec, oracle, cur, pred, w, h, 650)
     kinds = M.kinds_mixed(f.n, 13)
-    d_kinds = _dev(codec, kinds)
+    d_kinds = dev(codec, kinds)
     for qp in (0, 22, 51):
         f.check(f.code(qp=qp, kind_in=d_kinds.ptr), f.want(qp=qp, rounding=ROUNDING, kinds_in=kinds), (kind, qp))
 
@@ -290,8 +261,8 @@ def test_the_chain_eagerly_and_from_one_graph(codec, oracle):
     cur_y = cur_y.copy()
     cur_y[:64, 64:] = R.case("oriented", 64, 64)[0]                         # a CTU with no counterpart in the reference
     ct, rt = R.tiles(oracle, (cur_y, cur_u, cur_v), 804), R.tiles(oracle, (ref_y, ref_u, ref_v), 805)
-    start, fills = _noise(w * h * 2, 806), _noise(w * h * 2, 807)
-    dc, dr, dp, drec, dout = _dev(codec, ct), _dev(codec, rt), _dev(codec, start), _dev(codec, fills), _dev(codec, fills)
+    start, fills = noise(w * h * 2, 806), noise(w * h * 2, 807)
+    dc, dr, dp, drec, dout = dev(codec, ct), dev(codec, rt), dev(codec, start), dev(codec, fills), dev(codec, fills)
     d_int, d_best = codec.alloc(nb * 8), codec.alloc(nb * 8)
     outs = {"level": codec.alloc(n * 12288), "nnz": codec.alloc(n * 24), "kind": codec.alloc(16 * n), "mode": codec.alloc(16 * n), "cost": codec.alloc(n * 48)}
     st = codec.stream_create()
@@ -309,7 +280,7 @@ def test_the_chain_eagerly_and_from_one_graph(codec, oracle):
             codec.deblock_dev(drec.ptr, w, h, dbk, dout.ptr, stream=st)
 
         def results():
-            _sync_or_exit(codec, 0, st)
+            sync_or_exit(codec, 0, st)
             return ([dp.download(np.uint8, w * h * 2), drec.download(np.uint8, w * h * 2), dout.download(np.uint8, w * h * 2), d_best.download(np.uint8, nb * 8)] +
                     [outs[k].download(np.uint8, n * per) for k, per in Frame.OUT])
 
@@ -359,29 +330,15 @@ def arena_case(oracle):
             "d_cost": want.costs.ravel(), "coded": want, "oracle": oracle}
 
 
-def _displacements(halved=None):
-    """every pointer at exactly its documented alignment and no more (odd multiples, varying between the buffers); `halved`: that one
-    at half its alignment"""
-    return {p: (align // 2, align // 2) if p == halved else (align * (2 * i + 1), align) for i, (p, align) in enumerate(PTRS.items())}
-
-
 def _arena(codec, arena_case, disp, guard_seed):
-    a, s = Arena(codec), {}
-    for i, p in enumerate(PTRS):
-        if p in OUTPUTS:
-            nbytes, written = (AW * AH * 2, np.zeros((AW * AH * 2 // 512, 512), bool)) if p == "d_recon" else (arena_case[p].nbytes, None)
-            if written is not None:
-                written[:, :384] = True
-            s[p] = a.output(p, nbytes, disp[p][1], disp[p][0], written=None if written is None else written.ravel())
-        else:
-            s[p] = a.input(p, arena_case[p], disp[p][1], disp[p][0], guard_seed + i)
-    return a, s
+    return arena_slots(codec, PTRS, OUTPUTS, arena_case, disp, guard_seed, written={"d_recon": tile_written(AW * AH // 256, "both")},
+                       sizes={"d_recon": AW * AH * 2})
 
 
 def _call_arena(codec, s):
     p = codec.mixed_params(AW, AH, 0, ROUNDING, 32, **{name: slot.ptr for name, slot in s.items()})
     rc = codec.L.xDct32CodeMixedFrameGpu(codec.ctx, p, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -389,7 +346,7 @@ def _call_arena(codec, s):
 def test_minimum_alignment(codec, arena_case):
     results = []
     for guard_seed in (31, 51):
-        a, s = _arena(codec, arena_case, _displacements(), guard_seed)
+        a, s = _arena(codec, arena_case, displacements(PTRS), guard_seed)
         assert _call_arena(codec, s) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()                                                     # guards, m_I of d_recon, inputs
         for p in OUTPUTS:
@@ -406,7 +363,7 @@ def test_minimum_alignment(codec, arena_case):
 @gpu
 @pytest.mark.parametrize("ptr", [p for p in PTRS if PTRS[p] > 1])
 def test_half_alignment_is_rejected(codec, arena_case, ptr):
-    a, s = _arena(codec, arena_case, _displacements(halved=ptr), 33)
+    a, s = _arena(codec, arena_case, displacements(PTRS, halved=ptr), 33)
     assert _call_arena(codec, s) == EINVAL
     assert CALL.encode() in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
@@ -418,7 +375,7 @@ def test_argument_errors(codec):
     """one refused call per rule of the header; a refused call launches nothing and names itself"""
     L, ctx = codec.L, codec.ctx
     buf = codec.alloc(8 << 20)
-    fill = _noise(8 << 20, 95)
+    fill = noise(8 << 20, 95)
     buf.upload(fill)
     # 64x64: tile arrays of 8 KiB, 12 KiB of levels; 24, 6, 6, 48, 6, 6, 6 bytes
     cur, prd, rec, lvl = (buf.ptr + (i << 20) for i in (1, 2, 3, 4))
@@ -458,5 +415,5 @@ def test_argument_errors(codec):
     for p in (P(qp=0, rounding=0, d_nnz=0, d_cost=0), P(qp=51, rounding=511, penalty=1 << 24), P(d_qp=qps, qp=99, d_kind_in=kin, d_mode_in=min_),
               P(d_recon=prd), P(d_kind_in=kin, d_kind=kin), P(d_mode_in=min_, d_mode=min_), P(d_pred=cur)):
         rc = L.xDct32CodeMixedFrameGpu(ctx, p, None)
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from _arena import Arena
+from _dev import EINVAL, records, sync_or_exit, tiles
 from _util import fullrange_np, intra_refs_np, me_frames, residual_np, splitmix64
 import test_gpu_mc_chroma as mcc
 import test_gpu_me_tiles as met
@@ -31,7 +32,6 @@ import test_gpu_transform_ctu_tiles as ctu
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
 
 # `...Dev(` declarations of the header that have no row.  Fixed: a new entry point needs a row, not an entry here.
 EXCLUDED = frozenset()
@@ -515,13 +515,13 @@ def _(oracle, size, costs, rows):
 def _mc_case(oracle, entry, size, luma, chroma):
     w, h = size
     y, u, v = _yuv(w, h, 270 + w)
-    ref = mcc._tiles(oracle, y, u, v, 271)
+    ref = tiles(oracle, (y, u, v), 271)
     mv = mcc._vectors(w, h, 272 + w)
     cost = (splitmix64(273, 0, len(mv)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)      # the cost field is ignored
     base = rct._tiles_mix(w, h, 274)                                                    # only the planes' masks matter
     want_y = met._mc_np(y, mv, w, h) if luma else None
     want_u, want_v, _ = mcc._mcc_np(u, v, mv, w, h) if chroma else (None, None, None)
-    return Case({"d_ref": ref, "d_mv": mcc._records(mv, cost)}, {"d_pred": _recon_want(oracle, base, w, h, y=want_y, u=want_u, v=want_v)},
+    return Case({"d_ref": ref, "d_mv": records(mv, cost)}, {"d_pred": _recon_want(oracle, base, w, h, y=want_y, u=want_u, v=want_v)},
                 lambda L, c, p: getattr(L, entry)(c, p["d_ref"], p["d_mv"], w, h, p["d_pred"], None), {})
 
 
@@ -734,9 +734,7 @@ def _launch(codec, r, case, displacement, guard_seed):
             p[name] = None                                                # an optional argument this variant leaves out
     with _options(codec, case.options):
         rc = case.call(codec.L, codec.ctx, p)
-        sync = codec.L.xHipStreamSync(codec.ctx, None)
-    if sync != 0 or rc not in (0, EINVAL):                                # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
+        sync_or_exit(codec, rc)
     return rc, arena, outs
 
 

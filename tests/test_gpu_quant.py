@@ -9,21 +9,12 @@ import pytest
 
 import _quant_ref as Q
 from _quant_ref import EXTREMES, _bytes, _coefficients, _levels, _res_mix, _tiles_mix   # the data recipes, shared with tests/_frame_cases.py
-from _arena import Arena
+from _dev import EINVAL, arena_slots, dev, displacements, sync_or_exit, tile_written
 from _util import me_frames, splitmix64
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 ROUNDINGS = [0, 171, 511]
-
-
-# ---- data ---------------------------------------------------------------------------------------------------------------------------
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
 
 
 # ---- 1. the region call against the reference -------------------------------------------------------------------------------------
@@ -71,7 +62,7 @@ def test_in_place_equals_out_of_place(codec, inverse):
     n = 18
     x = _levels(n, 0x5500) if inverse else _coefficients(n, 0x5501)
     cls, qps = _bytes(n, 0x5502, 15), _bytes(n, 0x5503, 63)
-    d_in, d_out, d_io, dk, dq = _dev(codec, x), codec.alloc(x.nbytes), _dev(codec, x), _dev(codec, cls), _dev(codec, qps)
+    d_in, d_out, d_io, dk, dq = dev(codec, x), codec.alloc(x.nbytes), dev(codec, x), dev(codec, cls), dev(codec, qps)
     nnz = [None if inverse else codec.alloc(4 * n) for _ in range(2)]
     codec.quant_regions_dev(inverse, d_in.ptr, d_out.ptr, n, dk.ptr, dq.ptr, 0, 171, nnz[0].ptr if nnz[0] else 0)
     codec.quant_regions_dev(inverse, d_io.ptr, d_io.ptr, n, dk.ptr, dq.ptr, 0, 171, nnz[1].ptr if nnz[1] else 0)
@@ -88,7 +79,7 @@ def test_in_place_equals_out_of_place(codec, inverse):
 def test_partial_overlap_is_refused(codec):
     n = 3
     x = _coefficients(n + 1, 0x5510)
-    d = _dev(codec, x)
+    d = dev(codec, x)
     for d_in, d_out in ((d.ptr, d.ptr + 2048), (d.ptr + 2048, d.ptr), (d.ptr, d.ptr + 16)):
         rc = codec.L.xQuantRegionsGpu(codec.ctx, 0, d_in, d_out, n, None, None, 22, 171, None, None)
         assert rc == EINVAL and b"xQuantRegionsGpu" in codec.L.xHipLastError(codec.ctx)
@@ -132,7 +123,7 @@ def test_fused_against_reference_and_chain(codec, oracle, fused_frames, w, h, mo
     if mode == "qp0":
         assert (want_nnz > 512).all()
 
-    dc, dp, dr, dq = _dev(codec, cur), _dev(codec, pred), _dev(codec, base), (_dev(codec, qps) if qps is not None else None)
+    dc, dp, dr, dq = dev(codec, cur), dev(codec, pred), dev(codec, base), (dev(codec, qps) if qps is not None else None)
     dl, dn = codec.alloc(n * 12288), codec.alloc(max(n * 24, 16))
     q = dq.ptr if dq else 0
     codec.dct32_code_ctu_tiles_dev(dc.ptr, dp.ptr, w, h, q, qp, rounding, dl.ptr, dn.ptr, dr.ptr)
@@ -145,7 +136,7 @@ def test_fused_against_reference_and_chain(codec, oracle, fused_frames, w, h, mo
     assert np.array_equal(dp.download(np.uint8, w * h * 2), pred) and np.array_equal(dc.download(np.uint8, w * h * 2), cur)
 
     # the four-call chain
-    dz, dn2, dr2 = codec.alloc(n * 12288), codec.alloc(max(n * 24, 16)), _dev(codec, base)
+    dz, dn2, dr2 = codec.alloc(n * 12288), codec.alloc(max(n * 24, 16)), dev(codec, base)
     codec.dct32_fwd_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dz.ptr)
     codec.quant_regions_dev(0, dz.ptr, dz.ptr, 6 * n, 0, q, qp, rounding, dn2.ptr)
     codec.stream_sync()
@@ -196,36 +187,16 @@ def test_numpy_conveniences(codec, oracle, fused_frames):
 
 
 # ---- 4. minimum alignment inside guard bands -------------------------------------------------------------------------------------
-def _sync_or_exit(codec, rc):
-    sync = codec.L.xHipStreamSync(codec.ctx, None)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
 REGION_PTRS = {"d_in": 16, "d_out": 16, "d_class": 1, "d_qp": 1, "d_nnz": 4}
 FUSED_PTRS = {"d_cur": 16, "d_pred": 16, "d_qp": 1, "d_level": 16, "d_nnz": 4, "d_recon": 16}
-
-
-def _displacements(ptrs, halved=None):
-    """every pointer at exactly its documented alignment and no more (odd multiples, varying between the buffers); `halved`: that one
-    at half its alignment"""
-    out = {}
-    for i, (name, align) in enumerate(ptrs.items()):
-        out[name] = (align // 2, align // 2) if name == halved else (align * (2 * i + 1), align)
-    return out
 
 
 def _region_case(codec, inverse, disp, guard_seed):
     n = 7
     x = _levels(n, 0x5600) if inverse else _coefficients(n, 0x5601)
     cls, qps = _bytes(n, 0x5602, 15), _bytes(n, 0x5603, 63)
-    a = Arena(codec)
-    s = {"d_in": a.input("d_in", x, disp["d_in"][1], disp["d_in"][0], guard_seed),
-         "d_class": a.input("d_class", cls, 1, disp["d_class"][0], guard_seed + 1),
-         "d_qp": a.input("d_qp", qps, 1, disp["d_qp"][0], guard_seed + 2),
-         "d_out": a.output("d_out", n * 2048, disp["d_out"][1], disp["d_out"][0])}
-    if not inverse:
-        s["d_nnz"] = a.output("d_nnz", 4 * n, disp["d_nnz"][1], disp["d_nnz"][0])
+    placed = ("d_in", "d_class", "d_qp", "d_out") + (() if inverse else ("d_nnz",))   # the inputs first; no counts behind an inverse call
+    a, s = arena_slots(codec, placed, ("d_out", "d_nnz"), {"d_in": x, "d_class": cls, "d_qp": qps}, disp, guard_seed, sizes={"d_out": n * 2048, "d_nnz": 4 * n})
     want = Q.quant_regions(x, bool(inverse), cls, qps, 0, 171)
     return a, s, n, want
 
@@ -233,7 +204,7 @@ def _region_case(codec, inverse, disp, guard_seed):
 def _call_region(codec, inverse, s, n, qp=0, rounding=171, nnz="own"):
     d_nnz = s["d_nnz"].ptr if nnz == "own" and "d_nnz" in s else nnz if isinstance(nnz, int) else None
     rc = codec.L.xQuantRegionsGpu(codec.ctx, inverse, s["d_in"].ptr, s["d_out"].ptr, n, s["d_class"].ptr, s["d_qp"].ptr, qp, rounding, d_nnz, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -241,7 +212,7 @@ def _call_region(codec, inverse, s, n, qp=0, rounding=171, nnz="own"):
 def test_regions_at_minimum_alignment(codec, inverse):
     results = []
     for guard_seed in (11, 12):
-        a, s, n, want = _region_case(codec, inverse, _displacements(REGION_PTRS), guard_seed)
+        a, s, n, want = _region_case(codec, inverse, displacements(REGION_PTRS), guard_seed)
         assert _call_region(codec, inverse, s, n) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()                                                     # guards intact, inputs unchanged
         out = got["d_out"].view(np.int16).reshape(n, 1024)
@@ -254,7 +225,7 @@ def test_regions_at_minimum_alignment(codec, inverse):
 
 @pytest.mark.parametrize("ptr", [k for k, v in REGION_PTRS.items() if v > 1])
 def test_regions_half_alignment_is_rejected(codec, ptr):
-    a, s, n, _ = _region_case(codec, 0, _displacements(REGION_PTRS, halved=ptr), 13)
+    a, s, n, _ = _region_case(codec, 0, displacements(REGION_PTRS, halved=ptr), 13)
     assert _call_region(codec, 0, s, n) == EINVAL
     assert b"xQuantRegionsGpu" in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
@@ -263,10 +234,10 @@ def test_regions_half_alignment_is_rejected(codec, ptr):
 @pytest.mark.parametrize("what", ["qp52", "rounding512", "nnz-with-inverse"])
 def test_regions_argument_errors(codec, what):
     inverse = 1 if what == "nnz-with-inverse" else 0
-    a, s, n, _ = _region_case(codec, 0, _displacements(REGION_PTRS), 14)
+    a, s, n, _ = _region_case(codec, 0, displacements(REGION_PTRS), 14)
     if what == "qp52":
         rc = codec.L.xQuantRegionsGpu(codec.ctx, 0, s["d_in"].ptr, s["d_out"].ptr, n, s["d_class"].ptr, None, 52, 171, s["d_nnz"].ptr, None)
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
     elif what == "rounding512":
         rc = _call_region(codec, 0, s, n, rounding=512)
     else:
@@ -279,22 +250,16 @@ def _fused_case(codec, fused_frames, disp, guard_seed):
     """the 192x128 frame (six CTUs) with per-region qp bytes, every buffer placed by `disp`"""
     cur, pred, base = fused_frames[(192, 128)]
     qps, _ = _qp_args("per-region", 6)
-    written = np.zeros((192 * 128 * 2 // 512, 512), bool)
-    written[:, :384] = True                                                 # m_I is a hole
-    a = Arena(codec)
-    s = {"d_cur": a.input("d_cur", cur, disp["d_cur"][1], disp["d_cur"][0], guard_seed),
-         "d_pred": a.input("d_pred", pred, disp["d_pred"][1], disp["d_pred"][0], guard_seed + 1),
-         "d_qp": a.input("d_qp", qps, 1, disp["d_qp"][0], guard_seed + 2),
-         "d_level": a.output("d_level", 6 * 12288, disp["d_level"][1], disp["d_level"][0]),
-         "d_nnz": a.output("d_nnz", 6 * 24, disp["d_nnz"][1], disp["d_nnz"][0]),
-         "d_recon": a.output("d_recon", base.size, disp["d_recon"][1], disp["d_recon"][0], written=written.ravel())}
+    a, s = arena_slots(codec, FUSED_PTRS, ("d_level", "d_nnz", "d_recon"), {"d_cur": cur, "d_pred": pred, "d_qp": qps}, disp, guard_seed,
+                       written={"d_recon": tile_written(192 * 128 // 256, "both")},   # m_I is a hole
+                       sizes={"d_level": 6 * 12288, "d_nnz": 6 * 24, "d_recon": base.size})
     return a, s, qps
 
 
 def _call_fused(codec, s, w=192, h=128, qp=0, rounding=171, with_qp=True):
     rc = codec.L.xDct32CodeCtuTilesGpu(codec.ctx, s["d_cur"].ptr, s["d_pred"].ptr, w, h, s["d_qp"].ptr if with_qp else None, qp, rounding,
                                        s["d_level"].ptr, s["d_nnz"].ptr, s["d_recon"].ptr, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -302,7 +267,7 @@ def test_fused_at_minimum_alignment(codec, oracle, fused_frames):
     cur, pred, _ = fused_frames[(192, 128)]
     results = []
     for guard_seed in (21, 22):
-        a, s, qps = _fused_case(codec, fused_frames, _displacements(FUSED_PTRS), guard_seed)
+        a, s, qps = _fused_case(codec, fused_frames, displacements(FUSED_PTRS), guard_seed)
         assert _call_fused(codec, s) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()                                                     # guards, the m_I holes, inputs
         want_level, want_nnz, want_recon = Q.code_ctu_tiles(oracle, cur, pred, 192, 128, qps, 0, 171, base=s["d_recon"].image[s["d_recon"].start:][:cur.size])
@@ -316,7 +281,7 @@ def test_fused_at_minimum_alignment(codec, oracle, fused_frames):
 
 @pytest.mark.parametrize("ptr", [k for k, v in FUSED_PTRS.items() if v > 1])
 def test_fused_half_alignment_is_rejected(codec, fused_frames, ptr):
-    a, s, _ = _fused_case(codec, fused_frames, _displacements(FUSED_PTRS, halved=ptr), 23)
+    a, s, _ = _fused_case(codec, fused_frames, displacements(FUSED_PTRS, halved=ptr), 23)
     assert _call_fused(codec, s) == EINVAL
     assert b"xDct32CodeCtuTilesGpu" in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
@@ -324,7 +289,7 @@ def test_fused_half_alignment_is_rejected(codec, fused_frames, ptr):
 
 @pytest.mark.parametrize("what", ["qp52", "rounding512", "width96"])
 def test_fused_argument_errors(codec, fused_frames, what):
-    a, s, _ = _fused_case(codec, fused_frames, _displacements(FUSED_PTRS), 24)
+    a, s, _ = _fused_case(codec, fused_frames, displacements(FUSED_PTRS), 24)
     if what == "qp52":
         rc = _call_fused(codec, s, qp=52, with_qp=False)
     elif what == "rounding512":
@@ -347,8 +312,8 @@ def test_inter_loop_in_a_graph(codec, oracle):
     nb, n = (w // 8) * (h // 8), codec.ctu_count(w, h)
     start = _tiles_mix(w, h, 0x6300)
     qps, _ = _qp_args("per-region", n)
-    dc, dr, dq = _dev(codec, ct), _dev(codec, rt), _dev(codec, qps)
-    db, dp, dl, dn = codec.alloc(nb * 8), _dev(codec, start), codec.alloc(n * 12288), codec.alloc(n * 24)
+    dc, dr, dq = dev(codec, ct), dev(codec, rt), dev(codec, qps)
+    db, dp, dl, dn = codec.alloc(nb * 8), dev(codec, start), codec.alloc(n * 12288), codec.alloc(n * 24)
     st = codec.stream_create()
     try:
         codec._check(codec.L.xHipMeScratchReserve(codec.ctx, st, w, h), "xHipMeScratchReserve")
@@ -395,7 +360,7 @@ def test_mixed_set_loop_with_the_quantiser_in_place(codec, oracle):
     cur, pred, base = _tiles_mix(w, h, 0x6400), _tiles_mix(w, h, 0x6401), _tiles_mix(w, h, 0x6402)
     cls = _bytes(6 * n, 0x6403, 15)
     qps = _bytes(6 * n, 0x6404, 63)
-    dc, dp, dr, dk, dq = _dev(codec, cur), _dev(codec, pred), _dev(codec, base), _dev(codec, cls), _dev(codec, qps)
+    dc, dp, dr, dk, dq = dev(codec, cur), dev(codec, pred), dev(codec, base), dev(codec, cls), dev(codec, qps)
     dz, dn = codec.alloc(n * 12288), codec.alloc(n * 24)
     codec.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr, dz.ptr)
     codec.quant_regions_dev(0, dz.ptr, dz.ptr, 6 * n, dk.ptr, dq.ptr, 0, 171, dn.ptr)

@@ -14,25 +14,12 @@ import _quant_ref as Q
 import _rdoq_ref as R
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, call_struct, dev, sync_or_exit
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 PTRS = {"d_coef": 16, "d_level": 16, "d_class": 1, "d_qp": 1, "d_nnz": 4, "d_stat": 8}
 DISP = {name: align * (2 * i + 1) for i, (name, align) in enumerate(PTRS.items())}          # exactly the documented alignment, no more
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
 
 
 # ---- the batches, and the reference computed once per batch -----------------------------------------------------------------------------
@@ -81,9 +68,7 @@ def rdoq(codec, coef, cls, qps, qp, lam, in_place=False, with_nnz=True, with_sta
     if with_stat:
         s["d_stat"] = a.output("d_stat", 16 * n, 8, DISP["d_stat"])
     p = codec.rdoq_params(*[s[name].ptr if name in s else 0 for name in PTRS], n_regions=n, qp=qp, lam=lam)
-    rc = codec.L.xRdoQuantRegionsGpu(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, codec.L.xHipLastError(codec.ctx)
+    call_struct(codec, "xRdoQuantRegionsGpu", p, stream)
     got = a.check()                                                         # guard bands and inputs
     return (got["d_level"].view(np.int16).reshape(n, 1024), got["d_nnz"].view(np.uint32) if with_nnz else None,
             got["d_stat"].view(R.STAT_DTYPE) if with_stat else None)
@@ -202,7 +187,7 @@ def test_both_calls_in_one_graph(codec):
                 d_qp.upload(qps)
                 d_level.upload(np.full(n * 1024, 0x5A5A, np.int16))
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 stat2 = d_stat2.download(np.uint8, 16 * n).view(R.STAT_DTYPE)
                 _same(d_level.download(np.int16, n * 1024).reshape(n, 1024), d_nnz.download(np.uint32, n),
                       d_stat.download(np.uint8, 16 * n).view(R.STAT_DTYPE), want, want_stat)
@@ -228,7 +213,7 @@ def levels_bits(codec, lv, cls=None, nnz=None):
     p = codec.rdoq_params(8, s["d_level"].ptr, s["d_class"].ptr if cls is not None else 0, 3, s["d_nnz"].ptr if nnz is not None else 0, s["d_stat"].ptr,
                           n, 99, -5)
     rc = codec.L.xLevelsBitsGpu(codec.ctx, ctypes.byref(p), None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     assert rc == 0, codec.L.xHipLastError(codec.ctx)
     return a.check()["d_stat"].view(R.STAT_DTYPE)
 
@@ -272,7 +257,7 @@ def test_chain(codec, oracle, w, h):
     want, want_stat, counters = R.rdo_quant(coef, None, None, qp, lam)
     assert want.any() and counters["changed"] > 0
     want_recon = Q.recon_of_coefficients(oracle, Q.quant_regions(want, True, None, None, qp), pred, base, w, h)
-    dc, dp, dr = _dev(codec, cur), _dev(codec, pred), _dev(codec, base)
+    dc, dp, dr = dev(codec, cur), dev(codec, pred), dev(codec, base)
     dz, dn, ds = codec.alloc(n * 12288), codec.alloc(n * 24), codec.alloc(n * 96)
     codec.dct32_fwd_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dz.ptr)
     codec.rdo_quant_dev(codec.rdoq_params(dz.ptr, dz.ptr, 0, 0, dn.ptr, ds.ptr, 6 * n, qp, lam))
@@ -290,7 +275,7 @@ def test_chain(codec, oracle, w, h):
     back, back_nnz = codec.levels_unpack(rec, words, 6 * n)
     assert np.array_equal(back, want) and np.array_equal(back_nnz, want_stat["n_nz"])
     # the deblocking call reads the very array the call wrote
-    d_out = _dev(codec, recon)
+    d_out = dev(codec, recon)
     codec.deblock_dev(dr.ptr, w, h, codec.deblock_params(d_nnz=dn.ptr, qp=qp), d_out.ptr)
     codec.stream_sync()
     assert np.array_equal(d_out.download(np.uint8, w * h * 2), codec.deblock(recon, w, h, base=recon, nnz=want_stat["n_nz"], qp=qp))
@@ -360,14 +345,14 @@ def test_argument_errors(codec):
                          ("d_stat", "d_qp"), ("d_nnz", "d_stat")):
         refused("xRdoQuantRegionsGpu", **{field: good[other] + (extent[other] - 1) // PTRS[field] * PTRS[field]})
         refused("xRdoQuantRegionsGpu", **{field: good[other]})
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     assert np.array_equal(buf.download(np.uint8, 8 * M), fill)             # nothing was launched
     # the edges of what is accepted: no regions (nothing is looked at), a qp out of range beside d_qp, garbage in what xLevelsBitsGpu ignores
     for rc in (L.xRdoQuantRegionsGpu(ctx, ctypes.byref(codec.rdoq_params(n_regions=0, qp=99, lam=-1)), None),
                L.xLevelsBitsGpu(ctx, ctypes.byref(codec.rdoq_params(n_regions=0)), None)):
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)
     assert np.array_equal(buf.download(np.uint8, 8 * M), fill)
     rc = L.xRdoQuantRegionsGpu(ctx, ctypes.byref(codec.rdoq_params(**dict(good, qp=99))), None)     # qp is not looked at beside d_qp
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     assert rc == 0, L.xHipLastError(ctx)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 from hypothesis import HealthCheck, given, settings, strategies as st
 
+from _dev import dev
+from _quant_ref import _clip, _planes
 from _util import extremes_np, fullrange_np, residual_np, splitmix64
 
 pytestmark = pytest.mark.gpu
@@ -15,20 +17,8 @@ EXTREMES = np.array([32767, -32767, -32768, 255, -255, 256, -256], np.int16)
 
 
 # ---- numpy statement of the tile layout and of the reconstruction ---------------------------------------------------------
-def _planes(tiles, w, h):
-    """(y, u, v) planes held by a tile array (the inverse of xConvInputFmt's packing)"""
-    t = np.asarray(tiles, np.uint8).reshape(h // 16, w // 16, 512)
-    y = t[:, :, :256].reshape(h // 16, w // 16, 16, 16).transpose(0, 2, 1, 3).reshape(h, w)
-    c = t[:, :, 256:384].reshape(h // 16, w // 16, 8, 8, 2).transpose(0, 2, 1, 3, 4).reshape(h // 2, w // 2, 2)
-    return y, c[..., 0].copy(), c[..., 1].copy()
-
-
 def _unblocks(b, hh, ww, edge):
     return np.asarray(b).reshape(hh // edge, ww // edge, edge, edge).transpose(0, 2, 1, 3).reshape(hh, ww)
-
-
-def _clip(pred, res):
-    return np.clip(pred.astype(np.int32) + res.astype(np.int32), 0, 255).astype(np.uint8)
 
 
 def _with(oracle, base, w, h, y=None, u=None, v=None):
@@ -77,15 +67,8 @@ def _assert_pairs_covered(pred, res):
             assert np.any((r == v) & (p == q)), (int(v), q)
 
 
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
 def _sentinel(codec, nbytes):
-    return _dev(codec, np.full(nbytes, SENTINEL, np.uint8))
+    return dev(codec, np.full(nbytes, SENTINEL, np.uint8))
 
 
 # ---- 1. unfused reconstruction against numpy, 5. in place ----------------------------------------------------------------------
@@ -97,14 +80,14 @@ def test_recon_luma_against_numpy(codec, oracle, edge, w, h):
     plane = _unblocks(res.reshape(-1, edge * edge), h, w, edge)
     _assert_pairs_covered(py, plane)
     want_y = _clip(py, plane)
-    d_pred, d_res = _dev(codec, pred), _dev(codec, res)
+    d_pred, d_res = dev(codec, pred), dev(codec, res)
     d_out = _sentinel(codec, pred.nbytes)                                # m_C and m_I must keep the sentinel
     codec.recon_luma_dev(d_pred.ptr, d_res.ptr, w, h, edge, d_out.ptr)
     codec.stream_sync()
     got = d_out.download(np.uint8, pred.nbytes)
     assert np.array_equal(got, _with(oracle, np.full(pred.size, SENTINEL, np.uint8), w, h, y=want_y))
     assert np.array_equal(d_pred.download(np.uint8, pred.nbytes), pred)  # the input is not touched
-    d_inplace = _dev(codec, pred)                                         # d_recon == d_pred: same m_Y, the rest of pred kept
+    d_inplace = dev(codec, pred)                                         # d_recon == d_pred: same m_Y, the rest of pred kept
     codec.recon_luma_dev(d_inplace.ptr, d_res.ptr, w, h, edge, d_inplace.ptr)
     codec.stream_sync()
     assert np.array_equal(d_inplace.download(np.uint8, pred.nbytes), _with(oracle, pred, w, h, y=want_y))
@@ -122,20 +105,20 @@ def test_recon_chroma_against_numpy(codec, oracle, edge, w, h, pitch):
     _assert_pairs_covered(np.concatenate([pu.ravel(), pv.ravel()]), np.concatenate([plane_u.ravel(), plane_v.ravel()]))
     want_u, want_v = _clip(pu, plane_u), _clip(pv, plane_v)
     if pitch == 1:                                                       # two planar block streams
-        d_u, d_v = _dev(codec, res_u), _dev(codec, res_v)
+        d_u, d_v = dev(codec, res_u), dev(codec, res_v)
         pu_ptr, pv_ptr = d_u.ptr, d_v.ptr
     else:                                                                # one stream U0 V0 (hole) U1 V1 (hole) ...
         both = np.full((n, pitch, edge * edge), 0x7777, np.int16)
         both[:, 0], both[:, 1] = res_u.reshape(n, -1), res_v.reshape(n, -1)
-        d_both = _dev(codec, both)
+        d_both = dev(codec, both)
         pu_ptr, pv_ptr = d_both.ptr, d_both.ptr + edge * edge * 2
-    d_pred = _dev(codec, pred)
+    d_pred = dev(codec, pred)
     d_out = _sentinel(codec, pred.nbytes)                                # m_Y and m_I must keep the sentinel
     codec.recon_chroma_dev(d_pred.ptr, pu_ptr, pv_ptr, w, h, edge, d_out.ptr, pitch)
     codec.stream_sync()
     got = d_out.download(np.uint8, pred.nbytes)
     assert np.array_equal(got, _with(oracle, np.full(pred.size, SENTINEL, np.uint8), w, h, u=want_u, v=want_v))
-    d_inplace = _dev(codec, pred)
+    d_inplace = dev(codec, pred)
     codec.recon_chroma_dev(d_inplace.ptr, pu_ptr, pv_ptr, w, h, edge, d_inplace.ptr, pitch)
     codec.stream_sync()
     assert np.array_equal(d_inplace.download(np.uint8, pred.nbytes), _with(oracle, pred, w, h, u=want_u, v=want_v))
@@ -146,11 +129,11 @@ def test_recon_chroma_against_numpy(codec, oracle, edge, w, h, pitch):
 def test_residual_then_recon_gives_back_cur(codec, oracle, w, h):
     cur, pred = _tiles_mix(w, h, 600 + w), _tiles_mix(w, h, 700 + w)
     cy, cu, cv = _planes(cur, w, h)
-    d_cur = _dev(codec, cur)
+    d_cur = dev(codec, cur)
     npl = (w // 2) * (h // 2)
     for ledge in ((32, 8) if w % 32 == 0 and h % 32 == 0 else (8,)):
         for cedge in ((32, 8) if w % 64 == 0 and h % 64 == 0 else (8,)):
-            d_pred = _dev(codec, pred)
+            d_pred = dev(codec, pred)
             d_res, d_ru, d_rv = codec.alloc(w * h * 2), codec.alloc(npl * 2), codec.alloc(npl * 2)
             codec.residual_luma_dev(d_cur.ptr, d_pred.ptr, w, h, ledge, d_res.ptr)
             codec.residual_chroma_dev(d_cur.ptr, d_pred.ptr, w, h, cedge, d_ru.ptr, d_rv.ptr)
@@ -180,12 +163,12 @@ def test_fused_inverse_into_tiles(codec, oracle, w, h, source):
     on full-range coefficients (the inverse's int16 clipping) and on xDct32FwdFromTilesDev's (the real loop)"""
     n = (w // 32) * (h // 32)
     pred = _tiles_mix(w, h, 800 + w)
-    d_pred = _dev(codec, pred)
+    d_pred = dev(codec, pred)
     if source == "fullrange":
         coef = fullrange_np(n * 1024, 900 + w).reshape(n, 1024)
-        d_coef = _dev(codec, coef)
+        d_coef = dev(codec, coef)
     else:
-        d_cur = _dev(codec, _tiles_mix(w, h, 901 + w))
+        d_cur = dev(codec, _tiles_mix(w, h, 901 + w))
         d_coef = codec.alloc(n * 2048)
         codec.dct32_fwd_from_tiles_dev(d_cur.ptr, d_pred.ptr, w, h, d_coef.ptr)
         codec.stream_sync()
@@ -194,7 +177,7 @@ def test_fused_inverse_into_tiles(codec, oracle, w, h, source):
     py, _, _ = _planes(pred, w, h)
     want = _with(oracle, pred, w, h, y=_clip(py, _unblocks(res, h, w, 32)))
     # two-call path
-    d_res, d_two = codec.alloc(n * 2048), _dev(codec, pred)
+    d_res, d_two = codec.alloc(n * 2048), dev(codec, pred)
     codec.dct32_inv_dev(d_coef.ptr, d_res.ptr, n)
     codec.recon_luma_dev(d_two.ptr, d_res.ptr, w, h, 32, d_two.ptr)
     codec.stream_sync()
@@ -219,14 +202,14 @@ def test_fused_inverse_follows_the_inverse_blocks_per_wave_option(codec, oracle)
     n = (w // 32) * (h // 32)
     pred = _tiles_mix(w, h, 1000)
     coef = extremes_np(n * 1024, 1001)
-    d_pred, d_coef = _dev(codec, pred), _dev(codec, coef)
+    d_pred, d_coef = dev(codec, pred), dev(codec, coef)
     py, _, _ = _planes(pred, w, h)
     want = _with(oracle, pred, w, h, y=_clip(py, _unblocks(oracle.dct32_inv(coef, threads=8), h, w, 32)))
     saved = codec.get_option("dct32_inv_blocks_per_wave")
     try:
         for bpw in (1, 2, 3, 7):
             codec.set_option("dct32_inv_blocks_per_wave", bpw)
-            d_out = _dev(codec, pred)
+            d_out = dev(codec, pred)
             codec.dct32_inv_to_tiles_dev(d_coef.ptr, d_pred.ptr, w, h, d_out.ptr)
             codec.stream_sync()
             assert np.array_equal(d_out.download(np.uint8, pred.nbytes), want), bpw
@@ -242,7 +225,7 @@ def test_whole_ctu_inverse_into_tiles(codec, oracle, w, h, source):
     on whole tiles, m_I untouched"""
     n_ctu = (w // 64) * (h // 64)
     cur, pred = _tiles_mix(w, h, 1100 + w), _tiles_mix(w, h, 1200 + w)
-    d_cur, d_pred = _dev(codec, cur), _dev(codec, pred)
+    d_cur, d_pred = dev(codec, cur), dev(codec, pred)
     if source == "forward":
         d_coef = codec.alloc(n_ctu * 12288)
         codec.dct32_fwd_ctu_from_tiles_dev(d_cur.ptr, d_pred.ptr, w, h, d_coef.ptr)
@@ -250,7 +233,7 @@ def test_whole_ctu_inverse_into_tiles(codec, oracle, w, h, source):
         coef = d_coef.download(np.int16, n_ctu * 6144)
     else:
         coef = fullrange_np(n_ctu * 6144, 1300 + w)
-        d_coef = _dev(codec, coef)
+        d_coef = dev(codec, coef)
     # unfused: the inverse batch of all six blocks, luma re-ordered to frame raster, chroma read in place at block_pitch 6
     d_res = codec.alloc(n_ctu * 12288)
     codec.dct32_inv_dev(d_coef.ptr, d_res.ptr, n_ctu * 6)
@@ -258,7 +241,7 @@ def test_whole_ctu_inverse_into_tiles(codec, oracle, w, h, source):
     res = d_res.download(np.int16, n_ctu * 6144).reshape(n_ctu, 6, 1024)
     assert np.array_equal(res.reshape(-1, 1024), oracle.dct32_inv(coef, threads=8))
     luma = res[:, :4].reshape(h // 64, w // 64, 2, 2, 1024).transpose(0, 2, 1, 3, 4).reshape(-1)
-    d_luma, d_two = _dev(codec, luma), _sentinel(codec, cur.nbytes)
+    d_luma, d_two = dev(codec, luma), _sentinel(codec, cur.nbytes)
     codec.recon_luma_dev(d_pred.ptr, d_luma.ptr, w, h, 32, d_two.ptr)
     codec.recon_chroma_dev(d_pred.ptr, d_res.ptr + 4 * 2048, d_res.ptr + 5 * 2048, w, h, 32, d_two.ptr, 6)
     codec.stream_sync()
@@ -389,10 +372,10 @@ def test_recon_random(codec, oracle, cw, ch, half, kind, pitch, in_place, seed):
     gen = (_res_mix, fullrange_np, extremes_np, residual_np)[kind]
     pred = _tiles_mix(w, h, seed)
     py, pu, pv = _planes(pred, w, h)
-    d_pred = _dev(codec, pred)
+    d_pred = dev(codec, pred)
 
     def run(call):
-        d_out = _dev(codec, pred) if in_place else _sentinel(codec, pred.nbytes)
+        d_out = dev(codec, pred) if in_place else _sentinel(codec, pred.nbytes)
         call(d_out.ptr if in_place else d_pred.ptr, d_out.ptr)
         codec.stream_sync()
         return d_out.download(np.uint8, pred.nbytes)
@@ -402,7 +385,7 @@ def test_recon_random(codec, oracle, cw, ch, half, kind, pitch, in_place, seed):
         if w % (2 * edge if edge == 8 else 32) or h % (2 * edge if edge == 8 else 32):
             continue
         res = gen(npx, seed + edge)
-        d_res = _dev(codec, res)
+        d_res = dev(codec, res)
         got = run(lambda src, dst: codec.recon_luma_dev(src, d_res.ptr, w, h, edge, dst))
         assert np.array_equal(got, _with(oracle, base, w, h, y=_clip(py, _unblocks(res, h, w, edge)))), edge
         if edge == 32:
@@ -418,7 +401,7 @@ def test_recon_random(codec, oracle, cw, ch, half, kind, pitch, in_place, seed):
         both = np.zeros((n, pitch, 2, edge * edge), np.int16)            # U stream and V stream each at `pitch`, V after U's holes
         both[:, 0, 0], both[:, 0, 1] = ru.reshape(n, -1), rv.reshape(n, -1)
         flat = np.concatenate([both[:, :, 0].ravel(), both[:, :, 1].ravel()])
-        d_both = _dev(codec, flat)
+        d_both = dev(codec, flat)
         pv_ptr = d_both.ptr + n * pitch * edge * edge * 2
         got = run(lambda src, dst: codec.recon_chroma_dev(src, d_both.ptr, pv_ptr, w, h, edge, dst, pitch))
         want = _with(oracle, base, w, h, u=_clip(pu, _unblocks(ru, h // 2, w // 2, edge)), v=_clip(pv, _unblocks(rv, h // 2, w // 2, edge)))
@@ -426,7 +409,7 @@ def test_recon_random(codec, oracle, cw, ch, half, kind, pitch, in_place, seed):
     if w % 64 == 0 and h % 64 == 0:
         n_ctu = npx // 4096
         coef = gen(n_ctu * 6144, seed + 7)
-        d_coef = _dev(codec, coef)
+        d_coef = dev(codec, coef)
         got = run(lambda src, dst: codec.dct32_inv_ctu_to_tiles_dev(d_coef.ptr, src, w, h, dst))
         z = oracle.dct32_inv(coef, threads=8).reshape(n_ctu, 6, 1024)
         zy = z[:, :4].reshape(h // 64, w // 64, 2, 2, 1024).transpose(0, 2, 1, 3, 4).reshape(-1, 1024)

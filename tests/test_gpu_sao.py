@@ -10,11 +10,10 @@ import pytest
 import _deblock_ref as D
 import _sao_ref as R
 import x266_amd
-from _arena import Arena
+from _dev import EINVAL, arena_slots, dev, displacements, noise, records, run, sync_or_exit, tile_written, tiles
 from _util import me_frames, splitmix64
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 NAMES = ("xSaoStatsGpu", "xSaoDecideGpu", "xSaoSearchGpu", "xSaoApplyGpu")
 
 
@@ -30,41 +29,6 @@ def test_library_exports_and_binds_the_four_calls():
         assert callable(getattr(x266_amd.Codec, method)), method
 
 
-# ---- data -----------------------------------------------------------------------------------------------------------------------------
-def _tiles(oracle, planes, seed):
-    """the tile array of three planes with random m_I bytes (which no call may read)"""
-    t = oracle.conv_input_fmt(*planes).reshape(-1, 512)
-    t[:, 384:] = (splitmix64(seed, 0, t.shape[0] * 128) & np.uint64(255)).astype(np.uint8).reshape(-1, 128)
-    return t.ravel()
-
-
-def _noise(n, seed):
-    return (splitmix64(seed, 0, n) & np.uint64(255)).astype(np.uint8)
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
-def _sync_or_exit(codec, rc):
-    sync = codec.L.xHipStreamSync(codec.ctx, None)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _run(codec, fn, *args):
-    """a ..._dev call that must succeed, then a sync; a device error ends the session"""
-    try:
-        fn(*args)
-    except x266_amd.X266Error:
-        _sync_or_exit(codec, -2)
-        raise
-    _sync_or_exit(codec, 0)
-
-
 # ---- 1. each call against the statement -----------------------------------------------------------------------------------------------
 @gpu
 @pytest.mark.parametrize("w,h", R.SIZES)
@@ -72,27 +36,27 @@ def test_each_call_against_the_statement(codec, oracle, w, h):
     """every kind of the recipe, three lambdas: statistics, the decision on them, the fused search with and without d_stats, and apply
     over a random pre-fill (m_I and everything outside the planes untouched); all inputs unchanged"""
     n = codec.ctu_count(w, h)
-    base = _noise(w * h * 2, 77)
+    base = noise(w * h * 2, 77)
     for kind in R.KINDS:
         org_p, dec_p = R.case(kind, w, h)
-        org, dec = _tiles(oracle, org_p, 60 + h), _tiles(oracle, dec_p, 61 + h)
+        org, dec = tiles(oracle, org_p, 60 + h), tiles(oracle, dec_p, 61 + h)
         want_stats = R.stats(org_p, dec_p)
         words = R.stats_words(want_stats)
-        d_org, d_dec, d_stats = _dev(codec, org), _dev(codec, dec), _dev(codec, _noise(n * 1152, 78))
-        _run(codec, codec.sao_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_stats.ptr)
+        d_org, d_dec, d_stats = dev(codec, org), dev(codec, dec), dev(codec, noise(n * 1152, 78))
+        run(codec, codec.sao_stats_dev, d_org.ptr, d_dec.ptr, w, h, d_stats.ptr)
         assert np.array_equal(d_stats.download(np.int32, n * 288), words), kind
         for lam in R.LAMBDAS:
             want = R.decide(want_stats, lam).ravel()
-            d_par, d_par2, d_par3 = (_dev(codec, _noise(n * 24, 79 + i)) for i in range(3))
-            d_stats2 = _dev(codec, _noise(n * 1152, 83))
-            _run(codec, codec.sao_decide_dev, d_stats.ptr, n, lam, d_par.ptr)
-            _run(codec, codec.sao_search_dev, d_org.ptr, d_dec.ptr, w, h, lam, d_par2.ptr, d_stats2.ptr)
-            _run(codec, codec.sao_search_dev, d_org.ptr, d_dec.ptr, w, h, lam, d_par3.ptr, 0)
+            d_par, d_par2, d_par3 = (dev(codec, noise(n * 24, 79 + i)) for i in range(3))
+            d_stats2 = dev(codec, noise(n * 1152, 83))
+            run(codec, codec.sao_decide_dev, d_stats.ptr, n, lam, d_par.ptr)
+            run(codec, codec.sao_search_dev, d_org.ptr, d_dec.ptr, w, h, lam, d_par2.ptr, d_stats2.ptr)
+            run(codec, codec.sao_search_dev, d_org.ptr, d_dec.ptr, w, h, lam, d_par3.ptr, 0)
             for d in (d_par, d_par2, d_par3):
                 assert np.array_equal(d.download(np.uint8, n * 24), want), (kind, lam)
             assert np.array_equal(d_stats2.download(np.int32, n * 288), words), (kind, lam)
-            d_out = _dev(codec, base)
-            _run(codec, codec.sao_apply_dev, d_dec.ptr, w, h, d_par.ptr, d_out.ptr)
+            d_out = dev(codec, base)
+            run(codec, codec.sao_apply_dev, d_dec.ptr, w, h, d_par.ptr, d_out.ptr)
             assert np.array_equal(d_out.download(np.uint8, base.size), R.apply_tiles(oracle, dec, want, w, h, base)), (kind, lam)
             assert np.array_equal(d_par.download(np.uint8, n * 24), want), (kind, lam)
         assert np.array_equal(d_org.download(np.uint8, org.size), org) and np.array_equal(d_dec.download(np.uint8, dec.size), dec), kind
@@ -121,7 +85,7 @@ def test_hand_written_parameters(codec, oracle):
         pick = ((r >> np.uint64(8)) & np.uint64(7)).astype(np.int64)
         ends = ((r >> np.uint64(16)) & np.uint64(15)).astype(np.uint8)
         planes.append(np.where(pick == 0, ends, np.where(pick == 1, 255 - ends, p)).astype(np.uint8))
-    dec = _tiles(oracle, planes, 90)
+    dec = tiles(oracle, planes, 90)
     params = np.zeros((6, 3, 8), np.uint8)
     params[0] = [_record(1, 30, (127, -127, 5, -128)), _record(2, 0xFE, (127, -128, 100, -100)), _record(1, 0xFF, (-7, 7, -127, 127))]
     params[1] = [_record(2, 0x47, (-128, 127, -3, 3)), _record(1, 29, (1, 2, 3, 4)), _record(2, 0x81, (9, -9, 9, -9))]
@@ -130,12 +94,12 @@ def test_hand_written_parameters(codec, oracle):
     params[4] = [_record(1, 31, (-128, -128, -128, -128)), _record(2, 3, (2, 1, -1, -2)), _record(4, 0, (1, 1, 1, 1))]
     params[5] = [_record(2, 2, (6, 0, 0, -6)), _record(2, 0xFC, (127, 0, 0, -128)), _record(2, 0x07, (0, 127, -128, 0))]
     params[:, :, 6:] = 0xA5                                                 # zero[] is not read
-    base = _noise(w * h * 2, 91)
+    base = noise(w * h * 2, 91)
     want = R.apply_tiles(oracle, dec, params, w, h, base)
     changed = (want.reshape(-1, 512)[:, :384] != dec.reshape(-1, 512)[:, :384])
     assert changed.any() and (want.reshape(-1, 512)[:, :384][changed] == 0).any() and (want.reshape(-1, 512)[:, :384][changed] == 255).any()
-    d_in, d_par, d_out = _dev(codec, dec), _dev(codec, params), _dev(codec, base)
-    _run(codec, codec.sao_apply_dev, d_in.ptr, w, h, d_par.ptr, d_out.ptr)
+    d_in, d_par, d_out = dev(codec, dec), dev(codec, params), dev(codec, base)
+    run(codec, codec.sao_apply_dev, d_in.ptr, w, h, d_par.ptr, d_out.ptr)
     assert np.array_equal(d_out.download(np.uint8, base.size), want)
     assert np.array_equal(d_in.download(np.uint8, dec.size), dec) and np.array_equal(d_par.download(np.uint8, params.size), params.ravel())
 
@@ -145,13 +109,7 @@ def _coding_inputs(oracle, w, h, seed):
     cur_y, ref_y = me_frames(w, h, 0, seed, mv=(-3, 2), noise=5)
     cur_u, ref_u = me_frames(w // 2, h // 2, 0, seed + 1, mv=(-1, 1), noise=5)
     cur_v, ref_v = me_frames(w // 2, h // 2, 0, seed + 2, mv=(-1, 1), noise=5)
-    return _tiles(oracle, (cur_y, cur_u, cur_v), seed + 3), _tiles(oracle, (ref_y, ref_u, ref_v), seed + 4)
-
-
-def _records(mv):
-    rec = np.zeros((len(mv), 4), np.int16)
-    rec[:, :2] = mv
-    return rec
+    return tiles(oracle, (cur_y, cur_u, cur_v), seed + 3), tiles(oracle, (ref_y, ref_u, ref_v), seed + 4)
 
 
 @gpu
@@ -161,15 +119,15 @@ def test_chain_behind_coding_and_deblocking(codec, oracle):
     w, h, n = 128, 64, codec.ctu_count(128, 64)
     cur, pred = _coding_inputs(oracle, w, h, 900)
     side = D.case("blocks", w, h)[3]
-    dc, dp, dl, dn = _dev(codec, cur), _dev(codec, pred), codec.alloc(n * 12288), codec.alloc(n * 24)
-    d_intra, d_mv = _dev(codec, side.intra), _dev(codec, _records(side.mv))
-    _run(codec, codec.dct32_code_ctu_tiles_dev, dc.ptr, dp.ptr, w, h, 0, 44, 171, dl.ptr, dn.ptr, dp.ptr)
-    _run(codec, codec.deblock_dev, dp.ptr, w, h, codec.deblock_params(0, d_intra.ptr, dn.ptr, 0, d_mv.ptr, 44, 0, 0), dp.ptr)
+    dc, dp, dl, dn = dev(codec, cur), dev(codec, pred), codec.alloc(n * 12288), codec.alloc(n * 24)
+    d_intra, d_mv = dev(codec, side.intra), dev(codec, records(side.mv))
+    run(codec, codec.dct32_code_ctu_tiles_dev, dc.ptr, dp.ptr, w, h, 0, 44, 171, dl.ptr, dn.ptr, dp.ptr)
+    run(codec, codec.deblock_dev, dp.ptr, w, h, codec.deblock_params(0, d_intra.ptr, dn.ptr, 0, d_mv.ptr, 44, 0, 0), dp.ptr)
     deblocked = dp.download(np.uint8, w * h * 2)
-    base = _noise(w * h * 2, 92)
-    d_par, d_sao = codec.alloc(n * 24), _dev(codec, base)
-    _run(codec, codec.sao_search_dev, dc.ptr, dp.ptr, w, h, 4, d_par.ptr, 0)
-    _run(codec, codec.sao_apply_dev, dp.ptr, w, h, d_par.ptr, d_sao.ptr)
+    base = noise(w * h * 2, 92)
+    d_par, d_sao = codec.alloc(n * 24), dev(codec, base)
+    run(codec, codec.sao_search_dev, dc.ptr, dp.ptr, w, h, 4, d_par.ptr, 0)
+    run(codec, codec.sao_apply_dev, dp.ptr, w, h, d_par.ptr, d_sao.ptr)
     want_par = R.decide(R.stats_tiles(oracle, cur, deblocked, w, h), 4)
     assert want_par[:, :, 0].any()                                          # the chain does filter something
     assert np.array_equal(d_par.download(np.uint8, n * 24), want_par.ravel())
@@ -177,7 +135,7 @@ def test_chain_behind_coding_and_deblocking(codec, oracle):
     assert np.array_equal(got, R.apply_tiles(oracle, deblocked, want_par, w, h, base))
     assert np.array_equal(dp.download(np.uint8, w * h * 2), deblocked) and np.array_equal(dc.download(np.uint8, w * h * 2), cur)
     d_next = codec.alloc(w * h * 2)
-    _run(codec, codec.motion_comp_qpel_dev, d_sao.ptr, d_mv.ptr, w, h, d_next.ptr)
+    run(codec, codec.motion_comp_qpel_dev, d_sao.ptr, d_mv.ptr, w, h, d_next.ptr)
 
 
 @gpu
@@ -186,7 +144,7 @@ def test_code_deblock_and_sao_in_one_graph(codec, oracle):
     w, h, n = 128, 64, codec.ctu_count(128, 64)
     frames = [_coding_inputs(oracle, w, h, 910 + 10 * i) for i in range(3)]
     side = D.case("steps", w, h)[3]
-    d_intra, d_mv = _dev(codec, side.intra), _dev(codec, _records(side.mv))
+    d_intra, d_mv = dev(codec, side.intra), dev(codec, records(side.mv))
     dc, dp, dl, dn = codec.alloc(w * h * 2), codec.alloc(w * h * 2), codec.alloc(n * 12288), codec.alloc(n * 24)
     d_par, d_stats, d_sao = codec.alloc(n * 24), codec.alloc(n * 1152), codec.alloc(w * h * 2)
     params = codec.deblock_params(0, d_intra.ptr, dn.ptr, 0, d_mv.ptr, 44, 0, 0)
@@ -204,9 +162,7 @@ def test_code_deblock_and_sao_in_one_graph(codec, oracle):
             d_sao.upload(np.zeros(w * h * 2, np.uint8))
 
         def results():
-            rc = codec.L.xHipStreamSync(codec.ctx, st)
-            if rc != 0:
-                pytest.exit("device error (sync %d): %s" % (rc, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
+            sync_or_exit(codec, 0, st)
             return d_sao.download(np.uint8, w * h * 2), d_par.download(np.uint8, n * 24), d_stats.download(np.int32, n * 288)
 
         eager = []
@@ -243,30 +199,15 @@ OUTPUTS = {"xSaoStatsGpu": ("d_stats",), "xSaoDecideGpu": ("d_param",), "xSaoSea
 @pytest.fixture(scope="module")
 def arena_case(oracle):
     org_p, dec_p = R.case("sharp3", AW, AH)
-    org, dec = _tiles(oracle, org_p, 804), _tiles(oracle, dec_p, 805)
+    org, dec = tiles(oracle, org_p, 804), tiles(oracle, dec_p, 805)
     st = R.stats(org_p, dec_p)
     par = R.decide(st, ALAM)
     return {"d_org": org, "d_dec": dec, "d_in": dec, "d_stats": R.stats_words(st), "d_param": par.ravel(), "oracle": oracle}
 
 
-def _displacements(name, halved=None):
-    """every pointer at exactly its documented alignment and no more (odd multiples, varying between the buffers); `halved`: that one
-    at half its alignment"""
-    return {p: (align // 2, align // 2) if p == halved else (align * (2 * i + 1), align) for i, (p, align) in enumerate(PTRS[name].items())}
-
-
 def _arena(codec, arena_case, name, disp, guard_seed):
-    a, s = Arena(codec), {}
-    for i, p in enumerate(PTRS[name]):
-        if p in OUTPUTS[name]:
-            nbytes, written = arena_case[p].nbytes if p != "d_out" else AW * AH * 2, None
-            if p == "d_out":
-                written = np.zeros((AW * AH * 2 // 512, 512), bool)
-                written[:, :384] = True
-            s[p] = a.output(p, nbytes, disp[p][1], disp[p][0], written=None if written is None else written.ravel())
-        else:
-            s[p] = a.input(p, arena_case[p], disp[p][1], disp[p][0], guard_seed + i)
-    return a, s
+    return arena_slots(codec, PTRS[name], OUTPUTS[name], arena_case, disp, guard_seed, written={"d_out": tile_written(AW * AH // 256, "both")},
+                       sizes={"d_out": AW * AH * 2})
 
 
 def _call_arena(codec, name, s):
@@ -279,7 +220,7 @@ def _call_arena(codec, name, s):
         rc = L.xSaoSearchGpu(codec.ctx, s["d_org"].ptr, s["d_dec"].ptr, AW, AH, ALAM, s["d_param"].ptr, s["d_stats"].ptr, None)
     else:
         rc = L.xSaoApplyGpu(codec.ctx, s["d_in"].ptr, AW, AH, s["d_param"].ptr, s["d_out"].ptr, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -288,7 +229,7 @@ def _call_arena(codec, name, s):
 def test_minimum_alignment(codec, arena_case, name):
     results = []
     for guard_seed in (31, 51):
-        a, s = _arena(codec, arena_case, name, _displacements(name), guard_seed)
+        a, s = _arena(codec, arena_case, name, displacements(PTRS[name]), guard_seed)
         assert _call_arena(codec, name, s) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()                                                     # guards, m_I of d_out, inputs
         for p in OUTPUTS[name]:
@@ -306,7 +247,7 @@ def test_minimum_alignment(codec, arena_case, name):
 @gpu
 @pytest.mark.parametrize("name,ptr", [(n, p) for n in NAMES for p in PTRS[n]])
 def test_half_alignment_is_rejected(codec, arena_case, name, ptr):
-    a, s = _arena(codec, arena_case, name, _displacements(name, halved=ptr), 33)
+    a, s = _arena(codec, arena_case, name, displacements(PTRS[name], halved=ptr), 33)
     assert _call_arena(codec, name, s) == EINVAL
     assert name.encode() in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
@@ -317,7 +258,7 @@ def test_argument_errors(codec):
     """one refused call per rule, for every call; a refused call launches nothing and names itself"""
     L, ctx = codec.L, codec.ctx
     buf = codec.alloc(8 << 20)
-    fill = _noise(8 << 20, 95)
+    fill = noise(8 << 20, 95)
     buf.upload(fill)
     o, d, out = buf.ptr + (1 << 20), buf.ptr + (2 << 20), buf.ptr + (3 << 20)    # 64x64 tile arrays (8 KiB each)
     st, par = buf.ptr + (4 << 20), buf.ptr + (5 << 20)                      # 1152 and 24 bytes per CTU
@@ -360,5 +301,5 @@ def test_argument_errors(codec):
     for rc in (L.xSaoDecideGpu(ctx, V(st), 0, 0, V(par), None), L.xSaoDecideGpu(ctx, V(st), 1, 65535, V(par), None),
                L.xSaoStatsGpu(ctx, V(o), V(o), 64, 64, V(st), None), L.xSaoSearchGpu(ctx, V(o), V(o), 64, 64, 65535, V(par), None, None),
                L.xSaoApplyGpu(ctx, V(d), 64, 64, V(par), V(out), None)):
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)

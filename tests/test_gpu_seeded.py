@@ -10,11 +10,11 @@ import pytest
 import _seeded_ref as R
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, call_struct, same, sync_or_exit
 from _util import Oracle
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 PTRS = {"d_cur": 16, "d_ref": 16, "d_seed": 8, "d_best": 8, "d_j": 4}
 DISP = {name: align * (2 * i + 1) for i, (name, align) in enumerate(PTRS.items())}          # exactly the documented alignment, no more
 CENTRES = [0, 31, 1, 2, 4, 8, 16]
@@ -25,17 +25,6 @@ LAMBDAS = [0, 16, 200, 65535]
 @functools.lru_cache(None)
 def _oracle():
     return Oracle()
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _same(got, want, what):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad[:8], got[bad[:8]], want[bad[:8]])
 
 
 @functools.lru_cache(None)
@@ -83,9 +72,7 @@ def seeded(codec, cur_tiles, ref_tiles, w, h, seeds, scale, centres, r, lam, wit
     best = a.output("d_best", 8 * nb, 8, DISP["d_best"])
     dj = a.output("d_j", 4 * nb, 4, DISP["d_j"]) if with_j else None
     p = codec.seed_params(w, h, scale, centres, r, lam, d_cur=cur.ptr, d_ref=ref.ptr, d_seed=seed.ptr, d_best=best.ptr, d_j=dj.ptr if with_j else 0)
-    rc = codec.L.xSatd8x8SeededSearchGpu(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, codec.L.xHipLastError(codec.ctx)
+    call_struct(codec, "xSatd8x8SeededSearchGpu", p, stream)
     got = a.check()                                                         # guard bands, and every input unchanged
     return got["d_best"].view(R.ME_DTYPE), got["d_j"].view(np.uint32) if with_j else None
 
@@ -95,9 +82,9 @@ def check_case(codec, kind, w, h, seed_kind, scale, centres, r, lam, **kw):
     best, j = want(kind, w, h, seed_kind, scale, centres, r, lam)
     got, got_j = seeded(codec, cur_t, ref_t, w, h, seeds_of(seed_kind, w, h, scale), scale, centres, r, lam, **kw)
     what = (kind, w, h, seed_kind, scale, centres, r, lam)
-    _same(got, best, ("d_best",) + what)
+    same(got, best, ("d_best",) + what)
     if got_j is not None:
-        _same(got_j, j, ("d_j",) + what)
+        same(got_j, j, ("d_j",) + what)
     return got, got_j
 
 
@@ -150,8 +137,8 @@ def test_one_frame_as_both_and_without_d_j(codec):
         s = seeds_of("small", w, h, scale)
         best, j, _ = R.search(_oracle(), cur, cur, s, scale, 31, 2, 16)
         got, got_j = seeded(codec, cur_t, None, w, h, s, scale, 31, 2, 16, same_frame=True)
-        _same(got, best, "d_best, one frame")
-        _same(got_j, j, "d_j, one frame")
+        same(got, best, "d_best, one frame")
+        same(got_j, j, "d_j, one frame")
         with_j, _ = check_case(codec, "random", w, h, "small", scale, 31, 2, 16)
         without, none = seeded(codec, cur_t, ref_t, w, h, s, scale, 31, 2, 16, with_j=False)
         assert none is None and with_j.tobytes() == without.tobytes()
@@ -165,7 +152,7 @@ def test_a_zero_seed_is_the_exhaustive_search_at_range_8(codec, w, h):
         nb = (w // 8) * (h // 8)
         got, j = seeded(codec, cur_t, ref_t, w, h, np.zeros((nb, 2), np.int16), 0, 0, 8, 0)
         mv, cost, _ = codec.search_tiles(cur_t, ref_t, w, h, 8)
-        _sync_or_exit(codec, 0)
+        sync_or_exit(codec, 0)
         assert np.array_equal(got["mvx"], mv[:, 0]) and np.array_equal(got["mvy"], mv[:, 1]), kind
         assert np.array_equal(got["cost"], cost) and np.array_equal(j, cost), kind
 
@@ -182,7 +169,7 @@ def test_range_0_is_the_centre_entry_of_the_refinement(codec, scale):
         assert np.abs(vec).max() <= 8183
         got, j = seeded(codec, cur_t, ref_t, w, h, s, scale, 0, 0, 0)
         _, _, costs = codec.refine_qpel_tiles(cur_t, ref_t, w, h, vec.astype(np.int16), want_costs=True)
-        _sync_or_exit(codec, 0)
+        sync_or_exit(codec, 0)
         assert np.array_equal(got["mvx"], vec[:, 0]) and np.array_equal(got["mvy"], vec[:, 1])
         assert np.array_equal(got["cost"], costs[:, 24]) and np.array_equal(j, costs[:, 24])
 
@@ -201,11 +188,11 @@ def test_seeded_search_and_refinement_in_one_graph(codec):
     fill()
     codec.satd_seeded_search_dev(p)
     codec.satd_refine_qpel_from_tiles_dev(d_cur.ptr, d_ref.ptr, w, h, d_best.ptr, d_q.ptr)
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     plain = grab()
     best, j = want("random", w, h, "small", scale, 31, 2, 16)
-    _same(plain[0].view(R.ME_DTYPE), best, "d_best, plain")
-    _same(plain[1].view(np.uint32), j, "d_j, plain")
+    same(plain[0].view(R.ME_DTYPE), best, "d_best, plain")
+    same(plain[1].view(np.uint32), j, "d_j, plain")
     st = codec.stream_create()
     try:
         codec.graph_begin(st)                                                # no xHipMeScratchReserve: neither call uses the scratch
@@ -216,7 +203,7 @@ def test_seeded_search_and_refinement_in_one_graph(codec):
             for _ in range(2):
                 fill()
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 for a, b, what in zip(grab(), plain, ("d_best", "d_j", "the refined field")):
                     assert a.tobytes() == b.tobytes(), what
         finally:
@@ -274,7 +261,7 @@ def test_argument_errors(codec):
                 refused(**{field: good[other] + (extent[other] - 1) // PTRS[field] * PTRS[field]})   # onto the other's last bytes
                 refused(**{field: good[other]})
     refused(seed_scale=0, d_best=good["d_seed"] + 8 * nb - 8)                # the seeds' extent follows the scale
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     assert np.array_equal(buf.download(np.uint8, fill.size), fill)          # nothing was launched
     # the edges of what is accepted: d_j NULL, one frame as both, every scalar at either end of its range
     _, _, cur_t, ref_t = frames("random", w, h)
@@ -288,11 +275,11 @@ def test_argument_errors(codec):
         buf.upload(image)
         p = codec.seed_params(**dict(good, seed_scale=scale, centres=centres, range=r, lambda_q4=lam, d_j=0, d_ref=good["d_cur"] if one else good["d_ref"]))
         rc = L.xSatd8x8SeededSearchGpu(ctx, ctypes.byref(p), None)
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, L.xHipLastError(ctx)
         now = buf.download(np.uint8, fill.size)
         cur, ref, _, _ = frames("random", w, h)
         best, _, _ = R.search(_oracle(), cur, cur if one else ref, s, scale, centres, r, lam)
-        _same(now[4 * M:4 * M + 8 * nb].view(R.ME_DTYPE), best, ("d_best", scale, centres, r, lam, one))
+        same(now[4 * M:4 * M + 8 * nb].view(R.ME_DTYPE), best, ("d_best", scale, centres, r, lam, one))
         now[4 * M:4 * M + 8 * nb] = image[4 * M:4 * M + 8 * nb]
         assert np.array_equal(now, image)                                    # ... and nothing else was written, d_j's region included

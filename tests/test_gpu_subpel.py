@@ -9,42 +9,15 @@ import pytest
 
 import _quant_ref as Q
 import _subpel_ref as R
-from _arena import Arena
-from _util import me_frames, splitmix64
+from _dev import EINVAL, arena_slots, dev, displacements, records, sentinels, sync_or_exit, tile_written, tiles
+from _util import me_frames
 from test_gpu_mc_chroma import _mv_mix
 
 gpu = pytest.mark.gpu
-EINVAL = -1
 LARGER = [(48, 32), (144, 80), (272, 208)]
 
 
 # ---- data -------------------------------------------------------------------------------------------------------------------------------
-def _tiles(oracle, y, u, v, seed):
-    """the tile array of three planes with random m_I bytes (which no call may read)"""
-    t = oracle.conv_input_fmt(y, u, v).reshape(-1, 512)
-    t[:, 384:] = (splitmix64(seed, 0, t.shape[0] * 128) & np.uint64(255)).astype(np.uint8).reshape(-1, 128)
-    return t.ravel()
-
-
-def _sentinels(w, h, seed=77):
-    return (splitmix64(seed, 0, w * h * 2) & np.uint64(255)).astype(np.uint8)
-
-
-def _records(mv, cost=None):
-    rec = np.zeros((len(mv), 4), np.int16)
-    rec[:, :2] = mv
-    if cost is not None:
-        rec.view(np.uint32)[:, 1] = cost
-    return rec
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
 def _unpack(raw, nb):
     raw = np.ascontiguousarray(raw).view(np.uint8)
     return raw.view(np.int16).reshape(nb, 4)[:, :2].copy(), raw.view(np.uint32).reshape(nb, 2)[:, 1].copy()
@@ -75,10 +48,10 @@ def test_mc_against_the_statement(codec, oracle, w, h):
     is the random pre-fill byte for byte; the fused call equals the statement of both planes"""
     mv = R.vectors(w, h, w * h)
     luma, chroma = R.Counts(4), R.Counts(8)
-    base = _sentinels(w, h)
+    base = sentinels(w, h)
     for n, kind in enumerate(R.KINDS):
         y, u, v = R.planes(kind, w, h, 31 + w + 7 * n)
-        rt = _tiles(oracle, y, u, v, 40 + h)
+        rt = tiles(oracle, (y, u, v), 40 + h)
         luma += R.mc_luma(y, mv)[1]
         chroma += R.mc_chroma(u, v, mv)[2]
         for planes in ("luma", "chroma", "both"):
@@ -92,10 +65,10 @@ def test_mc_against_the_statement(codec, oracle, w, h):
 @pytest.mark.parametrize("w,h", LARGER)
 def test_fused_call_is_luma_then_chroma(codec, oracle, w, h):
     y, u, v = R.planes("random", w, h, 300 + w)
-    rt = _tiles(oracle, y, R.plane("extreme", w // 2, h // 2, 301), v, 302)
+    rt = tiles(oracle, (y, R.plane("extreme", w // 2, h // 2, 301), v), 302)
     mv = R.mv_mix_q((w // 8) * (h // 8), w, h, 303 + h)
-    base = _sentinels(w, h, 78)
-    dr, dm, d_two, d_one = _dev(codec, rt), _dev(codec, _records(mv, 0xFFFFFFFF)), _dev(codec, base), _dev(codec, base)   # the cost field is ignored
+    base = sentinels(w, h, 78)
+    dr, dm, d_two, d_one = dev(codec, rt), dev(codec, records(mv, 0xFFFFFFFF)), dev(codec, base), dev(codec, base)   # the cost field is ignored
     codec.motion_comp_qpel_luma_dev(dr.ptr, dm.ptr, w, h, d_two.ptr)
     codec.motion_comp_qpel_chroma_dev(dr.ptr, dm.ptr, w, h, d_two.ptr)
     codec.motion_comp_qpel_dev(dr.ptr, dm.ptr, w, h, d_one.ptr)
@@ -111,10 +84,10 @@ def test_fused_call_is_luma_then_chroma(codec, oracle, w, h):
 def test_vectors_4m_reproduce_the_integer_calls(codec, oracle, w, h):
     nb = (w // 8) * (h // 8)
     y, u, v = R.planes("random", w, h, 400 + w)
-    rt = _tiles(oracle, y, u, v, 401)
+    rt = tiles(oracle, (y, u, v), 401)
     m = np.clip(_mv_mix(nb, w, h, 402 + h), -8191, 8191).astype(np.int16)
     assert np.abs(m).max() == 8191 and (m & 1).any()
-    base = _sentinels(w, h, 79)
+    base = sentinels(w, h, 79)
     assert np.array_equal(codec.motion_comp_qpel(rt, 4 * m, w, h, base=base), codec.motion_comp(rt, m, w, h, base=base))
     assert np.array_equal(codec.motion_comp_qpel(rt, 4 * m, w, h, base=base, planes="luma"), codec.motion_comp_luma(rt, m, w, h, base=base))
     assert np.array_equal(codec.motion_comp_qpel(rt, 4 * m, w, h, base=base, planes="chroma"),
@@ -126,10 +99,10 @@ def test_zero_vectors_copy_and_a_constant_frame_stays_constant(codec, oracle):
     w, h = 96, 64
     nb = (w // 8) * (h // 8)
     y, u, v = R.planes("random", w, h, 500)
-    rt = _tiles(oracle, y, u, v, 501)
+    rt = tiles(oracle, (y, u, v), 501)
     for planes in ("luma", "chroma", "both"):
         assert np.array_equal(codec.motion_comp_qpel(rt, np.zeros((nb, 2), np.int16), w, h, base=rt, planes=planes), rt)
-    flat = _tiles(oracle, np.full_like(y, 201), np.full_like(u, 255), np.full_like(v, 1), 502)
+    flat = tiles(oracle, (np.full_like(y, 201), np.full_like(u, 255), np.full_like(v, 1)), 502)
     got = codec.motion_comp_qpel(flat, R.mv_mix_q(nb, w, h, 503), w, h).reshape(-1, 512)
     assert (got[:, :256] == 201).all()
     assert (got[:, 256:384:2] == 255).all() and (got[:, 257:384:2] == 1).all()
@@ -173,7 +146,7 @@ def _chroma_for(w, h, seed):
 @pytest.mark.parametrize("w,h", [(16, 16), (48, 32), (144, 80)])
 def test_refinement_against_the_reference(codec, oracle, refine_refs, w, h, source):
     cur, ref, mv_int, want_mv, want_cost, want_costs = refine_refs(w, h, source)
-    ct, rt = _tiles(oracle, cur, *_chroma_for(w, h, 610), 612), _tiles(oracle, ref, *_chroma_for(w, h, 613), 615)
+    ct, rt = tiles(oracle, (cur, *_chroma_for(w, h, 610)), 612), tiles(oracle, (ref, *_chroma_for(w, h, 613)), 615)
     mv, cost, costs = codec.refine_qpel_tiles(ct, rt, w, h, mv_int, want_costs=True)
     assert np.array_equal(costs, want_costs)
     assert np.array_equal(mv, want_mv) and np.array_equal(cost, want_cost)
@@ -185,7 +158,7 @@ def test_refinement_of_constant_frames_returns_the_centre(codec, oracle):
     w, h = 48, 32
     nb = (w // 8) * (h // 8)
     u, v = _chroma_for(w, h, 620)
-    ct, rt = _tiles(oracle, np.full((h, w), 90, np.uint8), u, v, 622), _tiles(oracle, np.full((h, w), 101, np.uint8), u, v, 623)
+    ct, rt = tiles(oracle, (np.full((h, w), 90, np.uint8), u, v), 622), tiles(oracle, (np.full((h, w), 101, np.uint8), u, v), 623)
     m = _mv_mix(nb, w, h, 624)
     mv, cost, costs = codec.refine_qpel_tiles(ct, rt, w, h, m, want_costs=True)
     assert np.array_equal(mv, 4 * np.clip(m, -8191, 8191))
@@ -200,7 +173,7 @@ def test_refinement_recovers_a_fractional_displacement(codec, oracle):
     nb = (w // 8) * (h // 8)
     ref = me_frames(w, h, 0, 630)[0]
     u, v = _chroma_for(w, h, 631)
-    rt = _tiles(oracle, ref, u, v, 633)
+    rt = tiles(oracle, (ref, u, v), 633)
     ct = codec.motion_comp_qpel(rt, np.tile(np.int16([[13, -10]]), (nb, 1)), w, h, base=rt, planes="luma")
     cur = oracle.conv_output_420(ct, w, h)[0]
     assert np.array_equal(cur, R.mc_luma(ref, np.tile(np.int16([[13, -10]]), (nb, 1)))[0])
@@ -219,8 +192,8 @@ def test_refinement_is_consistent_with_the_search(codec, oracle):
     w, h, rng = 144, 80, 8
     nb = (w // 8) * (h // 8)
     cur, ref = me_frames(w, h, 0, 640, mv=(-3, 2), noise=5)
-    ct, rt = _tiles(oracle, cur, *_chroma_for(w, h, 641), 643), _tiles(oracle, ref, *_chroma_for(w, h, 644), 646)
-    dc, dr = _dev(codec, ct), _dev(codec, rt)
+    ct, rt = tiles(oracle, (cur, *_chroma_for(w, h, 641)), 643), tiles(oracle, (ref, *_chroma_for(w, h, 644)), 646)
+    dc, dr = dev(codec, ct), dev(codec, rt)
     d_int, d_best, d_best2, d_costs = codec.alloc(nb * 8), codec.alloc(nb * 8), codec.alloc(nb * 8), codec.alloc(nb * 196)
     codec.satd_search_from_tiles_dev(dc.ptr, dr.ptr, w, h, rng, d_int.ptr)
     codec.satd_refine_qpel_from_tiles_dev(dc.ptr, dr.ptr, w, h, d_int.ptr, d_best.ptr, d_costs.ptr)
@@ -251,16 +224,16 @@ def test_inter_loop_eagerly_and_in_a_graph(codec, oracle):
     cur_y, ref_y = me_frames(w, h, 0, 700, mv=(-4, 2), noise=5)
     cur_u, ref_u = me_frames(w // 2, h // 2, 0, 701, mv=(-2, 1), noise=5)
     cur_v, ref_v = me_frames(w // 2, h // 2, 0, 703, mv=(-2, 1), noise=5)
-    ct, rt = _tiles(oracle, cur_y, cur_u, cur_v, 704), _tiles(oracle, ref_y, ref_u, ref_v, 705)
-    start = _sentinels(w, h, 80)
+    ct, rt = tiles(oracle, (cur_y, cur_u, cur_v), 704), tiles(oracle, (ref_y, ref_u, ref_v), 705)
+    start = sentinels(w, h, 80)
     # the chain from the references
     m = oracle.satd_search(cur_y, np.pad(ref_y, rng, mode="edge"), rng, rng)[0]
     q, q_cost, _ = R.refine(oracle, cur_y, ref_y, m)
     pred = R.mc_tiles(oracle, rt, q, w, h, start)
     want_level, want_nnz, want_recon = Q.code_ctu_tiles(oracle, ct, pred, w, h, None, qp, rounding)
 
-    dc, dr = _dev(codec, ct), _dev(codec, rt)
-    d_int, d_best, dp, dl, dn = codec.alloc(nb * 8), codec.alloc(nb * 8), _dev(codec, start), codec.alloc(n * 12288), codec.alloc(n * 24)
+    dc, dr = dev(codec, ct), dev(codec, rt)
+    d_int, d_best, dp, dl, dn = codec.alloc(nb * 8), codec.alloc(nb * 8), dev(codec, start), codec.alloc(n * 12288), codec.alloc(n * 24)
     st = codec.stream_create()
     try:
         codec._check(codec.L.xHipMeScratchReserve(codec.ctx, st, w, h), "xHipMeScratchReserve")     # the search's; the refinement has none
@@ -296,7 +269,7 @@ def test_inter_loop_eagerly_and_in_a_graph(codec, oracle):
     finally:
         codec.stream_destroy(st)
     # luma SATD from tiles of (cur, quarter-sample pred) against (cur, integer pred)
-    d_q, d_i, ds = _dev(codec, pred), _dev(codec, codec.motion_comp(rt, m, w, h, base=start)), [codec.alloc(nb * 4), codec.alloc(nb * 4)]
+    d_q, d_i, ds = dev(codec, pred), dev(codec, codec.motion_comp(rt, m, w, h, base=start)), [codec.alloc(nb * 4), codec.alloc(nb * 4)]
     codec.satd8x8_from_tiles_dev(dc.ptr, d_q.ptr, w, h, ds[0].ptr)
     codec.satd8x8_from_tiles_dev(dc.ptr, d_i.ptr, w, h, ds[1].ptr)
     codec.stream_sync()
@@ -307,48 +280,28 @@ def test_inter_loop_eagerly_and_in_a_graph(codec, oracle):
 
 
 # ---- 4. arguments and alignment ------------------------------------------------------------------------------------------------------
-def _sync_or_exit(codec, rc):
-    sync = codec.L.xHipStreamSync(codec.ctx, None)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
 MC_CALLS = {"xMotionCompQpelLumaGpu": "luma", "xMotionCompQpelChromaGpu": "chroma", "xMotionCompQpelGpu": "both"}
 MC_PTRS = {"d_ref": 16, "d_mv": 8, "d_pred": 16}
 REFINE_PTRS = {"d_cur": 16, "d_ref": 16, "d_int": 8, "d_best": 8, "d_costs": 4}
 AW, AH = 48, 32
 
 
-def _displacements(ptrs, halved=None):
-    """every pointer at exactly its documented alignment and no more (odd multiples, varying between the buffers); `halved`: that one
-    at half its alignment"""
-    out = {}
-    for i, (name, align) in enumerate(ptrs.items()):
-        out[name] = (align // 2, align // 2) if name == halved else (align * (2 * i + 1), align)
-    return out
-
-
 @pytest.fixture(scope="module")
 def arena_frames(oracle):
     y, u, v = R.planes("random", AW, AH, 800)
     cur = me_frames(AW, AH, 0, 803)[0]
-    return _tiles(oracle, cur, u, v, 804), _tiles(oracle, y, u, v, 805), R.mv_mix_q((AW // 8) * (AH // 8), AW, AH, 806)
+    return tiles(oracle, (cur, u, v), 804), tiles(oracle, (y, u, v), 805), R.mv_mix_q((AW // 8) * (AH // 8), AW, AH, 806)
 
 
 def _mc_case(codec, arena_frames, planes, disp, guard_seed):
     _, rt, mv = arena_frames
-    written = np.zeros((AW * AH * 2 // 512, 512), bool)
-    written[:, {"luma": slice(0, 256), "chroma": slice(256, 384), "both": slice(0, 384)}[planes]] = True
-    a = Arena(codec)
-    s = {"d_ref": a.input("d_ref", rt, disp["d_ref"][1], disp["d_ref"][0], guard_seed),
-         "d_mv": a.input("d_mv", _records(mv), disp["d_mv"][1], disp["d_mv"][0], guard_seed + 1),
-         "d_pred": a.output("d_pred", rt.size, disp["d_pred"][1], disp["d_pred"][0], written=written.ravel())}
-    return a, s
+    return arena_slots(codec, MC_PTRS, ("d_pred",), {"d_ref": rt, "d_mv": records(mv)}, disp, guard_seed,
+                       written={"d_pred": tile_written(AW * AH // 256, planes)}, sizes={"d_pred": rt.size})
 
 
 def _call_mc(codec, name, s, w=AW, h=AH):
     rc = getattr(codec.L, name)(codec.ctx, s["d_ref"].ptr, s["d_mv"].ptr, w, h, s["d_pred"].ptr, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -358,7 +311,7 @@ def test_mc_at_minimum_alignment(codec, oracle, arena_frames, name):
     _, rt, mv = arena_frames
     results = []
     for guard_seed in (31, 32):
-        a, s = _mc_case(codec, arena_frames, MC_CALLS[name], _displacements(MC_PTRS), guard_seed)
+        a, s = _mc_case(codec, arena_frames, MC_CALLS[name], displacements(MC_PTRS), guard_seed)
         assert _call_mc(codec, name, s) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()["d_pred"]                                           # guards, the planes the call does not own, inputs
         base = s["d_pred"].image[s["d_pred"].start:][:rt.size]
@@ -371,7 +324,7 @@ def test_mc_at_minimum_alignment(codec, oracle, arena_frames, name):
 @pytest.mark.parametrize("ptr", list(MC_PTRS))
 @pytest.mark.parametrize("name", list(MC_CALLS))
 def test_mc_half_alignment_is_rejected(codec, arena_frames, name, ptr):
-    a, s = _mc_case(codec, arena_frames, MC_CALLS[name], _displacements(MC_PTRS, halved=ptr), 33)
+    a, s = _mc_case(codec, arena_frames, MC_CALLS[name], displacements(MC_PTRS, halved=ptr), 33)
     assert _call_mc(codec, name, s) == EINVAL
     assert name.encode() in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()
@@ -380,18 +333,13 @@ def test_mc_half_alignment_is_rejected(codec, arena_frames, name, ptr):
 def _refine_arena(codec, arena_frames, disp, guard_seed):
     ct, rt, mv = arena_frames
     nb = (AW // 8) * (AH // 8)
-    a = Arena(codec)
-    s = {"d_cur": a.input("d_cur", ct, disp["d_cur"][1], disp["d_cur"][0], guard_seed),
-         "d_ref": a.input("d_ref", rt, disp["d_ref"][1], disp["d_ref"][0], guard_seed + 1),
-         "d_int": a.input("d_int", _records(mv), disp["d_int"][1], disp["d_int"][0], guard_seed + 2),
-         "d_best": a.output("d_best", nb * 8, disp["d_best"][1], disp["d_best"][0]),
-         "d_costs": a.output("d_costs", nb * 196, disp["d_costs"][1], disp["d_costs"][0])}
-    return a, s
+    return arena_slots(codec, REFINE_PTRS, ("d_best", "d_costs"), {"d_cur": ct, "d_ref": rt, "d_int": records(mv)}, disp, guard_seed,
+                       sizes={"d_best": nb * 8, "d_costs": nb * 196})
 
 
 def _call_refine(codec, s, w=AW, h=AH):
     rc = codec.L.xSatd8x8RefineQpelFromTilesGpu(codec.ctx, s["d_cur"].ptr, s["d_ref"].ptr, w, h, s["d_int"].ptr, s["d_best"].ptr, s["d_costs"].ptr, None)
-    _sync_or_exit(codec, rc)
+    sync_or_exit(codec, rc)
     return rc
 
 
@@ -402,7 +350,7 @@ def test_refinement_at_minimum_alignment(codec, oracle, arena_frames):
     want_mv, want_cost, want_costs = R.refine(oracle, oracle.conv_output_420(ct, AW, AH)[0], oracle.conv_output_420(rt, AW, AH)[0], mv)
     results = []
     for guard_seed in (41, 42):
-        a, s = _refine_arena(codec, arena_frames, _displacements(REFINE_PTRS), guard_seed)
+        a, s = _refine_arena(codec, arena_frames, displacements(REFINE_PTRS), guard_seed)
         assert _call_refine(codec, s) == 0, codec.L.xHipLastError(codec.ctx)
         got = a.check()
         got_mv, got_cost = _unpack(got["d_best"], nb)
@@ -416,7 +364,7 @@ def test_refinement_at_minimum_alignment(codec, oracle, arena_frames):
 @gpu
 @pytest.mark.parametrize("ptr", list(REFINE_PTRS))
 def test_refinement_half_alignment_is_rejected(codec, arena_frames, ptr):
-    a, s = _refine_arena(codec, arena_frames, _displacements(REFINE_PTRS, halved=ptr), 43)
+    a, s = _refine_arena(codec, arena_frames, displacements(REFINE_PTRS, halved=ptr), 43)
     assert _call_refine(codec, s) == EINVAL
     assert b"xSatd8x8RefineQpelFromTilesGpu" in codec.L.xHipLastError(codec.ctx)
     a.check_untouched()

@@ -15,28 +15,15 @@ import _rdoq_ref as R
 import _tdecide_ref as T
 import x266_amd
 from _arena import Arena
+from _dev import EINVAL, call_struct, dev, sync_or_exit
 from test_gpu_transform_ctu_tiles import _slot_mats, _tiles_mix, _wholly_outside, ref_inverse
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 PTRS = {"d_cur": 16, "d_pred": 16, "d_qp": 1, "d_cand": 2, "d_class": 1, "d_level": 16, "d_nnz": 4, "d_stat": 8, "d_cost": 8}
 DISP = {name: align * (2 * i + 1) for i, (name, align) in enumerate(PTRS.items())}          # exactly the documented alignment, no more
 EXTENT = {"d_class": 1, "d_level": 2048, "d_nnz": 4, "d_stat": 16, "d_cost": 128}          # bytes per region of the outputs
 FRAMES = [(64, 64), (80, 48), (144, 80)]
-
-
-def _sync_or_exit(codec, rc, stream=None):
-    sync = codec.L.xHipStreamSync(codec.ctx, stream)
-    if sync != 0 or rc not in (0, EINVAL):                                  # a device error: nothing more is started on this GPU
-        pytest.exit("device error (call %d, sync %d): %s" % (rc, sync, codec.L.xHipLastError(codec.ctx).decode()), returncode=3)
-
-
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
 
 
 @functools.lru_cache(None)
@@ -68,9 +55,7 @@ def decide(codec, cur, pred, w, h, qps=None, qp=32, lam=368, cand_luma=T.CLASSES
             s[name] = a.output(name, each * n, PTRS[name], DISP[name])
     p = codec.tdecide_params(*[s[name].ptr if name in s else 0 for name in PTRS], width=w, height=h, qp=qp, lam=lam, cand_luma=cand_luma,
                              cand_chroma=cand_chroma, class_bits=class_bits)
-    rc = codec.L.xTransformDecideCtuTilesGpu(codec.ctx, ctypes.byref(p), stream)
-    _sync_or_exit(codec, rc, stream)
-    assert rc == 0, codec.L.xHipLastError(codec.ctx)
+    call_struct(codec, "xTransformDecideCtuTilesGpu", p, stream)
     got = a.check()                                                         # guard bands and inputs
     view = {"d_class": np.uint8, "d_level": np.int16, "d_nnz": np.uint32, "d_stat": R.STAT_DTYPE, "d_cost": np.uint64}
     out = {name: got[name].view(view[name]) if name in got else None for name in EXTENT}
@@ -85,8 +70,8 @@ def compose(codec, cur, pred, w, h, qps=None, qp=32, lam=368, cand_luma=T.CLASSE
     n = T.n_regions(w, h)
     masks = T.effective_masks(n, cand_luma, cand_chroma, cand)
     bits = [0] * 16 if class_bits is None else list(class_bits) + [0] * (16 - len(class_bits))
-    dc, dp, dk = _dev(codec, cur), _dev(codec, pred), codec.alloc(max(n, 16))
-    d_qp = _dev(codec, np.asarray(qps, np.uint8)) if qps is not None else None
+    dc, dp, dk = dev(codec, cur), dev(codec, pred), codec.alloc(max(n, 16))
+    d_qp = dev(codec, np.asarray(qps, np.uint8)) if qps is not None else None
     dz, dl, ds = codec.alloc(n * 2048), codec.alloc(n * 2048), codec.alloc(n * 16)
     out = {"d_class": np.zeros(n, np.uint8), "d_level": np.zeros((n, 1024), np.int16), "d_stat": np.zeros(n, R.STAT_DTYPE),
            "d_cost": np.full((n, 16), T.ALL_ONES, np.uint64)}
@@ -97,7 +82,7 @@ def compose(codec, cur, pred, w, h, qps=None, qp=32, lam=368, cand_luma=T.CLASSE
         dk.upload(np.full(max(n, 16), k, np.uint8))
         codec.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr, dz.ptr)
         codec.rdo_quant_dev(codec.rdoq_params(dz.ptr, dl.ptr, dk.ptr, d_qp.ptr if d_qp else 0, 0, ds.ptr, n, qp, lam))
-        _sync_or_exit(codec, 0)
+        sync_or_exit(codec, 0)
         level, stat = dl.download(np.int16, n * 1024).reshape(n, 1024), ds.download(np.uint8, 16 * n).view(R.STAT_DTYPE)
         for r in np.flatnonzero((masks >> k) & 1):
             j = int(stat["dist"][r]) + lam * (int(stat["bits"][r]) + bits[k])
@@ -299,7 +284,7 @@ def test_in_a_graph(codec):
                 dp.upload(data[i][1])
                 outs["d_level"].upload(np.full(n * 1024, 0x5A5A, np.int16))
                 codec.graph_launch(graph, st)
-                _sync_or_exit(codec, 0, st)
+                sync_or_exit(codec, 0, st)
                 for name, each in EXTENT.items():
                     assert outs[name].download(np.uint8, each * n).tobytes() == want[i][name].tobytes(), (i, name)
         finally:
@@ -316,14 +301,14 @@ def test_chain(codec, oracle):
     n = T.n_regions(w, h)
     cur, pred = frames(w, h, "kinds")
     base = _tiles_mix(w, h, 0x7E00)
-    dc, dp, dr = _dev(codec, cur), _dev(codec, pred), _dev(codec, base)
+    dc, dp, dr = dev(codec, cur), dev(codec, pred), dev(codec, base)
     outs = {name: codec.alloc(max(each * n, 16)) for name, each in EXTENT.items()}
     dz = codec.alloc(n * 2048)
     codec.transform_decide_dev(codec.tdecide_params(dc.ptr, dp.ptr, 0, 0, outs["d_class"].ptr, outs["d_level"].ptr, outs["d_nnz"].ptr, outs["d_stat"].ptr,
                                                     outs["d_cost"].ptr, w, h, qp, lam))
     codec.quant_regions_dev(1, outs["d_level"].ptr, dz.ptr, n, outs["d_class"].ptr, 0, qp, 0)
     codec.transform_ctu_to_tiles_dev(dz.ptr, outs["d_class"].ptr, dp.ptr, w, h, dr.ptr)
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     cls, level = outs["d_class"].download(np.uint8, n), outs["d_level"].download(np.int16, n * 1024).reshape(n, 1024)
     nnz, stat = outs["d_nnz"].download(np.uint32, n), outs["d_stat"].download(np.uint8, 16 * n).view(R.STAT_DTYPE)
     want = _ref(oracle, cur, pred, w, h, np.arange(n), qp=qp, lam=lam)
@@ -389,10 +374,10 @@ def test_argument_errors(codec):
             if other != o:
                 refused(**{o: good[other]})
                 refused(**{o: good[other] + (extent[other] - 1) // PTRS[o] * PTRS[o]})
-    _sync_or_exit(codec, 0)
+    sync_or_exit(codec, 0)
     assert np.array_equal(buf.download(np.uint8, 10 * M), fill)             # nothing was launched
     # the edges of what is accepted: d_cur == d_pred, a qp out of range beside d_qp, every optional pointer NULL
     for change in (dict(d_pred=good["d_cur"]), dict(qp=99), dict(d_qp=0, d_cand=0, d_nnz=0, d_stat=0, d_cost=0)):
         rc = L.xTransformDecideCtuTilesGpu(ctx, ctypes.byref(codec.tdecide_params(**dict(good, **change))), None)
-        _sync_or_exit(codec, rc)
+        sync_or_exit(codec, rc)
         assert rc == 0, (change, L.xHipLastError(ctx))

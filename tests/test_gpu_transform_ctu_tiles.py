@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 import x266_amd
+from _dev import dev
+from _quant_ref import _planes, _tiles_mix
 from _util import me_frames, splitmix64
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +27,6 @@ def _count(w, h):
 
 
 # ---- numpy statement ----------------------------------------------------------------------------------------------------------
-def _planes(tiles, w, h):
-    """(y, u, v) planes held by a tile array (the inverse of xConvInputFmt's packing)"""
-    t = np.asarray(tiles, np.uint8).reshape(h // 16, w // 16, 512)
-    y = t[:, :, :256].reshape(h // 16, w // 16, 16, 16).transpose(0, 2, 1, 3).reshape(h, w)
-    c = t[:, :, 256:384].reshape(h // 16, w // 16, 8, 8, 2).transpose(0, 2, 1, 3, 4).reshape(h // 2, w // 2, 2)
-    return y, c[..., 0].copy(), c[..., 1].copy()
-
-
 def _regions_of_planes(y, u, v, w, h):
     """[n_ctus, 6, 32, 32] int16 regions of three int16 planes, zero outside the frame"""
     nx, ny = _ctus(w, h)
@@ -131,16 +125,6 @@ def ref_inverse(oracle, coef, classes, pred, w, h, base, mats=None):
 
 
 # ---- data ---------------------------------------------------------------------------------------------------------------------
-def _tiles_mix(w, h, seed):
-    """m_Y / m_C: a third 0, a third 255, a third random; m_I random bytes"""
-    t = (splitmix64(seed, 0, w * h * 2) & np.uint64(255)).astype(np.uint8).reshape(-1, 512)
-    r = splitmix64(seed + 1, 0, t.shape[0] * 384)
-    kind = r % np.uint64(3)
-    pix = np.select([kind == 0, kind == 1], [np.uint64(0), np.uint64(255)], (r >> np.uint64(8)) & np.uint64(255)).astype(np.uint8)
-    t[:, :384] = pix.reshape(-1, 384)
-    return t.ravel()
-
-
 def _coef_mix(n, seed):
     """int16 coefficients: a quarter each full range, the extremes, small (-256..255) and -1 / 0 / 1"""
     r = splitmix64(seed, 0, n)
@@ -177,24 +161,17 @@ def _encoder_classes(w, h, seed):
     return ((cls & 12) | size).astype(np.uint8).ravel()
 
 
-def _dev(codec, arr):
-    arr = np.ascontiguousarray(arr)
-    d = codec.alloc(max(arr.nbytes, 16))
-    d.upload(arr)
-    return d
-
-
 def _run_forward(codec, cur, pred, w, h, classes):
     n = _count(w, h)
-    dc, dp, dk = _dev(codec, cur), _dev(codec, pred), _dev(codec, classes)
-    dz = _dev(codec, np.full(n * 12288, SENTINEL, np.uint8))
+    dc, dp, dk = dev(codec, cur), dev(codec, pred), dev(codec, classes)
+    dz = dev(codec, np.full(n * 12288, SENTINEL, np.uint8))
     codec.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr, dz.ptr)
     codec.stream_sync()
     return dz.download(np.int16, n * 6144).reshape(n, 6, 1024)
 
 
 def _run_inverse(codec, coef, classes, pred, w, h, base):
-    dz, dk, dp, dr = _dev(codec, coef), _dev(codec, classes), _dev(codec, pred), _dev(codec, base)
+    dz, dk, dp, dr = dev(codec, coef), dev(codec, classes), dev(codec, pred), dev(codec, base)
     codec.transform_ctu_to_tiles_dev(dz.ptr, dk.ptr, dp.ptr, w, h, dr.ptr)
     codec.stream_sync()
     return dr.download(np.uint8, base.size)
@@ -228,7 +205,7 @@ def test_forward_and_inverse_against_numpy(codec, oracle, w, h):
     base = np.full(pred.size, SENTINEL, np.uint8)                        # m_I must keep the sentinel
     assert np.array_equal(_run_inverse(codec, coef, cls, pred, w, h, base), ref_inverse(oracle, coef, cls, pred, w, h, base))
     # d_recon == d_pred: the same m_Y / m_C, pred's m_I kept
-    dz, dk, dp = _dev(codec, coef), _dev(codec, cls), _dev(codec, pred)
+    dz, dk, dp = dev(codec, coef), dev(codec, cls), dev(codec, pred)
     codec.transform_ctu_to_tiles_dev(dz.ptr, dk.ptr, dp.ptr, w, h, dp.ptr)
     codec.stream_sync()
     assert np.array_equal(dp.download(np.uint8, pred.size), ref_inverse(oracle, coef, cls, pred, w, h, pred))
@@ -278,14 +255,14 @@ def test_equals_the_tile_transform_on_the_ctu_residual(codec, oracle, w, h):
     cur, pred = _tiles_mix(w, h, 100 + w), _tiles_mix(w, h, 101 + h)
     cls = _classes(n, 102)
     res = _ctu_residual(cur, pred, w, h, cls)
-    dr, dk, dt = _dev(codec, res), _dev(codec, cls), codec.alloc(res.nbytes)
+    dr, dk, dt = dev(codec, res), dev(codec, cls), codec.alloc(res.nbytes)
     codec.transform_tiles_dev(0, dr.ptr, dt.ptr, 6 * n, 0, dk.ptr)
     codec.stream_sync()
     want = dt.download(np.int16, res.size).reshape(n, 6, 1024)
     assert np.array_equal(_run_forward(codec, cur, pred, w, h, cls), want)
     # inverse = xTransformTilesDev(1) followed by the numpy reconstruction
     coef = _coef_mix(n * 6144, 103)
-    dz = _dev(codec, coef)
+    dz = dev(codec, coef)
     codec.transform_tiles_dev(1, dz.ptr, dt.ptr, 6 * n, 0, dk.ptr)
     codec.stream_sync()
     res_back = dt.download(np.int16, coef.size).reshape(-1, 1024)
@@ -298,7 +275,7 @@ def test_all_dct32_equals_the_dct32_ctu_calls(codec, w, h):
     n = _count(w, h)
     cur, pred = _tiles_mix(w, h, 110 + w), _tiles_mix(w, h, 111 + h)
     cls = np.full(6 * n, 3, np.uint8)                                    # X266_TILE_CLASS(X266_TR_DCT2, 32)
-    dc, dp, dk = _dev(codec, cur), _dev(codec, pred), _dev(codec, cls)
+    dc, dp, dk = dev(codec, cur), dev(codec, pred), dev(codec, cls)
     dz = codec.alloc(n * 12288)
     codec.dct32_fwd_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dz.ptr)
     codec.stream_sync()
@@ -306,7 +283,7 @@ def test_all_dct32_equals_the_dct32_ctu_calls(codec, w, h):
     assert np.array_equal(_run_forward(codec, cur, pred, w, h, cls), want)
     coef = _coef_mix(n * 6144, 112)
     dz.upload(coef)
-    dr = _dev(codec, np.full(pred.size, SENTINEL, np.uint8))
+    dr = dev(codec, np.full(pred.size, SENTINEL, np.uint8))
     codec.dct32_inv_ctu_to_tiles_dev(dz.ptr, dp.ptr, w, h, dr.ptr)
     codec.stream_sync()
     base = np.full(pred.size, SENTINEL, np.uint8)
@@ -369,7 +346,7 @@ def test_frames_beyond_4_gib(codec, oracle):
     codec.fill_residual_dev(d_cur.ptr, nt * 256, 0xC0)                  # any bytes are a valid tile array
     codec.fill_residual_dev(d_pred.ptr, nt * 256, 0xC1)
     cls = _classes(n, 0xC2)
-    d_cls = _dev(codec, cls)
+    d_cls = dev(codec, cls)
 
     def fetch(buf, byte_off, count, dtype):
         out = np.empty(count, dtype)
@@ -415,8 +392,8 @@ def test_inter_loop_at_2160p_and_in_a_graph(codec, oracle):
     cls = _encoder_classes(w, h, 1402)
     assert set(np.unique(cls[6 * (n - 1) + 2:6 * (n - 1) + 4] & 3)) <= {0, 1, 2}
     nb = (w // 8) * (h // 8)
-    dc, dr, dk = _dev(codec, cur), _dev(codec, ref), _dev(codec, cls)
-    db, dp, dz = codec.alloc(nb * 8), _dev(codec, ref), codec.alloc(n * 12288)  # pred starts as the reference: co-located chroma
+    dc, dr, dk = dev(codec, cur), dev(codec, ref), dev(codec, cls)
+    db, dp, dz = codec.alloc(nb * 8), dev(codec, ref), codec.alloc(n * 12288)  # pred starts as the reference: co-located chroma
     st = codec.stream_create()
     try:
         codec._check(codec.L.xHipMeScratchReserve(codec.ctx, st, w, h), "xHipMeScratchReserve")
@@ -504,12 +481,12 @@ def test_argument_errors(codec, oracle):
     cls = _classes(n, 142)
     raw = np.zeros(6 * n + 3, np.uint8)
     raw[3:] = cls
-    dc, dp, dk, dz = _dev(codec, cur), _dev(codec, pred), _dev(codec, raw), codec.alloc(n * 12288)
+    dc, dp, dk, dz = dev(codec, cur), dev(codec, pred), dev(codec, raw), codec.alloc(n * 12288)
     codec.transform_ctu_from_tiles_dev(dc.ptr, dp.ptr, w, h, dk.ptr + 3, dz.ptr)
     codec.stream_sync()
     coef = dz.download(np.int16, n * 6144).reshape(n, 6, 1024)
     assert np.array_equal(coef, ref_forward(oracle, cur, pred, w, h, cls))
-    dr = _dev(codec, pred)
+    dr = dev(codec, pred)
     codec.transform_ctu_to_tiles_dev(dz.ptr, dk.ptr + 3, dp.ptr, w, h, dr.ptr)
     codec.stream_sync()
     assert np.array_equal(dr.download(np.uint8, pred.size), ref_inverse(oracle, coef, cls, pred, w, h, pred))
