@@ -79,7 +79,7 @@ int  xHipDeviceInfo(const x266hip_ctx *ctx, char *name, size_t name_cap,
  *                            (2 = the one comparison variant per kernel family north_star asks for)
  *   "dct32_blocks_per_wave", "dct32_inv_blocks_per_wave", "dct32_fwdinv_blocks_per_wave" (1 / 2 / 0 = automatic: 2, or 8 when d_coef is NULL)
  *                            consecutive blocks (tiles, for the transform set's inverses) one wave loops over
- *   "dct32_wg_threads"       workgroup size of the DCT32 / transform-set kernels (64, 128, 192, 256; default 0 = the measured
+ *   "dct32_wg_threads"       workgroup size of the calls listed below (64, 128, 192, 256; default 0 = the measured
  *                            best: 64, and 256 for the fused forward + inverse kernel)
  *   "satd_groups_per_wave", "satd_wg_threads", "satd_lds_bytes_per_wave"
  *                            SATD batch: 32-block groups per wave, workgroup size, LDS charged per wave (= cap on resident
@@ -87,7 +87,8 @@ int  xHipDeviceInfo(const x266hip_ctx *ctx, char *name, size_t name_cap,
  *                            "satd_lds_bytes_per_wave" takes 0 .. 16384 in multiples of 16 (whole 16-byte rows; 16 KiB x the four waves of
  *                            the largest workgroup = the 64 KiB a launch may ask for; values below the kernel's own need are raised to it)
  *   "tile_tiles_per_wave"    xTransformTilesDev: consecutive tiles per wave (0 = 2)
- *   "adaptive_per_wave"      shrink the per-wave run on small batches (default 1)
+ *   "adaptive_per_wave"      shrink the per-wave run on small batches (default 1): a per-wave count is cut to units / (CU count x 40), at
+ *                            least 1, so below CU count x 40 x 2 units (20 480 on 256 CUs) a per-wave option has NO effect unless this is 0
  *   "me_tile_rows"           motion-search tile height in block rows (0, the default: chosen from the frame size and the CU count);
  *                            applies to xSatd8x8SearchDev / xSad8x8SearchDev and their tiled forms ...SearchFromTilesDev alike
  *   "autotune"               0 (default) / 1: boxes differ in which launch shape a few kernels run fastest in (by up to 5 %).  With 1, the FIRST
@@ -101,6 +102,24 @@ int  xHipDeviceInfo(const x266hip_ctx *ctx, char *name, size_t name_cap,
  *                            k of its table -- no timing, so also under capture; the same calls as above keep the default shape -- and
  *                            a family with k or fewer candidates (8 / 5 / 6 / 5) returns X266HIP_EINVAL and launches nothing.
  *                            Setting the option to any value forgets what the context has tuned or counted so far.
+ * The calls that take each option (what one wave takes is a 32x32 block, a tile, a 32-block SATD group; tests/_option_cases.py holds
+ * this list as a table and tests/test_gpu_options.py runs it; the "autotune" families are named above):
+ *   "dct32_variant":                xDct32FwdBatchDev, xDct32FwdBatch, xTransformFwdBatchDev (contiguous 32x32 batches)
+ *   "dct32_blocks_per_wave":        xDct32FwdBatchDev, xDct32FwdBatch, xTransformFwdBatchDev (contiguous 32x32 batches; else one tile per wave)
+ *   "dct32_inv_blocks_per_wave":    xDct32InvBatchDev, xDct32InvBatch, xTransformInvBatchDev, xDct32InvToTilesDev
+ *   "dct32_fwdinv_blocks_per_wave": xDct32FwdInvBatchDev
+ *   "dct32_wg_threads":             xDct32FwdBatchDev, xDct32FwdBatch, xDct32InvBatchDev, xDct32InvBatch, xDct32FwdInvBatchDev,
+ *                                   xTransformFwdBatchDev, xTransformInvBatchDev, xTransformTilesDev, xDct32FwdFromTilesDev,
+ *                                   xDct32FwdChromaFromTilesDev, xDct32FwdCtuFromTilesDev, xDct32InvToTilesDev, xDct32InvCtuToTilesDev,
+ *                                   xDct32CodeCtuTilesGpu, xTransformCtuFromTilesDev, xTransformCtuToTilesDev
+ *   "satd_variant":                 xSatd8x8BatchDev, xSatd8x8Batch, xSatd8x8FromTilesDev (0 / 1 / 3; 2 runs as 0)
+ *   "satd_groups_per_wave":         xSatd8x8BatchDev, xSatd8x8Batch, xDct32SatdFrameDev (the staged body in two-wave workgroups: 0 = 2)
+ *   "satd_wg_threads":              xSatd8x8BatchDev, xSatd8x8Batch
+ *   "satd_lds_bytes_per_wave":      xSatd8x8BatchDev, xSatd8x8Batch
+ *   "tile_tiles_per_wave":          xTransformTilesDev
+ *   "adaptive_per_wave":            every call above that takes a per-wave option
+ *   "me_tile_rows":                 xSatd8x8SearchDev, xSatd8x8SearchFromTilesDev (0, or snapped to 2 / 4 / 8: 1 and 3 run 2, 5 .. 7 run 4);
+ *                                   xSad8x8SearchDev, xSad8x8SearchFromTilesDev (two block rows whatever the value)
  * Rounds 1-3 had sixteen more (cache-policy bits, LDS staging on / off, padding, per-kernel LDS charges, ...): the forms they
  * selected lost their A/Bs (profiles/r01_*.txt) and are gone. */
 int  xHipSetOption(x266hip_ctx *ctx, const char *key, int value);

@@ -16,11 +16,11 @@ SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
 
-def build(tmp_path, driver, extra_flags=()):
-    """(executable, the compiler's CompletedProcess) of tests/cpp/<driver>.cpp"""
+def build(tmp_path, driver, extra_flags=(), source=None):
+    """(executable, the compiler's CompletedProcess) of tests/cpp/<driver>.cpp, or of `source` (a driver a test wrote itself)"""
     exe = os.path.join(str(tmp_path), driver + ("_san" if extra_flags else ""))
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra"] + list(extra_flags) + ["-I", os.path.join(ROOT, "x266_amd", "csrc"),
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", driver + ".cpp")], capture_output=True, text=True)
+                        "-o", exe, str(source) if source else os.path.join(ROOT, "tests", "cpp", driver + ".cpp")], capture_output=True, text=True)
     return exe, r
 
 

@@ -203,10 +203,12 @@ def test_mixed_class_tiles_random(codec, oracle, n_tiles, seed, inverse, tpw, tp
     x = _data(kind, n_tiles, 1024, seed)
     if inverse and kind != 0:
         x = (x >> 2).astype(np.int16)                                    # keep coefficients in a sane range (clipping is still exercised by kind 2)
-    saved = {k: codec.get_option(k) for k in ("tile_tiles_per_wave", "dct32_wg_threads")}
+    saved = {k: codec.get_option(k) for k in ("tile_tiles_per_wave", "dct32_wg_threads", "adaptive_per_wave")}
     try:
         codec.set_option("tile_tiles_per_wave", tpw)
         codec.set_option("dct32_wg_threads", tpb)
+        if tpw >= 2:
+            codec.set_option("adaptive_per_wave", 0)                     # or these sizes run one tile per wave whatever tpw says (tests/_option_cases.py)
         din, dout, dcls = codec.alloc(n_tiles * 2048), codec.alloc(n_tiles * 2048), codec.alloc(max(n_tiles, 16))
         din.upload(x)
         dcls.upload(cls)
@@ -242,9 +244,11 @@ def test_frame_lanes_random(codec, oracle, n_dct, n_satd, kind, seed, gpw):
     """xDct32SatdFrameDev (round 3): both lanes of a frame in one grid, random and ragged counts on either side (zero included),
     random SATD run length per wave -- equal to the oracle's two transforms."""
     x, d = _data(kind, max(n_dct, 1), 1024, seed), _data(kind, max(n_satd, 1), 64, seed + 1)
-    saved = {k: codec.get_option(k) for k in ("satd_groups_per_wave",)}
+    saved = {k: codec.get_option(k) for k in ("satd_groups_per_wave", "adaptive_per_wave")}
     try:
         codec.set_option("satd_groups_per_wave", gpw)
+        if gpw >= 2:
+            codec.set_option("adaptive_per_wave", 0)                     # or these sizes run one group per wave whatever gpw says (tests/_option_cases.py)
         din, dout = codec.alloc(x.nbytes), codec.alloc(x.nbytes)
         sin, sout = codec.alloc(d.nbytes), codec.alloc(max(n_satd, 4) * 4)
         din.upload(x)

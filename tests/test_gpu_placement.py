@@ -140,14 +140,15 @@ def _(oracle, n, shift):
 
 
 @row("xDct32SatdFrameDev", [("d_dct_in", 16), ("d_dct_out", 16), ("d_diff", 16), ("d_satd_out", 16)],
-     product(n=[(1, 31), (2, 33), (3, 255), (7, 257), (9, 289), (17, 1)], satd_variant=[0, 1, 3]))
-def _(oracle, n, satd_variant):
+     product(n=[(1, 31), (2, 33), (3, 255), (7, 257), (9, 289), (17, 1)], satd_variant=[0, 1, 3]) +        # the run length left at 0
+     product(n=[(1, 31), (2, 33), (3, 255), (7, 257), (9, 289), (17, 1)], satd_variant=[0, 1, 3], gpw=[1, 3]))
+def _(oracle, n, satd_variant, gpw=0):
     nd, ns = n
     x, d = _mixed(nd, 1024, 50 + nd), _mixed(ns, 64, 51 + ns)
     return Case({"d_dct_in": x, "d_diff": d},
                 {"d_dct_out": (_b(oracle.dct32_fwd(x)), None), "d_satd_out": (_b(oracle.satd8x8(d)), None)},
                 lambda L, c, p: L.xDct32SatdFrameDev(c, p["d_dct_in"], p["d_dct_out"], nd, p["d_diff"], p["d_satd_out"], ns, None),
-                dict(LOOPS, satd_variant=satd_variant))
+                dict(LOOPS, satd_variant=satd_variant, satd_groups_per_wave=gpw))   # the lanes' run length: 0 = 2, the staged body's default
 
 
 # ---- SATD / SAD batches ------------------------------------------------------------------------------------------------------------

@@ -205,8 +205,9 @@ def test_fused_inverse_follows_the_inverse_blocks_per_wave_option(codec, oracle)
     d_pred, d_coef = dev(codec, pred), dev(codec, coef)
     py, _, _ = _planes(pred, w, h)
     want = _with(oracle, pred, w, h, y=_clip(py, _unblocks(oracle.dct32_inv(coef, threads=8), h, w, 32)))
-    saved = codec.get_option("dct32_inv_blocks_per_wave")
+    saved, adaptive = codec.get_option("dct32_inv_blocks_per_wave"), codec.get_option("adaptive_per_wave")
     try:
+        codec.set_option("adaptive_per_wave", 0)                            # or 91 blocks run one per wave whatever the option says (tests/_option_cases.py)
         for bpw in (1, 2, 3, 7):
             codec.set_option("dct32_inv_blocks_per_wave", bpw)
             d_out = dev(codec, pred)
@@ -215,6 +216,7 @@ def test_fused_inverse_follows_the_inverse_blocks_per_wave_option(codec, oracle)
             assert np.array_equal(d_out.download(np.uint8, pred.nbytes), want), bpw
     finally:
         codec.set_option("dct32_inv_blocks_per_wave", saved)
+        codec.set_option("adaptive_per_wave", adaptive)
 
 
 # ---- 4. whole CTU -----------------------------------------------------------------------------------------------------------------
