@@ -1407,6 +1407,73 @@ typedef struct x266_seed_t {
 } x266_seed_t;
 int xSatd8x8SeededSearchGpu(x266hip_ctx *ctx, const x266_seed_t *p, void *stream);
 
+/* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
+ * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source
+ * frame and a decoded frame, for luma and both chroma planes, computed where the frames live and reduced to 48 bytes per CTU and
+ * 64 bytes per frame.  No upstream counterpart: the SSIM is x264's (its ssim_end1 over 8x8 windows on a grid of 4x4 blocks), as
+ * recalled, in integers; the arithmetic here is the contract.
+ *
+ * Geometry.  Frame sides are positive multiples of 16; tiles are 16x16 in raster order, width / 16 per row; CTUs are
+ * ceil(width / 64) x ceil(height / 64) in raster order.  A tile's luma is m_Y, its chroma m_C: 8 rows of 8 interleaved (U, V)
+ * pairs; m_I is never read.  a is a sample of d_src, b the co-located sample of d_dec.
+ *
+ * SSE, per plane and CTU: the sum of (a - b)^2 over the CTU's in-frame samples, at most 4096 * 65025, which fits uint32.
+ *
+ * SSIM, per plane on the plane's grid of 4x4 blocks: W4 = width / 4 by H4 = height / 4 blocks for luma; a chroma plane is
+ * (width / 2) x (height / 2) samples, its grid width / 8 by height / 8 blocks.  A window sits at every block position (bx, by) with
+ * 0 <= bx < W4 - 1 and 0 <= by < H4 - 1 (the plane's own W4, H4) and covers the 8x8 samples of blocks (bx .. bx + 1, by .. by + 1);
+ * it belongs to the CTU of its top-left block, (bx >> 4, by >> 4) for luma and (bx >> 3, by >> 3) for chroma.  Windows cross tile
+ * and CTU borders freely.  A 16x16 frame has 9 luma windows and 1 window per chroma plane.
+ * Per window, over its 64 samples: S1 = sum a, S2 = sum b, SS = sum (a^2 + b^2), S12 = sum a b, and
+ *   vars  = 64 SS - S1^2 - S2^2            covar = 64 S12 - S1 S2   (signed)
+ *   ln    = 2 S1 S2 + 416                  ld    = S1^2 + S2^2 + 416
+ *   cn    = 2 covar + 235963  (signed)     cd    = vars + 235963
+ *   lq    = (ln << 30) / ld                                  unsigned 64-bit
+ *   cq    = sign(cn) * ((|cn| << 30) / cd)                   the quotient truncates toward zero, as C's / does
+ *   q     = (lq * cq) >> 30                                  an arithmetic shift of the signed 64-bit product: it floors
+ * 416 and 235963 are x264's ssim_c1 and ssim_c2 for 8-bit samples.  Always ln <= ld and |cn| <= cd, so |q| <= 2^30, and no
+ * intermediate passes 2^61.  Identical windows give exactly 2^30; all 0 against all 255 gives 1677; an 8x8 checkerboard of 0 / 255
+ * ((x + y) & 1) against its inverse gives cn = -132935237 and q = -1069943477.
+ * ssim[p] of a CTU's record is the sum of q over the CTU's windows of plane p (Y, U, V), win_y and win_c their counts (the two
+ * chroma planes have the same windows).  With a flag off, that flag's fields are written 0.
+ * d_total[8]: sse Y, U, V, then ssim Y, U, V, then win_y, then win_c, each summed over all CTUs.
+ *
+ * xQualityStatsGpu takes one host struct, read during the call and never from the device; the pointers in it are device pointers
+ * (alignments: the field comments).  It reads d_src and d_dec and writes every record of d_ctu, those of partial CTUs included; then,
+ * if d_total is given, a second launch of ONE workgroup adds the records xQualityTotalsChunk() at a time -- integer sums, no
+ * atomics, the same bytes on every run.  The call allocates nothing, does not synchronise, launches on the caller's stream, can be
+ * captured into a graph, and its result does not depend on any launch option.  It sits after reconstruction or after the last loop
+ * filter of a frame, on the frame the next one will predict from.
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p; a NULL or misaligned d_src, d_dec or d_ctu; a
+ * misaligned d_total; a side that is not a positive multiple of 16; flags that are 0 or have other bits set; a span that does not
+ * fit in the address space; an output overlapping any other buffer of the call (the two inputs may coincide).  The extents are
+ * width * height * 2 (d_src, d_dec), 48 n_ctu (d_ctu) and 64 bytes (d_total). */
+#define X266_QUALITY_SSE  1
+#define X266_QUALITY_SSIM 2
+typedef struct x266_quality_ctu_t {
+    int64_t  ssim[3];      /* Y, U, V: sum of the windows' Q30 values                                       */
+    uint32_t sse[3];       /* Y, U, V: sum of (src - dec)^2 over the CTU's in-frame samples                 */
+    uint32_t win_y, win_c; /* windows counted into ssim[0], and into each of ssim[1], ssim[2]               */
+    uint32_t reserved;     /* written 0                                                                     */
+} x266_quality_ctu_t;      /* 48 bytes */
+typedef struct x266_quality_t {
+    const x266_ref_block_t *d_src;   /* [n_tiles], 16-byte aligned                                          */
+    const x266_ref_block_t *d_dec;   /* [n_tiles], 16-byte aligned; may equal d_src                         */
+    x266_quality_ctu_t *d_ctu;       /* [n_ctu], 16-byte aligned; output                                    */
+    int64_t *d_total;                /* [8] or NULL, 8-byte aligned; output                                 */
+    int width, height;               /* positive multiples of 16                                            */
+    int flags;                       /* X266_QUALITY_SSE | X266_QUALITY_SSIM, not 0                         */
+} x266_quality_t;
+int xQualityStatsGpu(x266hip_ctx *ctx, const x266_quality_t *p, void *stream);
+/* Records the totals' workgroup of xQualityStatsGpu takes per step (a test walks CTU counts around it). */
+int xQualityTotalsChunk(void);
+/* PSNR and SSIM from a frame's totals (host only; reads 8 int64, host memory; plain IEEE double throughout).  For p of Y, U, V:
+ * psnr[p] = 10 log10(65025 N_p / sse_p) with N = width * height for Y and a quarter of it for each chroma plane; psnr[3] is the same
+ * over the three planes' summed SSE and summed samples; 100.0 exactly where the SSE is 0.  ssim[p] = total / (win_p * 2^30), or 1.0
+ * where the plane has no window.  X266HIP_EINVAL: a NULL pointer, a side that is not a positive multiple of 16, a negative SSE, or
+ * window counts that are not the geometry's -- each either 0 (a run without X266_QUALITY_SSIM) or (W4 - 1) * (H4 - 1) of its plane. */
+int xQualityFromTotals(const int64_t total[8], int width, int height, double psnr[4], double ssim[3]);
+
 /* Synthetic residual stream with the reference's stimulus distribution
  * ((rand()&0xFF)-(rand()&0xFF), src_tb/dct32.c:191-193) from a counter-based
  * SplitMix64: sample i = lo8(r) - lo8(r>>8), r = mix(seed+(first_index+i+1)*phi). */

@@ -65,6 +65,16 @@ class AqParams(ctypes.Structure):
 AQ_TILE_DTYPE = np.dtype([(name, "<u4") for name in ("sum_y", "ssq_y", "sum_u", "ssq_u", "sum_v", "ssq_v", "energy", "log2_q8")])
 
 
+class QualityParams(ctypes.Structure):
+    """x266_quality_t of include/x266hip.h"""
+    _fields_ = [("d_src", _P), ("d_dec", _P), ("d_ctu", _P), ("d_total", _P), ("width", ctypes.c_int), ("height", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+# x266_quality_ctu_t of include/x266hip.h
+QUALITY_CTU_DTYPE = np.dtype([("ssim", "<i8", (3,)), ("sse", "<u4", (3,)), ("win_y", "<u4"), ("win_c", "<u4"), ("reserved", "<u4")])
+QUALITY_SSE, QUALITY_SSIM = 1, 2        # X266_QUALITY_SSE, X266_QUALITY_SSIM
+
+
 class LaParams(ctypes.Structure):
     """x266_la_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_src", "d_low", "d_intra", "d_mode", "d_inter0", "d_inter1", "d_block", "d_total", "d_prop", "d_prop_ref0",
@@ -213,6 +223,9 @@ def load_library(path=None):
     L.xAqDecideGpu.argtypes = [_P, ctypes.POINTER(AqParams), _P]
     L.xAqTotalsChunk.argtypes = []
     L.xWeightsFromTotals.argtypes = [_P, _P, ctypes.c_int, ctypes.POINTER(WpParams)]
+    L.xQualityStatsGpu.argtypes = [_P, ctypes.POINTER(QualityParams), _P]
+    L.xQualityTotalsChunk.argtypes = []
+    L.xQualityFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, _P, _P]
     for name in LA_CALLS.values():
         getattr(L, name).argtypes = [_P, ctypes.POINTER(LaParams), _P]
     L.xSatd8x8SeededSearchGpu.argtypes = [_P, ctypes.POINTER(SeedParams), _P]
@@ -1245,6 +1258,10 @@ class Codec:
         if c.size != 8 or r.size != 8 or load_library().xWeightsFromTotals(_P(c.ctypes.data), _P(r.ctypes.data), int(lst), ctypes.byref(wp)) != 0:
             raise X266Error("xWeightsFromTotals: list must be 0 or 1, log2_denom 0..7, and the totals those of two frames of one size")
         return wp
+
+    # -- frame quality: SSE and SSIM per CTU and per frame (the numpy calls are x266_amd.quality's) ---------
+    def quality_stats_dev(self, params, stream=0):
+        self._check(self.L.xQualityStatsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xQualityStatsGpu")
 
     # -- the lookahead: half-size frames, frame costs, the propagation tree --------------------------------
     @staticmethod

@@ -10,7 +10,7 @@
 // and the level rate estimate (rdoq_regions, levels_bits) -- are held the same way by tests/cpp/struct_rules_check.cpp: one description
 // per struct, one walk over every call of every one; a new struct call adds a row to its struct's description there, a new struct a
 // description.  The transform decision (transform_decide, x266_tdecide_t) has a stand-alone driver of the same form,
-// tests/cpp/tdecide_rules_check.cpp.
+// tests/cpp/tdecide_rules_check.cpp, and so has frame quality (quality_stats, x266_quality_t): tests/cpp/quality_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -526,6 +526,33 @@ inline const char *transform_decide(const x266_tdecide_t *p)
                      opt(out("d_stat", p->d_stat, 8, mul(n, 16))), opt(out("d_cost", p->d_cost, 8, mul(n, 128))), in("d_cur", p->d_cur, 16, frame_bytes),
                      in("d_pred", p->d_pred, 16, frame_bytes), opt(in("d_qp", p->d_qp, 1, n)), opt(in("d_cand", p->d_cand, 2, mul(n, 2)))};
     return check(b);
+}
+
+// ---- frame quality ------------------------------------------------------------------------------------------------------------------
+// xQualityStatsGpu: the device pointers are the fields of the host-read x266_quality_t, held by tests/cpp/quality_rules_check.cpp.  It
+// reads d_src and d_dec (which may be the same frame) and writes d_ctu and, if given, d_total: no output may overlap anything.
+constexpr const char *kQualityFlags = "flags must be X266_QUALITY_SSE, X266_QUALITY_SSIM or both";
+inline const char *quality_stats(const x266_quality_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (p->flags == 0 || (p->flags & ~(X266_QUALITY_SSE | X266_QUALITY_SSIM))) return kQualityFlags;
+    const size_t frame_bytes = tile_bytes(p->width, p->height);
+    const Buf b[] = {out("d_ctu", p->d_ctu, 16, mul(ctus(p->width, p->height), sizeof(x266_quality_ctu_t))), opt(out("d_total", p->d_total, 8, 64)),
+                     in("d_src", p->d_src, 16, frame_bytes), in("d_dec", p->d_dec, 16, frame_bytes)};
+    return check(b);
+}
+// xQualityFromTotals (host pointers): the totals of one frame, as xQualityStatsGpu writes them -- a window count is the geometry's, or 0
+// after a run without X266_QUALITY_SSIM
+inline const char *quality_from_totals(const int64_t *total, int w, int h, double *psnr, double *ssim)
+{
+    if (!total || !psnr || !ssim) return kNull;
+    if (const char *why = frame(w, h, 16)) return why;
+    for (int i = 0; i < 3; ++i)
+        if (total[i] < 0) return "an SSE total is negative";
+    const int64_t win_y = ((int64_t)(w / 4) - 1) * ((int64_t)(h / 4) - 1), win_c = ((int64_t)(w / 8) - 1) * ((int64_t)(h / 8) - 1);
+    if ((total[6] != 0 && total[6] != win_y) || (total[7] != 0 && total[7] != win_c)) return "a window count is not the frame's";
+    return nullptr;
 }
 
 // ---- source analysis ----------------------------------------------------------------------------------------------------------------

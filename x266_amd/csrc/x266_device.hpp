@@ -287,6 +287,9 @@ hipError_t launch_transform_decide(const x266_tdecide_t &p, const TileTab *d_tab
 hipError_t launch_aq_stats(const x266_aq_t &p, hipStream_t stream);
 hipError_t launch_aq_decide(const x266_aq_t &p, hipStream_t stream);
 int aq_totals_chunk();
+// frame quality (quality_kernels.hip): the CTU records, then (d_total given) the totals' one workgroup of quality_totals_chunk() records per step
+hipError_t launch_quality_stats(const x266_quality_t &p, hipStream_t stream);
+int quality_totals_chunk();
 // the lookahead (lookahead_kernels.hip): frame cost = the block records, then the totals' one workgroup of la_totals_chunk() blocks per step
 hipError_t launch_la_downscale(const x266_la_t &p, hipStream_t stream);
 hipError_t launch_la_intra_costs(const x266_la_t &p, hipStream_t stream);

@@ -24,6 +24,7 @@
 #include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_levels.hpp"
+#include "x266_quality.hpp"
 #include "x266_rdoq.hpp"
 #include "x266_lookahead.hpp"
 #include "x266_tables.hpp"
@@ -1461,6 +1462,24 @@ int xWeightsFromTotals(const int64_t cur[8], const int64_t ref[8], int list, x26
 {
     if (args::weights_from_totals(cur, ref, list, wp)) return X266HIP_EINVAL;
     for (int plane = 0; plane < 3; ++plane) aq_plane_weight(cur, ref, plane, wp->log2_denom[plane ? 1 : 0], &wp->w[list][plane], &wp->o[list][plane]);
+    return X266HIP_OK;
+}
+
+// ---- frame quality (quality_kernels.hip, x266_quality.hpp) --------------------------------------------------------------------------------------
+int xQualityStatsGpu(x266hip_ctx *ctx, const x266_quality_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::quality_stats(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "frame quality launch", launch_quality_stats(*p, (hipStream_t)stream));
+}
+
+int xQualityTotalsChunk(void) { return quality_totals_chunk(); }
+
+int xQualityFromTotals(const int64_t total[8], int width, int height, double psnr[4], double ssim[3])
+{
+    if (args::quality_from_totals(total, width, height, psnr, ssim)) return X266HIP_EINVAL;
+    quality_from_totals(total, width, height, psnr, ssim);
     return X266HIP_OK;
 }
 
