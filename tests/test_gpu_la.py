@@ -23,8 +23,9 @@ PTRS = {"d_src": 16, "d_low": 16, "d_intra": 4, "d_mode": 1, "d_inter0": 8, "d_i
         "d_prop_ref1": 8, "d_aq_offset": 2, "d_offset": 2, "d_qp": 1}
 DISP = {name: align * (2 * i + 1) for i, (name, align) in enumerate(PTRS.items())}          # exactly the documented alignment, no more
 SIZES = [(32, 32), (64, 32), (32, 64), (96, 160), (160, 96)]
-# n = (w / 16) (h / 16) is a multiple of 4 (both sides are multiples of 32): CHUNK + 4 is the first block count past the totals' step
-TALL = (32, 8 * (CHUNK + 4))
+# n = (w / 16) (h / 16) is a multiple of 4 (both sides are multiples of 32): CHUNK - 4 and CHUNK + 4 are the block counts next to the totals'
+# step, 2 CHUNK + 12 is two full steps and a ragged one
+TALL = [(32, 8 * n) for n in (CHUNK - 4, CHUNK, CHUNK + 4, 2 * CHUNK + 12)]
 KINDS = ["zeros", "ones", "random", "hramp", "vramp", "checker"]
 M_I = np.arange(512) >= 384                                                 # a tile's info bytes: no lookahead call reads or writes them
 
@@ -139,15 +140,17 @@ def test_downscale_and_intra_costs(codec, w, h, kind):
         assert cost.max() >= 2048 and cost.max() <= 32640
 
 
-def test_a_frame_past_the_totals_step(codec):
-    w, h = TALL
-    assert CHUNK == x266_amd.la_totals_chunk() and codec.L.xLaTotalsChunk() == CHUNK and (w // 16) * (h // 16) == CHUNK + 4
+@pytest.mark.parametrize("w,h", TALL)
+def test_a_frame_past_the_totals_step(codec, w, h):
+    n = (w // 16) * (h // 16)
+    assert CHUNK == x266_amd.la_totals_chunk() and codec.L.xLaTotalsChunk() == CHUNK
+    assert n in (CHUNK - 4, CHUNK, CHUNK + 4, 2 * CHUNK + 12)
     tiles, low, cost, mode = ref("random", w, h)
     downscale(codec, tiles, w, h, low)
     intra_costs(codec, low, w, h, cost, mode)
     l0, l1 = lists(cost, 5)
     rec, tot = frame_cost(codec, cost, mode, l0, l1, w, h, 300)
-    assert int(tot[7]) == CHUNK + 4 and tot[2] and tot[3] and tot[4]
+    assert int(tot[7]) == n and tot[2] and tot[3] and tot[4]
     prop = np.random.RandomState(6).randint(0, 1 << 20, rec.size).astype(np.uint64)
     propagate(codec, rec, prop, np.zeros(rec.size, np.uint64), prop.copy(), w, h)
     tree_qp(codec, rec, prop, None, w, h, 512)

@@ -358,13 +358,6 @@ __global__ __launch_bounds__(1024) void alf_sum_stats_kernel(const int32_t *stat
     }
 }
 
-__device__ __forceinline__ int64_t wave_sum(int64_t v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // the cost of one class record (n taps) under coefficients c: sum c_i^2 A_ii + 2 sum_{i<j} c_i c_j A_ij - 256 sum c_i b_i
 template <int N>
 __device__ __forceinline__ int64_t record_cost(const int32_t *rec, const int8_t *coef)

@@ -6,12 +6,13 @@
 // half j & 1 (8 bytes: four (U, V) pairs) -- 384 of the tile's 512 bytes, m_I is never touched.  Sums are v_sad_u8 against 0, squares
 // v_dot4_u32_u8 of a dword with itself, U and V split by their byte masks; the row of 16 lanes is summed by DPP and its first lane
 // writes the 32-byte record.  Totals: ONE workgroup walks the records kAqTotalsChunk at a time, as a linear stream of 16-byte halves --
-// integer sums in a fixed order, no atomics.  Decide: 16 lanes per CTU, one per tile; the quadrant and CTU sums are four xor-shuffles inside the row (aq_ctu_qp).
+// integer sums in a fixed order, no atomics (workgroup_totals, x266_lanes.hpp).  Decide: 16 lanes per CTU, one per tile (ctu_lane, x266_ctu_tiles.hpp); the quadrant and CTU sums are four xor-shuffles inside the row (aq_ctu_qp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "x266_aq.hpp"
+#include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 
 namespace x266 {
@@ -74,8 +75,7 @@ __global__ __launch_bounds__(kAqTotalsThreads) void aq_totals_kernel(const x266_
 {
     constexpr unsigned kWaves = kAqTotalsThreads / 64;
     static_assert(kAqTotalsThreads % 2 == 0 && 4 * kAqTotalsThreads == 2 * kAqTotalsChunk, "a full step is four halves per lane, of one parity");
-    __shared__ uint64_t part[kWaves][8];
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned tid = threadIdx.x;
     const v4i *half = reinterpret_cast<const v4i *>(tile);
     const size_t n_halves = n_tiles * 2;
     uint64_t acc[4] = {0, 0, 0, 0};
@@ -92,50 +92,29 @@ __global__ __launch_bounds__(kAqTotalsThreads) void aq_totals_kernel(const x266_
         add(d);
     }
     for (; j < n_halves; j += kAqTotalsThreads) add(half[j]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint64_t v = acc[k];
-#pragma unroll
-        for (int d = 2; d < 64; d <<= 1) v += (uint64_t)__shfl_xor((long long)v, d, 64);   // lanes of one parity
-        if (lane < 2) part[wave][4 * lane + k] = v;
-    }
-    __syncthreads();
+    const uint64_t all = workgroup_totals<kWaves, 2>(acc, tid);               // slots 0..3 the even lanes' sums, 4..7 the odd lanes': a record's words
     if (tid < 8) {
-        uint64_t all = 0;
-#pragma unroll
-        for (unsigned w = 0; w < kWaves; ++w) all += part[w][tid];
         if (tid < 6) total[tid] = (int64_t)all;                             // the six sums
         if (tid == 7) total[6] = (int64_t)all;                              // log2_q8; word 6 of a record, the energy, has no total
         if (tid == 6) total[7] = (int64_t)n_tiles;
     }
 }
 
-struct AqFrame {
-    unsigned tiles_w, tiles_h, ctus_w;
-    size_t n_ctu;
-};
-
 // a row of 16 lanes per CTU, lane i its tile (i & 3, i >> 2)
-__global__ __launch_bounds__(64 * kAqWavesPerWg) void aq_decide_kernel(const x266_aq_tile_t *__restrict__ tile, const int64_t *__restrict__ total, AqFrame f,
+__global__ __launch_bounds__(64 * kAqWavesPerWg) void aq_decide_kernel(const x266_aq_tile_t *__restrict__ tile, const int64_t *__restrict__ total, TileFrame f,
                                                                        int mode, int strength_q8, int base_qp, int chroma_qp_offset,
                                                                        int16_t *__restrict__ offset, uint8_t *__restrict__ qp)
 {
-    const unsigned lane = threadIdx.x & 63, i = lane & 15;
-    const size_t ctu = ((size_t)blockIdx.x * (64 * kAqWavesPerWg) + threadIdx.x) >> 4;
-    const bool ctu_ok = ctu < f.n_ctu;
-    const size_t cy = ctu / f.ctus_w, cx = ctu % f.ctus_w;
-    const size_t tx = cx * 4 + (i & 3), ty = cy * 4 + (i >> 2);
-    const bool in_frame = ctu_ok && tx < f.tiles_w && ty < f.tiles_h;
+    const CtuLane m = ctu_lane(threadIdx.x, blockIdx.x, kAqWavesPerWg, f);
     const size_t n_tiles = (size_t)f.tiles_w * f.tiles_h;
     const int ref_q8 = aq_ref_q8(mode, mode == 1 ? 0 : total[6], (int64_t)n_tiles);
     int s = 0, n = 0;
-    if (in_frame) {
-        const size_t t = ty * f.tiles_w + tx;
-        s = aq_offset_q8(strength_q8, (int)tile[t].log2_q8, ref_q8);
+    if (m.in_frame) {
+        s = aq_offset_q8(strength_q8, (int)tile[m.t].log2_q8, ref_q8);
         n = 1;
-        if (offset) offset[t] = (int16_t)s;
+        if (offset) offset[m.t] = (int16_t)s;
     }
-    aq_ctu_qp(s, n, lane, ctu_ok, ctu, base_qp, chroma_qp_offset, qp);
+    aq_ctu_qp(s, n, threadIdx.x & 63, m.ctu_ok, m.ctu, base_qp, chroma_qp_offset, qp);
 }
 
 }  // namespace
@@ -155,11 +134,7 @@ hipError_t launch_aq_stats(const x266_aq_t &p, hipStream_t stream)
 
 hipError_t launch_aq_decide(const x266_aq_t &p, hipStream_t stream)
 {
-    AqFrame f;
-    f.tiles_w = (unsigned)(p.width / 16);
-    f.tiles_h = (unsigned)(p.height / 16);
-    f.ctus_w = (f.tiles_w + 3) / 4;
-    f.n_ctu = (size_t)f.ctus_w * ((f.tiles_h + 3) / 4);
+    const TileFrame f = tile_frame(p.width, p.height);
     unsigned wgs = 0;
     if (hipError_t e = wave_grid((f.n_ctu + 3) / 4, kAqWavesPerWg, &wgs)) return e;
     hipLaunchKernelGGL(aq_decide_kernel, dim3(wgs), dim3(64 * kAqWavesPerWg), 0, stream, p.d_tile, p.d_total, f, p.mode, p.strength_q8, p.qp, p.chroma_qp_offset,

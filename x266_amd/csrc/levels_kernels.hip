@@ -4,7 +4,8 @@
 //
 // One wave per region, lane g = CG bit g.  The region's 2 KiB cross an LDS slab of the wave's own: two 1 KiB-linear 16-byte accesses
 // per lane on the global side (the quantiser's shape), four 8-byte LDS accesses per lane -- the four rows of its CG -- on the other.
-// The lane's 16-bit map is formed in scan order, __ballot(map != 0) is cg_mask, a wave prefix sum of popcount(map) places the levels.
+// The lane's 16-bit map is formed in scan order, __ballot(map != 0) is cg_mask, a wave prefix sum of popcount(map) places the levels
+// (wave_exclusive_sum, x266_lanes.hpp).
 // Pack is three launches on one stream: count (records without offsets), scan (offsets and totals: ONE workgroup that walks the
 // records kLevelsScanChunk at a time and carries a running total -- no workgroup ever waits for another, no position is handed out
 // by an atomic, so the bytes depend on the data alone), write (recomputes from the levels, builds the payload in LDS at the stream's
@@ -28,28 +29,6 @@ constexpr unsigned kPayloadSlabBytes = (kLevelsMaxWords + 8) * 2;          // up
 constexpr unsigned kLevelSlabBytes = (kLevelsRegionWords + 16) * 2;
 static_assert(kPayloadSlabBytes % 16 == 0 && kLevelSlabBytes % 16 == 0, "slabs hold whole 16-byte chunks");
 static_assert(sizeof(x266_level_region_t) == 32, "the record is 32 bytes");
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t x)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t y = (uint32_t)__shfl_xor((int)x, o);
-        x = x > y ? x : y;
-    }
-    return x;
-}
-
-// the sum of x over the lanes below this one
-__device__ __forceinline__ uint32_t wave_exclusive_sum(uint32_t x, unsigned lane)
-{
-    uint32_t s = x;
-#pragma unroll
-    for (unsigned o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)s, o);
-        if (lane >= o) s += t;
-    }
-    return s - x;
-}
 
 __device__ __forceinline__ void region_to_lds(const int16_t *level, size_t r, unsigned lane, char *slab)
 {

@@ -9,12 +9,13 @@
 // Intra costs: a wave takes 8 blocks, 8 lanes each, lane y row y.  A lane forms its row of each candidate, transforms the difference
 // along the row, and the columns run across the 8 lanes: three xor-shuffles of four registers holding two 16-bit coefficients each.
 // Frame cost: a lane per block; totals: ONE workgroup walks the records kLaTotalsChunk at a time -- integer sums in a fixed order, no
-// atomics.  Propagate: a lane per block, up to four 64-bit atomic adds (no return value).  Tree qp: 16 lanes per CTU, one per tile, and
-// the source analysis' reduction (aq_ctu_qp).
+// atomics (workgroup_totals, x266_lanes.hpp).  Propagate: a lane per block, up to four 64-bit atomic adds (no return value).  Tree qp: 16
+// lanes per CTU, one per tile (ctu_lane, x266_ctu_tiles.hpp), and the source analysis' reduction (aq_ctu_qp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 #include "x266_lookahead.hpp"
 
@@ -145,8 +146,7 @@ __global__ __launch_bounds__(kLaTotalsThreads) void la_totals_kernel(const x266_
 {
     constexpr unsigned kWaves = kLaTotalsThreads / 64;
     static_assert(2 * kLaTotalsThreads == kLaTotalsChunk, "a full step is two blocks per lane");
-    __shared__ uint64_t part[kWaves][7];
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned tid = threadIdx.x;
     uint64_t acc[7] = {0, 0, 0, 0, 0, 0, 0};
     auto add = [&](size_t j) {
         const v4i r = *reinterpret_cast<const v4i *>(block + j);
@@ -165,23 +165,8 @@ __global__ __launch_bounds__(kLaTotalsThreads) void la_totals_kernel(const x266_
         add(j + kLaTotalsThreads);
     }
     for (; j < n_blocks; j += kLaTotalsThreads) add(j);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        uint64_t v = acc[k];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) v += (uint64_t)__shfl_xor((long long)v, d, 64);
-        if (lane == 0) part[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < 8) {
-        uint64_t all = n_blocks;
-        if (tid < 7) {
-            all = 0;
-#pragma unroll
-            for (unsigned w = 0; w < kWaves; ++w) all += part[w][tid];
-        }
-        total[tid] = (int64_t)all;
-    }
+    const uint64_t all = workgroup_totals<kWaves>(acc, tid);
+    if (tid < 8) total[tid] = (int64_t)(tid < 7 ? all : n_blocks);
 }
 
 // ---- 5. one step of the propagation tree -----------------------------------------------------------------------------------------------------
@@ -205,30 +190,20 @@ __global__ __launch_bounds__(256) void la_propagate_kernel(const x266_la_block_t
 }
 
 // ---- 6. the qp map -------------------------------------------------------------------------------------------------------------------------
-struct LaFrame {
-    unsigned tiles_w, tiles_h, ctus_w;
-    size_t n_ctu;
-};
-
 // a row of 16 lanes per CTU, lane i its tile (i & 3, i >> 2), as the source analysis' decision
 __global__ __launch_bounds__(64 * kLaWavesPerWg) void la_tree_qp_kernel(const x266_la_block_t *__restrict__ block, const uint64_t *__restrict__ prop,
-                                                                        const int16_t *__restrict__ aq_offset, LaFrame f, int strength_q8, int base_qp,
+                                                                        const int16_t *__restrict__ aq_offset, TileFrame f, int strength_q8, int base_qp,
                                                                         int chroma_qp_offset, int16_t *__restrict__ offset, uint8_t *__restrict__ qp)
 {
-    const unsigned lane = threadIdx.x & 63, i = lane & 15;
-    const size_t ctu = ((size_t)blockIdx.x * (64 * kLaWavesPerWg) + threadIdx.x) >> 4;
-    const bool ctu_ok = ctu < f.n_ctu;
-    const size_t cy = ctu / f.ctus_w, cx = ctu % f.ctus_w;
-    const size_t tx = cx * 4 + (i & 3), ty = cy * 4 + (i >> 2);
-    const bool in_frame = ctu_ok && tx < f.tiles_w && ty < f.tiles_h;
+    const CtuLane m = ctu_lane(threadIdx.x, blockIdx.x, kLaWavesPerWg, f);
+    const size_t t = m.t;
     int s = 0, n = 0;
-    if (in_frame) {
-        const size_t t = ty * f.tiles_w + tx;
+    if (m.in_frame) {
         s = la_tree_offset_q8(aq_offset ? (int)aq_offset[t] : 0, la_gain_q8(block[t].intra, prop ? prop[t] : 0, strength_q8));
         n = 1;
         if (offset) offset[t] = (int16_t)s;
     }
-    aq_ctu_qp(s, n, lane, ctu_ok, ctu, base_qp, chroma_qp_offset, qp);
+    aq_ctu_qp(s, n, threadIdx.x & 63, m.ctu_ok, m.ctu, base_qp, chroma_qp_offset, qp);
 }
 
 }  // namespace
@@ -280,11 +255,7 @@ hipError_t launch_la_propagate(const x266_la_t &p, hipStream_t stream)
 
 hipError_t launch_la_tree_qp(const x266_la_t &p, hipStream_t stream)
 {
-    LaFrame f;
-    f.tiles_w = (unsigned)(p.width / 16);
-    f.tiles_h = (unsigned)(p.height / 16);
-    f.ctus_w = (f.tiles_w + 3) / 4;
-    f.n_ctu = (size_t)f.ctus_w * ((f.tiles_h + 3) / 4);
+    const TileFrame f = tile_frame(p.width, p.height);
     unsigned wgs = 0;
     if (hipError_t e = wave_grid((f.n_ctu + 3) / 4, kLaWavesPerWg, &wgs)) return e;
     hipLaunchKernelGGL(la_tree_qp_kernel, dim3(wgs), dim3(64 * kLaWavesPerWg), 0, stream, p.d_block, p.d_prop, p.d_aq_offset, f, p.strength_q8, p.qp,

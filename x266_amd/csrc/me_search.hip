@@ -374,7 +374,7 @@ __global__ __launch_bounds__(WG, WPS) void satd_search_kernel(const MeParams P, 
     for (int blk = wave; blk < NBLK; blk += n_waves) {                 // minimum over the 64 lane slots of a block
         unsigned long long v = slots[blk * 64 + lane];
 #pragma unroll
-        for (int mm = 32; mm >= 1; mm >>= 1) {
+        for (int mm = 32; mm >= 1; mm >>= 1) {                          // wave_min (x266_lanes.hpp) written out: through the call the compiler schedules these kernels, which the benchmark times, differently
             const unsigned long long o = (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)v, mm)
                                          | ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mm) << 32);
             v = o < v ? o : v;

@@ -9,13 +9,15 @@
 // and of the V block), which it stores into the CTU's grid of block sums in LDS: 17x17 luma and 9x9 per chroma plane, three dwords per
 // block.  The grids' last column and row are the halo: a second pass of 144 lanes takes the nine tiles right of and below the CTU the same way and
 // stores their first block column / row.  A tile off the frame is not read and its blocks are not stored; no window reaches them.  Then one lane per
-// window -- 256 luma, then 64 per chroma plane -- adds its four blocks and does the two 64-bit divisions, and a workgroup reduction (wave shuffles,
+// window -- 256 luma, then 64 per chroma plane -- adds its four blocks and does the two 64-bit divisions, and a workgroup reduction (wave_sum,
 // then four partial sums through LDS) gives the 48-byte record.  The SSE-only instantiation has no halo pass, no grid and no division.
-// Totals: ONE workgroup walks the records kQualityTotalsChunk at a time, a record per lane -- integer sums in a fixed order, no atomics.
+// Totals: ONE workgroup walks the records kQualityTotalsChunk at a time, a record per lane -- integer sums in a fixed order, no atomics
+// (workgroup_totals, x266_lanes.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "x266_ctu_tiles.hpp"
 #include "x266_device.hpp"
 #include "x266_quality.hpp"
 
@@ -27,10 +29,6 @@ constexpr unsigned kQualityThreads = 256, kQualityWaves = kQualityThreads / 64;
 constexpr unsigned kGridY = 17, kGridC = 9;         // block sums of a CTU and its halo: luma, one chroma plane
 static_assert(sizeof(x266_quality_ctu_t) == 48, "the record is 48 bytes");
 static_assert(sizeof(x266_ref_block_t) == 512, "a tile is 512 bytes");
-
-struct QualityFrame {
-    unsigned tiles_w, tiles_h, ctus_w;
-};
 
 // Sums over the four lanes of a quad that leave every lane with the one sum it stores: each step a lane keeps half of what it holds and takes the
 // other lane's share of that half, so four values cost three permutes, not eight.
@@ -52,13 +50,6 @@ __device__ __forceinline__ uint32_t quad_sum_of_mine(uint32_t x0, uint32_t x1, u
     return a + from_quad_xor2(a);
 }
 
-__device__ __forceinline__ int64_t sum_over_wave(int64_t v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += (int64_t)__shfl_xor((long long)v, d, 64);
-    return v;
-}
-
 // the block sums of a grid in LDS: three planes of dwords
 template <unsigned N> struct BlockGrid {
     uint32_t s[N][N], ss[N][N], ab[N][N];
@@ -73,7 +64,7 @@ template <unsigned N> struct BlockGrid {
 };
 
 template <bool SSIM, bool SSE>
-__global__ __launch_bounds__(kQualityThreads) void quality_kernel(const x266_ref_block_t *__restrict__ src, const x266_ref_block_t *__restrict__ dec, QualityFrame f,
+__global__ __launch_bounds__(kQualityThreads) void quality_kernel(const x266_ref_block_t *__restrict__ src, const x266_ref_block_t *__restrict__ dec, TileFrame f,
                                                                   x266_quality_ctu_t *__restrict__ ctu)
 {
     __shared__ BlockGrid<kGridY> grid_y;
@@ -148,7 +139,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(const x266_ref
     }
     // slots of part: 0..2 ssim Y, U, V; 3 sse Y; 4 sse U | sse V << 32 (a CTU's is at most 1024 * 65025 per plane); 6 win_y | win_c << 16 (at most 256, 64)
     auto to_part = [&](int slot, int64_t v) {
-        v = sum_over_wave(v);
+        v = wave_sum(v);
         if (lane == 0) part[wave][slot] = v;
     };
     if (SSIM) {
@@ -196,8 +187,7 @@ __global__ __launch_bounds__(kQualityTotalsThreads) void quality_totals_kernel(c
 {
     constexpr unsigned kWaves = kQualityTotalsThreads / 64;
     static_assert(kQualityTotalsChunk == kQualityTotalsThreads, "a step is one record per lane");
-    __shared__ int64_t part[kWaves][8];
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned tid = threadIdx.x;
     int64_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (size_t j = tid; j < n_ctu; j += kQualityTotalsChunk) {
         const v4i *rec = reinterpret_cast<const v4i *>(ctu + j);
@@ -211,22 +201,12 @@ __global__ __launch_bounds__(kQualityTotalsThreads) void quality_totals_kernel(c
         acc[6] += (uint32_t)r2[1];
         acc[7] += (uint32_t)r2[2];
     }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int64_t s = sum_over_wave(acc[i]);
-        if (lane == 0) part[wave][i] = s;
-    }
-    __syncthreads();
-    if (tid < 8) {
-        int64_t all = 0;
-#pragma unroll
-        for (unsigned w = 0; w < kWaves; ++w) all += part[w][tid];
-        total[tid] = all;
-    }
+    const int64_t all = workgroup_totals<kWaves>(acc, tid);
+    if (tid < 8) total[tid] = all;
 }
 
 template <bool SSIM, bool SSE>
-hipError_t launch_quality(const x266_quality_t &p, const QualityFrame &f, unsigned n_ctu, hipStream_t stream)
+hipError_t launch_quality(const x266_quality_t &p, const TileFrame &f, unsigned n_ctu, hipStream_t stream)
 {
     hipLaunchKernelGGL((quality_kernel<SSIM, SSE>), dim3(n_ctu), dim3(kQualityThreads), 0, stream, p.d_src, p.d_dec, f, p.d_ctu);
     return hipGetLastError();
@@ -238,20 +218,16 @@ int quality_totals_chunk() { return (int)kQualityTotalsChunk; }
 
 hipError_t launch_quality_stats(const x266_quality_t &p, hipStream_t stream)
 {
-    QualityFrame f;
-    f.tiles_w = (unsigned)(p.width / 16);
-    f.tiles_h = (unsigned)(p.height / 16);
-    f.ctus_w = (f.tiles_w + 3) / 4;
-    const size_t n_ctu = (size_t)f.ctus_w * ((f.tiles_h + 3) / 4);
+    const TileFrame f = tile_frame(p.width, p.height);
     unsigned wgs = 0;
-    if (hipError_t e = wave_grid(n_ctu, 1, &wgs)) return e;                  // a workgroup per CTU
+    if (hipError_t e = wave_grid(f.n_ctu, 1, &wgs)) return e;                  // a workgroup per CTU
     const bool ssim = (p.flags & X266_QUALITY_SSIM) != 0, sse = (p.flags & X266_QUALITY_SSE) != 0;
     if (hipError_t e = ssim && sse ? launch_quality<true, true>(p, f, wgs, stream)
                        : ssim      ? launch_quality<true, false>(p, f, wgs, stream)
                                    : launch_quality<false, true>(p, f, wgs, stream))
         return e;
     if (!p.d_total) return hipSuccess;
-    hipLaunchKernelGGL(quality_totals_kernel, dim3(1), dim3(kQualityTotalsThreads), 0, stream, p.d_ctu, n_ctu, p.d_total);
+    hipLaunchKernelGGL(quality_totals_kernel, dim3(1), dim3(kQualityTotalsThreads), 0, stream, p.d_ctu, f.n_ctu, p.d_total);
     return hipGetLastError();
 }
 

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * kRdoqWavesPerWg) void rdoq_regions_kernel(cons
     if (nnz && lane == 0) nnz[r] = n_nz;
     if (stat) {
         const uint32_t bits = wave_sum(mine.bits);
-        const uint64_t total = wave_sum64(mine.dist);
+        const uint64_t total = wave_sum(mine.dist);
         if (lane == 0) {
             stat[r].dist = total;
             stat[r].bits = bits;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64 * kRdoqWavesPerWg) void tdecide_kernel(const TDe
         const CgPlace place = cg_place(kk, lane, origin);
         const RdoqLane mine = rdoq_steps(l, kk, lane, place, quant_params(kk + 2u, qp, kRdoqRoundNearest), a.lambda);
         const uint32_t bits = wave_sum(mine.bits), n_nz = wave_sum(mine.count);
-        uint64_t dist = wave_sum64(mine.dist);
+        uint64_t dist = wave_sum(mine.dist);
         dist = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)dist) |
                (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(dist >> 32)) << 32;
         const unsigned side = (a.class_bits[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;

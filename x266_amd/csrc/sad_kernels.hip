@@ -7,8 +7,8 @@
 //
 // Mapping: HBM-bound (2*n*n bytes in, 4 out per block pair).  Blocks are n*n contiguous bytes; a block is cut into 16-byte chunks,
 // one v_sad_u8 chain (4 bytes per instruction, 4 per chunk) per chunk, chunk = lane for 1 KiB-linear loads; the partial sums of a
-// block's chunks meet in DPP steps inside the row of 16 lanes (and four v_readlane for blocks of 64 chunks and more; blocks never
-// straddle a wave).  Launch shape = the read stream's (diag_kernels.hip): every wave issues its 2 x STEPS loads up front (4 KiB of each
+// block's chunks meet in DPP steps inside the row of 16 lanes (sum_over_span, x266_lanes.hpp; and four v_readlane for blocks of 64 chunks
+// and more: wave_sum; blocks never straddle a wave).  Launch shape = the read stream's (diag_kernels.hip): every wave issues its 2 x STEPS loads up front (4 KiB of each
 // input at STEPS = 4), four-wave workgroups charged 32 KiB of LDS each = twenty resident waves per CU
 // (profiles/r04_sad_shapes.txt: 8x8 0.0886 -> 0.0842 ms, 16x16 0.0878 -> 0.0789 on a 16384 x 16384 frame pair).
 #include <hip/hip_runtime.h>
@@ -27,16 +27,12 @@ __device__ __forceinline__ uint32_t sad_chunk(const v4i &a, const v4i &b, uint32
     return s;
 }
 
-// sum over aligned groups of SPAN lanes (every lane of the group ends up with it; SPAN = 64: wave-uniform)
+// a block's sum from the SPAN = 1, 4, 16 or 64 lanes that hold its chunks (every one of them ends up with it; SPAN = 64: wave-uniform)
 template <int SPAN>
-__device__ __forceinline__ uint32_t span_sum(uint32_t x)
+__device__ __forceinline__ uint32_t block_sum(uint32_t x)
 {
-    if (SPAN >= 2) x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
-    if (SPAN >= 4) x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, true);     // quad_perm [2,3,0,1]
-    if (SPAN >= 8) x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, true);    // row_half_mirror
-    if (SPAN >= 16) x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, true);   // row_mirror
-    if (SPAN >= 64) x = (uint32_t)(__builtin_amdgcn_readlane((int)x, 0) + __builtin_amdgcn_readlane((int)x, 16) + __builtin_amdgcn_readlane((int)x, 32) + __builtin_amdgcn_readlane((int)x, 48));
-    return x;
+    if constexpr (SPAN == 64) return wave_sum(x);
+    else return sum_over_span<SPAN>(x);
 }
 
 // LOGC = log2(16-byte chunks per block): 0 (4x4), 2 (8x8), 4 (16x16), 6 (32x32), 8 (64x64); STEPS = 1 KiB-linear loads per input and wave
@@ -77,14 +73,14 @@ __global__ __launch_bounds__(256) void sad_kernel(const uint8_t *__restrict__ a,
             uint32_t s = 0;
 #pragma unroll
             for (int i = 0; i < PER; ++i) s = sad_chunk(va[g * PER + i], vb[g * PER + i], s);
-            s = span_sum<64>(s);
+            s = wave_sum(s);
             const size_t blk = chunk0 / CPB + g;
             if (lane == 0 && blk < n_blocks) store_result4(out + blk, s);
         }
     } else {
 #pragma unroll
         for (int i = 0; i < STEPS; ++i) {
-            const uint32_t s = span_sum<SPAN>(sad_chunk(va[i], vb[i], 0));
+            const uint32_t s = block_sum<SPAN>(sad_chunk(va[i], vb[i], 0));
             const size_t blk = (chunk0 + 64 * i + lane) / CPB;
             if ((lane & (SPAN - 1)) == 0 && blk < n_blocks) {
                 // agent-scope result stores (x266_device.hpp) where they pay, paired A/B on four boxes (tools/gpu_ab_sad.py): 4x4 -1 to -3 %, 8x8 -3 to -4.5 %,

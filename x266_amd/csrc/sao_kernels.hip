@@ -16,7 +16,7 @@
 // when the band changes -- neighbouring samples mostly share a band, so this is a few LDS adds per lane instead of 16, and it needs
 // neither 32 registers per lane nor per-wave copies of the bins.  All adds are integer adds: the result does not depend on order.
 // Decision: one wave per CTU, a lane per bin (x266_sao.hpp: sao_bin_search), class sums and the 29 window sums through LDS, the
-// least window by a wave minimum over (cost, position) keys.
+// least window by a wave minimum over (cost, position) keys (wave_min, x266_lanes.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -189,16 +189,6 @@ __device__ __forceinline__ void stats_reduce(const uint32_t (&acc)[kStep][16], c
 }
 
 // ---- decision: one wave, lane = bin.  Every thread of the workgroup calls this (it holds barriers); `active` is uniform per wave ----
-__device__ __forceinline__ int64_t wave_min(int64_t key)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t other = __shfl_xor(key, d, 64);
-        key = other < key ? other : key;
-    }
-    return key;
-}
-
 __device__ __forceinline__ void sao_decide(const int32_t *bins, DecideScratch &scr, int lambda_q4, x266_sao_t *out, int lane, bool active)
 {
     if (active && lane < kSaoBins) {

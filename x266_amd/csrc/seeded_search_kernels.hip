@@ -11,7 +11,7 @@
 //      in walk order: a lane transforms its own 8x8 window (lane = position, as in me_search.hip) and scores it against its block's
 //      coefficients with 32 v_sad_u16; satd(cur - ref) = (sum |Hc - Hr| + 2) >> 2 exactly.  J = SATD + vector cost; the lane keeps
 //      the least key {J : walk index} per block, so that among equal J the first candidate of the walk wins;
-//   4. the keys' minimum over the wave, per block; lane 0 turns the walk index back into the vector and J back into the SATD.
+//   4. the keys' minimum over the wave (wave_min, x266_lanes.hpp), per block; lane 0 turns the walk index back into the vector and J back into the SATD.
 // Nothing depends on a launch option; the result is a function of the arguments alone.
 #include <hip/hip_runtime.h>
 
@@ -127,13 +127,7 @@ __global__ __launch_bounds__(64 * kSeedWavesPerWg) void seeded_search_kernel(con
 #pragma unroll
     for (int b = 0; b < 4; ++b) {                                           // 4.
         if (b >= nb) break;
-        unsigned long long v = least[b];
-#pragma unroll
-        for (int mm = 32; mm >= 1; mm >>= 1) {
-            const unsigned long long o = (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)v, mm)
-                                         | ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mm) << 32);
-            v = o < v ? o : v;
-        }
+        const unsigned long long v = wave_min(least[b]);
         if (lane == 0) {
             const SeedStep st = seed_walk_step((int)(uint32_t)v, r);
             const SeedVec c = s.centre[st.centre];

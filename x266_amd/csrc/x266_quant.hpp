@@ -78,12 +78,4 @@ __device__ __forceinline__ uint32_t dequantise_pair(uint32_t w, const QuantParam
     return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16);
 }
 
-// the sum of a per-lane count over the wave, as a wave-uniform value: the four rows' sums (x266_device.hpp) added on the scalar side
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x)
-{
-    x = sum_over_row16(x);
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 0) + (uint32_t)__builtin_amdgcn_readlane((int)x, 16) +
-           (uint32_t)__builtin_amdgcn_readlane((int)x, 32) + (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
-}
-
 }  // namespace x266

@@ -22,28 +22,6 @@ constexpr unsigned kRdoqWavesPerWg = 4;
 constexpr unsigned kRdoqRegionBytes = kLevelsRegionWords * 2;
 static_assert(sizeof(x266_rdoq_region_t) == 16, "the record is 16 bytes");
 
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t x, unsigned o)
-{
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), o);
-    return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t x, unsigned o)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, (int)o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), (int)o);
-    return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t x, unsigned src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, (int)src), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), (int)src);
-    return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x)
-{
-#pragma unroll
-    for (unsigned o = 32; o >= 1; o >>= 1) x += shfl_xor64(x, o);
-    return x;
-}
-
 __device__ __forceinline__ void rdoq_region_to_lds(const int16_t *src_base, size_t r, unsigned lane, char *slab)
 {
     const char *src = reinterpret_cast<const char *>(src_base) + r * kRdoqRegionBytes + lane * 16;
