@@ -1407,6 +1407,90 @@ typedef struct x266_seed_t {
 } x266_seed_t;
 int xSatd8x8SeededSearchGpu(x266hip_ctx *ctx, const x266_seed_t *p, void *stream);
 
+/* ---- inter partition decision: merge the 8x8 vectors of a refined field into partitions of 16x16, 32x32 and 64x64 samples ----
+ * The searches and the refinement leave one quarter-sample vector per 8x8 block.  This call decides, per CTU and bottom up, which
+ * neighbouring blocks share a vector, by SATD plus vector bits, and returns again one x266_me_result_t per 8x8 block -- which
+ * xMotionCompQpelGpu, xMotionCompBiQpelTiles and the deblocking calls take unchanged -- beside the partition's level per block (what a
+ * host needs for the partition map and for the transform candidates of x266_tdecide_t.d_cand) and the price of every CTU.  No upstream
+ * counterpart; the arithmetic here is the contract.
+ *
+ * Geometry.  width, height are positive multiples of 16; bw = width / 8, bh = height / 8; block b = by * bw + bx.  Level k = 0..3 has
+ * nodes of n = 1 << k blocks a side (8, 16, 32, 64 samples) on the grid anchored at (0, 0): node (nx, ny) of level k covers blocks
+ * X .. X + n - 1, Y .. Y + n - 1 with (X, Y) = (nx << k, ny << k).  A node is WHOLE if it lies inside the frame: nx < (bw >> k) and
+ * ny < (bh >> k); every node of levels 0 and 1 is.  A node of level 2 or 3 that sticks out of the frame is CUT: it has no vector of its
+ * own and always splits; its children that lie wholly outside the frame do not exist.  CTUs are the nodes of level 3, whole or cut,
+ * ceil(width / 64) x ceil(height / 64) in raster order as in xTransformCtuFromTilesDev.
+ * Input field.  d_mv holds one quarter-sample record per 8x8 block, the d_best of xSatd8x8RefineQpelFromTilesGpu; cost is ignored.
+ * in(bx, by) = clamp(component, -32766, 32766).
+ * Distortion.  D(b, q) = satd8x8(cur_b - P_q(b)) with P_q the luma prediction of xMotionCompQpelLumaGpu under the vector q: its edge
+ * rule, filters and rounding.  D(node, q) is the sum of D(b, q) over the node's blocks.  There is no weighted prediction here.
+ * Predictor of a node, from the INPUT field alone (nodes do not depend on each other's decisions): A = in(X - 1, Y), B = in(X, Y - 1),
+ * C = in(X + n, Y - 1) if that block is inside the frame, else in(X - 1, Y - 1).  If exactly one of the three is inside the frame, P is
+ * that one; otherwise P is the component-wise median of the three, a block outside the frame counting as (0, 0).
+ * Rate and cost.  R(k, q) = (k > 0 ? 1 : 0) + L(qx - Px) + L(qy - Py) with L the signed Exp-Golomb length of xSatd8x8SeededSearchGpu
+ * (L(0) = 1, L(1) = L(-1) = 3, ..), here of quarter-sample differences: |d| <= 65535, so L <= 33 and R <= 67.
+ * Jw(node, q) = D(node, q) + ((lambda_q4 * R) >> 4); everything fits uint32.
+ * Whole-node winners, bottom up and independent of the split decisions.  Level 0: W(b) = in(b).  For a whole node of level k >= 1, walk
+ * its children in raster order (top left, top right, bottom left, bottom right); for each child vector W(child) take dy = -r..r
+ * ascending, then dx = -r..r ascending: q = W(child) + (dx, dy) in quarter samples, each component then held to -32768..32767 (three
+ * levels of +-1 around +-32766 would leave int16; only vectors far outside any frame reach this).  Duplicates are allowed.  The least Jw
+ * wins, among equal values the first of the walk: W(node).
+ * Decision, bottom up.  Best(level-0 node) = Jw(b, W(b)).  For a whole node of level k >= 1, S = the sum of Best over its children +
+ * ((lambda_q4 * 1) >> 4); the node is ONE partition if Jw(node, W(node)) <= S (a tie merges) and Best = that Jw; otherwise it splits and
+ * Best = S.  For a cut node Best is the sum of Best over its existing children, with no flag.
+ * Outputs.  d_out[b] = the vector of the partition that contains b and D(b, that vector), the block's OWN 8x8 SATD.  d_level[b] = the
+ * partition's level, 0..3.  d_ctu[c]: j = Best of the CTU; dist = the summed distortion of its partitions; bits = their summed R plus
+ * one per whole node that split; parts = the number of partitions.  j is a sum of per-term floors -- one ">> 4" per partition and per
+ * split flag -- and NOT dist + ((lambda_q4 * bits) >> 4).  d_nodes, if given, holds W(node) and cost = Jw(node, W(node)) of every whole
+ * node: level 1 first, its (bw >> 1) * (bh >> 1) nodes in raster order, then level 2 ((bw >> 2) * (bh >> 2)), then level 3.
+ *
+ * Worked values.  A 32 x 32 frame (bw = bh = 4) with in(0, 0) = (4, -8), in(1, 0) = (12, -2), in(0, 1) = (3, 5), in(1, 1) = (-7, 9):
+ * block (1, 0) has only A inside the frame, P = (4, -8); block (0, 1) has B = (4, -8) and C = (12, -2) inside and A outside, P =
+ * (median(0, 4, 12), median(0, -8, -2)) = (4, -2); block (1, 1) has A = (3, 5), B = (12, -2) and C = in(2, 0); with in(2, 0) = (5, 1)
+ * P = (5, 1).  The level-1 node at (X, Y) = (2, 2) has no block at (4, 1), so its C = in(1, 1).  With P = (4, -2) and lambda_q4 16,
+ * q = (6, -2) at level 1 has R = 1 + L(2) + L(0) = 7 and Jw = D + 7; with lambda_q4 24, Jw = D + 10; q = P at level 0 has R = 2.
+ *
+ * What follows from it:
+ *   1. with range 0 every output vector is an input vector (clamped) of the same CTU;
+ *   2. with range 0, an input field with the same vector q in every block gives every whole CTU as one level-3 partition (the walk
+ *      only meets q and a tie merges), cut CTUs their largest whole nodes, and the costs in d_out are the D(b, q) of
+ *      xMotionCompQpelLumaGpu + xSatd8x8FromTilesDev -- at lambda_q4 0 and at every lambda_q4 >= 8.  Below 8 the per-term floors can
+ *      favour the split by one: at lambda_q4 7 a node with P = q costs (7 * 3) >> 4 = 1 beside its SATD, its four children and the
+ *      flag (7 * 2) >> 4 = 0 and 7 >> 4 = 0, so it splits;
+ *   3. lambda_q4 0 and range 0: d_ctu[c].j <= the sum over the CTU's blocks of D(b, in(b));
+ *   4. d_out through xMotionCompQpelLumaGpu and xSatd8x8FromTilesDev returns exactly the costs in d_out.
+ *
+ * One host struct, read during the call; the pointers in it are device pointers (alignments: the field comments).  d_cur == d_ref is
+ * allowed.  The outputs overlap nothing: in place (d_out == d_mv) is NOT allowed, nodes read their neighbours' input vectors.  One
+ * launch, one workgroup per CTU, no atomics: the same bytes on every run.  The call allocates nothing, needs no xHipMeScratchReserve
+ * and can be captured into a graph; its result does not depend on any launch option.  X266HIP_EINVAL, with nothing launched and the
+ * call named in xHipLastError: a NULL p, a NULL or misaligned required buffer, a misaligned d_nodes, a side that is not a positive
+ * multiple of 16, a scalar outside the range its field comment states, a span that does not fit in the address space, and an output
+ * that overlaps any other buffer of the call.  The extents are width * height * 2 (d_cur, d_ref), 8 bytes (d_mv, d_out) and 1 byte
+ * (d_level) per 8x8 block, 16 bytes per CTU (d_ctu) and 8 bytes per whole node of levels 1..3 (d_nodes).  Offsets are size_t; frames
+ * beyond 2^32 bytes are untested.
+ * Out of scope: bi-directional partitions, weighted prediction, chroma in the cost, rectangular and ternary splits, merge and skip
+ * candidates, a predictor that follows the decided partitions in coding order, and the motion side's compact stream. */
+typedef struct x266_part_ctu_t {
+    uint32_t j;            /* Best of the CTU: a sum of per-term floors                                     */
+    uint32_t dist;         /* the summed distortion of its partitions                                       */
+    uint32_t bits;         /* their summed R plus one per whole node that split                             */
+    uint32_t parts;        /* the number of partitions                                                      */
+} x266_part_ctu_t;         /* 16 bytes */
+typedef struct x266_part_t {
+    const x266_ref_block_t *d_cur;         /* [(width / 16) * (height / 16)], 16-byte aligned; only m_Y is read                 */
+    const x266_ref_block_t *d_ref;         /* the same size, 16-byte aligned; only m_Y is read; may be d_cur                    */
+    const x266_me_result_t *d_mv;          /* [(width / 8) * (height / 8)], 8-byte aligned; quarter samples; cost is ignored    */
+    x266_me_result_t *d_out;               /* one per 8x8 block, 8-byte aligned; output                                         */
+    uint8_t *d_level;                      /* one per 8x8 block, 1-byte aligned; output: the partition's level, 0..3            */
+    x266_part_ctu_t *d_ctu;                /* one per CTU, 8-byte aligned; output                                               */
+    x266_me_result_t *d_nodes;             /* one per whole node of levels 1..3 or NULL, 8-byte aligned; output                 */
+    int width, height;                     /* positive multiples of 16                                                          */
+    int range;                             /* r, 0..1                                                                           */
+    int lambda_q4;                         /* 0..65535                                                                          */
+} x266_part_t;
+int xInterPartitionDecideGpu(x266hip_ctx *ctx, const x266_part_t *p, void *stream);
+
 /* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
  * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source
  * frame and a decoded frame, for luma and both chroma planes, computed where the frames live and reduced to 48 bytes per CTU and

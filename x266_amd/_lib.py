@@ -94,6 +94,16 @@ class SeedParams(ctypes.Structure):
                [(name, ctypes.c_int) for name in ("width", "height", "seed_scale", "centres", "range", "lambda_q4")]
 
 
+class PartParams(ctypes.Structure):
+    """x266_part_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_cur", "d_ref", "d_mv", "d_out", "d_level", "d_ctu", "d_nodes")] + \
+               [(name, ctypes.c_int) for name in ("width", "height", "range", "lambda_q4")]
+
+
+# x266_part_ctu_t of include/x266hip.h
+PART_CTU_DTYPE = np.dtype([(name, "<u4") for name in ("j", "dist", "bits", "parts")])
+
+
 class MixedParams(ctypes.Structure):
     """x266_mixed_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
@@ -229,6 +239,7 @@ def load_library(path=None):
     for name in LA_CALLS.values():
         getattr(L, name).argtypes = [_P, ctypes.POINTER(LaParams), _P]
     L.xSatd8x8SeededSearchGpu.argtypes = [_P, ctypes.POINTER(SeedParams), _P]
+    L.xInterPartitionDecideGpu.argtypes = [_P, ctypes.POINTER(PartParams), _P]
     L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -1346,6 +1357,10 @@ class Codec:
         db, dj = self.alloc(nb * 8), self.alloc(max(nb * 4, 16))
         self.satd_seeded_search_dev(self.seed_params(w, h, seed_scale, centres, rng, lambda_q4, d_cur=dc.ptr, d_ref=dr.ptr, d_seed=ds.ptr, d_best=db.ptr, d_j=dj.ptr))
         return self._fetch_best(db, nb, dj, (nb,))
+
+    # -- the inter partition decision: the numpy calls are x266_amd/partition.py's ------------------------------
+    def inter_partition_decide_dev(self, params, stream=0):
+        self._check(self.L.xInterPartitionDecideGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xInterPartitionDecideGpu")
 
     # -- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames -------------------------
     @staticmethod

@@ -5,48 +5,19 @@
 //
 // Both stages are separable and run the same way: the lanes of a group each form the unshifted horizontal sums of ONE row of the
 // block's window (one load deep, not a chain of dependent row gathers per lane), park them as int16 in a wave-private LDS slot, and
-// the vertical stage reads across the rows.  No kernel here synchronises beyond its own wave.
+// the vertical stage reads across the rows.  No kernel here synchronises beyond its own wave.  The window-row load, where a block's
+// window row lies, the vertical stage over a slot and the 16-lane Hadamard are x266_subpel_blocks.hpp's, shared with the inter
+// partition decision (partition_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "x266_device.hpp"
 #include "x266_interp.hpp"
+#include "x266_subpel_blocks.hpp"
 
 namespace x266 {
 namespace {
-
-// The 16 bytes of one clamped plane row from element xs on (luma: samples, chroma: (U, V) pairs), `row` = the row's bytes in tile
-// column 0; a row of either plane is `width` bytes, 16 per tile.  Spans inside the frame are five aligned dwords (each within one
-// 16-byte tile row; one that would start past the row is moved back and holds nothing that is used) and funnel shifts, spans that
-// cross the left or right edge are read element by element with clamped x.
-template <bool CHROMA>
-__device__ __forceinline__ void load_window_row(const uint8_t *row, int xs, int width, uint32_t (&w)[4])
-{
-    const int pw = CHROMA ? width >> 1 : width, used = CHROMA ? 7 : 15;
-    if (xs >= 0 && xs + used - 1 <= pw - 1) {
-        const int x0 = CHROMA ? 2 * xs : xs, xa = x0 & ~3;
-        uint32_t d[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int x = xa + 4 * k < width - 4 ? xa + 4 * k : width - 4;
-            d[k] = *reinterpret_cast<const uint32_t *>(row + (size_t)(x >> 4) * 512 + (x & 15));
-        }
-        const unsigned sh = (unsigned)(x0 & 3) * 8;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = 0;
-#pragma unroll
-        for (int j = 0; j < (CHROMA ? 8 : 16); ++j) {
-            int x = xs + j;
-            x = x < 0 ? 0 : (x > pw - 1 ? pw - 1 : x);
-            if (CHROMA) w[j >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t *>(row + (size_t)(x >> 3) * 512 + (x & 7) * 2) << (16 * (j & 1));
-            else        w[j >> 2] |= (uint32_t)row[(size_t)(x >> 4) * 512 + (x & 15)] << (8 * (j & 3));
-        }
-    }
-}
 
 // One block of one plane by one group of lanes: luma 16 lanes for the 8x8 block `blk` (0..3, raster) of tile `tile`, chroma 8
 // lanes for its 4x4 (U, V) block.  Lane l forms the sums of window row l (luma 15 rows, chroma 7; the group's last lane fills a
@@ -138,57 +109,6 @@ __global__ __launch_bounds__(192) void mc_qpel_kernel(const x266_ref_block_t *__
 // ---- bi-directional motion compensation ---------------------------------------------------------------------------------------------
 // The unrounded V (x266_interp.hpp) of a lane's four outputs from BOTH references: the group's lanes as in mc_qpel_block, one slot
 // per list.  Both lists' row loads are issued before the first horizontal stage, so the two fetches overlap.
-template <bool CHROMA>
-struct WindowRow { const uint8_t *row; int xs, fx, fy; };
-
-template <bool CHROMA>
-__device__ __forceinline__ WindowRow<CHROMA> window_row(const x266_ref_block_t *ref, x266_me_result_t r, int height, int tiles_x, int tx, int ty, int blk, int l)
-{
-    typedef Interp<CHROMA> I;
-    constexpr int edge = CHROMA ? 4 : 8, lg = I::kLog2Phases;
-    const int ph = CHROMA ? height >> 1 : height;
-    int sy = (ty * 2 + (blk >> 1)) * edge + (r.mvy >> lg) - I::kBefore + l;
-    sy = sy < 0 ? 0 : (sy > ph - 1 ? ph - 1 : sy);
-    WindowRow<CHROMA> s;
-    s.row = reinterpret_cast<const uint8_t *>(ref) + (CHROMA ? 256 : 0) + (size_t)(sy >> (CHROMA ? 3 : 4)) * (size_t)tiles_x * 512 + (sy & (CHROMA ? 7 : 15)) * 16;
-    s.xs = (tx * 2 + (blk & 1)) * edge + (r.mvx >> lg) - I::kBefore;
-    s.fx = r.mvx & ((1 << lg) - 1);
-    s.fy = r.mvy & ((1 << lg) - 1);
-    return s;
-}
-
-// the vertical stage of the lane's four outputs (row l >> 1, half l & 1 of the block) over the group's slot, unrounded
-template <bool CHROMA>
-__device__ __forceinline__ void vertical_v4(const v4i *slot, int fy, int l, int (&v)[4])
-{
-    typedef Interp<CHROMA> I;
-    int t[8];
-    interp_taps<CHROMA>(fy, t);
-    const int y = l >> 1, half = l & 1;
-    uint2 rows[I::kTaps];
-#pragma unroll
-    for (int k = 0; k < I::kTaps; ++k) {
-        const v4i r = slot[y + k];
-        rows[k] = half ? make_uint2((uint32_t)r[2], (uint32_t)r[3]) : make_uint2((uint32_t)r[0], (uint32_t)r[1]);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int col[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < I::kTaps; ++k) col[k] = hsum_of(c < 2 ? rows[k].x : rows[k].y, c & 1);
-        v[c] = interp_vertical_v<CHROMA>(col, t);
-    }
-}
-
-// index of 8x8 luma block `blk` of tile `tile` in the raster order of blocks
-__device__ __forceinline__ size_t block_of_tile(size_t tile, int tiles_x, int blk, int *tx, int *ty)
-{
-    const size_t y = tile / (size_t)tiles_x, x = tile - y * (size_t)tiles_x;
-    *tx = (int)x;
-    *ty = (int)y;
-    return (y * 2 + (size_t)(blk >> 1)) * (size_t)(2 * tiles_x) + x * 2 + (size_t)(blk & 1);
-}
-
 template <bool CHROMA>
 __device__ __forceinline__ void bi_block_v(const x266_ref_block_t *__restrict__ ref0, const x266_ref_block_t *__restrict__ ref1, x266_me_result_t r0,
                                            x266_me_result_t r1, int width, int height, int tiles_x, int tx, int ty, int blk, int l, v4i *slot0, v4i *slot1,
@@ -298,7 +218,7 @@ __global__ __launch_bounds__(256) void satd_bi_costs_kernel(const x266_ref_block
     const size_t b = block_of_tile(tile, tiles_x, blk, &tx, &ty);
     int v0[4], v1[4];
     bi_block_v<false>(ref0, ref1, mv0[b], mv1[b], width, height, tiles_x, tx, ty, blk, l, slots[g][0], slots[g][1], v0, v1);
-    const uint32_t cw = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(cur + tile) + ((blk >> 1) * 8 + (l >> 1)) * 16 + (blk & 1) * 8 + (l & 1) * 4);
+    const uint32_t cw = cur_block_word(cur + tile, blk, l);
     uint32_t cost[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -306,24 +226,7 @@ __global__ __launch_bounds__(256) void satd_bi_costs_kernel(const x266_ref_block
         int d[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) d[c] = (int)((cw >> (8 * c)) & 255u) - bi_combine(t, v0[c], v1[c]);
-        const int a0 = d[0] + d[1], a1 = d[0] - d[1], a2 = d[2] + d[3], a3 = d[2] - d[3];
-        d[0] = a0 + a2;
-        d[1] = a1 + a3;
-        d[2] = a0 - a2;
-        d[3] = a1 - a3;
-#pragma unroll
-        for (int m = 1; m <= 8; m <<= 1)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int o = __shfl_xor(d[c], m);
-                d[c] = (l & m) ? o - d[c] : d[c] + o;
-            }
-        uint32_t sum = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) sum += (uint32_t)(d[c] < 0 ? -d[c] : d[c]);
-#pragma unroll
-        for (int m = 1; m <= 8; m <<= 1) sum += (uint32_t)__shfl_xor((int)sum, m);
-        cost[k] = (sum + 2) >> 2;
+        cost[k] = satd8x8_group16(d, l);
     }
     if (l == 0) {
         if (costs) {

@@ -10,7 +10,8 @@
 // and the level rate estimate (rdoq_regions, levels_bits) -- are held the same way by tests/cpp/struct_rules_check.cpp: one description
 // per struct, one walk over every call of every one; a new struct call adds a row to its struct's description there, a new struct a
 // description.  The transform decision (transform_decide, x266_tdecide_t) has a stand-alone driver of the same form,
-// tests/cpp/tdecide_rules_check.cpp, and so has frame quality (quality_stats, x266_quality_t): tests/cpp/quality_rules_check.cpp.
+// tests/cpp/tdecide_rules_check.cpp, and so have frame quality (quality_stats, x266_quality_t): tests/cpp/quality_rules_check.cpp, and the
+// inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -22,6 +23,7 @@
 #include <cstring>
 
 #include "../../include/x266hip.h"
+#include "x266_part.hpp"
 #include "x266_seed.hpp"
 
 namespace x266 {
@@ -671,6 +673,23 @@ inline const char *seeded_search(const x266_seed_t *p)
     const size_t n = blocks8(p->width, p->height);
     const Buf b[] = {out("d_best", p->d_best, 8, n * 8), opt(out("d_j", p->d_j, 4, n * 4)), in("d_cur", p->d_cur, 16, tile_bytes(p->width, p->height)),
                      in("d_ref", p->d_ref, 16, tile_bytes(p->width, p->height)), in("d_seed", p->d_seed, 8, seed_cells(p->width, p->height, p->seed_scale) * 8)};
+    return check(b);
+}
+
+// ---- the inter partition decision -----------------------------------------------------------------------------------------------------
+// xInterPartitionDecideGpu: the device pointers are the fields of the host-read x266_part_t, held by tests/cpp/partition_rules_check.cpp.
+// The node counts and the range of r are x266_part.hpp's, the kernel's own.  The two frames are read-only and may be one; an output
+// overlaps nothing, the input field included: nodes read their neighbours' input vectors.
+constexpr const char *kPartScalars = "range must be 0 or 1 and lambda_q4 0..65535";
+inline const char *partition_decide(const x266_part_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (p->range < 0 || p->range > kPartMaxRange || !lambda_ok(p->lambda_q4)) return kPartScalars;
+    const size_t n = blocks8(p->width, p->height), frame_bytes = tile_bytes(p->width, p->height);
+    const Buf b[] = {out("d_out", p->d_out, 8, n * 8), out("d_level", p->d_level, 1, n), out("d_ctu", p->d_ctu, 8, ctus(p->width, p->height) * sizeof(x266_part_ctu_t)),
+                     opt(out("d_nodes", p->d_nodes, 8, part_nodes_total(p->width / 8, p->height / 8) * 8)), in("d_cur", p->d_cur, 16, frame_bytes),
+                     in("d_ref", p->d_ref, 16, frame_bytes), in("d_mv", p->d_mv, 8, n * 8)};
     return check(b);
 }
 

@@ -283,6 +283,8 @@ hipError_t launch_la_tree_qp(const x266_la_t &p, hipStream_t stream);
 int la_totals_chunk();
 // the seeded search (seeded_search_kernels.hip): one launch, one wave per seed cell, no scratch
 hipError_t launch_seeded_search(const x266_seed_t &p, hipStream_t stream);
+// the inter partition decision (partition_kernels.hip): one launch, one workgroup per CTU, no scratch
+hipError_t launch_partition_decide(const x266_part_t &p, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

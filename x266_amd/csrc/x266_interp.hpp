@@ -73,15 +73,21 @@ __device__ __forceinline__ int interp_vertical_v(const int (&col)[8], const int 
     return s >> 6;                                                          // arithmetic: floors a negative sum
 }
 
-// The vertical stage and the rounding of one sample.
-template <bool CHROMA>
-__device__ __forceinline__ int interp_vertical(const int (&col)[8], const int (&t)[8])
+// The rounding of one sample from its unrounded V: clip8((V + 32) >> 6).
+__device__ __forceinline__ int interp_round(int unrounded)
 {
-    const int v = interp_vertical_v<CHROMA>(col, t) + 32;
+    const int v = unrounded + 32;
     // clip8(v >> 6) with the clamp in front of the shift: v >> 6 < 0 exactly when v < 0, > 255 exactly when v > 255 * 64 + 63.  (A
     // clamp behind the shift is what the compiler packs two results at a time with v_ashr_pk_u8_i32, which writes one half of its
     // destination and keeps the other: on an MI355X the kept half carried the bits of a negative sum into the neighbouring bytes.)
     return (v < 0 ? 0 : (v > 16383 ? 16383 : v)) >> 6;
+}
+
+// The vertical stage and the rounding of one sample.
+template <bool CHROMA>
+__device__ __forceinline__ int interp_vertical(const int (&col)[8], const int (&t)[8])
+{
+    return interp_round(interp_vertical_v<CHROMA>(col, t));
 }
 
 // The uni / bi combine of the header's x266_wp_t, ONE copy for the three bi-directional calls.  All three forms are

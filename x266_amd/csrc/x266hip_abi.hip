@@ -1541,6 +1541,15 @@ int xSatd8x8SeededSearchGpu(x266hip_ctx *ctx, const x266_seed_t *p, void *stream
     return launched(ctx, "seeded search launch", launch_seeded_search(*p, (hipStream_t)stream));
 }
 
+// ---- the inter partition decision (partition_kernels.hip, x266_part.hpp) ---------------------------------------------------------------------------
+int xInterPartitionDecideGpu(x266hip_ctx *ctx, const x266_part_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::partition_decide(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "partition decision launch", launch_partition_decide(*p, (hipStream_t)stream));
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).
