@@ -1470,7 +1470,8 @@ int xSatd8x8SeededSearchGpu(x266hip_ctx *ctx, const x266_seed_t *p, void *stream
  * (d_level) per 8x8 block, 16 bytes per CTU (d_ctu) and 8 bytes per whole node of levels 1..3 (d_nodes).  Offsets are size_t; frames
  * beyond 2^32 bytes are untested.
  * Out of scope: bi-directional partitions, weighted prediction, chroma in the cost, rectangular and ternary splits, merge and skip
- * candidates, a predictor that follows the decided partitions in coding order, and the motion side's compact stream. */
+ * candidates.  A predictor that follows the decided partitions in coding order, and the compact stream of the decided field, are
+ * xMotionPackGpu's (below). */
 typedef struct x266_part_ctu_t {
     uint32_t j;            /* Best of the CTU: a sum of per-term floors                                     */
     uint32_t dist;         /* the summed distortion of its partitions                                       */
@@ -1490,6 +1491,101 @@ typedef struct x266_part_t {
     int lambda_q4;                         /* 0..65535                                                                          */
 } x266_part_t;
 int xInterPartitionDecideGpu(x266hip_ctx *ctx, const x266_part_t *p, void *stream);
+
+/* ---- the compact motion stream: the decided field as a per-CTU stream for the host's entropy coder, and back ----
+ * xInterPartitionDecideGpu leaves its decision dense: 8 + 1 bytes per 8x8 block, although a frame is a few thousand partitions.
+ * xMotionPackGpu turns d_out and d_level into one 32-byte record per CTU and four 16-bit words per partition in coding order, the
+ * differences formed against a predictor a decoder can reproduce; xMotionUnpackGpu is the exact inverse on the vectors and levels and the
+ * entry of a decoder into xMotionCompQpelGpu.  No upstream counterpart; the arithmetic here is the contract.
+ *
+ * Geometry.  width, height, bw, bh, the levels, the nodes and which of them are WHOLE, CUT or do not exist, and the CTUs in raster
+ * order: exactly as the inter partition decision states them (above).  n_ctu = ceil(width / 64) * ceil(height / 64).  Inside a CTU the
+ * block at (x, y), each 0..7 relative to the CTU's first block, has the Morton index i = 0..63: bit 2b of i is bit b of x and bit
+ * 2b + 1 of i is bit b of y (i = 0, 1, 2, 3 are (0,0), (1,0), (0,1), (1,1); i = 4 is (2,0)).  A node of level k is the 4^k consecutive
+ * indices from a multiple of 4^k.
+ * Coding order: CTUs in raster order; inside a CTU the quadtree walk top left, top right, bottom left, bottom right -- which visits
+ * the partitions in ascending Morton index of their first block.
+ *
+ * Partitions as pack sees them.  Pack trusts only first blocks.  It walks each CTU from level 3 down: the node of level k whose first
+ * block is (X, Y) is ONE partition if it is whole and (d_level[Y * bw + X] & 3) >= k; otherwise it splits into its existing children.
+ * A cut node always splits; level 0 always ends the walk.  The partition's vector q is d_mv[Y * bw + X], the full int16 range, no
+ * clamp.  So a field that is not constant inside its partitions, and level bytes with high bits set or that disagree inside a
+ * partition, are legal input: pack canonicalises them to what the first blocks say.  (A predictor that reads such a block -- below, it
+ * reads d_mv where it stands -- cannot be reproduced by a decoder, which only ever sees the canonical field: differences are decodable
+ * for fields that are constant inside their partitions, which is what xInterPartitionDecideGpu emits.)
+ * The head mask.  head_mask has bit i set when block i is the first block of a partition.  A reader recovers the level of head h from
+ * the mask and the geometry: the largest k for which h is a multiple of 4^k, the node of level k at h is whole, and no other mask bit
+ * lies in (h, h + 4^k).
+ *
+ * Causal predictor.  The predictor of a partition of n = 1 << k blocks a side at (X, Y) reads d_mv at the blocks A = (X - 1, Y),
+ * B = (X, Y - 1), and C = (X + n, Y - 1) if that block is inside the frame AND precedes the partition in coding order -- its CTU's
+ * raster index is lower, or it lies in the same CTU with a Morton index below the head's --, otherwise C = (X - 1, Y - 1).  A, B and
+ * (X - 1, Y - 1) always precede.  If exactly one of the three is inside the frame, P is that one; otherwise P is the component-wise
+ * median of the three, a block outside the frame counting as (0, 0): the rule of the partition decision, on other blocks and without
+ * its clamp.
+ * Differences, payload and bits.  The true difference is d = q - P in int32, |d| <= 65535.  The payload of a partition is 4 words:
+ * qx, qy, then the low 16 bits of dx and of dy.  A decoder recovers q = (int16_t)(P + (int16_t)word): P + (int16_t)word and q differ
+ * by a multiple of 65536, q fits int16, and the cast keeps exactly the low 16 bits -- so the result is q whatever |d| was.  The payload of
+ * a CTU is its partitions in coding order, d_stream[offset .. offset + n_words).  bits = the sum over the CTU's partitions of
+ * (k > 0 ? 1 : 0) + L(dx) + L(dy), plus one per whole node that split; L is the signed Exp-Golomb length of xSatd8x8SeededSearchGpu
+ * (xMotionVectorBits: L(0) = 1, L(+-1) = 3, L(+-65535) = 33).  This is the accounting of x266_part_ctu_t.bits under the causal predictor,
+ * so the two are comparable.  max_abs is the largest |dx| or |dy| of the CTU.
+ *
+ * Worked values.  A 32 x 32 frame (bw = bh = 4) that is all level 1 has the heads 0, 4, 8 and 12 at the blocks (0,0), (2,0), (0,2) and
+ * (2,2), head_mask 0x1111, parts 4, n_words 16.  The partition at (0,2) has C = block (2,1): its Morton index 6 is below 8, it is
+ * available.  The partition at (2,2) has (4,1) outside the frame, so C = (1,1).  Were (1,1) a level-0 block, Morton 3, its above-right
+ * (2,0) is Morton 4 and not yet coded, so its C = (0,0) -- the decision's own predictor would have used in(2,0) there.
+ *
+ * Offsets and capacity.  offset[c] is the exclusive prefix sum of n_words over the CTUs before c, in 64 bits, a multiple of 4.
+ * xMotionPackGpu writes every record.  d_total[0] = the total number of words, d_total[1] = the number of leading CTUs whose payload
+ * lies completely inside cap_words (n_ctu exactly when the stream fits).  The payload of CTU c is written if and only if offset +
+ * n_words <= cap_words; no word at or beyond cap_words is ever written.  cap_words == 0 with d_stream == NULL is the count-only call:
+ * records and totals to size a buffer with.  Three launches on the caller's stream: count and records, the offsets (the scan of
+ * xLevelsPackGpu, xLevelsScanChunk() records per step), write.
+ *
+ * xMotionUnpackGpu trusts nothing in a record but head_mask and offset.  A mask is well formed if bit 0 is set, no bit of a block that
+ * does not exist is set, and every existing block i lies in [h, h + 4^level(h)) of the largest head h <= i.  A CTU whose mask is
+ * malformed, or with offset + 4 * popcount(head_mask) > cap_words (computed without overflow), is written as vector (0, 0), cost 0,
+ * level 0 in all its existing blocks.  Otherwise every block gets its partition's (qx, qy), cost 0 and level.  Words 2 and 3 of a
+ * partition are not read; nothing outside [0, cap_words) of the stream is ever read: the stream comes from a host decoder, and offset
+ * needs no alignment there.  d_total is ignored; d_stream may be NULL when cap_words == 0.  One launch.
+ *
+ * Both calls take one host struct, read during the call; the pointers in it are device pointers (alignments: the field comments).
+ * One wave per CTU, no atomics: the same input gives the same bytes on every run.  Neither call allocates; both can be captured into a
+ * graph; the result depends on no launch option.  X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a
+ * NULL or misaligned required buffer, a side that is not a positive multiple of 16, a span that does not fit in the address space, an
+ * output overlapping any other buffer of the call.  The extents are 8 bytes (d_mv) and 1 byte (d_level) per 8x8 block, 32 bytes per CTU
+ * (d_ctu), cap_words * 2 (d_stream) and 16 bytes (d_total).  Offsets are size_t; frames beyond 2^32 bytes are untested.
+ * Out of scope: bi-directional and intra blocks in the stream, merge and skip candidates, binarisation and CABAC, and a device-side
+ * reconstruction of the vectors from the differences (it needs a wavefront; xMotionPredictor covers it on the host). */
+typedef struct x266_motion_ctu_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
+    uint64_t head_mask;  /* bit i set: block i of the CTU (Morton index) starts a partition  */
+    uint64_t offset;     /* start of the CTU's payload in d_stream, in 16-bit words          */
+    uint32_t n_words;    /* 4 * parts                                                        */
+    uint32_t parts;      /* popcount(head_mask)                                              */
+    uint32_t bits;       /* flags + Exp-Golomb bits of the differences                       */
+    uint32_t max_abs;    /* largest |true difference component| of the CTU, 0..65535         */
+} x266_motion_ctu_t;
+typedef struct x266_motion_t {
+    x266_me_result_t *d_mv;      /* [bw * bh], 8-byte aligned; pack reads, unpack writes (cost = 0)              */
+    uint8_t *d_level;            /* [bw * bh], any alignment; pack reads (value & 3), unpack writes              */
+    x266_motion_ctu_t *d_ctu;    /* [n_ctu], 8-byte aligned; pack writes, unpack reads                           */
+    uint16_t *d_stream;          /* [cap_words], 16-byte aligned; pack writes, unpack reads                      */
+    uint64_t *d_total;           /* [2], 8-byte aligned; pack writes {words, leading CTUs that fit}; unpack ignores (may be NULL there) */
+    int width, height;           /* positive multiples of 16 */
+    uint64_t cap_words;
+} x266_motion_t;
+int xMotionPackGpu  (x266hip_ctx *ctx, const x266_motion_t *p, void *stream);
+int xMotionUnpackGpu(x266hip_ctx *ctx, const x266_motion_t *p, void *stream);
+/* Host only, the functions the kernels run.  xMotionWalk: the partitions of CTU `ctu` of a width x height frame under head_mask, in coding
+ * order: head[j] the Morton index of the first block and level[j] the level of partition j < the return value, the other entries 0;
+ * X266HIP_EINVAL for a malformed mask (as xMotionUnpackGpu judges it), a bad size, a ctu >= n_ctu or a NULL array.  xMotionPredictor: the
+ * causal predictor p of the whole node of `level` at block (X, Y) from a host copy of the field ([bw * bh], only mvx and mvy are read);
+ * X266HIP_EINVAL for a bad size, a NULL pointer, a level outside 0..3 or an (X, Y) that is not the first block of a whole node of that
+ * level.  xMotionVectorBits: L(d) for |d| <= 65535, else -1. */
+int xMotionWalk(int width, int height, size_t ctu, uint64_t head_mask, uint8_t head[64], uint8_t level[64]);
+int xMotionPredictor(int width, int height, const x266_me_result_t *field, int X, int Y, int level, int16_t p[2]);
+int xMotionVectorBits(int d);
 
 /* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
  * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source

@@ -104,6 +104,16 @@ class PartParams(ctypes.Structure):
 PART_CTU_DTYPE = np.dtype([(name, "<u4") for name in ("j", "dist", "bits", "parts")])
 
 
+class MotionParams(ctypes.Structure):
+    """x266_motion_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_mv", "d_level", "d_ctu", "d_stream", "d_total")] + \
+               [("width", ctypes.c_int), ("height", ctypes.c_int), ("cap_words", ctypes.c_uint64)]
+
+
+# x266_motion_ctu_t of include/x266hip.h
+MOTION_CTU_DTYPE = np.dtype([("head_mask", "<u8"), ("offset", "<u8"), ("n_words", "<u4"), ("parts", "<u4"), ("bits", "<u4"), ("max_abs", "<u4")])
+
+
 class MixedParams(ctypes.Structure):
     """x266_mixed_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
@@ -240,6 +250,11 @@ def load_library(path=None):
         getattr(L, name).argtypes = [_P, ctypes.POINTER(LaParams), _P]
     L.xSatd8x8SeededSearchGpu.argtypes = [_P, ctypes.POINTER(SeedParams), _P]
     L.xInterPartitionDecideGpu.argtypes = [_P, ctypes.POINTER(PartParams), _P]
+    L.xMotionPackGpu.argtypes = [_P, ctypes.POINTER(MotionParams), _P]
+    L.xMotionUnpackGpu.argtypes = [_P, ctypes.POINTER(MotionParams), _P]
+    L.xMotionWalk.argtypes = [ctypes.c_int, ctypes.c_int, _SZ, ctypes.c_uint64, _P, _P]
+    L.xMotionPredictor.argtypes = [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]
+    L.xMotionVectorBits.argtypes = [ctypes.c_int]
     L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -1361,6 +1376,13 @@ class Codec:
     # -- the inter partition decision: the numpy calls are x266_amd/partition.py's ------------------------------
     def inter_partition_decide_dev(self, params, stream=0):
         self._check(self.L.xInterPartitionDecideGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xInterPartitionDecideGpu")
+
+    # -- the compact motion stream: the numpy calls and the host helpers are x266_amd/motion.py's -----------------
+    def motion_pack_dev(self, params, stream=0):
+        self._check(self.L.xMotionPackGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xMotionPackGpu")
+
+    def motion_unpack_dev(self, params, stream=0):
+        self._check(self.L.xMotionUnpackGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xMotionUnpackGpu")
 
     # -- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames -------------------------
     @staticmethod

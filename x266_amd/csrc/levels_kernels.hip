@@ -8,7 +8,7 @@
 // (wave_exclusive_sum, x266_lanes.hpp).
 // Pack is three launches on one stream: count (records without offsets), scan (offsets and totals: ONE workgroup that walks the
 // records kLevelsScanChunk at a time and carries a running total -- no workgroup ever waits for another, no position is handed out
-// by an atomic, so the bytes depend on the data alone), write (recomputes from the levels, builds the payload in LDS at the stream's
+// by an atomic, so the bytes depend on the data alone; the kernel is x266_levels.hpp's, shared with the motion stream), write (recomputes from the levels, builds the payload in LDS at the stream's
 // own 16-byte phase and stores whole 16-byte chunks, single words only at the two ragged ends it shares with its neighbours).
 // Unpack reads its maps straight from the stream, checks every extent against cap_words BEFORE any load, stages the levels through
 // LDS the same way and writes the whole region, zeros included.
@@ -145,50 +145,6 @@ __global__ __launch_bounds__(64 * kLevelsWavesPerWg) void levels_pack_kernel(con
     }
 }
 
-// offset[r] = the sum of n_words over the regions before r; total[0] = the sum over all, total[1] = the regions that fit.  One workgroup.
-__global__ __launch_bounds__(kLevelsScanChunk) void levels_scan_kernel(x266_level_region_t *region, size_t n_regions, uint64_t cap_words,
-                                                                      uint64_t *total)
-{
-    constexpr unsigned kWaves = kLevelsScanChunk / 64;
-    __shared__ uint32_t wave_words[kWaves], wave_fit[kWaves];
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint64_t carry = 0, fit = 0;
-    uint32_t ahead = tid < n_regions ? region[tid].n_words : 0u;
-    for (size_t base = 0; base < n_regions; base += kLevelsScanChunk) {
-        const size_t i = base + tid;
-        uint32_t n_words = ahead;
-        size_t next = i + kLevelsScanChunk;
-        asm volatile("" : "+v"(n_words), "+v"(next));                       // this step's value has landed BEFORE the next load is issued: the wait
-        ahead = next < n_regions ? region[next].n_words : 0u;               // for it is not a wait for that one, which flies over this step's barriers
-        const uint32_t below = wave_exclusive_sum(n_words, lane);
-        if (lane == 63) wave_words[wave] = below + n_words;
-        __syncthreads();
-        uint32_t before = 0, chunk = 0;
-#pragma unroll
-        for (unsigned w = 0; w < kWaves; ++w) {
-            const uint32_t v = wave_words[w];
-            before += w < wave ? v : 0u;
-            chunk += v;
-        }
-        const uint64_t offset = carry + before + below;
-        const bool fits = i < n_regions && offset <= cap_words && n_words <= cap_words - offset;
-        if (i < n_regions) region[i].offset = offset;
-        const uint64_t fitting = __ballot(fits);
-        if (lane == 0) wave_fit[wave] = (uint32_t)__popcll(fitting);
-        __syncthreads();
-        uint32_t f = 0;
-#pragma unroll
-        for (unsigned w = 0; w < kWaves; ++w) f += wave_fit[w];
-        carry += chunk;
-        fit += f;
-        __syncthreads();                                                    // the two arrays are written again in the next step
-    }
-    if (tid == 0) {
-        total[0] = carry;
-        total[1] = fit;
-    }
-}
-
 __global__ __launch_bounds__(64 * kLevelsWavesPerWg) void levels_unpack_kernel(int16_t *__restrict__ level, const uint8_t *__restrict__ cls,
                                                                               uint32_t *__restrict__ nnz, const x266_level_region_t *__restrict__ region,
                                                                               const uint16_t *__restrict__ stream, size_t n_regions, uint64_t cap_words)
@@ -267,7 +223,7 @@ hipError_t launch_levels_pack(const x266_levels_t &p, hipStream_t stream)
                            (uint64_t)0);
         if (hipError_t e = hipGetLastError()) return e;
     }
-    hipLaunchKernelGGL(levels_scan_kernel, dim3(1), dim3(kLevelsScanChunk), 0, stream, p.d_region, p.n_regions, p.cap_words, p.d_total);
+    hipLaunchKernelGGL(levels_scan_kernel<x266_level_region_t>, dim3(1), dim3(kLevelsScanChunk), 0, stream, p.d_region, p.n_regions, p.cap_words, p.d_total);
     if (hipError_t e = hipGetLastError()) return e;
     if (p.n_regions && p.cap_words && p.d_stream)
         hipLaunchKernelGGL(levels_pack_kernel<true>, dim3(wgs), block, 0, stream, p.d_level, p.d_class, p.d_nnz, p.d_region, p.d_stream, p.n_regions, p.cap_words);

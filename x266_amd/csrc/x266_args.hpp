@@ -11,7 +11,8 @@
 // per struct, one walk over every call of every one; a new struct call adds a row to its struct's description there, a new struct a
 // description.  The transform decision (transform_decide, x266_tdecide_t) has a stand-alone driver of the same form,
 // tests/cpp/tdecide_rules_check.cpp, and so have frame quality (quality_stats, x266_quality_t): tests/cpp/quality_rules_check.cpp, and the
-// inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp.
+// inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp, and the compact motion stream (motion_pack,
+// motion_unpack, x266_motion_t): tests/cpp/motion_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -690,6 +691,31 @@ inline const char *partition_decide(const x266_part_t *p)
     const Buf b[] = {out("d_out", p->d_out, 8, n * 8), out("d_level", p->d_level, 1, n), out("d_ctu", p->d_ctu, 8, ctus(p->width, p->height) * sizeof(x266_part_ctu_t)),
                      opt(out("d_nodes", p->d_nodes, 8, part_nodes_total(p->width / 8, p->height / 8) * 8)), in("d_cur", p->d_cur, 16, frame_bytes),
                      in("d_ref", p->d_ref, 16, frame_bytes), in("d_mv", p->d_mv, 8, n * 8)};
+    return check(b);
+}
+
+// ---- the compact motion stream --------------------------------------------------------------------------------------------------------
+// xMotionPackGpu, xMotionUnpackGpu: the device pointers are the fields of the host-read x266_motion_t, held by
+// tests/cpp/motion_rules_check.cpp.  The stream's extent and the count-only call (d_stream NULL with cap_words 0) are the level stream's;
+// d_total is the pack call's alone.  An output overlaps nothing.
+inline const char *motion_pack(const x266_motion_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    const size_t n = blocks8(p->width, p->height);
+    Buf b[] = {out("d_ctu", p->d_ctu, 8, ctus(p->width, p->height) * sizeof(x266_motion_ctu_t)), out("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)),
+               out("d_total", p->d_total, 8, 16), in("d_mv", p->d_mv, 8, n * 8), in("d_level", p->d_level, 1, n)};
+    b[1].optional = p->cap_words == 0;
+    return check(b);
+}
+inline const char *motion_unpack(const x266_motion_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    const size_t n = blocks8(p->width, p->height);
+    Buf b[] = {out("d_mv", p->d_mv, 8, n * 8), out("d_level", p->d_level, 1, n), in("d_ctu", p->d_ctu, 8, ctus(p->width, p->height) * sizeof(x266_motion_ctu_t)),
+               in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words))};
+    b[3].optional = p->cap_words == 0;
     return check(b);
 }
 

@@ -1,10 +1,15 @@
 // x266_levels.hpp -- the compact level stream: the one copy of the scan tables and of the coefficient-group arithmetic that the kernels
-// of levels_kernels.hip and the host helper xLevelScan share.  The statement is include/x266hip.h's (xLevelsPackGpu ...).
+// of levels_kernels.hip and the host helper xLevelScan share, and the offset scan that the level stream and the motion stream
+// (motion_kernels.hip) share.  The statement is include/x266hip.h's (xLevelsPackGpu ...).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+
+#include "../../include/x266hip.h"
+#include "x266_lanes.hpp"
 
 namespace x266 {
 
@@ -63,6 +68,52 @@ __host__ __device__ constexpr unsigned level_scan4(unsigned i)
 {
     constexpr LevelTab t = make_level_tab();
     return t.scan4[i & 15u];
+}
+
+// The offset scan of a compact stream's records: offset[r] = the sum of n_words over the records before r; total[0] = the sum over all,
+// total[1] = the leading records whose payload fits.  One workgroup.  Record is x266_level_region_t (levels_kernels.hip) or
+// x266_motion_ctu_t (motion_kernels.hip), which share their first 20 bytes: only n_words is read and only offset written.
+template <typename Record>
+__global__ __launch_bounds__(kLevelsScanChunk) void levels_scan_kernel(Record *region, size_t n_regions, uint64_t cap_words, uint64_t *total)
+{
+    constexpr unsigned kWaves = kLevelsScanChunk / 64;
+    __shared__ uint32_t wave_words[kWaves], wave_fit[kWaves];
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t carry = 0, fit = 0;
+    uint32_t ahead = tid < n_regions ? region[tid].n_words : 0u;
+    for (size_t base = 0; base < n_regions; base += kLevelsScanChunk) {
+        const size_t i = base + tid;
+        uint32_t n_words = ahead;
+        size_t next = i + kLevelsScanChunk;
+        asm volatile("" : "+v"(n_words), "+v"(next));                       // this step's value has landed BEFORE the next load is issued: the wait
+        ahead = next < n_regions ? region[next].n_words : 0u;               // for it is not a wait for that one, which flies over this step's barriers
+        const uint32_t below = wave_exclusive_sum(n_words, lane);
+        if (lane == 63) wave_words[wave] = below + n_words;
+        __syncthreads();
+        uint32_t before = 0, chunk = 0;
+#pragma unroll
+        for (unsigned w = 0; w < kWaves; ++w) {
+            const uint32_t v = wave_words[w];
+            before += w < wave ? v : 0u;
+            chunk += v;
+        }
+        const uint64_t offset = carry + before + below;
+        const bool fits = i < n_regions && offset <= cap_words && n_words <= cap_words - offset;
+        if (i < n_regions) region[i].offset = offset;
+        const uint64_t fitting = __ballot(fits);
+        if (lane == 0) wave_fit[wave] = (uint32_t)__popcll(fitting);
+        __syncthreads();
+        uint32_t f = 0;
+#pragma unroll
+        for (unsigned w = 0; w < kWaves; ++w) f += wave_fit[w];
+        carry += chunk;
+        fit += f;
+        __syncthreads();                                                    // the two arrays are written again in the next step
+    }
+    if (tid == 0) {
+        total[0] = carry;
+        total[1] = fit;
+    }
 }
 
 }  // namespace x266

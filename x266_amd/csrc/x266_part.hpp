@@ -54,6 +54,13 @@ X266_HD inline int part_median3(int a, int b, int c)
     const int lo = a < b ? a : b, hi = a < b ? b : a;
     return c < lo ? lo : (c > hi ? hi : c);
 }
+// P from the three spots, one outside the frame handed in as (0, 0): exactly one inside -> that one; otherwise the component-wise median.
+// Shared with the causal predictor of the motion stream (x266_motion.hpp).
+X266_HD inline PartVec part_predict3(bool has_a, const PartVec &a, bool has_b, const PartVec &b, bool has_c, const PartVec &c)
+{
+    if ((int)has_a + (int)has_b + (int)has_c == 1) return has_a ? a : (has_b ? b : c);
+    return PartVec{part_median3(a.x, b.x, c.x), part_median3(a.y, b.y, c.y)};
+}
 X266_HD inline PartVec part_predictor(const x266_me_result_t *mv, int bw, int X, int Y, int n)
 {                                                                           // (X, Y) inside the frame: no neighbour lies below it
     const bool has_a = X > 0, has_b = Y > 0;
@@ -61,8 +68,7 @@ X266_HD inline PartVec part_predictor(const x266_me_result_t *mv, int bw, int X,
     const PartVec zero = {0, 0};
     const PartVec a = has_a ? part_in(mv, bw, X - 1, Y) : zero, b = has_b ? part_in(mv, bw, X, Y - 1) : zero;
     const PartVec c = c_right ? part_in(mv, bw, X + n, Y - 1) : (has_c ? part_in(mv, bw, X - 1, Y - 1) : zero);
-    if ((int)has_a + (int)has_b + (int)has_c == 1) return has_a ? a : (has_b ? b : c);
-    return PartVec{part_median3(a.x, b.x, c.x), part_median3(a.y, b.y, c.y)};
+    return part_predict3(has_a, a, has_b, b, has_c, c);
 }
 
 // ---- R(k, q) = (k > 0) + L(qx - Px) + L(qy - Py), at most 67, and what it costs: (lambda_q4 * R) >> 4

@@ -24,6 +24,7 @@
 #include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_levels.hpp"
+#include "x266_motion.hpp"
 #include "x266_quality.hpp"
 #include "x266_rdoq.hpp"
 #include "x266_lookahead.hpp"
@@ -1549,6 +1550,53 @@ int xInterPartitionDecideGpu(x266hip_ctx *ctx, const x266_part_t *p, void *strea
     X_DEV(ctx);
     return launched(ctx, "partition decision launch", launch_partition_decide(*p, (hipStream_t)stream));
 }
+
+// ---- the compact motion stream (motion_kernels.hip, x266_motion.hpp) -------------------------------------------------------------------------------
+int xMotionPackGpu(x266hip_ctx *ctx, const x266_motion_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::motion_pack(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "motion pack launch", launch_motion_pack(*p, (hipStream_t)stream));
+}
+
+int xMotionUnpackGpu(x266hip_ctx *ctx, const x266_motion_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::motion_unpack(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "motion unpack launch", launch_motion_unpack(*p, (hipStream_t)stream));
+}
+
+// the three host helpers: the functions of x266_motion.hpp that the kernels run, on the host
+int xMotionWalk(int width, int height, size_t ctu, uint64_t head_mask, uint8_t head[64], uint8_t level[64])
+{
+    if (args::frame(width, height, 16) || !head || !level || ctu >= args::ctus(width, height)) return X266HIP_EINVAL;
+    const MotionCtu g = motion_ctu(width / 8, height / 8, ctu);
+    if (!motion_mask_well_formed(g, head_mask)) return X266HIP_EINVAL;
+    int parts = 0;
+    for (unsigned i = 0; i < 64; ++i) {
+        head[i] = level[i] = 0;
+        if (head_mask >> i & 1u) {                                          // ascending Morton index is the coding order
+            head[parts] = (uint8_t)i;
+            level[parts++] = (uint8_t)motion_head_level(g, head_mask, i);
+        }
+    }
+    return parts;
+}
+
+int xMotionPredictor(int width, int height, const x266_me_result_t *field, int X, int Y, int level, int16_t p[2])
+{
+    if (args::frame(width, height, 16) || !field || !p || level < 0 || level >= kPartLevels) return X266HIP_EINVAL;
+    const int bw = width / 8, bh = height / 8, n = 1 << level;
+    if (X < 0 || Y < 0 || (X & (n - 1)) || (Y & (n - 1)) || !part_whole(bw, bh, level, X >> level, Y >> level)) return X266HIP_EINVAL;
+    const PartVec v = motion_predictor(field, bw, X, Y, n);
+    p[0] = (int16_t)v.x;
+    p[1] = (int16_t)v.y;
+    return X266HIP_OK;
+}
+
+int xMotionVectorBits(int d) { return d < -kMotionMaxDiff || d > kMotionMaxDiff ? -1 : seed_code_length(d); }
 
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
