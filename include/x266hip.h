@@ -1587,6 +1587,130 @@ int xMotionWalk(int width, int height, size_t ctu, uint64_t head_mask, uint8_t h
 int xMotionPredictor(int width, int height, const x266_me_result_t *field, int X, int Y, int level, int16_t p[2]);
 int xMotionVectorBits(int d);
 
+/* ---- the entropy coder: the levels as a range-coded byte stream, one independent substream per 32x32 region, and back ----
+ * xLevelsPackGpu hands words to a host coder; xRdoQuantRegionsGpu, xTransformDecideCtuTilesGpu and xLevelsBitsGpu optimise against a
+ * static rate model.  xEntropyEncodeLevelsGpu codes the levels themselves, on the device, with an adaptive binary range coder whose
+ * syntax mirrors that model term by term, so that estimate and bytes can be compared; xEntropyDecodeLevelsGpu is the exact inverse and
+ * the entry of a decoder into xQuantRegionsGpu(1).  No upstream counterpart; the arithmetic here is the contract.
+ *
+ * Region, class byte, block layout, scan, CGs and CG bit g: exactly as the compact level stream states them (xLevelsPackGpu,
+ * xLevelScan).  N = 4 << (class & 3), n = log2 N; d_class == NULL: N = 32.  pos(), g, rem() and the position class are the rate
+ * model's (xRdoQuantRegionsGpu).
+ *
+ * Syntax of a region.  Its (32 / N)^2 blocks in raster order; per block:
+ *     cbf                             one bin: the block has a non-zero level.  If 0 the block ends here.
+ *     last position p = (u_p, v_p)    the last non-zero scan position, u_p first, then v_p.  A coordinate t: its group index g (g = t for
+ *                                     t < 4, otherwise 2 ilog2(t) + ((t >> (ilog2(t) - 1)) & 1)) as g one-bins and, if g < 2n - 1, a
+ *                                     zero-bin: min(g + 1, 2n - 1) bins, bin i coded with context (x or y, i).  For g >= 4 then the
+ *                                     (g >> 1) - 1 low bits of t as bypass bins, most significant first.
+ *     the CGs s = 0 .. s_p in ascending scan order, s_p the CG of p:
+ *         cgf                         for 0 < s < s_p only: the CG has a non-zero level.  If 0 the CG ends here.  CG 0 and CG s_p are
+ *                                     implied coded (CG 0 even when it holds no level).
+ *         the positions i of the CG in ascending scan order, in CG s_p only those up to p:
+ *             sig                     the level is non-zero; context = the position class (0, 1 or 2).  Not coded for p itself.
+ *             for a non-zero level l: gt1 (|l| > 1); if set gt2 (|l| > 2); if set the remainder r = |l| - 3 in bypass bins: min(r, 3)
+ *                                     ones, then a zero if r < 3, otherwise Exp-Golomb order 0 of r - 3 (with v = r - 2 and k =
+ *                                     ilog2(v): k ones, a zero, the k low bits of v, most significant first); rem(r) bins in all.
+ *                                     Then the sign as a bypass bin, 1 = negative.  All bins of one coefficient stay together.
+ * The level -32768 is legal: magnitude 32768, r = 32765, k = 14.
+ * Decoded positions cannot leave the block: a coordinate's prefix stops at g = 2n - 1, and for g >= 4 the decoder forms t =
+ * ((2 + (g & 1)) << ((g >> 1) - 1)) | suffix with (g >> 1) <= n - 1, so t < 2^n; for n = 2, t = g <= 3.  Every (u, v) below N names one
+ * scan position of the block.
+ *
+ * Contexts.  Per block size 25, in this order: cbf; last x, bin 0..8; last y, bin 0..8; cgf; sig of class 0, 1, 2; gt1; gt2.  The
+ * table is 4 x 25 = X266_ENTROPY_CONTEXTS entries, size 4 first.  A context is the probability p of a ZERO bin in 1/2048, 11 bits.
+ * Every region starts from the call's initial table: regions are independent substreams, and nothing adapted ever leaves a region.
+ * The initial table `init` is HOST memory, 100 uint16, read during the call and passed to the kernels by value; every entry must lie
+ * in 31 .. 2017 (the interval the adaptation below never leaves).  NULL is the default table (xEntropyDefaultInit): from the model's
+ * costs c0, c1 of a zero and a one in 1/16 bit, p = 2048 * 2^(-c0/16) / (2^(-c0/16) + 2^(-c1/16)) rounded to nearest and held to 31 ..
+ * 2017; 1024 for cbf (the model has no term) and for the last-position prefix (16 per bin).  Per size: 19 x 1024, then cgf 1385, sig
+ * 723 1242 1609, gt1 1325, gt2 1263.  A host may pass any table; the decoder must take the same one.  Neither call accepts or returns
+ * adapted tables.
+ *
+ * Coder: the LZMA range coder, as recalled.  range is 32 bits and starts at 0xFFFFFFFF; low is a mathematical integer that starts at 0
+ * (an implementation keeps 33 bits of it, a cache byte and a count of pending 0xFF bytes for the carry).
+ *     context bin b with probability p:  bound = (range >> 11) * p.   b = 0: range = bound, p += (2048 - p) >> 5.
+ *                                                                    b = 1: low += bound, range -= bound, p -= p >> 5.
+ *     bypass bin b:                      range >>= 1; if b: low += range.
+ *     after every bin, while range < 2^24:  range <<= 8, low <<= 8 (one byte leaves; with p in 31 .. 2017 this happens at most once).
+ *     termination:                       low = (low + 0xFFFFFF) & ~0xFFFFFF, then five more byte shifts.
+ * The bytes are low, big endian.  The leading byte -- always 0, a carry never reaches it -- is not stored, and trailing zero bytes are
+ * not stored (after the termination's rounding at least the last three are zero).  n_bytes counts what is stored.  The decoder starts
+ * with range = 0xFFFFFFFF and code = the first four stored bytes, reads 0 beyond the end of a substream, and for a context bin takes b
+ * = 0 iff code < bound (otherwise code -= bound), for a bypass bin b = 1 iff code >= range after the halving (then code -= range); it
+ * renormalises with code = (code << 8 | next byte); all in 32-bit unsigned arithmetic.  So an all-zero region is 0 bytes, and a
+ * region's overhead over its information is one or two bytes, not five.
+ * Worked values, 32x32 regions under the default table, bytes in hex.  The only level DC = 1: 80 (4 context bins, 1 bypass bin; one
+ * word, 0x0080).  The only level DC = -32768: 9f ff fa ea cd (5 and 33 bins).  The only level a 3 at index 1023, the last scan position:
+ * ff ff ff 7e fb 80 04 12 (114 and 8 bins).
+ * The largest substream.  A region has at most 3456 context bins (64 blocks of 4x4: 1 + 6 + 15 + 32 each) and at most 33 824 bypass bins
+ * (1024 levels of rem(32765) + 1 = 33 bins, and 32 last-position suffix bits at 8x8).  A context bin shrinks the range by no less than
+ * 31/2048 less the truncation of range >> 11, under 6.05 bits; a bypass bin costs under 1.0001 bits.  That is under 54 740 bits, no
+ * more than 6843 byte shifts, and with the termination 6847 bytes: X266_ENTROPY_MAX_BYTES = 6848, 3424 words.  (All 1024 levels at
+ * +-32767 under a table of 2017s come to 4342 bytes; the bound is the floor's, not a measured one.)
+ *
+ * Stream and records.  d_stream is in 16-bit words, little endian: byte j of a substream is bits 8 (j & 1) .. of word offset + j / 2.  A
+ * substream of odd length is padded with one zero byte; n_words = (n_bytes + 1) / 2.  Per region one 32-byte record whose first 20 bytes
+ * are laid out as x266_level_region_t's.  offset[r] is the exclusive prefix sum of n_words, in 64 bits.
+ * xEntropyEncodeLevelsGpu writes every record.  d_total[0] = the total number of words, d_total[1] = the number of leading regions whose
+ * payload lies completely inside cap_words (n_regions exactly when the stream fits).  The payload of region r is written if and only if
+ * offset + n_words <= cap_words; no word at or beyond cap_words is ever written.  cap_words == 0 with d_stream == NULL is the count-only
+ * call: records and totals to size a buffer with.  With d_nnz != NULL a region with d_nnz[r] == 0 counts as all zero and its levels are
+ * not read.  n_regions == 0 writes d_total = {0, 0} and nothing else.  Three launches on the caller's stream: count and records, the
+ * offsets (the scan of xLevelsPackGpu, xLevelsScanChunk() records per step), write.  One wave per region; no atomics, no allocation; the
+ * same input gives the same bytes on every run and under every launch option; the call can be captured into a graph.
+ *
+ * xEntropyDecodeLevelsGpu trusts nothing in a record but offset and n_bytes, and holds both against cap_words before any load: a region
+ * with offset > cap_words, (n_bytes + 1) / 2 > cap_words - offset or n_bytes > X266_ENTROPY_MAX_BYTES is written as all zero with
+ * d_nnz[r] = 0.  Nothing outside [0, cap_words) of the stream is ever read, and inside a substream only its n_bytes count.  Decoding is
+ * total: every loop of the syntax is bounded, so any bytes decode to some region or are malformed.  Malformed: an Exp-Golomb prefix
+ * longer than 14, a magnitude above 32768, the value +32768.  A malformed region is written as all zero with d_nnz[r] = 0.  Otherwise all
+ * 1024 levels are written, absent ones as zeros, and with d_nnz != NULL the non-zero count.  (A decoded region may hold a coded CG
+ * without a level or a last position at a zero CG 0 only through garbage; re-encoding it gives the canonical bytes.)  d_total is
+ * ignored; d_stream may be NULL when cap_words == 0.  One launch.
+ *
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned required buffer, a NULL
+ * d_stream with cap_words != 0, an entry of init outside 31 .. 2017, a span that does not fit in the address space, an output
+ * overlapping any other buffer.  The extents are the compact level stream's, with n_regions * 32 for d_region.  With n_regions == 0
+ * only d_total of the encode call is looked at.
+ * Out of scope, the follow-ups: coding the motion stream, class bytes, intra modes, kinds and qp; per-frame context statistics coming
+ * back from the device; context carry-over between regions, WPP-style rows included; sign hiding and dependent quantisation; splitting
+ * a region's blocks over lanes as separate coders (a format question: separate coders are separate substreams); any real VVC or HEVC
+ * bit-stream syntax.  Until the side information is coded and contexts carry over, a "bitrate" from these calls is the residual's alone. */
+#define X266_ENTROPY_CONTEXTS  100
+#define X266_ENTROPY_MAX_BYTES 6848
+typedef struct x266_entropy_region_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
+    uint32_t ctx_bins;     /* context-coded bins of the region                                   */
+    uint32_t bypass_bins;  /* bypass bins of the region                                          */
+    uint64_t offset;       /* start of the region's substream in d_stream, in 16-bit words       */
+    uint32_t n_words;      /* (n_bytes + 1) / 2                                                  */
+    uint32_t n_bytes;      /* bytes of the substream, 0 .. X266_ENTROPY_MAX_BYTES                */
+    uint32_t n_nz;         /* non-zero levels of the region (what d_nnz holds)                   */
+    uint32_t reserved;     /* written 0                                                          */
+} x266_entropy_region_t;
+typedef struct x266_entropy_t {
+    int16_t  *d_level;                 /* [n_regions * 1024], 16-byte aligned; encode reads, decode writes            */
+    const uint8_t *d_class;            /* [n_regions] or NULL (every region 32x32), any alignment                     */
+    uint32_t *d_nnz;                   /* [n_regions] or NULL, 4-byte aligned; encode reads, decode writes (above)    */
+    x266_entropy_region_t *d_region;   /* [n_regions], 8-byte aligned; encode writes, decode reads                    */
+    uint16_t *d_stream;                /* [cap_words], 16-byte aligned; encode writes, decode reads                   */
+    uint64_t *d_total;                 /* [2], 8-byte aligned; encode writes, decode ignores (may be NULL there)      */
+    const uint16_t *init;              /* HOST memory, [X266_ENTROPY_CONTEXTS], or NULL: the default table            */
+    size_t    n_regions;
+    uint64_t  cap_words;
+} x266_entropy_t;
+int xEntropyEncodeLevelsGpu(x266hip_ctx *ctx, const x266_entropy_t *p, void *stream);
+int xEntropyDecodeLevelsGpu(x266hip_ctx *ctx, const x266_entropy_t *p, void *stream);
+/* Host only, the functions the kernels run.  xEntropyDefaultInit writes the default table.  xEntropyEncodeRegion codes the 1024 levels of
+ * one region of class `cls` (only cls & 3 counts) from `init` (NULL: the default): it returns n_bytes, stores the first min(n_bytes, cap)
+ * bytes in out (which may be NULL with cap 0) and, with bins != NULL, the context and the bypass bin counts.  xEntropyDecodeRegion
+ * writes all 1024 levels and, with n_nz != NULL, the count; it returns 0, or 1 for a malformed substream (then zeros).  Both return
+ * X266HIP_EINVAL for a NULL level array, a NULL buffer with a length, a table entry outside 31 .. 2017 or an n_bytes above
+ * X266_ENTROPY_MAX_BYTES. */
+int xEntropyDefaultInit(uint16_t init[X266_ENTROPY_CONTEXTS]);
+int xEntropyEncodeRegion(const int16_t *level, int cls, const uint16_t *init, uint8_t *out, size_t cap, uint32_t bins[2]);
+int xEntropyDecodeRegion(const uint8_t *bytes, size_t n_bytes, int cls, const uint16_t *init, int16_t *level, uint32_t *n_nz);
+
 /* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
  * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source
  * frame and a decoded frame, for luma and both chroma planes, computed where the frames live and reduced to 48 bytes per CTU and

@@ -114,6 +114,19 @@ class MotionParams(ctypes.Structure):
 MOTION_CTU_DTYPE = np.dtype([("head_mask", "<u8"), ("offset", "<u8"), ("n_words", "<u4"), ("parts", "<u4"), ("bits", "<u4"), ("max_abs", "<u4")])
 
 
+class EntropyParams(ctypes.Structure):
+    """x266_entropy_t of include/x266hip.h; `init` is a HOST address (or None: the default table)"""
+    _fields_ = [(name, _P) for name in ("d_level", "d_class", "d_nnz", "d_region", "d_stream", "d_total", "init")] + \
+               [("n_regions", ctypes.c_size_t), ("cap_words", ctypes.c_uint64)]
+
+
+# x266_entropy_region_t of include/x266hip.h
+ENTROPY_REGION_DTYPE = np.dtype([("ctx_bins", "<u4"), ("bypass_bins", "<u4"), ("offset", "<u8"), ("n_words", "<u4"), ("n_bytes", "<u4"), ("n_nz", "<u4"),
+                                 ("reserved", "<u4")])
+ENTROPY_CONTEXTS = 100
+ENTROPY_MAX_BYTES = 6848
+
+
 class MixedParams(ctypes.Structure):
     """x266_mixed_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
@@ -255,6 +268,11 @@ def load_library(path=None):
     L.xMotionWalk.argtypes = [ctypes.c_int, ctypes.c_int, _SZ, ctypes.c_uint64, _P, _P]
     L.xMotionPredictor.argtypes = [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]
     L.xMotionVectorBits.argtypes = [ctypes.c_int]
+    L.xEntropyEncodeLevelsGpu.argtypes = [_P, ctypes.POINTER(EntropyParams), _P]
+    L.xEntropyDecodeLevelsGpu.argtypes = [_P, ctypes.POINTER(EntropyParams), _P]
+    L.xEntropyDefaultInit.argtypes = [_P]
+    L.xEntropyEncodeRegion.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P]
+    L.xEntropyDecodeRegion.argtypes = [_P, _SZ, ctypes.c_int, _P, _P, _P]
     L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -1383,6 +1401,13 @@ class Codec:
 
     def motion_unpack_dev(self, params, stream=0):
         self._check(self.L.xMotionUnpackGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xMotionUnpackGpu")
+
+    # -- the entropy coder of the level stream: the numpy calls and the host helpers are x266_amd/entropy.py's ----
+    def entropy_encode_levels_dev(self, params, stream=0):
+        self._check(self.L.xEntropyEncodeLevelsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyEncodeLevelsGpu")
+
+    def entropy_decode_levels_dev(self, params, stream=0):
+        self._check(self.L.xEntropyDecodeLevelsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyDecodeLevelsGpu")
 
     # -- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames -------------------------
     @staticmethod

@@ -11,8 +11,9 @@
 // per struct, one walk over every call of every one; a new struct call adds a row to its struct's description there, a new struct a
 // description.  The transform decision (transform_decide, x266_tdecide_t) has a stand-alone driver of the same form,
 // tests/cpp/tdecide_rules_check.cpp, and so have frame quality (quality_stats, x266_quality_t): tests/cpp/quality_rules_check.cpp, and the
-// inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp, and the compact motion stream (motion_pack,
-// motion_unpack, x266_motion_t): tests/cpp/motion_rules_check.cpp.
+// inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp, the compact motion stream (motion_pack,
+// motion_unpack, x266_motion_t): tests/cpp/motion_rules_check.cpp, and the entropy coder (entropy_encode, entropy_decode, x266_entropy_t):
+// tests/cpp/entropy_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -715,6 +716,44 @@ inline const char *motion_unpack(const x266_motion_t *p)
     const size_t n = blocks8(p->width, p->height);
     Buf b[] = {out("d_mv", p->d_mv, 8, n * 8), out("d_level", p->d_level, 1, n), in("d_ctu", p->d_ctu, 8, ctus(p->width, p->height) * sizeof(x266_motion_ctu_t)),
                in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words))};
+    b[3].optional = p->cap_words == 0;
+    return check(b);
+}
+
+// ---- the entropy coder of the level stream -------------------------------------------------------------------------------------------------
+// xEntropyEncodeLevelsGpu, xEntropyDecodeLevelsGpu: the device pointers are the fields of the host-read x266_entropy_t, held by
+// tests/cpp/entropy_rules_check.cpp.  Buffers, extents and the count-only call are the compact level stream's; `init` is host memory and
+// every entry of it lies in 31 .. 2017, the interval the adaptation never leaves.
+constexpr const char *kEntropyInit = "every entry of init must be 31..2017";
+inline bool entropy_init_ok(const uint16_t *init)
+{
+    if (!init) return true;
+    for (unsigned i = 0; i < X266_ENTROPY_CONTEXTS; ++i)
+        if (init[i] < 31 || init[i] > 2017) return false;
+    return true;
+}
+inline const char *entropy_encode(const x266_entropy_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (!entropy_init_ok(p->init)) return kEntropyInit;
+    const size_t n = p->n_regions;
+    if (n == 0) {
+        const Buf b[] = {out("d_total", p->d_total, 8, 16)};
+        return check(b);
+    }
+    Buf b[] = {out("d_region", p->d_region, 8, mul(n, 32)), out("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), out("d_total", p->d_total, 8, 16),
+               in("d_level", p->d_level, 16, mul(n, 2048)), opt(in("d_class", p->d_class, 1, n)), opt(in("d_nnz", p->d_nnz, 4, mul(n, 4)))};
+    b[1].optional = p->cap_words == 0;
+    return check(b);
+}
+inline const char *entropy_decode(const x266_entropy_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (!entropy_init_ok(p->init)) return kEntropyInit;
+    const size_t n = p->n_regions;
+    if (n == 0) return nullptr;
+    Buf b[] = {out("d_level", p->d_level, 16, mul(n, 2048)), opt(out("d_nnz", p->d_nnz, 4, mul(n, 4))), in("d_region", p->d_region, 8, mul(n, 32)),
+               in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), opt(in("d_class", p->d_class, 1, n))};
     b[3].optional = p->cap_words == 0;
     return check(b);
 }

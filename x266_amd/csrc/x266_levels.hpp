@@ -1,15 +1,22 @@
 // x266_levels.hpp -- the compact level stream: the one copy of the scan tables and of the coefficient-group arithmetic that the kernels
 // of levels_kernels.hip and the host helper xLevelScan share, and the offset scan that the level stream and the motion stream
 // (motion_kernels.hip) share.  The statement is include/x266hip.h's (xLevelsPackGpu ...).
+// The tables are plain C++ (a host-only driver includes them through x266_entropy.hpp); the scan kernel exists under hipcc alone.
 #pragma once
-
-#include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/x266hip.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
 #include "x266_lanes.hpp"
+#define X266_HD __host__ __device__
+#else
+#define X266_HD
+#endif
 
 namespace x266 {
 
@@ -58,21 +65,22 @@ constexpr LevelTab make_level_tab()
 }
 
 // k = class & 3 (N = 4 << k), g = 0..63
-__host__ __device__ inline unsigned level_cg_origin(unsigned k, unsigned g)
+X266_HD inline unsigned level_cg_origin(unsigned k, unsigned g)
 {
     constexpr LevelTab t = make_level_tab();
     return t.origin[k & 3u][g & 63u];
 }
 // y * 4 + x of scan position i of a 4x4 CG
-__host__ __device__ constexpr unsigned level_scan4(unsigned i)
+X266_HD constexpr unsigned level_scan4(unsigned i)
 {
     constexpr LevelTab t = make_level_tab();
     return t.scan4[i & 15u];
 }
 
+#if defined(__HIPCC__)
 // The offset scan of a compact stream's records: offset[r] = the sum of n_words over the records before r; total[0] = the sum over all,
 // total[1] = the leading records whose payload fits.  One workgroup.  Record is x266_level_region_t (levels_kernels.hip) or
-// x266_motion_ctu_t (motion_kernels.hip), which share their first 20 bytes: only n_words is read and only offset written.
+// x266_motion_ctu_t (motion_kernels.hip) or x266_entropy_region_t (entropy_kernels.hip), which share their first 20 bytes: only n_words is read and only offset written.
 template <typename Record>
 __global__ __launch_bounds__(kLevelsScanChunk) void levels_scan_kernel(Record *region, size_t n_regions, uint64_t cap_words, uint64_t *total)
 {
@@ -115,5 +123,6 @@ __global__ __launch_bounds__(kLevelsScanChunk) void levels_scan_kernel(Record *r
         total[1] = fit;
     }
 }
+#endif
 
 }  // namespace x266

@@ -23,6 +23,7 @@
 #include "x266_aq.hpp"
 #include "x266_args.hpp"
 #include "x266_device.hpp"
+#include "x266_entropy.hpp"
 #include "x266_levels.hpp"
 #include "x266_motion.hpp"
 #include "x266_quality.hpp"
@@ -1597,6 +1598,68 @@ int xMotionPredictor(int width, int height, const x266_me_result_t *field, int X
 }
 
 int xMotionVectorBits(int d) { return d < -kMotionMaxDiff || d > kMotionMaxDiff ? -1 : seed_code_length(d); }
+
+// ---- the entropy coder of the level stream (entropy_kernels.hip, x266_entropy.hpp) -------------------------------------------------------------------
+int xEntropyEncodeLevelsGpu(x266hip_ctx *ctx, const x266_entropy_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_encode(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "entropy encode launch", launch_entropy_encode(*p, (hipStream_t)stream));
+}
+
+int xEntropyDecodeLevelsGpu(x266hip_ctx *ctx, const x266_entropy_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_decode(p)) return refuse(ctx, __func__, why);
+    if (p->n_regions == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "entropy decode launch", launch_entropy_decode(*p, (hipStream_t)stream));
+}
+
+// the three host helpers: the functions of x266_entropy.hpp that the kernels run, on the host
+int xEntropyDefaultInit(uint16_t init[X266_ENTROPY_CONTEXTS])
+{
+    if (!init) return X266HIP_EINVAL;
+    for (unsigned i = 0; i < kEntropyContexts; ++i) init[i] = kEntropyDefault.p[i];
+    return X266HIP_OK;
+}
+
+int xEntropyEncodeRegion(const int16_t *level, int cls, const uint16_t *init, uint8_t *out, size_t cap, uint32_t bins[2])
+{
+    if (!level || (!out && cap) || !args::entropy_init_ok(init)) return X266HIP_EINVAL;
+    const unsigned k = (unsigned)cls & 3u;
+    uint16_t ctx[kEntropyCtxPerSize];
+    for (unsigned i = 0; i < kEntropyCtxPerSize; ++i) ctx[i] = (init ? init : kEntropyDefault.p)[k * kEntropyCtxPerSize + i];
+    EntropyEnc e;
+    entropy_enc_start(e, out, cap > kEntropyMaxBytes ? kEntropyMaxBytes : (uint32_t)cap);
+    entropy_encode_region(e, level, k, entropy_cg_mask(level, k), ctx);
+    const uint32_t n_bytes = entropy_enc_finish(e);
+    if (bins) {
+        bins[0] = e.ctx_bins;
+        bins[1] = e.bypass_bins;
+    }
+    return (int)n_bytes;
+}
+
+int xEntropyDecodeRegion(const uint8_t *bytes, size_t n_bytes, int cls, const uint16_t *init, int16_t *level, uint32_t *n_nz)
+{
+    if (!level || (!bytes && n_bytes) || n_bytes > kEntropyMaxBytes || !args::entropy_init_ok(init)) return X266HIP_EINVAL;
+    const unsigned k = (unsigned)cls & 3u;
+    uint16_t ctx[kEntropyCtxPerSize];
+    for (unsigned i = 0; i < kEntropyCtxPerSize; ++i) ctx[i] = (init ? init : kEntropyDefault.p)[k * kEntropyCtxPerSize + i];
+    for (unsigned i = 0; i < kLevelsRegionWords; ++i) level[i] = 0;
+    EntropyDec d;
+    entropy_dec_start(d, bytes, (uint32_t)n_bytes);
+    uint32_t count = 0;
+    const bool good = entropy_decode_region(d, level, k, ctx, &count);
+    if (!good) {
+        for (unsigned i = 0; i < kLevelsRegionWords; ++i) level[i] = 0;
+        count = 0;
+    }
+    if (n_nz) *n_nz = count;
+    return good ? 0 : 1;
+}
 
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own

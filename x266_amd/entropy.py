@@ -1,0 +1,95 @@
+"""The entropy coder of the level stream (include/x266hip.h: xEntropyEncodeLevelsGpu, xEntropyDecodeLevelsGpu): the numpy calls around
+Codec.entropy_encode_levels_dev and Codec.entropy_decode_levels_dev, built from the pieces the Codec's own numpy methods are built from,
+and the three host helpers of the library (xEntropyDefaultInit, xEntropyEncodeRegion, xEntropyDecodeRegion).  No arithmetic lives here."""
+import numpy as np
+
+from ._lib import ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES, ENTROPY_REGION_DTYPE, Codec, EntropyParams, X266Error, _NULL, load_library
+
+
+def _init_table(init):
+    """the host table a call reads: None stays None (the default); the array must outlive the call, so it is returned"""
+    if init is None:
+        return None
+    table = np.ascontiguousarray(init, np.uint16).ravel()
+    if table.size != ENTROPY_CONTEXTS:
+        raise X266Error("init must hold %d entries" % ENTROPY_CONTEXTS)
+    return table
+
+
+def entropy_params(**fields):
+    """an x266_entropy_t by field name: device addresses (absent or 0: NULL) and the HOST address `init`, then n_regions and cap_words"""
+    scalars = [fields.pop("n_regions", 0), fields.pop("cap_words", 0)]
+    return Codec._keyword_params(EntropyParams, "entropy_params", fields, scalars)
+
+
+def entropy_encode_levels(codec, levels, classes=None, nnz=None, cap_words=None, init=None):
+    """numpy convenience around xEntropyEncodeLevelsGpu: [n_regions, 1024] int16 (and a class byte and a non-zero count per region, None:
+    NULL; init: 100 uint16 or None) -> (records [n_regions] of ENTROPY_REGION_DTYPE, stream uint16 [cap_words], total uint64 [2]).
+    cap_words None: a count-only call sizes the stream exactly; words the call does not write are 0."""
+    lv = np.ascontiguousarray(levels, np.int16).reshape(-1, 1024)
+    n = lv.shape[0]
+    table = _init_table(init)
+    d_level = codec._upload(lv)
+    d_class, d_nnz = codec._table(classes, np.uint8, n), codec._table(nnz, np.uint32, n)
+    d_region, d_tot = codec.alloc(max(32 * n, 16)), codec.alloc(16)
+    p = entropy_params(d_level=d_level.ptr, d_class=d_class.ptr, d_nnz=d_nnz.ptr, d_region=d_region.ptr, d_total=d_tot.ptr,
+                       init=table.ctypes.data if table is not None else 0, n_regions=n)
+    if cap_words is None:
+        codec.entropy_encode_levels_dev(p)
+        cap_words = codec._fetch((d_tot, np.uint64, (2,)))[0]
+    cap_words = int(cap_words)
+    d_str = codec._upload(np.zeros(cap_words, np.uint16)) if cap_words else _NULL
+    p.d_stream, p.cap_words = d_str.ptr or None, cap_words
+    codec.entropy_encode_levels_dev(p)
+    return codec._fetch((d_region, ENTROPY_REGION_DTYPE, (n,)), (d_str, np.uint16, (cap_words,)), (d_tot, np.uint64, (2,)))
+
+
+def entropy_decode_levels(codec, records, stream, classes=None, init=None):
+    """numpy convenience around xEntropyDecodeLevelsGpu: records (ENTROPY_REGION_DTYPE) and the stream's words -> (levels [n_regions, 1024]
+    int16, nnz [n_regions] uint32)"""
+    rec = np.ascontiguousarray(records, ENTROPY_REGION_DTYPE).ravel()
+    n = rec.size
+    words = np.ascontiguousarray(stream, np.uint16).ravel()
+    table = _init_table(init)
+    d_region = codec._upload(rec)
+    d_str = codec._upload(words) if words.size else _NULL
+    d_class = codec._table(classes, np.uint8, n)
+    d_level, d_nnz = codec.alloc(max(2048 * n, 16)), codec.alloc(max(4 * n, 16))
+    codec.entropy_decode_levels_dev(entropy_params(d_level=d_level.ptr, d_class=d_class.ptr, d_nnz=d_nnz.ptr, d_region=d_region.ptr, d_stream=d_str.ptr,
+                                                   init=table.ctypes.data if table is not None else 0, n_regions=n, cap_words=words.size))
+    return codec._fetch((d_level, np.int16, (n, 1024)), (d_nnz, np.uint32, (n,)))
+
+
+# ---- the host helpers: the library's own functions, no device ------------------------------------------------------------------------------
+def entropy_default_init():
+    """xEntropyDefaultInit: the default table, 100 uint16"""
+    table = np.zeros(ENTROPY_CONTEXTS, np.uint16)
+    if load_library().xEntropyDefaultInit(table.ctypes.data) != 0:
+        raise X266Error("xEntropyDefaultInit failed")
+    return table
+
+
+def entropy_encode_region(level, cls=3, init=None, cap=ENTROPY_MAX_BYTES):
+    """xEntropyEncodeRegion: (the substream's first min(n_bytes, cap) bytes, n_bytes, context bins, bypass bins)"""
+    lv = np.ascontiguousarray(level, np.int16).ravel()
+    if lv.size != 1024:
+        raise X266Error("a region is 1024 levels")
+    table = _init_table(init)
+    out, bins = np.zeros(max(int(cap), 1), np.uint8), np.zeros(2, np.uint32)
+    n = load_library().xEntropyEncodeRegion(lv.ctypes.data, int(cls), table.ctypes.data if table is not None else None, out.ctypes.data if cap else None, int(cap),
+                                            bins.ctypes.data)
+    if n < 0:
+        raise X266Error("xEntropyEncodeRegion: a bad argument")
+    return out[:min(n, int(cap))].tobytes(), n, int(bins[0]), int(bins[1])
+
+
+def entropy_decode_region(data, cls=3, init=None):
+    """xEntropyDecodeRegion: (levels [1024] int16, n_nz, malformed)"""
+    raw = np.frombuffer(bytes(data), np.uint8)
+    table = _init_table(init)
+    level, n_nz = np.zeros(1024, np.int16), np.zeros(1, np.uint32)
+    rc = load_library().xEntropyDecodeRegion(raw.ctypes.data if raw.size else None, raw.size, int(cls), table.ctypes.data if table is not None else None,
+                                             level.ctypes.data, n_nz.ctypes.data)
+    if rc < 0:
+        raise X266Error("xEntropyDecodeRegion: a bad argument")
+    return level, int(n_nz[0]), rc == 1
