@@ -1556,8 +1556,9 @@ int xInterPartitionDecideGpu(x266hip_ctx *ctx, const x266_part_t *p, void *strea
  * NULL or misaligned required buffer, a side that is not a positive multiple of 16, a span that does not fit in the address space, an
  * output overlapping any other buffer of the call.  The extents are 8 bytes (d_mv) and 1 byte (d_level) per 8x8 block, 32 bytes per CTU
  * (d_ctu), cap_words * 2 (d_stream) and 16 bytes (d_total).  Offsets are size_t; frames beyond 2^32 bytes are untested.
- * Out of scope: bi-directional and intra blocks in the stream, merge and skip candidates, binarisation and CABAC, and a device-side
- * reconstruction of the vectors from the differences (it needs a wavefront; xMotionPredictor covers it on the host). */
+ * Out of scope: bi-directional and intra blocks in the stream, merge and skip candidates.  Binarisation and coding of the stream are
+ * xEntropyEncodeMvGpu's, the device-side reconstruction of the vectors from the differences is xMotionReconstructGpu's (both below;
+ * xMotionPredictor covers the latter on the host). */
 typedef struct x266_motion_ctu_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
     uint64_t head_mask;  /* bit i set: block i of the CTU (Morton index) starts a partition  */
     uint64_t offset;     /* start of the CTU's payload in d_stream, in 16-bit words          */
@@ -1673,10 +1674,10 @@ int xMotionVectorBits(int d);
  * d_stream with cap_words != 0, an entry of init outside 31 .. 2017, a span that does not fit in the address space, an output
  * overlapping any other buffer.  The extents are the compact level stream's, with n_regions * 32 for d_region.  With n_regions == 0
  * only d_total of the encode call is looked at.
- * Out of scope, the follow-ups: coding the motion stream, class bytes, intra modes, kinds and qp; per-frame context statistics coming
+ * Out of scope, the follow-ups: class bytes, intra modes, kinds and qp (the motion stream is xEntropyEncodeMvGpu's, below); per-frame context statistics coming
  * back from the device; context carry-over between regions, WPP-style rows included; sign hiding and dependent quantisation; splitting
  * a region's blocks over lanes as separate coders (a format question: separate coders are separate substreams); any real VVC or HEVC
- * bit-stream syntax.  Until the side information is coded and contexts carry over, a "bitrate" from these calls is the residual's alone. */
+ * bit-stream syntax.  Until the side information is coded and contexts carry over, a "bitrate" from these two calls is the residual's alone (xEntropyEncodeMvGpu adds the motion's). */
 #define X266_ENTROPY_CONTEXTS  100
 #define X266_ENTROPY_MAX_BYTES 6848
 typedef struct x266_entropy_region_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
@@ -1710,6 +1711,137 @@ int xEntropyDecodeLevelsGpu(x266hip_ctx *ctx, const x266_entropy_t *p, void *str
 int xEntropyDefaultInit(uint16_t init[X266_ENTROPY_CONTEXTS]);
 int xEntropyEncodeRegion(const int16_t *level, int cls, const uint16_t *init, uint8_t *out, size_t cap, uint32_t bins[2]);
 int xEntropyDecodeRegion(const uint8_t *bytes, size_t n_bytes, int cls, const uint16_t *init, int16_t *level, uint32_t *n_nz);
+
+/* ---- the entropy coder of the motion stream: range-coded CTU substreams, and the vectors rebuilt from the differences ----
+ * xMotionPackGpu leaves the motion field as 16-bit words for a host coder, and xMotionUnpackGpu reads the vectors themselves, which a bit
+ * stream does not carry.  xEntropyEncodeMvGpu codes the quadtree and the differences of pack's stream on the device, one independent
+ * substream per CTU under the range coder of the levels (above; the coder, its bytes, the stream's words and the padding are exactly
+ * those); xEntropyDecodeMvGpu is its inverse and writes a stream of pack's form with the vectors left out; xMotionReconstructGpu
+ * rebuilds the dense field from the differences on the device.  No upstream counterpart; the arithmetic here is the contract.
+ *
+ * Geometry, Morton index, nodes (WHOLE, CUT, not existing), head mask, level of a head, well-formedness of a mask, causal predictor and
+ * the payload of a partition: exactly as the compact motion stream states them (xMotionPackGpu).
+ *
+ * Syntax of a CTU.  The payload is the quadtree, and the vectors are coded where the walk reaches them.  Visit the level-3 node of the
+ * CTU; for a node of level k whose first block is h:
+ *     the node does not exist (h is outside the frame)   nothing
+ *     k == 0                                             a partition
+ *     the node is CUT                                    no bin; visit its four children top left, top right, bottom left, bottom right
+ *     the node is WHOLE                                  one bin `split` with context split[k]: 0 = the node is one partition, 1 = visit
+ *                                                        its four children in the same order
+ * A partition codes dx, then dy: the TRUE differences, |d| <= 65535.  The encoder has qx, qy and the low 16 bits w of each difference
+ * in pack's words: P = (int16_t)(q - (int16_t)w) and d = q - P, exact by the argument of the pack section.  One component d:
+ *     nz     d != 0, context per component.  If 0 the component ends here.
+ *     gt1    |d| > 1, context per component.
+ *     if set: r = |d| - 2 in bypass bins as Exp-Golomb order 1: with v = r + 2 and k = ilog2(v) >= 1, k - 1 ones, a zero, then the k low
+ *            bits of v, most significant first.  r <= 65533, so v <= 65535, k <= 15: at most 30 bins.
+ *     sign   a bypass bin, 1 = negative.
+ * Contexts.  X266_ENTROPY_MOTION_CONTEXTS = 7, in this order: split of level 1, 2, 3; nz of x, of y; gt1 of x, of y.  They restart at
+ * every CTU from the call's table: CTUs are independent substreams.  `init` is HOST memory, 7 uint16 in 31 .. 2017, read during the call
+ * and passed by value; NULL is the default table (xEntropyMvDefaultInit), all 1024: the estimate this syntax mirrors
+ * (xMotionVectorBits, one bit per flag) has no skew.
+ * Bins against bits.  L(d) is 1 for d = 0, 3 for |d| = 1 and 2 ilog2(|d|) + 3 above (k = 2|d| - (d > 0) has ilog2(k + 1) = ilog2(|d|) +
+ * 1 for |d| >= 1); the component's bins are 1, 3 and 2 ilog2(|d|) + 3: the same.  The flags are one bin each.  So for every readable
+ * CTU ctx_bins + bypass_bins == x266_motion_ctu_t.bits exactly, and the coded bytes are that estimate made adaptive.
+ *
+ * Decoder rules.  Every loop is bounded (64 blocks, 3 levels, 15 prefix bins, 15 suffix bits).  The only malformed case is an
+ * Exp-Golomb prefix of more than 14 ones; a well-formed prefix gives v <= 65535, so |d| <= 65535 always.  The decoder puts out the low 16
+ * bits of d.  The mask it builds is well formed by construction.
+ * The empty substream and the flat CTU.  Zero bytes decode, under every table, to the FLAT CTU: every whole node unsplit wherever the
+ * cut nodes above it lead, every difference zero (all its bins are zero bins, and a decoder that reads zeros takes the zero side of
+ * every context bin).  The flat CTU also encodes to zero bytes: a still CTU costs nothing.  This one rule covers every failure:
+ *     on encode  a CTU whose mask is malformed (as xMotionUnpackGpu judges it) or with offset + 4 * popcount(head_mask) > in_words
+ *                (computed without overflow) is coded as the empty substream; its record says parts = 0, unreadable = 1 and no bins.
+ *     on decode  a record with offset > cap_words, (n_bytes + 1) / 2 > cap_words - offset or n_bytes > X266_ENTROPY_MOTION_MAX_BYTES
+ *                decodes as the empty substream (d_status 1); a malformed substream gives the flat CTU as well (d_status 2).
+ * Nothing outside [0, cap_words) of d_stream, respectively [0, in_words) of d_words, is ever read.
+ *
+ * The largest substream.  At most 21 split bins (1 + 4 + 16) and 64 partitions x 4 = 277 context bins, each under 6.05 bits (the level
+ * coder's bound), and at most 64 x 2 x 31 = 3968 bypass bins, each under 1.0001 bits: under 5645 bits, no more than 706 byte shifts, and
+ * with the termination 710 bytes.  X266_ENTROPY_MOTION_MAX_BYTES = 720, a multiple of 16 for the staging slab.  (64 level-0 partitions
+ * with every |d| = 65535 come to 511 bytes under the default table; the bound is the floor's, not a measured one.)
+ *
+ * Worked values, under the default table, bytes in hex (context bins, bypass bins):
+ *     64 x 64, one level-3 partition, d = (0, 0):               no bytes (3, 0)
+ *     64 x 64, one level-3 partition, d = (1, 0):               40 (4, 1)
+ *     64 x 64, one level-3 partition, d = (-2, 5):              67 90 (5, 8)
+ *     64 x 64, one level-3 partition, d = (-65535, 65535):      7f ff bb ff ff ff df ff c0 (5, 62)
+ *     32 x 32, all level 1 (heads 0, 4, 8, 12; level 3 is cut, level 2 is whole and splits),
+ *              d in coding order (4, -8), (0, 0), (-1, 1), (0, 3):   b8 78 3e d0 c2 (18, 17)
+ *     16 x 16, four level-0 blocks (levels 3 and 2 are cut), all d = 0:   80 (9, 0)
+ *     16 x 16, one level-1 partition, d = 0 (the flat CTU):     no bytes (3, 0)
+ *
+ * xEntropyEncodeMvGpu reads d_ctu[c].head_mask and offset and the words d_words[offset .. offset + 4 * popcount) of pack's stream
+ * (offset needs no alignment), and writes every record of d_coded.  offset there is the exclusive prefix sum of n_words, in 64 bits;
+ * d_total[0] = the total number of words, d_total[1] = the number of leading CTUs whose substream lies completely inside cap_words.  A
+ * substream is written if and only if offset + n_words <= cap_words; no word at or beyond cap_words is ever written.  cap_words == 0
+ * with d_stream == NULL is the count-only call.  Three launches on the caller's stream: count and records, the offsets (the scan of
+ * xLevelsPackGpu), write.
+ * xEntropyDecodeMvGpu trusts nothing in a record of d_coded but offset and n_bytes, and holds both against cap_words before any
+ * load.  CTU c's payload goes to the fixed place d_words[256 c ..): per partition the words 0, 0, low16(dx), low16(dy); words of
+ * [256 c, 256 c + 256) beyond the payload are not written.  It writes every field of d_ctu[c]: head_mask, offset = 256 c, n_words =
+ * 4 * parts, parts, and bits and max_abs recomputed from the decoded true differences.  For an encoder's input that came from
+ * xMotionPackGpu, decode of encode returns pack's records in every field but offset, and pack's words 2 and 3.  d_status, if not NULL,
+ * gets 0 (good), 1 (record outside the capacity) or 2 (malformed substream) per CTU.  d_total is ignored; d_stream may be NULL when
+ * cap_words == 0; in_words is ignored.  One launch.
+ * Both: one wave per CTU, the coder's chain on one lane over LDS; no atomics, no allocation; the same input gives the same bytes on
+ * every run and under every launch option; the calls can be captured into a graph.
+ *
+ * xMotionReconstructGpu takes x266_motion_t as it is: xMotionUnpackGpu for a stream whose words 0 and 1 are not to be trusted.  It
+ * reads d_ctu[c].head_mask, offset and the words 2 and 3 of each partition -- words 0 and 1 are never read, nor anything outside
+ * [0, cap_words) -- and writes d_mv (cost 0) and d_level for every existing block.  Per partition in coding order q = (int16_t)(P +
+ * (int16_t)word), P the causal predictor over the field as reconstructed so far.  A CTU whose mask is malformed or whose payload does
+ * not lie inside cap_words is written as vector (0, 0), level 0, exactly as unpack writes it; later CTUs predict from those zeros, so
+ * the result is a function of the input alone.  d_total is ignored; the X266HIP_EINVAL rules and the extents are unpack's.
+ * Schedule.  CTU (cx, cy) reads the CTUs to its left, above, above left and above RIGHT (C of a partition that touches the CTU's top
+ * right corner), so it belongs to step cx + 2 cy of cw + 2 (ch - 1) steps: one launch per step on the caller's stream, one wave per
+ * CTU of the step, ordered by the stream alone -- no flags, no waiting on memory, no cooperative launch.
+ *
+ * X266HIP_EINVAL for the two coder calls, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned
+ * required buffer (alignments: the field comments), a NULL d_stream with cap_words != 0, an entry of init outside 31 .. 2017, a side
+ * that is not a positive multiple of 16, a span that does not fit in the address space, an output overlapping any other buffer.  The
+ * extents are 32 bytes per CTU for d_ctu and for d_coded, in_words * 2 (encode) or 512 bytes per CTU (decode) for d_words, cap_words * 2
+ * for d_stream, 16 bytes for d_total and one byte per CTU for d_status.  On encode d_words may be NULL when in_words == 0.
+ * Out of scope: class bytes, intra modes, kinds and qp; context carry-over between CTUs; adapted tables coming back from the device;
+ * bi-directional fields; merge and skip candidates; a persistent or flag-synchronised wavefront kernel. */
+#define X266_ENTROPY_MOTION_CONTEXTS  7
+#define X266_ENTROPY_MOTION_MAX_BYTES 720
+typedef struct x266_entropy_motion_ctu_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
+    uint32_t ctx_bins;     /* context-coded bins of the CTU                                      */
+    uint32_t bypass_bins;  /* bypass bins of the CTU                                             */
+    uint64_t offset;       /* start of the CTU's substream in d_stream, in 16-bit words          */
+    uint32_t n_words;      /* (n_bytes + 1) / 2                                                  */
+    uint32_t n_bytes;      /* bytes of the substream, 0 .. X266_ENTROPY_MOTION_MAX_BYTES         */
+    uint32_t parts;        /* partitions coded; 0 for an unreadable CTU                          */
+    uint32_t unreadable;   /* 1: the input CTU could not be read and was coded as the empty substream */
+} x266_entropy_motion_ctu_t;
+typedef struct x266_entropy_motion_t {
+    x266_motion_ctu_t *d_ctu;            /* [n_ctu], 8-byte aligned; encode reads head_mask and offset only, decode writes every field */
+    uint16_t *d_words;                   /* 16-byte aligned; encode reads pack's stream, [in_words]; decode writes [256 * n_ctu]       */
+    x266_entropy_motion_ctu_t *d_coded;  /* [n_ctu], 8-byte aligned; encode writes, decode reads offset and n_bytes only              */
+    uint16_t *d_stream;                  /* [cap_words], 16-byte aligned; the coded bytes, little-endian words as the level coder's   */
+    uint64_t *d_total;                   /* [2], 8-byte aligned; encode writes {words, leading CTUs that fit}; decode ignores (may be NULL there) */
+    uint8_t  *d_status;                  /* [n_ctu] or NULL, any alignment; decode only: 0 good, 1 record outside the capacity, 2 malformed substream */
+    const uint16_t *init;                /* HOST memory, [X266_ENTROPY_MOTION_CONTEXTS], or NULL: the default table                   */
+    int width, height;                   /* positive multiples of 16 */
+    uint64_t in_words, cap_words;
+} x266_entropy_motion_t;
+int xEntropyEncodeMvGpu(x266hip_ctx *ctx, const x266_entropy_motion_t *p, void *stream);
+int xEntropyDecodeMvGpu(x266hip_ctx *ctx, const x266_entropy_motion_t *p, void *stream);
+int xMotionReconstructGpu  (x266hip_ctx *ctx, const x266_motion_t *p, void *stream);
+/* Host only, the functions the kernels run.  xEntropyMvDefaultInit writes the default table.  xEntropyEncodeMvCtu codes CTU `ctu`
+ * of a width x height frame from its head mask and its 4 * popcount(head_mask) words of pack's form under `init` (NULL: the default):
+ * it returns n_bytes, stores the first min(n_bytes, cap) bytes in out (which may be NULL with cap 0) and, with bins != NULL, the context
+ * and the bypass bin counts; X266HIP_EINVAL for a malformed mask, a bad size, a ctu >= n_ctu, a NULL words, a NULL out with a cap or a
+ * table entry outside 31 .. 2017.  xEntropyDecodeMvCtu writes the head mask, the payload (0, 0, low16(dx), low16(dy) per partition,
+ * the rest of words[256] zero) and the number of partitions; it returns 0, or 1 for a malformed substream (then the flat CTU), or
+ * X266HIP_EINVAL for a bad size, a ctu >= n_ctu, a NULL output, a NULL bytes with a length, an n_bytes above
+ * X266_ENTROPY_MOTION_MAX_BYTES or a bad table. */
+int xEntropyMvDefaultInit(uint16_t init[X266_ENTROPY_MOTION_CONTEXTS]);
+int xEntropyEncodeMvCtu(int width, int height, size_t ctu, uint64_t head_mask, const uint16_t *words, const uint16_t *init, uint8_t *out,
+                            size_t cap, uint32_t bins[2]);
+int xEntropyDecodeMvCtu(int width, int height, size_t ctu, const uint8_t *bytes, size_t n_bytes, const uint16_t *init, uint64_t *head_mask,
+                            uint16_t words[256], uint32_t *parts);
 
 /* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
  * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source

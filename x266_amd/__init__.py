@@ -11,11 +11,13 @@ from ._lib import (X266Error, Codec, lib_path, load_library, build_library,  # n
                    RdoqParams, RDOQ_REGION_DTYPE, level_bits, last_pos_bits, cg_flag_bits, TDecideParams, TDECIDE_CLASSES,
                    AqParams, AQ_TILE_DTYPE, aq_totals_chunk, QualityParams, QUALITY_CTU_DTYPE, QUALITY_SSE, QUALITY_SSIM,
                    LaParams, LA_BLOCK_DTYPE, la_totals_chunk, scene_cut_from_totals, SeedParams, MixedParams, PartParams, PART_CTU_DTYPE,
-                   MotionParams, MOTION_CTU_DTYPE, EntropyParams, ENTROPY_REGION_DTYPE, ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES)
+                   MotionParams, MOTION_CTU_DTYPE, EntropyParams, ENTROPY_REGION_DTYPE, ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES,
+                   EntropyMotionParams, ENTROPY_MOTION_CTU_DTYPE, ENTROPY_MOTION_CONTEXTS, ENTROPY_MOTION_MAX_BYTES)
 
 __all__ = ["X266Error", "Codec", "lib_path", "load_library", "build_library",
            "pack_diff_rows", "pack_dct_word", "LevelsParams", "LEVEL_REGION_DTYPE", "level_scan", "levels_scan_chunk",
            "RdoqParams", "RDOQ_REGION_DTYPE", "level_bits", "last_pos_bits", "cg_flag_bits", "TDecideParams", "TDECIDE_CLASSES",
            "AqParams", "AQ_TILE_DTYPE", "aq_totals_chunk", "QualityParams", "QUALITY_CTU_DTYPE", "QUALITY_SSE", "QUALITY_SSIM",
            "LaParams", "LA_BLOCK_DTYPE", "la_totals_chunk", "scene_cut_from_totals", "SeedParams", "MixedParams", "PartParams", "PART_CTU_DTYPE",
-           "MotionParams", "MOTION_CTU_DTYPE", "EntropyParams", "ENTROPY_REGION_DTYPE", "ENTROPY_CONTEXTS", "ENTROPY_MAX_BYTES"]
+           "MotionParams", "MOTION_CTU_DTYPE", "EntropyParams", "ENTROPY_REGION_DTYPE", "ENTROPY_CONTEXTS", "ENTROPY_MAX_BYTES",
+           "EntropyMotionParams", "ENTROPY_MOTION_CTU_DTYPE", "ENTROPY_MOTION_CONTEXTS", "ENTROPY_MOTION_MAX_BYTES"]

@@ -127,6 +127,19 @@ ENTROPY_CONTEXTS = 100
 ENTROPY_MAX_BYTES = 6848
 
 
+class EntropyMotionParams(ctypes.Structure):
+    """x266_entropy_motion_t of include/x266hip.h; `init` is a HOST address (or None: the default table)"""
+    _fields_ = [(name, _P) for name in ("d_ctu", "d_words", "d_coded", "d_stream", "d_total", "d_status", "init")] + \
+               [("width", ctypes.c_int), ("height", ctypes.c_int), ("in_words", ctypes.c_uint64), ("cap_words", ctypes.c_uint64)]
+
+
+# x266_entropy_motion_ctu_t of include/x266hip.h
+ENTROPY_MOTION_CTU_DTYPE = np.dtype([("ctx_bins", "<u4"), ("bypass_bins", "<u4"), ("offset", "<u8"), ("n_words", "<u4"), ("n_bytes", "<u4"), ("parts", "<u4"),
+                                     ("unreadable", "<u4")])
+ENTROPY_MOTION_CONTEXTS = 7
+ENTROPY_MOTION_MAX_BYTES = 720
+
+
 class MixedParams(ctypes.Structure):
     """x266_mixed_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
@@ -273,6 +286,12 @@ def load_library(path=None):
     L.xEntropyDefaultInit.argtypes = [_P]
     L.xEntropyEncodeRegion.argtypes = [_P, ctypes.c_int, _P, _P, _SZ, _P]
     L.xEntropyDecodeRegion.argtypes = [_P, _SZ, ctypes.c_int, _P, _P, _P]
+    L.xEntropyEncodeMvGpu.argtypes = [_P, ctypes.POINTER(EntropyMotionParams), _P]
+    L.xEntropyDecodeMvGpu.argtypes = [_P, ctypes.POINTER(EntropyMotionParams), _P]
+    L.xMotionReconstructGpu.argtypes = [_P, ctypes.POINTER(MotionParams), _P]
+    L.xEntropyMvDefaultInit.argtypes = [_P]
+    L.xEntropyEncodeMvCtu.argtypes = [ctypes.c_int, ctypes.c_int, _SZ, ctypes.c_uint64, _P, _P, _P, _SZ, _P]
+    L.xEntropyDecodeMvCtu.argtypes = [ctypes.c_int, ctypes.c_int, _SZ, _P, _SZ, _P, _P, _P, _P]
     L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -1408,6 +1427,10 @@ class Codec:
 
     def entropy_decode_levels_dev(self, params, stream=0):
         self._check(self.L.xEntropyDecodeLevelsGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyDecodeLevelsGpu")
+
+    # -- the vectors from the differences: the numpy call is x266_amd/motion.py's; the coder of the motion stream is x266_amd/entropy.py's ----
+    def motion_reconstruct_dev(self, params, stream=0):
+        self._check(self.L.xMotionReconstructGpu(self.ctx, ctypes.byref(params) if params is not None else None, stream), "xMotionReconstructGpu")
 
     # -- mixed inter / intra coding of a frame: intra 32x32 regions in P- and B-frames -------------------------
     @staticmethod

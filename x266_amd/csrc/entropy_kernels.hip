@@ -12,6 +12,7 @@
 // 16-byte chunks, single words only at the two ragged ends a substream shares with its neighbours).
 // Decode checks offset and n_bytes against cap_words BEFORE any load, stages the substream through LDS the same way, decodes on lane 0
 // into a zeroed region slab and writes the whole region, zeros included; a malformed region is cleared again.
+// The slab copy (substream_copy) is x266_entropy.hpp's: entropy_motion_kernels.hip, the motion stream's coder of the same shape, shares it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -114,16 +115,7 @@ __global__ __launch_bounds__(64 * kEntropyWavesPerWg) void entropy_encode_kernel
     if (n_bytes > kEntropyMaxBytes || ((n_bytes + 1u) >> 1) != n_words) return;   // as counted; held against the record all the same
     const uint16_t *src = reinterpret_cast<const uint16_t *>(lds_stream[wave_in_wg]);
     uint16_t *dst = stream + (offset - phase);                              // 16-byte aligned: d_stream is, and offset - phase is a multiple of 8
-    const unsigned n_chunks = (phase + n_words + 7u) >> 3;
-    for (unsigned c = lane; c < n_chunks; c += 64) {
-        const unsigned lo = c * 8;
-        if (lo >= phase && lo + 8 <= phase + n_words) {
-            *reinterpret_cast<v4i *>(dst + lo) = *reinterpret_cast<const v4i *>(src + lo);
-        } else {
-            for (unsigned w = lo; w < lo + 8; ++w)
-                if (w >= phase && w < phase + n_words) dst[w] = src[w];
-        }
-    }
+    substream_copy(dst, src, phase, n_words, lane);
 }
 
 __global__ __launch_bounds__(64 * kEntropyWavesPerWg) void entropy_decode_kernel(int16_t *__restrict__ level, const uint8_t *__restrict__ cls,
@@ -156,16 +148,7 @@ __global__ __launch_bounds__(64 * kEntropyWavesPerWg) void entropy_decode_kernel
     uint16_t *pay = reinterpret_cast<uint16_t *>(lds_stream[wave_in_wg]);
     if (n_words) {
         const uint16_t *src = stream + (offset - phase);
-        const unsigned n_chunks = (phase + n_words + 7u) >> 3;
-        for (unsigned c = lane; c < n_chunks; c += 64) {
-            const unsigned lo = c * 8;
-            if (lo >= phase && lo + 8 <= phase + n_words) {
-                *reinterpret_cast<v4i *>(pay + lo) = *reinterpret_cast<const v4i *>(src + lo);
-            } else {
-                for (unsigned w = lo; w < lo + 8; ++w)
-                    if (w >= phase && w < phase + n_words) pay[w] = src[w];
-            }
-        }
+        substream_copy(pay, src, phase, n_words, lane);
     }
     char *slab = lds_region[wave_in_wg];
     uint16_t *ctx = lds_ctx[wave_in_wg];

@@ -11,6 +11,7 @@
 // on this record, whose first 20 bytes are the level record's), write (each head lane stores its 8 bytes; offsets are multiples of four
 // words, so every store is aligned).  Unpack is one launch: the mask is tested lane by lane before any word of the stream is read.
 // No atomics, no workgroup waits for another: the bytes depend on the data alone.
+// xMotionReconstructGpu, unpack for a stream that carries only the differences, is entropy_motion_kernels.hip's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -13,7 +13,8 @@
 // tests/cpp/tdecide_rules_check.cpp, and so have frame quality (quality_stats, x266_quality_t): tests/cpp/quality_rules_check.cpp, and the
 // inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp, the compact motion stream (motion_pack,
 // motion_unpack, x266_motion_t): tests/cpp/motion_rules_check.cpp, and the entropy coder (entropy_encode, entropy_decode, x266_entropy_t):
-// tests/cpp/entropy_rules_check.cpp.
+// tests/cpp/entropy_rules_check.cpp, and the entropy coder of the motion stream (entropy_motion_encode, entropy_motion_decode,
+// x266_entropy_motion_t; motion_reconstruct): tests/cpp/entropy_motion_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -757,6 +758,43 @@ inline const char *entropy_decode(const x266_entropy_t *p)
     b[3].optional = p->cap_words == 0;
     return check(b);
 }
+
+// ---- the entropy coder of the motion stream ----------------------------------------------------------------------------------------------
+// xEntropyEncodeMvGpu, xEntropyDecodeMvGpu: the device pointers are the fields of the host-read x266_entropy_motion_t, held by
+// tests/cpp/entropy_motion_rules_check.cpp.  `init` is host memory, 7 entries in 31 .. 2017; the stream's extent and the count-only call
+// are the level stream's; d_words is in_words * 2 bytes on encode (NULL allowed when that is 0) and 512 bytes per CTU on decode.
+// xMotionReconstructGpu has the rules of xMotionUnpackGpu.
+inline bool entropy_motion_init_ok(const uint16_t *init)
+{
+    if (!init) return true;
+    for (unsigned i = 0; i < X266_ENTROPY_MOTION_CONTEXTS; ++i)
+        if (init[i] < 31 || init[i] > 2017) return false;
+    return true;
+}
+inline const char *entropy_motion_encode(const x266_entropy_motion_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (!entropy_motion_init_ok(p->init)) return kEntropyInit;
+    const size_t n = ctus(p->width, p->height);
+    Buf b[] = {out("d_coded", p->d_coded, 8, n * sizeof(x266_entropy_motion_ctu_t)), out("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)),
+               out("d_total", p->d_total, 8, 16), in("d_ctu", p->d_ctu, 8, n * sizeof(x266_motion_ctu_t)), in("d_words", p->d_words, 16, levels_stream_bytes(p->in_words))};
+    b[1].optional = p->cap_words == 0;
+    b[4].optional = p->in_words == 0;
+    return check(b);
+}
+inline const char *entropy_motion_decode(const x266_entropy_motion_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (const char *why = frame(p->width, p->height, 16)) return why;
+    if (!entropy_motion_init_ok(p->init)) return kEntropyInit;
+    const size_t n = ctus(p->width, p->height);
+    Buf b[] = {out("d_ctu", p->d_ctu, 8, n * sizeof(x266_motion_ctu_t)), out("d_words", p->d_words, 16, n * 512), opt(out("d_status", p->d_status, 1, n)),
+               in("d_coded", p->d_coded, 8, n * sizeof(x266_entropy_motion_ctu_t)), in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words))};
+    b[4].optional = p->cap_words == 0;
+    return check(b);
+}
+inline const char *motion_reconstruct(const x266_motion_t *p) { return motion_unpack(p); }
 
 // ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------
 inline const char *intra32_refs_from_tiles(const void *d_frame, int w, int h, int component, const void *d_refs)

@@ -288,9 +288,14 @@ hipError_t launch_partition_decide(const x266_part_t &p, hipStream_t stream);
 // the compact motion stream (motion_kernels.hip): pack = count, the level stream's offset scan, write on one stream; unpack is one launch
 hipError_t launch_motion_pack(const x266_motion_t &p, hipStream_t stream);
 hipError_t launch_motion_unpack(const x266_motion_t &p, hipStream_t stream);
+// the vectors from the differences: one launch per wavefront step cx + 2 cy, one wave per CTU of the step, stream order alone
+hipError_t launch_motion_reconstruct(const x266_motion_t &p, hipStream_t stream);
 // the entropy coder of the level stream (entropy_kernels.hip): encode = count, the level stream's offset scan, write on one stream; decode is one launch
 hipError_t launch_entropy_encode(const x266_entropy_t &p, hipStream_t stream);
 hipError_t launch_entropy_decode(const x266_entropy_t &p, hipStream_t stream);
+// the entropy coder of the motion stream (entropy_kernels.hip): the same three launches on x266_entropy_motion_ctu_t; decode is one launch
+hipError_t launch_entropy_motion_encode(const x266_entropy_motion_t &p, hipStream_t stream);
+hipError_t launch_entropy_motion_decode(const x266_entropy_motion_t &p, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

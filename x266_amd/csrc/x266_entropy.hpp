@@ -152,7 +152,7 @@ X266_HD inline void entropy_enc_bypass(EntropyEnc &e, unsigned bit)
     ++e.bypass_bins;
 }
 
-// the `count` low bits of value, most significant first; count <= 14
+// the `count` low bits of value, most significant first; any count up to 32 (the level syntax asks for 14 at most, the motion syntax 15)
 X266_HD inline void entropy_enc_bits(EntropyEnc &e, unsigned value, unsigned count)
 {
     for (unsigned i = count; i-- > 0;) entropy_enc_bypass(e, (value >> i) & 1u);
@@ -383,5 +383,25 @@ inline uint64_t entropy_cg_mask(const int16_t *level, unsigned k)
     }
     return mask;
 }
+
+#if defined(__HIPCC__)
+typedef int entropy_v4i __attribute__((ext_vector_type(4)));
+// The words [phase, phase + n_words) of src to the same places of dst; word 0 of both is 16-byte aligned (an LDS slab on one side, the
+// stream at offset - phase on the other): whole 16-byte chunks, single words only at the two ragged ends a substream shares with its
+// neighbours.  Nothing outside the substream's own words is read or written.
+__device__ __forceinline__ void substream_copy(uint16_t *dst, const uint16_t *src, unsigned phase, unsigned n_words, unsigned lane)
+{
+    const unsigned n_chunks = (phase + n_words + 7u) >> 3;
+    for (unsigned c = lane; c < n_chunks; c += 64) {
+        const unsigned lo = c * 8;
+        if (lo >= phase && lo + 8 <= phase + n_words) {
+            *reinterpret_cast<entropy_v4i *>(dst + lo) = *reinterpret_cast<const entropy_v4i *>(src + lo);
+        } else {
+            for (unsigned w = lo; w < lo + 8; ++w)
+                if (w >= phase && w < phase + n_words) dst[w] = src[w];
+        }
+    }
+}
+#endif
 
 }  // namespace x266

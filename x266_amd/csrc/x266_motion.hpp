@@ -125,14 +125,20 @@ X266_HD inline PartVec motion_vec_at(const x266_me_result_t *mv, int bw, int bx,
     const x266_me_result_t r = mv[(size_t)by * (size_t)bw + (size_t)bx];
     return PartVec{r.mvx, r.mvy};
 }
-X266_HD inline PartVec motion_predictor(const x266_me_result_t *mv, int bw, int X, int Y, int n)
+// at(bx, by) is the vector of a block inside the frame; only the spots the rule names are asked for
+template <class At>
+X266_HD inline PartVec motion_predictor_from(At at, int bw, int X, int Y, int n)
 {
     const bool has_a = X > 0, has_b = Y > 0;
     const bool c_right = motion_c_right_precedes(bw, X, Y, n), has_c = c_right || (X > 0 && Y > 0);
     const PartVec zero = {0, 0};
-    const PartVec a = has_a ? motion_vec_at(mv, bw, X - 1, Y) : zero, b = has_b ? motion_vec_at(mv, bw, X, Y - 1) : zero;
-    const PartVec c = c_right ? motion_vec_at(mv, bw, X + n, Y - 1) : (has_c ? motion_vec_at(mv, bw, X - 1, Y - 1) : zero);
+    const PartVec a = has_a ? at(X - 1, Y) : zero, b = has_b ? at(X, Y - 1) : zero;
+    const PartVec c = c_right ? at(X + n, Y - 1) : (has_c ? at(X - 1, Y - 1) : zero);
     return part_predict3(has_a, a, has_b, b, has_c, c);
+}
+X266_HD inline PartVec motion_predictor(const x266_me_result_t *mv, int bw, int X, int Y, int n)
+{
+    return motion_predictor_from([=](int bx, int by) { return motion_vec_at(mv, bw, bx, by); }, bw, X, Y, n);
 }
 
 // ---- a partition's share of `bits`: its flag, the two differences, and the whole nodes that split above it

@@ -24,6 +24,7 @@
 #include "x266_args.hpp"
 #include "x266_device.hpp"
 #include "x266_entropy.hpp"
+#include "x266_entropy_motion.hpp"
 #include "x266_levels.hpp"
 #include "x266_motion.hpp"
 #include "x266_quality.hpp"
@@ -1658,6 +1659,81 @@ int xEntropyDecodeRegion(const uint8_t *bytes, size_t n_bytes, int cls, const ui
         count = 0;
     }
     if (n_nz) *n_nz = count;
+    return good ? 0 : 1;
+}
+
+// ---- the entropy coder of the motion stream (entropy_kernels.hip, x266_entropy_motion.hpp) and the vectors from the differences (motion_kernels.hip)
+int xEntropyEncodeMvGpu(x266hip_ctx *ctx, const x266_entropy_motion_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_motion_encode(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "motion entropy encode launch", launch_entropy_motion_encode(*p, (hipStream_t)stream));
+}
+
+int xEntropyDecodeMvGpu(x266hip_ctx *ctx, const x266_entropy_motion_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_motion_decode(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "motion entropy decode launch", launch_entropy_motion_decode(*p, (hipStream_t)stream));
+}
+
+int xMotionReconstructGpu(x266hip_ctx *ctx, const x266_motion_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::motion_reconstruct(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "motion reconstruct launch", launch_motion_reconstruct(*p, (hipStream_t)stream));
+}
+
+// the three host helpers: the functions of x266_entropy_motion.hpp that the kernels run, on the host
+int xEntropyMvDefaultInit(uint16_t init[X266_ENTROPY_MOTION_CONTEXTS])
+{
+    if (!init) return X266HIP_EINVAL;
+    for (unsigned i = 0; i < kEntropyMotionContexts; ++i) init[i] = kEntropyMotionDefault.p[i];
+    return X266HIP_OK;
+}
+
+int xEntropyEncodeMvCtu(int width, int height, size_t ctu, uint64_t head_mask, const uint16_t *words, const uint16_t *init, uint8_t *out, size_t cap,
+                            uint32_t bins[2])
+{
+    if (args::frame(width, height, 16) || ctu >= args::ctus(width, height) || !words || (!out && cap) || !args::entropy_motion_init_ok(init)) return X266HIP_EINVAL;
+    const MotionCtu g = motion_ctu(width / 8, height / 8, ctu);
+    if (!motion_mask_well_formed(g, head_mask)) return X266HIP_EINVAL;
+    uint16_t c[kEntropyMotionContexts];
+    for (unsigned i = 0; i < kEntropyMotionContexts; ++i) c[i] = (init ? init : kEntropyMotionDefault.p)[i];
+    EntropyEnc e;
+    entropy_enc_start(e, out, cap > kEntropyMotionMaxBytes ? kEntropyMotionMaxBytes : (uint32_t)cap);
+    entropy_motion_encode_ctu(e, g, head_mask, words, c);
+    const uint32_t n_bytes = entropy_enc_finish(e);
+    if (bins) {
+        bins[0] = e.ctx_bins;
+        bins[1] = e.bypass_bins;
+    }
+    return (int)n_bytes;
+}
+
+int xEntropyDecodeMvCtu(int width, int height, size_t ctu, const uint8_t *bytes, size_t n_bytes, const uint16_t *init, uint64_t *head_mask, uint16_t words[256],
+                            uint32_t *parts)
+{
+    if (args::frame(width, height, 16) || ctu >= args::ctus(width, height) || !head_mask || !words || !parts || (!bytes && n_bytes) ||
+        n_bytes > kEntropyMotionMaxBytes || !args::entropy_motion_init_ok(init))
+        return X266HIP_EINVAL;
+    const MotionCtu g = motion_ctu(width / 8, height / 8, ctu);
+    uint16_t c[kEntropyMotionContexts];
+    for (unsigned i = 0; i < kEntropyMotionContexts; ++i) c[i] = (init ? init : kEntropyMotionDefault.p)[i];
+    for (unsigned i = 0; i < kMotionCtuWords; ++i) words[i] = 0;
+    EntropyDec d;
+    entropy_dec_start(d, bytes, (uint32_t)n_bytes);
+    EntropyMotionCtu r;
+    const bool good = entropy_motion_decode_ctu(d, g, c, words, &r);
+    if (!good) {
+        for (unsigned i = 0; i < kMotionCtuWords; ++i) words[i] = 0;
+        entropy_motion_flat_ctu(g, c, words, &r);
+    }
+    *head_mask = r.mask;
+    *parts = r.parts;
     return good ? 0 : 1;
 }
 

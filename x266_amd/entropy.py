@@ -1,9 +1,13 @@
 """The entropy coder of the level stream (include/x266hip.h: xEntropyEncodeLevelsGpu, xEntropyDecodeLevelsGpu): the numpy calls around
 Codec.entropy_encode_levels_dev and Codec.entropy_decode_levels_dev, built from the pieces the Codec's own numpy methods are built from,
-and the three host helpers of the library (xEntropyDefaultInit, xEntropyEncodeRegion, xEntropyDecodeRegion).  No arithmetic lives here."""
+and the three host helpers of the library (xEntropyDefaultInit, xEntropyEncodeRegion, xEntropyDecodeRegion); below them the same for the
+motion stream (xEntropyEncodeMvGpu, xEntropyDecodeMvGpu and their three helpers).  No arithmetic lives here."""
+import ctypes
+
 import numpy as np
 
-from ._lib import ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES, ENTROPY_REGION_DTYPE, Codec, EntropyParams, X266Error, _NULL, load_library
+from ._lib import (ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES, ENTROPY_MOTION_CONTEXTS, ENTROPY_MOTION_CTU_DTYPE, ENTROPY_MOTION_MAX_BYTES, ENTROPY_REGION_DTYPE,
+                   MOTION_CTU_DTYPE, Codec, EntropyMotionParams, EntropyParams, X266Error, _NULL, load_library)
 
 
 def _init_table(init):
@@ -93,3 +97,99 @@ def entropy_decode_region(data, cls=3, init=None):
     if rc < 0:
         raise X266Error("xEntropyDecodeRegion: a bad argument")
     return level, int(n_nz[0]), rc == 1
+
+
+# ---- the motion stream (xEntropyEncodeMvGpu, xEntropyDecodeMvGpu) -----------------------------------------------------------------------
+def _motion_table(init):
+    if init is None:
+        return None
+    table = np.ascontiguousarray(init, np.uint16).ravel()
+    if table.size != ENTROPY_MOTION_CONTEXTS:
+        raise X266Error("init must hold %d entries" % ENTROPY_MOTION_CONTEXTS)
+    return table
+
+
+def entropy_motion_params(**fields):
+    """an x266_entropy_motion_t by field name: device addresses (absent or 0: NULL) and the HOST address `init`, then width, height, in_words
+    and cap_words"""
+    scalars = [fields.pop("width", 0), fields.pop("height", 0), fields.pop("in_words", 0), fields.pop("cap_words", 0)]
+    return Codec._keyword_params(EntropyMotionParams, "entropy_motion_params", fields, scalars)
+
+
+def entropy_encode_motion_dev(codec, params, stream=0):
+    codec._check(codec.L.xEntropyEncodeMvGpu(codec.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyEncodeMvGpu")
+
+
+def entropy_decode_motion_dev(codec, params, stream=0):
+    codec._check(codec.L.xEntropyDecodeMvGpu(codec.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyDecodeMvGpu")
+
+
+def entropy_encode_motion(codec, records, words, w, h, cap_words=None, init=None):
+    """numpy convenience around xEntropyEncodeMvGpu: the records (MOTION_CTU_DTYPE) and the words of xMotionPackGpu for a w x h frame
+    (init: 7 uint16 or None) -> (coded [n_ctu] of ENTROPY_MOTION_CTU_DTYPE, stream uint16 [cap_words], total uint64 [2]).  cap_words None: a
+    count-only call sizes the stream exactly; words the call does not write are 0."""
+    n_ctu = codec.ctu_count(w, h)
+    src = np.ascontiguousarray(words, np.uint16).ravel()
+    table = _motion_table(init)
+    d_ctu = codec._table(records, MOTION_CTU_DTYPE, n_ctu)
+    d_words = codec._upload(src) if src.size else _NULL
+    d_coded, d_tot = codec.alloc(32 * n_ctu), codec.alloc(16)
+    p = entropy_motion_params(d_ctu=d_ctu.ptr, d_words=d_words.ptr, d_coded=d_coded.ptr, d_total=d_tot.ptr, init=table.ctypes.data if table is not None else 0,
+                              width=w, height=h, in_words=src.size)
+    if cap_words is None:
+        entropy_encode_motion_dev(codec, p)
+        cap_words = codec._fetch((d_tot, np.uint64, (2,)))[0]
+    cap_words = int(cap_words)
+    d_str = codec._upload(np.zeros(cap_words, np.uint16)) if cap_words else _NULL
+    p.d_stream, p.cap_words = d_str.ptr or None, cap_words
+    entropy_encode_motion_dev(codec, p)
+    return codec._fetch((d_coded, ENTROPY_MOTION_CTU_DTYPE, (n_ctu,)), (d_str, np.uint16, (cap_words,)), (d_tot, np.uint64, (2,)))
+
+
+def entropy_decode_motion(codec, coded, stream, w, h, init=None):
+    """numpy convenience around xEntropyDecodeMvGpu: the coded records (ENTROPY_MOTION_CTU_DTYPE) and the stream's words of a w x h frame ->
+    (records [n_ctu] of MOTION_CTU_DTYPE, words uint16 [256 * n_ctu] -- zero where the call writes nothing --, status uint8 [n_ctu])"""
+    n_ctu = codec.ctu_count(w, h)
+    src = np.ascontiguousarray(stream, np.uint16).ravel()
+    table = _motion_table(init)
+    d_coded = codec._table(coded, ENTROPY_MOTION_CTU_DTYPE, n_ctu)
+    d_str = codec._upload(src) if src.size else _NULL
+    d_ctu, d_words, d_status = codec.alloc(32 * n_ctu), codec._upload(np.zeros(256 * n_ctu, np.uint16)), codec.alloc(max(n_ctu, 16))
+    entropy_decode_motion_dev(codec, entropy_motion_params(d_ctu=d_ctu.ptr, d_words=d_words.ptr, d_coded=d_coded.ptr, d_stream=d_str.ptr, d_status=d_status.ptr,
+                                                          init=table.ctypes.data if table is not None else 0, width=w, height=h, cap_words=src.size))
+    return codec._fetch((d_ctu, MOTION_CTU_DTYPE, (n_ctu,)), (d_words, np.uint16, (256 * n_ctu,)), (d_status, np.uint8, (n_ctu,)))
+
+
+def entropy_motion_default_init():
+    """xEntropyMvDefaultInit: the default table, 7 uint16"""
+    table = np.zeros(ENTROPY_MOTION_CONTEXTS, np.uint16)
+    if load_library().xEntropyMvDefaultInit(table.ctypes.data) != 0:
+        raise X266Error("xEntropyMvDefaultInit failed")
+    return table
+
+
+def entropy_encode_motion_ctu(w, h, ctu, head_mask, words, init=None, cap=ENTROPY_MOTION_MAX_BYTES):
+    """xEntropyEncodeMvCtu: (the substream's first min(n_bytes, cap) bytes, n_bytes, context bins, bypass bins)"""
+    src = np.ascontiguousarray(words, np.uint16).ravel()
+    if src.size != 4 * bin(int(head_mask)).count("1"):
+        raise X266Error("a partition is four words")
+    src = np.concatenate([src, np.zeros(4, np.uint16)])                       # never an empty array: its address would be NULL
+    table = _motion_table(init)
+    out, bins = np.zeros(max(int(cap), 1), np.uint8), np.zeros(2, np.uint32)
+    n = load_library().xEntropyEncodeMvCtu(int(w), int(h), int(ctu), int(head_mask), src.ctypes.data, table.ctypes.data if table is not None else None,
+                                               out.ctypes.data if cap else None, int(cap), bins.ctypes.data)
+    if n < 0:
+        raise X266Error("xEntropyEncodeMvCtu: a malformed mask or a bad argument")
+    return out[:min(n, int(cap))].tobytes(), n, int(bins[0]), int(bins[1])
+
+
+def entropy_decode_motion_ctu(w, h, ctu, data, init=None):
+    """xEntropyDecodeMvCtu: (head_mask, words uint16 [4 * parts], malformed)"""
+    raw = np.frombuffer(bytes(data), np.uint8)
+    table = _motion_table(init)
+    mask, words, parts = np.zeros(1, np.uint64), np.zeros(256, np.uint16), np.zeros(1, np.uint32)
+    rc = load_library().xEntropyDecodeMvCtu(int(w), int(h), int(ctu), raw.ctypes.data if raw.size else None, raw.size,
+                                                table.ctypes.data if table is not None else None, mask.ctypes.data, words.ctypes.data, parts.ctypes.data)
+    if rc < 0:
+        raise X266Error("xEntropyDecodeMvCtu: a bad argument")
+    return int(mask[0]), words[:4 * int(parts[0])].copy(), rc == 1

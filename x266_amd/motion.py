@@ -1,5 +1,5 @@
-"""The compact motion stream (include/x266hip.h: xMotionPackGpu, xMotionUnpackGpu): the numpy calls around Codec.motion_pack_dev and
-Codec.motion_unpack_dev, built from the pieces the Codec's own numpy methods are built from, and the three host helpers of the library
+"""The compact motion stream (include/x266hip.h: xMotionPackGpu, xMotionUnpackGpu, xMotionReconstructGpu): the numpy calls around
+Codec.motion_pack_dev, Codec.motion_unpack_dev and Codec.motion_reconstruct_dev, built from the pieces the Codec's own numpy methods are built from, and the three host helpers of the library
 (xMotionWalk, xMotionPredictor, xMotionVectorBits).  No arithmetic lives here."""
 import ctypes
 
@@ -67,3 +67,16 @@ def motion_predictor(w, h, field, X, Y, level):
 def motion_vector_bits(d):
     """xMotionVectorBits: L(d), or -1 beyond |d| = 65535"""
     return int(load_library().xMotionVectorBits(int(d)))
+
+
+def motion_reconstruct(codec, records, stream, w, h):
+    """numpy convenience around xMotionReconstructGpu: records (MOTION_CTU_DTYPE) and the stream's words of a w x h frame, of which only the
+    differences (words 2 and 3 of a partition) are read -> (mv [nb, 2] int16, cost [nb] uint32 -- all 0 --, level [nb] uint8)"""
+    nb, n_ctu = (w // 8) * (h // 8), codec.ctu_count(w, h)
+    words = np.ascontiguousarray(stream, np.uint16).ravel()
+    d_ctu = codec._table(records, MOTION_CTU_DTYPE, n_ctu)
+    d_str = codec._upload(words) if words.size else _NULL
+    d_mv, d_level = codec.alloc(8 * nb), codec.alloc(max(nb, 16))
+    codec.motion_reconstruct_dev(motion_params(d_mv=d_mv.ptr, d_level=d_level.ptr, d_ctu=d_ctu.ptr, d_stream=d_str.ptr, width=w, height=h, cap_words=words.size))
+    raw, level = codec._fetch((d_mv, np.uint8, (nb * 8,)), (d_level, np.uint8, (nb,)))
+    return raw.view(np.int16).reshape(nb, 4)[:, :2].copy(), raw.view(np.uint32).reshape(nb, 2)[:, 1].copy(), level
