@@ -1674,10 +1674,12 @@ int xMotionVectorBits(int d);
  * d_stream with cap_words != 0, an entry of init outside 31 .. 2017, a span that does not fit in the address space, an output
  * overlapping any other buffer.  The extents are the compact level stream's, with n_regions * 32 for d_region.  With n_regions == 0
  * only d_total of the encode call is looked at.
- * Out of scope, the follow-ups: class bytes, intra modes, kinds and qp (the motion stream is xEntropyEncodeMvGpu's, below); per-frame context statistics coming
+ * Out of scope, the follow-ups: per-frame context statistics coming
  * back from the device; context carry-over between regions, WPP-style rows included; sign hiding and dependent quantisation; splitting
  * a region's blocks over lanes as separate coders (a format question: separate coders are separate substreams); any real VVC or HEVC
- * bit-stream syntax.  Until the side information is coded and contexts carry over, a "bitrate" from these two calls is the residual's alone (xEntropyEncodeMvGpu adds the motion's). */
+ * bit-stream syntax.  Class bytes, intra modes, kinds and qp are not in this substream: the motion stream is xEntropyEncodeMvGpu's and the
+ * side information xEntropyEncodeSideGpu's (both below).  A "bitrate" from these two calls is the residual's alone; the three coders
+ * together hold what a P-frame needs, and until contexts carry over their bytes are an upper estimate of a real stream's. */
 #define X266_ENTROPY_CONTEXTS  100
 #define X266_ENTROPY_MAX_BYTES 6848
 typedef struct x266_entropy_region_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
@@ -1802,7 +1804,8 @@ int xEntropyDecodeRegion(const uint8_t *bytes, size_t n_bytes, int cls, const ui
  * that is not a positive multiple of 16, a span that does not fit in the address space, an output overlapping any other buffer.  The
  * extents are 32 bytes per CTU for d_ctu and for d_coded, in_words * 2 (encode) or 512 bytes per CTU (decode) for d_words, cap_words * 2
  * for d_stream, 16 bytes for d_total and one byte per CTU for d_status.  On encode d_words may be NULL when in_words == 0.
- * Out of scope: class bytes, intra modes, kinds and qp; context carry-over between CTUs; adapted tables coming back from the device;
+ * Out of scope: class bytes, intra modes, kinds and qp (they travel in the side stream, xEntropyEncodeSideGpu, below); context carry-over
+ * between CTUs; adapted tables coming back from the device;
  * bi-directional fields; merge and skip candidates; a persistent or flag-synchronised wavefront kernel. */
 #define X266_ENTROPY_MOTION_CONTEXTS  7
 #define X266_ENTROPY_MOTION_MAX_BYTES 720
@@ -1842,6 +1845,150 @@ int xEntropyEncodeMvCtu(int width, int height, size_t ctu, uint64_t head_mask, c
                             size_t cap, uint32_t bins[2]);
 int xEntropyDecodeMvCtu(int width, int height, size_t ctu, const uint8_t *bytes, size_t n_bytes, const uint16_t *init, uint64_t *head_mask,
                             uint16_t words[256], uint32_t *parts);
+
+/* ---- the entropy coder of the side information: kinds, intra modes, coded flags, classes and qp as range-coded CTU substreams ----
+ * The level substreams need the class bytes to be parsed, xQuantRegionsGpu(1) needs the qp, the deblocking calls need the kinds and
+ * the intra reconstruction the modes; none of these is in the level or the motion stream.  xEntropyEncodeSideGpu codes what
+ * xDct32CodeMixedFrameGpu, xTransformDecideCtuTilesGpu and xAqDecideGpu / xLaTreeQpGpu decide per 32x32 region into a third stream,
+ * one independent substream per CTU under the range coder of the levels (above; the coder, its bytes, the stream's words and the
+ * padding are exactly those); xEntropyDecodeSideGpu is its inverse.  With the level and the motion coder this holds everything the
+ * chain needs to reconstruct a P-frame.  No upstream counterpart; the arithmetic here is the contract.
+ *
+ * Regions.  r = 6 ctu + q, q over Y0 Y1 Y2 Y3 U V, as the coding calls index them; Y0 Y1 are the top two luma regions of the CTU, Y2 Y3
+ * the bottom two.  The calls take n_ctu, not a frame size: a region outside the frame still has its bytes.
+ *
+ * Canonical values: what is coded, and what decode returns.  Per CTU and q:
+ *     K[q]   d_kind[r] != 0 for q <= 3.  There is ONE chroma kind: K[4] = K[5] = (d_kind[6 ctu + 4] != 0); entry 5 is ignored on
+ *            encode, decode writes both entries.
+ *     M[q]   for an intra region min(d_mode[r], 34), for an inter region 255.  There is one chroma mode, entry 4's: entry 5 is ignored on
+ *            encode, decode writes it into entries 4 and 5.
+ *     Z[q]   d_nnz[r] != 0: the region is CODED.  Decode writes 1 or 0.
+ *     C[q]   k = d_class[r] & 15, and k = 3 when (k & 3) == 3: the transforms read a size-32 class of any type as the 32-point DCT-II,
+ *            so C lies in X266_TDECIDE_CLASSES.  An uncoded region has C = 3.
+ *     Q[q]   min(d_qp[r], 51).  An uncoded region has Q = its predictor (below).
+ * A NULL array on encode: d_kind NULL = every kind 0; d_nnz NULL = every region coded; d_class NULL = every class 3; d_qp NULL = every
+ * luma qp is `qp` and every chroma qp clamp(qp + chroma_qp_offset, 0, 51).  d_mode == NULL with d_kind != NULL is X266HIP_EINVAL.  A
+ * NULL array on decode is not written.
+ *
+ * Syntax of a CTU.  For q = 0..3 in order: kind; the luma mode if intra; coded; if coded the class, then the qp difference.  Then the
+ * chroma part: one kind; the chroma mode if intra; then for q = 4 and for q = 5: coded, and if coded the class, then the qp difference.
+ * "Truncated unary of v with maximum m" is v one-bins and, if v < m, a zero-bin.
+ *     kind          one bin, 1 = intra.  Contexts: luma, chroma.
+ *     luma mode     HEVC's three most probable modes from A and B.  A is the mode of the left neighbour inside the CTU (q - 1 for odd
+ *                   q), B of the above neighbour inside the CTU (q - 2 for q >= 2); a neighbour that is absent or inter counts as mode 1.
+ *                   Nothing outside the CTU is read.  A == B < 2: {0, 1, 26}.  A == B >= 2: {A, 2 + ((A + 29) & 31), 2 + ((A - 1) & 31)}.
+ *                   A != B: {A, B, the first of 0, 1, 26 that is neither}.  Bin mpm (one context), 1 = M is in the list.  If set: the
+ *                   index as truncated unary with maximum 2 in bypass bins.  Otherwise the rank of M among the 32 other modes in
+ *                   ascending order as 5 bypass bits, most significant first; every rank 0..31 names a mode.
+ *     chroma mode   The list: M[0] if K[0], then 0, 26, 10, 1, duplicates dropped: 4 or 5 entries, in the order xDct32CodeMixedFrameGpu
+ *                   tries them.  Bin listed (one context), 1 = M is in the list.  If set: the index as truncated unary with maximum
+ *                   (entries - 1) in bypass bins.  Otherwise the rank among the 31 or 30 unlisted modes in ascending order as 5 bypass
+ *                   bits; a decoded rank at or beyond their number is malformed.
+ *     coded         one bin, Z.  Contexts: luma, chroma.
+ *     class         bin small = (C != 3), contexts luma, chroma.  If set: 2 - (C & 3) as truncated unary with maximum 2, context per bin
+ *                   (two), then C >> 2 as truncated unary with maximum 3, context per bin (three).
+ *     qp difference d = Q - pred.  cur starts at `qp`.  A coded luma region has pred = cur and then sets cur = Q; an uncoded luma region
+ *                   decodes to Q = cur.  U has pred = clamp(cur + chroma_qp_offset, 0, 51) with cur as Y3 left it; V has pred = U's Q,
+ *                   coded or not.  Bins: nz (d != 0; contexts luma, chroma); gt1 (|d| > 1; one context); if set r = |d| - 2 <= 49 as
+ *                   Exp-Golomb order 0 in bypass bins (v = r + 1, k = ilog2(v): k ones, a zero, the k low bits of v, most significant
+ *                   first; k <= 5); the sign as a bypass bin, 1 = negative.  A prefix of more than 5 ones is malformed; a decoded Q
+ *                   outside 0..51 is malformed.
+ * Contexts.  X266_ENTROPY_SIDE_CONTEXTS = 16, in this order: kind luma, chroma; mpm; listed; coded luma, chroma; small luma, chroma; the
+ * two bins of the size code; the three bins of the type code; nz luma, chroma; gt1.  They restart at every CTU from the call's table.
+ * `init` is HOST memory, 16 uint16 in 31 .. 2017, read during the call and passed by value; NULL is the default table
+ * (xEntropySideDefaultInit), all 1024: nothing measured justifies a skew.  The decoder must take the same table.
+ *
+ * Decoder rules.  Every loop is bounded: 6 regions, 5 list entries, 35 modes, unary codes of at most 2, 3 and 4 bins, 6 prefix bins, 5
+ * suffix bits.  The malformed cases are the three above: a chroma rank beyond the unlisted modes, a qp prefix of more than 5 ones, a Q
+ * outside 0..51.
+ * The flat CTU: every kind 0 and no region coded.  Its 11 bins (5 kinds, 6 coded flags) are all zero bins, so it encodes to 0 bytes,
+ * and zero bytes decode, under every table, to the flat CTU: kind 0, mode 255, d_nnz 0, class 3, qp equal to the predictors (`qp` for
+ * luma, clamp(qp + chroma_qp_offset, 0, 51) for chroma).  This one rule covers every failure on decode: a record with offset >
+ * cap_words, (n_bytes + 1) / 2 > cap_words - offset or n_bytes > X266_ENTROPY_SIDE_MAX_BYTES decodes as the flat CTU (d_status 1), and
+ * so does a malformed substream (d_status 2).  Nothing outside [0, cap_words) of d_stream is ever read, and inside a substream only its
+ * n_bytes count.
+ * Round trip.  Decode of encode returns the canonical form of the input, exactly, for every input byte value; encode of that canonical
+ * form gives the same bytes.
+ *
+ * The largest substream.  Context bins: a luma region has kind, mpm, coded, small, 2 + 3 class bins, nz, gt1 = 11, the chroma part kind
+ * and listed and per region coded, small, 2 + 3, nz, gt1 = 2 + 2 x 9: 64 in all, each under 6.05 bits (the level coder's bound).  Bypass
+ * bins: a mode rank is 5 (an index is at most 4), a qp difference at most 5 + 1 + 5 + 1 = 12: 4 x 17 + 5 + 2 x 12 = 97, each under
+ * 1.0001 bits.  That is under 485 bits, no more than 61 byte shifts, and with the termination 65 bytes: X266_ENTROPY_SIDE_MAX_BYTES =
+ * 80, a multiple of 16.  (The worst CTU that can be built -- every region intra with an unlisted mode, every class 12, every
+ * difference +-51 -- comes to 20 bytes under the default table and to 43 under a table of 2017s; the bound is the floor's, not a
+ * measured one.)
+ *
+ * Worked values, qp 32 and chroma_qp_offset 0 unless said, under the default table, bytes in hex (context bins, bypass bins):
+ *     the flat CTU:                                                        no bytes (11, 0)
+ *     Y0 intra with mode 26 (list {0, 1, 26}, index 2), nothing coded:     f0 (12, 2)
+ *     Y0 intra with mode 10 (rank 8 of the 32 others), nothing coded:      8f ff fc (12, 5)
+ *     chroma intra with mode 34 (list {0, 26, 10, 1}, rank 30):            01 0c 0e (12, 5)
+ *     Y0 coded with class 0, Y1 coded with class 14, both d = 0:           78 df ae (22, 0)
+ *     Y0 coded with Q = 33 (d = +1):                                       50 (14, 1)
+ *     qp 51, Y0 coded with Q = 0 (d = -51):                                5f d2 7c (14, 12)
+ *     every array NULL (all inter, all coded, class 3, d = 0):             44 4d 5a (23, 0)
+ *
+ * xEntropyEncodeSideGpu writes every record of d_coded.  offset there is the exclusive prefix sum of n_words, in 64 bits; d_total[0] =
+ * the total number of words, d_total[1] = the number of leading CTUs whose substream lies completely inside cap_words.  A substream is
+ * written if and only if offset + n_words <= cap_words; no word at or beyond cap_words is ever written.  cap_words == 0 with d_stream
+ * == NULL is the count-only call.  n_ctu == 0 writes d_total = {0, 0} and nothing else.  Three launches on the caller's stream: count
+ * and records, the offsets (the scan of xLevelsPackGpu), write.
+ * xEntropyDecodeSideGpu trusts nothing in a record of d_coded but offset and n_bytes, and holds both against cap_words before any load.
+ * It writes the six entries of every output array that is not NULL, and d_status, if not NULL: 0 (good), 1 (record outside the
+ * capacity) or 2 (malformed substream) per CTU.  d_total is ignored; d_stream may be NULL when cap_words == 0.  One launch; n_ctu == 0
+ * launches nothing.
+ * Both: ONE LANE per CTU -- a CTU has at most 161 bins, too few to give it a wave --, the coder's state in the lane's registers, its 16
+ * contexts and its bytes in LDS; no atomics, no allocation; the same input gives the same bytes on every run and under every launch
+ * option; the calls can be captured into a graph.
+ *
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned required buffer (d_coded,
+ * d_stream unless cap_words == 0, d_total on encode; alignments: the field comments), d_kind without d_mode on encode, an entry of init
+ * outside 31 .. 2017, qp outside 0..51, chroma_qp_offset outside -12..12, a span that does not fit in the address space, an output
+ * overlapping any other buffer.  The extents are 6 bytes per CTU for d_kind, d_mode, d_class and d_qp, 24 for d_nnz, 32 for d_coded,
+ * cap_words * 2 for d_stream, 16 for d_total, one byte per CTU for d_status.  With n_ctu == 0 only the scalars, init and d_total of
+ * the encode call are looked at.
+ * Out of scope: direction bytes of B-frames; SAO and ALF parameters; a frame header or any container around the three streams; context
+ * carry-over between CTUs; deriving class_bits of the transform decision from a table; adapted tables coming back from the device. */
+#define X266_ENTROPY_SIDE_CONTEXTS  16
+#define X266_ENTROPY_SIDE_MAX_BYTES 80
+typedef struct x266_entropy_side_ctu_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
+    uint32_t ctx_bins;     /* context-coded bins of the CTU                                      */
+    uint32_t bypass_bins;  /* bypass bins of the CTU                                             */
+    uint64_t offset;       /* start of the CTU's substream in d_stream, in 16-bit words          */
+    uint32_t n_words;      /* (n_bytes + 1) / 2                                                  */
+    uint32_t n_bytes;      /* bytes of the substream, 0 .. X266_ENTROPY_SIDE_MAX_BYTES           */
+    uint32_t n_intra;      /* intra regions of the CTU, 0 .. 6 (V counts with U's kind)          */
+    uint32_t n_coded;      /* coded regions of the CTU, 0 .. 6                                   */
+} x266_entropy_side_ctu_t;
+typedef struct x266_entropy_side_t {
+    uint8_t  *d_kind;                  /* [6 n_ctu] or NULL, any alignment; encode reads, decode writes                        */
+    uint8_t  *d_mode;                  /* [6 n_ctu] or NULL, any alignment; encode reads, decode writes                        */
+    uint8_t  *d_class;                 /* [6 n_ctu] or NULL, any alignment; encode reads, decode writes                        */
+    uint8_t  *d_qp;                    /* [6 n_ctu] or NULL, any alignment; encode reads, decode writes                        */
+    uint32_t *d_nnz;                   /* [6 n_ctu] or NULL, 4-byte aligned; encode reads, decode writes (1 or 0)               */
+    x266_entropy_side_ctu_t *d_coded;  /* [n_ctu], 8-byte aligned; encode writes, decode reads offset and n_bytes only         */
+    uint16_t *d_stream;                /* [cap_words], 16-byte aligned; the coded bytes, little-endian words as the level coder's */
+    uint64_t *d_total;                 /* [2], 8-byte aligned; encode writes {words, leading CTUs that fit}; decode ignores (may be NULL there) */
+    uint8_t  *d_status;                /* [n_ctu] or NULL, any alignment; decode only: 0 good, 1 record outside the capacity, 2 malformed substream */
+    const uint16_t *init;              /* HOST memory, [X266_ENTROPY_SIDE_CONTEXTS], or NULL: the default table                */
+    size_t    n_ctu;
+    uint64_t  cap_words;
+    int       qp;                      /* 0..51, the frame's                                                                   */
+    int       chroma_qp_offset;        /* -12..12                                                                              */
+} x266_entropy_side_t;
+int xEntropyEncodeSideGpu(x266hip_ctx *ctx, const x266_entropy_side_t *p, void *stream);
+int xEntropyDecodeSideGpu(x266hip_ctx *ctx, const x266_entropy_side_t *p, void *stream);
+/* Host only, the functions the kernels run.  xEntropySideDefaultInit writes the default table.  xEntropyEncodeSideCtu codes one CTU from
+ * six entries of each array (a NULL array as on the device call) under `init` (NULL: the default): it returns n_bytes, stores the first
+ * min(n_bytes, cap) bytes in out (which may be NULL with cap 0) and, with bins != NULL, the context and the bypass bin counts;
+ * X266HIP_EINVAL for kind without mode, a NULL out with a cap, a qp or chroma_qp_offset out of range or a table entry outside 31 .. 2017.
+ * xEntropyDecodeSideCtu writes six entries of every array that is not NULL; it returns 0, or 1 for a malformed substream (then the flat
+ * CTU), or X266HIP_EINVAL for a NULL bytes with a length, an n_bytes above X266_ENTROPY_SIDE_MAX_BYTES, a bad scalar or a bad table. */
+int xEntropySideDefaultInit(uint16_t init[X266_ENTROPY_SIDE_CONTEXTS]);
+int xEntropyEncodeSideCtu(const uint8_t *kind, const uint8_t *mode, const uint8_t *cls, const uint8_t *qp_in, const uint32_t *nnz, int qp,
+                          int chroma_qp_offset, const uint16_t *init, uint8_t *out, size_t cap, uint32_t bins[2]);
+int xEntropyDecodeSideCtu(const uint8_t *bytes, size_t n_bytes, int qp, int chroma_qp_offset, const uint16_t *init, uint8_t *kind, uint8_t *mode,
+                          uint8_t *cls, uint8_t *qp_out, uint32_t *nnz);
 
 /* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
  * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source

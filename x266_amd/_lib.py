@@ -140,6 +140,19 @@ ENTROPY_MOTION_CONTEXTS = 7
 ENTROPY_MOTION_MAX_BYTES = 720
 
 
+class EntropySideParams(ctypes.Structure):
+    """x266_entropy_side_t of include/x266hip.h; `init` is a HOST address (or None: the default table)"""
+    _fields_ = [(name, _P) for name in ("d_kind", "d_mode", "d_class", "d_qp", "d_nnz", "d_coded", "d_stream", "d_total", "d_status", "init")] + \
+               [("n_ctu", ctypes.c_size_t), ("cap_words", ctypes.c_uint64), ("qp", ctypes.c_int), ("chroma_qp_offset", ctypes.c_int)]
+
+
+# x266_entropy_side_ctu_t of include/x266hip.h
+ENTROPY_SIDE_CTU_DTYPE = np.dtype([("ctx_bins", "<u4"), ("bypass_bins", "<u4"), ("offset", "<u8"), ("n_words", "<u4"), ("n_bytes", "<u4"), ("n_intra", "<u4"),
+                                   ("n_coded", "<u4")])
+ENTROPY_SIDE_CONTEXTS = 16
+ENTROPY_SIDE_MAX_BYTES = 80
+
+
 class MixedParams(ctypes.Structure):
     """x266_mixed_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
@@ -292,6 +305,11 @@ def load_library(path=None):
     L.xEntropyMvDefaultInit.argtypes = [_P]
     L.xEntropyEncodeMvCtu.argtypes = [ctypes.c_int, ctypes.c_int, _SZ, ctypes.c_uint64, _P, _P, _P, _SZ, _P]
     L.xEntropyDecodeMvCtu.argtypes = [ctypes.c_int, ctypes.c_int, _SZ, _P, _SZ, _P, _P, _P, _P]
+    L.xEntropyEncodeSideGpu.argtypes = [_P, ctypes.POINTER(EntropySideParams), _P]
+    L.xEntropyDecodeSideGpu.argtypes = [_P, ctypes.POINTER(EntropySideParams), _P]
+    L.xEntropySideDefaultInit.argtypes = [_P]
+    L.xEntropyEncodeSideCtu.argtypes = [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _SZ, _P]
+    L.xEntropyDecodeSideCtu.argtypes = [_P, _SZ, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
     L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]

@@ -14,7 +14,8 @@
 // inter partition decision (partition_decide, x266_part_t): tests/cpp/partition_rules_check.cpp, the compact motion stream (motion_pack,
 // motion_unpack, x266_motion_t): tests/cpp/motion_rules_check.cpp, and the entropy coder (entropy_encode, entropy_decode, x266_entropy_t):
 // tests/cpp/entropy_rules_check.cpp, and the entropy coder of the motion stream (entropy_motion_encode, entropy_motion_decode,
-// x266_entropy_motion_t; motion_reconstruct): tests/cpp/entropy_motion_rules_check.cpp.
+// x266_entropy_motion_t; motion_reconstruct): tests/cpp/entropy_motion_rules_check.cpp, and the entropy coder of the side information
+// (entropy_side_encode, entropy_side_decode, x266_entropy_side_t): tests/cpp/entropy_side_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -795,6 +796,51 @@ inline const char *entropy_motion_decode(const x266_entropy_motion_t *p)
     return check(b);
 }
 inline const char *motion_reconstruct(const x266_motion_t *p) { return motion_unpack(p); }
+
+// ---- the entropy coder of the side information -------------------------------------------------------------------------------------------
+// xEntropyEncodeSideGpu, xEntropyDecodeSideGpu: the device pointers are the fields of the host-read x266_entropy_side_t, held by
+// tests/cpp/entropy_side_rules_check.cpp.  `init` is host memory, 16 entries in 31 .. 2017; the stream's extent and the count-only call are
+// the level stream's; the five arrays are optional on both sides, but kinds cannot be coded without their modes.
+constexpr const char *kEntropySideScalars = "qp must be 0..51 and chroma_qp_offset -12..12";
+constexpr const char *kEntropySideModes = "d_kind needs d_mode";
+inline bool entropy_side_init_ok(const uint16_t *init)
+{
+    if (!init) return true;
+    for (unsigned i = 0; i < X266_ENTROPY_SIDE_CONTEXTS; ++i)
+        if (init[i] < 31 || init[i] > 2017) return false;
+    return true;
+}
+inline bool entropy_side_scalars_ok(int qp, int chroma_qp_offset) { return qp >= 0 && qp <= 51 && chroma_qp_offset >= -12 && chroma_qp_offset <= 12; }
+inline const char *entropy_side_encode(const x266_entropy_side_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (!entropy_side_scalars_ok(p->qp, p->chroma_qp_offset)) return kEntropySideScalars;
+    if (!entropy_side_init_ok(p->init)) return kEntropyInit;
+    const size_t n = p->n_ctu;
+    if (n == 0) {
+        const Buf b[] = {out("d_total", p->d_total, 8, 16)};
+        return check(b);
+    }
+    if (p->d_kind && !p->d_mode) return kEntropySideModes;
+    Buf b[] = {out("d_coded", p->d_coded, 8, mul(n, 32)), out("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words)), out("d_total", p->d_total, 8, 16),
+               opt(in("d_kind", p->d_kind, 1, mul(n, 6))), opt(in("d_mode", p->d_mode, 1, mul(n, 6))), opt(in("d_class", p->d_class, 1, mul(n, 6))),
+               opt(in("d_qp", p->d_qp, 1, mul(n, 6))), opt(in("d_nnz", p->d_nnz, 4, mul(n, 24)))};
+    b[1].optional = p->cap_words == 0;
+    return check(b);
+}
+inline const char *entropy_side_decode(const x266_entropy_side_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (!entropy_side_scalars_ok(p->qp, p->chroma_qp_offset)) return kEntropySideScalars;
+    if (!entropy_side_init_ok(p->init)) return kEntropyInit;
+    const size_t n = p->n_ctu;
+    if (n == 0) return nullptr;
+    Buf b[] = {opt(out("d_kind", p->d_kind, 1, mul(n, 6))), opt(out("d_mode", p->d_mode, 1, mul(n, 6))), opt(out("d_class", p->d_class, 1, mul(n, 6))),
+               opt(out("d_qp", p->d_qp, 1, mul(n, 6))), opt(out("d_nnz", p->d_nnz, 4, mul(n, 24))), opt(out("d_status", p->d_status, 1, n)),
+               in("d_coded", p->d_coded, 8, mul(n, 32)), in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words))};
+    b[7].optional = p->cap_words == 0;
+    return check(b);
+}
 
 // ---- intra coding of tiled frames --------------------------------------------------------------------------------------------------
 inline const char *intra32_refs_from_tiles(const void *d_frame, int w, int h, int component, const void *d_refs)

@@ -25,6 +25,7 @@
 #include "x266_device.hpp"
 #include "x266_entropy.hpp"
 #include "x266_entropy_motion.hpp"
+#include "x266_entropy_side.hpp"
 #include "x266_levels.hpp"
 #include "x266_motion.hpp"
 #include "x266_quality.hpp"
@@ -1734,6 +1735,66 @@ int xEntropyDecodeMvCtu(int width, int height, size_t ctu, const uint8_t *bytes,
     }
     *head_mask = r.mask;
     *parts = r.parts;
+    return good ? 0 : 1;
+}
+
+// ---- the entropy coder of the side information (entropy_side_kernels.hip, x266_entropy_side.hpp) ------------------------------------------------
+int xEntropyEncodeSideGpu(x266hip_ctx *ctx, const x266_entropy_side_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_side_encode(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "side entropy encode launch", launch_entropy_side_encode(*p, (hipStream_t)stream));
+}
+
+int xEntropyDecodeSideGpu(x266hip_ctx *ctx, const x266_entropy_side_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_side_decode(p)) return refuse(ctx, __func__, why);
+    if (p->n_ctu == 0) return X266HIP_OK;
+    X_DEV(ctx);
+    return launched(ctx, "side entropy decode launch", launch_entropy_side_decode(*p, (hipStream_t)stream));
+}
+
+// the three host helpers: the functions of x266_entropy_side.hpp that the kernels run, on the host
+int xEntropySideDefaultInit(uint16_t init[X266_ENTROPY_SIDE_CONTEXTS])
+{
+    if (!init) return X266HIP_EINVAL;
+    for (unsigned i = 0; i < kEntropySideContexts; ++i) init[i] = kEntropySideDefault.p[i];
+    return X266HIP_OK;
+}
+
+int xEntropyEncodeSideCtu(const uint8_t *kind, const uint8_t *mode, const uint8_t *cls, const uint8_t *qp_in, const uint32_t *nnz, int qp, int chroma_qp_offset,
+                          const uint16_t *init, uint8_t *out, size_t cap, uint32_t bins[2])
+{
+    if ((kind && !mode) || (!out && cap) || !args::entropy_side_scalars_ok(qp, chroma_qp_offset) || !args::entropy_side_init_ok(init)) return X266HIP_EINVAL;
+    uint16_t c[kEntropySideContexts];
+    for (unsigned i = 0; i < kEntropySideContexts; ++i) c[i] = (init ? init : kEntropySideDefault.p)[i];
+    const EntropySideCtu s = entropy_side_canon(kind, mode, cls, qp_in, nnz, qp, chroma_qp_offset);
+    EntropyEnc e;
+    entropy_enc_start(e, out, cap > kEntropySideMaxBytes ? kEntropySideMaxBytes : (uint32_t)cap);
+    entropy_side_encode_ctu(e, s, c, 1u, qp, chroma_qp_offset);
+    const uint32_t n_bytes = entropy_enc_finish(e);
+    if (bins) {
+        bins[0] = e.ctx_bins;
+        bins[1] = e.bypass_bins;
+    }
+    return (int)n_bytes;
+}
+
+int xEntropyDecodeSideCtu(const uint8_t *bytes, size_t n_bytes, int qp, int chroma_qp_offset, const uint16_t *init, uint8_t *kind, uint8_t *mode, uint8_t *cls,
+                          uint8_t *qp_out, uint32_t *nnz)
+{
+    if ((!bytes && n_bytes) || n_bytes > kEntropySideMaxBytes || !args::entropy_side_scalars_ok(qp, chroma_qp_offset) || !args::entropy_side_init_ok(init))
+        return X266HIP_EINVAL;
+    uint16_t c[kEntropySideContexts];
+    for (unsigned i = 0; i < kEntropySideContexts; ++i) c[i] = (init ? init : kEntropySideDefault.p)[i];
+    EntropyDec d;
+    entropy_dec_start(d, bytes, (uint32_t)n_bytes);
+    EntropySideCtu s;
+    const bool good = entropy_side_decode_ctu(d, c, 1u, qp, chroma_qp_offset, &s);
+    if (!good) s = entropy_side_flat_ctu(qp, chroma_qp_offset);
+    entropy_side_store(s, kind, mode, cls, qp_out, nnz);
     return good ? 0 : 1;
 }
 

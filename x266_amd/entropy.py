@@ -1,13 +1,15 @@
 """The entropy coder of the level stream (include/x266hip.h: xEntropyEncodeLevelsGpu, xEntropyDecodeLevelsGpu): the numpy calls around
 Codec.entropy_encode_levels_dev and Codec.entropy_decode_levels_dev, built from the pieces the Codec's own numpy methods are built from,
 and the three host helpers of the library (xEntropyDefaultInit, xEntropyEncodeRegion, xEntropyDecodeRegion); below them the same for the
-motion stream (xEntropyEncodeMvGpu, xEntropyDecodeMvGpu and their three helpers).  No arithmetic lives here."""
+motion stream (xEntropyEncodeMvGpu, xEntropyDecodeMvGpu and their three helpers) and for the side information (xEntropyEncodeSideGpu,
+xEntropyDecodeSideGpu and their three helpers).  No arithmetic lives here."""
 import ctypes
 
 import numpy as np
 
 from ._lib import (ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES, ENTROPY_MOTION_CONTEXTS, ENTROPY_MOTION_CTU_DTYPE, ENTROPY_MOTION_MAX_BYTES, ENTROPY_REGION_DTYPE,
-                   MOTION_CTU_DTYPE, Codec, EntropyMotionParams, EntropyParams, X266Error, _NULL, load_library)
+                   ENTROPY_SIDE_CONTEXTS, ENTROPY_SIDE_CTU_DTYPE, ENTROPY_SIDE_MAX_BYTES, MOTION_CTU_DTYPE, Codec, EntropyMotionParams, EntropyParams,
+                   EntropySideParams, X266Error, _NULL, load_library)
 
 
 def _init_table(init):
@@ -193,3 +195,106 @@ def entropy_decode_motion_ctu(w, h, ctu, data, init=None):
     if rc < 0:
         raise X266Error("xEntropyDecodeMvCtu: a bad argument")
     return int(mask[0]), words[:4 * int(parts[0])].copy(), rc == 1
+
+
+# ---- the side information (xEntropyEncodeSideGpu, xEntropyDecodeSideGpu) ------------------------------------------------------------------
+SIDE_ARRAYS = (("d_kind", np.uint8), ("d_mode", np.uint8), ("d_class", np.uint8), ("d_qp", np.uint8), ("d_nnz", np.uint32))
+
+
+def _side_table(init):
+    if init is None:
+        return None
+    table = np.ascontiguousarray(init, np.uint16).ravel()
+    if table.size != ENTROPY_SIDE_CONTEXTS:
+        raise X266Error("init must hold %d entries" % ENTROPY_SIDE_CONTEXTS)
+    return table
+
+
+def entropy_side_params(**fields):
+    """an x266_entropy_side_t by field name: device addresses (absent or 0: NULL) and the HOST address `init`, then n_ctu, cap_words, qp and
+    chroma_qp_offset"""
+    scalars = [fields.pop("n_ctu", 0), fields.pop("cap_words", 0), fields.pop("qp", 0), fields.pop("chroma_qp_offset", 0)]
+    return Codec._keyword_params(EntropySideParams, "entropy_side_params", fields, scalars)
+
+
+def entropy_encode_side_dev(codec, params, stream=0):
+    codec._check(codec.L.xEntropyEncodeSideGpu(codec.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyEncodeSideGpu")
+
+
+def entropy_decode_side_dev(codec, params, stream=0):
+    codec._check(codec.L.xEntropyDecodeSideGpu(codec.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyDecodeSideGpu")
+
+
+def entropy_encode_side(codec, n_ctu, kind=None, mode=None, classes=None, qps=None, nnz=None, qp=32, chroma_qp_offset=0, cap_words=None, init=None):
+    """numpy convenience around xEntropyEncodeSideGpu: [6 n_ctu] entries of each array (None: NULL; init: 16 uint16 or None) -> (coded [n_ctu]
+    of ENTROPY_SIDE_CTU_DTYPE, stream uint16 [cap_words], total uint64 [2]).  cap_words None: a count-only call sizes the stream exactly; words
+    the call does not write are 0."""
+    n_ctu = int(n_ctu)
+    table = _side_table(init)
+    held = {name: codec._table(a, dtype, 6 * n_ctu) for (name, dtype), a in zip(SIDE_ARRAYS, (kind, mode, classes, qps, nnz))}
+    d_coded, d_tot = codec.alloc(max(32 * n_ctu, 16)), codec.alloc(16)
+    p = entropy_side_params(d_coded=d_coded.ptr, d_total=d_tot.ptr, init=table.ctypes.data if table is not None else 0, n_ctu=n_ctu, qp=qp,
+                            chroma_qp_offset=chroma_qp_offset, **{name: d.ptr for name, d in held.items()})
+    if cap_words is None:
+        entropy_encode_side_dev(codec, p)
+        cap_words = codec._fetch((d_tot, np.uint64, (2,)))[0]
+    cap_words = int(cap_words)
+    d_str = codec._upload(np.zeros(cap_words, np.uint16)) if cap_words else _NULL
+    p.d_stream, p.cap_words = d_str.ptr or None, cap_words
+    entropy_encode_side_dev(codec, p)
+    return codec._fetch((d_coded, ENTROPY_SIDE_CTU_DTYPE, (n_ctu,)), (d_str, np.uint16, (cap_words,)), (d_tot, np.uint64, (2,)))
+
+
+def entropy_decode_side(codec, coded, stream, qp=32, chroma_qp_offset=0, init=None):
+    """numpy convenience around xEntropyDecodeSideGpu: the coded records (ENTROPY_SIDE_CTU_DTYPE) and the stream's words -> (kind, mode,
+    class, qp uint8 [6 n_ctu], nnz uint32 [6 n_ctu], status uint8 [n_ctu])"""
+    rec = np.ascontiguousarray(coded, ENTROPY_SIDE_CTU_DTYPE).ravel()
+    n_ctu = rec.size
+    src = np.ascontiguousarray(stream, np.uint16).ravel()
+    table = _side_table(init)
+    d_coded = codec._upload(rec)
+    d_str = codec._upload(src) if src.size else _NULL
+    held = {name: codec.alloc(max(6 * n_ctu * np.dtype(dtype).itemsize, 16)) for name, dtype in SIDE_ARRAYS}
+    d_status = codec.alloc(max(n_ctu, 16))
+    entropy_decode_side_dev(codec, entropy_side_params(d_coded=d_coded.ptr, d_stream=d_str.ptr, d_status=d_status.ptr, init=table.ctypes.data if table is not None else 0,
+                                                       n_ctu=n_ctu, cap_words=src.size, qp=qp, chroma_qp_offset=chroma_qp_offset,
+                                                       **{name: d.ptr for name, d in held.items()}))
+    return codec._fetch(*([(held[name], dtype, (6 * n_ctu,)) for name, dtype in SIDE_ARRAYS] + [(d_status, np.uint8, (n_ctu,))]))
+
+
+def entropy_side_default_init():
+    """xEntropySideDefaultInit: the default table, 16 uint16"""
+    table = np.zeros(ENTROPY_SIDE_CONTEXTS, np.uint16)
+    if load_library().xEntropySideDefaultInit(table.ctypes.data) != 0:
+        raise X266Error("xEntropySideDefaultInit failed")
+    return table
+
+
+def entropy_encode_side_ctu(kind=None, mode=None, classes=None, qps=None, nnz=None, qp=32, chroma_qp_offset=0, init=None, cap=ENTROPY_SIDE_MAX_BYTES):
+    """xEntropyEncodeSideCtu: six entries of each array (None: NULL) -> (the substream's first min(n_bytes, cap) bytes, n_bytes, context bins,
+    bypass bins)"""
+    held = []
+    for (name, dtype), a in zip(SIDE_ARRAYS, (kind, mode, classes, qps, nnz)):
+        held.append(None if a is None else np.ascontiguousarray(a, dtype).ravel())
+        if held[-1] is not None and held[-1].size != 6:
+            raise X266Error("%s: a CTU is six regions" % name)
+    table = _side_table(init)
+    out, bins = np.zeros(max(int(cap), 1), np.uint8), np.zeros(2, np.uint32)
+    n = load_library().xEntropyEncodeSideCtu(*([a.ctypes.data if a is not None else None for a in held] +
+                                               [int(qp), int(chroma_qp_offset), table.ctypes.data if table is not None else None, out.ctypes.data if cap else None,
+                                                int(cap), bins.ctypes.data]))
+    if n < 0:
+        raise X266Error("xEntropyEncodeSideCtu: a bad argument")
+    return out[:min(n, int(cap))].tobytes(), n, int(bins[0]), int(bins[1])
+
+
+def entropy_decode_side_ctu(data, qp=32, chroma_qp_offset=0, init=None):
+    """xEntropyDecodeSideCtu: (kind, mode, class, qp uint8 [6], nnz uint32 [6], malformed)"""
+    raw = np.frombuffer(bytes(data), np.uint8)
+    table = _side_table(init)
+    got = [np.zeros(6, dtype) for _, dtype in SIDE_ARRAYS]
+    rc = load_library().xEntropyDecodeSideCtu(raw.ctypes.data if raw.size else None, raw.size, int(qp), int(chroma_qp_offset),
+                                              table.ctypes.data if table is not None else None, *[a.ctypes.data for a in got])
+    if rc < 0:
+        raise X266Error("xEntropyDecodeSideCtu: a bad argument")
+    return tuple(got) + (rc == 1,)
