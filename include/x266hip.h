@@ -1674,8 +1674,7 @@ int xMotionVectorBits(int d);
  * d_stream with cap_words != 0, an entry of init outside 31 .. 2017, a span that does not fit in the address space, an output
  * overlapping any other buffer.  The extents are the compact level stream's, with n_regions * 32 for d_region.  With n_regions == 0
  * only d_total of the encode call is looked at.
- * Out of scope, the follow-ups: per-frame context statistics coming
- * back from the device; context carry-over between regions, WPP-style rows included; sign hiding and dependent quantisation; splitting
+ * Out of scope, the follow-ups (per-frame context statistics are xEntropyStatsLevelsGpu's, below): context carry-over between regions, WPP-style rows included; sign hiding and dependent quantisation; splitting
  * a region's blocks over lanes as separate coders (a format question: separate coders are separate substreams); any real VVC or HEVC
  * bit-stream syntax.  Class bytes, intra modes, kinds and qp are not in this substream: the motion stream is xEntropyEncodeMvGpu's and the
  * side information xEntropyEncodeSideGpu's (both below).  A "bitrate" from these two calls is the residual's alone; the three coders
@@ -1948,7 +1947,8 @@ int xEntropyDecodeMvCtu(int width, int height, size_t ctu, const uint8_t *bytes,
  * cap_words * 2 for d_stream, 16 for d_total, one byte per CTU for d_status.  With n_ctu == 0 only the scalars, init and d_total of
  * the encode call are looked at.
  * Out of scope: direction bytes of B-frames; SAO and ALF parameters; a frame header or any container around the three streams; context
- * carry-over between CTUs; deriving class_bits of the transform decision from a table; adapted tables coming back from the device. */
+ * carry-over between CTUs; deriving class_bits of the transform decision from a table.  (No longer out of scope: adapted tables, a
+ * frame's own through xEntropyStatsSideGpu and xEntropyInitFromCounts, below.) */
 #define X266_ENTROPY_SIDE_CONTEXTS  16
 #define X266_ENTROPY_SIDE_MAX_BYTES 80
 typedef struct x266_entropy_side_ctu_t {   /* 32 bytes; the first 20 bytes are laid out as x266_level_region_t's */
@@ -1989,6 +1989,91 @@ int xEntropyEncodeSideCtu(const uint8_t *kind, const uint8_t *mode, const uint8_
                           int chroma_qp_offset, const uint16_t *init, uint8_t *out, size_t cap, uint32_t bins[2]);
 int xEntropyDecodeSideCtu(const uint8_t *bytes, size_t n_bytes, int qp, int chroma_qp_offset, const uint16_t *init, uint8_t *kind, uint8_t *mode,
                           uint8_t *cls, uint8_t *qp_out, uint32_t *nnz);
+
+/* ---- per-context bin statistics on the device, and initial tables from them ----
+ * The level and the side coder start every substream from a static table.  These calls count, per context, the zero and the one bins
+ * that a frame's arrays put into that context, and turn the counts into an initial table.  Which context a bin goes to and whether it is
+ * 0 or 1 depends on the coded arrays alone -- not on the table, the coder's state or the order of the bins -- so the counts need no
+ * coder.  The calls read exactly what the encoders read, which is exactly what the decoders write: a decoder that runs them on frame
+ * N's decoded arrays derives the table the encoder derived from the same arrays, and both code frame N + 1 under it.  Backward
+ * adaptation per frame: no table crosses the wire and every substream stays independent.
+ *
+ * Counts.  An array of 2 * n_contexts counters: counts[2 c] the zero bins of context c, counts[2 c + 1] its one bins, c in the order of
+ * the coder's table (X266_ENTROPY_CONTEXTS = 100 for levels, size 4 first; X266_ENTROPY_SIDE_CONTEXTS = 16 for side information).
+ * Bypass bins are not counted.
+ *
+ * xEntropyInitFromCounts: for context c with z = counts[2 c], o = counts[2 c + 1] and n = z + o, in unsigned 64-bit integers,
+ *     n == 0:    init[c] = 1024
+ *     otherwise: init[c] = (4096 z + n) / (2 n)   (integer division: 2048 z / n rounded half up), then held to 31 .. 2017.
+ * It returns 0, or X266HIP_EINVAL -- nothing written -- for a NULL counts or init with n_contexts != 0 or any z or o of 2^51 or more
+ * (4096 z + n stays below 2^64).  n_contexts is the caller's: 100, 16 or any other.
+ *
+ * xEntropyCountRegion ADDS to counts[200] the context bins of one region: the walk of the level coder's syntax (above) over the 1024
+ * levels under class `cls` (only cls & 3 counts) with a sink that counts instead of coding -- the one copy of the syntax, not a second.
+ * coded == 0 is the encoder's d_nnz[r] == 0 case: the region's 64 >> 2 k blocks (k = cls & 3) each give one zero cbf bin of size k and
+ * level is not read (it may be NULL).  X266HIP_EINVAL for a NULL counts, or a NULL level with coded != 0.
+ * xEntropyCountSideCtu ADDS to counts[32] the context bins of one CTU from six entries of each array, with the NULL conventions and the
+ * canonical form of xEntropyEncodeSideCtu; X266HIP_EINVAL for kind without mode, a NULL counts, a qp or chroma_qp_offset out of range.
+ * For both, the sum of what a call adds equals bins[0] of the matching encode helper under any table.  These two are the definition
+ * the device calls are held against.
+ *
+ * xEntropyStatsLevelsGpu reads d_level, d_class (or NULL: every region 32x32) and d_nnz (or NULL) exactly as xEntropyEncodeLevelsGpu
+ * does, a region with d_nnz[r] == 0 counting as all zero with its levels not read, and writes
+ *     d_counts   uint64[2 * X266_ENTROPY_CONTEXTS]: the sum of xEntropyCountRegion over the n_regions regions, for every input.  Hence
+ *                the sum over d_counts equals the sum of ctx_bins over the records of xEntropyEncodeLevelsGpu on the same arrays.
+ *     d_part     uint32[xEntropyStatsRows(n_regions, X266_ENTROPY_STATS_REGIONS)][2 * X266_ENTROPY_CONTEXTS]: row j holds the counts of
+ *                the regions [j * X266_ENTROPY_STATS_REGIONS, (j + 1) * X266_ENTROPY_STATS_REGIONS) that exist.  It is contract, not
+ *                scratch: a host forms per-slice tables from its rows.  A region has at most 3456 context bins, a row at most
+ *                32 * 3456 = 110 592: no counter of a row can pass 32 bits.
+ * xEntropyStatsSideGpu reads the five arrays, qp and chroma_qp_offset as xEntropyEncodeSideGpu does (same NULL conventions, the
+ * canonical form is what is counted, so the counts of any arrays equal the counts of their decoded form) and writes d_counts
+ * uint64[2 * X266_ENTROPY_SIDE_CONTEXTS], the sum of xEntropyCountSideCtu over the n_ctu CTUs, and d_part
+ * uint32[xEntropyStatsRows(n_ctu, X266_ENTROPY_SIDE_STATS_CTUS)][2 * X266_ENTROPY_SIDE_CONTEXTS], row j the CTUs [64 j, 64 j + 64); a
+ * CTU has at most 64 context bins (11 for each of Y0..Y3 and U, 9 for V).
+ * xEntropyStatsRows(n_units, per_row) = ceil(n_units / per_row), 0 for per_row == 0.
+ * Both calls: two launches on the caller's stream -- the rows, then one workgroup that adds the rows in ascending order --, no global
+ * atomics, no allocation, no host synchronisation; they can be captured into a graph; the same input gives the same bytes on every run.
+ * They read no launch option.  n == 0 writes the zeros of d_counts and nothing else (d_part and the inputs are not looked at).
+ * The level kernel is a data-parallel statement of the syntax, not the coder's serial walk: one wave per region at a time, lane g = CG
+ * bit g, the scan-ordered significance, |l| > 1 and |l| > 2 maps of its 16 levels, and every count from ballots and popcounts.  The side
+ * kernel takes one lane per CTU and runs the syntax's own walk with the counting sink.
+ *
+ * X266HIP_EINVAL, with nothing launched and the call named in xHipLastError: a NULL p, a NULL or misaligned d_counts (8 bytes), and
+ * with n != 0 a NULL or misaligned d_part (16), d_level (16) or d_nnz (4, if given), d_kind without d_mode, qp outside 0..51 or
+ * chroma_qp_offset outside -12..12 (side call, also with n == 0), a span that does not fit in the address space, an output overlapping
+ * any other buffer.  Extents: d_counts 1600 (levels) or 256 (side) bytes, d_part rows * 800 or rows * 128 bytes, the inputs as on the
+ * encode calls.
+ * Left out on purpose, a follow-up if it ever pays: the motion coder.  Its contexts number 7, its stream is 3 473 of the measured frame's
+ * 424 933 bytes, and 1 947 of 2 040 CTUs cost no byte.  Neither call changes a default table. */
+#define X266_ENTROPY_STATS_REGIONS   32
+#define X266_ENTROPY_SIDE_STATS_CTUS 64
+typedef struct x266_entropy_stats_t {
+    const int16_t  *d_level;           /* [n_regions * 1024], 16-byte aligned                                          */
+    const uint8_t  *d_class;           /* [n_regions] or NULL (every region 32x32), any alignment                      */
+    const uint32_t *d_nnz;             /* [n_regions] or NULL, 4-byte aligned                                          */
+    uint64_t *d_counts;                /* [2 * X266_ENTROPY_CONTEXTS], 8-byte aligned                                  */
+    uint32_t *d_part;                  /* [rows][2 * X266_ENTROPY_CONTEXTS], 16-byte aligned                           */
+    size_t    n_regions;
+} x266_entropy_stats_t;
+typedef struct x266_entropy_side_stats_t {
+    const uint8_t  *d_kind;            /* [6 n_ctu] or NULL, any alignment                                             */
+    const uint8_t  *d_mode;            /* [6 n_ctu] or NULL, any alignment                                             */
+    const uint8_t  *d_class;           /* [6 n_ctu] or NULL, any alignment                                             */
+    const uint8_t  *d_qp;              /* [6 n_ctu] or NULL, any alignment                                             */
+    const uint32_t *d_nnz;             /* [6 n_ctu] or NULL, 4-byte aligned                                            */
+    uint64_t *d_counts;                /* [2 * X266_ENTROPY_SIDE_CONTEXTS], 8-byte aligned                             */
+    uint32_t *d_part;                  /* [rows][2 * X266_ENTROPY_SIDE_CONTEXTS], 16-byte aligned                      */
+    size_t    n_ctu;
+    int       qp;                      /* 0..51, the frame's                                                           */
+    int       chroma_qp_offset;        /* -12..12                                                                      */
+} x266_entropy_side_stats_t;
+int xEntropyStatsLevelsGpu(x266hip_ctx *ctx, const x266_entropy_stats_t *p, void *stream);
+int xEntropyStatsSideGpu(x266hip_ctx *ctx, const x266_entropy_side_stats_t *p, void *stream);
+size_t xEntropyStatsRows(size_t n_units, size_t per_row);
+int xEntropyInitFromCounts(const uint64_t *counts, size_t n_contexts, uint16_t *init);
+int xEntropyCountRegion(const int16_t *level, int cls, int coded, uint64_t counts[2 * X266_ENTROPY_CONTEXTS]);
+int xEntropyCountSideCtu(const uint8_t *kind, const uint8_t *mode, const uint8_t *cls, const uint8_t *qp_in, const uint32_t *nnz, int qp,
+                         int chroma_qp_offset, uint64_t counts[2 * X266_ENTROPY_SIDE_CONTEXTS]);
 
 /* ---- frame quality: SSE, PSNR and SSIM of a decoded tiled frame against its source, per CTU and per frame ----
  * The instrument behind every statement about RDOQ, the transform decision and the loop filters: the distortion between a source

@@ -13,7 +13,8 @@ from ._lib import (X266Error, Codec, lib_path, load_library, build_library,  # n
                    LaParams, LA_BLOCK_DTYPE, la_totals_chunk, scene_cut_from_totals, SeedParams, MixedParams, PartParams, PART_CTU_DTYPE,
                    MotionParams, MOTION_CTU_DTYPE, EntropyParams, ENTROPY_REGION_DTYPE, ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES,
                    EntropyMotionParams, ENTROPY_MOTION_CTU_DTYPE, ENTROPY_MOTION_CONTEXTS, ENTROPY_MOTION_MAX_BYTES,
-                   EntropySideParams, ENTROPY_SIDE_CTU_DTYPE, ENTROPY_SIDE_CONTEXTS, ENTROPY_SIDE_MAX_BYTES)
+                   EntropySideParams, ENTROPY_SIDE_CTU_DTYPE, ENTROPY_SIDE_CONTEXTS, ENTROPY_SIDE_MAX_BYTES,
+                   EntropyStatsParams, EntropySideStatsParams, ENTROPY_STATS_REGIONS, ENTROPY_SIDE_STATS_CTUS)
 
 __all__ = ["X266Error", "Codec", "lib_path", "load_library", "build_library",
            "pack_diff_rows", "pack_dct_word", "LevelsParams", "LEVEL_REGION_DTYPE", "level_scan", "levels_scan_chunk",
@@ -22,4 +23,5 @@ __all__ = ["X266Error", "Codec", "lib_path", "load_library", "build_library",
            "LaParams", "LA_BLOCK_DTYPE", "la_totals_chunk", "scene_cut_from_totals", "SeedParams", "MixedParams", "PartParams", "PART_CTU_DTYPE",
            "MotionParams", "MOTION_CTU_DTYPE", "EntropyParams", "ENTROPY_REGION_DTYPE", "ENTROPY_CONTEXTS", "ENTROPY_MAX_BYTES",
            "EntropyMotionParams", "ENTROPY_MOTION_CTU_DTYPE", "ENTROPY_MOTION_CONTEXTS", "ENTROPY_MOTION_MAX_BYTES",
-           "EntropySideParams", "ENTROPY_SIDE_CTU_DTYPE", "ENTROPY_SIDE_CONTEXTS", "ENTROPY_SIDE_MAX_BYTES"]
+           "EntropySideParams", "ENTROPY_SIDE_CTU_DTYPE", "ENTROPY_SIDE_CONTEXTS", "ENTROPY_SIDE_MAX_BYTES",
+           "EntropyStatsParams", "EntropySideStatsParams", "ENTROPY_STATS_REGIONS", "ENTROPY_SIDE_STATS_CTUS"]

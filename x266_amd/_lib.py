@@ -153,6 +153,22 @@ ENTROPY_SIDE_CONTEXTS = 16
 ENTROPY_SIDE_MAX_BYTES = 80
 
 
+class EntropyStatsParams(ctypes.Structure):
+    """x266_entropy_stats_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_level", "d_class", "d_nnz", "d_counts", "d_part")] + [("n_regions", ctypes.c_size_t)]
+
+
+class EntropySideStatsParams(ctypes.Structure):
+    """x266_entropy_side_stats_t of include/x266hip.h"""
+    _fields_ = [(name, _P) for name in ("d_kind", "d_mode", "d_class", "d_qp", "d_nnz", "d_counts", "d_part")] + \
+               [("n_ctu", ctypes.c_size_t), ("qp", ctypes.c_int), ("chroma_qp_offset", ctypes.c_int)]
+
+
+# X266_ENTROPY_STATS_REGIONS and X266_ENTROPY_SIDE_STATS_CTUS of include/x266hip.h: the regions and the CTUs of a row of d_part
+ENTROPY_STATS_REGIONS = 32
+ENTROPY_SIDE_STATS_CTUS = 64
+
+
 class MixedParams(ctypes.Structure):
     """x266_mixed_t of include/x266hip.h"""
     _fields_ = [(name, _P) for name in ("d_cur", "d_pred", "d_qp", "d_kind_in", "d_mode_in", "d_level", "d_nnz", "d_kind", "d_mode", "d_cost", "d_recon")] + \
@@ -310,6 +326,13 @@ def load_library(path=None):
     L.xEntropySideDefaultInit.argtypes = [_P]
     L.xEntropyEncodeSideCtu.argtypes = [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _SZ, _P]
     L.xEntropyDecodeSideCtu.argtypes = [_P, _SZ, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P]
+    L.xEntropyStatsLevelsGpu.argtypes = [_P, ctypes.POINTER(EntropyStatsParams), _P]
+    L.xEntropyStatsSideGpu.argtypes = [_P, ctypes.POINTER(EntropySideStatsParams), _P]
+    L.xEntropyStatsRows.argtypes = [_SZ, _SZ]
+    L.xEntropyStatsRows.restype = _SZ
+    L.xEntropyInitFromCounts.argtypes = [_P, _SZ, _P]
+    L.xEntropyCountRegion.argtypes = [_P, ctypes.c_int, ctypes.c_int, _P]
+    L.xEntropyCountSideCtu.argtypes = [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P]
     L.xDct32CodeMixedFrameGpu.argtypes = [_P, ctypes.POINTER(MixedParams), _P]
     L.xLaTotalsChunk.argtypes = []
     L.xSceneCutFromTotals.argtypes = [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]

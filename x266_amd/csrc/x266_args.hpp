@@ -15,7 +15,8 @@
 // motion_unpack, x266_motion_t): tests/cpp/motion_rules_check.cpp, and the entropy coder (entropy_encode, entropy_decode, x266_entropy_t):
 // tests/cpp/entropy_rules_check.cpp, and the entropy coder of the motion stream (entropy_motion_encode, entropy_motion_decode,
 // x266_entropy_motion_t; motion_reconstruct): tests/cpp/entropy_motion_rules_check.cpp, and the entropy coder of the side information
-// (entropy_side_encode, entropy_side_decode, x266_entropy_side_t): tests/cpp/entropy_side_rules_check.cpp.
+// (entropy_side_encode, entropy_side_decode, x266_entropy_side_t): tests/cpp/entropy_side_rules_check.cpp, and the bin statistics
+// (entropy_stats_levels, entropy_stats_side, x266_entropy_stats_t, x266_entropy_side_stats_t): tests/cpp/entropy_stats_rules_check.cpp.
 //
 // A call's buffers are declared once (Buf) and walked by one checker: NULL, alignment, "does the span fit in the address
 // space", "does an output overlap anything".  An extent of 0 means that the extent is not part of the call's rules today: the
@@ -839,6 +840,40 @@ inline const char *entropy_side_decode(const x266_entropy_side_t *p)
                opt(out("d_qp", p->d_qp, 1, mul(n, 6))), opt(out("d_nnz", p->d_nnz, 4, mul(n, 24))), opt(out("d_status", p->d_status, 1, n)),
                in("d_coded", p->d_coded, 8, mul(n, 32)), in("d_stream", p->d_stream, 16, levels_stream_bytes(p->cap_words))};
     b[7].optional = p->cap_words == 0;
+    return check(b);
+}
+
+// ---- the per-context bin statistics ----------------------------------------------------------------------------------------------------------
+// xEntropyStatsLevelsGpu, xEntropyStatsSideGpu: the device pointers are the fields of the host-read x266_entropy_stats_t and
+// x266_entropy_side_stats_t, held by tests/cpp/entropy_stats_rules_check.cpp.  The inputs are the encode calls'; d_counts is 16 bytes per
+// context and d_part that per row of X266_ENTROPY_STATS_REGIONS regions or X266_ENTROPY_SIDE_STATS_CTUS CTUs.  With n == 0 only d_counts
+// (and the side call's scalars) are looked at.
+inline size_t entropy_stats_rows(size_t n_units, size_t per_row) { return per_row ? n_units / per_row + (n_units % per_row != 0) : 0; }
+inline const char *entropy_stats_levels(const x266_entropy_stats_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    const size_t n = p->n_regions, counts = 16 * X266_ENTROPY_CONTEXTS;
+    if (n == 0) {
+        const Buf b[] = {out("d_counts", p->d_counts, 8, counts)};
+        return check(b);
+    }
+    const Buf b[] = {out("d_counts", p->d_counts, 8, counts), out("d_part", p->d_part, 16, mul(entropy_stats_rows(n, X266_ENTROPY_STATS_REGIONS), counts / 2)),
+                     in("d_level", p->d_level, 16, mul(n, 2048)), opt(in("d_class", p->d_class, 1, n)), opt(in("d_nnz", p->d_nnz, 4, mul(n, 4)))};
+    return check(b);
+}
+inline const char *entropy_stats_side(const x266_entropy_side_stats_t *p)
+{
+    if (!p) return "NULL parameter struct";
+    if (!entropy_side_scalars_ok(p->qp, p->chroma_qp_offset)) return kEntropySideScalars;
+    const size_t n = p->n_ctu, counts = 16 * X266_ENTROPY_SIDE_CONTEXTS;
+    if (n == 0) {
+        const Buf b[] = {out("d_counts", p->d_counts, 8, counts)};
+        return check(b);
+    }
+    if (p->d_kind && !p->d_mode) return kEntropySideModes;
+    const Buf b[] = {out("d_counts", p->d_counts, 8, counts), out("d_part", p->d_part, 16, mul(entropy_stats_rows(n, X266_ENTROPY_SIDE_STATS_CTUS), counts / 2)),
+                     opt(in("d_kind", p->d_kind, 1, mul(n, 6))), opt(in("d_mode", p->d_mode, 1, mul(n, 6))), opt(in("d_class", p->d_class, 1, mul(n, 6))),
+                     opt(in("d_qp", p->d_qp, 1, mul(n, 6))), opt(in("d_nnz", p->d_nnz, 4, mul(n, 24)))};
     return check(b);
 }
 

@@ -299,6 +299,9 @@ hipError_t launch_entropy_motion_decode(const x266_entropy_motion_t &p, hipStrea
 // the entropy coder of the side information (entropy_side_kernels.hip): the same three launches on x266_entropy_side_ctu_t, one lane per CTU; decode is one launch
 hipError_t launch_entropy_side_encode(const x266_entropy_side_t &p, hipStream_t stream);
 hipError_t launch_entropy_side_decode(const x266_entropy_side_t &p, hipStream_t stream);
+// the per-context bin statistics (entropy_stats_kernels.hip): the rows, then one workgroup adding them in ascending order
+hipError_t launch_entropy_stats_levels(const x266_entropy_stats_t &p, hipStream_t stream);
+hipError_t launch_entropy_stats_side(const x266_entropy_side_stats_t &p, hipStream_t stream);
 hipError_t launch_mem_ceiling(int kind, const void *d_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_fill_residual(int16_t *d_dst, size_t n_samples, uint64_t seed,
                                 uint64_t first_index, const LaunchCfg &cfg, hipStream_t stream);

@@ -3,6 +3,8 @@
 // and xEntropyDefaultInit share.  The statement is include/x266hip.h's (xEntropyEncodeLevelsGpu ...); the scan and the CG origins are
 // x266_levels.hpp's; g of pos() and rem() are restated here from x266_rdoq.hpp so that this file stays plain C++ for the host-only
 // driver (tests/cpp/entropy_rules_check.cpp); tests/test_entropy_ref.py holds the bin counts against xLastPosBits and xLevelBits.
+// The syntax walks are templates over their sink: EntropyEnc codes, EntropyCounter (below) counts the bins per context for the
+// statistics (xEntropyCountRegion, xEntropyStatsSideGpu ...); the table rule of xEntropyInitFromCounts is here as well.
 //
 // What the kernels rely on:
 //   * a probability that starts in 31 .. 2017 stays there: p += (2048 - p) >> 5 stops at 2017, p -= p >> 5 at 31.  With range >= 2^24
@@ -152,8 +154,41 @@ X266_HD inline void entropy_enc_bypass(EntropyEnc &e, unsigned bit)
     ++e.bypass_bins;
 }
 
+// ---- the counting sink ---------------------------------------------------------------------------------------------------------------------
+// What the syntax walks below (entropy_enc_last, entropy_enc_level, entropy_encode_region and the side syntax of x266_entropy_side.hpp) take
+// in place of an EntropyEnc to COUNT the context bins instead of coding them: the walks are templates over their sink, so that the
+// statistics (xEntropyCountRegion, xEntropyCountSideCtu, xEntropyStatsSideGpu) run the one copy of each syntax.  `base` is the address
+// the walk's context 0 has (never read or written through; the side walk is told a stride of 1); context c's zero bins are counted in
+// counts[2 c * PITCH], its one bins in counts[(2 c + 1) * PITCH].  Bypass bins are not counted.
+template <class T, unsigned PITCH>
+struct EntropyCounter {
+    T *counts;
+    const uint16_t *base;
+};
+template <class T, unsigned PITCH>
+X266_HD inline void entropy_enc_bin(EntropyCounter<T, PITCH> &e, uint16_t *ctx, unsigned bit)
+{
+    const unsigned c = (unsigned)(ctx - e.base);
+    e.counts[(2u * c + (bit ? 1u : 0u)) * PITCH] += 1;
+}
+template <class T, unsigned PITCH>
+X266_HD inline void entropy_enc_bypass(EntropyCounter<T, PITCH> &, unsigned)
+{
+}
+
+// the initial probability of a context that took z zero and o one bins, both below 2^51: 2048 z / (z + o) rounded half up, held to the
+// interval the adaptation never leaves (xEntropyInitFromCounts)
+inline uint16_t entropy_init_from_counts(uint64_t z, uint64_t o)
+{
+    const uint64_t n = z + o;
+    if (n == 0) return 1024;
+    const uint64_t p = (4096u * z + n) / (2u * n);
+    return (uint16_t)(p < kEntropyProbMin ? kEntropyProbMin : p > kEntropyProbMax ? kEntropyProbMax : p);
+}
+
 // the `count` low bits of value, most significant first; any count up to 32 (the level syntax asks for 14 at most, the motion syntax 15)
-X266_HD inline void entropy_enc_bits(EntropyEnc &e, unsigned value, unsigned count)
+template <class Sink>
+X266_HD inline void entropy_enc_bits(Sink &e, unsigned value, unsigned count)
 {
     for (unsigned i = count; i-- > 0;) entropy_enc_bypass(e, (value >> i) & 1u);
 }
@@ -167,7 +202,8 @@ X266_HD inline uint32_t entropy_enc_finish(EntropyEnc &e)
 }
 
 // one coordinate t of the last position of a block of 1 << n: ctx points at the coordinate's nine prefix contexts
-X266_HD inline void entropy_enc_last(EntropyEnc &e, uint16_t *ctx, unsigned t, unsigned n)
+template <class Sink>
+X266_HD inline void entropy_enc_last(Sink &e, uint16_t *ctx, unsigned t, unsigned n)
 {
     const unsigned g = entropy_last_group(t), top = 2u * n - 1u;
     for (unsigned i = 0; i < g; ++i) entropy_enc_bin(e, ctx + i, 1u);
@@ -176,7 +212,8 @@ X266_HD inline void entropy_enc_last(EntropyEnc &e, uint16_t *ctx, unsigned t, u
 }
 
 // a non-zero level l at a position whose significance is already coded
-X266_HD inline void entropy_enc_level(EntropyEnc &e, uint16_t *ctx, int l)
+template <class Sink>
+X266_HD inline void entropy_enc_level(Sink &e, uint16_t *ctx, int l)
 {
     const unsigned a = (unsigned)(l < 0 ? -l : l);
     entropy_enc_bin(e, ctx + kCtxGt1, a > 1u);
@@ -200,7 +237,8 @@ X266_HD inline void entropy_enc_level(EntropyEnc &e, uint16_t *ctx, int l)
 
 // A region: `level` its 1024 levels in the region's own layout, k = class & 3, cg_mask bit g set when CG g has a non-zero level,
 // ctx the 25 contexts of this block size, initialised by the caller.  Only coded CGs are read.
-X266_HD inline void entropy_encode_region(EntropyEnc &e, const int16_t *level, unsigned k, uint64_t cg_mask, uint16_t *ctx)
+template <class Sink>
+X266_HD inline void entropy_encode_region(Sink &e, const int16_t *level, unsigned k, uint64_t cg_mask, uint16_t *ctx)
 {
     const unsigned n = k + 2u, size = 4u << k, per_block = 1u << (2u * k), blocks = 64u >> (2u * k);
     for (unsigned blk = 0; blk < blocks; ++blk) {

@@ -156,7 +156,8 @@ X266_HD inline unsigned side_unrank(uint64_t set, unsigned rank)
 
 // ---- the elements ------------------------------------------------------------------------------------------------------------------------
 // v <= top as truncated unary: v ones, then a zero if v < top.  ctx == nullptr: bypass bins, otherwise bin i has context i
-X266_HD inline void side_enc_unary(EntropyEnc &e, uint16_t *ctx, unsigned stride, unsigned v, unsigned top)
+template <class Sink>
+X266_HD inline void side_enc_unary(Sink &e, uint16_t *ctx, unsigned stride, unsigned v, unsigned top)
 {
     for (unsigned i = 0; i < top; ++i) {
         const unsigned bit = i < v;
@@ -174,7 +175,8 @@ X266_HD inline unsigned side_dec_unary(EntropyDec &d, uint16_t *ctx, unsigned st
 }
 
 // a mode against a list of n entries: the flag, then the index (truncated unary, bypass) or the rank among the other modes (5 bypass bits)
-X266_HD inline void side_enc_mode(EntropyEnc &e, uint16_t *flag, uint64_t list, unsigned n, unsigned m)
+template <class Sink>
+X266_HD inline void side_enc_mode(Sink &e, uint16_t *flag, uint64_t list, unsigned n, unsigned m)
 {
     const unsigned at = side_list_find(list, n, m);
     entropy_enc_bin(e, flag, at < n);
@@ -188,7 +190,8 @@ X266_HD inline unsigned side_dec_mode(EntropyDec &d, uint16_t *flag, uint64_t li
     return side_unrank(side_list_set(list, n), entropy_dec_bits(d, 5u));
 }
 
-X266_HD inline void side_enc_class(EntropyEnc &e, uint16_t *ctx, unsigned stride, unsigned chroma, unsigned c)
+template <class Sink>
+X266_HD inline void side_enc_class(Sink &e, uint16_t *ctx, unsigned stride, unsigned chroma, unsigned c)
 {
     entropy_enc_bin(e, ctx + (kSideCtxSmall + chroma) * stride, c != 3u);
     if (c == 3u) return;
@@ -203,7 +206,8 @@ X266_HD inline unsigned side_dec_class(EntropyDec &d, uint16_t *ctx, unsigned st
 }
 
 // the qp difference dq, |dq| <= 51
-X266_HD inline void side_enc_dqp(EntropyEnc &e, uint16_t *ctx, unsigned stride, unsigned chroma, int dq)
+template <class Sink>
+X266_HD inline void side_enc_dqp(Sink &e, uint16_t *ctx, unsigned stride, unsigned chroma, int dq)
 {
     const unsigned a = (unsigned)(dq < 0 ? -dq : dq);
     entropy_enc_bin(e, ctx + (kSideCtxNz + chroma) * stride, a != 0u);
@@ -236,7 +240,8 @@ X266_HD inline bool side_dec_dqp(EntropyDec &d, uint16_t *ctx, unsigned stride, 
 
 // ---- a CTU -------------------------------------------------------------------------------------------------------------------------------
 // s: canonical (entropy_side_canon or a decoder's output); ctx: the 16 contexts at ctx[i * stride], initialised by the caller
-X266_HD inline void entropy_side_encode_ctu(EntropyEnc &e, const EntropySideCtu &s, uint16_t *ctx, unsigned stride, int qp, int chroma_qp_offset)
+template <class Sink>
+X266_HD inline void entropy_side_encode_ctu(Sink &e, const EntropySideCtu &s, uint16_t *ctx, unsigned stride, int qp, int chroma_qp_offset)
 {
     unsigned cur = (unsigned)qp, u = 0;
     for (unsigned q = 0; q < kSideRegions; ++q) {

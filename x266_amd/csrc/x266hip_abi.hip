@@ -1798,6 +1798,56 @@ int xEntropyDecodeSideCtu(const uint8_t *bytes, size_t n_bytes, int qp, int chro
     return good ? 0 : 1;
 }
 
+// ---- the per-context bin statistics (entropy_stats_kernels.hip) and the tables from them -----------------------------------------------------------
+int xEntropyStatsLevelsGpu(x266hip_ctx *ctx, const x266_entropy_stats_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_stats_levels(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "level statistics launch", launch_entropy_stats_levels(*p, (hipStream_t)stream));
+}
+
+int xEntropyStatsSideGpu(x266hip_ctx *ctx, const x266_entropy_side_stats_t *p, void *stream)
+{
+    if (!ctx) return X266HIP_EINVAL;
+    if (const char *why = args::entropy_stats_side(p)) return refuse(ctx, __func__, why);
+    X_DEV(ctx);
+    return launched(ctx, "side statistics launch", launch_entropy_stats_side(*p, (hipStream_t)stream));
+}
+
+size_t xEntropyStatsRows(size_t n_units, size_t per_row) { return args::entropy_stats_rows(n_units, per_row); }
+
+int xEntropyInitFromCounts(const uint64_t *counts, size_t n_contexts, uint16_t *init)
+{
+    if (n_contexts == 0) return X266HIP_OK;
+    if (!counts || !init) return X266HIP_EINVAL;
+    for (size_t c = 0; c < n_contexts; ++c)
+        if ((counts[2 * c] | counts[2 * c + 1]) >> 51) return X266HIP_EINVAL;
+    for (size_t c = 0; c < n_contexts; ++c) init[c] = entropy_init_from_counts(counts[2 * c], counts[2 * c + 1]);
+    return X266HIP_OK;
+}
+
+// the two counting helpers: the walks of x266_entropy.hpp and x266_entropy_side.hpp with the counting sink in place of the coder
+int xEntropyCountRegion(const int16_t *level, int cls, int coded, uint64_t counts[2 * X266_ENTROPY_CONTEXTS])
+{
+    if (!counts || (!level && coded)) return X266HIP_EINVAL;
+    const unsigned k = (unsigned)cls & 3u;
+    uint16_t ctx[kEntropyCtxPerSize] = {};                                  // the walk's addresses; the sink touches no context
+    EntropyCounter<uint64_t, 1> e = {counts + 2u * k * kEntropyCtxPerSize, ctx};
+    entropy_encode_region(e, level, k, coded ? entropy_cg_mask(level, k) : 0ull, ctx);
+    return X266HIP_OK;
+}
+
+int xEntropyCountSideCtu(const uint8_t *kind, const uint8_t *mode, const uint8_t *cls, const uint8_t *qp_in, const uint32_t *nnz, int qp, int chroma_qp_offset,
+                         uint64_t counts[2 * X266_ENTROPY_SIDE_CONTEXTS])
+{
+    if ((kind && !mode) || !counts || !args::entropy_side_scalars_ok(qp, chroma_qp_offset)) return X266HIP_EINVAL;
+    uint16_t ctx[kEntropySideContexts] = {};
+    EntropyCounter<uint64_t, 1> e = {counts, ctx};
+    entropy_side_encode_ctu(e, entropy_side_canon(kind, mode, cls, qp_in, nnz, qp, chroma_qp_offset), ctx, 1u, qp, chroma_qp_offset);
+    return X266HIP_OK;
+}
+
 // ---- host-pointer batch API --------------------------------------------------
 // Chunks of the batch rotate over three staging slots; uploads, kernels and downloads each have a stream of their own
 // and are ordered by the slots' events: H2D(i+1) and D2H(i-1) overlap kernel(i).

@@ -2,14 +2,15 @@
 Codec.entropy_encode_levels_dev and Codec.entropy_decode_levels_dev, built from the pieces the Codec's own numpy methods are built from,
 and the three host helpers of the library (xEntropyDefaultInit, xEntropyEncodeRegion, xEntropyDecodeRegion); below them the same for the
 motion stream (xEntropyEncodeMvGpu, xEntropyDecodeMvGpu and their three helpers) and for the side information (xEntropyEncodeSideGpu,
-xEntropyDecodeSideGpu and their three helpers).  No arithmetic lives here."""
+xEntropyDecodeSideGpu and their three helpers), and at the end the per-context bin statistics (xEntropyStatsLevelsGpu, xEntropyStatsSideGpu,
+xEntropyInitFromCounts and the two counting helpers).  No arithmetic lives here."""
 import ctypes
 
 import numpy as np
 
 from ._lib import (ENTROPY_CONTEXTS, ENTROPY_MAX_BYTES, ENTROPY_MOTION_CONTEXTS, ENTROPY_MOTION_CTU_DTYPE, ENTROPY_MOTION_MAX_BYTES, ENTROPY_REGION_DTYPE,
                    ENTROPY_SIDE_CONTEXTS, ENTROPY_SIDE_CTU_DTYPE, ENTROPY_SIDE_MAX_BYTES, MOTION_CTU_DTYPE, Codec, EntropyMotionParams, EntropyParams,
-                   EntropySideParams, X266Error, _NULL, load_library)
+                   ENTROPY_SIDE_STATS_CTUS, ENTROPY_STATS_REGIONS, EntropySideParams, EntropySideStatsParams, EntropyStatsParams, X266Error, _NULL, load_library)
 
 
 def _init_table(init):
@@ -298,3 +299,95 @@ def entropy_decode_side_ctu(data, qp=32, chroma_qp_offset=0, init=None):
     if rc < 0:
         raise X266Error("xEntropyDecodeSideCtu: a bad argument")
     return tuple(got) + (rc == 1,)
+
+
+# ---- the per-context bin statistics (xEntropyStatsLevelsGpu, xEntropyStatsSideGpu) and the tables from them ---------------------------------
+def entropy_stats_rows(n_units, per_row):
+    """xEntropyStatsRows: the rows of d_part for n_units regions or CTUs"""
+    return int(load_library().xEntropyStatsRows(int(n_units), int(per_row)))
+
+
+def entropy_stats_params(**fields):
+    """an x266_entropy_stats_t by field name: device addresses (absent or 0: NULL), then n_regions"""
+    scalars = [fields.pop("n_regions", 0)]
+    return Codec._keyword_params(EntropyStatsParams, "entropy_stats_params", fields, scalars)
+
+
+def entropy_side_stats_params(**fields):
+    """an x266_entropy_side_stats_t by field name: device addresses (absent or 0: NULL), then n_ctu, qp and chroma_qp_offset"""
+    scalars = [fields.pop("n_ctu", 0), fields.pop("qp", 0), fields.pop("chroma_qp_offset", 0)]
+    return Codec._keyword_params(EntropySideStatsParams, "entropy_side_stats_params", fields, scalars)
+
+
+def entropy_stats_levels_dev(codec, params, stream=0):
+    codec._check(codec.L.xEntropyStatsLevelsGpu(codec.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyStatsLevelsGpu")
+
+
+def entropy_stats_side_dev(codec, params, stream=0):
+    codec._check(codec.L.xEntropyStatsSideGpu(codec.ctx, ctypes.byref(params) if params is not None else None, stream), "xEntropyStatsSideGpu")
+
+
+def entropy_stats_levels(codec, levels, classes=None, nnz=None):
+    """numpy convenience around xEntropyStatsLevelsGpu: [n_regions, 1024] int16 (and a class byte and a non-zero count per region, None:
+    NULL) -> (counts uint64 [100, 2], zero bins then one bins of each context; part uint32 [rows, 100, 2], one row per
+    ENTROPY_STATS_REGIONS regions)"""
+    lv = np.ascontiguousarray(levels, np.int16).reshape(-1, 1024)
+    n = lv.shape[0]
+    rows = entropy_stats_rows(n, ENTROPY_STATS_REGIONS)
+    d_level = codec._upload(lv) if n else _NULL
+    d_class, d_nnz = codec._table(classes, np.uint8, n), codec._table(nnz, np.uint32, n)
+    d_counts, d_part = codec.alloc(16 * ENTROPY_CONTEXTS), codec.alloc(max(8 * ENTROPY_CONTEXTS * rows, 16))
+    entropy_stats_levels_dev(codec, entropy_stats_params(d_level=d_level.ptr, d_class=d_class.ptr, d_nnz=d_nnz.ptr, d_counts=d_counts.ptr, d_part=d_part.ptr,
+                                                         n_regions=n))
+    return codec._fetch((d_counts, np.uint64, (ENTROPY_CONTEXTS, 2)), (d_part, np.uint32, (rows, ENTROPY_CONTEXTS, 2)))
+
+
+def entropy_stats_side(codec, n_ctu, kind=None, mode=None, classes=None, qps=None, nnz=None, qp=32, chroma_qp_offset=0):
+    """numpy convenience around xEntropyStatsSideGpu: [6 n_ctu] entries of each array (None: NULL) -> (counts uint64 [16, 2], part uint32
+    [rows, 16, 2], one row per ENTROPY_SIDE_STATS_CTUS CTUs)"""
+    n_ctu = int(n_ctu)
+    rows = entropy_stats_rows(n_ctu, ENTROPY_SIDE_STATS_CTUS)
+    held = {name: codec._table(a, dtype, 6 * n_ctu) for (name, dtype), a in zip(SIDE_ARRAYS, (kind, mode, classes, qps, nnz))}
+    d_counts, d_part = codec.alloc(16 * ENTROPY_SIDE_CONTEXTS), codec.alloc(max(8 * ENTROPY_SIDE_CONTEXTS * rows, 16))
+    entropy_stats_side_dev(codec, entropy_side_stats_params(d_counts=d_counts.ptr, d_part=d_part.ptr, n_ctu=n_ctu, qp=qp, chroma_qp_offset=chroma_qp_offset,
+                                                            **{name: d.ptr for name, d in held.items()}))
+    return codec._fetch((d_counts, np.uint64, (ENTROPY_SIDE_CONTEXTS, 2)), (d_part, np.uint32, (rows, ENTROPY_SIDE_CONTEXTS, 2)))
+
+
+def entropy_init_from_counts(counts):
+    """xEntropyInitFromCounts: counts [n_contexts, 2] (zero bins, one bins; Python integers below 2^64) -> the table, n_contexts uint16"""
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1, 2))
+    table = np.zeros(c.shape[0], np.uint16)
+    if c.shape[0] and load_library().xEntropyInitFromCounts(c.ctypes.data, c.shape[0], table.ctypes.data) != 0:
+        raise X266Error("xEntropyInitFromCounts: a count of 2^51 or more")
+    return table
+
+
+def entropy_count_region(level, cls=3, coded=True, counts=None):
+    """xEntropyCountRegion: the context bins of one region ADDED to counts (uint64 [100, 2]; None: zeros), which is returned.  coded False:
+    the region counts as all zero and level may be None"""
+    lv = None if level is None else np.ascontiguousarray(level, np.int16).ravel()
+    if lv is not None and lv.size != 1024:
+        raise X266Error("a region is 1024 levels")
+    out = np.zeros((ENTROPY_CONTEXTS, 2), np.uint64) if counts is None else counts
+    if out.dtype != np.uint64 or out.shape != (ENTROPY_CONTEXTS, 2) or not out.flags.c_contiguous:
+        raise X266Error("counts: uint64 [%d, 2]" % ENTROPY_CONTEXTS)
+    if load_library().xEntropyCountRegion(lv.ctypes.data if lv is not None else None, int(cls), int(bool(coded)), out.ctypes.data) != 0:
+        raise X266Error("xEntropyCountRegion: a bad argument")
+    return out
+
+
+def entropy_count_side_ctu(kind=None, mode=None, classes=None, qps=None, nnz=None, qp=32, chroma_qp_offset=0, counts=None):
+    """xEntropyCountSideCtu: the context bins of one CTU (six entries of each array, None: NULL) ADDED to counts (uint64 [16, 2]; None:
+    zeros), which is returned"""
+    held = []
+    for (name, dtype), a in zip(SIDE_ARRAYS, (kind, mode, classes, qps, nnz)):
+        held.append(None if a is None else np.ascontiguousarray(a, dtype).ravel())
+        if held[-1] is not None and held[-1].size != 6:
+            raise X266Error("%s: a CTU is six regions" % name)
+    out = np.zeros((ENTROPY_SIDE_CONTEXTS, 2), np.uint64) if counts is None else counts
+    if out.dtype != np.uint64 or out.shape != (ENTROPY_SIDE_CONTEXTS, 2) or not out.flags.c_contiguous:
+        raise X266Error("counts: uint64 [%d, 2]" % ENTROPY_SIDE_CONTEXTS)
+    if load_library().xEntropyCountSideCtu(*([a.ctypes.data if a is not None else None for a in held] + [int(qp), int(chroma_qp_offset), out.ctypes.data])) != 0:
+        raise X266Error("xEntropyCountSideCtu: a bad argument")
+    return out
